@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the mem_process_seqs() hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one call of mem_process_seqs() (through the C ABI of libmpibwa_amd.so) on one chunk of
 synthetic 2x150 bp paired-end reads, i.e. exactly what mpiBWA's main loop does per chunk
@@ -9,11 +9,19 @@ synthetic 2x150 bp paired-end reads, i.e. exactly what mpiBWA's main loop does p
 torch.distributed.run and the reads are sharded (independent chunks per rank, no data-path collective;
 the only collective is the one-off RCCL broadcast of the index from rank 0, as the north star asks).
 
-The JSON line carries, besides the contract fields,
+A plain run sets up, warms up, times the K steps and prints the JSON line: the contract fields and what the timed steps
+themselves recorded (stage and kernel times, work counts, the seeding kernel's launch time).  --full adds what takes runs of
+its own, after the timed region:
   roofline      — the SMEM seeding kernel: algorithmic bytes (64 B per occ block touched + read + output,
-                  SURVEY.md §8d, counted on the device) / its HIP-event time, against 8 TB/s HBM3E
+                  SURVEY.md §8d, counted on the device by a counting pass) / its HIP-event time, against 8 TB/s HBM3E;
+                  also with one call in flight and with the chip to itself
   cpu_baseline  — the reference's own mem_process_seqs (oracle/_ref/libbwaref.so, compiled from the
-                  reference sources) on a bounded sample of the same reads, on this box's host cores.
+                  reference sources) on a bounded sample of the same reads, on the host's cores, and the
+                  SAM parity of every step against it
+  alt_workloads — the same bench, shortened, on other synthetic references (--alt-legs).
+
+--dump-outputs DIR writes, after the timed steps, the SAM text the last timed step returned for a fixed, seeded sample
+of its reads (float32 byte values, at most 64 MB in all): two builds compared output for output.
 """
 import argparse
 import ctypes as C
@@ -56,7 +64,45 @@ def kernel_sources_sha256(root):
     return h.hexdigest()
 
 
+DUMP_READS = 16384          # --dump-outputs: reads sampled from the last timed step ...
+DUMP_TEXT_BYTES = 15_000_000   # ... and at most this much of their SAM text (60 MB as float32)
+
+
+def copy_batch(b):
+    """Another bseq1_t[] over a byte copy of b's strings, the same as abi.SeqBatch builds from the reads (b must not have been
+    aligned yet: mem_process_seqs rewrites the bases in place)."""
+    from mpibwa_amd import abi
+    nb = abi.SeqBatch.__new__(abi.SeqBatch)
+    nb.libc, nb.n = b.libc, b.n
+    nb._arena = type(b._arena).from_buffer_copy(b._arena)
+    nb._rec = b._rec.copy()
+    shift = np.uint64((C.addressof(nb._arena) - C.addressof(b._arena)) % (1 << 64))
+    for f in ("name", "comment", "seq", "qual"):
+        v = nb._rec[f][:nb.n]
+        v[v != 0] += shift
+    nb.arr = C.cast(nb._rec.ctypes.data, C.POINTER(abi.bseq1_t))
+    return nb
+
+
+def sample_sam(ptrs, seed):
+    """--dump-outputs: the SAM text one step returned for a fixed, seeded sample of its reads (in read order), as float32 byte
+    values, with each read's offset into it and the read's index in the chunk."""
+    pick = np.sort(np.random.default_rng(seed).choice(len(ptrs), size=min(len(ptrs), DUMP_READS), replace=False))
+    texts, total = [], 0
+    for i in pick:
+        t = C.string_at(int(ptrs[i])) if ptrs[i] else b""
+        if total + len(t) > DUMP_TEXT_BYTES:
+            break
+        texts.append(t)
+        total += len(t)
+    off = np.zeros(len(texts) + 1, dtype=np.float64)
+    off[1:] = np.cumsum([len(t) for t in texts])
+    return {"sam_text": np.frombuffer(b"".join(texts), dtype=np.uint8).astype(np.float32), "sam_offsets": off,
+            "read_index": pick[:len(texts)].astype(np.float64)}
+
+
 def main():
+    t_start = time.time()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=24)   # (three rounds of the eight calls in flight: with 12 the start-up and the tail of the timed region weigh too much)
@@ -74,13 +120,17 @@ def main():
     ap.add_argument("--repeat-frac", type=float, default=float(os.environ.get("MPIBWA_BENCH_REPEAT_FRAC", "0.05")),
                     help="share of the synthetic genome covered by planted repeat families (SURVEY §8d config 1: 0.05; real GRCh38 is ~0.5: see README)")
     ap.add_argument("--genome-model", default=os.environ.get("MPIBWA_BENCH_GENOME_MODEL", "grch38like"), choices=["uniform", "grch38like"],
-                    help="grch38like (default since round 4): SURVEY §8d's generator — order-3 Markov base composition, GC 41 %, repeat families of "
-                         "up to 10^4 copies, 0-5 % divergence; uniform: i.i.d. bases + planted repeats of 2-40 copies (the headline workload of rounds 1-3)")
+                    help="grch38like (default since round 4): SURVEY §8d's generator — order-3 Markov base composition, GC 41 %%, repeat families of "
+                         "up to 10^4 copies, 0-5 %% divergence; uniform: i.i.d. bases + planted repeats of 2-40 copies (the headline workload of rounds 1-3)")
     ap.add_argument("--alt-legs", default=os.environ.get("MPIBWA_BENCH_ALT_LEGS", "grch38like:0.5,uniform:0.05"),
-                    help="after the headline (N = 1 only): the same bench, shortened, on these other references (model:repeat_frac,...), each in a "
+                    help="with --full, before the headline (N = 1 only): the same bench, shortened, on these other references (model:repeat_frac,...), each in a "
                          "child process of its own so that the headline line survives whatever happens there; '' = none")
-    ap.add_argument("--quick", action="store_true", help="no one-call-in-flight leg and no counting pass (the alt legs run this way: no roofline figures)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the alt legs, the one-call-in-flight leg, the counting pass and the lone "
+                         "launch of the seeding kernels (roofline), the reference's CPU baseline and the SAM parity check against it")
+    ap.add_argument("--quick", action="store_true", help="with --full: no one-call-in-flight leg and no counting pass (the alt legs run this way: no roofline figures)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the SAM text of a seeded sample of the last timed step's reads to DIR/*.npy")
     ap.add_argument("--check-parity", action="store_true",
                     help="every rank also aligns its chunks with the reference (oracle/_ref) and compares the SAM: `parity_all_ranks` "
                          "(N > 1 runs carry no CPU baseline; for small configurations)")
@@ -110,7 +160,7 @@ def main():
     # process touches the GPU (a child has the whole device, and the headline survives whatever happens there, e.g. a timeout);
     # attached to the line as alt_workloads, not part of `value` ----
     alt_workloads = None
-    if rank == 0 and world == 1 and args.alt_legs and not args.quick:
+    if rank == 0 and world == 1 and args.full and args.alt_legs and not args.quick:
         import subprocess
         alt_workloads = []
         n_fly_legs = max(1, min(args.in_flight, 12))
@@ -118,7 +168,7 @@ def main():
             model, frac = spec.split(":")
             if model == args.genome_model and float(frac) == args.repeat_frac:
                 continue
-            cmd = [sys.executable, os.path.abspath(__file__), "--quick", "--alt-legs", "", "--genome-model", model, "--repeat-frac", frac, "--chunks", "2",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--quick", "--alt-legs", "", "--genome-model", model, "--repeat-frac", frac, "--chunks", "2",
                    "--steps", "8", "--warmup", "2", "--in-flight", str(n_fly_legs), "--cpu-sample-pairs", "30000", "--genome-mbp", str(args.genome_mbp),
                    "--pairs", str(args.pairs), "--read-len", str(args.read_len), "--workdir", args.workdir]
             t_leg = time.perf_counter()
@@ -148,35 +198,58 @@ def main():
     if world > 1:
         dist.barrier()
     lib = api.load_library(build_if_missing=False)
+    lib.mi355x_collect_sam_into.restype = C.c_size_t
+    lib.mi355x_collect_sam_into.argtypes = [C.POINTER(abi.bseq1_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+
+    # ---- reads: seeded per rank and chunk, same generator as the tests (2 % unmappable, 1 % subst., 0.1 % indel) ----
+    # Config 1 is 1 M pairs: `--chunks` distinct chunks of `--pairs` pairs; step s aligns chunk s mod n_chunks, so the
+    # arenas, branch histories and cached index blocks of consecutive steps differ as they do in a real run.  They are
+    # simulated and batched in a thread of their own as soon as the genome is at hand, while the index is built and uploaded.
+    import threading
+    n_chunks = max(1, args.chunks)
+    n_fly = max(1, min(args.in_flight, 12))
+    inputs = {}
+
+    def make_inputs(genome):
+        try:
+            t1 = time.time()
+            chunk_reads = [genome.simulate_pairs(args.pairs, seed=args.seed + 16 * rank + c, read_len=args.read_len, frag_mean=max(400.0, 2.2 * args.read_len))
+                           for c in range(n_chunks)]
+            # every caller thread owns a bseq1_t[] (and its .sam) per chunk: one built from the reads, the others byte copies of it
+            first = [abi.SeqBatch(api.libc, chunk_reads[c]) for c in range(n_chunks)]
+            inputs.update(chunk_reads=chunk_reads, batches=[first] + [[copy_batch(b) for b in first] for _ in range(n_fly - 1)],
+                          seconds=time.time() - t1)
+        except Exception as e:
+            inputs["error"] = e
+
+    maker = []
+
+    def on_genome(genome):
+        maker.append(threading.Thread(target=make_inputs, args=(genome,)))
+        maker[0].start()
 
     # ---- reference genome + index: built once by rank 0 on its GPU, broadcast over RCCL/xGMI ----
     os.makedirs(args.workdir, exist_ok=True)
     t0 = time.time()
     idx = bigindex.make_or_get(args.workdir, genome_mbp=args.genome_mbp, seed=38, rank=rank, world=world,
                                local_rank=dev, dist=dist if world > 1 else None, log=log if rank == 0 else None,
-                               repeat_frac=args.repeat_frac, model=args.genome_model)
+                               repeat_frac=args.repeat_frac, model=args.genome_model, on_genome=on_genome)
     eng = idx.engine
     if rank == 0:
         log("index ready in %.1f s: l_pac=%d, occ blocks %.2f GB, SA %.2f GB" %
             (time.time() - t0, idx.l_pac, idx.blk_bytes / 1e9, idx.sa_bytes / 1e9))
-
-    # ---- reads: seeded per rank and chunk, same generator as the tests (2 % unmappable, 1 % subst., 0.1 % indel) ----
-    # Config 1 is 1 M pairs: `--chunks` distinct chunks of `--pairs` pairs; step s aligns chunk s mod n_chunks, so the
-    # arenas, branch histories and cached index blocks of consecutive steps differ as they do in a real run.
-    n_chunks = max(1, args.chunks)
-    chunk_reads = [idx.simulate_pairs(args.pairs, seed=args.seed + 16 * rank + c, read_len=args.read_len, frag_mean=max(400.0, 2.2 * args.read_len))
-                   for c in range(n_chunks)]
-    import hashlib
-    import threading
-    n_fly = max(1, min(args.in_flight, 12))
-    # every caller thread owns a bseq1_t[] (and its .sam) per chunk
-    batches = [[abi.SeqBatch(api.libc, chunk_reads[c]) for c in range(n_chunks)] for _ in range(n_fly)]
+    maker[0].join()
+    if "error" in inputs:
+        raise inputs["error"]
+    chunk_reads, batches = inputs["chunk_reads"], inputs["batches"]
+    if rank == 0:
+        log("reads simulated and batched in %.1f s (beside the index), all set up %.1f s after the start" % (inputs["seconds"], time.time() - t_start))
     cores = int(lib.mi355x_host_cpus())
     opt = eng.opt(flag=abi.MEM_F_PE, n_threads=cores)
     lib_verbose = C.c_int.in_dll(eng.lib, "bwa_verbose")
     lib_verbose.value = 1   # keep the per-chunk stderr chatter out of the timed region
 
-    pending = []   # (thread, seqs[i].sam pointers) of finished steps; the caller (mpiBWA's writer thread, src/mainParallel.c:103-127) owns them
+    pending = []   # (thread, chunk, step, seqs[i].sam pointers) of finished steps; the caller (mpiBWA's writer thread, src/mainParallel.c:103-127) owns them
     lock = threading.Lock()
 
     step_no = [0]   # steps handed out so far (all phases): step s aligns chunk s mod n_chunks
@@ -207,7 +280,7 @@ def main():
                 eng.process_batch(opt, b)
                 st = eng.stats()                                          # this thread's last call
                 with lock:
-                    pending.append((t, c, b._rec["sam"].copy()))          # hand the output over, one pointer per read
+                    pending.append((t, c, s_, b._rec["sam"].copy()))      # hand the output over, one pointer per read
                     for k, v in st.items():
                         acc[k] = acc.get(k, 0) + v
                     if by_chunk is not None:
@@ -220,11 +293,15 @@ def main():
         for x in th:
             x.join()
 
-    digests = [set() for _ in range(n_chunks)]   # md5 of every step's SAM, per chunk
-    sam_bytes_seen = [0]
+    digests = [set() for _ in range(n_chunks)]   # hash of every step's SAM, per chunk (--full: checked against the reference's)
+    sam_bytes_of_chunk = {}   # a chunk's SAM is the same at every step (--full checks it)
     dg_lock = threading.Lock()
+    sam_buf, sam_cap = C.c_void_p(None), C.c_size_t(0)   # one buffer, kept from step to step (collect_one never runs twice at once)
+    dump_step = [-1]   # --dump-outputs: the step whose SAM sample is kept, and the sample
+    dumped = {}
 
-    import xxhash
+    if args.full:
+        import xxhash
 
     def sam_digest(buf):
         return xxhash.xxh3_128_hexdigest(buf)
@@ -232,26 +309,24 @@ def main():
     def collect_one(entry):
         # concatenate + free one step's SAM strings, as mpiBWA's copy_buffer_thr does (src/mainParallel.c:103-127); on a record array of
         # its own, so that the caller thread may already be aligning the same chunk again
-        t, c, ptrs = entry
+        t, c, s_, ptrs = entry
+        if s_ == dump_step[0]:
+            dumped.update(sample_sam(ptrs, args.seed))
         tmp = np.zeros(len(ptrs), dtype=abi.SeqBatch.dtype())
         tmp["sam"] = ptrs
-        n = C.c_size_t(0)
-        p = lib.mi355x_collect_sam(C.cast(tmp.ctypes.data, C.POINTER(abi.bseq1_t)), len(ptrs), C.byref(n))
-        d = sam_digest((C.c_char * n.value).from_address(p))
-        api.libc.free(C.c_void_p(p))
+        n = lib.mi355x_collect_sam_into(C.cast(tmp.ctypes.data, C.POINTER(abi.bseq1_t)), len(ptrs), C.byref(sam_buf), C.byref(sam_cap))
+        d = sam_digest((C.c_char * n).from_address(sam_buf.value)) if args.full else None
         with dg_lock:
             digests[c].add(d)
-            sam_bytes_seen[0] += n.value
+            sam_bytes_of_chunk[c] = n
 
     def drain():
-        before = sam_bytes_seen[0]
         while True:
             with lock:
                 e = pending.pop(0) if pending else None
             if e is None:
                 break
             collect_one(e)
-        return sam_bytes_seen[0] - before
 
     class Writer:
         """The caller's writer thread: takes the finished steps' SAM off the aligner threads' hands while they align the next chunks
@@ -278,12 +353,14 @@ def main():
             self.stop = True
             self.th.join()
 
+    t0 = time.time()
     run_steps(max(args.warmup, 1) * max(n_fly, n_chunks), {}, in_step=True)   # every call context warms its work buffers
     drain()
+    if rank == 0:
+        log("warm-up: %d steps in %.1f s" % (step_no[0], time.time() - t0))
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    seen0 = sam_bytes_seen[0]
     writer = Writer() if os.environ.get("MPIBWA_BENCH_WRITER", "0") == "1" else None   # (A/B: 8.5-8.7 vs 10.9-13.1 Mreads/s with eight calls in flight: it takes 0.45 CPU-s per step)
     t0 = time.perf_counter()
     c0 = time.process_time()
@@ -293,6 +370,8 @@ def main():
         print("[bench] timed region starts", file=sys.stderr, flush=True)
     thr0 = cgroup_throttle()
     acc = {}
+    timed0 = step_no[0]
+    dump_step[0] = timed0 + args.steps - 1 if args.dump_outputs and rank == 0 else -1
     run_steps(args.steps, acc)
     torch.cuda.synchronize()
     if world > 1:
@@ -306,13 +385,22 @@ def main():
     thr1 = cgroup_throttle()
     if writer:
         writer.finish()      # what the writer had not got to yet is collected outside the timed region
-    drain()
-    sam_bytes = sam_bytes_seen[0] - seen0
+    if args.full:
+        drain()
+    elif dump_step[0] >= 0 and not dumped:
+        dumped.update(sample_sam(next(e[3] for e in pending if e[2] == dump_step[0]), args.seed))
+    # (a plain run leaves the timed steps' SAM to the process exit: freeing it here would take ~0.1 s per step)
+    sam_bytes = sum(sam_bytes_of_chunk[s_ % n_chunks] for s_ in range(timed0, timed0 + args.steps))
+    if dump_step[0] >= 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in dumped.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+        log("outputs of step %d (chunk %d): SAM text of %d reads -> %s" % (dump_step[0], dump_step[0] % n_chunks, len(dumped["read_index"]), args.dump_outputs))
     # the latency mode next to it, outside the timed region: one call in flight, every chunk once (the kernels' durations when
     # they have the GPU to themselves; inside the timed region a launch shares the chip with the kernels of the other calls)
     alone = {}
     alone_s = None
-    if not args.quick:
+    if args.full and not args.quick:
         time.sleep(2.2)   # the library treats a caller as a busy one for two seconds after it last had three calls in flight
         run_steps(1, {}, fly=1)   # (the lone caller's mode has work buffers of its own: first touch outside the figure)
         drain()
@@ -325,7 +413,7 @@ def main():
     # touches + read + output): counted on the device by the counting variant of the kernel, every chunk once, outside the
     # timed region (the production variant leaves the per-extension block arithmetic out); a timed step on chunk c moved
     # exactly those bytes
-    if not args.quick:
+    if args.full and not args.quick:
         os.environ["MPIBWA_SMEM_COUNT"] = "1"
         counted = {}
         run_steps(n_chunks, {}, fly=1, by_chunk=counted)
@@ -341,7 +429,7 @@ def main():
     # shares the chip with seven other calls' kernels, the lone caller's launches hold half a chunk.  Never part of `value`; a failure
     # here only leaves the field out.
     smem_alone = None
-    if not args.quick and rank == 0 and os.environ.get("MPIBWA_BENCH_SMEM_ALONE", "1") != "0":
+    if args.full and not args.quick and rank == 0 and os.environ.get("MPIBWA_BENCH_SMEM_ALONE", "1") != "0":
         try:
             tr = bytes.maketrans(b"ACGTN", bytes([0, 1, 2, 3, 4]))
             ends = [e.translate(tr) for _, a, b in chunk_reads[0] for e in (a, b)]
@@ -448,7 +536,7 @@ def main():
                                "frac": round(g / 485.0, 4), "launch_ms_per_step": round(acc["k_ext_ms"] / args.steps, 2)}
 
     # ---- CPU baseline + parity: the reference itself on this box's host cores, every chunk once, rank 0 at N=1 only ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             from oracle import pyoracle as po
             if po.ref_available():
@@ -517,6 +605,7 @@ def main():
                               "broadcast_s": round(eng.bcast_seconds, 3) if eng.bcast_seconds is not None else None}
     if alt_workloads is not None:
         out["alt_workloads"] = alt_workloads
+    api.libc.free(sam_buf)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -148,12 +148,12 @@ def synth_packed_genome_grch38like(total_bases, seed=38, n_contigs=24, repeat_fr
     return pac, lens
 
 
-class BigIndex:
-    def __init__(self, prefix, pac, lens, engine):
-        self.prefix, self.pac, self.lens, self.engine = prefix, pac, lens, engine
+class Genome:
+    """A packed genome (2 bit/base, MSB first) and its contig lengths: what the read simulator needs, before any index exists."""
+
+    def __init__(self, pac, lens):
+        self.pac, self.lens = pac, lens
         self.l_pac = int(lens.sum())
-        self.blk_bytes = int(engine.bwt.contents.bwt_size) * 4
-        self.sa_bytes = int(engine.bwt.contents.n_sa) * 8
 
     def simulate_pairs(self, n_pairs, seed=1, read_len=150, frag_mean=400.0, frag_sd=50.0, sub=0.01, indel=0.001,
                        frac_random=0.02):
@@ -198,6 +198,14 @@ class BigIndex:
         return reads
 
 
+class BigIndex(Genome):
+    def __init__(self, prefix, pac, lens, engine):
+        super().__init__(pac, lens)
+        self.prefix, self.engine = prefix, engine
+        self.blk_bytes = int(engine.bwt.contents.bwt_size) * 4
+        self.sa_bytes = int(engine.bwt.contents.n_sa) * 8
+
+
 def _load_packed_genome(prefix):
     """The packed genome and contig lengths back from the node-local files rank 0 wrote (.pac mapped, not copied)."""
     with open(prefix + ".ann") as f:
@@ -212,7 +220,11 @@ def _load_packed_genome(prefix):
     return pac, lens
 
 
-def make_or_get(workdir, genome_mbp=3100.0, seed=38, rank=0, world=1, local_rank=0, dist=None, log=None, repeat_frac=0.05, model="uniform"):
+def make_or_get(workdir, genome_mbp=3100.0, seed=38, rank=0, world=1, local_rank=0, dist=None, log=None, repeat_frac=0.05, model="uniform",
+                on_genome=None):
+    """The index of the seeded synthetic genome, built on the GPU once per node and made resident.  on_genome(Genome), if given,
+    is called once as soon as the genome is at hand, before the index is built or uploaded (those run in the library with the
+    GIL released: the caller may simulate reads in a thread of its own meanwhile)."""
     lib = api.load_library()
     lib.mi355x_index_build_gpu.restype = C.c_int
     lib.mi355x_index_build_gpu.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_char_p, C.POINTER(C.c_double)]
@@ -228,6 +240,9 @@ def make_or_get(workdir, genome_mbp=3100.0, seed=38, rank=0, world=1, local_rank
         if log:
             log("synthetic genome: %.1f Mbp in %d contigs, generated in %.1f s" % (lens.sum() / 1e6, len(lens), time.time() - t0))
         write_meta_files(prefix, pac, lens)
+        if on_genome is not None:
+            on_genome(Genome(pac, lens))
+            on_genome = None
         secs = C.c_double(0)
         lib.mi355x_index_build_gpu(local_rank, pac.ctypes.data, int(lens.sum()), prefix.encode(), C.byref(secs))
         open(prefix + ".ok", "w").write("built in %.1f s\n" % secs.value)   # only a completed build is ever reused
@@ -237,6 +252,8 @@ def make_or_get(workdir, genome_mbp=3100.0, seed=38, rank=0, world=1, local_rank
     if dist is not None:
         dist.barrier()
     pac, lens = _load_packed_genome(prefix)
+    if on_genome is not None:
+        on_genome(Genome(pac, lens))
     # one rank per GPU.  Every rank maps the host side of the index from the node-local files (the host stages need pac
     # and the contig table); the device side is uploaded once by rank 0 and broadcast to the other GPUs over RCCL/xGMI.
     eng = api.Engine(prefix, device=local_rank, dist=dist, rank=rank)

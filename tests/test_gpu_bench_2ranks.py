@@ -21,7 +21,7 @@ def test_bench_two_ranks_shard_reads_and_broadcast_the_index(tmp_path, built):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MPIBWA_BENCH_BACKEND=backend, MPIBWA_BENCH_DIR=str(tmp_path), MPIBWA_HOST_THREADS="6")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29747",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-mbp", "50", "--pairs", "20000", "--chunks", "2",
-           "--in-flight", "2", "--check-parity"]
+           "--in-flight", "2", "--check-parity", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-3000:] + "\n" + "\n".join(l for l in r.stderr.splitlines() if not l.startswith("[M::"))[-6000:])

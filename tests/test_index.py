@@ -1,5 +1,5 @@
-"""Index builder / loader: known answer = the reference's own prebuilt hg19.small index (md5 fixture) when the
-reference tree is present, and cross-reading by the compiled reference otherwise."""
+"""Index builder / loader: known answer = the reference's own prebuilt hg19.small index (md5 fixture; the reference's
+examples/data/hg19.small.tar.gz is kept under tests/golden/mpibwa_examples), and cross-reading by the compiled reference."""
 import hashlib
 import json
 import os
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_DATA = "/root/reference/examples/data/hg19.small.tar.gz"
+REF_DATA = os.path.join(HERE, "golden", "mpibwa_examples", "hg19.small.tar.gz")
 
 
 def _md5(path):
@@ -21,7 +21,6 @@ def test_hg19_small_md5_fixture_is_committed():
     assert set(fx) == {"pac", "ann", "amb", "bwt", "sa"}
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DATA), reason="reference example data only exists in the build container")
 def test_builder_reproduces_reference_index(tmp_path, built):
     from mpibwa_amd import api
     with tarfile.open(REF_DATA) as tf:

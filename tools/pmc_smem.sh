@@ -9,7 +9,7 @@ O=$R/gpurun_out/pmc_smem
 rm -rf $O; mkdir -p $O
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "gather_probe" -d $O/probe --output-format csv -- python3 $R/tools/gather_probe_one.py > $O/probe.log 2>&1
 echo "probe rc=$?"
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "smem_" -d $O/smem --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --in-flight 1 --no-cpu-baseline --alt-legs "" > $O/smem.log 2>&1
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "smem_" -d $O/smem --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --in-flight 1 --no-cpu-baseline --alt-legs "" > $O/smem.log 2>&1
 echo "smem rc=$?"
 python3 - $O $R <<'PY'
 import csv, glob, json, sys
