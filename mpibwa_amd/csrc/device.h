@@ -258,11 +258,14 @@ struct MswParams {
 };
 size_t msw_lds_bytes(int max_len);
 // d_rows: scratch of n_req * (longest window) u16
-// h_req / h_len (read lengths) / h_list / d_list (2 n_req ints each) given: requests next to each other for the same mate and orientation
-// are aligned two per quad in packed 16-bit arithmetic (msw2_kernel); otherwise every request on its own
+// h_req / h_len (read lengths) / h_list / d_list (2 n_req ints each) / d_tail (msw_tail_ints(n_req) ints) given: requests next to each
+// other for the same mate and orientation are aligned two per quad in packed 16-bit arithmetic (msw2_kernel), and the alignments that
+// need the reverse pass get it in a launch of their own behind it (msw_tail_kernel); otherwise every request on its own
 void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req, const uint8_t *d_seq, const int64_t *d_off, const int *d_len,
                 const uint8_t *d_pac, MswRes *d_res, uint16_t *d_rows, int max_len, const MswReq *h_req = nullptr, const int *h_len = nullptr,
-                int *h_list = nullptr, int *d_list = nullptr);
+                int *h_list = nullptr, int *d_list = nullptr, int *d_tail = nullptr);
+#define MSW_TAIL_BUCKETS 9
+inline size_t msw_tail_ints(size_t n_req) { return 16 + MSW_TAIL_BUCKETS * n_req; }   // bucket counters + a list of n_req per bucket
 MswParams msw_params(const mem_opt_t *opt, int64_t l_pac);
 
 // ---- seed enumeration between SMEM and SA lookup (fm_kernels.hip) ----

@@ -677,15 +677,17 @@ extern "C" int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	Timer tm;
 	tm.start(st);
 	std::vector<int> h_list(2 * (size_t)n_req + 16);
-	int *d_list;
+	int *d_list, *d_tail;
 	HIP_OK(hipMalloc(&d_list, (2 * (size_t)n_req + 16) * sizeof(int)));
-	launch_msw(st, msw_params(opt, l_pac), n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, d_rows, max_len, rq.data(), lens.data(), h_list.data(), d_list);
+	HIP_OK(hipMalloc(&d_tail, msw_tail_ints(n_req) * sizeof(int)));
+	launch_msw(st, msw_params(opt, l_pac), n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, d_rows, max_len, rq.data(), lens.data(), h_list.data(), d_list,
+	           d_tail);
 	double ms = tm.stop(st);
 	HIP_OK(hipGetLastError());
 	static_assert(sizeof(MswRes) == 32, "MswRes layout");
 	HIP_OK(hipMemcpy(out8, d_res, (size_t)n_req * sizeof(MswRes), hipMemcpyDeviceToHost));
 	(void)hipFree(d_seq); (void)hipFree(d_pac); (void)hipFree(d_off); (void)hipFree(d_len); (void)hipFree(d_req); (void)hipFree(d_res);
-	(void)hipFree(d_rows); (void)hipFree(d_list);
+	(void)hipFree(d_rows); (void)hipFree(d_list); (void)hipFree(d_tail);
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;
 }

@@ -246,7 +246,8 @@ __global__ __launch_bounds__(64) void msw_kernel(MswParams P, int n_work, int n_
 // the row loop; what differs per row — the two target bases — selects one of 16 rows of a 128-entry table in LDS that holds, per
 // query code, the two substitution scores as a packed pair.  The row state of a position is one dword: H and E of both alignments
 // as four bytes, unpacked and repacked with one v_perm_b32 each.  Row maxima, best cell, saturation are kept per alignment as in
-// msw_pass (32-bit keys); the reverse pass and the b[] scan run per alignment through msw_tail, as for single requests.
+// msw_pass.  The kernel ends with the forward pass: an alignment that needs no second pass gets its final record here, the others
+// (score >= minsc, not saturated) are listed for msw_tail_kernel, which runs the b[] scan and the reverse pass densely behind it.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef short msw_s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ msw_s2 s2_of(uint32_t v) { return __builtin_bit_cast(msw_s2, v); }
@@ -260,19 +261,34 @@ __device__ __forceinline__ msw_s2 s2_sub0(msw_s2 a, msw_s2 b)
 	return __builtin_bit_cast(msw_s2, __builtin_elementwise_sub_sat(__builtin_bit_cast(msw_u2, a), __builtin_bit_cast(msw_u2, b)));
 }
 
+// The lists of alignments that need the second pass (msw_tail_kernel), by the length of that pass: rows ~ score / a (three classes),
+// cells per lane ~ qe (three classes); bucket MSW_TAIL_BUCKETS - 1 holds the longest.
+__device__ __forceinline__ int msw_tail_bucket(int score, int qe, int a)
+{
+	const int sb = score >= 80 * a ? 2 : score >= 40 * a ? 1 : 0;
+	const int qb = qe >= 96 ? 2 : qe >= 48 ? 1 : 0;
+	return sb * 3 + qb;
+}
+
+// scores of target base t against query codes 0..3 / code 4, without indexing the parameter block at run time (no scratch copy of it)
+__device__ __forceinline__ uint32_t msw_slo(const MswParams &P, int t) { return t == 0 ? P.slo[0] : t == 1 ? P.slo[1] : t == 2 ? P.slo[2] : P.slo[3]; }
+__device__ __forceinline__ int msw_s4(const MswParams &P, int t) { return t == 0 ? P.s4[0] : t == 1 ? P.s4[1] : t == 2 ? P.s4[2] : P.s4[3]; }
+
+// tail_n[MSW_TAIL_BUCKETS] (zeroed before the launch) / tail_list[MSW_TAIL_BUCKETS][tail_cap]: the alignments msw_tail_kernel completes
 __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int n_req, const int *__restrict__ pairs, const MswReq *__restrict__ req,
                                                   const uint8_t *__restrict__ seq, const int64_t *__restrict__ off, const int *__restrict__ lens,
-                                                  const uint8_t *__restrict__ pac, MswRes *__restrict__ res, uint16_t *__restrict__ rows, int s_max)
+                                                  const uint8_t *__restrict__ pac, MswRes *__restrict__ res, uint16_t *__restrict__ rows, int s_max,
+                                                  int *__restrict__ tail_n, int *__restrict__ tail_list, int tail_cap)
 {
 	extern __shared__ uint32_t lds2[];
-	uint32_t *cell = lds2;                                   // [s_max][64]: H_A, E_A, H_B, E_B as bytes (reverse passes: msw_pass's layout)
+	uint32_t *cell = lds2;                                   // [s_max][64]: H_A, E_A, H_B, E_B as bytes
 	uint32_t *codes = lds2 + (size_t)s_max * 64;             // [(s_max + 7) / 8][64]: eight 4-bit entries per dword: query code, bit 3 = end of a segment
 	uint32_t *stab = codes + (size_t)((s_max + 7) >> 3) * 64;   // [16][8]: (target base A, target base B) x query code -> the two scores, packed
 	const int lane = threadIdx.x, j = lane & 3;
 	for (int e = lane; e < 128; e += 64) {
 		const int ta = e >> 5, tb = (e >> 3) & 3, q = e & 7;
-		const int sa = q < 4 ? (int)(int8_t)(P.slo[ta] >> (8 * q)) : q == 4 ? P.s4[ta] : 0;
-		const int sb = q < 4 ? (int)(int8_t)(P.slo[tb] >> (8 * q)) : q == 4 ? P.s4[tb] : 0;
+		const int sa = q < 4 ? (int)(int8_t)(msw_slo(P, ta) >> (8 * q)) : q == 4 ? msw_s4(P, ta) : 0;
+		const int sb = q < 4 ? (int)(int8_t)(msw_slo(P, tb) >> (8 * q)) : q == 4 ? msw_s4(P, tb) : 0;
 		stab[e] = (uint32_t)(uint16_t)(int16_t)sa | (uint32_t)(uint16_t)(int16_t)sb << 16;
 	}
 	const int slot = blockIdx.x * 16 + (lane >> 2);
@@ -417,11 +433,129 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 	fA.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxA); fA.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teA); fA.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeA);
 	fB.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxB); fB.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teB); fB.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeB);
 	satA = msw_dpp<MSW_QP(3, 3, 3, 3)>(satA); satB = msw_dpp<MSW_QP(3, 3, 3, 3)>(satB);
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-	msw_tail(cell, P, pac, live, qa, qlen, ms, rA, n_req, fA, satA, rows, res);
-	if (__any(live && hasB)) msw_tail(cell, P, pac, live && hasB, qb, qlen, ms, hasB ? rB : 0, n_req, fB, satB, rows, res);
+	// Every alignment gets its record as msw_tail would leave it without a second pass (lane 0: A, lane 1: B).  One that reaches minsc
+	// unsaturated needs the b[] scan and the reverse pass: its request index goes to one of the MSW_TAIL_BUCKETS lists of msw_tail_kernel
+	// (wave-aggregated appends), which completes the record.
+	const int minsc = P.min_seed_len * P.a;
+	const bool mineA = live && j == 0, mineB = live && hasB && j == 1;
+	const MswPassOut f = j == 0 ? fA : fB;
+	const int sat = j == 0 ? satA : satB;
+	const bool tail = (mineA || mineB) && !sat && f.score >= minsc && f.qe >= 0 && f.te >= 0;
+	if (mineA || mineB) {
+		MswRes out;
+		out.score = f.score; out.te = f.te; out.qe = f.qe; out.score2 = -1; out.te2 = -1; out.tb = -1; out.qb = -1; out.flags = sat;
+		res[j == 0 ? rA : rB] = out;
+	}
+	const int bucket = msw_tail_bucket(f.score, f.qe, P.a);
+#pragma unroll
+	for (int b = 0; b < MSW_TAIL_BUCKETS; ++b) {
+		const bool in = tail && bucket == b;
+		const unsigned long long m = __builtin_amdgcn_ballot_w64(in);
+		if (!m) continue;
+		const int leader = __ffsll((long long)m) - 1;
+		int at = 0;
+		if (lane == leader) at = atomicAdd(&tail_n[b], __popcll(m));
+		at = __shfl(at, leader);
+		if (in) tail_list[(size_t)b * tail_cap + at + __popcll(m & ((1ull << lane) - 1))] = j == 0 ? rA : rB;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// msw_tail_kernel: what follows the forward pass of the alignments msw2_kernel listed (score >= minsc, not saturated) — score2 / te2
+// from the row maxima and the reverse pass that finds where the alignment starts — 16 alignments per wave, one per quad, all of them
+// live.  A wave runs in lockstep as long as its longest reverse pass (rows ~ score / a, cells ~ qe), so msw2_kernel sorts the
+// alignments into buckets by score and qe and this kernel takes the buckets one after the other, the long ones first.
+// b[] scan: each lane of a quad fetches 16 of the next 64 row maxima (independent loads, all in flight at once), the quad parks them in
+// LDS and every lane applies the sequential run rule of src/ksw.c:196-226 to the 64 values in row order.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, const int *__restrict__ tail_n, const int *__restrict__ tail_list, int tail_cap,
+                                                      const MswReq *__restrict__ req, const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
+                                                      const int *__restrict__ lens, const uint8_t *__restrict__ pac, MswRes *__restrict__ res,
+                                                      const uint16_t *__restrict__ rows)
+{
+	extern __shared__ uint32_t lds_t[];
+	uint16_t *blk = (uint16_t *)lds_t;                       // [16 quads][64 rows]: the row maxima of the b[] block in hand
+	uint32_t *cell = lds_t + 16 * 64 / 2;                    // msw_pass's layout
+	const int lane = threadIdx.x, j = lane & 3, quad = lane >> 2;
+	// the slot in the concatenation of the buckets, long reverse passes first
+	int slot = blockIdx.x * 16 + quad, b = MSW_TAIL_BUCKETS - 1;
+	for (; b >= 0; --b) {
+		const int n = tail_n[b];
+		if (slot < n) break;
+		slot -= n;
+	}
+	const bool live = b >= 0;
+	if (!__any(live)) return;
+	const int r = live ? tail_list[(size_t)b * tail_cap + slot] : 0;
+	MswReq rq;
+	rq.rb = rq.re = 0; rq.read = 0; rq.is_rev = 0;
+	MswRes out;
+	out.score = 0; out.te = -1; out.qe = -1; out.score2 = -1; out.te2 = -1; out.tb = -1; out.qb = -1; out.flags = 0;
+	if (live) { rq = req[r]; out = res[r]; }
+	const int qlen = live ? lens[rq.read] : 0;
+	const int tlen = live ? (int)(rq.re - rq.rb) : 0;
+	const uint8_t *ms = seq + (live ? off[rq.read] : 0);
+	const bool byte_flavour = qlen * P.a < 250;
+	const int PP = byte_flavour ? 16 : 8;
+	const int minsc = P.min_seed_len * P.a;
+	const int sat_limit = byte_flavour ? 255 - P.shift : 0x10000;
+	// ---- b[]: runs of rows whose maximum reaches minsc; second best = best run outside te +- ceil(score / max) ----
+	{
+		const int d = (out.score + P.max_sc - 1) / P.max_sc;
+		const int low = out.te - d, high = out.te + d;
+		int last_sc = -1, last_i = -1, sc2 = -1, te2 = -1;
+		int twave = tlen;
+		for (int o = 32; o; o >>= 1) twave = max(twave, __shfl_xor(twave, o));
+		uint16_t *qb = blk + quad * 64;
+		for (int i0 = 0; i0 < twave; i0 += 64) {
+			uint16_t v[16];
+#pragma unroll
+			for (int u = 0; u < 16; ++u) {
+				const int i = i0 + u * 4 + j;
+				v[u] = i < tlen ? rows[(size_t)i * n_req + r] : (uint16_t)0;
+			}
+			bool any = false;
+#pragma unroll
+			for (int u = 0; u < 16; ++u) {
+				qb[u * 4 + j] = v[u];
+				any |= i0 + u * 4 + j < tlen && (int)v[u] >= minsc;
+			}
+			if (!__any(any)) continue;
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			const int kend = min(64, tlen - i0);
+			for (int k = 0; k < kend; ++k) {
+				const int i = i0 + k, im = qb[k];
+				if (im < minsc) continue;
+				if (last_i < 0 || last_i + 1 != i) {
+					if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
+					last_sc = im; last_i = i;
+				} else if (last_sc < im) { last_sc = im; last_i = i; }
+			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		}
+		if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
+		out.score2 = sc2; out.te2 = te2;
+	}
+	// ---- the reverse pass over the reversed prefixes: where does the best local alignment start (KSW_XSTART) ----
+	int qlen2 = live ? out.qe + 1 : 0;
+	if (live && out.qe >= qlen) qlen2 = 0;   // cannot happen (the maximum of a row is reached on a real base first); stay in bounds
+	const int slen2 = (qlen2 + PP - 1) / PP, npos2 = slen2 * PP, S2 = npos2 >> 2;
+	if (qlen2 > 0)   // the codes of positions qe .. 0, padded, dealt to the quad; H and E cleared
+		for (int kk = 0; kk < S2; ++kk) {
+			const int k = j * S2 + kk;
+			const uint32_t c = k < qlen2 ? msw_code(ms, qlen, rq.is_rev, qlen2 - 1 - k) : MSW_PAD;
+			cell[kk * 64 + lane] = c << 26 | ((k + 1) % slen2 == 0 ? 0x80000000u : 0u);
+		}
+	int sat2 = 0;
+	const MswPassOut g = msw_pass(cell, P, pac, qlen2 > 0, S2, out.te + 1, rq.rb + out.te, -1, out.score, sat_limit, nullptr, 0, &sat2);
+	if (qlen2 > 0 && g.score == out.score) { out.tb = out.te - g.te; out.qb = out.qe - g.qe; }
+	if (live && qlen2 == 0) out.flags = 1;
+	if (sat2) out.flags = 1;
+	if (live && j == 0) res[r] = out;
 }
 
 } // namespace
@@ -437,15 +571,44 @@ size_t msw2_lds_bytes(int max_len)
 	return ((size_t)s_max * 64 + (size_t)((s_max + 7) / 8) * 64 + 128) * 4;
 }
 
+size_t msw_tail_lds_bytes(int max_len)
+{
+	return 16 * 64 * sizeof(uint16_t) + msw_lds_bytes(max_len);   // the b[] block of every quad + msw_pass's rows
+}
+
+// MPIBWA_CPUSEC diagnostic (waits for the launch): how many alignments of msw2_kernel's work items reach min_seed_len * a — those go
+// through the b[] scan and the reverse pass — and how many waves of 16 work items hold at least one such alignment as their first (A)
+// or second (B) request, i.e. would run that tail in lockstep if the tails ran in the forward kernel
+static void msw_tail_census(void *stream, const MswParams &P, int n_req, int n_pairs, const int *h_list, const MswRes *d_res)
+{
+	std::vector<MswRes> res((size_t)n_req);
+	HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+	HIP_OK(hipMemcpy(res.data(), d_res, (size_t)n_req * sizeof(MswRes), hipMemcpyDeviceToHost));
+	const int minsc = P.min_seed_len * P.a;
+	long hits_a = 0, hits_b = 0, waves_a = 0, waves_b = 0;
+	for (int w = 0; w * 16 < n_pairs; ++w) {
+		bool any_a = false, any_b = false;
+		for (int s = w * 16; s < std::min(n_pairs, w * 16 + 16); ++s) {
+			const int ra = h_list[2 * s], rb = h_list[2 * s + 1];
+			if (res[ra].score >= minsc) { ++hits_a; any_a = true; }
+			if (rb >= 0 && res[rb].score >= minsc) { ++hits_b; any_b = true; }
+		}
+		waves_a += any_a; waves_b += any_b;
+	}
+	fprintf(stderr, "[msw] packed work items: %ld + %ld alignments reach min_seed_len*a (%d); of %d waves, %ld hold an A hit, %ld a B hit\n", hits_a, hits_b,
+	        minsc, (n_pairs + 15) / 16, waves_a, waves_b);
+}
+
 // h_req: the requests as the host holds them (for the pairing), or null: every request on its own.  h_list / d_list: room for
 // 2 n_req ints each (host side page-locked in the pipeline): the pairs first (2 ints each), then the single requests.
 void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req, const uint8_t *d_seq, const int64_t *d_off, const int *d_len,
-                const uint8_t *d_pac, MswRes *d_res, uint16_t *d_rows, int max_len, const MswReq *h_req, const int *h_len, int *h_list, int *d_list)
+                const uint8_t *d_pac, MswRes *d_res, uint16_t *d_rows, int max_len, const MswReq *h_req, const int *h_len, int *h_list, int *d_list,
+                int *d_tail)
 {
 	if (n_req <= 0) return;
-	const size_t lds = msw_lds_bytes(max_len), lds2 = msw2_lds_bytes(max_len);
+	const size_t lds = msw_lds_bytes(max_len), lds2 = msw2_lds_bytes(max_len), lds_t = msw_tail_lds_bytes(max_len);
 	if (lds > 160 * 1024) die("mate-rescue kernel: reads of %d bp do not fit the LDS row buffers", max_len);
-	static size_t s_attr = 0, s_attr2 = 0;
+	static size_t s_attr = 0, s_attr2 = 0, s_attr_t = 0;
 	if (lds > s_attr) {
 		HIP_OK(hipFuncSetAttribute((const void *)msw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		s_attr = lds;
@@ -453,7 +616,7 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 	static const bool pairing = !(getenv("MPIBWA_MSW_PAIRS") && atoi(getenv("MPIBWA_MSW_PAIRS")) == 0);
 	int n_pairs = 0, n_single = n_req;
 	const int *d_single = nullptr;
-	if (pairing && h_req && h_len && h_list && d_list && lds2 <= 160 * 1024) {
+	if (pairing && h_req && h_len && h_list && d_list && d_tail && lds2 <= 160 * 1024 && lds_t <= 160 * 1024) {
 		// two requests next to each other for the same mate in the same orientation (mem_sam_pe lists an end's anchors one after the
 		// other: the windows of a repeat read's anchors are such runs), both in the byte flavour
 		// work items of msw2_kernel from the front of the list (two ints each; a byte-flavour request without a partner: (k, -1)), the
@@ -478,15 +641,28 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 				HIP_OK(hipFuncSetAttribute((const void *)msw2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
 				s_attr2 = lds2;
 			}
+			if (lds_t > s_attr_t) {
+				HIP_OK(hipFuncSetAttribute((const void *)msw_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
+				s_attr_t = lds_t;
+			}
+			// the forward passes, then — same stream, before the next batch reuses d_rows — the second passes of the alignments they
+			// listed: at most one per byte-flavour request, so (2 n_pairs - n_alone) / 16 waves are enough; the ones without work return
 			const int s_max = (max_len + 15) / 16 * 16 / 4;
+			int *d_tail_n = d_tail, *d_tail_list = d_tail + 16;
+			HIP_OK(hipMemsetAsync(d_tail_n, 0, MSW_TAIL_BUCKETS * sizeof(int), (hipStream_t)stream));
 			hipLaunchKernelGGL(msw2_kernel, dim3((n_pairs + 15) / 16), dim3(64), lds2, (hipStream_t)stream, P, n_pairs, n_req, (const int *)d_list, d_req, d_seq, d_off,
-			                   d_len, d_pac, d_res, d_rows, s_max);
+			                   d_len, d_pac, d_res, d_rows, s_max, d_tail_n, d_tail_list, n_req);
+			const int n_byte = 2 * n_pairs - n_alone;
+			hipLaunchKernelGGL(msw_tail_kernel, dim3((n_byte + 15) / 16), dim3(64), lds_t, (hipStream_t)stream, P, n_req, (const int *)d_tail_n,
+			                   (const int *)d_tail_list, n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, (const uint16_t *)d_rows);
 		}
 	}
 	if (n_single)
 		hipLaunchKernelGGL(msw_kernel, dim3((n_single + 15) / 16), dim3(64), lds, (hipStream_t)stream, P, n_single, n_req, d_single, d_req, d_seq, d_off, d_len, d_pac,
 		                   d_res, d_rows);
 	HIP_OK(hipGetLastError());
+	static const bool say = getenv("MPIBWA_CPUSEC") != nullptr;
+	if (say && n_pairs) msw_tail_census(stream, P, n_req, n_pairs, h_list, d_res);
 }
 
 } // namespace mbw

@@ -422,7 +422,7 @@ struct Workspace {
 	DevBuf heavy, hoff, grp_scratch, grp_clist, grp_ustart, grp_unit_rd, grp_unit_av, grp_nunits, c_rabs, c_rcnt;
 	PinBuf h_regs2;
 	PinBuf h_flat, h_sa, h_qbl, h_chains, h_seeds, h_srt, h_regs, h_nregs, h_mreq[2], h_mres[2], h_ahdr[2], h_apool[2];
-	DevBuf mreq[2], mres[2], mrows[2], alist[2], mlist[2];
+	DevBuf mreq[2], mres[2], mrows[2], alist[2], mlist[2], mtail[2];
 	PinBuf h_mlist[2];
 	DevBuf seq, off, len, intv, nintv, cnt, scratch, nseeds, lrep, seed_off, rows, qbl, sa;
 	DevBuf chain_off, chains, seeds, srt, reg_off, regs, nregs, tab, areq, ahdr, apool, agap, acnt, areq2, ahdr2, apool2, acnt2;
@@ -1574,11 +1574,12 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		const MswParams mp = msw_params(opt, bns->l_pac);
 		P.mev.start(P.st);
 		int *h_ml = (int *)WS.h_mlist[slot].ensure(2 * P.n_mreq * sizeof(int) + 64), *d_ml = (int *)WS.mlist[slot].ensure(2 * P.n_mreq * sizeof(int) + 64);
+		int *d_mt = (int *)WS.mtail[slot].ensure(msw_tail_ints(per) * sizeof(int));   // (one batch after the other on the stream)
 		static_assert(sizeof(MswReq) == sizeof(MswReqH), "host/device record layouts differ");
 		for (size_t b = 0; b < P.n_mreq; b += per) {
 			const int cnt = (int)std::min(per, P.n_mreq - b);
 			launch_msw(P.st, mp, cnt, d_req + b, d_seq, d_off, d_len, (const uint8_t *)ix.d_pac, d_res + b, d_rows, max_len, (const MswReq *)(P.mreq + b), lens,
-			           h_ml + 2 * b, d_ml + 2 * b);
+			           h_ml + 2 * b, d_ml + 2 * b, d_mt);
 		}
 		P.mev.stop(P.st);
 		HIP_OK(hipMemcpyAsync(P.mres, d_res, P.n_mreq * sizeof(MswRes), hipMemcpyDeviceToHost, P.st));   // pinned: truly asynchronous
