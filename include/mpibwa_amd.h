@@ -272,6 +272,23 @@ int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_read
                            const int64_t *seed_off, const uint64_t *rbeg, const int32_t *qbeg_len, int which,
                            int64_t *out, int64_t out_cap, int64_t *out_off);
 
+/* Chain -> alignment regions (mem_chain2aln, src/bwamem.c:632-786, applied to the chains of a read in order as mem_align1_core does)
+ * for n_reads reads given as nt4 codes (reads[off[r] .. off[r+1])) and their chains as mem_chain_t holds them after mem_chain_flt and
+ * mem_flt_chained_seeds: read r has n_chains[r] chains, chain c has rid chain_rid[c], frac_rep chain_frac[c] and chain_nseeds[c] seeds,
+ * all of them back to back, seed s = (seed_rbeg[s], seed_qbeg[s], seed_len[s], seed_score[s]) in the chain's array order.  The
+ * library's own packing, c2a_kernel and its chain groups and the region packing run as the pipeline runs them, on the resident index
+ * (mi355x_index_upload).  heavy_t: reads with more chains than that are split into independent groups of chains (0: never);
+ * early: 1 = no-DP closed form and early row stops (the product's default), 0 = every row of the reference, 2 = both, differences
+ * counted; layout 0 = the slots of device-chained reads (read r owns a sparse run of slots), 1 = those of host-chained reads (dense,
+ * behind the others).  Output per read from out[out_off[r]]: n_regs, then per region rb, re, qb, qe, rid, score, truesc, w, seedcov,
+ * seedlen0, frac_rep (float bits).  stat4: DP cells, extensions, extensions without DP, extensions that differ (early = 2);
+ * *n_units: units of the groups path.  Returns the number of int64 written, or -1 if out_cap is too small. */
+int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const uint8_t *reads, const int64_t *off,
+                         const int *n_chains, const int *chain_rid, const float *chain_frac, const int *chain_nseeds,
+                         const int64_t *seed_rbeg, const int *seed_qbeg, const int *seed_len, const int *seed_score,
+                         int heavy_t, int early, int layout, int64_t *out, int64_t out_cap, int64_t *out_off,
+                         uint64_t *stat4, int *n_units);
+
 /* Final global re-alignment (mem_reg2aln's loop src/bwamem.c:1106-1122 around bwa_gen_cigar2 src/bwa.c:121-207 and
  * ksw_global2 src/ksw.c:504-606) for n_req regions [rb,re) x [qb,qe) of read `read` (nt4 codes, read r =
  * reads[off[r]..off[r+1])) against the 2-bit packed reference `pac` of l_pac bases, computed by aln_kernel.

@@ -17,7 +17,7 @@ EXPORTS = [
     "mem_process_seqs", "mem_opt_init", "bwa_fill_scmat", "bwa_idx_load_from_disk", "bwa_mem2idx", "bwa_idx_destroy",
     "mi355x_index_upload", "mi355x_index_alloc", "mi355x_index_buffers", "mi355x_index_d2d", "mi355x_index_commit",
     "mi355x_finalize", "mi355x_index_build", "mi355x_index_build_gpu",
-    "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
+    "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
 ]
 
@@ -76,6 +76,8 @@ def load_library(build_if_missing=True):
     sig("mi355x_sa_dense_info", C.c_double, [P(C.c_size_t)])
     sig("mi355x_extend_batch", C.c_int, [P(abi.mem_opt_t), C.c_int] + [C.c_void_p] * 8 + [P(C.c_double), P(C.c_uint64)])
     sig("mi355x_chain_batch", C.c_int64, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p])
+    sig("mi355x_c2a_batch", C.c_int64, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 3 +
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("mi355x_fastq_scan", C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p])
     sig("mi355x_fastq_chunks", C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p])
     sig("mi355x_fastq_fill", C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p])
@@ -319,6 +321,44 @@ class Engine:
                 chs.append((rid, fb, fe, r0, r1, fr, sd))
             res.append(chs)
         return res
+
+    C2A_FIELDS = ("rb", "re", "qb", "qe", "rid", "score", "truesc", "w", "seedcov", "seedlen0", "frac_rep")
+
+    def chain2aln(self, opt, reads, chains, heavy_t=8, early=1, layout=0):
+        """Chain -> regions stage (mi355x_c2a_batch) on the resident index.  reads: nt4 code arrays; chains: per read a list of chains
+        (rid, frac_rep, [(rbeg, qbeg, len, score), ...]) as mem_chain_t holds them after mem_chain_flt and mem_flt_chained_seeds.
+        heavy_t: chain count above which a read goes through the chain groups (0: never); early: 0, 1 or 2; layout: 0 = slots of
+        device-chained reads, 1 = of host-chained reads.  Returns (per read an int64 array (n_regs, 11) in C2A_FIELDS order, frac_rep as
+        float bits; {"cells", "n_ext", "n_closed", "n_diff"}; units)."""
+        n = len(reads)
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        flat = np.concatenate([np.asarray(r, dtype=np.uint8) for r in reads]) if n else np.zeros(0, np.uint8)
+        flat = np.ascontiguousarray(np.append(flat, np.zeros(1, np.uint8)))
+        n_chains = np.array([len(c) for c in chains], dtype=np.int32)
+        ch = [c for per in chains for c in per]
+        rid = np.array([c[0] for c in ch] or [0], dtype=np.int32)
+        frac = np.array([c[1] for c in ch] or [0], dtype=np.float32)
+        nsd = np.array([len(c[2]) for c in ch] or [0], dtype=np.int32)
+        sd = np.array([s for c in ch for s in c[2]] or [(0, 0, 0, 0)], dtype=np.int64).reshape(-1, 4)
+        rbeg = np.ascontiguousarray(sd[:, 0])
+        qbeg, ln, sc = (np.ascontiguousarray(sd[:, k], dtype=np.int32) for k in (1, 2, 3))
+        cap = n + 11 * max(int(nsd.sum()), 1) + 64
+        out = np.zeros(cap, dtype=np.int64)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        stat = np.zeros(4, dtype=np.uint64)
+        units = C.c_int(0)
+        rc = self.lib.mi355x_c2a_batch(opt, C.cast(self.bns, C.c_void_p), n, flat.ctypes.data, off.ctypes.data, n_chains.ctypes.data, rid.ctypes.data,
+                                       frac.ctypes.data, nsd.ctypes.data, rbeg.ctypes.data, qbeg.ctypes.data, ln.ctypes.data, sc.ctypes.data,
+                                       int(heavy_t), int(early), int(layout), out.ctypes.data, cap, out_off.ctypes.data, stat.ctypes.data, C.addressof(units))
+        assert rc >= 0
+        res = []
+        for r in range(n):
+            p = int(out_off[r])
+            m = int(out[p])
+            res.append(out[p + 1:p + 1 + 11 * m].reshape(m, 11).copy())
+        st = dict(zip(("cells", "n_ext", "n_closed", "n_diff"), (int(x) for x in stat)))
+        return res, st, units.value
 
     REG_DT = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("rid", "<i4"), ("score", "<i4"), ("truesc", "<i4"), ("w", "<i4"),
                        ("seedcov", "<i4"), ("seedlen0", "<i4"), ("frac_rep", "<f4"), ("pad", "<i4")])

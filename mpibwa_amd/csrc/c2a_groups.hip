@@ -154,4 +154,42 @@ void launch_c2a_groups(void *stream, int n_el, int n_heavy, const int *d_hoff, c
 	HIP_OK(hipGetLastError());
 }
 
+C2aUnits c2a_prepare_units(void *stream, C2aGroupBufs &B, int heavy_t, int n, const int *chain_cnt, size_t n_chain_slots, const int *d_chain_beg,
+                           const int *d_reg_beg, const DevChain *d_chains, int *d_nregs, void (*wait)(void *stream))
+{
+	C2aUnits units;
+	if (heavy_t <= 0) return units;
+	hipStream_t st = (hipStream_t)stream;
+	int n_heavy = 0;
+	int64_t n_el = 0;
+	for (int i = 0; i < n; ++i)
+		if (chain_cnt[i] > heavy_t) { ++n_heavy; n_el += chain_cnt[i]; }
+	if (n_heavy == 0 || n_el >= 0x7fffffff) return units;
+	int *hv = (int *)B.h_heavy.ensure((size_t)n_heavy * 4 + 64), *ho = (int *)B.h_hoff.ensure((size_t)(n_heavy + 1) * 4 + 64);
+	int k = 0, tot = 0;
+	for (int i = 0; i < n; ++i)
+		if (chain_cnt[i] > heavy_t) { hv[k] = i; ho[k] = tot; tot += chain_cnt[i]; ++k; }
+	ho[k] = tot;
+	int *d_hv = (int *)B.heavy.ensure((size_t)n_heavy * 4), *d_ho = (int *)B.hoff.ensure((size_t)(n_heavy + 1) * 4);
+	void *d_gs = B.scratch.ensure(c2a_groups_scratch_bytes((int)n_el));
+	int *d_clist = (int *)B.clist.ensure((size_t)n_el * 4), *d_ustart = (int *)B.ustart.ensure((size_t)(n_el + 1) * 4);
+	int *d_urd = (int *)B.unit_rd.ensure((size_t)n_el * 4), *d_uav = (int *)B.unit_av.ensure((size_t)n_el * 4);
+	unsigned int *d_nu = (unsigned int *)B.nunits.ensure(64);
+	units.c_rabs = (int *)B.c_rabs.ensure(n_chain_slots * 4);
+	units.c_rcnt = (int *)B.c_rcnt.ensure(n_chain_slots * 4);
+	HIP_OK(hipMemcpyAsync(d_hv, hv, (size_t)n_heavy * 4, hipMemcpyHostToDevice, st));
+	HIP_OK(hipMemcpyAsync(d_ho, ho, (size_t)(n_heavy + 1) * 4, hipMemcpyHostToDevice, st));
+	launch_c2a_groups(st, (int)n_el, n_heavy, d_ho, d_hv, d_chain_beg, d_reg_beg, d_chains, d_gs, d_clist, d_ustart, d_urd, d_uav, d_nu);
+	// (the number of units sizes the launch: a grid padded to the number of chains would be millions of empty workgroups)
+	unsigned int *nu = (unsigned int *)B.h_nunits.ensure(64);
+	HIP_OK(hipMemcpyAsync(nu, d_nu, 4, hipMemcpyDeviceToHost, st));
+	if (wait) wait(st);
+	else HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	units.max_units = (int)nu[0]; units.heavy_t = heavy_t; units.n_units = d_nu; units.ustart = d_ustart;
+	units.unit_rd = d_urd; units.unit_av = d_uav; units.clist = d_clist;
+	HIP_OK(hipMemsetAsync(d_nregs, 0, (size_t)(n + 1) * 4, st));   // the units of a read add their regions up
+	return units;
+}
+
 } // namespace mbw

@@ -80,6 +80,11 @@ struct DevBuf {
 	void *ensure(size_t bytes);
 	void release();
 };
+// grow-only page-locked host buffer: staging for the bulk H2D / D2H copies (full PCIe rate, no per-chunk page faults)
+struct PinBuf {
+	void *p = nullptr; size_t cap = 0;
+	void *ensure(size_t bytes);
+};
 // pipeline.hip: called when a device allocation has failed; true = something was freed or a call has ended: try again
 bool device_memory_pressure(size_t wanted);
 void release_idle_work_buffers();   // all call contexts that are not inside a call (mi355x_finalize)
@@ -148,6 +153,23 @@ struct C2aUnits {
 	const int *clist = nullptr;
 	int *c_rabs = nullptr, *c_rcnt = nullptr;           // per chain (same numbering as the chain array): where its regions are, how many
 };
+// what the units of a launch need: launch_c2a_groups' inputs, outputs and scratch, the per-chain region places, the unit count read back
+struct C2aGroupBufs {
+	PinBuf h_heavy, h_hoff, h_nunits;
+	DevBuf heavy, hoff, scratch, clist, ustart, unit_rd, unit_av, nunits, c_rabs, c_rcnt;
+};
+// The units of the reads with more than heavy_t chains (chain_cnt: host copy of d_chain_cnt; n_chain_slots: size of the chain array):
+// launch_c2a_groups on `stream`, then one round trip for the number of units, which sizes launch_c2a's grid.  With units, d_nregs
+// (n + 1 entries) is zeroed on `stream` behind them.  max_units = 0: heavy_t is 0 or no read has that many chains.  wait: how to wait
+// for the stream (null: hipStreamSynchronize).
+C2aUnits c2a_prepare_units(void *stream, C2aGroupBufs &B, int heavy_t, int n, const int *chain_cnt, size_t n_chain_slots, const int *d_chain_beg,
+                           const int *d_reg_beg, const DevChain *d_chains, int *d_nregs, void (*wait)(void *stream) = nullptr);
+// c2a_kernel's launch order: the reads by decreasing number of seeds (counting sort), the long-running ones first
+void c2a_launch_order(int n, const int *nseeds, int *order);
+// the length tables of c2a_kernel (rows gap, bound5, bound3, ceil95, thr10) and chain_kernel (row 5: mem_flt_chained_seeds is a no-op),
+// max_len + 2 entries per row: the reference's floating-point decisions resolved per length
+void c2a_length_tables(const mem_opt_t *opt, int max_len, std::vector<int> &tab);
+void c2a_params(const mem_opt_t *opt, int64_t l_pac, int early, C2aParams &cp, ExtParams &ep);
 size_t c2a_groups_scratch_bytes(int n_el);
 void launch_c2a_groups(void *stream, int n_el, int n_heavy, const int *d_hoff, const int *d_heavy, const int *d_chain_beg, const int *d_reg_beg,
                        const DevChain *d_chains, void *d_scratch, int *d_clist, int *d_ustart, int *d_unit_rd, int *d_unit_av, unsigned int *d_n_units);

@@ -65,6 +65,16 @@ void DevBuf::release()
 	if (p) (void)hipFree(p);
 	p = nullptr; cap = 0;
 }
+void *PinBuf::ensure(size_t bytes)
+{
+	if (bytes > cap) {
+		note_buffer_growth(cap, bytes + bytes / 4 + 4096, "page-locked");
+		if (p) HIP_OK(hipHostFree(p));
+		cap = bytes + bytes / 4 + 4096;
+		HIP_OK(hipHostMalloc(&p, cap, hipHostMallocDefault));
+	}
+	return p;
+}
 
 static void require_device(int local_rank)
 {
@@ -363,6 +373,39 @@ SmemParams smem_params(const mem_opt_t *opt)
 	if (opt->split_width < 0 || opt->split_width >= 65535) die("split_width %d: the seeding kernel packs re-seed requests into 16 bits", opt->split_width);
 	sp.max_mem_intv = (int)opt->max_mem_intv;
 	return sp;
+}
+
+void c2a_length_tables(const mem_opt_t *opt, int max_len, std::vector<int> &tab)
+{
+	const int TS = max_len + 2;
+	tab.assign(6 * (size_t)TS, 0);
+	for (int l = 0; l < TS; ++l) {
+		tab[l] = cal_max_gap(opt, l);
+		tab[TS + l] = clamp_band(opt, l, 1 << 28, opt->pen_clip5);
+		tab[2 * TS + l] = clamp_band(opt, l, 1 << 28, opt->pen_clip3);
+		tab[3 * TS + l] = (int)ceil(l * .95);
+		tab[4 * TS + l] = (int)floor(.1 * l);
+		// mem_flt_chained_seeds returns at once for this length (src/bwamem.c:600-602)
+		const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log(l > 0 ? l : 1);
+		tab[5 * TS + l] = (l > 0 && min_l > 0.05f * l) ? 1 : 0;
+	}
+}
+
+void c2a_launch_order(int n, const int *nseeds, int *order)
+{
+	const int NB = 1024;
+	std::vector<int> start(NB + 1, 0);
+	for (int i = 0; i < n; ++i) ++start[NB - 1 - std::min(nseeds[i], NB - 1) + 1];
+	for (int b = 0; b < NB; ++b) start[b + 1] += start[b];
+	for (int i = 0; i < n; ++i) order[start[NB - 1 - std::min(nseeds[i], NB - 1)]++] = i;
+}
+
+void c2a_params(const mem_opt_t *opt, int64_t l_pac, int early, C2aParams &cp, ExtParams &ep)
+{
+	cp.l_pac = l_pac; cp.a = opt->a; cp.w = opt->w; cp.pen_clip5 = opt->pen_clip5; cp.pen_clip3 = opt->pen_clip3;
+	cp.early = early;
+	memcpy(ep.mat, opt->mat, 25);
+	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
 }
 
 // band clamp of src/ksw.c:395-407 (host side, double arithmetic as in the reference)
@@ -793,6 +836,179 @@ extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns,
 				const DevSeed &s = seeds[d.seed_beg + k];
 				out[at++] = s.rbeg; out[at++] = s.qbeg; out[at++] = s.len;
 			}
+		}
+	}
+	out_off[n_reads] = at;
+	return at;
+}
+
+// Stage-level entry point of chain -> regions (tests): see include/mpibwa_amd.h.  The chains are packed by the library's own
+// pack_chain_for_device and laid out as the pipeline lays out device-chained reads (layout 0: read r owns the slots from seed_off[r],
+// which leaves room behind its seeds as the seeding counts do) or host-chained ones (layout 1: dense, behind S slots); then the
+// pipeline's sequence: the length tables, the launch order, the chain groups with their round trip, c2a_kernel, reg_pack_kernel.
+extern "C" int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const uint8_t *reads, const int64_t *off,
+                                    const int *n_chains, const int *chain_rid, const float *chain_frac, const int *chain_nseeds,
+                                    const int64_t *seed_rbeg, const int *seed_qbeg, const int *seed_len, const int *seed_score,
+                                    int heavy_t, int early, int layout, int64_t *out, int64_t out_cap, int64_t *out_off,
+                                    uint64_t *stat4, int *n_units)
+{
+	using namespace mbw;
+	need_index();
+	if (bns->l_pac != g_idx.l_pac) die("mi355x_c2a_batch: the index given is not the resident one");
+	if (layout != 0 && layout != 1) die("mi355x_c2a_batch: layout %d", layout);
+	if (n_reads <= 0) return 0;
+	const int64_t l_pac = bns->l_pac;
+	int max_len = 0;
+	std::vector<int> lens(n_reads);
+	for (int i = 0; i < n_reads; ++i) { lens[i] = (int)(off[i + 1] - off[i]); max_len = std::max(max_len, lens[i]); }
+	std::vector<int> tab;
+	c2a_length_tables(opt, max_len, tab);
+	const int TS = max_len + 2;
+	// the chains through the library's packing; every seed checked against what mem_chain guarantees, so that no window leaves the index
+	std::vector<int> cbeg(n_reads + 1, 0), sbeg(n_reads + 1, 0), nseeds(n_reads, 0);
+	int64_t NC = 0, NS = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		cbeg[i] = (int)NC; sbeg[i] = (int)NS;
+		for (int c = 0; c < n_chains[i]; ++c) nseeds[i] += chain_nseeds[NC + c];
+		NC += n_chains[i]; NS += nseeds[i];
+	}
+	cbeg[n_reads] = (int)NC; sbeg[n_reads] = (int)NS;
+	std::vector<DevChain> pch(std::max<int64_t>(NC, 1));
+	std::vector<DevSeed> psd(std::max<int64_t>(NS, 1));
+	{
+		HChain ch;
+		std::vector<uint64_t> key;
+		int64_t s = 0;
+		for (int i = 0; i < n_reads; ++i)
+			for (int c = cbeg[i]; c < cbeg[i + 1]; ++c) {
+				ch.rid = chain_rid[c]; ch.frac_rep = chain_frac[c];
+				ch.seeds.resize(chain_nseeds[c]);
+				if (ch.rid < 0 || ch.rid >= bns->n_seqs) die("mi355x_c2a_batch: chain %d: rid %d", c, ch.rid);
+				for (int k = 0; k < chain_nseeds[c]; ++k, ++s) {
+					HSeed &h = ch.seeds[k];
+					h.rbeg = seed_rbeg[s]; h.qbeg = seed_qbeg[s]; h.len = seed_len[s]; h.score = seed_score[s];
+					if (h.len <= 0 || h.qbeg < 0 || h.qbeg + h.len > lens[i] || h.rbeg < 0 || h.rbeg + h.len > 2 * l_pac)
+						die("mi355x_c2a_batch: read %d, chain %d: seed %d out of bounds", i, c, k);
+				}
+				DevChain &d = pch[c];
+				pack_chain_for_device(bns, ch, lens[i], tab.data(), key, d, psd.data() + (s - chain_nseeds[c]));
+				for (int k = 0; k < chain_nseeds[c]; ++k) {
+					const DevSeed &t = psd[s - chain_nseeds[c] + k];
+					if (t.rbeg < d.rmax0 || t.rbeg + t.len > d.rmax1) die("mi355x_c2a_batch: read %d, chain %d: a seed leaves the chain's contig or strand", i, c);
+				}
+			}
+	}
+	// slots: layout 0 gives read i the run seed_off[i] .. (its seeds, and a few more: the seeding stage counts the seeds before chaining)
+	// for chains, seeds and regions alike; layout 1 puts them densely behind a base, the chains and the seeds each from their own offset
+	std::vector<int> chain_beg(n_reads), chain_cnt(n_reads), reg_beg(n_reads);
+	std::vector<int64_t> seed_at(n_reads);
+	int64_t n_slots = 0, n_chain_slots = 0;
+	if (layout == 0) {
+		int64_t so = 0;
+		for (int i = 0; i < n_reads; ++i) {
+			chain_beg[i] = reg_beg[i] = (int)so; seed_at[i] = so;
+			so += std::max(nseeds[i], n_chains[i]) + (i % 3);
+		}
+		n_slots = n_chain_slots = so;
+	} else {
+		const int64_t base = NS + 5;
+		for (int i = 0; i < n_reads; ++i) { chain_beg[i] = (int)(base + cbeg[i]); reg_beg[i] = (int)(base + sbeg[i]); seed_at[i] = base + sbeg[i]; }
+		n_slots = base + NS; n_chain_slots = base + NC;
+	}
+	if (n_slots > 0x7fffffff) die("mi355x_c2a_batch: too many seeds");
+	std::vector<DevChain> hch(std::max<int64_t>(n_chain_slots, 1));
+	std::vector<DevSeed> hsd(std::max<int64_t>(n_slots, 1));
+	std::vector<unsigned int> hsrt(std::max<int64_t>(n_slots, 1), 0);
+	for (int i = 0; i < n_reads; ++i) {
+		chain_cnt[i] = n_chains[i];
+		int64_t at = seed_at[i];
+		for (int c = 0; c < n_chains[i]; ++c) {
+			DevChain d = pch[cbeg[i] + c];
+			const int64_t from = sbeg[i] + (at - seed_at[i]);
+			for (int k = 0; k < d.n_seeds; ++k) { hsd[at + k] = psd[from + k]; hsrt[at + k] = (unsigned int)k; }
+			d.seed_beg = (int)at;
+			at += d.n_seeds;
+			hch[chain_beg[i] + c] = d;
+		}
+	}
+	// the reads in 16-byte slots, 16 bytes of padding behind the last one (the kernel stages a read 4 bytes at a time)
+	std::vector<int64_t> slot(n_reads + 1, 0);
+	for (int i = 0; i < n_reads; ++i) slot[i + 1] = slot[i] + ((lens[i] + 15) & ~15);
+	std::vector<uint8_t> flat(slot[n_reads] + 16, 4);
+	for (int i = 0; i < n_reads; ++i) memcpy(flat.data() + slot[i], reads + off[i], (size_t)lens[i]);
+	std::vector<int> order(n_reads);
+	c2a_launch_order(n_reads, nseeds.data(), order.data());
+
+	hipStream_t st = 0;
+	uint8_t *d_seq; int64_t *d_off; int *d_len, *d_cbeg, *d_ccnt, *d_rbeg, *d_nregs, *d_tab, *d_order, *d_reg_pos;
+	DevChain *d_ch; DevSeed *d_sd; unsigned int *d_srt; DevReg *d_regs, *d_packed; unsigned long long *d_stat;
+	HIP_OK(hipMalloc(&d_seq, flat.size())); HIP_OK(hipMalloc(&d_off, (size_t)(n_reads + 1) * 8)); HIP_OK(hipMalloc(&d_len, (size_t)n_reads * 4));
+	HIP_OK(hipMalloc(&d_cbeg, (size_t)n_reads * 4)); HIP_OK(hipMalloc(&d_ccnt, (size_t)n_reads * 4)); HIP_OK(hipMalloc(&d_rbeg, (size_t)n_reads * 4));
+	HIP_OK(hipMalloc(&d_nregs, (size_t)(n_reads + 1) * 4)); HIP_OK(hipMalloc(&d_tab, tab.size() * 4)); HIP_OK(hipMalloc(&d_order, (size_t)n_reads * 4));
+	HIP_OK(hipMalloc(&d_reg_pos, (size_t)(n_reads + 1) * 4));
+	HIP_OK(hipMalloc(&d_ch, hch.size() * sizeof(DevChain))); HIP_OK(hipMalloc(&d_sd, hsd.size() * sizeof(DevSeed)));
+	HIP_OK(hipMalloc(&d_srt, hsrt.size() * 4)); HIP_OK(hipMalloc(&d_regs, hsd.size() * sizeof(DevReg)));
+	HIP_OK(hipMalloc(&d_packed, hsd.size() * sizeof(DevReg))); HIP_OK(hipMalloc(&d_stat, C2A_STAT_SLOTS * 64));
+	const size_t tmp_bytes = reg_pack_tmp_bytes(n_reads);
+	void *d_tmp;
+	HIP_OK(hipMalloc(&d_tmp, tmp_bytes));
+	HIP_OK(hipMemcpy(d_seq, flat.data(), flat.size(), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_off, slot.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_len, lens.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_cbeg, chain_beg.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_ccnt, chain_cnt.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_rbeg, reg_beg.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_order, order.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_ch, hch.data(), hch.size() * sizeof(DevChain), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_sd, hsd.data(), hsd.size() * sizeof(DevSeed), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_srt, hsrt.data(), hsrt.size() * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemset(d_stat, 0, C2A_STAT_SLOTS * 64));
+	{
+		C2aGroupBufs B;
+		const C2aUnits units = c2a_prepare_units(st, B, heavy_t, n_reads, chain_cnt.data(), (size_t)std::max<int64_t>(n_chain_slots, 1), d_cbeg, d_rbeg,
+		                                         d_ch, d_nregs);
+		C2aParams cp;
+		ExtParams ep;
+		c2a_params(opt, l_pac, early, cp, ep);
+		launch_c2a(st, cp, ep, n_reads, d_seq, d_off, d_len, d_cbeg, d_ccnt, d_ch, d_sd, d_srt, d_rbeg, d_regs, d_nregs, d_tab, TS,
+		           (const uint8_t *)g_idx.d_pac, d_stat, max_len, d_order, units.max_units > 0 ? &units : nullptr);
+		launch_reg_pack(st, n_reads, d_rbeg, d_nregs, d_reg_pos, d_regs, d_packed, d_tmp, tmp_bytes, units.max_units > 0 ? &units : nullptr, d_cbeg, d_ccnt);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		if (n_units) *n_units = units.max_units;
+		B.heavy.release(); B.hoff.release(); B.scratch.release(); B.clist.release(); B.ustart.release(); B.unit_rd.release();
+		B.unit_av.release(); B.nunits.release(); B.c_rabs.release(); B.c_rcnt.release();
+		if (B.h_heavy.p) HIP_OK(hipHostFree(B.h_heavy.p));
+		if (B.h_hoff.p) HIP_OK(hipHostFree(B.h_hoff.p));
+		if (B.h_nunits.p) HIP_OK(hipHostFree(B.h_nunits.p));
+	}
+	std::vector<int> nregs(n_reads), reg_pos(n_reads + 1);
+	std::vector<unsigned long long> stat(C2A_STAT_SLOTS * 8);
+	HIP_OK(hipMemcpy(nregs.data(), d_nregs, (size_t)n_reads * 4, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(reg_pos.data(), d_reg_pos, (size_t)(n_reads + 1) * 4, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(stat.data(), d_stat, C2A_STAT_SLOTS * 64, hipMemcpyDeviceToHost));
+	std::vector<DevReg> regs(std::max(reg_pos[n_reads], 1));
+	HIP_OK(hipMemcpy((void *)regs.data(), d_packed, (size_t)reg_pos[n_reads] * sizeof(DevReg), hipMemcpyDeviceToHost));
+	(void)hipFree(d_seq); (void)hipFree(d_off); (void)hipFree(d_len); (void)hipFree(d_cbeg); (void)hipFree(d_ccnt); (void)hipFree(d_rbeg);
+	(void)hipFree(d_nregs); (void)hipFree(d_tab); (void)hipFree(d_order); (void)hipFree(d_reg_pos); (void)hipFree(d_ch); (void)hipFree(d_sd);
+	(void)hipFree(d_srt); (void)hipFree(d_regs); (void)hipFree(d_packed); (void)hipFree(d_stat); (void)hipFree(d_tmp);
+	for (int k = 0; k < 4; ++k) {
+		uint64_t t = 0;
+		for (int sl = 0; sl < C2A_STAT_SLOTS; ++sl) t += stat[(size_t)sl * 8 + k];
+		if (stat4) stat4[k] = t;
+	}
+	int64_t at = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		out_off[i] = at;
+		if (at + 1 + 11 * (int64_t)nregs[i] > out_cap) return -1;
+		out[at++] = nregs[i];
+		for (int k = 0; k < nregs[i]; ++k) {
+			const DevReg &a = regs[reg_pos[i] + k];
+			uint32_t fb;
+			memcpy(&fb, &a.frac_rep, 4);
+			const int64_t v[11] = {a.rb, a.re, a.qb, a.qe, a.rid, a.score, a.truesc, a.w, a.seedcov, a.seedlen0, (int64_t)fb};
+			for (int f = 0; f < 11; ++f) out[at++] = v[f];
 		}
 	}
 	out_off[n_reads] = at;

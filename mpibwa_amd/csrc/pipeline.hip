@@ -394,21 +394,6 @@ struct HostBuf {
 	void *ensure(size_t bytes) { if (bytes > cap) { free(p); cap = bytes + bytes / 4 + 4096; p = malloc(cap); if (!p) die("out of memory"); } return p; }
 };
 
-// grow-only page-locked host buffer: staging for the bulk H2D / D2H copies (full PCIe rate, no per-chunk page faults)
-struct PinBuf {
-	void *p = nullptr; size_t cap = 0;
-	void *ensure(size_t bytes)
-	{
-		if (bytes > cap) {
-			note_buffer_growth(cap, bytes + bytes / 4 + 4096, "page-locked");
-			if (p) HIP_OK(hipHostFree(p));
-			cap = bytes + bytes / 4 + 4096;
-			HIP_OK(hipHostMalloc(&p, cap, hipHostMallocDefault));
-		}
-		return p;
-	}
-};
-
 struct Workspace {
 	PinBuf h_nch, h_cbeg, h_ccnt, h_rbeg, h_nseeds, h_lrep, h_nintv;
 	// (every copy to or from the device uses page-locked host memory: a pageable target makes hipMemcpyAsync wait — spinning —
@@ -418,8 +403,7 @@ struct Workspace {
 	PinBuf h_c2a_stat;
 	PinBuf h_order;
 	// reads with many chains, extended as independent groups of chains (c2a_groups.hip)
-	PinBuf h_heavy, h_hoff, h_nunits;
-	DevBuf heavy, hoff, grp_scratch, grp_clist, grp_ustart, grp_unit_rd, grp_unit_av, grp_nunits, c_rabs, c_rcnt;
+	C2aGroupBufs grp;
 	PinBuf h_regs2;
 	PinBuf h_flat, h_sa, h_qbl, h_chains, h_seeds, h_srt, h_regs, h_nregs, h_mreq[2], h_mres[2], h_ahdr[2], h_apool[2];
 	DevBuf mreq[2], mres[2], mrows[2], alist[2], mlist[2], mtail[2];
@@ -928,21 +912,11 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		EvTimer ev_smem, ev_sa, ev_ext;
 		unsigned long long *d_cnt = (unsigned long long *)W.cnt.ensure(256);
 		unsigned long long *cnt = (unsigned long long *)W.h_cnt.ensure(256);
-		std::vector<int> gap_h(max_len + 2);
-		for (int l = 0; l < max_len + 2; ++l) gap_h[l] = cal_max_gap(opt, l);
 		// length tables for the device (the floating-point decisions of the reference, resolved per length on the host)
 		const int TS = max_len + 2;
-		std::vector<int> tab(6 * TS);
-		for (int l = 0; l < TS; ++l) {
-			tab[l] = gap_h[l];
-			tab[TS + l] = clamp_band(opt, l, 1 << 28, opt->pen_clip5);
-			tab[2 * TS + l] = clamp_band(opt, l, 1 << 28, opt->pen_clip3);
-			tab[3 * TS + l] = (int)ceil(l * .95);
-			tab[4 * TS + l] = (int)floor(.1 * l);
-			// mem_flt_chained_seeds returns at once for this length (src/bwamem.c:600-602)
-			const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log(l > 0 ? l : 1);
-			tab[5 * TS + l] = (l > 0 && min_l > 0.05f * l) ? 1 : 0;
-		}
+		std::vector<int> tab;
+		c2a_length_tables(opt, max_len, tab);
+		const int *gap_h = tab.data();   // (row 0: cal_max_gap)
 		int *d_tab = (int *)W.tab.ensure(tab.size() * 4);
 		HIP_OK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
 
@@ -1135,7 +1109,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 						DevChain d;
 						const size_t at = o.sd.size();
 						o.sd.resize(at + cs); o.srt.resize(at + cs);
-						pack_chain_for_device(bns, ch, seqs_r[i].l_seq, gap_h.data(), key, d, o.sd.data() + at);
+						pack_chain_for_device(bns, ch, seqs_r[i].l_seq, gap_h, key, d, o.sd.data() + at);
 						d.seed_beg = (int)at;   // block-local for now
 						for (int k = 0; k < cs; ++k) o.srt[at + k] = (unsigned int)k;   // the order array only carries "skipped" marks
 						o.ch.push_back(d);
@@ -1230,58 +1204,18 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 			HIP_OK(hipMemsetAsync(d_c2a_stat, 0, C2A_STAT_SLOTS * 64, st));
 			// launch order: reads by decreasing number of seeds (counting sort), the long-running ones first
 			int *order = (int *)W.h_order.ensure((size_t)n * 4 + 8);
-			{
-				const int NB = 1024;
-				std::vector<int> start(NB + 1, 0);
-				for (int i = 0; i < n; ++i) ++start[NB - 1 - std::min(nseeds[i], NB - 1) + 1];
-				for (int b = 0; b < NB; ++b) start[b + 1] += start[b];
-				for (int i = 0; i < n; ++i) order[start[NB - 1 - std::min(nseeds[i], NB - 1)]++] = i;
-			}
+			c2a_launch_order(n, nseeds, order);
 			int *d_order = (int *)W.order.ensure((size_t)n * 4);
 			HIP_OK(hipMemcpyAsync(d_order, order, (size_t)n * 4, hipMemcpyHostToDevice, st));
 			// Reads with more than a handful of chains (high-copy repeats: hundreds of chains at hundreds of loci) are not walked by one
 			// wavefront: their chains are split into groups that cannot see each other's regions (c2a_groups.hip), a unit of c2a_kernel each.
 			// MPIBWA_C2A_HEAVY=<chains> moves the threshold (0: every read is walked by one wavefront, as before round 4).
 			static const int heavy_t = getenv("MPIBWA_C2A_HEAVY") ? atoi(getenv("MPIBWA_C2A_HEAVY")) : 8;
-			C2aUnits units;
-			if (heavy_t > 0) {
-				int n_heavy = 0;
-				int64_t n_el = 0;
-				for (int i = 0; i < n; ++i)
-					if (chain_cnt[i] > heavy_t) { ++n_heavy; n_el += chain_cnt[i]; }
-				if (n_heavy > 0 && n_el < 0x7fffffff) {
-					int *hv = (int *)W.h_heavy.ensure((size_t)n_heavy * 4 + 64), *ho = (int *)W.h_hoff.ensure((size_t)(n_heavy + 1) * 4 + 64);
-					int k = 0, tot = 0;
-					for (int i = 0; i < n; ++i)
-						if (chain_cnt[i] > heavy_t) { hv[k] = i; ho[k] = tot; tot += chain_cnt[i]; ++k; }
-					ho[k] = tot;
-					int *d_hv = (int *)W.heavy.ensure((size_t)n_heavy * 4), *d_ho = (int *)W.hoff.ensure((size_t)(n_heavy + 1) * 4);
-					void *d_gs = W.grp_scratch.ensure(c2a_groups_scratch_bytes((int)n_el));
-					int *d_clist = (int *)W.grp_clist.ensure((size_t)n_el * 4), *d_ustart = (int *)W.grp_ustart.ensure((size_t)(n_el + 1) * 4);
-					int *d_urd = (int *)W.grp_unit_rd.ensure((size_t)n_el * 4), *d_uav = (int *)W.grp_unit_av.ensure((size_t)n_el * 4);
-					unsigned int *d_nu = (unsigned int *)W.grp_nunits.ensure(64);
-					const size_t n_chain_slots = (size_t)std::max<int64_t>(base + NC, 1);
-					units.c_rabs = (int *)W.c_rabs.ensure(n_chain_slots * 4);
-					units.c_rcnt = (int *)W.c_rcnt.ensure(n_chain_slots * 4);
-					HIP_OK(hipMemcpyAsync(d_hv, hv, (size_t)n_heavy * 4, hipMemcpyHostToDevice, st));
-					HIP_OK(hipMemcpyAsync(d_ho, ho, (size_t)(n_heavy + 1) * 4, hipMemcpyHostToDevice, st));
-					launch_c2a_groups(st, (int)n_el, n_heavy, d_ho, d_hv, d_chain_beg, d_reg_beg, d_chains, d_gs, d_clist, d_ustart, d_urd, d_uav, d_nu);
-					// (the number of units sizes the launch: a grid padded to the number of chains would be millions of empty workgroups)
-					unsigned int *nu = (unsigned int *)W.h_nunits.ensure(64);
-					HIP_OK(hipMemcpyAsync(nu, d_nu, 4, hipMemcpyDeviceToHost, st));
-					stream_wait(st);
-					HIP_OK(hipGetLastError());
-					units.max_units = (int)nu[0]; units.heavy_t = heavy_t; units.n_units = d_nu; units.ustart = d_ustart;
-					units.unit_rd = d_urd; units.unit_av = d_uav; units.clist = d_clist;
-					HIP_OK(hipMemsetAsync(d_nregs, 0, (size_t)(n + 1) * 4, st));   // the units of a read add their regions up
-				}
-			}
+			const C2aUnits units = c2a_prepare_units(st, W.grp, heavy_t, n, chain_cnt, (size_t)std::max<int64_t>(base + NC, 1), d_chain_beg, d_reg_beg,
+			                                         d_chains, d_nregs, [](void *s) { stream_wait((hipStream_t)s); });
 			C2aParams cp;
-			cp.l_pac = bns->l_pac; cp.a = opt->a; cp.w = opt->w; cp.pen_clip5 = opt->pen_clip5; cp.pen_clip3 = opt->pen_clip3;
-			cp.early = c2a_early_mode();
 			ExtParams ep;
-			memcpy(ep.mat, opt->mat, 25);
-			ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
+			c2a_params(opt, bns->l_pac, c2a_early_mode(), cp, ep);
 			stage(50);
 			std::unique_lock<TurnLock> turn(g_c2a_turn, std::defer_lock);
 			if (take_turns) turn.lock();

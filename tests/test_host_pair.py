@@ -9,22 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from c2a_cases import CHAIN_T_BYTES, _alnreg_v, _chain_v, _ref_handle, _regs_copy
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.skipif(not po.ref_available(), reason="oracle/_ref/libbwaref.so not built")
-
-
-def _ref_handle():
-    """a ctypes handle of our own on the reference's library: the prototypes set here must not change those of oracle/pyoracle.py's handle"""
-    import os
-    po.ref_lib()
-    h = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(po.__file__)), "_ref", "libbwaref.so"))
-    h.bwa_fill_scmat.argtypes = [C.c_int, C.c_int, C.c_void_p]
-    return h
-
-
-class _alnreg_v(C.Structure):   # mem_alnreg_v (src/bwamem.h:79)
-    _fields_ = [("n", C.c_size_t), ("m", C.c_size_t), ("a", C.c_void_p)]
 
 
 @pytest.fixture(scope="module")
@@ -56,12 +44,6 @@ def _batch(ref, lib_ref, opt, reads):
     pes = (abi.mem_pestat_t * 4)()
     lib_ref.mem_pestat(opt, ref.bns.contents.l_pac, n, regs, pes)
     return regs, seqs, pes
-
-
-def _regs_copy(v):
-    if not v.n:
-        return np.zeros(0, dtype=po.ALNREG_DT)
-    return np.ctypeslib.as_array(C.cast(v.a, C.POINTER(C.c_uint8)), shape=(v.n * 88,)).view(po.ALNREG_DT).copy()
 
 
 CASES = [
@@ -173,13 +155,6 @@ def test_host_sam_pe_with_alt_contigs(genome_alt, kw):
                                     [("a" + n, a, b) for n, a, b in simulate.simulate_reads(alt_seqs, 250, 150, paired=True, seed=62, frag_mean=300.0, frag_sd=30.0)])
     n_rescued, n_many, n_xa, n_supp, n_lines = _compare_pairs(lib, lib_ref, ref, opt, reads, str(kw))
     assert n_lines >= 2 * len(reads) and _compare_pairs.n_pa > 50, (n_lines, _compare_pairs.n_pa, n_xa)   # (pa:f: = a primary hit that has an ALT twin)
-
-
-class _chain_v(C.Structure):   # mem_chain_v (src/bwamem.c:180)
-    _fields_ = [("n", C.c_size_t), ("m", C.c_size_t), ("a", C.c_void_p)]
-
-
-CHAIN_T_BYTES = 40   # mem_chain_t (src/bwamem.c:174-179): n, m, first, rid, w:29|kept:2|is_alt:1, frac_rep, pos, seeds*
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(a=2, b=5, o_del=8, e_del=2, o_ins=7, e_ins=3, T=50, zdrop=150), dict(mask_level_redun=0.8, w=40),
