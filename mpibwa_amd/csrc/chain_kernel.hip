@@ -1,15 +1,16 @@
-// chain_kernel.hip — seeds -> chains -> filtered chains on the device, one lane per read.
+// chain_kernel.hip — seeds -> chains -> filtered chains on the device.
 //
 // Device counterpart of mem_chain (src/bwamem.c:251-315), test_and_merge (:190-211), mem_chain_weight (:213-237) and
-// mem_chain_flt (:327-385).  One body (chain_read) over two kinds of storage and two statements of the reference's ordered map:
-//  * the reads the reference's own data structure keeps trivial: its map is a B-tree whose root holds up to 9 keys
-//    (src/kbtree.h, node size 512 B), so a read that never has more than 9 chains lives in one sorted array — MapArray, with the
-//    B-tree's rules for equal keys (a new key goes right behind the FIRST equal one; a lookup that hits equal keys returns the
-//    first), state in LDS (StoreLds).  Three launches with growing LDS footprints (chain_kernel<seeds, chains, ...>);
-//  * the reads with more chains: the B-tree itself (MapBtree: kb_intervalp / kb_putp with t = 5), state in an HBM slice per read
-//    (StoreGen), up to 255 seeds and chains (chain_general_kernel).
-// Reads with more than 255 seeds, or long enough for mem_flt_chained_seeds to act (l_query >= ~700 bp), are flagged
-// (n_chains = -1) and take the host path (host_chain.cpp).
+// mem_chain_flt (:327-385).  Who chains a read is decided by how much of the reference's ordered map it needs:
+//  * the reads the reference's own data structure keeps trivial, one LANE per read (chain_kernel, body chain_read): its map is a
+//    B-tree whose root holds up to 9 keys (src/kbtree.h, node size 512 B), so a read that never has more than 9 chains lives in one
+//    sorted array — MapArray, with the B-tree's rules for equal keys (a new key goes right behind the FIRST equal one; a lookup that
+//    hits equal keys returns the first), state in LDS (StoreLds).  Three launches with growing LDS footprints
+//    (chain_kernel<seeds, chains, ...>: up to 16, 64 and 255 seeds);
+//  * the reads with more chains than one node holds, or with more than 255 seeds: one WAVEFRONT per read, the map as a sorted array
+//    in LDS (chain_heavy_kernel<256 / 1024 / 4096 seeds>, further down);
+//  * the rest stays flagged (n_chains < 0) and takes the host path (host_chain.cpp): more than 4 096 seeds, two chains at one
+//    position (where the shape of the reference's tree shows), or long enough for mem_flt_chained_seeds to act (l_query >= ~700 bp).
 //
 // The unstable sort of mem_chain_flt is ks_introsort (src/ksort.h:176-226) statement by statement (ck_introsort).
 // Floating-point compares (mask_level, drop_ratio, frac_rep) are IEEE single precision in the same expression shapes as
@@ -21,7 +22,6 @@
 // Latency-bound integer work: ~1.5 k instructions per ordinary read, a few hundred bytes of HBM per read.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <algorithm>
 #include <cstdlib>
 #include <mutex>
 #include <utility>
@@ -44,21 +44,13 @@ typedef long long i64;
 #define CK_MAXCH_SMALL 4
 #define CK_MAXSEEDS_SMALL 16   // first launch: every read, up to this many seeds and CK_MAXCH_SMALL chains
 #define CK_MAXSEEDS 64         // second launch: what the first declined, up to this many seeds
-#define CK_MAXSEEDS_BIG 255    // third launch (and the B-tree kernel): reads with more seeds than that (seed numbers are bytes)
-#define CK_MAXCH_GEN 255       // third launch: chains per read (chain numbers are bytes, 255 = none)
-#define CK_MAXNODES 128        // ... and B-tree nodes per read (255 keys in nodes of >= 4 need 64 leaves + their parents)
-enum { F_POS_LO = 0, F_POS_HI, F_FIRST_Q, F_LAST_R_LO, F_LAST_R_HI, F_LAST_Q, F_LAST_LEN, F_RID, F_N, F_W, F_KEPT, F_FIRSTOV, F_NFIELDS,
-       F_HEAD = F_NFIELDS, F_TAIL, F_NFIELDS_GEN };
+#define CK_MAXSEEDS_BIG 255    // third launch: reads with more seeds than that (seed numbers are bytes, 255 = in no chain)
+enum { F_POS_LO = 0, F_POS_HI, F_FIRST_Q, F_LAST_R_LO, F_LAST_R_HI, F_LAST_Q, F_LAST_LEN, F_RID, F_N, F_W, F_KEPT, F_FIRSTOV, F_NFIELDS };
 
 // ---- where a read's working set lives ----
-// StoreLds: the reads the reference's ordered map keeps in ONE node (at most 9 chains): everything in LDS, [..][lane].
-// StoreGen: up to 255 chains: the same fields in a per-read slice of an HBM scratch buffer, plus the seeds of a chain as a
-//           linked list in arrival order (the weight and emission loops of a read with 150 seeds and 50 chains would otherwise
-//           scan all seeds once per chain) and the nodes of the B-tree.
-template <int MAXCH_>
+// The reads the reference's ordered map keeps in ONE node (at most 9 chains): everything in LDS, [..][lane].
+template <int MAXCH>
 struct StoreLds {
-	static constexpr int MAXCH = MAXCH_;
-	static constexpr bool GENERAL = false;
 	uint32_t *tab;    // [F_NFIELDS * MAXCH][64]
 	uint8_t *cid_;    // [MAXS + 1][64]     chain id of every seed (255 = in no chain)
 	uint8_t *ord_;    // [16][64]           chain ids in tree order, later in filter order
@@ -69,39 +61,26 @@ struct StoreLds {
 	__device__ __forceinline__ uint8_t &ord(int k) const { return ord_[k * 64 + lane]; }
 	__device__ __forceinline__ uint8_t &tmp(int k) const { return tmp_[k * 64 + lane]; }
 };
-struct GenNode { uint8_t internal, n, key[2 * 5 - 1], child[2 * 5], pad[3]; };   // the reference's node: t = 5, up to 9 keys (src/kbtree.h, 512-byte nodes of 40-byte chains)
-struct StoreGen {
-	static constexpr int MAXCH = CK_MAXCH_GEN;
-	static constexpr bool GENERAL = true;
-	uint32_t *tab;    // [F_NFIELDS_GEN][CK_MAXCH_GEN]
-	uint8_t *cid_, *ord_, *tmp_, *next_;   // [256] each
-	GenNode *nodes;   // [CK_MAXNODES]
-	__device__ __forceinline__ uint32_t &f(int field, int id) const { return tab[field * CK_MAXCH_GEN + id]; }
-	__device__ __forceinline__ uint8_t &cid(int k) const { return cid_[k]; }
-	__device__ __forceinline__ uint8_t &ord(int k) const { return ord_[k]; }
-	__device__ __forceinline__ uint8_t &tmp(int k) const { return tmp_[k]; }
-	__device__ __forceinline__ uint8_t &next(int k) const { return next_[k]; }
-};
-constexpr size_t CK_GEN_BYTES = ((size_t)F_NFIELDS_GEN * CK_MAXCH_GEN * 4 + 4 * 256 + CK_MAXNODES * sizeof(GenNode) + 255) & ~(size_t)255;
 
-template <class S> __device__ __forceinline__ i64 st_pos(const S &L, int id) { return (i64)((unsigned long long)L.f(F_POS_HI, id) << 32 | L.f(F_POS_LO, id)); }
-template <class S> __device__ __forceinline__ i64 st_last_r(const S &L, int id) { return (i64)((unsigned long long)L.f(F_LAST_R_HI, id) << 32 | L.f(F_LAST_R_LO, id)); }
+template <int MAXCH> __device__ __forceinline__ i64 st_pos(const StoreLds<MAXCH> &L, int id) { return (i64)((unsigned long long)L.f(F_POS_HI, id) << 32 | L.f(F_POS_LO, id)); }
+template <int MAXCH> __device__ __forceinline__ i64 st_last_r(const StoreLds<MAXCH> &L, int id) { return (i64)((unsigned long long)L.f(F_LAST_R_HI, id) << 32 | L.f(F_LAST_R_LO, id)); }
 
 // ---- the ordered map of mem_chain (src/bwamem.c:263, 288-300; src/kbtree.h) ----
 // One node: a sorted array with the B-tree's rules for equal keys (a new key goes right behind the first key that is not
 // smaller ... stepped back; a lookup that hits equal keys returns the first of them).
+template <int MAXCH>
 struct MapArray {
 	int n = 0;
-	template <class S> __device__ __forceinline__ int lower(const S &L, i64 pos) const   // closest chain at or before pos, or -1
+	__device__ __forceinline__ int lower(const StoreLds<MAXCH> &L, i64 pos) const   // closest chain at or before pos, or -1
 	{
 		int f = 0;
 		while (f < n && st_pos(L, L.ord(f)) < pos) ++f;
 		const int li = (f < n && st_pos(L, L.ord(f)) == pos) ? f : f - 1;
 		return li >= 0 ? (int)L.ord(li) : -1;
 	}
-	template <class S> __device__ __forceinline__ bool put(const S &L, int id, i64 pos)
+	__device__ __forceinline__ bool put(const StoreLds<MAXCH> &L, int id, i64 pos)   // ord[] stays in key order
 	{
-		if (n == S::MAXCH) return false;   // the reference's root node would split here
+		if (n == MAXCH) return false;   // the reference's root node would split here
 		int f = 0;
 		while (f < n && st_pos(L, L.ord(f)) < pos) ++f;
 		const int li = (f < n && st_pos(L, L.ord(f)) == pos) ? f : f - 1;
@@ -109,115 +88,6 @@ struct MapArray {
 		L.ord(li + 1) = (uint8_t)id;
 		++n;
 		return true;
-	}
-	template <class S> __device__ __forceinline__ void in_order(const S &) const {}   // ord already is
-};
-// The B-tree itself (kb_intervalp / kb_putp of src/kbtree.h with t = 5), because with equal keys what a lookup returns
-// depends on where the splits put them.
-struct MapBtree {
-	int n = 0, n_nodes = 0, root = 0;
-	bool full = false;
-	template <class S> __device__ __forceinline__ int make(const S &L)
-	{
-		if (n_nodes == CK_MAXNODES) { full = true; return 0; }
-		GenNode &x = L.nodes[n_nodes];
-		x.internal = 0; x.n = 0;
-		return n_nodes++;
-	}
-	// index of the last key <= pos in the node (-1: none); *r = sign(pos - that key's successor rule) as __kb_getp_aux
-	template <class S> __device__ __forceinline__ int locate(const S &L, const GenNode &x, i64 pos, int *r) const
-	{
-		int begin = 0, end = x.n;
-		if (x.n == 0) return -1;
-		while (begin < end) {
-			const int mid = (begin + end) >> 1;
-			if (st_pos(L, x.key[mid]) < pos) begin = mid + 1;
-			else end = mid;
-		}
-		if (begin == x.n) { *r = 1; return x.n - 1; }
-		const i64 kp = st_pos(L, x.key[begin]);
-		*r = (kp < pos) - (pos < kp);
-		if (*r < 0) --begin;
-		return begin;
-	}
-	template <class S> __device__ __forceinline__ int lower(const S &L, i64 pos) const
-	{
-		if (n == 0) return -1;
-		int low = -1, r = 0, xi = root;
-		for (;;) {
-			const GenNode &x = L.nodes[xi];
-			const int i = locate(L, x, pos, &r);
-			if (i >= 0 && r == 0) return x.key[i];
-			if (i >= 0) low = x.key[i];
-			if (!x.internal) return low;
-			xi = x.child[i + 1];
-		}
-	}
-	template <class S> __device__ __forceinline__ void split(const S &L, int xi, int i, int yi)
-	{
-		const int zi = make(L);
-		if (full) return;
-		GenNode &x = L.nodes[xi], &y = L.nodes[yi], &z = L.nodes[zi];
-		z.internal = y.internal;
-		z.n = 4;
-		for (int k = 0; k < 4; ++k) z.key[k] = y.key[5 + k];
-		if (y.internal) for (int k = 0; k < 5; ++k) z.child[k] = y.child[5 + k];
-		y.n = 4;
-		for (int k = x.n; k > i; --k) x.child[k + 1] = x.child[k];
-		x.child[i + 1] = (uint8_t)zi;
-		for (int k = x.n - 1; k >= i; --k) x.key[k + 1] = x.key[k];
-		x.key[i] = y.key[4];
-		++x.n;
-	}
-	template <class S> __device__ __forceinline__ bool put(const S &L, int id, i64 pos)
-	{
-		if (n == S::MAXCH) return false;
-		if (n_nodes == 0) root = make(L);
-		int r = root, rr = 0;
-		if (L.nodes[r].n == 9) {
-			const int si = make(L);
-			if (full) return false;
-			root = si; L.nodes[si].internal = 1; L.nodes[si].n = 0;
-			L.nodes[si].child[0] = (uint8_t)r;
-			split(L, si, 0, r);
-			if (full) return false;
-			r = si;
-		}
-		int xi = r;
-		while (L.nodes[xi].internal) {
-			int i = locate(L, L.nodes[xi], pos, &rr) + 1;
-			if (L.nodes[L.nodes[xi].child[i]].n == 9) {
-				split(L, xi, i, L.nodes[xi].child[i]);
-				if (full) return false;
-				if (st_pos(L, L.nodes[xi].key[i]) < pos) ++i;
-			}
-			xi = L.nodes[xi].child[i];
-		}
-		GenNode &x = L.nodes[xi];
-		const int i = locate(L, x, pos, &rr);
-		for (int k = x.n - 1; k > i; --k) x.key[k + 1] = x.key[k];
-		x.key[i + 1] = (uint8_t)id;
-		++x.n;
-		++n;
-		return true;
-	}
-	template <class S> __device__ __forceinline__ void in_order(const S &L) const   // chain ids in key order into ord[]
-	{
-		if (n == 0) return;
-		int sn[8], si[8], sp = 0, out = 0;   // node, children already entered (a tree of <= 255 keys with >= 4 per node is at most 4 levels deep)
-		sn[0] = root; si[0] = 0;
-		while (sp >= 0) {
-			const GenNode &x = L.nodes[sn[sp]];
-			if (!x.internal) {
-				for (int k = 0; k < x.n; ++k) L.ord(out++) = x.key[k];
-				--sp;
-				continue;
-			}
-			const int i = si[sp];
-			if (i > 0 && i <= x.n) L.ord(out++) = x.key[i - 1];   // back from child i - 1: its separator key
-			if (i <= x.n) { si[sp] = i + 1; ++sp; sn[sp] = x.child[i]; si[sp] = 0; }
-			else --sp;
-		}
 	}
 };
 
@@ -239,14 +109,14 @@ __device__ __forceinline__ i64 ck_depos(i64 l_pac, i64 pos) { return pos >= l_pa
 // the unstable sort of mem_chain_flt for any n: ks_introsort (src/ksort.h:176-226) on the chain ids in ord[0, n), "less" =
 // heavier first — median-of-three quicksort with an explicit stack, ranges of <= 16 left to one final insertion sort, comb
 // sort when the depth budget runs out (sortutil.h is the host's statement of the same)
-template <class S, class LT>
-__device__ __forceinline__ void ck_insertion(const S &L, int s, int t, LT lt)   // [s, t)
+template <int MAXCH, class LT>
+__device__ __forceinline__ void ck_insertion(const StoreLds<MAXCH> &L, int s, int t, LT lt)   // [s, t)
 {
 	for (int i = s + 1; i < t; ++i)
 		for (int j = i; j > s && lt(L.ord(j), L.ord(j - 1)); --j) { const uint8_t x = L.ord(j); L.ord(j) = L.ord(j - 1); L.ord(j - 1) = x; }
 }
-template <class S, class LT>
-__device__ __forceinline__ void ck_comb(const S &L, int a, int n, LT lt)
+template <int MAXCH, class LT>
+__device__ __forceinline__ void ck_comb(const StoreLds<MAXCH> &L, int a, int n, LT lt)
 {
 	const double shrink = 1.2473309501039786540366528676643;
 	int gap = n;
@@ -264,8 +134,8 @@ __device__ __forceinline__ void ck_comb(const S &L, int a, int n, LT lt)
 	} while (swapped || gap > 2);
 	if (gap != 1) ck_insertion(L, a, a + n, lt);
 }
-template <class S, class LT>
-__device__ __forceinline__ void ck_introsort(const S &L, int n, LT lt)
+template <int MAXCH, class LT>
+__device__ __forceinline__ void ck_introsort(const StoreLds<MAXCH> &L, int n, LT lt)
 {
 	if (n < 2) return;
 	if (n == 2) {
@@ -312,8 +182,8 @@ __device__ __forceinline__ void ck_introsort(const S &L, int n, LT lt)
 }
 
 // mem_chain + mem_chain_flt + emission for ONE read (one lane).  Returns the number of kept chains, or -1: host path.
-template <class S, class MAP>
-__device__ __forceinline__ int chain_read(const S &L, const ChainParams &P, int rd, int ns, int lq, i64 so, const int *__restrict__ l_rep,
+template <int MAXCH>
+__device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainParams &P, int rd, int ns, int lq, i64 so, const int *__restrict__ l_rep,
                                           const unsigned long long *__restrict__ sa, const int32_t *__restrict__ qbl, const i64 *__restrict__ ann_off,
                                           const uint8_t *__restrict__ ann_alt, int n_seqs, const int *__restrict__ gap, DevChain *__restrict__ chains,
                                           DevSeed *__restrict__ seeds, unsigned int *__restrict__ srt)
@@ -324,16 +194,12 @@ __device__ __forceinline__ int chain_read(const S &L, const ChainParams &P, int 
 	auto S_L = [&](int k) -> int { return qbl[2 * (so + k) + 1]; };
 	// the seeds of chain `id` in arrival order
 	auto members = [&](int id, auto fn) {
-		if constexpr (S::GENERAL) {
-			for (int k = (int)L.f(F_HEAD, id); k != 255; k = L.next(k)) fn(k);
-		} else {
-			for (int k = 0; k < ns; ++k)
-				if (L.cid(k) == id) fn(k);
-		}
+		for (int k = 0; k < ns; ++k)
+			if (L.cid(k) == id) fn(k);
 	};
 
 	// ---------------- mem_chain: seeds into the ordered map ----------------
-	MAP map;
+	MapArray<MAXCH> map;
 	int n_ch = 0;
 	i64 c_lo = 0, c_hi = -1;
 	int c_rid = -1;
@@ -375,7 +241,6 @@ __device__ __forceinline__ int chain_read(const S &L, const ChainParams &P, int 
 						L.f(F_LAST_Q, id) = (uint32_t)qb; L.f(F_LAST_LEN, id) = (uint32_t)len;
 						L.f(F_N, id) += 1;
 						L.cid(k) = (uint8_t)id;
-						if constexpr (S::GENERAL) { L.next((int)L.f(F_TAIL, id)) = (uint8_t)k; L.next(k) = 255; L.f(F_TAIL, id) = (uint32_t)k; }
 						merged = true;
 					}
 				}
@@ -383,19 +248,17 @@ __device__ __forceinline__ int chain_read(const S &L, const ChainParams &P, int 
 		}
 		if (merged) continue;
 		const int id = n_ch;
-		if (id >= S::MAXCH) return -1;
+		if (id >= MAXCH) return -1;
 		// (the record first: the map compares positions through it)
 		L.f(F_POS_LO, id) = (uint32_t)rb; L.f(F_POS_HI, id) = (uint32_t)((unsigned long long)rb >> 32);
 		L.f(F_FIRST_Q, id) = (uint32_t)qb;
 		L.f(F_LAST_R_LO, id) = (uint32_t)rb; L.f(F_LAST_R_HI, id) = (uint32_t)((unsigned long long)rb >> 32);
 		L.f(F_LAST_Q, id) = (uint32_t)qb; L.f(F_LAST_LEN, id) = (uint32_t)len;
 		L.f(F_RID, id) = (uint32_t)rid; L.f(F_N, id) = 1;
-		if constexpr (S::GENERAL) { L.f(F_HEAD, id) = L.f(F_TAIL, id) = (uint32_t)k; L.next(k) = 255; }
-		if (!map.put(L, id, rb)) return -1;   // more chains (or tree nodes) than this launch keeps: host path
+		if (!map.put(L, id, rb)) return -1;   // more chains than this launch keeps: a later launch, or the host path
 		L.cid(k) = (uint8_t)id;
 		++n_ch;
 	}
-	map.in_order(L);
 
 	// ---------------- mem_chain_flt ----------------
 	int n = 0;
@@ -556,12 +419,10 @@ chain_kernel(ChainParams P, int n_reads, const int *__restrict__ lens, const int
 	if (LO >= 0) { if (n_chains[rd] != -1 || ns <= LO) return; }
 	else if (ns == 0) { n_chains[rd] = 0; return; }
 	if (ns > MAXS || !noflt[lq]) { n_chains[rd] = -1; return; }
-	n_chains[rd] = chain_read<StoreLds<MAXCH>, MapArray>(L, P, rd, ns, lq, seed_off[rd], l_rep, sa, qbl, ann_off, ann_alt, n_seqs, gap, chains, seeds, srt);
+	n_chains[rd] = chain_read(L, P, rd, ns, lq, seed_off[rd], l_rep, sa, qbl, ann_off, ann_alt, n_seqs, gap, chains, seeds, srt);
 }
 
 // chain_pick_kernel lists the reads a later launch is for: declined so far (n_chains = -1), lo < seeds <= hi, at most cap of them.
-// Last launch: the reads all single-node launches declined (more than 9 chains) are chained with the reference's B-tree, a lane per
-// read, the working set in an HBM slice.
 __global__ void __launch_bounds__(256)
 chain_pick_kernel(int n_reads, const int *__restrict__ lens, const int *__restrict__ n_seeds, const int *__restrict__ n_chains,
                   const int *__restrict__ noflt, int lo, int hi, int cap, int *__restrict__ list, unsigned int *__restrict__ count)
@@ -576,28 +437,6 @@ chain_pick_kernel(int n_reads, const int *__restrict__ lens, const int *__restri
 	base = __shfl(base, lead);
 	const unsigned int at = base + (unsigned int)__popcll(m & ((1ull << lane) - 1));
 	if (mine && at < (unsigned int)cap) list[at] = rd;
-}
-
-__global__ void __launch_bounds__(64)
-chain_general_kernel(ChainParams P, const int *__restrict__ list, const unsigned int *__restrict__ count, int cap, const int *__restrict__ lens,
-                     const int *__restrict__ n_seeds, const int *__restrict__ l_rep, const i64 *__restrict__ seed_off,
-                     const unsigned long long *__restrict__ sa, const int32_t *__restrict__ qbl, const i64 *__restrict__ ann_off,
-                     const uint8_t *__restrict__ ann_alt, int n_seqs, const int *__restrict__ tab, uint8_t *__restrict__ scratch,
-                     DevChain *__restrict__ chains, DevSeed *__restrict__ seeds, unsigned int *__restrict__ srt, int *__restrict__ n_chains)
-{
-	const int t = blockIdx.x * 64 + threadIdx.x;
-	const int n_list = (int)(*count < (unsigned int)cap ? *count : (unsigned int)cap);
-	if (t >= n_list) return;
-	const int rd = list[t];
-	uint8_t *base = scratch + (size_t)t * CK_GEN_BYTES;
-	StoreGen L;
-	L.tab = (uint32_t *)base;
-	L.cid_ = base + (size_t)F_NFIELDS_GEN * CK_MAXCH_GEN * 4;
-	L.ord_ = L.cid_ + 256; L.tmp_ = L.ord_ + 256; L.next_ = L.tmp_ + 256;
-	L.nodes = (GenNode *)(L.next_ + 256);
-	const int r = chain_read<StoreGen, MapBtree>(L, P, rd, n_seeds[rd], lens[rd], seed_off[rd], l_rep, sa, qbl, ann_off, ann_alt, n_seqs, tab, chains,
-	                                              seeds, srt);
-	n_chains[rd] = r < 0 ? -2 : r;   // (-2: declined for good — the next round of this kernel must not pick the read again)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1068,23 +907,33 @@ void launch_reg_pack(void *stream, int n_reads, const int *d_reg_beg, const int 
 
 static size_t chain_lds_bytes(int maxs, int maxch) { return (size_t)F_NFIELDS * maxch * 64 * 4 + (size_t)(2 * (maxs + 1) + 16) * 64; }
 
-// scratch of launch_chain: [the B-tree kernel's slices for `cap` reads][its list][two retry lists][counters][two lists of reads with more
-// than 255 seeds][the slices of chain_heavy_kernel's persistent waves]
+// scratch of launch_chain: [two retry lists][counters][two lists of reads with more than 255 seeds][the slices of chain_heavy_kernel's
+// persistent waves]
 #define HV_WAVES_T 4096   // waves of the 256-seed instantiation (5.3 KB of LDS each): the reads with more than 9 chains
 #define HV_WAVES_S 1024   // ... of the 1024-seed instantiation (21 KB: 7 per CU)
 #define HV_WAVES_L 256    // ... of the 4096-seed one (84 KB: one per CU)
 static size_t heavy_scratch_bytes() { return HV_WAVES_T * hv_scratch_bytes(256) + HV_WAVES_S * hv_scratch_bytes(1024) + HV_WAVES_L * hv_scratch_bytes(4096); }
-size_t chain_general_bytes(int cap, int n_reads)
+size_t chain_scratch_bytes(int n_reads) { return (size_t)n_reads * 8 + 512 + (size_t)n_reads * 8 + 256 + heavy_scratch_bytes(); }
+
+// two side streams of a call's stream (created once per stream), with the events that fork them off it and join them back
+struct ChainSide { hipStream_t s[2]; hipEvent_t fork, join[2]; };
+static ChainSide chain_side_streams(hipStream_t st)
 {
-	return (size_t)cap * CK_GEN_BYTES + (size_t)cap * 4 + (size_t)n_reads * 8 + 512 + (size_t)n_reads * 8 + 256 + heavy_scratch_bytes();
+	static std::mutex side_mu;
+	static std::vector<std::pair<hipStream_t, ChainSide>> sides;
+	std::lock_guard<std::mutex> lk(side_mu);
+	for (auto &e : sides) if (e.first == st) return e.second;
+	ChainSide sd;
+	for (int k = 0; k < 2; ++k) { HIP_OK(hipStreamCreateWithFlags(&sd.s[k], hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(&sd.join[k], hipEventDisableTiming)); }
+	HIP_OK(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
+	sides.emplace_back(st, sd);
+	return sd;
 }
 
-// d_gen / gen_cap: scratch of chain_general_bytes(gen_cap) for the third launch (reads with more than 9 chains, up to 255
-// seeds and chains, at most gen_cap of them per call); null / 0: those reads keep n_chains = -1 (host path).
 void launch_chain(void *stream, const ChainParams &P, int n_reads, const int *d_len, const int *d_nseeds, const int *d_lrep,
                   const int64_t *d_seed_off, const uint64_t *d_sa, const int32_t *d_qbl, const int64_t *d_ann_off, const uint8_t *d_ann_alt,
                   int n_seqs, const int *d_tab, int tab_stride, DevChain *d_chains, DevSeed *d_seeds, unsigned int *d_srt, int *d_nchains,
-                  void *d_gen, int gen_cap)
+                  void *d_scratch)
 {
 	if (n_reads <= 0) return;
 	const size_t lds_s = chain_lds_bytes(CK_MAXSEEDS_SMALL, CK_MAXCH_SMALL), lds = chain_lds_bytes(CK_MAXSEEDS, CK_MAXCH), lds_big = chain_lds_bytes(CK_MAXSEEDS_BIG, CK_MAXCH);
@@ -1098,97 +947,59 @@ void launch_chain(void *stream, const ChainParams &P, int n_reads, const int *d_
 	const dim3 grid((n_reads + 63) / 64), block(64);
 #define CHAIN_ARGS P, n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs, d_tab, \
 	               tab_stride, d_chains, d_seeds, d_srt, d_nchains
-	const int big = getenv("MPIBWA_CHAIN_BIG") ? atoi(getenv("MPIBWA_CHAIN_BIG")) : 2;   // 0: up to 64 seeds only, 1: + 255 seeds, 2: + the B-tree kernel
-	const int *noflt = d_tab + 5 * tab_stride;
+	// chain_heavy_kernel<CAP> on stream `s`: the reads of `list` (`n` of them, handed out through `work`), the slices of its waves at `scr`
+#define LAUNCH_HEAVY(CAP, waves, s, list, n, work, scr)                                                                                                       \
+	hipLaunchKernelGGL((chain_heavy_kernel<CAP>), dim3(waves), dim3(64), hv_lds_bytes(CAP), s, P, (const int *)(list), (const unsigned int *)(n), work,      \
+	                   n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, \
+	                   n_seqs, d_tab, scr, d_chains, d_seeds, d_srt, d_nchains)
+	const int big = getenv("MPIBWA_CHAIN_BIG") ? atoi(getenv("MPIBWA_CHAIN_BIG")) : 2;   // 0: up to 64 seeds only, 1: + 255 seeds, 2: + a wavefront per read
+	int *list_a = (int *)d_scratch, *list_b = list_a + n_reads;
+	unsigned int *count = (unsigned int *)(list_b + n_reads);   // [0] more than 9 chains, [1] 64-seed retry, [2] 255-seed retry, [4], [6] heavy: list sizes; [3], [5], [7] work counters
+	int *list_h1 = (int *)((uint8_t *)count + 512), *list_h2 = list_h1 + n_reads;
+	uint8_t *scr_t = (uint8_t *)(((uintptr_t)(list_h2 + n_reads) + 255) & ~(uintptr_t)255);
+	uint8_t *scr_s = scr_t + HV_WAVES_T * hv_scratch_bytes(256), *scr_l = scr_s + HV_WAVES_S * hv_scratch_bytes(1024);
+	HIP_OK(hipMemsetAsync(count, 0, 64, st));
+	// the reads declined so far with lo < seeds <= hi, listed for the launch that takes them
+	auto pick = [&](int lo, int hi, int *list, unsigned int *n) {
+		hipLaunchKernelGGL(chain_pick_kernel, dim3((n_reads + 255) / 256), dim3(256), 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, d_tab + 5 * tab_stride, lo, hi,
+		                   n_reads, list, n);
+	};
 	hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS_SMALL, CK_MAXCH_SMALL, -1>), grid, block, lds_s, st, CHAIN_ARGS, (const int *)nullptr, (const unsigned int *)nullptr);
-	if (!d_gen || gen_cap <= 0) {   // no scratch for the lists: the retries look at every read
-		hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS, CK_MAXCH, 0>), grid, block, lds, st, CHAIN_ARGS, (const int *)nullptr, (const unsigned int *)nullptr);
-		if (big >= 1) hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS_BIG, CK_MAXCH, CK_MAXSEEDS>), grid, block, lds_big, st, CHAIN_ARGS, (const int *)nullptr, (const unsigned int *)nullptr);
-	} else {
-		uint8_t *scratch = (uint8_t *)d_gen;
-		int *list_g = (int *)(scratch + (size_t)gen_cap * CK_GEN_BYTES);
-		int *list_a = list_g + gen_cap, *list_b = list_a + n_reads;
-		unsigned int *count = (unsigned int *)(list_b + n_reads);   // [0] general, [1] 64-seed retry, [2] 255-seed retry, [4..7] heavy: list sizes and work counters
-		int *list_h1 = (int *)((uint8_t *)count + 512), *list_h2 = list_h1 + n_reads;
-		uint8_t *hv_scr = (uint8_t *)(((uintptr_t)(list_h2 + n_reads) + 255) & ~(uintptr_t)255);
-		HIP_OK(hipMemsetAsync(count, 0, 64, st));
-		const dim3 pgrid((n_reads + 255) / 256), pblock(256);
-		hipLaunchKernelGGL(chain_pick_kernel, pgrid, pblock, 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, noflt, 0, CK_MAXSEEDS, n_reads, list_a, count + 1);
-		hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS, CK_MAXCH, 0>), grid, block, lds, st, CHAIN_ARGS, (const int *)list_a, (const unsigned int *)(count + 1));
-		if (big >= 1) {
-			hipLaunchKernelGGL(chain_pick_kernel, pgrid, pblock, 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, noflt, CK_MAXSEEDS, CK_MAXSEEDS_BIG, n_reads, list_b,
-			                   count + 2);
-			hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS_BIG, CK_MAXCH, CK_MAXSEEDS>), grid, block, lds_big, st, CHAIN_ARGS, (const int *)list_b, (const unsigned int *)(count + 2));
-		}
-		static const bool use_general = getenv("MPIBWA_CHAIN_GENERAL") && atoi(getenv("MPIBWA_CHAIN_GENERAL")) != 0;
-		bool launch_t = false;
-		if (big >= 2 && !use_general) {
-			// the reads with more than 9 chains (up to 255 seeds): a wavefront per read with the B-tree in LDS (on a low-complexity
-			// reference a third of the reads are of this kind; a lane per read with the tree in HBM — chain_general_kernel, rounds 2-3 —
-			// took 51 ms per chunk there)
-			int *list_t = list_a;   // (the 64-seed retry is done with it)
-			hipLaunchKernelGGL(chain_pick_kernel, pgrid, pblock, 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, noflt, 0, CK_MAXSEEDS_BIG, n_reads, list_t, count);
-			launch_t = true;   // (launched below, next to the instantiations for more seeds)
-		}
-		if (big >= 2 && use_general) {
-			// the scratch holds gen_cap reads at a time: several rounds over it (on a low-complexity reference a third of the reads have
-			// more than 9 chains; a round that finds nothing left is two empty launches)
-			static const int rounds = getenv("MPIBWA_CHAIN_ROUNDS") ? std::max(1, atoi(getenv("MPIBWA_CHAIN_ROUNDS"))) : 4;
-			for (int r = 0; r < rounds; ++r) {
-				if (r) HIP_OK(hipMemsetAsync(count, 0, 4, st));
-				hipLaunchKernelGGL(chain_pick_kernel, pgrid, pblock, 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, noflt, 0, CK_MAXSEEDS_BIG, gen_cap, list_g, count);
-				hipLaunchKernelGGL(chain_general_kernel, dim3((gen_cap + 63) / 64), dim3(64), 0, st, P, (const int *)list_g, (const unsigned int *)count, gen_cap, d_len,
-				                   d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs,
-				                   d_tab, scratch, d_chains, d_seeds, d_srt, d_nchains);
-			}
-		}
-		if (big >= 2 && !(getenv("MPIBWA_CHAIN_HEAVY") && atoi(getenv("MPIBWA_CHAIN_HEAVY")) == 0)) {
-			// reads with more than 255 seeds (high-copy repeats): a wavefront per read, two LDS footprints
+	pick(0, CK_MAXSEEDS, list_a, count + 1);
+	hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS, CK_MAXCH, 0>), grid, block, lds, st, CHAIN_ARGS, (const int *)list_a, (const unsigned int *)(count + 1));
+	if (big >= 1) {
+		pick(CK_MAXSEEDS, CK_MAXSEEDS_BIG, list_b, count + 2);
+		hipLaunchKernelGGL((chain_kernel<CK_MAXSEEDS_BIG, CK_MAXCH, CK_MAXSEEDS>), grid, block, lds_big, st, CHAIN_ARGS, (const int *)list_b, (const unsigned int *)(count + 2));
+	}
+	if (big >= 2) {
+		// the reads with more than 9 chains (up to 255 seeds): a wavefront per read with the map in LDS (on a low-complexity reference a
+		// third of the reads are of this kind)
+		int *list_t = list_a;   // (the 64-seed retry is done with it)
+		pick(0, CK_MAXSEEDS_BIG, list_t, count);
+		// ... and the reads with more than 255 seeds (high-copy repeats), two more LDS footprints; MPIBWA_CHAIN_HEAVY=0 leaves those to the host
+		const bool heavy = !(getenv("MPIBWA_CHAIN_HEAVY") && atoi(getenv("MPIBWA_CHAIN_HEAVY")) == 0);
+		ChainSide sd = {};
+		if (heavy) {
 			static bool s_attr2 = false;
 			if (!s_attr2) {
 				HIP_OK(hipFuncSetAttribute((const void *)chain_heavy_kernel<4096>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv_lds_bytes(4096)));
 				s_attr2 = true;
 			}
-			uint8_t *scr_s = hv_scr + HV_WAVES_T * hv_scratch_bytes(256);
-			hipLaunchKernelGGL(chain_pick_kernel, pgrid, pblock, 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, noflt, CK_MAXSEEDS_BIG, 1024, n_reads, list_h1, count + 4);
-			hipLaunchKernelGGL(chain_pick_kernel, pgrid, pblock, 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, noflt, 1024, 4096, n_reads, list_h2, count + 6);
+			pick(CK_MAXSEEDS_BIG, 1024, list_h1, count + 4);
+			pick(1024, 4096, list_h2, count + 6);
 			// The instantiations are latency-bound launches of a few hundred to a few thousand waves each: side by side on two side streams
-			// of the call's stream (created once per stream) instead of one after the other — 23 -> 10 ms per sub-batch with one call in flight.
-			struct Side { hipStream_t s[2]; hipEvent_t fork, join[2]; };
-			static std::mutex side_mu;
-			static std::vector<std::pair<hipStream_t, Side>> sides;
-			Side sd;
-			{
-				std::lock_guard<std::mutex> lk(side_mu);
-				bool found = false;
-				for (auto &e : sides) if (e.first == st) { sd = e.second; found = true; break; }
-				if (!found) {
-					for (int k = 0; k < 2; ++k) { HIP_OK(hipStreamCreateWithFlags(&sd.s[k], hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(&sd.join[k], hipEventDisableTiming)); }
-					HIP_OK(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
-					sides.emplace_back(st, sd);
-				}
-			}
+			// of the call's stream instead of one after the other — 23 -> 10 ms per sub-batch with one call in flight.
+			sd = chain_side_streams(st);
 			HIP_OK(hipEventRecord(sd.fork, st));
 			for (int k = 0; k < 2; ++k) HIP_OK(hipStreamWaitEvent(sd.s[k], sd.fork, 0));
-			hipLaunchKernelGGL((chain_heavy_kernel<4096>), dim3(HV_WAVES_L), dim3(64), hv_lds_bytes(4096), sd.s[0], P, (const int *)list_h2, (const unsigned int *)(count + 6), count + 7,
-			                   n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs, d_tab,
-			                   scr_s + HV_WAVES_S * hv_scratch_bytes(1024), d_chains, d_seeds, d_srt, d_nchains);
-			hipLaunchKernelGGL((chain_heavy_kernel<1024>), dim3(HV_WAVES_S), dim3(64), hv_lds_bytes(1024), sd.s[1], P, (const int *)list_h1, (const unsigned int *)(count + 4), count + 5,
-			                   n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs, d_tab,
-			                   scr_s, d_chains, d_seeds, d_srt, d_nchains);
-			if (launch_t) {
-				hipLaunchKernelGGL((chain_heavy_kernel<256>), dim3(HV_WAVES_T), dim3(64), hv_lds_bytes(256), st, P, (const int *)list_a, (const unsigned int *)count, count + 3,
-				                   n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs, d_tab,
-				                   hv_scr, d_chains, d_seeds, d_srt, d_nchains);
-				launch_t = false;
-			}
-			for (int k = 0; k < 2; ++k) { HIP_OK(hipEventRecord(sd.join[k], sd.s[k])); HIP_OK(hipStreamWaitEvent(st, sd.join[k], 0)); }
+			LAUNCH_HEAVY(4096, HV_WAVES_L, sd.s[0], list_h2, count + 6, count + 7, scr_l);
+			LAUNCH_HEAVY(1024, HV_WAVES_S, sd.s[1], list_h1, count + 4, count + 5, scr_s);
 		}
-		if (launch_t)   // (MPIBWA_CHAIN_HEAVY=0: the 256-seed instantiation on its own)
-			hipLaunchKernelGGL((chain_heavy_kernel<256>), dim3(HV_WAVES_T), dim3(64), hv_lds_bytes(256), st, P, (const int *)list_a, (const unsigned int *)count, count + 3,
-			                   n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs, d_tab,
-			                   hv_scr, d_chains, d_seeds, d_srt, d_nchains);
+		LAUNCH_HEAVY(256, HV_WAVES_T, st, list_t, count, count + 3, scr_t);
+		if (heavy)
+			for (int k = 0; k < 2; ++k) { HIP_OK(hipEventRecord(sd.join[k], sd.s[k])); HIP_OK(hipStreamWaitEvent(st, sd.join[k], 0)); }
 	}
+#undef LAUNCH_HEAVY
 #undef CHAIN_ARGS
 	HIP_OK(hipGetLastError());
 }

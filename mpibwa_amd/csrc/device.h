@@ -187,14 +187,19 @@ struct ChainParams {
 	int w, max_chain_gap, min_chain_weight, min_seed_len, max_chain_extend;
 	float mask_level, drop_ratio;
 };
+ChainParams chain_params(const mem_opt_t *opt, int64_t l_pac);
+// the contig table of the chaining and pairing kernels: ann_off[k] = start of contig k, ann_off[n_seqs] = l_pac; ann_alt[k] = its ALT flag
+// (n_seqs + 1 entries each)
+void contig_table(const bntseq_t *bns, std::vector<int64_t> &ann_off, std::vector<uint8_t> &ann_alt);
 // Per read r: chains / seeds / order are written at index seed_off[r] onwards (a read never keeps more seeds or chains
-// than it had seeds); n_chains[r] = number of kept chains, or -1 when the read needs the host path (more than 9 chains,
-// more than 64 seeds, or long enough for mem_flt_chained_seeds).  d_tab: the length tables of c2a + row 5 = "flt is a no-op".
+// than it had seeds); n_chains[r] = number of kept chains, or < 0 when the read needs the host path (more than 4 096 seeds,
+// two chains at one position, or long enough for mem_flt_chained_seeds).  d_tab: the length tables of c2a (rows 0 and 5 are read:
+// the gap table and "flt is a no-op").  d_scratch: chain_scratch_bytes(n_reads) bytes (lists, counters, the persistent waves' slices).
 void launch_chain(void *stream, const ChainParams &P, int n_reads, const int *d_len, const int *d_nseeds, const int *d_lrep,
                   const int64_t *d_seed_off, const uint64_t *d_sa, const int32_t *d_qbl, const int64_t *d_ann_off, const uint8_t *d_ann_alt,
                   int n_seqs, const int *d_tab, int tab_stride, DevChain *d_chains, DevSeed *d_seeds, unsigned int *d_srt, int *d_nchains,
-                  void *d_gen = nullptr, int gen_cap = 0);
-size_t chain_general_bytes(int cap, int n_reads);   // scratch of launch_chain: the B-tree kernel's slices for `cap` reads + the retry lists
+                  void *d_scratch);
+size_t chain_scratch_bytes(int n_reads);
 
 size_t reg_pack_tmp_bytes(int n_reads);
 void launch_reg_pack(void *stream, int n_reads, const int *d_reg_beg, const int *d_nregs, int *d_reg_pos, const DevReg *d_regs, DevReg *d_packed,

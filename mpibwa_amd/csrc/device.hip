@@ -408,6 +408,21 @@ void c2a_params(const mem_opt_t *opt, int64_t l_pac, int early, C2aParams &cp, E
 	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
 }
 
+ChainParams chain_params(const mem_opt_t *opt, int64_t l_pac)
+{
+	ChainParams kp;
+	kp.l_pac = l_pac; kp.w = opt->w; kp.max_chain_gap = opt->max_chain_gap; kp.min_chain_weight = opt->min_chain_weight;
+	kp.min_seed_len = opt->min_seed_len; kp.max_chain_extend = opt->max_chain_extend; kp.mask_level = opt->mask_level; kp.drop_ratio = opt->drop_ratio;
+	return kp;
+}
+
+void contig_table(const bntseq_t *bns, std::vector<int64_t> &ann_off, std::vector<uint8_t> &ann_alt)
+{
+	ann_off.assign(bns->n_seqs + 1, bns->l_pac);
+	ann_alt.assign(bns->n_seqs + 1, 0);
+	for (int k = 0; k < bns->n_seqs; ++k) { ann_off[k] = bns->anns[k].offset; ann_alt[k] = bns->anns[k].is_alt ? 1 : 0; }
+}
+
 // band clamp of src/ksw.c:395-407 (host side, double arithmetic as in the reference)
 int clamp_band(const mem_opt_t *opt, int qlen, int w, int end_bonus)
 {
@@ -479,10 +494,9 @@ extern "C" int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, cons
 	if (!pair_params(opt, bns->l_pac, pes, n_processed, max_len, pp, &n_tab)) return -1;
 	std::vector<double> tab(n_tab + (size_t)pp.ltab_n);
 	pair_tables(opt, pes, pp, n_tab, tab.data());
-	std::vector<int64_t> ann_off(bns->n_seqs + 1);
-	std::vector<uint8_t> ann_alt(bns->n_seqs + 1, 0), ok((size_t)n_pairs, 1);
-	for (int k = 0; k < bns->n_seqs; ++k) { ann_off[k] = bns->anns[k].offset; ann_alt[k] = bns->anns[k].is_alt ? 1 : 0; }
-	ann_off[bns->n_seqs] = bns->l_pac;
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt, ok((size_t)n_pairs, 1);
+	contig_table(bns, ann_off, ann_alt);
 	const size_t n = (size_t)2 * n_pairs;
 	DevReg *d_first; int *d_nf; uint8_t *d_ok, *d_aa, *d_st; int64_t *d_ao; double *d_tab; AlnReq *d_rq; SamDesc *d_ds;
 	HIP_OK(hipMalloc(&d_first, n * PR_MAXREG * sizeof(DevReg))); HIP_OK(hipMalloc(&d_nf, n * 4)); HIP_OK(hipMalloc(&d_ok, n_pairs));
@@ -749,13 +763,8 @@ extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns,
 	int max_len = 0;
 	for (int i = 0; i < n_reads; ++i) max_len = std::max(max_len, lens[i]);
 	const int TS = max_len + 2;
-	std::vector<int> tab(6 * TS);
-	for (int l = 0; l < TS; ++l) {
-		tab[l] = cal_max_gap(opt, l);
-		tab[TS + l] = tab[2 * TS + l] = tab[3 * TS + l] = tab[4 * TS + l] = 0;
-		const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log(l > 0 ? l : 1);
-		tab[5 * TS + l] = (l > 0 && min_l > 0.05f * l) ? 1 : 0;
-	}
+	std::vector<int> tab;
+	c2a_length_tables(opt, max_len, tab);
 	std::vector<int> nseeds(n_reads);
 	for (int i = 0; i < n_reads; ++i) nseeds[i] = (int)(seed_off[i + 1] - seed_off[i]);
 	std::vector<int> nch(n_reads, 0);
@@ -764,10 +773,9 @@ extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns,
 	if (which == 0) {
 		int nd = 0;
 		if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
-		std::vector<int64_t> ann_off(bns->n_seqs + 1);
-		std::vector<uint8_t> ann_alt(bns->n_seqs + 1, 0);
-		for (int k = 0; k < bns->n_seqs; ++k) { ann_off[k] = bns->anns[k].offset; ann_alt[k] = bns->anns[k].is_alt ? 1 : 0; }
-		ann_off[bns->n_seqs] = bns->l_pac;
+		std::vector<int64_t> ann_off;
+		std::vector<uint8_t> ann_alt;
+		contig_table(bns, ann_off, ann_alt);
 		int *d_len, *d_ns, *d_lrep, *d_tab, *d_nch; int64_t *d_so, *d_ao; uint64_t *d_sa; int32_t *d_qbl; uint8_t *d_aa;
 		DevChain *d_ch; DevSeed *d_sd; unsigned int *d_srt;
 		HIP_OK(hipMalloc(&d_len, n_reads * 4 + 4)); HIP_OK(hipMalloc(&d_ns, n_reads * 4 + 4)); HIP_OK(hipMalloc(&d_lrep, n_reads * 4 + 4));
@@ -780,15 +788,11 @@ extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns,
 		HIP_OK(hipMemcpy(d_so, seed_off, (n_reads + 1) * 8, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_ao, ann_off.data(), ann_off.size() * 8, hipMemcpyHostToDevice));
 		HIP_OK(hipMemcpy(d_aa, ann_alt.data(), ann_alt.size(), hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_sa, rbeg, S * 8, hipMemcpyHostToDevice));
 		HIP_OK(hipMemcpy(d_qbl, qbeg_len, S * 8, hipMemcpyHostToDevice));
-		ChainParams kp;
-		kp.l_pac = bns->l_pac; kp.w = opt->w; kp.max_chain_gap = opt->max_chain_gap; kp.min_chain_weight = opt->min_chain_weight;
-		kp.min_seed_len = opt->min_seed_len; kp.max_chain_extend = opt->max_chain_extend; kp.mask_level = opt->mask_level; kp.drop_ratio = opt->drop_ratio;
-		void *d_gen = nullptr;
-		const int gen_cap = std::min(n_reads, 4096);
-		HIP_OK(hipMalloc(&d_gen, chain_general_bytes(gen_cap, n_reads)));
-		launch_chain(0, kp, n_reads, d_len, d_ns, d_lrep, d_so, d_sa, d_qbl, d_ao, d_aa, bns->n_seqs, d_tab, TS, d_ch, d_sd, d_srt, d_nch, d_gen, gen_cap);
+		void *d_scr = nullptr;
+		HIP_OK(hipMalloc(&d_scr, chain_scratch_bytes(n_reads)));
+		launch_chain(0, chain_params(opt, bns->l_pac), n_reads, d_len, d_ns, d_lrep, d_so, d_sa, d_qbl, d_ao, d_aa, bns->n_seqs, d_tab, TS, d_ch, d_sd, d_srt, d_nch, d_scr);
 		HIP_OK(hipDeviceSynchronize());
-		(void)hipFree(d_gen);
+		(void)hipFree(d_scr);
 		HIP_OK(hipMemcpy(nch.data(), d_nch, n_reads * 4, hipMemcpyDeviceToHost));
 		HIP_OK(hipMemcpy((void *)chains.data(), d_ch, S * sizeof(DevChain), hipMemcpyDeviceToHost));
 		HIP_OK(hipMemcpy((void *)seeds.data(), d_sd, S * sizeof(DevSeed), hipMemcpyDeviceToHost));

@@ -399,7 +399,7 @@ struct Workspace {
 	// (every copy to or from the device uses page-locked host memory: a pageable target makes hipMemcpyAsync wait — spinning —
 	// for the kernels queued before it, and a pageable source is pinned page by page at every call)
 	PinBuf h_cnt, h_off, h_len, h_seed_off, h_areq[2];
-	DevBuf nch, chain_cnt, reg_pos, regs_packed, ann_off, ann_alt, pack_tmp, order, chain_gen, c2a_stat;
+	DevBuf nch, chain_cnt, reg_pos, regs_packed, ann_off, ann_alt, pack_tmp, order, chain_scratch, c2a_stat;
 	PinBuf h_c2a_stat;
 	PinBuf h_order;
 	// reads with many chains, extended as independent groups of chains (c2a_groups.hip)
@@ -785,10 +785,9 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 	HIP_OK(hipStreamSynchronize(st));
 	stage(23);
 	// contig table for the chaining kernel: start of every contig (+ l_pac) and its ALT flag
-	std::vector<int64_t> ann_off(bns->n_seqs + 1);
-	std::vector<uint8_t> ann_alt(bns->n_seqs + 1, 0);
-	for (int k = 0; k < bns->n_seqs; ++k) { ann_off[k] = bns->anns[k].offset; ann_alt[k] = bns->anns[k].is_alt ? 1 : 0; }
-	ann_off[bns->n_seqs] = bns->l_pac;
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
 	int64_t *d_ann_off = (int64_t *)W.ann_off.ensure(ann_off.size() * 8);
 	uint8_t *d_ann_alt = (uint8_t *)W.ann_alt.ensure(ann_alt.size());
 	HIP_OK(hipMemcpyAsync(d_ann_off, ann_off.data(), ann_off.size() * 8, hipMemcpyHostToDevice, st));
@@ -1001,18 +1000,8 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 				d_seeds = (DevSeed *)W.seeds.ensure((size_t)2 * S * sizeof(DevSeed));
 				d_srt = (unsigned int *)W.srt.ensure((size_t)2 * S * 4);
 				int *d_nch = (int *)W.nch.ensure((size_t)n * 4);
-				ChainParams kp;
-				kp.l_pac = bns->l_pac; kp.w = opt->w; kp.max_chain_gap = opt->max_chain_gap; kp.min_chain_weight = opt->min_chain_weight;
-				kp.min_seed_len = opt->min_seed_len; kp.max_chain_extend = opt->max_chain_extend;
-				kp.mask_level = opt->mask_level; kp.drop_ratio = opt->drop_ratio;
-				// third launch (reads with more than 9 chains): room for a sixth of the reads, the rest of them stays with the host
-				// (MPIBWA_CHAIN_GENERAL=1: the reads with more than 9 chains through the lane-per-read B-tree kernel of rounds 2-3, which needs
-				// 18 KB of scratch per read: room for a sixth of the reads at a time)
-				static const bool use_general = getenv("MPIBWA_CHAIN_GENERAL") && atoi(getenv("MPIBWA_CHAIN_GENERAL")) != 0;
-				const int gen_cap = use_general ? std::min(n, std::max(4096, n / 6)) : std::min(n, 64);
-				void *d_gen = W.chain_gen.ensure(chain_general_bytes(gen_cap, n));
-				launch_chain(st, kp, n, d_len_r, d_nseeds, d_lrep, d_seed_off, d_sa, d_qbl, d_ann_off, d_ann_alt, bns->n_seqs, d_tab, TS, d_chains, d_seeds,
-				             d_srt, d_nch, d_gen, gen_cap);
+				launch_chain(st, chain_params(opt, bns->l_pac), n, d_len_r, d_nseeds, d_lrep, d_seed_off, d_sa, d_qbl, d_ann_off, d_ann_alt, bns->n_seqs, d_tab, TS, d_chains,
+				             d_seeds, d_srt, d_nch, W.chain_scratch.ensure(chain_scratch_bytes(n)));
 				nch = (int *)W.h_nch.ensure((size_t)n * 4 + 8);
 				HIP_OK(hipMemcpyAsync(nch, d_nch, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 			}
