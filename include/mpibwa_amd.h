@@ -313,6 +313,34 @@ int mi355x_pair_maxreg(void);
 int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], int64_t n_processed, int n_pairs,
                       const void *regs, const int *n_regs, int max_len, uint8_t *status, void *desc, void *req);
 
+/* SAM text of the pairs decided on the device: the CIGAR kernel (aln_kernel) and sam_emit_kernel, queued on one stream as the
+ * pipeline queues them, on chosen line descriptors.  2 n_pairs reads as nt4 codes (read r = reads[off[r] .. off[r+1])), their
+ * qualities at the same places (or NULL: QUAL is '*'), their names back to back (read r = names[name_off[r] .. name_off[r+1])); the
+ * read group is whatever bwa_set_rg() left in bwa_rg_id.  desc: 56 bytes per read (rb, re, qb, qe, req, rid, flag, mapq, score, sub,
+ * the layout mi355x_pair_batch returns; req = -3: a record of a pair without any hit, any other req < 0: not a record of the device,
+ * and then its mate's is not one either); reqs: the CIGAR requests (40 bytes each: rb, re, read, qb, qe, w2, truesc, pad), pair k owns
+ * reqs[req_base[k] .. req_base[k+1]) and desc.req counts from req_base[k].  arena_bytes: 0 = mi355x_sam_arena_bytes(2 n_pairs, longest
+ * read), the pipeline's own size; grid_blocks: 0 = the launcher's choice, otherwise a cap on the number of workgroups.
+ * out_len[r] >= 0: the record is arena_out[out_off[r] .. + out_len[r]); -1: handed back to the host (CIGAR declined, short fields
+ * beyond the staging row, arena full) together with its mate; -2: not a record of the device.  arena_out receives the arena and the
+ * 4096 guard bytes behind it, both filled with 0xA5 before the launch; *cursor the bytes the kernel claimed (it may exceed
+ * arena_bytes when waves were turned away); hdr_out the result headers of the requests (24 bytes each: score, NM, n_cigar, md_len,
+ * pool_off, flags). */
+size_t mi355x_sam_arena_bytes(int n_reads, int max_len);
+int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
+                     const uint8_t *quals, const char *names, const int *name_off, const void *desc, const void *reqs, const int *req_base,
+                     size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                     unsigned long long *cursor, void *hdr_out);
+
+/* Seed enumeration between SMEM and SA lookup (src/bwamem.c:161, 265-283): seed_prep_kernel (sort of a read's intervals by info,
+ * l_rep, number of seeds), the prefix sum over the counts, seed_enum_kernel (BWT row and (qbeg, len) of every seed, stepping through
+ * intervals larger than max_occ).  Read r has n_intv[r] intervals (x0, x1, size, info) from intv[4 * cap * r], in any order; with
+ * n_intv[r] > cap the first cap count.  intv comes back sorted; read r's seeds are rows / qbeg_len (2 ints per seed) from
+ * seed_off[r] (n_reads + 1 entries).  Returns the number of seeds, or -1 - that number when it exceeds seed_cap (rows and qbeg_len
+ * are then not written). */
+int64_t mi355x_seed_batch(int n_reads, int cap, int max_occ, uint64_t *intv, const int *n_intv, int *n_seeds, int *l_rep,
+                          int64_t *seed_off, uint64_t *rows, int32_t *qbeg_len, int64_t seed_cap);
+
 /* Mate-rescue local alignment: ksw_align2() exactly as mem_matesw() calls it (src/bwamem_pair.c:150-177,
  * src/ksw.c:321-356), for n_req windows [rb,re) of a 2-bit packed reference (doubled coordinate) against reads
  * given as nt4 codes (read r = reads[off[r]..off[r+1]) ).  out8 per request: score, te, qe, score2, te2, tb, qb

@@ -19,6 +19,7 @@ EXPORTS = [
     "mi355x_finalize", "mi355x_index_build", "mi355x_index_build_gpu",
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
+    "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_seed_batch",
 ]
 
 
@@ -113,6 +114,9 @@ def load_library(build_if_missing=True):
     sig("mi355x_pair_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("mi355x_global_batch", C.c_int, [P(abi.mem_opt_t), C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 +
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_double)])
+    sig("mi355x_sam_arena_bytes", C.c_size_t, [C.c_int, C.c_int])
+    sig("mi355x_sam_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
+    sig("mi355x_seed_batch", C.c_int64, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64])
     _LIB = lib
     return lib
 
@@ -381,6 +385,69 @@ class Engine:
         if rc != 0:
             raise RuntimeError("mi355x_pair_batch: the kernel cannot use these insert-size statistics")
         return status, desc, req
+
+    HDR_DT = np.dtype([("score", "<i4"), ("NM", "<i4"), ("n_cigar", "<i4"), ("md_len", "<i4"), ("pool_off", "<u4"), ("flags", "<i4")])
+    SAM_GUARD = 4096
+    SAM_GUARD_BYTE = 0xA5
+
+    def sam_records(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0):
+        """aln_kernel + sam_emit_kernel (mi355x_sam_batch) on chosen descriptors.  reads: 2 n_pairs nt4 code arrays; quals: as many byte
+        strings or None; names: one byte string per read; desc (2 n_pairs,) DESC_DT; reqs AREQ_DT; req_base (n_pairs + 1,).
+        -> dict: out_len, out_off, arena (arena_bytes of it), guard (the SAM_GUARD bytes behind it), arena_bytes, cursor, hdr (HDR_DT)"""
+        n = len(reads)
+        assert n % 2 == 0 and len(names) == n and len(desc) == n and len(req_base) == n // 2 + 1
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint8) for r in reads]))
+        fq = None
+        if quals is not None:
+            fq = np.frombuffer(b"".join(quals), dtype=np.uint8)
+            assert len(fq) == len(flat)
+        noff = np.zeros(n + 1, dtype=np.int32)
+        noff[1:] = np.cumsum([len(x) for x in names])
+        nm = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=self.DESC_DT)
+        reqs = np.ascontiguousarray(reqs, dtype=self.AREQ_DT)
+        req_base = np.ascontiguousarray(req_base, dtype=np.int32)
+        assert int(req_base[-1]) == len(reqs)
+        if not arena_bytes:
+            arena_bytes = int(self.lib.mi355x_sam_arena_bytes(n, max(len(r) for r in reads)))
+        out_len = np.zeros(n, dtype=np.int32)
+        out_off = np.zeros(n, dtype=np.uint64)
+        arena = np.zeros(arena_bytes + self.SAM_GUARD, dtype=np.uint8)
+        cursor = np.zeros(1, dtype=np.uint64)
+        hdr = np.zeros(max(len(reqs), 1), dtype=self.HDR_DT)
+        rc = self.lib.mi355x_sam_batch(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), n // 2, flat.ctypes.data, off.ctypes.data,
+                                       fq.ctypes.data if fq is not None else None, nm.ctypes.data, noff.ctypes.data, desc.ctypes.data,
+                                       reqs.ctypes.data if len(reqs) else None, req_base.ctypes.data, arena_bytes, int(grid_blocks), out_len.ctypes.data,
+                                       out_off.ctypes.data, arena.ctypes.data, cursor.ctypes.data, hdr.ctypes.data)
+        assert rc == 0
+        return {"out_len": out_len, "out_off": out_off, "arena": arena[:arena_bytes], "guard": arena[arena_bytes:], "arena_bytes": arena_bytes,
+                "cursor": int(cursor[0]), "hdr": hdr[:len(reqs)]}
+
+    def seeds(self, intervals, cap, max_occ):
+        """seed_prep_kernel + seed_enum_kernel (mi355x_seed_batch).  intervals: per read an (n_i, 4) uint64 array (x0, x1, size, info) in
+        any order; a read with more than cap reports its true count and hands over the first cap.
+        -> (sorted intervals per read, n_seeds, l_rep, per read (rows uint64 array, (n, 2) int32 array of qbeg, len))"""
+        n = len(intervals)
+        iv = np.zeros((n, cap, 4), dtype=np.uint64)
+        cnt = np.zeros(n, dtype=np.int32)
+        for r, a in enumerate(intervals):
+            a = np.asarray(a, dtype=np.uint64).reshape(-1, 4)
+            cnt[r] = len(a)
+            iv[r, :min(len(a), cap)] = a[:cap]
+        most = int(sum(min(int(s), max_occ) for r in range(n) for s in iv[r, :min(cnt[r], cap), 2]))
+        n_seeds = np.zeros(n, dtype=np.int32)
+        l_rep = np.zeros(n, dtype=np.int32)
+        seed_off = np.zeros(n + 1, dtype=np.int64)
+        rows = np.zeros(most + 1, dtype=np.uint64)
+        qbl = np.zeros((most + 1, 2), dtype=np.int32)
+        S = int(self.lib.mi355x_seed_batch(n, cap, max_occ, iv.ctypes.data, cnt.ctypes.data, n_seeds.ctypes.data, l_rep.ctypes.data,
+                                           seed_off.ctypes.data, rows.ctypes.data, qbl.ctypes.data, most))
+        if S < 0:
+            raise RuntimeError("mi355x_seed_batch: the kernel counts %d seeds, the intervals allow %d" % (-1 - S, most))
+        per = [(rows[seed_off[r]:seed_off[r + 1]].copy(), qbl[seed_off[r]:seed_off[r + 1]].copy()) for r in range(n)]
+        return [iv[r, :min(cnt[r], cap)].copy() for r in range(n)], n_seeds, l_rep, per
 
     def matesw(self, opt, l_pac, pac, reads, rb, re, read, is_rev):
         """mem_matesw's ksw_align2 for windows of `pac`; returns (n_req x 8 int32, kernel ms)."""

@@ -234,12 +234,15 @@ struct SamParams {
 	int has_qual, rg_len;
 	char rg[256];                // bwa_rg_id
 };
+size_t sam_arena_bytes(int n_reads, int max_len);   // the arena the pipeline gives n_reads records of reads of up to max_len bases
 // d_req_base[pair] = first CIGAR request of the pair in d_hdr; out_len[r] = bytes of the record at arena + out_off[r],
-// -1 = the host must format the pair, -2 = not a line of the device
+// -1 = the host must format the pair, -2 = not a line of the device.  grid_blocks > 0 caps the number of workgroups (stage tests:
+// the grid-stride loop with a few thousand reads); 0 = the launcher's own choice
 void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
                      const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
-                     uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len);
+                     uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
+                     int grid_blocks = 0);
 
 // ---- pairing decisions of the pairs with one plain hit per end (pair_kernel.hip) ----
 #define PR_MAXREG 8               // regions per read the kernel looks at (a read with more is the host's); 4 until round 4

@@ -1096,3 +1096,188 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	if (kernel_ms) *kernel_ms = ms;
 	return rc;
 }
+
+// Stage-level entry point of the SAM text kernel (tests): the CIGAR kernel and sam_emit_kernel on chosen line descriptors, queued on one
+// stream as the pipeline queues them for the pairs decided on the device (pipeline.hip: launch_dev).  Reads as nt4 codes in 16-byte
+// slots like the pipeline's, qualities (or none) at the same places, names back to back; the read group is bwa_rg_id.  The arena is
+// followed by SAM_GUARD bytes that no record may touch; arena and guard are filled with SAM_GUARD_BYTE before the launch.
+#define SAM_GUARD 4096
+#define SAM_GUARD_BYTE 0xA5
+extern "C" size_t mi355x_sam_arena_bytes(int n_reads, int max_len) { return sam_arena_bytes(n_reads, max_len); }
+extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
+                                const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_, const int *req_base,
+                                size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                                unsigned long long *cursor, void *hdr_out)
+{
+	using namespace mbw;
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
+	if (n_pairs <= 0) return 0;
+	hipStream_t st = 0;
+	const int n = 2 * n_pairs, n_req = req_base[n_pairs];
+	const int64_t l_pac = bns->l_pac;
+	const SamDesc *desc = (const SamDesc *)desc_;
+	const AlnReq *reqs = (const AlnReq *)reqs_;
+	std::vector<int64_t> slot(n + 1);
+	std::vector<int> lens(n);
+	int max_len = 0;
+	slot[0] = 0;
+	for (int i = 0; i < n; ++i) {
+		lens[i] = (int)(off[i + 1] - off[i]);
+		if (lens[i] <= 0 || name_off[i + 1] < name_off[i]) die("mi355x_sam_batch: bad read %d", i);
+		slot[i + 1] = slot[i] + ((lens[i] + 15) & ~15);
+		max_len = std::max(max_len, lens[i]);
+	}
+	// nothing the kernels index with may point outside what was uploaded
+	if (req_base[0] != 0 || n_req < 0) die("mi355x_sam_batch: bad req_base");
+	for (int k = 0; k < n_pairs; ++k) {
+		if (req_base[k + 1] < req_base[k]) die("mi355x_sam_batch: bad req_base at pair %d", k);
+		const SamDesc &a = desc[2 * k], &b = desc[2 * k + 1];
+		if ((a.req >= 0) != (b.req >= 0)) die("mi355x_sam_batch: pair %d has one record of the device's only", k);
+		for (int e = 0; e < 2; ++e) {
+			const SamDesc &d = desc[2 * k + e];
+			if (d.req < 0) continue;
+			const int q = req_base[k] + d.req;
+			if (q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != 2 * k + e) die("mi355x_sam_batch: bad descriptor %d", 2 * k + e);
+			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[2 * k + e] || d.qb > d.qe) die("mi355x_sam_batch: bad region %d", 2 * k + e);
+		}
+	}
+	for (int q = 0; q < n_req; ++q) {
+		const AlnReq &r = reqs[q];
+		if (r.read < 0) continue;
+		if (r.read >= n || r.rb < 0 || r.re > 2 * l_pac || r.rb > r.re || r.qb < 0 || r.qb > r.qe || r.qe > lens[r.read]) die("mi355x_sam_batch: bad request %d", q);
+	}
+	std::vector<uint8_t> flat(slot[n] + 16, 4), fq;
+	for (int i = 0; i < n; ++i) memcpy(flat.data() + slot[i], reads + off[i], (size_t)lens[i]);
+	if (quals) {
+		fq.assign(flat.size(), 0);
+		for (int i = 0; i < n; ++i) memcpy(fq.data() + slot[i], quals + off[i], (size_t)lens[i]);
+	}
+	std::vector<int> gaptab(max_len + 2);
+	for (int l = 0; l <= max_len + 1; ++l) {   // max_gap of bwa_gen_cigar2 (src/bwa.c:155-158), as pipeline.hip tabulates it
+		int max_ins = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_ins) / opt->e_ins + 1.);
+		int max_del = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_del) / opt->e_del + 1.);
+		int g = max_ins > max_del ? max_ins : max_del;
+		gaptab[l] = g > 1 ? g : 1;
+	}
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
+	std::vector<int> cno(bns->n_seqs + 1, 0);
+	for (int k = 0; k < bns->n_seqs; ++k) cno[k + 1] = cno[k] + (int)strlen(bns->anns[k].name);
+	std::vector<char> cn((size_t)cno[bns->n_seqs] + 1);
+	for (int k = 0; k < bns->n_seqs; ++k) memcpy(cn.data() + cno[k], bns->anns[k].name, (size_t)(cno[k + 1] - cno[k]));
+	SamParams sp;
+	sp.l_pac = l_pac; sp.has_qual = quals ? 1 : 0;
+	sp.rg_len = (int)strnlen(bwa_rg_id, sizeof bwa_rg_id);
+	memset(sp.rg, 0, sizeof sp.rg);
+	memcpy(sp.rg, bwa_rg_id, (size_t)sp.rg_len);
+	if (!arena_bytes) arena_bytes = sam_arena_bytes(n, max_len);
+	const size_t pool_bytes = (size_t)std::max(n_req, 1) * 96 + ((size_t)48 << 20);   // as launch_dev sizes it
+	const size_t n_names = (size_t)name_off[n];
+	uint8_t *d_seq, *d_qual = nullptr, *d_pac, *d_pool, *d_names, *d_arena; char *d_cn; int64_t *d_off, *d_ao; AlnReq *d_req; AlnHdr *d_hdr;
+	int *d_gap, *d_lists, *d_len, *d_noff, *d_cno, *d_base, *d_olen; unsigned long long *d_cnt, *d_used, *d_ooff; SamDesc *d_desc;
+	HIP_OK(hipMalloc(&d_seq, flat.size())); HIP_OK(hipMalloc(&d_pac, l_pac / 4 + 16)); HIP_OK(hipMalloc(&d_pool, pool_bytes));
+	if (quals) HIP_OK(hipMalloc(&d_qual, fq.size()));
+	HIP_OK(hipMalloc(&d_off, (size_t)(n + 1) * 8)); HIP_OK(hipMalloc(&d_len, (size_t)n * 4)); HIP_OK(hipMalloc(&d_req, (size_t)std::max(n_req, 1) * sizeof(AlnReq)));
+	HIP_OK(hipMalloc(&d_hdr, (size_t)std::max(n_req, 1) * sizeof(AlnHdr))); HIP_OK(hipMalloc(&d_gap, gaptab.size() * 4));
+	HIP_OK(hipMalloc(&d_lists, (size_t)std::max(n_req, 1) * 3 * 4)); HIP_OK(hipMalloc(&d_cnt, 256)); HIP_OK(hipMalloc(&d_used, 64));
+	HIP_OK(hipMalloc(&d_names, n_names + 64)); HIP_OK(hipMalloc(&d_noff, (size_t)(n + 1) * 4)); HIP_OK(hipMalloc(&d_cn, cn.size() + 64));
+	HIP_OK(hipMalloc(&d_cno, cno.size() * 4)); HIP_OK(hipMalloc(&d_ao, ann_off.size() * 8)); HIP_OK(hipMalloc(&d_base, (size_t)(n_pairs + 1) * 4));
+	HIP_OK(hipMalloc(&d_desc, (size_t)n * sizeof(SamDesc))); HIP_OK(hipMalloc(&d_arena, arena_bytes + SAM_GUARD));
+	HIP_OK(hipMalloc(&d_ooff, (size_t)n * 8)); HIP_OK(hipMalloc(&d_olen, (size_t)n * 4));
+	HIP_OK(hipMemcpy(d_seq, flat.data(), flat.size(), hipMemcpyHostToDevice));
+	if (quals) HIP_OK(hipMemcpy(d_qual, fq.data(), fq.size(), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_pac, pac, l_pac / 4 + 1, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_off, slot.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_len, lens.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+	if (n_req) HIP_OK(hipMemcpy(d_req, reqs, (size_t)n_req * sizeof(AlnReq), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_gap, gaptab.data(), gaptab.size() * 4, hipMemcpyHostToDevice));
+	if (n_names) HIP_OK(hipMemcpy(d_names, names, n_names, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_noff, name_off, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_cn, cn.data(), cn.size(), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_cno, cno.data(), cno.size() * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_ao, ann_off.data(), ann_off.size() * 8, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_base, req_base, (size_t)(n_pairs + 1) * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_desc, desc, (size_t)n * sizeof(SamDesc), hipMemcpyHostToDevice));
+	HIP_OK(hipMemset(d_hdr, 0, (size_t)std::max(n_req, 1) * sizeof(AlnHdr)));
+	HIP_OK(hipMemset(d_arena, SAM_GUARD_BYTE, arena_bytes + SAM_GUARD));
+	HIP_OK(hipMemset(d_ooff, 0, (size_t)n * 8));
+	HIP_OK(hipMemset(d_olen, 0xff, (size_t)n * 4));
+	HIP_OK(hipMemsetAsync(d_cnt, 0, 256, st));
+	HIP_OK(hipMemsetAsync(d_used, 0, 64, st));
+	AlnParams ap;
+	ap.l_pac = l_pac; ap.a = opt->a; ap.w = opt->w;
+	ExtParams ep;
+	memcpy(ep.mat, opt->mat, 25);
+	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
+	if (n_req) launch_aln(st, ap, ep, n_req, d_req, d_seq, d_off, d_pac, d_gap, d_hdr, d_pool, d_cnt, pool_bytes, max_len, max_len + 256, d_lists);
+	launch_sam_emit(st, sp, n, d_desc, d_base, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_noff, d_ao, d_cn, d_cno, d_arena, arena_bytes, d_used,
+	                d_ooff, d_olen, grid_blocks);
+	HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipMemcpy(out_len, d_olen, (size_t)n * 4, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(out_off, d_ooff, (size_t)n * 8, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(arena_out, d_arena, arena_bytes + SAM_GUARD, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(cursor, d_used, 8, hipMemcpyDeviceToHost));
+	if (n_req) HIP_OK(hipMemcpy(hdr_out, d_hdr, (size_t)n_req * sizeof(AlnHdr), hipMemcpyDeviceToHost));
+	(void)hipFree(d_seq); (void)hipFree(d_qual); (void)hipFree(d_pac); (void)hipFree(d_pool); (void)hipFree(d_off); (void)hipFree(d_len); (void)hipFree(d_req);
+	(void)hipFree(d_hdr); (void)hipFree(d_gap); (void)hipFree(d_lists); (void)hipFree(d_cnt); (void)hipFree(d_used); (void)hipFree(d_names); (void)hipFree(d_noff);
+	(void)hipFree(d_cn); (void)hipFree(d_cno); (void)hipFree(d_ao); (void)hipFree(d_base); (void)hipFree(d_desc); (void)hipFree(d_arena); (void)hipFree(d_ooff);
+	(void)hipFree(d_olen);
+	return 0;
+}
+
+// Stage-level entry point of the seed enumeration between SMEM and SA lookup (tests): seed_prep_kernel, the pipeline's prefix sum over
+// the seed counts, seed_enum_kernel, on chosen intervals (read r: n_intv[r] records of (x0, x1, size, info) from intv[r * cap * 4], in any
+// order; n_intv[r] > cap: the kernels look at the first cap).  intv comes back sorted by info; rows / qbeg_len: per seed the BWT row
+// and (qbeg, len), read r from seed_off[r].  Returns the number of seeds, or -1 - that number when it exceeds seed_cap (then only
+// n_seeds, l_rep and seed_off are valid).
+extern "C" int64_t mi355x_seed_batch(int n_reads, int cap, int max_occ, uint64_t *intv, const int *n_intv, int *n_seeds, int *l_rep,
+                                     int64_t *seed_off, uint64_t *rows, int32_t *qbeg_len, int64_t seed_cap)
+{
+	using namespace mbw;
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
+	if (n_reads <= 0) return 0;
+	if (cap <= 0 || max_occ <= 0) die("mi355x_seed_batch: cap and max_occ must be positive");
+	hipStream_t st = 0;
+	const size_t n_words = (size_t)n_reads * cap * 4;
+	uint64_t *d_intv, *d_rows = nullptr; int *d_nintv, *d_ns, *d_lrep; int64_t *d_so; int32_t *d_qbl = nullptr;
+	HIP_OK(hipMalloc(&d_intv, n_words * 8)); HIP_OK(hipMalloc(&d_nintv, (size_t)n_reads * 4)); HIP_OK(hipMalloc(&d_ns, (size_t)n_reads * 4));
+	HIP_OK(hipMalloc(&d_lrep, (size_t)n_reads * 4)); HIP_OK(hipMalloc(&d_so, (size_t)(n_reads + 1) * 8));
+	HIP_OK(hipMemcpy(d_intv, intv, n_words * 8, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_nintv, n_intv, (size_t)n_reads * 4, hipMemcpyHostToDevice));
+	launch_seed_prep(st, n_reads, cap, d_intv, d_nintv, max_occ, d_ns, d_lrep);
+	HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipMemcpy(n_seeds, d_ns, (size_t)n_reads * 4, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(l_rep, d_lrep, (size_t)n_reads * 4, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(intv, d_intv, n_words * 8, hipMemcpyDeviceToHost));
+	seed_off[0] = 0;
+	for (int i = 0; i < n_reads; ++i) seed_off[i + 1] = seed_off[i] + n_seeds[i];
+	const int64_t S = seed_off[n_reads];
+	// the device buffers hold what the intervals themselves allow (min(size, max_occ) + 1 rows each), wherever the counts of
+	// seed_prep_kernel put a read: counts that are too small show as seeds of one read over those of the next, never as a write outside
+	const bool fits = S <= seed_cap;
+	int64_t room = S;
+	for (int i = 0; i < n_reads; ++i) {
+		if (n_seeds[i] < 0) die("mi355x_seed_batch: read %d counts %d seeds", i, n_seeds[i]);
+		int64_t most = 0;
+		const int m = std::min(n_intv[i], cap);
+		for (int k = 0; k < m; ++k) most += (int64_t)std::min<uint64_t>(intv[((size_t)i * cap + k) * 4 + 2], (uint64_t)max_occ) + 1;
+		room = std::max(room, seed_off[i] + most);
+	}
+	if (fits && S > 0) {
+		HIP_OK(hipMalloc(&d_rows, (size_t)room * 8)); HIP_OK(hipMalloc(&d_qbl, (size_t)room * 8));
+		HIP_OK(hipMemset(d_rows, 0xff, (size_t)room * 8)); HIP_OK(hipMemset(d_qbl, 0xff, (size_t)room * 8));
+		HIP_OK(hipMemcpy(d_so, seed_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice));
+		launch_seed_enum(st, n_reads, cap, d_intv, d_nintv, max_occ, d_so, d_rows, d_qbl);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		HIP_OK(hipMemcpy(rows, d_rows, (size_t)S * 8, hipMemcpyDeviceToHost));
+		HIP_OK(hipMemcpy(qbeg_len, d_qbl, (size_t)S * 8, hipMemcpyDeviceToHost));
+	}
+	(void)hipFree(d_intv); (void)hipFree(d_nintv); (void)hipFree(d_ns); (void)hipFree(d_lrep); (void)hipFree(d_so); (void)hipFree(d_rows); (void)hipFree(d_qbl);
+	return fits ? S : -1 - S;
+}

@@ -1599,7 +1599,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		int *hb = (int *)WS.hj_base[slot].ensure((size_t)(nu + 1) * 4 + 64);
 		for (int k = 0; k <= nu; ++k) hb[k] = 2 * k;
 		int *d_base = (int *)WS.dj_base[slot].ensure((size_t)(nu + 1) * 4);
-		J.arena_bytes = (size_t)nr * (size_t)(2 * max_len + 320) + (1 << 20);
+		J.arena_bytes = sam_arena_bytes(nr, max_len);
 		uint8_t *d_arena = (uint8_t *)WS.dj_arena[slot].ensure(J.arena_bytes);
 		unsigned long long *d_used = (unsigned long long *)WS.dj_used[slot].ensure(64);
 		unsigned long long *d_ooff = (unsigned long long *)WS.dj_ooff[slot].ensure((size_t)nr * 8);
@@ -1680,7 +1680,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 			int *hb = (int *)WS.h_sbase[slot].ensure((size_t)(nu + 1) * 4 + 64);
 			for (int k = 0; k <= nu; ++k) hb[k] = (int)P.base[k];
 			int *d_base = (int *)WS.sbase[slot].ensure((size_t)(nu + 1) * 4);
-			P.arena_bytes = (size_t)nr * (size_t)(2 * max_len + 320) + (1 << 20);
+			P.arena_bytes = sam_arena_bytes(nr, max_len);
 			uint8_t *d_arena = (uint8_t *)WS.sarena[slot].ensure(P.arena_bytes);
 			unsigned long long *d_used = (unsigned long long *)WS.sused[slot].ensure(64);
 			unsigned long long *d_ooff = (unsigned long long *)WS.sooff[slot].ensure((size_t)nr * 8);

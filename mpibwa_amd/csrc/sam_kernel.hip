@@ -209,6 +209,9 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 				}
 			}
 		}
+		// a pair goes back as a whole: the two rows of a pair need not overflow together (other POS, TLEN sign, NM), and the host
+		// formats both records as soon as one is missing (reads 2k and 2k + 1 are neighbouring lanes)
+		if (__shfl_xor(status, 1) == -1 && status >= 0) { status = -1; total = 0; }
 		// place the wave's records back to back: exclusive prefix sum of the lengths, one atomic
 		int incl = total;
 		for (int d = 1; d < 64; d <<= 1) {
@@ -268,14 +271,23 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 	}
 }
 
+// Room for the records of n_reads reads: SEQ + QUAL + 320 bytes for everything else, and a megabyte.  Names, contig names, MD
+// and a read group can add up to more; a wave whose records do not fit any more hands them back to the host (status -1).
+size_t sam_arena_bytes(int n_reads, int max_len)
+{
+	return (size_t)n_reads * (size_t)(2 * max_len + 320) + (1 << 20);
+}
+
 void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
                      const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
-                     uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len)
+                     uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
+                     int grid_blocks)
 {
 	if (n_reads <= 0) return;
 	const int n_batch = (n_reads + 63) >> 6;
 	int blocks = n_batch < 256 * 8 ? n_batch : 256 * 8;   // 16.6 KB of LDS per wave: nine waves per CU
+	if (grid_blocks > 0 && grid_blocks < blocks) blocks = grid_blocks;
 	hipLaunchKernelGGL(sam_emit_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, P, n_reads, d_desc, d_req_base, d_hdr, d_pool, d_seq, d_off,
 	                   d_len, d_qual, d_names, d_name_off, (const long long *)d_ann_off, d_ann_names, d_ann_name_off, d_arena,
 	                   (unsigned long long)arena_bytes, d_arena_used, d_out_off, d_out_len);

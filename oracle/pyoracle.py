@@ -271,6 +271,64 @@ class RefIndex:
                 break
         return res
 
+    def set_rg(self, line):
+        """the reference's own bwa_set_rg (None: no read group); the ID it kept"""
+        return set_rg(self.lib, line)
+
+    def pair_records(self, opt, reads, quals, names, regs, flags, mapqs):
+        """The two records of every pair as mem_sam_pe writes them, by the reference's own mem_reg2aln and mem_aln2sam called the way its
+        paired branch calls them (src/bwamem_pair.c:339-358): h[i] = mem_reg2aln(region), h[i].mapq = q, h[i].flag |= 0x40 << i | extra,
+        mem_aln2sam(.., &s[i], 1, &h[i], 0, &h[!i]).  A pair whose first region has rb < 0 is a pair without any hit, written as the
+        no_pairing tail writes it (:371-389): mem_reg2aln on a null region, then mem_reg2sam on an empty region list with 0x41 / 0x81.
+        reads: 2 n nt4 code arrays; quals: byte strings or None; names: one per read; regs: (2 n,) ALNREG_DT; flags: the extra flag per
+        read; mapqs per read.  -> list of 2 n byte strings"""
+        lib = self.lib
+        P = C.POINTER
+        lib.mem_reg2aln.restype = mem_aln_t
+        lib.mem_reg2aln.argtypes = [P(abi.mem_opt_t), P(abi.bntseq_t), P(C.c_uint8), C.c_int, C.c_void_p, C.c_void_p]
+        lib.mem_aln2sam.restype = None
+        lib.mem_aln2sam.argtypes = [P(abi.mem_opt_t), P(abi.bntseq_t), P(_kstring), P(abi.bseq1_t), C.c_int, P(mem_aln_t), C.c_int, P(mem_aln_t)]
+        lib.mem_reg2sam.restype = None
+        lib.mem_reg2sam.argtypes = [P(abi.mem_opt_t), P(abi.bntseq_t), P(C.c_uint8), P(abi.bseq1_t), P(_alnreg_v), C.c_int, P(mem_aln_t)]
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        n = len(reads)
+        assert n % 2 == 0 and len(regs) == n and len(names) == n
+        out = []
+        for k in range(0, n, 2):
+            s = (abi.bseq1_t * 2)()
+            keep = []
+            for i in range(2):
+                sq = np.ascontiguousarray(reads[k + i], dtype=np.uint8)
+                nm = C.create_string_buffer(bytes(names[k + i]))
+                ql = C.create_string_buffer(bytes(quals[k + i])) if quals is not None else None
+                keep += [sq, nm, ql]
+                s[i].l_seq = len(sq)
+                s[i].name = C.addressof(nm)
+                s[i].seq = sq.ctypes.data
+                s[i].qual = C.addressof(ql) if ql is not None else None
+            h = (mem_aln_t * 2)()
+            if regs[k]["rb"] < 0:
+                for i in range(2):
+                    h[i] = lib.mem_reg2aln(opt, self.bns, self.pac, s[i].l_seq, s[i].seq, None)
+                none = _alnreg_v()
+                for i in range(2):
+                    lib.mem_reg2sam(opt, self.bns, self.pac, C.byref(s[i]), C.byref(none), (0x41, 0x81)[i], C.byref(h[1 - i]))
+                    out.append(C.string_at(s[i].sam))
+                    libc.free(C.c_void_p(s[i].sam))
+                continue
+            for i in range(2):
+                h[i] = lib.mem_reg2aln(opt, self.bns, self.pac, s[i].l_seq, s[i].seq, regs[k + i:k + i + 1].ctypes.data)
+                h[i].set_mapq(mapqs[k + i])
+                h[i].flag |= (0x40 << i) | int(flags[k + i])
+            for i in range(2):
+                ks = _kstring()
+                lib.mem_aln2sam(opt, self.bns, C.byref(ks), C.byref(s[i]), 1, C.byref(h[i]), 0, C.byref(h[1 - i]))
+                out.append(C.string_at(ks.s, ks.l))
+                libc.free(C.c_void_p(ks.s))
+            for i in range(2):
+                libc.free(C.c_void_p(h[i].cigar))
+        return out
+
 
 _inj = None
 
@@ -348,3 +406,45 @@ def ref_chains(opt, bns, read_len, intervals, do_flt=True):
         res.append((rid, w, kept, is_alt, fb, [tuple(int(x) for x in out[p + 3 * j:p + 3 * j + 3]) for j in range(ns)]))
         p += 3 * ns
     return res
+
+
+# ---------------------------------------------------------------------------
+# the reference's record writers on chosen regions (the checker of mi355x_sam_batch)
+# ---------------------------------------------------------------------------
+def set_rg(lib, line):
+    """bwa_set_rg of `lib` (the reference's or the product's) on an @RG line with escaped tabs; None clears the read group.  -> the ID kept"""
+    rg = (C.c_char * 256).in_dll(lib, "bwa_rg_id")
+    C.memset(rg, 0, 256)
+    if line is None:
+        return b""
+    lib.bwa_set_rg.restype = C.c_void_p
+    lib.bwa_set_rg.argtypes = [C.c_char_p]
+    p = lib.bwa_set_rg(line if isinstance(line, bytes) else line.encode())
+    assert p, "bwa_set_rg rejects this @RG line"
+    libc.free(C.c_void_p(p))
+    return bytes(rg.raw).split(b"\0")[0]
+
+
+class mem_aln_t(C.Structure):
+    """src/bwamem.h:87-98; `bits` is the bit-field word is_rev:1, is_alt:1, mapq:8, NM:22 (read and written through the helpers below:
+    a structure with bit-fields is not passed by value)"""
+    _fields_ = [("pos", C.c_int64), ("rid", C.c_int), ("flag", C.c_int), ("bits", C.c_uint32), ("n_cigar", C.c_int), ("cigar", C.c_void_p),
+                ("XA", C.c_void_p), ("score", C.c_int), ("sub", C.c_int), ("alt_sc", C.c_int)]
+
+    def set_mapq(self, q):
+        self.bits = (self.bits & ~(0xff << 2)) | ((int(q) & 0xff) << 2)
+
+    is_rev = property(lambda self: self.bits & 1)
+    mapq = property(lambda self: (self.bits >> 2) & 0xff)
+    NM = property(lambda self: self.bits >> 10)
+
+
+assert C.sizeof(mem_aln_t) == 56
+
+
+class _kstring(C.Structure):
+    _fields_ = [("l", C.c_size_t), ("m", C.c_size_t), ("s", C.c_void_p)]
+
+
+class _alnreg_v(C.Structure):
+    _fields_ = [("n", C.c_size_t), ("m", C.c_size_t), ("a", C.c_void_p)]

@@ -11,6 +11,7 @@ import pytest
 
 from mpibwa_amd import abi
 from oracle import pyoracle as po
+from ref_band import infer_bw as _infer_bw
 
 
 def _pes(specs):
@@ -20,13 +21,6 @@ def _pes(specs):
     for d, (low, high, avg, std) in specs.items():
         pes[d].failed = 0; pes[d].low = low; pes[d].high = high; pes[d].avg = avg; pes[d].std = std
     return pes
-
-
-def _infer_bw(l1, l2, score, a, q, r):   # src/bwamem.c:792-800
-    if l1 == l2 and l1 * a - score < (q + r - a) << 1:
-        return 0
-    w = int(float((l1 if l1 < l2 else l2) * a - score - q) / r + 2.)
-    return max(w, abs(l1 - l2))
 
 
 # (with more than one orientation alive mem_matesw always finds one that no mate hit explains and aligns: src/bwamem_pair.c:118-128 —
