@@ -332,6 +332,27 @@ int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *p
                      size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
                      unsigned long long *cursor, void *hdr_out);
 
+/* Decisions of the single-end branch of worker2 (src/bwamem.c:1187-1196: mem_mark_primary_se with id = n_processed + i, the walk of
+ * mem_reg2sam :1003-1049, mem_approx_mapq_se :952-976, with mem_sort_dedup_patch :437-489 and the XA test of src/bwamem_extra.c:91-110)
+ * for n_reads reads given by their regions as phase 1 leaves them (regs, n_regs, desc, req: the layouts of mi355x_pair_batch, one
+ * descriptor and one request per read), computed by se_simple_kernel.  status[i] = 1: the read is decided and ends in one record —
+ * desc[i].req = 0 and req[i] describe its line (flag without the strand bit), or desc[i].req = -3: the unmapped record (flag 4, no
+ * request).  Any other value: the kernel leaves the read to the library's host path; the value names the test that said so
+ * (0 not looked at, 2 comment column, 3 more than mi355x_pair_maxreg() regions, 4 two regions to patch, 5 region longer than the
+ * per-length table, 6 region on an ALT contig, 10 second primary region: supplementary line, 11 a secondary region with an XA entry).
+ * Returns 0. */
+int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_reads, const void *regs, const int *n_regs,
+                    int max_len, uint8_t *status, void *desc, void *req);
+
+/* mi355x_sam_batch's twin for single-end descriptors (the single-end instantiation of sam_emit_kernel): n_reads reads, read i owns
+ * reqs[req_base[i] .. req_base[i+1]) (req_base: n_reads + 1 entries) and there is no mate: RNEXT PNEXT TLEN are "* 0 0", no MC tag,
+ * FLAG is desc.flag | 0x10 on the reverse strand; a read is handed back (-1) alone.  Everything else — arena, guard, cursor,
+ * grid_blocks, hdr_out — as above. */
+int mi355x_sam_se_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
+                        const uint8_t *quals, const char *names, const int *name_off, const void *desc, const void *reqs, const int *req_base,
+                        size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                        unsigned long long *cursor, void *hdr_out);
+
 /* Seed enumeration between SMEM and SA lookup (src/bwamem.c:161, 265-283): seed_prep_kernel (sort of a read's intervals by info,
  * l_rep, number of seeds), the prefix sum over the counts, seed_enum_kernel (BWT row and (qbeg, len) of every seed, stepping through
  * intervals larger than max_occ).  Read r has n_intv[r] intervals (x0, x1, size, info) from intv[4 * cap * r], in any order; with
@@ -381,6 +402,7 @@ typedef struct {
 	uint64_t smem_tab_bytes;                     /* the part of smem_bytes (64 B per occ block) that the third pass took from its jump table instead of fetching */
 	uint64_t n_sam_dev;                          /* SAM records written by sam_kernel (the rest are formatted by the host) */
 	uint64_t n_pair_dev;                         /* pairs whose pairing decisions (mem_sam_pe) were taken on the device (pair_kernel.hip) */
+	uint64_t n_se_dev;                           /* single-end reads decided on the device (se_kernel.hip); their records count in n_sam_dev */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

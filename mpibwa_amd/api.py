@@ -19,7 +19,7 @@ EXPORTS = [
     "mi355x_finalize", "mi355x_index_build", "mi355x_index_build_gpu",
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
-    "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_seed_batch",
+    "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch",
 ]
 
 
@@ -116,6 +116,8 @@ def load_library(build_if_missing=True):
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_double)])
     sig("mi355x_sam_arena_bytes", C.c_size_t, [C.c_int, C.c_int])
     sig("mi355x_sam_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
+    sig("mi355x_sam_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
+    sig("mi355x_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("mi355x_seed_batch", C.c_int64, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64])
     _LIB = lib
     return lib
@@ -386,16 +388,36 @@ class Engine:
             raise RuntimeError("mi355x_pair_batch: the kernel cannot use these insert-size statistics")
         return status, desc, req
 
+    def singles(self, opt, regs, n_regs, max_len=150, n_processed=0):
+        """se_simple_kernel on single-end reads given by their regions: regs (n_reads, mi355x_pair_maxreg()) of REG_DT, n_regs (n_reads).
+        -> status (n_reads,) uint8, desc (n_reads,) DESC_DT, req (n_reads,) AREQ_DT"""
+        regs = np.ascontiguousarray(regs, dtype=self.REG_DT)
+        assert regs.shape[1] == self.lib.mi355x_pair_maxreg()
+        n_regs = np.ascontiguousarray(n_regs, dtype=np.int32)
+        n = len(n_regs)
+        assert regs.shape[0] == n
+        status = np.zeros(n, dtype=np.uint8)
+        desc = np.zeros(n, dtype=self.DESC_DT)
+        req = np.zeros(n, dtype=self.AREQ_DT)
+        rc = self.lib.mi355x_se_batch(opt, C.cast(self.bns, C.c_void_p), n_processed, n, regs.ctypes.data, n_regs.ctypes.data, max_len,
+                                      status.ctypes.data, desc.ctypes.data, req.ctypes.data)
+        assert rc == 0
+        return status, desc, req
+
     HDR_DT = np.dtype([("score", "<i4"), ("NM", "<i4"), ("n_cigar", "<i4"), ("md_len", "<i4"), ("pool_off", "<u4"), ("flags", "<i4")])
     SAM_GUARD = 4096
     SAM_GUARD_BYTE = 0xA5
 
-    def sam_records(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0):
+    def sam_records_se(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0):
+        """sam_records for single-end descriptors (mi355x_sam_se_batch): n_reads reads, desc (n_reads,), req_base (n_reads + 1,)."""
+        return self.sam_records(opt, reads, quals, names, desc, reqs, req_base, arena_bytes, grid_blocks, ends=1)
+
+    def sam_records(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0, ends=2):
         """aln_kernel + sam_emit_kernel (mi355x_sam_batch) on chosen descriptors.  reads: 2 n_pairs nt4 code arrays; quals: as many byte
         strings or None; names: one byte string per read; desc (2 n_pairs,) DESC_DT; reqs AREQ_DT; req_base (n_pairs + 1,).
         -> dict: out_len, out_off, arena (arena_bytes of it), guard (the SAM_GUARD bytes behind it), arena_bytes, cursor, hdr (HDR_DT)"""
         n = len(reads)
-        assert n % 2 == 0 and len(names) == n and len(desc) == n and len(req_base) == n // 2 + 1
+        assert n % ends == 0 and len(names) == n and len(desc) == n and len(req_base) == n // ends + 1
         off = np.zeros(n + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(r) for r in reads])
         flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint8) for r in reads]))
@@ -417,7 +439,8 @@ class Engine:
         arena = np.zeros(arena_bytes + self.SAM_GUARD, dtype=np.uint8)
         cursor = np.zeros(1, dtype=np.uint64)
         hdr = np.zeros(max(len(reqs), 1), dtype=self.HDR_DT)
-        rc = self.lib.mi355x_sam_batch(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), n // 2, flat.ctypes.data, off.ctypes.data,
+        fn = self.lib.mi355x_sam_batch if ends == 2 else self.lib.mi355x_sam_se_batch
+        rc = fn(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), n // ends, flat.ctypes.data, off.ctypes.data,
                                        fq.ctypes.data if fq is not None else None, nm.ctypes.data, noff.ctypes.data, desc.ctypes.data,
                                        reqs.ctypes.data if len(reqs) else None, req_base.ctypes.data, arena_bytes, int(grid_blocks), out_len.ctypes.data,
                                        out_off.ctypes.data, arena.ctypes.data, cursor.ctypes.data, hdr.ctypes.data)

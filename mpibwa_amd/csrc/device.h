@@ -243,6 +243,12 @@ void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDes
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                      uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
                      int grid_blocks = 0);
+// the single-end instantiation: a unit is one read (d_req_base[read]), no mate descriptor, a read is handed back alone
+void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+                        const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
+                        const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
+                        uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
+                        int grid_blocks = 0);
 
 // ---- pairing decisions of the pairs with one plain hit per end (pair_kernel.hip) ----
 #define PR_MAXREG 8               // regions per read the kernel looks at (a read with more is the host's); 4 until round 4
@@ -270,6 +276,24 @@ void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const De
                         const int64_t *d_ann_off, const uint8_t *d_ann_alt, const double *d_ptab, const double *d_ltab, uint8_t *d_status,
                         AlnReq *d_reqs, SamDesc *d_desc);
 void launch_desc_overlay(void *stream, int n_pairs, const uint8_t *d_status, const SamDesc *d_from, SamDesc *d_to);
+
+// ---- decisions of the single-end reads that end in one record (se_kernel.hip) ----
+// status codes of se_simple_kernel (the numbers of pair_simple_kernel's codes where the test is the same)
+#define SE_HOST 0                 // not looked at
+#define SE_DECIDED 1              // reqs[i] and desc[i] are what the host's COLLECT pass would have listed (desc.req = 0, or -3: the unmapped record)
+#define SE_HOST_COMMENT 2         // the read carries a comment column (-C)
+#define SE_HOST_MAXREG 3          // more than PR_MAXREG regions
+#define SE_HOST_PATCH 4           // two regions mem_patch_reg would align across
+#define SE_HOST_LENGTH 5          // a region longer than the per-length table
+#define SE_HOST_ALT 6             // a region on an ALT contig
+#define SE_HOST_SUPP 10           // a second primary region of at least T: supplementary line, SA tags
+#define SE_HOST_XA 11             // a secondary region within XA_drop_ratio of its primary: XA tag
+// PairParams for a single-end call: the options, id0 = n_processed (the hash tie-breaks of src/bwamem.c:527), every orientation
+// failed and an empty pair-score table; pair_tables(opt, the same pes, P, 0, tab) then fills the per-length table alone (P.ltab_n entries)
+void se_params(const mem_opt_t *opt, int64_t l_pac, int64_t n_processed, int max_len, PairParams &P, mem_pestat_t pes[4]);
+// d_first / d_nfirst as launch_first_reg leaves them; d_ok[i] = 0: the host's read whatever its regions; reqs and desc: one record per read
+void launch_se_simple(void *stream, const PairParams &P, int n_reads, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,
+                      const uint8_t *d_ann_alt, const double *d_ltab, uint8_t *d_status, AlnReq *d_reqs, SamDesc *d_desc);
 
 // ---- mate-rescue local alignment on the device (msw_kernel.hip) ----
 struct MswReq {                  // one ksw_align2() call of mem_matesw (src/bwamem_pair.c:150-177)

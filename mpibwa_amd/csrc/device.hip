@@ -476,7 +476,56 @@ void pair_tables(const mem_opt_t *opt, const mem_pestat_t pes[4], const PairPara
 	ltab[0] = 1.;
 	for (int l = 1; l < pp.ltab_n; ++l) ltab[l] = l < opt->mapQ_coef_len ? 1. : opt->mapQ_coef_fac / log(l);   // src/bwamem.c:964
 }
+void se_params(const mem_opt_t *opt, int64_t l_pac, int64_t n_processed, int max_len, PairParams &pp, mem_pestat_t pes[4])
+{
+	memset(pes, 0, 4 * sizeof(mem_pestat_t));
+	for (int d = 0; d < 4; ++d) pes[d].failed = 1;
+	size_t n_tab = 0;
+	pair_params(opt, l_pac, pes, n_processed, max_len, pp, &n_tab);   // (no orientation to tabulate: always usable, n_tab = 0)
+	pp.id0 = (uint64_t)n_processed;   // NOT pair_params' n_processed >> 1: the hash id of a single-end read is n_processed + i, of a pair (n_processed >> 1) + i
+	pp.no_rescue = 1;
+}
 } // namespace mbw
+
+// Stage entry of se_simple_kernel (se_kernel.hip) for parity tests: n_reads single-end reads given by their regions as they stand after
+// phase 1 (regs: PR_MAXREG DevReg records per read, n_regs per read); status[i] = 1: decided — desc[i] (SamDesc) and req[i] (AlnReq) are
+// what mem_reg2sam reports with one line; else the code of the test that sent the read to the host (device.h: SE_HOST_*).
+extern "C" int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_reads, const void *regs, const int *n_regs,
+                               int max_len, uint8_t *status, void *desc, void *req)
+{
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
+	if (n_reads <= 0) return 0;
+	if (max_len <= 0) die("mi355x_se_batch: max_len must be positive");
+	PairParams pp;
+	mem_pestat_t pes[4];
+	se_params(opt, bns->l_pac, n_processed, max_len, pp, pes);
+	std::vector<double> tab((size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, 0, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt, ok((size_t)n_reads, 1);
+	contig_table(bns, ann_off, ann_alt);
+	const size_t n = (size_t)n_reads;
+	const DevReg *hr = (const DevReg *)regs;
+	for (size_t i = 0; i < n; ++i)   // nothing the kernel indexes with may point outside what is uploaded
+		for (int j = 0; j < n_regs[i] && j < PR_MAXREG; ++j)
+			if (hr[i * PR_MAXREG + j].rid < 0 || hr[i * PR_MAXREG + j].rid >= bns->n_seqs) die("mi355x_se_batch: bad contig in region %d of read %zu", j, i);
+	DevReg *d_first; int *d_nf; uint8_t *d_ok, *d_aa, *d_st; double *d_tab; AlnReq *d_rq; SamDesc *d_ds;
+	HIP_OK(hipMalloc(&d_first, n * PR_MAXREG * sizeof(DevReg))); HIP_OK(hipMalloc(&d_nf, n * 4)); HIP_OK(hipMalloc(&d_ok, n));
+	HIP_OK(hipMalloc(&d_aa, ann_alt.size())); HIP_OK(hipMalloc(&d_st, n)); HIP_OK(hipMalloc(&d_tab, tab.size() * 8));
+	HIP_OK(hipMalloc(&d_rq, n * sizeof(AlnReq))); HIP_OK(hipMalloc(&d_ds, n * sizeof(SamDesc)));
+	HIP_OK(hipMemcpy(d_first, regs, n * PR_MAXREG * sizeof(DevReg), hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_nf, n_regs, n * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_ok, ok.data(), n, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_aa, ann_alt.data(), ann_alt.size(), hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+	launch_se_simple(0, pp, n_reads, d_first, d_nf, d_ok, d_aa, d_tab, d_st, d_rq, d_ds);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipMemcpy(status, d_st, n, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(desc, d_ds, n * sizeof(SamDesc), hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(req, d_rq, n * sizeof(AlnReq), hipMemcpyDeviceToHost));
+	(void)hipFree(d_first); (void)hipFree(d_nf); (void)hipFree(d_ok); (void)hipFree(d_aa); (void)hipFree(d_st); (void)hipFree(d_tab);
+	(void)hipFree(d_rq); (void)hipFree(d_ds);
+	return 0;
+}
 
 // Stage entry of pair_simple_kernel (pair_kernel.hip) for parity tests: n_pairs pairs given by the regions of their two ends
 // (regs: PR_MAXREG DevReg records per read, n_regs per read) as they stand after phase 1; status[k] = 1: decided — desc[2k], desc[2k+1]
@@ -1104,17 +1153,18 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 #define SAM_GUARD 4096
 #define SAM_GUARD_BYTE 0xA5
 extern "C" size_t mi355x_sam_arena_bytes(int n_reads, int max_len) { return sam_arena_bytes(n_reads, max_len); }
-extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
-                                const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_, const int *req_base,
-                                size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
-                                unsigned long long *cursor, void *hdr_out)
+// (ends = 2: a unit of req_base is a pair, the paired instantiation of the kernel; ends = 1: a unit is a read, the single-end one)
+static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_units, const uint8_t *reads,
+                     const int64_t *off, const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_,
+                     const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                     unsigned long long *cursor, void *hdr_out)
 {
 	using namespace mbw;
 	int nd = 0;
 	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
-	if (n_pairs <= 0) return 0;
+	if (n_units <= 0) return 0;
 	hipStream_t st = 0;
-	const int n = 2 * n_pairs, n_req = req_base[n_pairs];
+	const int n = ends * n_units, n_req = req_base[n_units];
 	const int64_t l_pac = bns->l_pac;
 	const SamDesc *desc = (const SamDesc *)desc_;
 	const AlnReq *reqs = (const AlnReq *)reqs_;
@@ -1124,28 +1174,28 @@ extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const
 	slot[0] = 0;
 	for (int i = 0; i < n; ++i) {
 		lens[i] = (int)(off[i + 1] - off[i]);
-		if (lens[i] <= 0 || name_off[i + 1] < name_off[i]) die("mi355x_sam_batch: bad read %d", i);
+		if (lens[i] <= 0 || name_off[i + 1] < name_off[i]) die("%s: bad read %d", who, i);
 		slot[i + 1] = slot[i] + ((lens[i] + 15) & ~15);
 		max_len = std::max(max_len, lens[i]);
 	}
 	// nothing the kernels index with may point outside what was uploaded
-	if (req_base[0] != 0 || n_req < 0) die("mi355x_sam_batch: bad req_base");
-	for (int k = 0; k < n_pairs; ++k) {
-		if (req_base[k + 1] < req_base[k]) die("mi355x_sam_batch: bad req_base at pair %d", k);
-		const SamDesc &a = desc[2 * k], &b = desc[2 * k + 1];
-		if ((a.req >= 0) != (b.req >= 0)) die("mi355x_sam_batch: pair %d has one record of the device's only", k);
-		for (int e = 0; e < 2; ++e) {
-			const SamDesc &d = desc[2 * k + e];
+	if (req_base[0] != 0 || n_req < 0) die("%s: bad req_base", who);
+	for (int k = 0; k < n_units; ++k) {
+		if (req_base[k + 1] < req_base[k]) die("%s: bad req_base at unit %d", who, k);
+		if (ends == 2 && (desc[2 * k].req >= 0) != (desc[2 * k + 1].req >= 0)) die("%s: pair %d has one record of the device's only", who, k);
+		for (int e = 0; e < ends; ++e) {
+			const int r = ends * k + e;
+			const SamDesc &d = desc[r];
 			if (d.req < 0) continue;
 			const int q = req_base[k] + d.req;
-			if (q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != 2 * k + e) die("mi355x_sam_batch: bad descriptor %d", 2 * k + e);
-			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[2 * k + e] || d.qb > d.qe) die("mi355x_sam_batch: bad region %d", 2 * k + e);
+			if (q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != r) die("%s: bad descriptor %d", who, r);
+			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[r] || d.qb > d.qe) die("%s: bad region %d", who, r);
 		}
 	}
 	for (int q = 0; q < n_req; ++q) {
 		const AlnReq &r = reqs[q];
 		if (r.read < 0) continue;
-		if (r.read >= n || r.rb < 0 || r.re > 2 * l_pac || r.rb > r.re || r.qb < 0 || r.qb > r.qe || r.qe > lens[r.read]) die("mi355x_sam_batch: bad request %d", q);
+		if (r.read >= n || r.rb < 0 || r.re > 2 * l_pac || r.rb > r.re || r.qb < 0 || r.qb > r.qe || r.qe > lens[r.read]) die("%s: bad request %d", who, q);
 	}
 	std::vector<uint8_t> flat(slot[n] + 16, 4), fq;
 	for (int i = 0; i < n; ++i) memcpy(flat.data() + slot[i], reads + off[i], (size_t)lens[i]);
@@ -1183,7 +1233,7 @@ extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const
 	HIP_OK(hipMalloc(&d_hdr, (size_t)std::max(n_req, 1) * sizeof(AlnHdr))); HIP_OK(hipMalloc(&d_gap, gaptab.size() * 4));
 	HIP_OK(hipMalloc(&d_lists, (size_t)std::max(n_req, 1) * 3 * 4)); HIP_OK(hipMalloc(&d_cnt, 256)); HIP_OK(hipMalloc(&d_used, 64));
 	HIP_OK(hipMalloc(&d_names, n_names + 64)); HIP_OK(hipMalloc(&d_noff, (size_t)(n + 1) * 4)); HIP_OK(hipMalloc(&d_cn, cn.size() + 64));
-	HIP_OK(hipMalloc(&d_cno, cno.size() * 4)); HIP_OK(hipMalloc(&d_ao, ann_off.size() * 8)); HIP_OK(hipMalloc(&d_base, (size_t)(n_pairs + 1) * 4));
+	HIP_OK(hipMalloc(&d_cno, cno.size() * 4)); HIP_OK(hipMalloc(&d_ao, ann_off.size() * 8)); HIP_OK(hipMalloc(&d_base, (size_t)(n_units + 1) * 4));
 	HIP_OK(hipMalloc(&d_desc, (size_t)n * sizeof(SamDesc))); HIP_OK(hipMalloc(&d_arena, arena_bytes + SAM_GUARD));
 	HIP_OK(hipMalloc(&d_ooff, (size_t)n * 8)); HIP_OK(hipMalloc(&d_olen, (size_t)n * 4));
 	HIP_OK(hipMemcpy(d_seq, flat.data(), flat.size(), hipMemcpyHostToDevice));
@@ -1198,7 +1248,7 @@ extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const
 	HIP_OK(hipMemcpy(d_cn, cn.data(), cn.size(), hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy(d_cno, cno.data(), cno.size() * 4, hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy(d_ao, ann_off.data(), ann_off.size() * 8, hipMemcpyHostToDevice));
-	HIP_OK(hipMemcpy(d_base, req_base, (size_t)(n_pairs + 1) * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_base, req_base, (size_t)(n_units + 1) * 4, hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy(d_desc, desc, (size_t)n * sizeof(SamDesc), hipMemcpyHostToDevice));
 	HIP_OK(hipMemset(d_hdr, 0, (size_t)std::max(n_req, 1) * sizeof(AlnHdr)));
 	HIP_OK(hipMemset(d_arena, SAM_GUARD_BYTE, arena_bytes + SAM_GUARD));
@@ -1212,8 +1262,8 @@ extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const
 	memcpy(ep.mat, opt->mat, 25);
 	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
 	if (n_req) launch_aln(st, ap, ep, n_req, d_req, d_seq, d_off, d_pac, d_gap, d_hdr, d_pool, d_cnt, pool_bytes, max_len, max_len + 256, d_lists);
-	launch_sam_emit(st, sp, n, d_desc, d_base, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_noff, d_ao, d_cn, d_cno, d_arena, arena_bytes, d_used,
-	                d_ooff, d_olen, grid_blocks);
+	(ends == 2 ? launch_sam_emit : launch_sam_emit_se)(st, sp, n, d_desc, d_base, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_noff, d_ao, d_cn, d_cno,
+	                                                   d_arena, arena_bytes, d_used, d_ooff, d_olen, grid_blocks);
 	HIP_OK(hipStreamSynchronize(st));
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipMemcpy(out_len, d_olen, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -1226,6 +1276,24 @@ extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const
 	(void)hipFree(d_cn); (void)hipFree(d_cno); (void)hipFree(d_ao); (void)hipFree(d_base); (void)hipFree(d_desc); (void)hipFree(d_arena); (void)hipFree(d_ooff);
 	(void)hipFree(d_olen);
 	return 0;
+}
+
+extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
+                                const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_, const int *req_base,
+                                size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                                unsigned long long *cursor, void *hdr_out)
+{
+	return sam_batch("mi355x_sam_batch", 2, opt, bns, pac, n_pairs, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
+	                 out_len, out_off, arena_out, cursor, hdr_out);
+}
+// The twin for single-end descriptors (mi355x_se_batch's): a unit of req_base is a read, the kernel's single-end instantiation runs
+extern "C" int mi355x_sam_se_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
+                                   const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_, const int *req_base,
+                                   size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                                   unsigned long long *cursor, void *hdr_out)
+{
+	return sam_batch("mi355x_sam_se_batch", 1, opt, bns, pac, n_reads, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
+	                 out_len, out_off, arena_out, cursor, hdr_out);
 }
 
 // Stage-level entry point of the seed enumeration between SMEM and SA lookup (tests): seed_prep_kernel, the pipeline's prefix sum over

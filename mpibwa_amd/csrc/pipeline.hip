@@ -800,6 +800,12 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 	const bool gpu_aln = getenv("MPIBWA_HOST_CIGAR") == nullptr && aln_lds_per_block(max_len, max_len + 256) <= (size_t)160 * 1024;
 	int *d_gap = nullptr;
 	bool gpu_sam = false;
+	// Single-end input: the reads that end in one record are decided by se_simple_kernel and written by the single-end instantiation of
+	// sam_emit_kernel (se_kernel.hip); the rest of the chunk takes the host path below.  MPIBWA_HOST_SE=1 keeps every read there.
+	// (-5: mem_reorder_primary5 stays host code, so the whole call does.)
+	const bool se_want = !pe && gpu_aln && getenv("MPIBWA_HOST_SAM") == nullptr && getenv("MPIBWA_HOST_SE") == nullptr && opt->mapQ_coef_len > 0 &&
+	                     !(opt->flag & (MEM_F_ALL | MEM_F_REF_HDR | MEM_F_PRIMARY5));
+	bool dev_se = false;   // se_want and the reads uniformly with or without qualities (set by the thread below)
 	SamDescH *sdesc = nullptr;
 	SamParams sam_par;
 	const uint8_t *d_qual = nullptr, *d_names = nullptr;
@@ -827,20 +833,26 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		// CIGAR kernel of the part; the REPLAY pass only copies those records out of the arena and formats the rest itself.
 		static_assert(sizeof(SamDesc) == sizeof(SamDescH), "host/device record layouts differ");
 		gpu_sam = pe && gpu_aln && getenv("MPIBWA_HOST_SAM") == nullptr && !(opt->flag & (MEM_F_ALL | MEM_F_REF_HDR));
-		if (gpu_sam) {
+		dev_se = se_want;
+		if (gpu_sam || dev_se) {
 			bool any_q = false, all_q = true;
 			for (int i = 0; i < n; ++i) { if (seqs[i].qual) any_q = true; else all_q = false; }
-			if (any_q && !all_q) gpu_sam = false;   // a mix of reads with and without qualities: the host formats the chunk
+			if (any_q && !all_q) gpu_sam = dev_se = false;   // a mix of reads with and without qualities: the host formats the chunk
+			if (dev_se) {   // a chunk whose reads all carry a comment (-C) is the host's: no set-up for a kernel that would take none
+				bool any_plain = false;
+				for (int i = 0; i < n && !any_plain; ++i) any_plain = !seqs[i].comment;
+				dev_se = any_plain;
+			}
 			sam_par.l_pac = bns->l_pac; sam_par.has_qual = any_q ? 1 : 0;
 			sam_par.rg_len = (int)strnlen(bwa_rg_id, sizeof bwa_rg_id);
 			memset(sam_par.rg, 0, sizeof sam_par.rg);
 			memcpy(sam_par.rg, bwa_rg_id, (size_t)sam_par.rg_len);
 		}
-		if (gpu_sam) {
-			sdesc = (SamDescH *)W.h_sdesc.ensure((size_t)n * sizeof(SamDescH) + 64);
+		if (gpu_sam || dev_se) {
+			if (gpu_sam) sdesc = (SamDescH *)W.h_sdesc.ensure((size_t)n * sizeof(SamDescH) + 64);
 			int *noff = (int *)W.h_noff.ensure((size_t)(n + 1) * 4 + 64);
 			std::vector<int> nlen(n);
-			parallel_for(n_thr, n, 8192, [&](int i) { sdesc[i].req = -1; nlen[i] = (int)strlen(seqs[i].name); });
+			parallel_for(n_thr, n, 8192, [&](int i) { if (sdesc) sdesc[i].req = -1; nlen[i] = (int)strlen(seqs[i].name); });
 			noff[0] = 0;
 			for (int i = 0; i < n; ++i) noff[i + 1] = noff[i] + nlen[i];
 			uint8_t *names = (uint8_t *)W.h_names.ensure((size_t)noff[n] + 64);
@@ -886,8 +898,9 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 	// sub-batch leaves the first region and the region count of its reads in chunk-wide arrays.
 	const bool dev_pair = pe && getenv("MPIBWA_HOST_PAIR") == nullptr && !(opt->flag & (MEM_F_NOPAIRING | MEM_F_ALL | MEM_F_REF_HDR | MEM_F_PRIMARY5)) &&
 	                      opt->mapQ_coef_len > 0;
-	DevReg *d_pr_first = dev_pair ? (DevReg *)W.pr_first.ensure((size_t)n * PR_MAXREG * sizeof(DevReg)) : nullptr;
-	int *d_pr_nfirst = dev_pair ? (int *)W.pr_nfirst.ensure((size_t)n * 4) : nullptr;
+	// (a single-end call that may take the device path fills the same arrays for se_simple_kernel)
+	DevReg *d_pr_first = dev_pair || se_want ? (DevReg *)W.pr_first.ensure((size_t)n * PR_MAXREG * sizeof(DevReg)) : nullptr;
+	int *d_pr_nfirst = dev_pair || se_want ? (int *)W.pr_nfirst.ensure((size_t)n * 4) : nullptr;
 	struct P1 { double k_smem = 0, k_sa = 0, k_ext = 0, smem = 0, sa = 0, chain = 0, ext = 0, regs = 0; uint64_t smem_bytes = 0, smem_tab_bytes = 0, sa_bytes = 0, cells = 0, n_ext = 0, n_intv = 0, n_seeds = 0, n_chains = 0; };
 	const int n_all = n;
 	static const bool take_turns = !(getenv("MPIBWA_TURNS") && atoi(getenv("MPIBWA_TURNS")) == 0);
@@ -1408,6 +1421,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 	// alignments nor plans nor formats it (it only copies the two finished records out, or takes the pair back if the device
 	// hands a record back).
 	const uint8_t *pstat = nullptr;
+	const uint8_t *se_codes = nullptr;   // the status codes of se_simple_kernel (pstat too, if it took any read)
 	const AlnReq *d_pr_req = nullptr;
 	const SamDesc *d_pr_desc = nullptr;
 	double pair_dev_ms = 0;
@@ -1439,6 +1453,38 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 			HIP_OK(hipGetLastError());
 			pstat = hs; d_pr_req = d_rq; d_pr_desc = d_ds;
 		}
+		pair_dev_ms = now_ms() - tp0;
+	}
+	// ---- single-end reads that end in one record: decided on the device (se_kernel.hip) ----
+	// status[i] = 1: the read's CIGAR request and line descriptor exist on the device; the host neither marks its primary hits nor
+	// formats it (it only copies the finished record out, or takes the read back if the device hands the record back).
+	if (dev_se) {
+		const double tp0 = now_ms();
+		stage(9);
+		PairParams pp;
+		mem_pestat_t none[4];
+		se_params(opt, bns->l_pac, n_processed, max_len, pp, none);
+		double *tab = (double *)W.h_pr_tab.ensure((size_t)pp.ltab_n * 8 + 64);
+		pair_tables(opt, none, pp, 0, tab);
+		stage(28);
+		uint8_t *ok = (uint8_t *)W.h_pr_ok.ensure((size_t)n + 64);
+		parallel_for(n_thr, n, 8192, [&](int i) { ok[i] = !seqs[i].comment; });
+		double *d_tab = (double *)W.pr_ptab.ensure((size_t)pp.ltab_n * 8 + 64);
+		uint8_t *d_ok = (uint8_t *)W.pr_ok.ensure((size_t)n + 64);
+		uint8_t *d_status = (uint8_t *)W.pr_status.ensure((size_t)n + 64);
+		AlnReq *d_rq = (AlnReq *)W.pr_req.ensure((size_t)n * sizeof(AlnReq));
+		SamDesc *d_ds = (SamDesc *)W.pr_desc.ensure((size_t)n * sizeof(SamDesc));
+		uint8_t *hs = (uint8_t *)W.h_pr_status.ensure((size_t)n + 64);
+		HIP_OK(hipMemcpyAsync(d_tab, tab, (size_t)pp.ltab_n * 8, hipMemcpyHostToDevice, st));
+		HIP_OK(hipMemcpyAsync(d_ok, ok, (size_t)n, hipMemcpyHostToDevice, st));
+		launch_se_simple(st, pp, n, d_pr_first, d_pr_nfirst, d_ok, d_ann_alt, d_tab, d_status, d_rq, d_ds);
+		HIP_OK(hipMemcpyAsync(hs, d_status, (size_t)n, hipMemcpyDeviceToHost, st));
+		stream_wait(st);
+		HIP_OK(hipGetLastError());
+		se_codes = hs;
+		bool any_dev = false;
+		for (int i = 0; i < n && !any_dev; ++i) any_dev = hs[i] == SE_DECIDED;
+		if (any_dev) { pstat = hs; d_pr_req = d_rq; d_pr_desc = d_ds; }   // (none taken: no device job over n empty requests)
 		pair_dev_ms = now_ms() - tp0;
 	}
 
@@ -1577,7 +1623,8 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		stage(14);
 		if (!pstat) return;
 		Part::DevJob &J = P.dj;
-		const int nu = P.hi - P.lo, r0 = P.lo << 1, nr = nu << 1;
+		const int ends = pe ? 2 : 1;   // reads (and requests) per unit
+		const int nu = P.hi - P.lo, r0 = P.lo * ends, nr = nu * ends;
 		J.n_req = (size_t)nr;
 		if (!J.n_req) return;
 		J.st = C.d_streams[slot];
@@ -1597,7 +1644,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		           max_len + 256, d_lists);
 		J.ev.stop(J.st);
 		int *hb = (int *)WS.hj_base[slot].ensure((size_t)(nu + 1) * 4 + 64);
-		for (int k = 0; k <= nu; ++k) hb[k] = 2 * k;
+		for (int k = 0; k <= nu; ++k) hb[k] = ends * k;
 		int *d_base = (int *)WS.dj_base[slot].ensure((size_t)(nu + 1) * 4);
 		J.arena_bytes = sam_arena_bytes(nr, max_len);
 		uint8_t *d_arena = (uint8_t *)WS.dj_arena[slot].ensure(J.arena_bytes);
@@ -1606,8 +1653,8 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		int *d_olen = (int *)WS.dj_olen[slot].ensure((size_t)nr * 4);
 		HIP_OK(hipMemcpyAsync(d_base, hb, (size_t)(nu + 1) * 4, hipMemcpyHostToDevice, J.st));
 		HIP_OK(hipMemsetAsync(d_used, 0, 64, J.st));
-		launch_sam_emit(J.st, sam_par, nr, d_pr_desc + r0, d_base, J.d_hdr, J.d_pool, d_seq, d_off + r0, d_len + r0, d_qual, d_names, d_noff + r0, d_ann_off,
-		                d_ann_names, d_ann_noff, d_arena, J.arena_bytes, d_used, d_ooff, d_olen);
+		(pe ? launch_sam_emit : launch_sam_emit_se)(J.st, sam_par, nr, d_pr_desc + r0, d_base, J.d_hdr, J.d_pool, d_seq, d_off + r0, d_len + r0, d_qual, d_names,
+		                                            d_noff + r0, d_ann_off, d_ann_names, d_ann_noff, d_arena, J.arena_bytes, d_used, d_ooff, d_olen, 0);
 		J.launched = true;
 	};
 	auto finish_dev = [&](Part &P, int slot) {
@@ -1615,7 +1662,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		Part::DevJob &J = P.dj;
 		if (!J.launched) return;
 		double ta = now_ms();
-		const int nr = (P.hi - P.lo) << 1;
+		const int nr = (P.hi - P.lo) * (pe ? 2 : 1);
 		stream_wait(J.st);
 		HIP_OK(hipGetLastError());
 		STAT.k_aln_ms += J.ev.ms();
@@ -1635,7 +1682,7 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		// a record handed back (CIGAR declined, row overflow): the host redoes that pair and needs the CIGAR results of the job
 		bool any_back = false;
 		for (int k = 0; k < (P.hi - P.lo) && !any_back; ++k)
-			if (pstat[P.lo + k] == 1 && (hl[2 * k] < 0 || hl[2 * k + 1] < 0)) any_back = true;
+			if (pstat[P.lo + k] == 1 && (pe ? hl[2 * k] < 0 || hl[2 * k + 1] < 0 : hl[k] < 0)) any_back = true;
 		if (any_back) {
 			unsigned long long *cnt8 = small + 8;
 			HIP_OK(hipMemcpyAsync(cnt8, J.d_cnt, 64, hipMemcpyDeviceToHost, J.st));
@@ -1777,12 +1824,33 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 				}
 				n_sam_dev += n_dev; tsc_devcopy += tsc;
 			});
-		} else if (which != 0) {
-			parallel_for(n_thr, P.hi - P.lo, 256, [&](int k) {
-				const int i = P.lo + k;
-				AlnCtx ctx;
-				if (gpu_aln) { ctx.mode = AlnCtx::REPLAY; ctx.hdr = P.hdr; ctx.pool = P.pool; ctx.cursor = P.base[k]; }
-				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln ? &ctx : nullptr, i);
+		} else if (which != 0 || pstat) {
+			parallel_blocks(n_thr, P.hi - P.lo, 256, [&](int, int, int k_lo, int k_hi) {
+				unsigned long long n_dev = 0;
+				for (int k = k_lo; k < k_hi; ++k) {
+					const int i = P.lo + k;
+					const bool dev_k = pstat && pstat[i] == 1;
+					const bool early = dev_k && P.dj.solen && P.dj.solen[k] >= 0;   // pass 0's reads: the record was written by sam_kernel
+					if (which != 2 && early != (which == 0)) continue;
+					if (early) {
+						const int len = P.dj.solen[k];
+						char *sam = (char *)malloc((size_t)len + 1);   // ownership passes to the caller, who free()s it
+						if (!sam) die("out of memory");
+						memcpy(sam, P.dj.sarena + P.dj.sooff[k], (size_t)len);
+						sam[len] = 0;
+						seqs[i].sam = sam;
+						++n_dev;
+						continue;
+					}
+					AlnCtx ctx;
+					if (gpu_aln) { ctx.mode = AlnCtx::REPLAY; ctx.hdr = P.hdr; ctx.pool = P.pool; ctx.cursor = P.base[k]; }
+					if (dev_k) {   // the device decided the read but handed its record back: the host decides it again (the same one request, or none)
+						mark_primary_se(opt, regs[i], n_processed + i);
+						ctx.hdr = P.dj.hdr; ctx.pool = P.dj.pool; ctx.cursor = (size_t)k;
+					}
+					reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln ? &ctx : nullptr, i);
+				}
+				n_sam_dev += n_dev;
 			});
 		}
 		emit_ms += now_ms() - ta;
@@ -1795,15 +1863,25 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 	// MPIBWA_DEV_JOB_LATE=0/1 forces either.
 	const char *dle = getenv("MPIBWA_DEV_JOB_LATE");
 	const bool dev_late = dle ? atoi(dle) != 0 : lease.crowded;
+	// Single-end calls have no rescue listing to run the device job under: its records are fetched once the host's reads are planned
+	// and their CIGAR job is out (dev_mid), so that the job runs under the planning and the copies of its records under that kernel.
+	// Where the device job of a part is fetched (finish_dev + replay 0), relative to the host reads' CIGAR job (launch .. finish):
+	//   dev_early  pairs, one call in flight     launch_dev, rescue listing, FETCH, collect, launch, finish          (as before)
+	//   dev_last   pairs, other calls in flight  rescue listing, collect, launch_dev, launch, finish, FETCH          (as before)
+	//   dev_mid    single-end, either            launch_dev (before or after collect, by dev_late), launch, FETCH, finish
+	// Exactly one of the three holds; replay 1 (the host's records) closes every part.
+	const bool dev_early = pe && !dev_late, dev_mid = !pe, dev_last = pe && dev_late;
 	if (n_parts == 1) {
 		parts[0].lo = 0; parts[0].hi = n_units;
 		if (!dev_late) launch_dev(parts[0], 0);
 		mcollect(parts[0], 0); mlaunch(parts[0], 0);
-		if (!dev_late) { finish_dev(parts[0], 0); replay(parts[0], 0); }
+		if (dev_early) { finish_dev(parts[0], 0); replay(parts[0], 0); }
 		collect(parts[0], 0); mfinish(parts[0]); collect(parts[0], 1);
 		if (dev_late) launch_dev(parts[0], 0);
-		launch(parts[0], 0); finish(parts[0]);
-		if (dev_late) { finish_dev(parts[0], 0); replay(parts[0], 0); }
+		launch(parts[0], 0);
+		if (dev_mid) { finish_dev(parts[0], 0); replay(parts[0], 0); }
+		finish(parts[0]);
+		if (dev_last) { finish_dev(parts[0], 0); replay(parts[0], 0); }
 		hprof_report("decisions + request lists");
 		replay(parts[0], 1);
 	} else {
@@ -1811,28 +1889,38 @@ extern "C" void mem_process_seqs(const mem_opt_t *opt, const bwt_t *bwt, const b
 		if (!dev_late) { launch_dev(parts[0], 0); launch_dev(parts[1], 1); }
 		mcollect(parts[0], 0); mlaunch(parts[0], 0);
 		mcollect(parts[1], 1); mlaunch(parts[1], 1);
-		if (!dev_late) { finish_dev(parts[0], 0); replay(parts[0], 0); }   // (the mate-rescue kernels of both parts are running)
+		if (dev_early) { finish_dev(parts[0], 0); replay(parts[0], 0); }   // (the mate-rescue kernels of both parts are running)
 		collect(parts[0], 0); mfinish(parts[0]); collect(parts[0], 1);
 		if (dev_late) launch_dev(parts[0], 0);
 		launch(parts[0], 0);
-		if (!dev_late) { finish_dev(parts[1], 1); replay(parts[1], 0); }
+		if (dev_early) { finish_dev(parts[1], 1); replay(parts[1], 0); }
 		collect(parts[1], 0); mfinish(parts[1]); collect(parts[1], 1);
 		if (dev_late) launch_dev(parts[1], 1);
 		launch(parts[1], 1);
+		if (dev_mid) { finish_dev(parts[0], 0); replay(parts[0], 0); }
 		finish(parts[0]);
-		if (dev_late) { finish_dev(parts[0], 0); replay(parts[0], 0); }
+		if (dev_last) { finish_dev(parts[0], 0); replay(parts[0], 0); }
 		replay(parts[0], 1);
+		if (dev_mid) { finish_dev(parts[1], 1); replay(parts[1], 0); }
 		finish(parts[1]);
-		if (dev_late) { finish_dev(parts[1], 1); replay(parts[1], 0); }
+		if (dev_last) { finish_dev(parts[1], 1); replay(parts[1], 0); }
 		replay(parts[1], 1);
 	}
 	STAT.plan_ms = plan_ms; STAT.aln_ms = aln_wait_ms; STAT.msw_ms = msw_ms; STAT.emit_ms = emit_ms;
 	STAT.n_sam_dev = n_sam_dev.load();
-	if (pstat) {
+	if (pstat || se_codes) {
+		const uint8_t *codes = pstat ? pstat : se_codes;
 		uint64_t c[16] = {0};
-		for (int k = 0; k < n_units; ++k) ++c[pstat[k] & 15];
-		STAT.n_pair_dev = c[1];
-		if (s_cpusec) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu\n",
+		for (int k = 0; k < n_units; ++k) ++c[codes[k] & 15];
+		if (pe) STAT.n_pair_dev = c[1];
+		else {
+			STAT.n_se_dev = c[1];
+			if (s_cpusec) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu\n",
+			                      n_units, (unsigned long long)c[SE_DECIDED], (unsigned long long)c[SE_HOST_COMMENT], PR_MAXREG, (unsigned long long)c[SE_HOST_MAXREG],
+			                      (unsigned long long)c[SE_HOST_PATCH], (unsigned long long)c[SE_HOST_LENGTH], (unsigned long long)c[SE_HOST_ALT],
+			                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA]);
+		}
+		if (pe && s_cpusec) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu\n",
 		                      n_units, (unsigned long long)c[1], (unsigned long long)c[2], PR_MAXREG, (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[6],
 		                      (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11]);
 	}

@@ -1,13 +1,14 @@
-// sam_kernel.hip — SAM text on the device for the records of confidently paired reads.
+// sam_kernel.hip — SAM text on the device for the records of confidently paired reads and of single-end reads with one record.
 //
 // Device counterpart of the tail of mem_reg2aln (src/bwamem.c:1123-1157: position, strand, squeeze of a leading /
 // trailing deletion, soft clips) and of mem_aln2sam (src/bwamem.c:825-946) for the case that makes up the bulk of a
 // chunk: a pair that mem_sam_pe reports through its "paired" branch (src/bwamem_pair.c:315-345) with ONE line per read —
 // no supplementary / ALT line, no XA, no pa tag, no comment, no XR — and (round 3) the two records of a pair without any hit.  Everything else (unpaired ends, supplementary
-// lines, XA, -a, -C, -V, single-end input) stays with the host's formatter (host_regs.cpp: aln2sam), and the host takes
+// lines, XA, -a, -C, -V) stays with the host's formatter (host_regs.cpp: aln2sam), and the host takes
 // a pair back whenever the device flags one of its reads (CIGAR computed by the host, record longer than the staging
 // buffer).  The host decides WHICH records are written here and all their numbers that involve floating point
-// (MAPQ); the kernel turns numbers into bytes.
+// (MAPQ); the kernel turns numbers into bytes.  The single-end instantiation (sam_emit_kernel<false>) writes the one record of a
+// read that mem_reg2sam (src/bwamem.c:1003-1049) reports with one line, from the descriptors of se_simple_kernel (se_kernel.hip).
 //
 // One wavefront per 64 reads, in two phases.
 //   1. a lane per read: the lane works out its record's alignment fields (sam_aln) and prints the short fields — FLAG, POS,
@@ -119,6 +120,9 @@ __device__ __forceinline__ T bcast(T v, int src)   // the value lane `src` (wave
 	return *(T *)&x;
 }
 
+// PE: the records of pairs (a unit of req_base is a pair, reads 2k and 2k + 1 describe each other's RNEXT / PNEXT / TLEN / MC and go
+// back to the host together); !PE: single-end records (a unit is a read, "*\t0\t0" for the mate columns, a read goes back alone)
+template <bool PE>
 __global__ void __launch_bounds__(64)
 sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, const int *__restrict__ req_base, const AlnHdr *__restrict__ hdr,
                 const uint8_t *__restrict__ pool, const uint8_t *__restrict__ seq, const int64_t *__restrict__ off, const int *__restrict__ lens,
@@ -140,7 +144,7 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 		const uint8_t *md = nullptr;
 		if (r < n_reads) {
 			const SamDesc D = desc[r];
-			if (D.req == -3) {   // a read of a pair without any hit: "QNAME FLAG * 0 0 * * 0 0 SEQ QUAL AS:i:0 XS:i:0 [RG]" (src/bwamem.c:853-858, 928-929)
+			if (D.req == -3) {   // a read without any hit (of a pair, or a single-end read): "QNAME FLAG * 0 0 * * 0 0 SEQ QUAL AS:i:0 XS:i:0 [RG]" (src/bwamem.c:853-858, 928-929)
 				lq = lens[r];
 				Sink S;
 				S.row = rows + lane * SAM_ROW; S.len = 0;
@@ -158,17 +162,17 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 				is_rev = 0; sq_at = off[r];
 				total = name_len + S.len + lq + 1 + (P.has_qual ? lq : 0) + P.rg_len + 1;
 				status = total;
-			} else if (D.req >= 0) {
-				const SamDesc M = desc[r ^ 1];
-				const int unit = r >> 1, lm = lens[r ^ 1];
+			} else if (D.req >= 0) {   // mem_aln2sam; !PE: without a mate (src/bwamem.c:867: "*\t0\t0"; no MC)
+				const int unit = PE ? r >> 1 : r;
 				lq = lens[r];
 				const SamAln p = sam_aln(D, hdr, pool, req_base[unit], P.l_pac, ann_off, lq);
-				const SamAln m = sam_aln(M, hdr, pool, req_base[unit], P.l_pac, ann_off, lm);
-				status = -1;             // a CIGAR the device declined, or a row that overflows: the host formats the pair
+				SamAln m = p;            // (PE: the mate's line; !PE: never read)
+				if constexpr (PE) m = sam_aln(desc[r ^ 1], hdr, pool, req_base[unit], P.l_pac, ann_off, lens[r ^ 1]);
+				status = -1;             // a CIGAR the device declined, or a row that overflows: the host formats the pair (the read)
 				if (p.ok && m.ok) {
 					Sink S;
 					S.row = rows + lane * SAM_ROW; S.len = 0;
-					const int flag = (D.flag & 0xffff) | 0x1 | (p.is_rev ? 0x10 : 0) | (m.is_rev ? 0x20 : 0);
+					const int flag = (D.flag & 0xffff) | (PE ? 0x1 : 0) | (p.is_rev ? 0x10 : 0) | (PE && m.is_rev ? 0x20 : 0);
 					const int n_p = p.n_cigar - p.skip_front - p.skip_back + (p.clip5 ? 1 : 0) + (p.clip3 ? 1 : 0);
 					const int n_m = m.n_cigar - m.skip_front - m.skip_back + (m.clip5 ? 1 : 0) + (m.clip3 ? 1 : 0);
 					name_at = name_off[r]; name_len = name_off[r + 1] - name_at;
@@ -178,16 +182,22 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 					S.ch('\t'); S.num(p.pos + 1); S.ch('\t'); S.num32(D.mapq); S.ch('\t');
 					if (n_p) S.cigar(p); else S.ch('*');
 					S.ch('\t');
-					if (p.rid == m.rid) S.ch('=');
-					else { mn_at = ann_name_off[m.rid]; mn_len = ann_name_off[m.rid + 1] - mn_at; }
-					e_b = S.len;
-					S.ch('\t'); S.num(m.pos + 1); S.ch('\t');
-					if (p.rid == m.rid) {
-						const long long p0 = p.pos + (p.is_rev ? p.rlen - 1 : 0), p1 = m.pos + (m.is_rev ? m.rlen - 1 : 0);
-						if (n_m == 0 || n_p == 0) S.ch('0');
-						else S.num(-(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
-					} else S.ch('0');
-					S.ch('\t');
+					if constexpr (PE) {
+						if (p.rid == m.rid) S.ch('=');
+						else { mn_at = ann_name_off[m.rid]; mn_len = ann_name_off[m.rid + 1] - mn_at; }
+						e_b = S.len;
+						S.ch('\t'); S.num(m.pos + 1); S.ch('\t');
+						if (p.rid == m.rid) {
+							const long long p0 = p.pos + (p.is_rev ? p.rlen - 1 : 0), p1 = m.pos + (m.is_rev ? m.rlen - 1 : 0);
+							if (n_m == 0 || n_p == 0) S.ch('0');
+							else S.num(-(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
+						} else S.ch('0');
+						S.ch('\t');
+					} else {
+						S.ch('*');
+						e_b = S.len;
+						S.lit("\t0\t0\t");
+					}
 					e_c = S.len;
 					if (!P.has_qual) S.ch('*');   // (which = 0: SEQ and QUAL are never trimmed)
 					if (n_p) {
@@ -196,7 +206,7 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 						md = p.md; md_len = p.md_len;
 					}
 					e_d = S.len;
-					if (n_m) { S.lit("\tMC:Z:"); S.cigar(m); }
+					if (PE && n_m) { S.lit("\tMC:Z:"); S.cigar(m); }
 					if (D.score >= 0) { S.lit("\tAS:i:"); S.num32(D.score); }
 					if (D.sub >= 0) { S.lit("\tXS:i:"); S.num32(D.sub); }
 					if (P.rg_len) S.lit("\tRG:Z:");
@@ -209,9 +219,9 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 				}
 			}
 		}
-		// a pair goes back as a whole: the two rows of a pair need not overflow together (other POS, TLEN sign, NM), and the host
-		// formats both records as soon as one is missing (reads 2k and 2k + 1 are neighbouring lanes)
-		if (__shfl_xor(status, 1) == -1 && status >= 0) { status = -1; total = 0; }
+		// PE: a pair goes back as a whole: the two rows of a pair need not overflow together (other POS, TLEN sign, NM), and the host
+		// formats both records as soon as one is missing (reads 2k and 2k + 1 are neighbouring lanes).  !PE: a read goes back alone.
+		if (PE && __shfl_xor(status, 1) == -1 && status >= 0) { status = -1; total = 0; }
 		// place the wave's records back to back: exclusive prefix sum of the lengths, one atomic
 		int incl = total;
 		for (int d = 1; d < 64; d <<= 1) {
@@ -278,7 +288,8 @@ size_t sam_arena_bytes(int n_reads, int max_len)
 	return (size_t)n_reads * (size_t)(2 * max_len + 320) + (1 << 20);
 }
 
-void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+template <bool PE>
+static void launch_sam_emit_t(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
                      const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                      uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
@@ -288,9 +299,29 @@ void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDes
 	const int n_batch = (n_reads + 63) >> 6;
 	int blocks = n_batch < 256 * 8 ? n_batch : 256 * 8;   // 16.6 KB of LDS per wave: nine waves per CU
 	if (grid_blocks > 0 && grid_blocks < blocks) blocks = grid_blocks;
-	hipLaunchKernelGGL(sam_emit_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, P, n_reads, d_desc, d_req_base, d_hdr, d_pool, d_seq, d_off,
+	hipLaunchKernelGGL(sam_emit_kernel<PE>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, P, n_reads, d_desc, d_req_base, d_hdr, d_pool, d_seq, d_off,
 	                   d_len, d_qual, d_names, d_name_off, (const long long *)d_ann_off, d_ann_names, d_ann_name_off, d_arena,
 	                   (unsigned long long)arena_bytes, d_arena_used, d_out_off, d_out_len);
 }
+
+#define SAM_EMIT_ARGS stream, P, n_reads, d_desc, d_req_base, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_name_off, d_ann_off, d_ann_names, \
+	d_ann_name_off, d_arena, arena_bytes, d_arena_used, d_out_off, d_out_len, grid_blocks
+void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+                     const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
+                     const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
+                     uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
+                     int grid_blocks)
+{
+	launch_sam_emit_t<true>(SAM_EMIT_ARGS);
+}
+void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+                        const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
+                        const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
+                        uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
+                        int grid_blocks)
+{
+	launch_sam_emit_t<false>(SAM_EMIT_ARGS);
+}
+#undef SAM_EMIT_ARGS
 
 } // namespace mbw

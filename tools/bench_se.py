@@ -1,0 +1,135 @@
+"""Single-end leg next to bench.py: trimmed single-end reads (BASELINE config 3: lengths uniform 50-300) through mem_process_seqs with
+the device path of the stage after the CIGAR kernel (se_simple_kernel, single-end sam_emit_kernel) and with MPIBWA_HOST_SE=1 (the host
+path: what the library did before it had one), alternately, on the same chunks.
+
+    python tools/bench_se.py [--reads N] [--chunks C] [--steps K] [--repeats R] [--genome-mbp M] [--out FILE]
+
+The reads come from the generator and the index cache bench.py uses (bigindex.make_or_get / simulate_pairs with 300-base reads; read 1 of
+every pair, cut to a seeded length in [50, 300]).  Every leg is a fresh child process under its own `timeout`; the run stops at the
+first leg that fails.  One JSON line per leg: Mreads/s, emit_ms and plan_ms per chunk, host CPU-seconds per chunk, n_se_dev / n_reads,
+n_sam_dev / n_reads and a hash of the SAM of all chunks, which must be the same in every leg.  A last child (one step, MPIBWA_CPUSEC=1)
+reports the status codes of se_simple_kernel."""
+import argparse
+import hashlib
+import json
+import os
+import re
+import resource
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def log(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def child(args):
+    import numpy as np
+    from mpibwa_amd import abi, api, bigindex
+    os.makedirs(args.workdir, exist_ok=True)
+    idx = bigindex.make_or_get(args.workdir, genome_mbp=args.genome_mbp, seed=38, log=log, repeat_frac=args.repeat_frac, model=args.genome_model)
+    eng = idx.engine
+    lib = api.load_library(build_if_missing=False)
+    batches = []
+    for c in range(args.chunks):
+        rng = np.random.default_rng(args.seed + 100 + c)
+        pairs = idx.simulate_pairs(args.reads, seed=args.seed + c, read_len=300, frag_mean=660.0)
+        lens = rng.integers(50, 301, size=len(pairs))
+        batches.append(abi.SeqBatch(api.libc, [(n, a[:int(l)], None) for (n, a, _), l in zip(pairs, lens)]))
+    opt = eng.opt(flag=0, n_threads=int(lib.mi355x_host_cpus()))
+    import ctypes as C
+    C.c_int.in_dll(eng.lib, "bwa_verbose").value = 1
+    # one pass over the chunks: the hash of their SAM, and the work buffers of the call context grow to their size
+    h = hashlib.sha256()
+    for c in range(args.chunks):
+        eng.process_batch(opt, batches[c], n_processed=c * args.reads)
+        h.update(eng.collect_sam(batches[c]))
+    acc, wall, cpu = {}, 0.0, 0.0
+    for s in range(args.steps):
+        c = s % args.chunks
+        ru0, t0 = resource.getrusage(resource.RUSAGE_SELF), time.perf_counter()
+        eng.process_batch(opt, batches[c], n_processed=c * args.reads)
+        t1, ru1 = time.perf_counter(), resource.getrusage(resource.RUSAGE_SELF)
+        wall += t1 - t0
+        cpu += (ru1.ru_utime + ru1.ru_stime) - (ru0.ru_utime + ru0.ru_stime)
+        for k, v in eng.stats().items():
+            acc[k] = acc.get(k, 0) + v
+        eng.collect_sam(batches[c])   # (the caller's writer: outside the timed region)
+    n = max(1, args.steps)
+    print(json.dumps({
+        "leg": args.leg, "rep": args.rep, "workload": "single-end, lengths uniform 50-300, %d chunks x %d reads vs %d Mbp (%s)" %
+        (args.chunks, args.reads, int(args.genome_mbp), args.genome_model), "steps": args.steps,
+        "mreads_s": round(acc.get("n_reads", 0) / wall / 1e6, 4), "ms_per_chunk": round(wall / n * 1e3, 2),
+        "emit_ms": round(acc.get("emit_ms", 0) / n, 2), "plan_ms": round(acc.get("plan_ms", 0) / n, 2),
+        "host_cpu_s_per_chunk": round(cpu / n, 3),
+        "se_dev_frac": round(acc.get("n_se_dev", 0) / max(1, acc.get("n_reads", 1)), 4),
+        "sam_dev_frac": round(acc.get("n_sam_dev", 0) / max(1, acc.get("n_reads", 1)), 4),
+        "sam_sha256": h.hexdigest()}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=300000, help="reads per chunk")
+    ap.add_argument("--chunks", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=9, help="timed calls per leg (after one untimed pass over the chunks)")
+    ap.add_argument("--repeats", type=int, default=2, help="alternations host / device")
+    ap.add_argument("--seed", type=int, default=3000)
+    ap.add_argument("--genome-mbp", type=float, default=float(os.environ.get("MPIBWA_BENCH_GENOME_MBP", "3100")))
+    ap.add_argument("--repeat-frac", type=float, default=float(os.environ.get("MPIBWA_BENCH_REPEAT_FRAC", "0.05")))
+    ap.add_argument("--genome-model", default=os.environ.get("MPIBWA_BENCH_GENOME_MODEL", "grch38like"))
+    ap.add_argument("--workdir", default=os.environ.get("MPIBWA_BENCH_DIR", "/tmp/mpibwa_bench"))
+    ap.add_argument("--leg-timeout", type=int, default=420, help="seconds a leg may take (index load included)")
+    ap.add_argument("--out", help="also write the JSON lines to this file")
+    ap.add_argument("--leg", choices=["host", "dev", "codes"], help=argparse.SUPPRESS)
+    ap.add_argument("--rep", type=int, default=0, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.leg:
+        return child(args)
+    lines = []
+    passthrough = ["--reads", str(args.reads), "--chunks", str(args.chunks), "--seed", str(args.seed), "--genome-mbp", str(args.genome_mbp),
+                   "--repeat-frac", str(args.repeat_frac), "--genome-model", args.genome_model, "--workdir", args.workdir]
+    legs = [(leg, rep) for rep in range(args.repeats) for leg in ("host", "dev")] + [("codes", 0)]
+    for leg, rep in legs:
+        env = dict(os.environ)
+        env.pop("MPIBWA_HOST_SE", None)
+        env.pop("MPIBWA_CPUSEC", None)
+        if leg == "host":
+            env["MPIBWA_HOST_SE"] = "1"
+        if leg == "codes":
+            env["MPIBWA_CPUSEC"] = "1"
+        cmd = ["timeout", "-k", "10", str(args.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", leg, "--rep", str(rep),
+               "--steps", "1" if leg == "codes" else str(args.steps)] + passthrough
+        # (the timed legs report their progress — genome, index, reads — on this process's stderr; the last one's is read for its line)
+        p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE if leg == "codes" else None, text=True)
+        if p.returncode != 0:
+            log((p.stderr or "")[-4000:])
+            log("leg %s (repeat %d) ended with status %d: stopping here" % (leg, rep, p.returncode))
+            return 1
+        rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        if leg == "codes":
+            m = [ln for ln in p.stderr.splitlines() if ln.startswith("[se_kernel]")]
+            rec = {"leg": "status codes of se_simple_kernel, last chunk", "line": m[-1] if m else None, "sam_sha256": rec["sam_sha256"]}
+            if m:
+                rec["counts"] = {k.strip(" ;:").replace("host: ", ""): int(v) for k, v in re.findall(r"([a-zA-Z>: ][a-zA-Z0-9>: ]*?) (\d+)(?=[,;]|$)", m[-1].split(":", 1)[1])}
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+    same = len({r["sam_sha256"] for r in lines}) == 1
+    by = {leg: [r for r in lines if r["leg"] == leg] for leg in ("host", "dev")}
+    summary = {"leg": "summary", "sam_identical_across_legs": same,
+               "host_mreads_s": [r["mreads_s"] for r in by["host"]], "dev_mreads_s": [r["mreads_s"] for r in by["dev"]],
+               "host_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["host"]], "dev_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["dev"]]}
+    lines.append(summary)
+    print(json.dumps(summary), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+    return 0 if same else 2
+
+
+if __name__ == "__main__":
+    sys.exit(main())
