@@ -66,7 +66,7 @@ struct SmemParams {
 
 // ---- device buffers reused across calls ----
 struct DevBuf;
-// A DevBuf that is constructed while an owner list is open (pipeline.hip: the work buffers of a call context) enters it, so that
+// A DevBuf that is constructed while an owner list is open (pipeline.h: the work buffers of a call context) enters it, so that
 // the context's buffers can be given back as a whole: when the index is released, or when another call's buffer does not fit.
 extern std::vector<DevBuf *> *g_devbuf_owner;
 struct DevBuf {
@@ -216,6 +216,11 @@ struct AlnHdr {                  // result header; cigar (n_cigar x u32) and MD 
 	int32_t flags;               // 1 = not done on the device (band matrix too large / caps): the host recomputes it
 };
 struct AlnParams { int64_t l_pac; int a, w; };
+void aln_params(const mem_opt_t *opt, int64_t l_pac, AlnParams &ap, ExtParams &ep);
+// the result pool of n_req requests: 96 bytes each + room for the partly used last slab of every wave (aln_kernel.hip: ALN_SLAB)
+inline size_t aln_pool_bytes(size_t n_req) { return n_req * 96 + ((size_t)48 << 20); }
+// max_gap of bwa_gen_cigar2 (src/bwa.c:155-158), a function of l_query only: max_len + 2 entries
+void cigar_gap_table(const mem_opt_t *opt, int max_len, std::vector<int> &tab);
 size_t aln_lds_per_block(int max_len, int tcap);   // LDS of the full-size CIGAR kernel for reads of up to max_len bases
 void launch_aln(void *stream, const AlnParams &P, const ExtParams &ep, int n_req, const AlnReq *d_req, const uint8_t *d_seq,
                 const int64_t *d_off, const uint8_t *d_pac, const int *d_gaptab, AlnHdr *d_hdr, uint8_t *d_pool,
@@ -234,7 +239,34 @@ struct SamParams {
 	int has_qual, rg_len;
 	char rg[256];                // bwa_rg_id
 };
+SamParams sam_params(int64_t l_pac, bool has_qual);   // + the read group, bwa_rg_id
+// the contig names back to back; name k is names[name_off[k] .. name_off[k + 1])
+void contig_names(const bntseq_t *bns, std::vector<char> &names, std::vector<int> &name_off);
 size_t sam_arena_bytes(int n_reads, int max_len);   // the arena the pipeline gives n_reads records of reads of up to max_len bases
+// One CIGAR-and-SAM job: aln_kernel over n_req requests, then sam_emit_kernel over the records of n_reads reads, queued on one stream.
+// The SAM stage (sam_stage.hip: the host's units and the units decided on the device) and the stage entries (device.hip: sam_batch)
+// all queue it through queue_aln_sam().
+struct ChunkDev {                // what is resident of the chunk: packed reads, qualities, names, the contig table, the CIGAR gap table
+	const uint8_t *d_seq = nullptr; const int64_t *d_off = nullptr; const int *d_len = nullptr; int max_len = 0;
+	const uint8_t *d_pac = nullptr; const int *d_gap = nullptr;
+	const uint8_t *d_qual = nullptr, *d_names = nullptr; const int *d_noff = nullptr;
+	const int64_t *d_ann_off = nullptr; const uint8_t *d_ann_alt = nullptr; const char *d_ann_names = nullptr; const int *d_ann_noff = nullptr;
+};
+struct AlnSamJob {
+	int n_req = 0; const AlnReq *d_req = nullptr; AlnHdr *d_hdr = nullptr; uint8_t *d_pool = nullptr; size_t pool_bytes = 0;
+	unsigned long long *d_cnt = nullptr; int *d_lists = nullptr;
+	// the records: reads r0 .. r0 + n_reads of the chunk, `ends` of them per unit (2: pairs, 1: single-end reads); n_reads = 0: no SAM launch
+	int ends = 2, r0 = 0, n_reads = 0;
+	const SamDesc *h_desc = nullptr;   // of the chunk; given: the job's slice is uploaded to d_desc first
+	SamDesc *d_desc = nullptr;         // of the chunk
+	const int *h_base = nullptr; int *d_base = nullptr;   // first request of every unit (n_reads / ends + 1 entries), uploaded here
+	uint8_t *d_arena = nullptr; size_t arena_bytes = 0; unsigned long long *d_used = nullptr, *d_ooff = nullptr; int *d_olen = nullptr;
+	int grid_blocks = 0;
+};
+// on `stream`: zero the counters, [ev_a] aln_kernel [ev_b] (when there are requests), then descriptors and request bases up, zero the
+// arena cursor, sam_emit_kernel.  ev_a / ev_b: hipEvent_t around the CIGAR kernel, or null
+void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const ChunkDev &D, const SamParams &sp, const AlnSamJob &J,
+                   void *ev_a = nullptr, void *ev_b = nullptr);
 // d_req_base[pair] = first CIGAR request of the pair in d_hdr; out_len[r] = bytes of the record at arena + out_off[r],
 // -1 = the host must format the pair, -2 = not a line of the device.  grid_blocks > 0 caps the number of workgroups (stage tests:
 // the grid-stride loop with a few thousand reads); 0 = the launcher's own choice
@@ -275,7 +307,6 @@ void launch_first_reg(void *stream, int n, const int *d_reg_pos, const int *d_nr
 void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,
                         const int64_t *d_ann_off, const uint8_t *d_ann_alt, const double *d_ptab, const double *d_ltab, uint8_t *d_status,
                         AlnReq *d_reqs, SamDesc *d_desc);
-void launch_desc_overlay(void *stream, int n_pairs, const uint8_t *d_status, const SamDesc *d_from, SamDesc *d_to);
 
 // ---- decisions of the single-end reads that end in one record (se_kernel.hip) ----
 // status codes of se_simple_kernel (the numbers of pair_simple_kernel's codes where the test is the same)

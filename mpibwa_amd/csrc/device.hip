@@ -423,6 +423,62 @@ void contig_table(const bntseq_t *bns, std::vector<int64_t> &ann_off, std::vecto
 	for (int k = 0; k < bns->n_seqs; ++k) { ann_off[k] = bns->anns[k].offset; ann_alt[k] = bns->anns[k].is_alt ? 1 : 0; }
 }
 
+void aln_params(const mem_opt_t *opt, int64_t l_pac, AlnParams &ap, ExtParams &ep)
+{
+	ap.l_pac = l_pac; ap.a = opt->a; ap.w = opt->w;
+	memcpy(ep.mat, opt->mat, 25);
+	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
+}
+
+void cigar_gap_table(const mem_opt_t *opt, int max_len, std::vector<int> &tab)
+{
+	tab.resize(max_len + 2);
+	for (int l = 0; l <= max_len + 1; ++l) {
+		int max_ins = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_ins) / opt->e_ins + 1.);
+		int max_del = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_del) / opt->e_del + 1.);
+		int g = max_ins > max_del ? max_ins : max_del;
+		tab[l] = g > 1 ? g : 1;
+	}
+}
+
+SamParams sam_params(int64_t l_pac, bool has_qual)
+{
+	SamParams sp;
+	sp.l_pac = l_pac; sp.has_qual = has_qual ? 1 : 0;
+	sp.rg_len = (int)strnlen(bwa_rg_id, sizeof bwa_rg_id);
+	memset(sp.rg, 0, sizeof sp.rg);
+	memcpy(sp.rg, bwa_rg_id, (size_t)sp.rg_len);
+	return sp;
+}
+
+void contig_names(const bntseq_t *bns, std::vector<char> &names, std::vector<int> &name_off)
+{
+	name_off.assign(bns->n_seqs + 1, 0);
+	for (int k = 0; k < bns->n_seqs; ++k) name_off[k + 1] = name_off[k] + (int)strlen(bns->anns[k].name);
+	names.resize((size_t)name_off[bns->n_seqs] + 1);
+	for (int k = 0; k < bns->n_seqs; ++k) memcpy(names.data() + name_off[k], bns->anns[k].name, (size_t)(name_off[k + 1] - name_off[k]));
+}
+
+void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const ChunkDev &D, const SamParams &sp, const AlnSamJob &J, void *ev_a, void *ev_b)
+{
+	hipStream_t st = (hipStream_t)stream;
+	HIP_OK(hipMemsetAsync(J.d_cnt, 0, 256, st));
+	AlnParams ap;
+	ExtParams ep;
+	aln_params(opt, l_pac, ap, ep);
+	if (ev_a) HIP_OK(hipEventRecord((hipEvent_t)ev_a, st));
+	if (J.n_req) launch_aln(st, ap, ep, J.n_req, J.d_req, D.d_seq, D.d_off, D.d_pac, D.d_gap, J.d_hdr, J.d_pool, J.d_cnt, J.pool_bytes, D.max_len, D.max_len + 256, J.d_lists);
+	if (ev_b) HIP_OK(hipEventRecord((hipEvent_t)ev_b, st));
+	if (!J.n_reads) return;
+	const int r0 = J.r0, nr = J.n_reads, nu = nr / J.ends;
+	if (J.h_desc) HIP_OK(hipMemcpyAsync(J.d_desc + r0, J.h_desc + r0, (size_t)nr * sizeof(SamDesc), hipMemcpyHostToDevice, st));
+	HIP_OK(hipMemcpyAsync(J.d_base, J.h_base, (size_t)(nu + 1) * 4, hipMemcpyHostToDevice, st));
+	HIP_OK(hipMemsetAsync(J.d_used, 0, 64, st));
+	(J.ends == 2 ? launch_sam_emit : launch_sam_emit_se)(st, sp, nr, J.d_desc + r0, J.d_base, J.d_hdr, J.d_pool, D.d_seq, D.d_off + r0, D.d_len + r0, D.d_qual, D.d_names,
+	                                                   D.d_noff + r0, D.d_ann_off, D.d_ann_names, D.d_ann_noff, J.d_arena, J.arena_bytes, J.d_used, J.d_ooff, J.d_olen,
+	                                                   J.grid_blocks);
+}
+
 // band clamp of src/ksw.c:395-407 (host side, double arithmetic as in the reference)
 int clamp_band(const mem_opt_t *opt, int qlen, int w, int end_bonus)
 {
@@ -1097,13 +1153,9 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 		rq[i].rb = rb[i]; rq[i].re = re[i]; rq[i].read = read[i]; rq[i].qb = qb[i]; rq[i].qe = qe[i]; rq[i].w2 = w[i]; rq[i].truesc = truesc[i];
 		rq[i].pad = 0;
 	}
-	std::vector<int> gaptab(max_len + 2);
-	for (int l = 0; l <= max_len + 1; ++l) {   // max_gap of bwa_gen_cigar2 (src/bwa.c:155-158), as pipeline.hip tabulates it
-		int max_ins = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_ins) / opt->e_ins + 1.);
-		int max_del = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_del) / opt->e_del + 1.);
-		int g = max_ins > max_del ? max_ins : max_del;
-		gaptab[l] = g > 1 ? g : 1;
-	}
+	std::vector<int> gaptab;
+	cigar_gap_table(opt, max_len, gaptab);
+	// (not aln_pool_bytes: a test may ask for nothing but long gapped alignments, whose CIGAR and MD outgrow the pipeline's 96-byte average)
 	const size_t pool_bytes = (size_t)n_req * (4 * 96 + 768) + ((size_t)48 << 20);
 	uint8_t *d_seq, *d_pac, *d_pool; int64_t *d_off; AlnReq *d_req; AlnHdr *d_hdr; int *d_gap, *d_lists; unsigned long long *d_cnt;
 	HIP_OK(hipMalloc(&d_seq, flat.size())); HIP_OK(hipMalloc(&d_pac, l_pac / 4 + 16)); HIP_OK(hipMalloc(&d_pool, pool_bytes));
@@ -1117,10 +1169,8 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	HIP_OK(hipMemcpy(d_gap, gaptab.data(), gaptab.size() * 4, hipMemcpyHostToDevice));
 	HIP_OK(hipMemset(d_cnt, 0, 256));
 	AlnParams ap;
-	ap.l_pac = l_pac; ap.a = opt->a; ap.w = opt->w;
 	ExtParams ep;
-	memcpy(ep.mat, opt->mat, 25);
-	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
+	aln_params(opt, l_pac, ap, ep);
 	Timer tm;
 	tm.start(st);
 	launch_aln(st, ap, ep, n_req, d_req, d_seq, d_off, d_pac, d_gap, d_hdr, d_pool, d_cnt, pool_bytes, max_len, max_len + 256, d_lists, which != 0);
@@ -1147,7 +1197,7 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 }
 
 // Stage-level entry point of the SAM text kernel (tests): the CIGAR kernel and sam_emit_kernel on chosen line descriptors, queued on one
-// stream as the pipeline queues them for the pairs decided on the device (pipeline.hip: launch_dev).  Reads as nt4 codes in 16-byte
+// stream through the pipeline's own queue_aln_sam().  Reads as nt4 codes in 16-byte
 // slots like the pipeline's, qualities (or none) at the same places, names back to back; the read group is bwa_rg_id.  The arena is
 // followed by SAM_GUARD bytes that no record may touch; arena and guard are filled with SAM_GUARD_BYTE before the launch.
 #define SAM_GUARD 4096
@@ -1203,27 +1253,17 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 		fq.assign(flat.size(), 0);
 		for (int i = 0; i < n; ++i) memcpy(fq.data() + slot[i], quals + off[i], (size_t)lens[i]);
 	}
-	std::vector<int> gaptab(max_len + 2);
-	for (int l = 0; l <= max_len + 1; ++l) {   // max_gap of bwa_gen_cigar2 (src/bwa.c:155-158), as pipeline.hip tabulates it
-		int max_ins = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_ins) / opt->e_ins + 1.);
-		int max_del = (int)((double)(((l + 1) >> 1) * opt->mat[0] - opt->o_del) / opt->e_del + 1.);
-		int g = max_ins > max_del ? max_ins : max_del;
-		gaptab[l] = g > 1 ? g : 1;
-	}
+	std::vector<int> gaptab;
+	cigar_gap_table(opt, max_len, gaptab);
 	std::vector<int64_t> ann_off;
 	std::vector<uint8_t> ann_alt;
 	contig_table(bns, ann_off, ann_alt);
-	std::vector<int> cno(bns->n_seqs + 1, 0);
-	for (int k = 0; k < bns->n_seqs; ++k) cno[k + 1] = cno[k] + (int)strlen(bns->anns[k].name);
-	std::vector<char> cn((size_t)cno[bns->n_seqs] + 1);
-	for (int k = 0; k < bns->n_seqs; ++k) memcpy(cn.data() + cno[k], bns->anns[k].name, (size_t)(cno[k + 1] - cno[k]));
-	SamParams sp;
-	sp.l_pac = l_pac; sp.has_qual = quals ? 1 : 0;
-	sp.rg_len = (int)strnlen(bwa_rg_id, sizeof bwa_rg_id);
-	memset(sp.rg, 0, sizeof sp.rg);
-	memcpy(sp.rg, bwa_rg_id, (size_t)sp.rg_len);
+	std::vector<int> cno;
+	std::vector<char> cn;
+	contig_names(bns, cn, cno);
+	const SamParams sp = sam_params(l_pac, quals != nullptr);
 	if (!arena_bytes) arena_bytes = sam_arena_bytes(n, max_len);
-	const size_t pool_bytes = (size_t)std::max(n_req, 1) * 96 + ((size_t)48 << 20);   // as launch_dev sizes it
+	const size_t pool_bytes = aln_pool_bytes((size_t)std::max(n_req, 1));
 	const size_t n_names = (size_t)name_off[n];
 	uint8_t *d_seq, *d_qual = nullptr, *d_pac, *d_pool, *d_names, *d_arena; char *d_cn; int64_t *d_off, *d_ao; AlnReq *d_req; AlnHdr *d_hdr;
 	int *d_gap, *d_lists, *d_len, *d_noff, *d_cno, *d_base, *d_olen; unsigned long long *d_cnt, *d_used, *d_ooff; SamDesc *d_desc;
@@ -1248,22 +1288,19 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 	HIP_OK(hipMemcpy(d_cn, cn.data(), cn.size(), hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy(d_cno, cno.data(), cno.size() * 4, hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy(d_ao, ann_off.data(), ann_off.size() * 8, hipMemcpyHostToDevice));
-	HIP_OK(hipMemcpy(d_base, req_base, (size_t)(n_units + 1) * 4, hipMemcpyHostToDevice));
 	HIP_OK(hipMemcpy(d_desc, desc, (size_t)n * sizeof(SamDesc), hipMemcpyHostToDevice));
 	HIP_OK(hipMemset(d_hdr, 0, (size_t)std::max(n_req, 1) * sizeof(AlnHdr)));
 	HIP_OK(hipMemset(d_arena, SAM_GUARD_BYTE, arena_bytes + SAM_GUARD));
 	HIP_OK(hipMemset(d_ooff, 0, (size_t)n * 8));
 	HIP_OK(hipMemset(d_olen, 0xff, (size_t)n * 4));
-	HIP_OK(hipMemsetAsync(d_cnt, 0, 256, st));
-	HIP_OK(hipMemsetAsync(d_used, 0, 64, st));
-	AlnParams ap;
-	ap.l_pac = l_pac; ap.a = opt->a; ap.w = opt->w;
-	ExtParams ep;
-	memcpy(ep.mat, opt->mat, 25);
-	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
-	if (n_req) launch_aln(st, ap, ep, n_req, d_req, d_seq, d_off, d_pac, d_gap, d_hdr, d_pool, d_cnt, pool_bytes, max_len, max_len + 256, d_lists);
-	(ends == 2 ? launch_sam_emit : launch_sam_emit_se)(st, sp, n, d_desc, d_base, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_noff, d_ao, d_cn, d_cno,
-	                                                   d_arena, arena_bytes, d_used, d_ooff, d_olen, grid_blocks);
+	ChunkDev D;
+	D.d_seq = d_seq; D.d_off = d_off; D.d_len = d_len; D.max_len = max_len; D.d_pac = d_pac; D.d_gap = d_gap;
+	D.d_qual = d_qual; D.d_names = d_names; D.d_noff = d_noff; D.d_ann_off = d_ao; D.d_ann_names = d_cn; D.d_ann_noff = d_cno;
+	AlnSamJob J;
+	J.n_req = n_req; J.d_req = d_req; J.d_hdr = d_hdr; J.d_pool = d_pool; J.pool_bytes = pool_bytes; J.d_cnt = d_cnt; J.d_lists = d_lists;
+	J.ends = ends; J.n_reads = n; J.d_desc = d_desc; J.h_base = req_base; J.d_base = d_base;
+	J.d_arena = d_arena; J.arena_bytes = arena_bytes; J.d_used = d_used; J.d_ooff = d_ooff; J.d_olen = d_olen; J.grid_blocks = grid_blocks;
+	queue_aln_sam(st, opt, l_pac, D, sp, J);
 	HIP_OK(hipStreamSynchronize(st));
 	HIP_OK(hipGetLastError());
 	HIP_OK(hipMemcpy(out_len, d_olen, (size_t)n * 4, hipMemcpyDeviceToHost));

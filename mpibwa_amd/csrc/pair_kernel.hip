@@ -253,17 +253,4 @@ void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const De
 	                   (const i64 *)d_ann_off, d_ann_alt, d_ptab, d_ltab, d_status, d_reqs, d_desc);
 }
 
-// the descriptors of the pairs decided on the device go over the (empty) ones the host uploaded for them
-__global__ void desc_overlay_kernel(int n_pairs, const uint8_t *__restrict__ status, const SamDesc *__restrict__ from, SamDesc *__restrict__ to)
-{
-	const int r = blockIdx.x * blockDim.x + threadIdx.x;
-	if (r >= 2 * n_pairs) return;
-	if (status[r >> 1] == 1) to[r] = from[r];
-}
-void launch_desc_overlay(void *stream, int n_pairs, const uint8_t *d_status, const SamDesc *d_from, SamDesc *d_to)
-{
-	if (n_pairs <= 0) return;
-	hipLaunchKernelGGL(desc_overlay_kernel, dim3((2 * n_pairs + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_pairs, d_status, d_from, d_to);
-}
-
 } // namespace mbw

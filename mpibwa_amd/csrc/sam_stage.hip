@@ -1,0 +1,524 @@
+// sam_stage.hip — the second half of mem_process_seqs(): the inputs of the SAM kernels, the units decided on the
+// device, mate rescue, the host's decisions and request lists, the CIGAR-and-SAM jobs, the records, and the schedule of the parts.
+#include "pipeline.h"
+
+namespace mbw {
+
+static_assert(sizeof(SamDesc) == sizeof(SamDescH), "host/device record layouts differ");
+static_assert(sizeof(MswReq) == sizeof(MswReqH) && sizeof(MswRes) == sizeof(MswResH), "host/device record layouts differ");
+static_assert(sizeof(AlnReq) == sizeof(AlnReqH) && sizeof(AlnHdr) == sizeof(AlnHdrH), "host/device record layouts differ");
+static const int MSW_MAX_T = 4096;
+static bool cpusec_on() { static const bool on = getenv("MPIBWA_CPUSEC") != nullptr; return on; }
+
+// ---- inputs of the SAM stage (names, qualities, contig names, the gap table of the CIGAR kernel): packed and uploaded by a
+// thread of their own on a side stream while phase 1 runs — 100 MB of qualities per chunk that nothing before the SAM stage reads
+void Call::start_sam_inputs()
+{
+	// (reads so long that one request's arrays do not fit the LDS of a CU — beyond ~1 700 bp — get their CIGARs from the library's host code)
+	gpu_aln = getenv("MPIBWA_HOST_CIGAR") == nullptr && aln_lds_per_block(max_len, max_len + 256) <= (size_t)160 * 1024;
+	// Single-end input: the reads that end in one record are decided by se_simple_kernel and written by the single-end instantiation of
+	// sam_emit_kernel (se_kernel.hip); the rest of the chunk takes the host path.  MPIBWA_HOST_SE=1 keeps every read there.
+	// (-5: mem_reorder_primary5 stays host code, so the whole call does.)
+	se_want = !pe && gpu_aln && getenv("MPIBWA_HOST_SAM") == nullptr && getenv("MPIBWA_HOST_SE") == nullptr && opt->mapQ_coef_len > 0 &&
+	          !(opt->flag & (MEM_F_ALL | MEM_F_REF_HDR | MEM_F_PRIMARY5));
+	sam_inputs.t = std::thread([this] { sam_inputs_body(); });
+}
+
+// (sets gpu_sam, dev_se — se_want and the reads uniformly with or without qualities —, sam_par, sdesc and the SAM inputs of D: read
+// by the caller once the thread is joined)
+void Call::sam_inputs_body()
+{
+	HIP_OK(hipSetDevice(ix.device));
+	hipStream_t sst = C.d_streams[1];
+	std::vector<int> gaptab;
+	cigar_gap_table(opt, max_len, gaptab);
+	int *d_gap = (int *)W.agap.ensure(gaptab.size() * 4);
+	D.d_gap = d_gap;
+	HIP_OK(hipMemcpyAsync(d_gap, gaptab.data(), gaptab.size() * 4, hipMemcpyHostToDevice, sst));
+	// ---- SAM text of confidently paired reads on the device (sam_kernel.hip) ----
+	// The COLLECT pass describes the two lines of every pair that qualifies (AlnCtx::desc); the kernel runs right behind the
+	// CIGAR kernel of the part; the REPLAY pass only copies those records out of the arena and formats the rest itself.
+	gpu_sam = pe && gpu_aln && getenv("MPIBWA_HOST_SAM") == nullptr && !(opt->flag & (MEM_F_ALL | MEM_F_REF_HDR));
+	dev_se = se_want;
+	if (gpu_sam || dev_se) {
+		bool any_q = false, all_q = true;
+		for (int i = 0; i < n; ++i) { if (seqs[i].qual) any_q = true; else all_q = false; }
+		if (any_q && !all_q) gpu_sam = dev_se = false;   // a mix of reads with and without qualities: the host formats the chunk
+		if (dev_se) {   // a chunk whose reads all carry a comment (-C) is the host's: no set-up for a kernel that would take none
+			bool any_plain = false;
+			for (int i = 0; i < n && !any_plain; ++i) any_plain = !seqs[i].comment;
+			dev_se = any_plain;
+		}
+		sam_par = sam_params(bns->l_pac, any_q);
+	}
+	if (gpu_sam || dev_se) {
+		if (gpu_sam) sdesc = (SamDescH *)W.h_sdesc.ensure((size_t)n * sizeof(SamDescH) + 64);
+		int *noff = (int *)W.h_noff.ensure((size_t)(n + 1) * 4 + 64);
+		std::vector<int> nlen(n);
+		parallel_for(n_thr, n, 8192, [&](int i) { if (sdesc) sdesc[i].req = -1; nlen[i] = (int)strlen(seqs[i].name); });
+		noff[0] = 0;
+		for (int i = 0; i < n; ++i) noff[i + 1] = noff[i] + nlen[i];
+		uint8_t *names = (uint8_t *)W.h_names.ensure((size_t)noff[n] + 64);
+		uint8_t *hq = sam_par.has_qual ? (uint8_t *)W.h_qual.ensure(flat_bytes) : nullptr;
+		parallel_for(n_thr, n, 4096, [&](int i) {
+			memcpy(names + noff[i], seqs[i].name, (size_t)nlen[i]);
+			if (hq) memcpy(hq + off[i], seqs[i].qual, (size_t)seqs[i].l_seq);
+		});
+		uint8_t *dn = (uint8_t *)W.snames.ensure((size_t)noff[n] + 64);
+		int *dno = (int *)W.snoff.ensure((size_t)(n + 1) * 4);
+		HIP_OK(hipMemcpyAsync(dn, names, (size_t)noff[n], hipMemcpyHostToDevice, sst));
+		HIP_OK(hipMemcpyAsync(dno, noff, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, sst));
+		if (hq) {
+			uint8_t *dq = (uint8_t *)W.squal.ensure(flat_bytes);
+			HIP_OK(hipMemcpyAsync(dq, hq, flat_bytes, hipMemcpyHostToDevice, sst));
+			D.d_qual = dq;
+		}
+		std::vector<int> cno;
+		std::vector<char> cn;
+		contig_names(bns, cn, cno);
+		char *dcn = (char *)W.sann_names.ensure(cn.size() + 64);
+		int *dcno = (int *)W.sann_noff.ensure(cno.size() * 4);
+		HIP_OK(hipMemcpyAsync(dcn, cn.data(), cn.size(), hipMemcpyHostToDevice, sst));
+		HIP_OK(hipMemcpyAsync(dcno, cno.data(), cno.size() * 4, hipMemcpyHostToDevice, sst));
+		stream_wait(sst);
+		D.d_names = dn; D.d_noff = dno; D.d_ann_names = dcn; D.d_ann_noff = dcno;
+	}
+	stream_wait(sst);
+}
+
+// ---- units with one plain hit per read: decided on the device (pair_kernel.hip: pairs, ends = 2; se_kernel.hip: single-end reads
+// that end in one record, ends = 1) ----
+// status[k] = 1: the unit's CIGAR requests and line descriptors exist on the device; the host neither lists rescue alignments nor
+// marks primary hits nor plans nor formats it (it only copies the finished records out, or takes the unit back if the device hands
+// a record back).
+void Call::decide_on_device(int ends)
+{
+	const double tp0 = now_ms();
+	stage(9);
+	const int nu = n / ends;
+	PairParams pp;
+	size_t n_tab = 0;
+	mem_pestat_t none[4];
+	const bool usable = ends == 2 ? pair_params(opt, bns->l_pac, pes, n_processed, max_len, pp, &n_tab) : true;
+	if (ends == 1) se_params(opt, bns->l_pac, n_processed, max_len, pp, none);
+	if (usable) {
+		const size_t tab_n = n_tab + (size_t)pp.ltab_n;   // pair scores (none for single-end reads), then the per-length table
+		double *tab = (double *)W.h_pr_tab.ensure(tab_n * 8 + 64);
+		pair_tables(opt, ends == 2 ? pes : none, pp, n_tab, tab);
+		stage(28);
+		uint8_t *ok = (uint8_t *)W.h_pr_ok.ensure((size_t)nu + 64);
+		parallel_for(n_thr, nu, 8192, [&](int k) {
+			const bseq1_t *s = &seqs[ends * k];
+			ok[k] = ends == 2 ? !s[0].comment && !s[1].comment && strcmp(s[0].name, s[1].name) == 0 : !s[0].comment;
+		});
+		double *d_tab = (double *)W.pr_ptab.ensure(tab_n * 8 + 64);
+		uint8_t *d_ok = (uint8_t *)W.pr_ok.ensure((size_t)nu + 64);
+		uint8_t *d_status = (uint8_t *)W.pr_status.ensure((size_t)nu + 64);
+		AlnReq *d_rq = (AlnReq *)W.pr_req.ensure((size_t)n * sizeof(AlnReq));
+		SamDesc *d_ds = (SamDesc *)W.pr_desc.ensure((size_t)n * sizeof(SamDesc));
+		uint8_t *hs = (uint8_t *)W.h_pr_status.ensure((size_t)nu + 64);
+		HIP_OK(hipMemcpyAsync(d_tab, tab, tab_n * 8, hipMemcpyHostToDevice, st));
+		HIP_OK(hipMemcpyAsync(d_ok, ok, (size_t)nu, hipMemcpyHostToDevice, st));
+		if (ends == 2) launch_pair_simple(st, pp, nu, d_pr_first, d_pr_nfirst, d_ok, D.d_ann_off, D.d_ann_alt, d_tab, d_tab + n_tab, d_status, d_rq, d_ds);
+		else launch_se_simple(st, pp, nu, d_pr_first, d_pr_nfirst, d_ok, D.d_ann_alt, d_tab, d_status, d_rq, d_ds);
+		HIP_OK(hipMemcpyAsync(hs, d_status, (size_t)nu, hipMemcpyDeviceToHost, st));
+		stream_wait(st);
+		HIP_OK(hipGetLastError());
+		bool any_dev = ends == 2;   // (single-end, none taken: no device job over n empty requests)
+		if (ends == 1) se_codes = hs;
+		for (int i = 0; i < nu && !any_dev; ++i) any_dev = hs[i] == SE_DECIDED;
+		if (any_dev) { pstat = hs; d_pr_req = d_rq; d_pr_desc = d_ds; }
+	}
+	pair_dev_ms = now_ms() - tp0;
+}
+
+// ---- mate rescue on the device: list the local alignments the pairs of a part will ask for, run them in one launch ----
+void Call::mcollect(Part &P)
+{
+	stage(10);
+	if (!gpu_msw) return;
+	double ta = now_ms();
+	const double ca = cpu_sec();
+	const int nu = P.hi - P.lo, n_blk = (nu + 255) / 256;
+	std::vector<std::vector<MswReqH>> blk_req(n_blk);
+	std::vector<uint32_t> u_first(nu), u_cnt(nu);
+	parallel_for(n_thr, n_blk, 1, [&](int blk) {
+		std::vector<MswReqH> &rq = blk_req[blk];
+		rq.reserve(256);
+		const int lo = P.lo + blk * 256, hi = std::min(P.hi, lo + 256);
+		for (int i = lo; i < hi; ++i) {
+			const size_t before = rq.size();
+			if (!(pstat && pstat[i] == 1)) sam_pe_msw_collect(opt, bns, pes, &seqs[i << 1], &regs[i << 1], i << 1, MSW_MAX_T, rq);
+			u_first[i - P.lo] = (uint32_t)before; u_cnt[i - P.lo] = (uint32_t)(rq.size() - before);
+		}
+	});
+	P.mbase.assign(nu + 1, 0);
+	for (int i = 0; i < nu; ++i) P.mbase[i + 1] = P.mbase[i] + u_cnt[i];
+	P.n_mreq = P.mbase[nu];
+	P.mreq = (MswReqH *)W.h_mreq[P.slot].ensure(P.n_mreq * sizeof(MswReqH) + 64);
+	P.mres = (MswResH *)W.h_mres[P.slot].ensure(P.n_mreq * sizeof(MswResH) + 64);
+	parallel_for(n_thr, nu, 4096, [&](int i) {
+		if (u_cnt[i]) memcpy(&P.mreq[P.mbase[i]], &blk_req[i >> 8][u_first[i]], (size_t)u_cnt[i] * sizeof(MswReqH));
+	});
+	msw_ms += now_ms() - ta;
+	cpu_msw += cpu_sec() - ca;
+}
+
+void Call::mlaunch(Part &P)
+{
+	stage(11);
+	if (!gpu_msw || P.n_mreq == 0) return;
+	P.mst = C.a_streams[P.slot];
+	int max_t = 1;
+	for (size_t k = 0; k < P.n_mreq; ++k) max_t = std::max(max_t, (int)(P.mreq[k].re - P.mreq[k].rb));
+	MswReq *d_req = (MswReq *)W.mreq[P.slot].ensure(P.n_mreq * sizeof(MswReq));
+	MswRes *d_res = (MswRes *)W.mres[P.slot].ensure(P.n_mreq * sizeof(MswRes));
+	// row-maximum scratch: at most 2 GiB at a time
+	size_t per = std::max<size_t>(64, (((size_t)1 << 31) / ((size_t)max_t * 2)) & ~(size_t)63);
+	per = std::min(per, (P.n_mreq + 63) & ~(size_t)63);
+	uint16_t *d_rows = (uint16_t *)W.mrows[P.slot].ensure(per * (size_t)max_t * 2);
+	HIP_OK(hipMemcpyAsync(d_req, P.mreq, P.n_mreq * sizeof(MswReq), hipMemcpyHostToDevice, P.mst));
+	const MswParams mp = msw_params(opt, bns->l_pac);
+	P.mev.start(P.mst);
+	int *h_ml = (int *)W.h_mlist[P.slot].ensure(2 * P.n_mreq * sizeof(int) + 64), *d_ml = (int *)W.mlist[P.slot].ensure(2 * P.n_mreq * sizeof(int) + 64);
+	int *d_mt = (int *)W.mtail[P.slot].ensure(msw_tail_ints(per) * sizeof(int));   // (one batch after the other on the stream)
+	for (size_t b = 0; b < P.n_mreq; b += per) {
+		const int cnt = (int)std::min(per, P.n_mreq - b);
+		launch_msw(P.mst, mp, cnt, d_req + b, D.d_seq, D.d_off, D.d_len, D.d_pac, d_res + b, d_rows, max_len, (const MswReq *)(P.mreq + b), lens,
+		           h_ml + 2 * b, d_ml + 2 * b, d_mt);
+	}
+	P.mev.stop(P.mst);
+	HIP_OK(hipMemcpyAsync(P.mres, d_res, P.n_mreq * sizeof(MswRes), hipMemcpyDeviceToHost, P.mst));   // pinned: truly asynchronous
+	P.m_launched = true;
+}
+
+void Call::mfinish(Part &P)
+{
+	stage(12);
+	if (!P.m_launched) return;
+	double ta = now_ms();
+	stream_wait(P.mst);
+	HIP_OK(hipGetLastError());
+	STAT.k_msw_ms += P.mev.ms();
+	STAT.n_msw += P.n_mreq;
+	msw_ms += now_ms() - ta;
+}
+
+// A: decisions + the list of CIGARs to compute.  Two rounds, so that the units that asked for no mate-rescue alignment
+// (most of them) are done while msw_kernel is still running: round 0 = those units, round 1 = the rest + the flat list.
+void Call::collect(Part &P, int round)
+{
+	stage(13);
+	double ta = now_ms();
+	const double ca = cpu_sec();
+	const int nu = P.hi - P.lo, n_blk = (nu + 255) / 256;
+	if (round == 0) { P.blk_req.assign(n_blk, std::vector<AlnReqH>()); P.u_first.assign(nu, 0); P.u_cnt.assign(nu, 0); }
+	parallel_for(n_thr, n_blk, 1, [&](int blk) {
+		std::vector<AlnReqH> &rq = P.blk_req[blk];
+		if (round == 0) rq.reserve(256 * 3);
+		AlnCtx ctx;
+		ctx.mode = AlnCtx::COLLECT; ctx.reqs = &rq;
+		const int lo = P.lo + blk * 256, hi = std::min(P.hi, lo + 256);
+		unsigned long long tsc_plan_blk = 0, tsc_emitc_blk = 0;
+		for (int i = lo; i < hi; ++i) {
+			const int k = i - P.lo;
+			if (pstat && pstat[i] == 1) continue;   // decided on the device
+			const bool waits = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
+			if (waits != (round == 1)) continue;
+			const size_t before = rq.size();
+			if (pe) {
+				MswCtx mc;
+				if (waits) { mc.req = P.mreq + P.mbase[k]; mc.res = P.mres + P.mbase[k]; mc.n = (int)(P.mbase[k + 1] - P.mbase[k]); }
+				const unsigned long long c0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
+				sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[i << 1], &regs[i << 1], plans[i], waits ? &mc : nullptr,
+				            i << 1);
+				const unsigned long long c1 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
+				ctx.desc = gpu_sam ? &sdesc[i << 1] : nullptr;
+				if (gpu_aln) sam_pe_emit(opt, bns, pac, pes, &seqs[i << 1], &regs[i << 1], plans[i], &ctx, i << 1);
+				if (cpusec_on()) { tsc_plan_blk += c1 - c0; tsc_emitc_blk += __builtin_ia32_rdtsc() - c1; }
+			} else {
+				mark_primary_se(opt, regs[i], n_processed + i);
+				if (opt->flag & MEM_F_PRIMARY5) reorder_primary5(opt->T, regs[i]);
+				if (gpu_aln) reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, &ctx, i);
+			}
+			P.u_first[k] = (uint32_t)before; P.u_cnt[k] = (uint32_t)(rq.size() - before);
+		}
+		if (cpusec_on()) { tsc_plan += tsc_plan_blk; tsc_emitc += tsc_emitc_blk; }
+	});
+	if (round == 1) {
+		P.base.assign(nu + 1, 0);
+		for (int i = 0; i < nu; ++i) P.base[i + 1] = P.base[i] + P.u_cnt[i];
+		P.n_req = P.base[nu];
+		P.req = (AlnReqH *)W.h_areq[P.slot].ensure(P.n_req * sizeof(AlnReqH) + 64);
+		parallel_for(n_thr, nu, 4096, [&](int i) {
+			if (P.u_cnt[i]) memcpy(&P.req[P.base[i]], &P.blk_req[i >> 8][P.u_first[i]], (size_t)P.u_cnt[i] * sizeof(AlnReqH));
+		});
+	}
+	plan_ms += now_ms() - ta;
+	cpu_collect += cpu_sec() - ca;
+}
+
+// ---- the CIGAR-and-SAM job ----
+// Queue a job over the reads of part P on jst.  d_req: the requests where they are on the device, or null: P.req is uploaded.  base:
+// the first request of every unit, or null: `ends` requests per unit.  with_sam: the records behind the CIGARs, from the descriptors
+// d_desc (of the chunk; h_desc given: the part's are uploaded first).
+void Call::job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const AlnReq *d_req, size_t n_req, const uint32_t *base, bool with_sam,
+                      const SamDescH *h_desc, SamDesc *d_desc)
+{
+	const int ends = pe ? 2 : 1;   // reads per unit
+	const int nu = P.hi - P.lo, nr = nu * ends;
+	J.B = &B; J.st = jst; J.n_req = n_req; J.n_reads = nr;
+	J.pool_bytes = aln_pool_bytes(n_req);
+	AlnSamJob Q;
+	AlnReq *d_up = d_req ? nullptr : (AlnReq *)B.req.ensure(n_req * sizeof(AlnReq));
+	J.d_hdr = (AlnHdr *)B.hdr.ensure(n_req * sizeof(AlnHdr));
+	J.d_pool = (uint8_t *)B.pool.ensure(J.pool_bytes);
+	J.d_cnt = (unsigned long long *)B.cnt.ensure(256);
+	if (d_up) HIP_OK(hipMemcpyAsync(d_up, P.req, n_req * sizeof(AlnReq), hipMemcpyHostToDevice, jst));
+	Q.n_req = (int)n_req; Q.d_req = d_req ? d_req : d_up; Q.d_hdr = J.d_hdr; Q.d_pool = J.d_pool; Q.pool_bytes = J.pool_bytes; Q.d_cnt = J.d_cnt;
+	Q.d_lists = (int *)B.lists.ensure(n_req * 3 * sizeof(int));
+	if (with_sam) {
+		int *hb = (int *)B.h_base.ensure((size_t)(nu + 1) * 4 + 64);
+		for (int k = 0; k <= nu; ++k) hb[k] = base ? (int)base[k] : ends * k;
+		J.arena_bytes = sam_arena_bytes(nr, max_len);
+		Q.ends = ends; Q.r0 = P.lo * ends; Q.n_reads = nr;
+		Q.h_desc = (const SamDesc *)h_desc; Q.d_desc = d_desc;
+		Q.h_base = hb; Q.d_base = (int *)B.base.ensure((size_t)(nu + 1) * 4);
+		Q.d_arena = (uint8_t *)B.arena.ensure(J.arena_bytes); Q.arena_bytes = J.arena_bytes;
+		Q.d_used = (unsigned long long *)B.used.ensure(64);
+		Q.d_ooff = (unsigned long long *)B.ooff.ensure((size_t)nr * 8);
+		Q.d_olen = (int *)B.olen.ensure((size_t)nr * 4);
+	}
+	// (the results are fetched in job_fetch: a D2H copy into pageable memory would block the host here)
+	queue_aln_sam(jst, opt, bns->l_pac, D, sam_par, Q, J.ev.a, J.ev.b);
+	J.launched = true; J.sam_launched = with_sam;
+}
+
+// the CIGAR results of a job: counters, then headers and what is used of the pool
+static void fetch_results(Job &J)
+{
+	JobBufs &B = *J.B;
+	HIP_OK(hipMemcpyAsync(J.small_cnt, J.d_cnt, 64, hipMemcpyDeviceToHost, J.st));
+	stream_wait(J.st);
+	const size_t used = std::min<size_t>(J.small_cnt[0], J.pool_bytes);
+	AlnHdrH *hh = (AlnHdrH *)B.h_hdr.ensure(J.n_req * sizeof(AlnHdr) + 64);
+	uint8_t *hp = (uint8_t *)B.h_pool.ensure(used + 64);
+	HIP_OK(hipMemcpyAsync(hh, J.d_hdr, J.n_req * sizeof(AlnHdr), hipMemcpyDeviceToHost, J.st));
+	if (used) HIP_OK(hipMemcpyAsync(hp, J.d_pool, used, hipMemcpyDeviceToHost, J.st));
+	stream_wait(J.st);
+	J.hdr = hh; J.pool = hp;
+}
+
+// its records: the arena cursor, then what is used of the arena, offsets and lengths
+static void fetch_records(Job &J)
+{
+	JobBufs &B = *J.B;
+	const int nr = J.n_reads;
+	HIP_OK(hipMemcpyAsync(J.small_used, B.used.p, 8, hipMemcpyDeviceToHost, J.st));
+	stream_wait(J.st);
+	const unsigned long long used = std::min<unsigned long long>(J.small_used[0], J.arena_bytes);
+	uint8_t *ha = (uint8_t *)B.h_arena.ensure((size_t)used + 64);
+	unsigned long long *ho = (unsigned long long *)B.h_ooff.ensure((size_t)nr * 8 + 64);
+	int *hl = (int *)B.h_olen.ensure((size_t)nr * 4 + 64);
+	if (used) HIP_OK(hipMemcpyAsync(ha, B.arena.p, (size_t)used, hipMemcpyDeviceToHost, J.st));
+	HIP_OK(hipMemcpyAsync(ho, B.ooff.p, (size_t)nr * 8, hipMemcpyDeviceToHost, J.st));
+	HIP_OK(hipMemcpyAsync(hl, B.olen.p, (size_t)nr * 4, hipMemcpyDeviceToHost, J.st));
+	stream_wait(J.st);
+	J.sarena = ha; J.sooff = ho; J.solen = hl;
+}
+
+// Wait for a job and fetch what the host needs of it.  FETCH_ALWAYS: the CIGAR results, then the records (the host's units: REPLAY reads
+// the results).  FETCH_IF_HANDED_BACK: the records, and the CIGAR results only if a unit decided on the device comes back without a
+// record (CIGAR declined, row overflow): the host redoes that unit and needs them.
+void Call::job_fetch(Job &J, const Part &P, Fetch policy)
+{
+	if (!J.launched) return;
+	const double ta = now_ms();
+	stream_wait(J.st);
+	HIP_OK(hipGetLastError());
+	STAT.k_aln_ms += J.ev.ms();
+	STAT.n_aln += J.n_req;
+	if (policy == FETCH_ALWAYS) fetch_results(J);
+	if (J.sam_launched) fetch_records(J);
+	if (policy == FETCH_IF_HANDED_BACK) {
+		const int ends = pe ? 2 : 1;
+		bool any_back = false;
+		for (int k = 0; k < P.hi - P.lo && !any_back; ++k)
+			for (int e = 0; e < ends; ++e) any_back = any_back || (pstat[P.lo + k] == 1 && J.solen[ends * k + e] < 0);
+		if (any_back) fetch_results(J);
+	}
+	aln_wait_ms += now_ms() - ta;
+}
+
+// The units decided on the device need nothing from the host any more: their CIGARs and records are queued right behind the
+// deciding kernel, on a stream of their own, and run under the host's rescue listing, planning and the mate-rescue kernel.
+void Call::launch_dev(Part &P)
+{
+	stage(14);
+	if (!pstat || P.hi == P.lo) return;
+	const int ends = pe ? 2 : 1;   // reads (and requests) per unit
+	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(256);
+	P.dev.small_used = small; P.dev.small_cnt = small + 8;
+	job_launch(P.dev, W.dev_job[P.slot], C.d_streams[P.slot], P, d_pr_req + (size_t)P.lo * ends, (size_t)(P.hi - P.lo) * ends, nullptr, true, nullptr,
+	           const_cast<SamDesc *>(d_pr_desc));
+}
+void Call::finish_dev(Part &P)
+{
+	stage(15);
+	job_fetch(P.dev, P, FETCH_IF_HANDED_BACK);
+}
+void Call::launch(Part &P)   // B (asynchronous)
+{
+	stage(16);
+	if (!gpu_aln || P.n_req == 0) return;
+	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(256);
+	P.host.small_cnt = small + 16; P.host.small_used = small + 24;
+	// (gpu_sam: the records of the part's qualifying pairs, queued right behind their CIGARs)
+	SamDesc *d_desc = gpu_sam ? (SamDesc *)W.sdesc.ensure((size_t)n * sizeof(SamDesc)) : nullptr;
+	job_launch(P.host, W.host_job[P.slot], C.a_streams[P.slot], P, nullptr, P.n_req, P.base.data(), gpu_sam, sdesc, d_desc);
+}
+void Call::finish(Part &P)   // wait for B, fetch the pool
+{
+	stage(17);
+	job_fetch(P.host, P, FETCH_ALWAYS);
+	if (cpusec_on() && P.host.launched) {
+		unsigned long long c[16];
+		HIP_OK(hipMemcpy(c, P.host.d_cnt, sizeof c, hipMemcpyDeviceToHost));
+		fprintf(stderr, "[aln lists] %zu requests: same-length %llu, narrow DP %llu, full DP %llu\n", P.host.n_req, c[8], c[9], c[10]);
+	}
+}
+
+// ---- C: the records ----
+// a finished record out of a job's arena: ownership passes to the caller, who free()s it
+void Call::take_record(int read, const Job &J, int at)
+{
+	const int len = J.solen[at];
+	char *sam = (char *)malloc((size_t)len + 1);
+	if (!sam) die("out of memory");
+	memcpy(sam, J.sarena + J.sooff[at], (size_t)len);
+	sam[len] = 0;
+	seqs[read].sam = sam;
+}
+
+// which: 0 = the records of the units decided on the device (as soon as their job is back: the copies run under the kernels
+// of the other units), 1 = everything else, 2 = both
+void Call::replay(Part &P, int which)
+{
+	stage(18);
+	const double ta = now_ms(), ca = cpu_sec(), sa_ = sys_sec();
+	const long pf = page_faults();
+	const int ends = pe ? 2 : 1;
+	// (a single-end chunk without reads of the device's has no pass 0)
+	// per-block counters: a shared atomic bumped once per unit costs more than copying the unit's records
+	if (pe || which != 0 || pstat) parallel_blocks(n_thr, P.hi - P.lo, pe ? 128 : 256, [&](int, int, int k_lo, int k_hi) {
+		unsigned long long n_dev = 0, tsc = 0;
+		for (int k = k_lo; k < k_hi; ++k) {
+			const int i = P.lo + k, r = ends * i;   // the unit, its first read
+			const bool dev_k = pstat && pstat[i] == 1;
+			const Job &J = dev_k ? P.dev : P.host;
+			bool written = J.solen != nullptr;   // every record of the unit was written by sam_emit_kernel
+			for (int e = 0; e < ends && written; ++e) written = J.solen[ends * k + e] >= 0;
+			const bool early = dev_k && written;   // pass 0's units
+			if (which != 2 && early != (which == 0)) continue;
+			if (written) {
+				const unsigned long long tq0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
+				for (int e = 0; e < ends; ++e) take_record(r + e, J, ends * k + e);
+				n_dev += ends;
+				if (cpusec_on()) tsc += __builtin_ia32_rdtsc() - tq0;
+				continue;
+			}
+			AlnCtx ctx;
+			if (gpu_aln) { ctx.mode = AlnCtx::REPLAY; ctx.hdr = P.host.hdr; ctx.pool = P.host.pool; ctx.cursor = P.base[k]; }
+			// the device decided the unit but handed a record back: the host decides it again (the same `ends` requests, same order)
+			if (dev_k) { ctx.hdr = P.dev.hdr; ctx.pool = P.dev.pool; ctx.cursor = (size_t)ends * k; }
+			if (pe) {
+				if (dev_k) sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[r], &regs[r], plans[i], nullptr, r);
+				sam_pe_emit(opt, bns, pac, pes, &seqs[r], &regs[r], plans[i], gpu_aln ? &ctx : nullptr, r);
+			} else {
+				if (dev_k) mark_primary_se(opt, regs[i], n_processed + i);
+				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln ? &ctx : nullptr, i);
+			}
+		}
+		n_sam_dev += n_dev; tsc_devcopy += tsc;
+	});
+	emit_ms += now_ms() - ta;
+	cpu_emit += cpu_sec() - ca;
+	sys_emit += sys_sec() - sa_; pf_emit += page_faults() - pf;
+}
+
+// ---- pairing decisions, then CIGAR/MD/NM on the GPU, then SAM text ----
+// Per part of the chunk:  A  decisions + a COLLECT pass that records which regions need a global re-alignment
+// (mem_reg2aln's DP);  B  aln_kernel does them all at once;  C  the same emission again (REPLAY) with the results
+// plugged in.  Two parts are software-pipelined so that B of one part runs while the host does A / C of the other.
+void Call::sam_stage()
+{
+	n_units = pe ? n >> 1 : n;
+	plans.resize(pe ? n_units : 0);
+	n_parts = (gpu_aln && n_units >= 20000 && n_sub > 1) ? 2 : 1;
+	if (const char *e = getenv("MPIBWA_SAM_PARTS")) n_parts = std::max(1, std::min(2, atoi(e)));
+	gpu_msw = pe && !(opt->flag & MEM_F_NO_RESCUE) && getenv("MPIBWA_HOST_MATESW") == nullptr && (int64_t)max_len * opt->a < 8192 &&
+	          msw_lds_bytes(max_len) <= 160 * 1024;
+	// When does the device units' job go out?  Alone, right behind the pairing kernel (its kernels and the copies of its records run
+	// under the host's work on the other pairs: 94.8-96.8 vs 98.7-102.8 ms per chunk); with other calls in flight, next to the host
+	// pairs' job (their kernels fill the gaps anyway and an early launch only delays their seeding: 12.0-12.7 vs 10.9-11.3 Mreads/s).
+	// MPIBWA_DEV_JOB_LATE=0/1 forces either.
+	const char *dle = getenv("MPIBWA_DEV_JOB_LATE");
+	const bool dev_late = dle ? atoi(dle) != 0 : crowded;
+	// Single-end calls have no rescue listing to run the device job under: its records are fetched once the host's reads are planned
+	// and their CIGAR job is out (dev_mid), so that the job runs under the planning and the copies of its records under that kernel.
+	// Where the device job of a part is fetched (finish_dev + replay 0), relative to the host reads' CIGAR job (launch .. finish):
+	//   dev_early  pairs, one call in flight     launch_dev, rescue listing, FETCH, collect, launch, finish          (as before)
+	//   dev_last   pairs, other calls in flight  rescue listing, collect, launch_dev, launch, finish, FETCH          (as before)
+	//   dev_mid    single-end, either            launch_dev (before or after collect, by dev_late), launch, FETCH, finish
+	// Exactly one of the three holds; replay 1 (the host's records) closes every part.
+	const bool dev_early = pe && !dev_late, dev_mid = !pe, dev_last = pe && dev_late;
+	for (int p = 0; p < n_parts; ++p) {   // (slot 0: the whole chunk or its first half)
+		parts[p].slot = p;
+		parts[p].lo = p ? n_units / 2 : 0;
+		parts[p].hi = p == n_parts - 1 ? n_units : n_units / 2;
+	}
+	if (!dev_late)
+		for (int p = 0; p < n_parts; ++p) launch_dev(parts[p]);
+	for (int p = 0; p < n_parts; ++p) { mcollect(parts[p]); mlaunch(parts[p]); }
+	for (int p = 0; p < n_parts; ++p) {   // (the mate-rescue kernels of all parts are running)
+		Part &P = parts[p];
+		if (dev_early) { finish_dev(P); replay(P, 0); }
+		collect(P, 0); mfinish(P); collect(P, 1);
+		if (dev_late) launch_dev(P);
+		launch(P);
+	}
+	for (int p = 0; p < n_parts; ++p) {
+		Part &P = parts[p];
+		if (dev_mid) { finish_dev(P); replay(P, 0); }
+		finish(P);
+		if (dev_last) { finish_dev(P); replay(P, 0); }
+		if (n_parts == 1) hprof_report("decisions + request lists");
+		replay(P, 1);
+	}
+	STAT.plan_ms = plan_ms; STAT.aln_ms = aln_wait_ms; STAT.msw_ms = msw_ms; STAT.emit_ms = emit_ms;
+	STAT.n_sam_dev = n_sam_dev.load();
+	report_decisions();
+	STAT.plan_ms += pair_dev_ms;
+}
+
+// how many units the device decided, and (MPIBWA_CPUSEC) why the others went to the host
+void Call::report_decisions()
+{
+	if (!pstat && !se_codes) return;
+	const uint8_t *codes = pstat ? pstat : se_codes;
+	uint64_t c[16] = {0};
+	for (int k = 0; k < n_units; ++k) ++c[codes[k] & 15];
+	if (pe) STAT.n_pair_dev = c[1];
+	else {
+		STAT.n_se_dev = c[1];
+		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu\n",
+		                      n_units, (unsigned long long)c[SE_DECIDED], (unsigned long long)c[SE_HOST_COMMENT], PR_MAXREG, (unsigned long long)c[SE_HOST_MAXREG],
+		                      (unsigned long long)c[SE_HOST_PATCH], (unsigned long long)c[SE_HOST_LENGTH], (unsigned long long)c[SE_HOST_ALT],
+		                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA]);
+	}
+	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu\n",
+	                      n_units, (unsigned long long)c[1], (unsigned long long)c[2], PR_MAXREG, (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[6],
+	                      (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11]);
+}
+
+} // namespace mbw
