@@ -313,6 +313,21 @@ int mi355x_pair_maxreg(void);
 int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], int64_t n_processed, int n_pairs,
                       const void *regs, const int *n_regs, int max_len, uint8_t *status, void *desc, void *req);
 
+/* The same decisions for the pairs pair_simple_kernel leaves because they need mate rescue, carry more than mi355x_pair_maxreg() regions
+ * on an end, or have one end without a region: pair_wave_kernel, a pair per wavefront, up to mi355x_pair_wave_maxreg() regions per end.
+ * The entry runs the pipeline's sequence: the host lists the rescue windows (src/bwamem_pair.c:131-150), the mate-rescue kernel aligns
+ * them, pair_wave_kernel replays mem_sam_pe with the results (rescue loop :265-276 with mem_matesw :111-180, primary marking, mem_pair,
+ * MAPQ with csub, the XA test).  2 n_pairs reads as nt4 codes (read r = reads[off[r] .. off[r+1])); regs: both ends' regions AFTER
+ * mem_sort_dedup_patch, 64-byte records back to back (the layout of mi355x_pair_batch), read r owns regs[reg_off[r] .. reg_off[r+1]).
+ * status, desc, req: as mi355x_pair_batch returns them; codes besides its own: 0 not handed to the kernel (a list that is not a fixed
+ * point of the redundancy pass, more than mi355x_pair_wave_maxreg() regions, an ALT hit, no region on either end), 12 a rescue
+ * alignment the replay needs is not on the device, 13 a list grows past mi355x_pair_wave_maxreg(), 14 the outcome depends on the
+ * order the reference's unstable sorts give equal keys.  *n_align: local alignments run.  Returns 0, or -1 as mi355x_pair_batch. */
+int mi355x_pair_wave_maxreg(void);
+int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                           int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                           void *desc, void *req, int *n_align);
+
 /* SAM text of the pairs decided on the device: the CIGAR kernel (aln_kernel) and sam_emit_kernel, queued on one stream as the
  * pipeline queues them, on chosen line descriptors.  2 n_pairs reads as nt4 codes (read r = reads[off[r] .. off[r+1])), their
  * qualities at the same places (or NULL: QUAL is '*'), their names back to back (read r = names[name_off[r] .. name_off[r+1])); the
@@ -403,6 +418,7 @@ typedef struct {
 	uint64_t n_sam_dev;                          /* SAM records written by sam_kernel (the rest are formatted by the host) */
 	uint64_t n_pair_dev;                         /* pairs whose pairing decisions (mem_sam_pe) were taken on the device (pair_kernel.hip) */
 	uint64_t n_se_dev;                           /* single-end reads decided on the device (se_kernel.hip); their records count in n_sam_dev */
+	uint64_t n_pair_wave_dev;                    /* pairs with mate rescue or up to 64 hits per end decided on the device (pair_wave_kernel.hip); not counted in n_pair_dev */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

@@ -19,7 +19,7 @@ EXPORTS = [
     "mi355x_finalize", "mi355x_index_build", "mi355x_index_build_gpu",
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
-    "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch",
+    "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
 ]
 
 
@@ -112,6 +112,8 @@ def load_library(build_if_missing=True):
     sig("mi355x_device_memory", C.c_int, [P(C.c_size_t), P(C.c_size_t)])
     sig("mi355x_buffer_growths", C.c_ulonglong, [])
     sig("mi355x_pair_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("mi355x_pair_wave_maxreg", C.c_int, [])
+    sig("mi355x_pair_wave_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 8)
     sig("mi355x_global_batch", C.c_int, [P(abi.mem_opt_t), C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 +
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_double)])
     sig("mi355x_sam_arena_bytes", C.c_size_t, [C.c_int, C.c_int])
@@ -387,6 +389,32 @@ class Engine:
         if rc != 0:
             raise RuntimeError("mi355x_pair_batch: the kernel cannot use these insert-size statistics")
         return status, desc, req
+
+    def pairs_wave(self, opt, pes, reads, regs, n_processed=0):
+        """pair_wave_kernel behind the pipeline's own rescue listing and mate-rescue kernel (mi355x_pair_wave_batch).  reads: 2 n_pairs nt4
+        code arrays; regs: per read a REG_DT array of its regions after mem_sort_dedup_patch (at most mi355x_pair_wave_maxreg() are taken).
+        -> status (n_pairs,) uint8, desc (2 n_pairs,) DESC_DT, req (2 n_pairs,) AREQ_DT, number of local alignments run"""
+        n = len(reads)
+        assert n % 2 == 0 and len(regs) == n
+        n_pairs = n // 2
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint8) for r in reads])) if n else np.zeros(1, dtype=np.uint8)
+        reg_off = np.zeros(n + 1, dtype=np.int32)
+        reg_off[1:] = np.cumsum([len(r) for r in regs])
+        allregs = np.zeros(max(1, int(reg_off[-1])), dtype=self.REG_DT)
+        for r, a in enumerate(regs):
+            allregs[reg_off[r]:reg_off[r + 1]] = np.asarray(a, dtype=self.REG_DT)
+        status = np.zeros(n_pairs, dtype=np.uint8)
+        desc = np.zeros(n, dtype=self.DESC_DT)
+        req = np.zeros(n, dtype=self.AREQ_DT)
+        n_align = C.c_int(0)
+        rc = self.lib.mi355x_pair_wave_batch(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), C.cast(pes, C.c_void_p), n_processed, n_pairs,
+                                             flat.ctypes.data, off.ctypes.data, allregs.ctypes.data, reg_off.ctypes.data, status.ctypes.data,
+                                             desc.ctypes.data, req.ctypes.data, C.cast(C.byref(n_align), C.c_void_p))
+        if rc != 0:
+            raise RuntimeError("mi355x_pair_wave_batch: the kernel cannot use these insert-size statistics")
+        return status, desc, req, n_align.value
 
     def singles(self, opt, regs, n_regs, max_len=150, n_processed=0):
         """se_simple_kernel on single-end reads given by their regions: regs (n_reads, mi355x_pair_maxreg()) of REG_DT, n_regs (n_reads).

@@ -282,6 +282,8 @@ void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const Sam
                         uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
                         int grid_blocks = 0);
 
+struct MswReq;
+struct MswRes;
 // ---- pairing decisions of the pairs with one plain hit per end (pair_kernel.hip) ----
 #define PR_MAXREG 8               // regions per read the kernel looks at (a read with more is the host's); 4 until round 4
 extern "C" int mi355x_pair_maxreg(void);
@@ -295,6 +297,7 @@ struct PairParams {
 	int low[4], high[4], failed[4];   // mem_pestat_t per orientation
 	int tab_off[4];           // start of each orientation's run in the pair-score table: entry [dist - low]
 	int ltab_n;               // entries of the per-length table
+	int max_XA_hits;          // min(max_XA_hits, max_XA_hits_alt): more qualifying secondary hits than this and no XA string is written (pair_wave_kernel)
 };
 // PairParams from the options and the insert-size statistics; false when the kernel cannot take this chunk (a degenerate
 // distribution); *n_tab = entries of the pair-score table.  pair_tables fills tab[n_tab + P.ltab_n] (scores, then the per-length table).
@@ -307,6 +310,33 @@ void launch_first_reg(void *stream, int n, const int *d_reg_pos, const int *d_nr
 void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,
                         const int64_t *d_ann_off, const uint8_t *d_ann_alt, const double *d_ptab, const double *d_ltab, uint8_t *d_status,
                         AlnReq *d_reqs, SamDesc *d_desc);
+
+// ---- pairing decisions of the pairs with mate rescue or up to PW_MAXREG hits per end (pair_wave_kernel.hip), a pair per wavefront ----
+#define PW_MAXREG 64              // regions per end, going in and while rescued hits are added
+extern "C" int mi355x_pair_wave_maxreg(void);
+// status codes of pair_wave_kernel: pair_simple_kernel's where the test is the same (6 ALT/length, 8 no proper pair, 9 score, 10 second
+// primary hit, 11 XA), and three of its own
+#define PW_HOST_LENGTH 6
+#define PW_HOST_NO_PAIR 8
+#define PW_HOST_SCORE 9
+#define PW_HOST_SUPP 10
+#define PW_HOST_XA 11
+#define PW_HOST_NO_RESULT 12      // a rescue alignment the replay needs is not on the device (not listed, flagged by msw2_kernel, host only)
+#define PW_HOST_FULL 13           // a list past PW_MAXREG
+#define PW_HOST_TIE 14            // the outcome depends on the reference's unstable sorts (equal end positions, equal (score, hash))
+// tags per (end, candidate hit, orientation): >= 0 the alignment's number in the pair's slice of the mate-rescue requests
+#define PW_TAG_NO_WINDOW (-1)     // mem_matesw would align nothing there (src/bwamem_pair.c:150)
+#define PW_TAG_HOST (-2)          // not listed (explained by a mate hit before any rescue) or a window msw2_kernel does not take
+// work[t]: the pair's number in the chunk (reads 2 work[t], 2 work[t] + 1 of d_len); reqs / desc [2t + e] are written when
+// wstatus[t] = 1 and left alone otherwise; lists[loff[2t + e] .. loff[2t + e + 1]): end e's regions after mem_sort_dedup_patch;
+// mreq / mres[mfirst[t] + tag]; tags[toff[t] ..]: 4 per candidate hit, end 0's candidates first
+void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
+                      const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
+                      const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc);
+// the decided pairs' records into the chunk-wide arrays (reqs / desc [2 work[t] + e]); clear_n > 0: reads clear_r0 .. + clear_n are
+// marked "not the device's" first (the arrays then describe the wave's pairs alone)
+void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const uint8_t *d_wstatus, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                              AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
 
 // ---- decisions of the single-end reads that end in one record (se_kernel.hip) ----
 // status codes of se_simple_kernel (the numbers of pair_simple_kernel's codes where the test is the same)

@@ -517,6 +517,7 @@ bool pair_params(const mem_opt_t *opt, int64_t l_pac, const mem_pestat_t pes[4],
 		}
 	}
 	pp.ltab_n = 4 * max_len + 256;
+	pp.max_XA_hits = std::min(opt->max_XA_hits, opt->max_XA_hits_alt);
 	*n_tab_ = n_tab;
 	return usable;
 }
@@ -617,6 +618,152 @@ extern "C" int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, cons
 	HIP_OK(hipMemcpy(req, d_rq, n * sizeof(AlnReq), hipMemcpyDeviceToHost));
 	(void)hipFree(d_first); (void)hipFree(d_nf); (void)hipFree(d_ok); (void)hipFree(d_aa); (void)hipFree(d_st); (void)hipFree(d_ao); (void)hipFree(d_tab);
 	(void)hipFree(d_rq); (void)hipFree(d_ds);
+	return 0;
+}
+
+// Stage entry of pair_wave_kernel (pair_wave_kernel.hip) for parity tests.  It runs the pipeline's own sequence — the host lists the
+// mate-rescue windows with their tags (sam_pe_msw_collect_tagged), launch_msw aligns them, pair_wave_kernel replays mem_sam_pe — on
+// n_pairs pairs given by their reads (nt4 codes, off[2 n_pairs + 1]) and both ends' regions as they stand after mem_sort_dedup_patch
+// (regs: DevReg records back to back, reg_off[2 n_pairs + 1]).  A pair whose lists are not fixed points of the redundancy pass, hold more
+// than PW_MAXREG regions or an ALT hit, or that has no region at all, is not handed to the kernel (status 0).  status[k] = 1: decided —
+// desc[2k], desc[2k + 1] (SamDesc) and req[2k], req[2k + 1] (AlnReq) are what mem_sam_pe's paired branch reports; else the code of the
+// test that left the pair to the host.  *n_align = mate-rescue alignments run.  Returns 0, or -1 when the insert-size statistics are not
+// usable by the kernel.
+extern "C" int mi355x_pair_wave_maxreg(void) { return PW_MAXREG; }
+extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                      int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                      void *desc, void *req, int *n_align)
+{
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
+	if (n_align) *n_align = 0;
+	if (n_pairs <= 0) return 0;
+	const int n_reads = 2 * n_pairs;
+	memset(status, 0, (size_t)n_pairs);
+	memset(desc, 0xff, (size_t)n_reads * sizeof(SamDesc));
+	memset(req, 0xff, (size_t)n_reads * sizeof(AlnReq));
+	// (the calls whose pairs are all the host's, as for pair_simple_kernel: -P, -a, -V, -5, mapQ_coef_len 0)
+	if ((opt->flag & (MEM_F_NOPAIRING | MEM_F_ALL | MEM_F_REF_HDR | MEM_F_PRIMARY5)) || !(opt->mapQ_coef_len > 0)) return 0;
+	const int64_t l_pac = bns->l_pac;
+	std::vector<int64_t> slot(n_reads + 1);
+	std::vector<int> lens(n_reads);
+	int max_len = 1;
+	slot[0] = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		lens[i] = (int)(off[i + 1] - off[i]);
+		slot[i + 1] = slot[i] + ((lens[i] + 15) & ~15);
+		max_len = std::max(max_len, lens[i]);
+	}
+	if ((int64_t)max_len * opt->a >= 8192 || msw_lds_bytes(max_len) > 160 * 1024) die("mate-rescue kernel: reads too long for the device path");
+	PairParams pp;
+	size_t n_tab = 0;
+	if (!pair_params(opt, l_pac, pes, n_processed, max_len, pp, &n_tab)) return -1;
+	std::vector<double> tab(n_tab + (size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, n_tab, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
+	// ---- the host's part: eligibility, windows, tags ----
+	const DevReg *hr = (const DevReg *)regs;
+	std::vector<int> work, loff(1, 0), toff;
+	std::vector<unsigned> mfirst;
+	std::vector<DevReg> lists;
+	std::vector<MswReqH> mreq;
+	std::vector<int16_t> tags;
+	std::vector<bseq1_t> s(2);
+	for (int k = 0; k < n_pairs; ++k) {
+		status[k] = 0;
+		HRegV a[2];
+		bool ok = true;
+		for (int e = 0; e < 2 && ok; ++e) {
+			for (int j = reg_off[2 * k + e]; j < reg_off[2 * k + e + 1]; ++j) {
+				const DevReg &d = hr[j];
+				if (d.rid < 0 || d.rid >= bns->n_seqs) die("mi355x_pair_wave_batch: bad contig in a region of pair %d", k);
+				HReg h;
+				h.rb = d.rb; h.re = d.re; h.qb = d.qb; h.qe = d.qe; h.rid = d.rid; h.score = d.score; h.truesc = d.truesc; h.w = d.w;
+				h.seedcov = d.seedcov; h.seedlen0 = d.seedlen0; h.frac_rep = d.frac_rep; h.secondary = -1; h.is_alt = bns->anns[d.rid].is_alt;
+				a[e].push_back(h);
+			}
+			// settled = another redundancy pass without patching returns the list as it is
+			HRegV c;
+			for (size_t j = 0; j < a[e].size(); ++j) c.push_back(a[e][j]);
+			sort_dedup_patch(opt, 0, 0, 0, c);
+			ok = c.size() == a[e].size() && c.settled;
+			for (size_t j = 0; j < c.size() && ok; ++j) ok = c[j].rb == a[e][j].rb && c[j].re == a[e][j].re && c[j].qb == a[e][j].qb && c[j].score == a[e][j].score;
+			a[e].settled = ok;
+		}
+		if (!ok || !pair_wave_eligible(a, PW_MAXREG)) continue;
+		s[0].l_seq = lens[2 * k]; s[1].l_seq = lens[2 * k + 1];
+		work.push_back(k);
+		mfirst.push_back((unsigned)mreq.size());
+		toff.push_back((int)tags.size());
+		sam_pe_msw_collect_tagged(opt, bns, pes, s.data(), a, 2 * k, 4096, mreq, tags);
+		for (int e = 0; e < 2; ++e) {
+			lists.insert(lists.end(), hr + reg_off[2 * k + e], hr + reg_off[2 * k + e + 1]);
+			loff.push_back((int)lists.size());
+		}
+	}
+	const int n_work = (int)work.size();
+	toff.push_back((int)tags.size());
+	const size_t n_mreq = mreq.size();
+	if (n_align) *n_align = (int)n_mreq;
+	if (n_work == 0) return 0;
+	// ---- device ----
+	hipStream_t st = 0;
+	std::vector<uint8_t> flat(slot[n_reads] + 16, 4);
+	for (int i = 0; i < n_reads; ++i) memcpy(flat.data() + slot[i], reads + off[i], lens[i]);
+	int max_t = 1;
+	for (size_t i = 0; i < n_mreq; ++i) max_t = std::max(max_t, (int)(mreq[i].re - mreq[i].rb));
+	std::vector<void *> owned;
+	auto up = [&](const void *h, size_t bytes) -> void * {
+		void *d = nullptr;
+		HIP_OK(hipMalloc(&d, bytes + 64));
+		owned.push_back(d);
+		if (h && bytes) HIP_OK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+		return d;
+	};
+	uint8_t *d_seq = (uint8_t *)up(flat.data(), flat.size());
+	uint8_t *d_pac = (uint8_t *)up(pac, (size_t)(l_pac / 4 + 1));
+	int64_t *d_off = (int64_t *)up(slot.data(), (size_t)(n_reads + 1) * 8);
+	int *d_len = (int *)up(lens.data(), (size_t)n_reads * 4);
+	MswReq *d_mreq = (MswReq *)up(mreq.data(), n_mreq * sizeof(MswReq));
+	MswRes *d_mres = (MswRes *)up(nullptr, n_mreq * sizeof(MswRes));
+	if (n_mreq) {
+		uint16_t *d_rows = (uint16_t *)up(nullptr, n_mreq * (size_t)max_t * 2);
+		std::vector<int> h_list(2 * n_mreq + 16);
+		int *d_list = (int *)up(nullptr, (2 * n_mreq + 16) * sizeof(int));
+		int *d_tail = (int *)up(nullptr, msw_tail_ints(n_mreq) * sizeof(int));
+		launch_msw(st, msw_params(opt, l_pac), (int)n_mreq, d_mreq, d_seq, d_off, d_len, d_pac, d_mres, d_rows, max_len, (const MswReq *)mreq.data(), lens.data(),
+		           h_list.data(), d_list, d_tail);
+		HIP_OK(hipStreamSynchronize(st));   // (h_list is read by the copy queued in launch_msw)
+	}
+	int *d_work = (int *)up(work.data(), (size_t)n_work * 4);
+	DevReg *d_lists = (DevReg *)up(lists.data(), lists.size() * sizeof(DevReg));
+	int *d_loff = (int *)up(loff.data(), loff.size() * 4);
+	unsigned *d_mfirst = (unsigned *)up(mfirst.data(), mfirst.size() * 4);
+	short *d_tags = (short *)up(tags.data(), tags.size() * 2);
+	int *d_toff = (int *)up(toff.data(), toff.size() * 4);
+	int64_t *d_ao = (int64_t *)up(ann_off.data(), ann_off.size() * 8);
+	double *d_tab = (double *)up(tab.data(), tab.size() * 8);
+	uint8_t *d_ws = (uint8_t *)up(nullptr, (size_t)n_work);
+	AlnReq *d_rq = (AlnReq *)up(nullptr, (size_t)2 * n_work * sizeof(AlnReq));
+	SamDesc *d_ds = (SamDesc *)up(nullptr, (size_t)2 * n_work * sizeof(SamDesc));
+	HIP_OK(hipMemset(d_ws, 0, (size_t)n_work));
+	launch_pair_wave(st, pp, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst, d_tags, d_toff, d_ao, d_tab, d_tab + n_tab, d_ws, d_rq, d_ds);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	std::vector<uint8_t> ws((size_t)n_work);
+	HIP_OK(hipMemcpy(ws.data(), d_ws, (size_t)n_work, hipMemcpyDeviceToHost));
+	std::vector<SamDesc> w_ds((size_t)2 * n_work);
+	std::vector<AlnReq> w_rq((size_t)2 * n_work);
+	HIP_OK(hipMemcpy(w_ds.data(), d_ds, w_ds.size() * sizeof(SamDesc), hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(w_rq.data(), d_rq, w_rq.size() * sizeof(AlnReq), hipMemcpyDeviceToHost));
+	for (int t = 0; t < n_work; ++t) {
+		status[work[t]] = ws[t];
+		if (ws[t] != 1) continue;
+		for (int e = 0; e < 2; ++e) { ((SamDesc *)desc)[2 * work[t] + e] = w_ds[2 * t + e]; ((AlnReq *)req)[2 * work[t] + e] = w_rq[2 * t + e]; }
+	}
+	for (void *d : owned) (void)hipFree(d);
 	return 0;
 }
 

@@ -244,6 +244,13 @@ void sam_pe_plan(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, 
                  HRegV a[2], PairPlan &plan, const MswCtx *mctx = nullptr, int read0 = 0);
 void sam_pe_msw_collect(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], const bseq1_t s[2], const HRegV a[2], int read0,
                         int max_tlen, std::vector<MswReqH> &out);
+// the same list, and for pair_wave_kernel (device.h) one tag per (end, candidate hit, orientation) — 4 per candidate, end 0's candidates
+// first —: the request's number counted from the pair's first, or why there is none (PW_TAG_NO_WINDOW / PW_TAG_HOST)
+void sam_pe_msw_collect_tagged(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], const bseq1_t s[2], const HRegV a[2], int read0,
+                               int max_tlen, std::vector<MswReqH> &out, std::vector<int16_t> &tags);
+// may pair_wave_kernel look at the pair?  Both lists fixed points of mem_sort_dedup_patch (or empty, but not both), at most max_reg
+// regions each, none on an ALT contig
+bool pair_wave_eligible(const HRegV a[2], int max_reg);
 void sam_pe_emit(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], bseq1_t s[2], HRegV a[2],
                  const PairPlan &plan, AlnCtx *ctx, int read0);
 

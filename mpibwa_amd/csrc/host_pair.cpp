@@ -409,6 +409,46 @@ void sam_pe_msw_collect(const mem_opt_t *opt, const bntseq_t *bns, const mem_pes
 	}
 }
 
+void sam_pe_msw_collect_tagged(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], const bseq1_t s[2], const HRegV a[2], int read0,
+                               int max_tlen, std::vector<MswReqH> &out, std::vector<int16_t> &tags)
+{
+	if (opt->flag & MEM_F_NO_RESCUE) return;
+	const size_t first = out.size();
+	for (int i = 0; i < 2; ++i) {
+		if (a[i].empty()) continue;
+		const int l_ms = s[!i].l_seq;
+		int nb = 0;
+		for (size_t j = 0; j < a[i].size() && nb < opt->max_matesw; ++j) {
+			if (a[i][j].score < a[i][0].score - opt->pen_unpaired) continue;
+			++nb;
+			int skip[4];
+			matesw_skips(bns, pes, &a[i][j], a[!i], skip);
+			for (int r = 0; r < 4; ++r) {
+				MswReqH q;
+				int is_rev;
+				// (an orientation a mate hit explains now is only needed if a later rescue removes that hit: no window is computed for it)
+				if (skip[r]) { tags.push_back(-2); continue; }
+				if (!matesw_window(opt, bns, pes, &a[i][j], l_ms, r, &q.rb, &q.re, &is_rev)) { tags.push_back(-1); continue; }
+				if (q.re - q.rb > max_tlen || out.size() - first >= 32000) { tags.push_back(-2); continue; }
+				q.read = read0 + !i; q.is_rev = is_rev;
+				tags.push_back((int16_t)(out.size() - first));
+				out.push_back(q);
+			}
+		}
+	}
+}
+
+bool pair_wave_eligible(const HRegV a[2], int max_reg)
+{
+	if (a[0].empty() && a[1].empty()) return false;
+	for (int e = 0; e < 2; ++e) {
+		if ((int)a[e].size() > max_reg || !(a[e].empty() || a[e].settled)) return false;
+		for (size_t j = 0; j < a[e].size(); ++j)
+			if (a[e][j].is_alt) return false;
+	}
+	return true;
+}
+
 struct Pair64 { uint64_t x, y; };
 static inline bool pair_lt(const Pair64 &a, const Pair64 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
 

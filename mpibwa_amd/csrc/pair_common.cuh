@@ -2,7 +2,7 @@
 // (se_kernel.hip): the reference's region clean-up, primary marking and single-end MAPQ for the short region lists both look at.
 //   mem_sort_dedup_patch  src/bwamem.c:437-489   (dedup_small, with ks_introsort's order for up to 16 elements: small_introsort)
 //   mem_mark_primary_se   src/bwamem.c:493-569   (mark_primary, reads without ALT hits; hash_64: src/utils.h:98-109)
-//   mem_approx_mapq_se    src/bwamem.c:952-976   (mapq_se, csub = 0)
+//   mem_approx_mapq_se    src/bwamem.c:952-976   (mapq_se; the two short-list kernels pass csub = 0)
 //   infer_bw              src/bwamem.c:792-800   (the band of mem_reg2aln's global alignment)
 // Floating point: the expressions are evaluated in the reference's types and order (the library is built with -ffp-contract=off).
 #ifndef MBW_PAIR_COMMON_CUH
@@ -117,25 +117,31 @@ __device__ __forceinline__ u64 hash_64(u64 key)   // src/utils.h:98-109
 	return key;
 }
 #define RAW_MAPQ(diff, a) ((int)(6.02 * (diff) / (a) + .499))
-// mem_approx_mapq_se (src/bwamem.c:952-976) with csub = 0 (no hit of these reads comes from mate rescue)
-__device__ __forceinline__ int mapq_se(const PairParams &P, const PReg &r, const double *__restrict__ ltab)
+// mem_approx_mapq_se (src/bwamem.c:952-976); l = max(query span, reference span); csub: the score of a tandem copy (a hit that comes from
+// mate rescue carries one, src/bwamem_pair.c:163; 0 for every other hit)
+__device__ __forceinline__ int mapq_se_of(const PairParams &P, int score, int sub_, int sub_n, int csub, int l, float frac_rep, const double *__restrict__ ltab)
 {
-	const int sub = r.sub ? r.sub : P.min_seed_len * P.a;
-	if (sub >= r.d.score) return 0;
-	const int l = r.d.qe - r.d.qb > r.d.re - r.d.rb ? r.d.qe - r.d.qb : (int)(r.d.re - r.d.rb);
-	const double identity = 1. - (double)(l * P.a - r.d.score) / (P.a + P.b) / l;
+	int sub = sub_ ? sub_ : P.min_seed_len * P.a;
+	sub = csub > sub ? csub : sub;
+	if (sub >= score) return 0;
+	const double identity = 1. - (double)(l * P.a - score) / (P.a + P.b) / l;
 	int mapq;
-	if (r.d.score == 0) mapq = 0;
+	if (score == 0) mapq = 0;
 	else {
 		double tmp = ltab[l];
 		tmp *= identity * identity;
-		mapq = (int)(6.02 * (r.d.score - sub) / P.a * tmp * tmp + .499);
+		mapq = (int)(6.02 * (score - sub) / P.a * tmp * tmp + .499);
 	}
-	if (r.sub_n > 0) mapq -= P.lnq[r.sub_n];
+	if (sub_n > 0) mapq -= P.lnq[sub_n];
 	if (mapq > 60) mapq = 60;
 	if (mapq < 0) mapq = 0;
-	mapq = (int)(mapq * (1. - r.d.frac_rep) + .499);
+	mapq = (int)(mapq * (1. - frac_rep) + .499);
 	return mapq;
+}
+__device__ __forceinline__ int mapq_se(const PairParams &P, const PReg &r, const double *__restrict__ ltab, int csub)
+{
+	const int l = r.d.qe - r.d.qb > r.d.re - r.d.rb ? r.d.qe - r.d.qb : (int)(r.d.re - r.d.rb);
+	return mapq_se_of(P, r.d.score, r.sub, r.sub_n, csub, l, r.d.frac_rep, ltab);
 }
 __device__ __forceinline__ int infer_bw(int l1, int l2, int score, int a, int q, int r)
 {

@@ -199,7 +199,7 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		for (int e = 0; e < 2; ++e) {
 			PReg &c = a[e][z[e]];
 			if (c.secondary >= 0) { c.sub = a[e][c.secondary].d.score; c.secondary = -2; }
-			q_se[e] = mapq_se(P, c, ltab);
+			q_se[e] = mapq_se(P, c, ltab, 0);
 		}
 		q_se[0] = q_se[0] > q_pe ? q_se[0] : q_pe < q_se[0] + 40 ? q_pe : q_se[0] + 40;
 		q_se[1] = q_se[1] > q_pe ? q_se[1] : q_pe < q_se[1] + 40 ? q_pe : q_se[1] + 40;
@@ -209,8 +209,8 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		q_se[1] = q_se[1] < cb ? q_se[1] : cb;
 	} else {
 		z[0] = z[1] = 0;
-		q_se[0] = mapq_se(P, a[0][0], ltab);
-		q_se[1] = mapq_se(P, a[1][0], ltab);
+		q_se[0] = mapq_se(P, a[0][0], ltab, 0);
+		q_se[1] = mapq_se(P, a[1][0], ltab, 0);
 	}
 	for (int e = 0; e < 2; ++e) {   // the chosen hit was secondary: swap roles with its parent (src/bwamem_pair.c:332-339)
 		const int kk = a[e][z[e]].secondary_all;

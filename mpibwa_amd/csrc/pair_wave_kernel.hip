@@ -1,0 +1,507 @@
+// pair_wave_kernel.hip — mem_sam_pe for the pairs that need mate rescue or carry up to 64 hits per end: a pair per wavefront.
+//
+// Device counterpart of
+//   mem_sam_pe            src/bwamem_pair.c:250-393   (rescue loop :265-276, primary marking, pairing, MAPQ, the two records)
+//   mem_matesw            src/bwamem_pair.c:111-180   (everything but the window and ksw_align2: the windows are listed by the host,
+//                                                       the alignments are msw2_kernel's results, already on the device)
+//   mem_sort_dedup_patch  src/bwamem.c:437-489        (as :176 calls it — no reference sequence, so nothing is patched — on a list that
+//                                                       is a fixed point of the pass plus one new hit: host_pair.cpp insert_into_settled)
+//   mem_mark_primary_se   src/bwamem.c:493-569        (reads without ALT hits)
+//   mem_pair              src/bwamem_pair.c:182-243
+//   mem_approx_mapq_se    src/bwamem.c:952-976        (with csub: a rescued hit carries the score of its tandem copy)
+//   mem_gen_alt           src/bwamem_extra.c:98-118   (only "does the chosen hit get an XA string?")
+//   mem_reg2aln           src/bwamem.c:1089-1105      (the band of the final global alignment)
+// The pairs are the ones pair_simple_kernel leaves with "rescue", "more than eight hits" or "one end without a hit".  The host hands over
+// both ends' lists as they stand after mem_sort_dedup_patch (fixed points of the pass: HRegV::settled), at most PW_MAXREG regions each,
+// none on an ALT contig, and per (end, candidate hit, orientation) a tag: the number of the alignment in the pair's slice of the
+// mate-rescue results, "the window is invalid: the reference aligns nothing", or "not on the device".
+//
+// One region per lane, both lists in LDS as one array per field (no bank conflicts, 2 x 64 x 64 B), mem_pair's keys behind them
+// (128 x 16 B) and the rescue candidates: 11 776 B of LDS per wave, 54 VGPRs, no scratch (the compiler's resource usage for gfx950).  The two sorts are rank sorts: mem_pair's keys are unique, so any sort gives the reference's array; two
+// hits with equal (score, hash) in mem_mark_primary_se — where the reference's unstable sort would decide — send the pair to the host.
+// The list u of mem_pair is never stored: only its maximum, the second-largest score and n_sub are used, so it is enumerated twice
+// and reduced.  Anything the wave cannot settle the way the reference does leaves the pair to the host with a code that says why.
+//
+// Floating point: as in pair_kernel.hip — the reference's types and order, -ffp-contract=off, the two transcendental sites tabulated.
+#include <hip/hip_runtime.h>
+#include "pair_common.cuh"
+
+namespace mbw {
+
+struct WList {   // the regions of one end, one array per field of mem_alnreg_t that mem_sam_pe reads
+	i64 rb[PW_MAXREG], re[PW_MAXREG];
+	int qb[PW_MAXREG], qe[PW_MAXREG], rid[PW_MAXREG], score[PW_MAXREG], truesc[PW_MAXREG], w[PW_MAXREG], csub[PW_MAXREG];
+	int sub[PW_MAXREG], sub_n[PW_MAXREG], secondary[PW_MAXREG], secondary_all[PW_MAXREG];
+	float frac_rep[PW_MAXREG];
+};
+struct WReg {
+	i64 rb, re;
+	int qb, qe, rid, score, truesc, w, csub, sub, sub_n, secondary, secondary_all;
+	float frac_rep;
+};
+__device__ __forceinline__ WReg wl_get(const WList &L, int i)
+{
+	WReg r;
+	r.rb = L.rb[i]; r.re = L.re[i]; r.qb = L.qb[i]; r.qe = L.qe[i]; r.rid = L.rid[i]; r.score = L.score[i]; r.truesc = L.truesc[i]; r.w = L.w[i];
+	r.csub = L.csub[i]; r.sub = L.sub[i]; r.sub_n = L.sub_n[i]; r.secondary = L.secondary[i]; r.secondary_all = L.secondary_all[i]; r.frac_rep = L.frac_rep[i];
+	return r;
+}
+__device__ __forceinline__ void wl_put(WList &L, int i, const WReg &r)
+{
+	L.rb[i] = r.rb; L.re[i] = r.re; L.qb[i] = r.qb; L.qe[i] = r.qe; L.rid[i] = r.rid; L.score[i] = r.score; L.truesc[i] = r.truesc; L.w[i] = r.w;
+	L.csub[i] = r.csub; L.sub[i] = r.sub; L.sub_n[i] = r.sub_n; L.secondary[i] = r.secondary; L.secondary_all[i] = r.secondary_all; L.frac_rep[i] = r.frac_rep;
+}
+
+struct Pair64 { u64 x, y; };
+__device__ __forceinline__ bool pair_lt64(const Pair64 &a, const Pair64 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
+
+__device__ __forceinline__ i64 wave_max(i64 v)
+{
+	for (int d = 32; d; d >>= 1) { const i64 o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
+	return v;
+}
+__device__ __forceinline__ i64 wave_min(i64 v)
+{
+	for (int d = 32; d; d >>= 1) { const i64 o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
+	return v;
+}
+__device__ __forceinline__ u64 wave_maxu(u64 v)
+{
+	for (int d = 32; d; d >>= 1) { const u64 o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
+	return v;
+}
+__device__ __forceinline__ int wave_sum(int v)
+{
+	for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+	return v;
+}
+
+__device__ __forceinline__ int pw_infer_dir(i64 l_pac, i64 b1, i64 b2, i64 *dist)   // src/bwamem_pair.c:23-30
+{
+	const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
+	const i64 p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
+	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
+	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
+}
+
+// q ends first; p looks back at it (src/bwamem.c:448-455)
+__device__ __forceinline__ bool pw_redundant(const PairParams &P, i64 q_rb, i64 q_re, int q_qb, int q_qe, i64 p_rb, i64 p_re, int p_qb, int p_qe)
+{
+	if (!(p_rb < q_re + P.max_chain_gap)) return false;
+	const i64 orr = q_re - p_rb;
+	const i64 oq = q_qb < p_qb ? q_qe - p_qb : p_qe - q_qb;
+	const i64 mr = q_re - q_rb < p_re - p_rb ? q_re - q_rb : p_re - p_rb;
+	const i64 mq = q_qe - q_qb < p_qe - p_qb ? q_qe - q_qb : p_qe - p_qb;
+	return orr > P.mask_level_redun * mr && oq > P.mask_level_redun * mq;
+}
+
+// The redundancy pass on "a fixed point of it + the new hit b" (host_pair.cpp insert_into_settled; the argument why this is
+// the reference's list is there).  Every lane holds a hit of the list M.  Returns 0, or the code of why the pair is the host's.
+__device__ __forceinline__ int pw_insert(const PairParams &P, WList &M, int &n, const WReg &b, int lane)
+{
+	bool red = false;
+	i64 e_re = 0;
+	int e_sc = 0;
+	if (lane < n && M.rid[lane] == b.rid) {
+		const i64 e_rb = M.rb[lane];
+		const int e_qb = M.qb[lane], e_qe = M.qe[lane];
+		e_re = M.re[lane]; e_sc = M.score[lane];
+		// (equal end positions: either may be the one the pass visits first)
+		red = e_re < b.re ? pw_redundant(P, e_rb, e_re, e_qb, e_qe, b.rb, b.re, b.qb, b.qe)
+		    : e_re > b.re ? pw_redundant(P, b.rb, b.re, b.qb, b.qe, e_rb, e_re, e_qb, e_qe)
+		    : (pw_redundant(P, e_rb, e_re, e_qb, e_qe, b.rb, b.re, b.qb, b.qe) || pw_redundant(P, b.rb, b.re, b.qb, b.qe, e_rb, e_re, e_qb, e_qe));
+	}
+	const u64 R = __ballot(red);
+	bool b_alive = true;
+	u64 dead = 0;
+	if (R) {
+		if (!__ballot(red && e_sc >= b.score)) dead = R;   // all of them score less: they die, b stays, whatever the order
+		else {
+			// the order of the events is that of the end positions: defined when these are distinct
+			if (__ballot(red && e_re == b.re)) return PW_HOST_TIE;
+			for (u64 m = R; m; m &= m - 1) {
+				const int j = __ffsll((long long)m) - 1;
+				const i64 re_j = M.re[j];
+				if (__ballot(red && lane != j && e_re == re_j)) return PW_HOST_TIE;
+			}
+			const i64 NONE_LO = (i64)0x8000000000000000ull, NONE_HI = ~NONE_LO;
+			// b looks back, nearest first: the hits that end before it die until one scores more, which kills b
+			const i64 killer_b = wave_max(red && e_re < b.re && e_sc > b.score ? e_re : NONE_LO);
+			if (killer_b != NONE_LO) { b_alive = false; dead = __ballot(red && e_re < b.re && e_re > killer_b); }
+			else {
+				dead = __ballot(red && e_re < b.re);
+				// the hits behind b meet it in turn: they die until one scores at least b's, which kills b
+				const i64 killer_a = wave_min(red && e_re > b.re && e_sc >= b.score ? e_re : NONE_HI);
+				if (killer_a != NONE_HI) { b_alive = false; dead |= __ballot(red && e_re > b.re && e_re < killer_a); }
+				else dead |= __ballot(red && e_re > b.re);
+			}
+		}
+	}
+	if (!dead && !b_alive) return 0;
+	// the survivors keep their order; b goes to its place by (score desc, rb, qb)
+	const u64 valid = n >= 64 ? ~(u64)0 : ((u64)1 << n) - 1;
+	const u64 alive = valid & ~dead;
+	const int n_new = __popcll(alive) + (b_alive ? 1 : 0);
+	if (n_new > PW_MAXREG) return PW_HOST_FULL;
+	const bool keep = (alive >> lane) & 1;
+	WReg me;
+	bool before_b = false;
+	if (keep) {
+		me = wl_get(M, lane);
+		before_b = me.score > b.score || (me.score == b.score && (me.rb < b.rb || (me.rb == b.rb && me.qb < b.qb)));
+	}
+	const int at = __popcll(__ballot(before_b));
+	const int pos = __popcll(alive & (((u64)1 << lane) - 1)) + (b_alive && !before_b ? 1 : 0);
+	__syncthreads();
+	if (keep) wl_put(M, pos, me);
+	if (b_alive && lane == 0) wl_put(M, at, b);
+	__syncthreads();
+	n = n_new;
+	return 0;
+}
+
+// mem_mark_primary_se (src/bwamem.c:521-569, its core :493-519) on one end, a hit per lane; H: 64 x 2 u64 of scratch.  false: two hits
+// compare equal in the sort by (score desc, hash)
+__device__ __forceinline__ bool pw_mark_primary(const PairParams &P, WList &A, int n, u64 id, Pair64 *H, int lane)
+{
+	if (n == 0) return true;
+	WReg me;
+	u64 h = 0;
+	if (lane < n) {
+		me = wl_get(A, lane);
+		h = hash_64(id + (u64)lane);
+		H[lane].x = h; H[lane].y = (u64)(unsigned)me.score;
+	}
+	__syncthreads();
+	int rank = 0;
+	bool tie = false;
+	if (lane < n)
+		for (int j = 0; j < n; ++j) {
+			const int sc = (int)H[j].y;
+			const u64 hj = H[j].x;
+			if (sc > me.score || (sc == me.score && hj < h)) ++rank;
+			else if (j != lane && sc == me.score && hj == h) tie = true;
+		}
+	if (__ballot(tie)) return false;
+	__syncthreads();
+	if (lane < n) { me.sub = 0; me.secondary = me.secondary_all = -1; wl_put(A, rank, me); }
+	__syncthreads();
+	int tmp = P.a + P.b;
+	tmp = P.o_del + P.e_del > tmp ? P.o_del + P.e_del : tmp;
+	tmp = P.o_ins + P.e_ins > tmp ? P.o_ins + P.e_ins : tmp;
+	int qb = 0, qe = 0, sc = 0, sub = 0, sub_n = 0, sec = -1;
+	if (lane < n) { qb = A.qb[lane]; qe = A.qe[lane]; sc = A.score[lane]; sub_n = A.sub_n[lane]; }
+	for (int i = 1; i < n; ++i) {   // hit i against the primary hits before it, in their order: the first it overlaps is its parent
+		const int qb_i = A.qb[i], qe_i = A.qe[i], sc_i = A.score[i];
+		bool ov = false;
+		if (lane < i && sec < 0) {
+			const int b_max = qb > qb_i ? qb : qb_i;
+			const int e_min = qe < qe_i ? qe : qe_i;
+			if (e_min > b_max) {
+				const int min_l = qe_i - qb_i < qe - qb ? qe_i - qb_i : qe - qb;
+				ov = e_min - b_max >= min_l * P.mask_level;   // significant overlap on the query
+			}
+		}
+		const u64 m = __ballot(ov);
+		if (m) {
+			const int j = __ffsll((long long)m) - 1;
+			if (lane == j) {
+				if (sub == 0) sub = sc_i;
+				if (sc - sc_i <= tmp) ++sub_n;
+			}
+			if (lane == i) sec = j;
+		}
+	}
+	if (lane < n) { A.sub[lane] = sub; A.sub_n[lane] = sub_n; A.secondary[lane] = sec; A.secondary_all[lane] = sec; }
+	__syncthreads();
+	return true;
+}
+
+// the candidate pairs (v[kk], v[i]) of mem_pair for one i (src/bwamem_pair.c:203-227): f(p) for each of them, p as the reference builds it
+template <class F>
+__device__ __forceinline__ void pw_pairs_of(const PairParams &P, const Pair64 *V, int i, int idi, const double *__restrict__ ptab, F f)
+{
+	const Pair64 vi = V[i];
+	for (int r = 0; r < 2; ++r) {
+		const int dir = r << 1 | (int)(vi.y >> 1 & 1);
+		if (P.failed[dir]) continue;
+		const int which = r << 1 | (int)((vi.y & 1) ^ 1);
+		for (int kk = i - 1; kk >= 0; --kk) {   // (the reference starts at the last key of kind `which` before i: the ones between are skipped here)
+			const Pair64 vk = V[kk];
+			if ((int)(vk.y & 3) != which) continue;
+			const i64 dist = (i64)vi.x - (i64)vk.x;
+			if (dist > P.high[dir]) break;
+			if (dist < P.low[dir]) continue;
+			int q = (int)((double)((vi.y >> 32) + (vk.y >> 32)) + ptab[P.tab_off[dir] + (int)(dist - P.low[dir])] + .499);
+			if (q < 0) q = 0;
+			Pair64 p;
+			p.y = (u64)kk << 32 | (u64)i;
+			p.x = (u64)q << 32 | (hash_64(p.y ^ (u64)(i64)idi) & 0xffffffffU);
+			f(p);
+		}
+	}
+}
+
+#define PW_GIVE_UP(code) do { if (lane == 0) wstatus[t] = (uint8_t)(code); return; } while (0)
+
+// work[t]: the pair (number in the chunk); its lists: lists[loff[2t + e] .. loff[2t + e + 1]); its mate-rescue alignments:
+// mreq / mres[mfirst[t] ..]; tags[toff[t] + 4 * (candidate) + orientation], the candidates of end 0 first, then end 1's (toff: n_work + 1 entries).
+// wstatus[t] = 1: reqs / desc [2t + e] are the pair's, as pair_simple_kernel writes them (reqs.read = 2 work[t] + e); else untouched.
+__global__ void __launch_bounds__(64)
+pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const DevReg *__restrict__ lists, const int *__restrict__ loff,
+                 const int *__restrict__ len, const MswReq *__restrict__ mreq, const MswRes *__restrict__ mres, const unsigned *__restrict__ mfirst,
+                 const short *__restrict__ tags, const int *__restrict__ toff, const i64 *__restrict__ ann_off, const double *__restrict__ ptab,
+                 const double *__restrict__ ltab, uint8_t *__restrict__ wstatus, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
+{
+	__shared__ WList L[2];
+	__shared__ Pair64 V[2 * PW_MAXREG];
+	__shared__ i64 c_rb[2][PW_MAXREG];   // the candidate hits of the rescue loop: what mem_matesw reads of them
+	__shared__ int c_rid[2][PW_MAXREG];
+	const int t = blockIdx.x, lane = threadIdx.x;
+	if (t >= n_work) return;
+	const int k = work[t];
+	int n[2];
+	for (int e = 0; e < 2; ++e) {
+		const int b = loff[2 * t + e];
+		n[e] = loff[2 * t + e + 1] - b;
+		if (n[e] > PW_MAXREG) PW_GIVE_UP(PW_HOST_FULL);
+		if (lane < n[e]) {
+			const DevReg d = lists[b + lane];
+			WReg r;
+			r.rb = d.rb; r.re = d.re; r.qb = d.qb; r.qe = d.qe; r.rid = d.rid; r.score = d.score; r.truesc = d.truesc; r.w = d.w; r.frac_rep = d.frac_rep;
+			r.csub = r.sub = r.sub_n = 0; r.secondary = r.secondary_all = -1;
+			wl_put(L[e], lane, r);
+		}
+	}
+	__syncthreads();
+
+	// ---- the rescue loop (src/bwamem_pair.c:265-276): the candidates are copied before any rescue, end 0's are used first ----
+	if (!P.no_rescue) {
+		int nc[2];
+		for (int e = 0; e < 2; ++e) {
+			const bool cand = lane < n[e] && L[e].score[lane] >= L[e].score[0] - P.pen_unpaired;
+			const u64 m = __ballot(cand);
+			const int ord = __popcll(m & (((u64)1 << lane) - 1));
+			if (cand && ord < P.max_matesw) { c_rb[e][ord] = L[e].rb[lane]; c_rid[e][ord] = L[e].rid[lane]; }
+			nc[e] = __popcll(m) < P.max_matesw ? __popcll(m) : P.max_matesw;
+		}
+		__syncthreads();
+		if (4 * (nc[0] + nc[1]) != toff[t + 1] - toff[t]) PW_GIVE_UP(PW_HOST_NO_RESULT);   // (the host listed other candidates: no tag is read)
+		const unsigned mb = mfirst[t];
+		for (int e = 0; e < 2; ++e) {
+			const int ma = !e;   // the mate's list takes the rescued hits
+			const int tb = toff[t] + (e ? 4 * nc[0] : 0);
+			for (int c = 0; c < nc[e]; ++c) {
+				const i64 a_rb = c_rb[e][c];
+				// mem_matesw :118-128: the orientations that failed or that a hit of the mate's CURRENT list explains
+				int r_l = -1;
+				if (lane < n[ma]) {
+					i64 dist;
+					const int r = pw_infer_dir(P.l_pac, a_rb, L[ma].rb[lane], &dist);
+					if (dist >= P.low[r] && dist <= P.high[r]) r_l = r;
+				}
+				bool skip[4];
+				for (int r = 0; r < 4; ++r) skip[r] = P.failed[r] || __ballot(r_l == r) != 0;
+				if (skip[0] && skip[1] && skip[2] && skip[3]) continue;
+				const int l_ms = len[2 * k + ma];
+				for (int r = 0; r < 4; ++r) {
+					if (skip[r]) continue;
+					const int tag = tags[tb + 4 * c + r];
+					if (tag == PW_TAG_NO_WINDOW) continue;   // the reference aligns nothing here (:150)
+					if (tag < 0) PW_GIVE_UP(PW_HOST_NO_RESULT);
+					const MswRes res = mres[mb + tag];
+					const MswReq rq = mreq[mb + tag];
+					if (res.flags) PW_GIVE_UP(PW_HOST_NO_RESULT);
+					if (!(res.score >= P.min_seed_len && res.qb >= 0)) continue;
+					WReg b;   // :155-170
+					const bool is_rev = rq.is_rev != 0;
+					b.rid = c_rid[e][c];
+					b.qb = is_rev ? l_ms - (res.qe + 1) : res.qb;
+					b.qe = is_rev ? l_ms - res.qb : res.qe + 1;
+					b.rb = is_rev ? (P.l_pac << 1) - (rq.rb + res.te + 1) : rq.rb + res.tb;
+					b.re = is_rev ? (P.l_pac << 1) - (rq.rb + res.tb) : rq.rb + res.te + 1;
+					b.score = res.score; b.csub = res.score2; b.secondary = -1;
+					b.truesc = b.w = b.sub = b.sub_n = 0; b.secondary_all = 0; b.frac_rep = 0.f;
+					const int why = pw_insert(P, L[ma], n[ma], b, lane);
+					if (why) PW_GIVE_UP(why);
+				}
+			}
+		}
+	}
+	if (n[0] == 0 || n[1] == 0) PW_GIVE_UP(PW_HOST_NO_PAIR);   // (n_pri = 0: the ends are reported independently)
+
+	const u64 id = P.id0 + (u64)k;
+	if (!pw_mark_primary(P, L[0], n[0], id << 1 | 0, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
+	if (!pw_mark_primary(P, L[1], n[1], id << 1 | 1, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
+
+	// ---- mem_pair (src/bwamem_pair.c:182-243) ----
+	const int nv = n[0] + n[1];
+	{
+		Pair64 key[2];
+		for (int r = 0; r < 2; ++r)
+			if (lane < n[r]) {
+				const i64 rb = L[r].rb[lane];
+				const int rid = L[r].rid[lane];
+				key[r].x = (u64)(rb < P.l_pac ? rb : (P.l_pac << 1) - 1 - rb);
+				key[r].x = (u64)rid << 32 | (key[r].x - (u64)ann_off[rid]);
+				key[r].y = (u64)L[r].score[lane] << 32 | (u64)(lane << 2 | (rb >= P.l_pac) << 1 | r);
+				V[r * n[0] + lane] = key[r];
+			}
+		__syncthreads();
+		int rank[2] = {0, 0};
+		for (int j = 0; j < nv; ++j) {   // (unique keys: the rank is the place in the reference's sorted array)
+			const Pair64 o = V[j];
+			if (lane < n[0] && pair_lt64(o, key[0])) ++rank[0];
+			if (lane < n[1] && pair_lt64(o, key[1])) ++rank[1];
+		}
+		__syncthreads();
+		for (int r = 0; r < 2; ++r)
+			if (lane < n[r]) V[rank[r]] = key[r];
+		__syncthreads();
+	}
+	const int idi = (int)((unsigned)(int)id << 8);
+	// u is not stored: its maximum under (x, y), the second-largest score and n_sub are reductions
+	Pair64 best;
+	best.x = best.y = 0;
+	int cnt = 0, q2 = -1;   // of this lane's candidates: how many, the best, the largest score among the others
+	for (int i = lane; i < nv; i += 64)
+		pw_pairs_of(P, V, i, idi, ptab, [&](const Pair64 &p) {
+			if (cnt == 0) best = p;
+			else if (pair_lt64(best, p)) { const int qb_ = (int)(best.x >> 32); q2 = q2 > qb_ ? q2 : qb_; best = p; }
+			else { const int qp = (int)(p.x >> 32); q2 = q2 > qp ? q2 : qp; }
+			++cnt;
+		});
+	const int nu = wave_sum(cnt);
+	if (nu == 0) PW_GIVE_UP(PW_HOST_NO_PAIR);   // no pair in a proper orientation and distance
+	const u64 gx = wave_maxu(cnt ? best.x : 0);
+	const bool top_x = cnt && best.x == gx;
+	const u64 gy = wave_maxu(top_x ? best.y : 0);   // (several candidates can share x; y = (kk, i) is unique)
+	const bool mine = top_x && best.y == gy;
+	int subo = (int)wave_max((i64)(mine ? q2 : cnt ? (int)(best.x >> 32) : -1));
+	if (nu < 2) subo = 0;
+	int tmp = P.a + P.b;
+	tmp = tmp > P.o_del + P.e_del ? tmp : P.o_del + P.e_del;
+	tmp = tmp > P.o_ins + P.e_ins ? tmp : P.o_ins + P.e_ins;
+	int n_sub = 0;
+	if (nu > 1) {
+		int c2 = 0;
+		for (int i = lane; i < nv; i += 64)
+			pw_pairs_of(P, V, i, idi, ptab, [&](const Pair64 &p) {
+				if (!(p.x == gx && p.y == gy) && subo - (int)(p.x >> 32) <= tmp) ++c2;
+			});
+		n_sub = wave_sum(c2);
+	}
+	int z[2];
+	{
+		const int i = (int)(gy >> 32), kk = (int)(gy << 32 >> 32);
+		const Pair64 vi = V[i], vk = V[kk];
+		z[vi.y & 1] = (int)(vi.y << 32 >> 34);
+		z[vk.y & 1] = (int)(vk.y << 32 >> 34);
+	}
+	const int o = (int)(gx >> 32);
+	if (o <= 0) PW_GIVE_UP(PW_HOST_SCORE);
+
+	// ---- is_multi, q_pe, q_se, the caps, the swap (:289-339); every lane computes the same numbers ----
+	for (int e = 0; e < 2; ++e)   // an end with several good primary hits is left to the single-end logic
+		if (__ballot(lane >= 1 && lane < n[e] && L[e].secondary[lane] < 0 && L[e].score[lane] >= P.T)) PW_GIVE_UP(PW_HOST_SUPP);
+	const int score_un = L[0].score[0] + L[1].score[0] - P.pen_unpaired;
+	subo = subo > score_un ? subo : score_un;
+	int q_pe = RAW_MAPQ(o - subo, P.a);
+	if (n_sub >= 40) PW_GIVE_UP(PW_HOST_LENGTH);   // (beyond the table of (int)(4.343 * log(n + 1) + .499))
+	if (n_sub > 0) q_pe -= P.lnq[n_sub];
+	if (q_pe < 0) q_pe = 0;
+	if (q_pe > 60) q_pe = 60;
+	q_pe = (int)(q_pe * (1. - .5 * (L[0].frac_rep[0] + L[1].frac_rep[0])) + .499);
+	int q_se[2], extra_flag = 1, sub_z[2];
+	const bool pair_wins = o > score_un;
+	if (!pair_wins) z[0] = z[1] = 0;
+	for (int e = 0; e < 2; ++e) {
+		const WReg c = wl_get(L[e], z[e]);
+		int sub = c.sub;
+		if (pair_wins && c.secondary >= 0) sub = L[e].score[c.secondary];   // (c.secondary = -2 in the reference: it is not read again)
+		sub_z[e] = sub;
+		const int l = c.qe - c.qb > c.re - c.rb ? c.qe - c.qb : (int)(c.re - c.rb);
+		if (l >= P.ltab_n || l <= 0 || c.sub_n >= 40) PW_GIVE_UP(PW_HOST_LENGTH);
+		q_se[e] = mapq_se_of(P, c.score, sub, c.sub_n, c.csub, l, c.frac_rep, ltab);
+		if (pair_wins) {
+			q_se[e] = q_se[e] > q_pe ? q_se[e] : q_pe < q_se[e] + 40 ? q_pe : q_se[e] + 40;
+			const int cap = RAW_MAPQ(c.score - c.csub, P.a);   // the tandem-repeat cap
+			q_se[e] = q_se[e] < cap ? q_se[e] : cap;
+		}
+	}
+	if (pair_wins) extra_flag |= 2;
+	__syncthreads();
+	for (int e = 0; e < 2; ++e) {   // the chosen hit was secondary: swap roles with its parent
+		const int kk = L[e].secondary_all[z[e]];
+		__syncthreads();
+		if (kk >= 0 && kk < n[e]) {
+			if (lane < n[e] && (L[e].secondary_all[lane] == kk || lane == kk)) L[e].secondary_all[lane] = z[e];
+			__syncthreads();
+			if (lane == 0) L[e].secondary_all[z[e]] = -1;
+			__syncthreads();
+		}
+	}
+	// ---- does the chosen hit get an XA string (src/bwamem_extra.c:105-118, no ALT hit here)?  Only with 1 .. max_XA_hits qualifying
+	// secondary hits under it; more than that and the reference writes none
+	for (int e = 0; e < 2; ++e) {
+		const int n_xa = __popcll(__ballot(lane < n[e] && L[e].secondary_all[lane] == z[e] &&
+		                                   L[e].score[lane] >= L[e].score[z[e]] * (double)P.XA_drop_ratio));
+		if (n_xa > 0 && n_xa <= P.max_XA_hits) PW_GIVE_UP(PW_HOST_XA);
+	}
+	if (lane < 2) {
+		const int e = lane;
+		const WReg R = wl_get(L[e], z[e]);
+		const int l1 = R.qe - R.qb, l2 = (int)(R.re - R.rb);
+		const int t2 = infer_bw(l1, l2, R.truesc, P.a, P.o_del, P.e_del);
+		int w2 = infer_bw(l1, l2, R.truesc, P.a, P.o_ins, P.e_ins);
+		w2 = w2 > t2 ? w2 : t2;
+		if (w2 > P.w) w2 = w2 < R.w ? w2 : R.w;   // (a rescued hit has w = 0)
+		AlnReq q;
+		q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = 0;
+		reqs[2 * t + e] = q;
+		SamDesc d;
+		d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = e; d.rid = R.rid;
+		d.flag = 0x40 << e | extra_flag; d.mapq = q_se[e] & 0xff; d.score = R.score;
+		d.sub = sub_z[e] > R.csub ? sub_z[e] : R.csub;   // mem_reg2aln: sub = max(sub, csub)
+		desc[2 * t + e] = d;
+	}
+	if (lane == 0) wstatus[t] = 1;
+}
+
+void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
+                      const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
+                      const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc)
+{
+	if (n_work <= 0) return;
+	hipLaunchKernelGGL(pair_wave_kernel, dim3(n_work), dim3(64), 0, (hipStream_t)stream, P, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst,
+	                   d_tags, d_toff, (const i64 *)d_ann_off, d_ptab, d_ltab, d_wstatus, d_reqs, d_desc);
+}
+
+// the decided pairs' requests and descriptors into the chunk-wide arrays the CIGAR-and-SAM job reads
+__global__ void pair_wave_clear_kernel(int r0, int n_reads, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_reads) return;
+	reqs[r0 + i].read = -1;
+	desc[r0 + i].req = -1;
+}
+__global__ void pair_wave_scatter_kernel(int n_work, const int *__restrict__ work, const uint8_t *__restrict__ wstatus, const AlnReq *__restrict__ w_reqs,
+                                         const SamDesc *__restrict__ w_desc, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= 2 * n_work) return;
+	const int t = i >> 1, e = i & 1;
+	if (wstatus[t] != 1) return;
+	reqs[2 * work[t] + e] = w_reqs[i];
+	desc[2 * work[t] + e] = w_desc[i];
+}
+void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const uint8_t *d_wstatus, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                              AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n)
+{
+	if (clear_n > 0) hipLaunchKernelGGL(pair_wave_clear_kernel, dim3((clear_n + 255) / 256), dim3(256), 0, (hipStream_t)stream, clear_r0, clear_n, d_reqs, d_desc);
+	if (n_work > 0)
+		hipLaunchKernelGGL(pair_wave_scatter_kernel, dim3((2 * n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_work, d_wstatus, d_w_reqs, d_w_desc,
+		                   d_reqs, d_desc);
+}
+
+} // namespace mbw

@@ -234,6 +234,11 @@ struct ChunkBufs {
 	PinBuf h_pr_ok, h_pr_status, h_pr_tab;
 	PinBuf h_mreq[2], h_mres[2], h_mlist[2];
 	DevBuf mreq[2], mres[2], mrows[2], mlist[2], mtail[2];
+	// pairs with mate rescue or long lists, decided by pair_wave_kernel behind the mate-rescue kernel of the part: work list, packed
+	// region lists and their offsets, first rescue request and tags per pair, status, the kernel's requests and descriptors
+	PinBuf h_wwork[2], h_wlists[2], h_wloff[2], h_wmfirst[2], h_wtags[2], h_wtoff[2], h_wstatus[2];
+	DevBuf wwork[2], wlists[2], wloff[2], wmfirst[2], wtags[2], wtoff[2], wstatus[2], wreq[2], wdesc[2];
+	JobBufs wave_job[2];  // their job when the device units' job of the part has already gone out
 	PinBuf h_areq[2];     // the host's CIGAR requests of a part, as listed
 	JobBufs host_job[2];  // the host's units ...
 	JobBufs dev_job[2];   // ... and the units decided on the device, launched right behind the deciding kernel
@@ -298,7 +303,15 @@ struct Part {
 	size_t n_mreq = 0;
 	hipStream_t mst = 0;
 	EvTimer mev;
-	bool m_launched = false;
+	bool m_launched = false, msw_launched = false;
+	// the pairs handed to pair_wave_kernel (chunk numbering), their status bytes once mfinish has waited, how many it decided
+	std::vector<int> work;
+	std::vector<unsigned> w_mfirst;
+	std::vector<int> w_toff;
+	std::vector<int16_t> w_tags;
+	const uint8_t *wstatus = nullptr;
+	int n_wave_dec = 0;
+	Job wave;                         // the job of the pairs it decided, when they do not ride in `dev`
 	// CIGAR requests while they are being listed: per block of 256 units, and where each unit's run starts
 	std::vector<std::vector<AlnReqH>> blk_req;
 	std::vector<uint32_t> u_first, u_cnt;
@@ -353,6 +366,13 @@ struct Call {
 	mem_pestat_t pes[4];
 
 	// ---- units decided on the device (sam_stage.hip) ----
+	uint8_t *pstat_w = nullptr;          // (pstat, writable: pair_wave_kernel's decisions are merged in)
+	bool dev_wave = false;               // pair_wave_kernel takes the pairs pair_simple_kernel leaves for rescue / long lists
+	std::vector<uint8_t> wave_cand, wave_dec;   // per pair: handed to pair_wave_kernel; decided by it
+	PairParams wave_pp;
+	const double *d_wave_tab = nullptr;  // the tables of decide_on_device, still on the device
+	size_t wave_n_tab = 0;
+	uint64_t n_wave = 0;
 	const uint8_t *pstat = nullptr;      // status[k] = 1: the unit's requests and descriptors exist on the device
 	const uint8_t *se_codes = nullptr;   // the status codes of se_simple_kernel (pstat too, if it took any read)
 	const AlnReq *d_pr_req = nullptr;
@@ -373,6 +393,8 @@ struct Call {
 	void mcollect(Part &P);           // mate rescue: list the local alignments the pairs of the part will ask for
 	void mlaunch(Part &P);            // ... run them in one launch (asynchronous)
 	void mfinish(Part &P);
+	void wave_launch(Part &P);        // pair_wave_kernel behind the mate-rescue kernel of the part (asynchronous)
+	void wave_records(Part &P, bool own_job);   // its pairs into the device units' arrays; own_job: and a job of their own
 	void collect(Part &P, int round); // A: decisions + the list of CIGARs to compute
 	void launch_dev(Part &P);         // the job of the units decided on the device (asynchronous)
 	void finish_dev(Part &P);
@@ -382,7 +404,7 @@ struct Call {
 	enum Fetch { FETCH_ALWAYS, FETCH_IF_HANDED_BACK };
 	void job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const AlnReq *d_req, size_t n_req, const uint32_t *base, bool with_sam,
 	                const SamDescH *h_desc, SamDesc *d_desc);
-	void job_fetch(Job &J, const Part &P, Fetch policy);
+	void job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units = false);
 	void take_record(int read, const Job &J, int at);
 	void report_decisions();
 

@@ -128,6 +128,7 @@ void Call::decide_on_device(int ends)
 		if (ends == 1) se_codes = hs;
 		for (int i = 0; i < nu && !any_dev; ++i) any_dev = hs[i] == SE_DECIDED;
 		if (any_dev) { pstat = hs; d_pr_req = d_rq; d_pr_desc = d_ds; }
+		if (any_dev && ends == 2) { pstat_w = hs; wave_pp = pp; d_wave_tab = d_tab; wave_n_tab = n_tab; }
 	}
 	pair_dev_ms = now_ms() - tp0;
 }
@@ -142,18 +143,42 @@ void Call::mcollect(Part &P)
 	const int nu = P.hi - P.lo, n_blk = (nu + 255) / 256;
 	std::vector<std::vector<MswReqH>> blk_req(n_blk);
 	std::vector<uint32_t> u_first(nu), u_cnt(nu);
+	// (dev_wave: the pairs pair_simple_kernel left for rescue, long lists or an end without a hit also get their tags, and are pair_wave_kernel's)
+	std::vector<std::vector<int16_t>> blk_tag(dev_wave ? n_blk : 0);
+	std::vector<std::vector<int>> blk_work(dev_wave ? n_blk : 0);   // (pair, first tag in blk_tag) ...
 	parallel_for(n_thr, n_blk, 1, [&](int blk) {
 		std::vector<MswReqH> &rq = blk_req[blk];
 		rq.reserve(256);
 		const int lo = P.lo + blk * 256, hi = std::min(P.hi, lo + 256);
 		for (int i = lo; i < hi; ++i) {
 			const size_t before = rq.size();
-			if (!(pstat && pstat[i] == 1)) sam_pe_msw_collect(opt, bns, pes, &seqs[i << 1], &regs[i << 1], i << 1, MSW_MAX_T, rq);
+			if (!(pstat && pstat[i] == 1)) {
+				const bseq1_t *s = &seqs[i << 1];
+				const bool cand = dev_wave && (pstat[i] == 3 || pstat[i] == 7 || pstat[i] == 2) && !s[0].comment && !s[1].comment &&
+				                  strcmp(s[0].name, s[1].name) == 0 && pair_wave_eligible(&regs[i << 1], PW_MAXREG);
+				if (cand) {
+					blk_work[blk].push_back(i); blk_work[blk].push_back((int)blk_tag[blk].size());
+					sam_pe_msw_collect_tagged(opt, bns, pes, s, &regs[i << 1], i << 1, MSW_MAX_T, rq, blk_tag[blk]);
+					wave_cand[i] = 1;
+				} else sam_pe_msw_collect(opt, bns, pes, s, &regs[i << 1], i << 1, MSW_MAX_T, rq);
+			}
 			u_first[i - P.lo] = (uint32_t)before; u_cnt[i - P.lo] = (uint32_t)(rq.size() - before);
 		}
 	});
 	P.mbase.assign(nu + 1, 0);
 	for (int i = 0; i < nu; ++i) P.mbase[i + 1] = P.mbase[i] + u_cnt[i];
+	P.work.clear(); P.w_mfirst.clear(); P.w_toff.clear(); P.w_tags.clear();
+	for (int blk = 0; blk < (int)blk_work.size(); ++blk) {
+		const size_t tag0 = P.w_tags.size();
+		for (size_t x = 0; x < blk_work[blk].size(); x += 2) {
+			const int i = blk_work[blk][x];
+			P.work.push_back(i);
+			P.w_mfirst.push_back(P.mbase[i - P.lo]);
+			P.w_toff.push_back((int)(tag0 + (size_t)blk_work[blk][x + 1]));
+		}
+		P.w_tags.insert(P.w_tags.end(), blk_tag[blk].begin(), blk_tag[blk].end());
+	}
+	P.w_toff.push_back((int)P.w_tags.size());
 	P.n_mreq = P.mbase[nu];
 	P.mreq = (MswReqH *)W.h_mreq[P.slot].ensure(P.n_mreq * sizeof(MswReqH) + 64);
 	P.mres = (MswResH *)W.h_mres[P.slot].ensure(P.n_mreq * sizeof(MswResH) + 64);
@@ -167,8 +192,11 @@ void Call::mcollect(Part &P)
 void Call::mlaunch(Part &P)
 {
 	stage(11);
-	if (!gpu_msw || P.n_mreq == 0) return;
+	if (!gpu_msw || (P.n_mreq == 0 && P.work.empty())) return;
 	P.mst = C.a_streams[P.slot];
+	P.m_launched = true;
+	if (P.n_mreq == 0) { wave_launch(P); return; }
+	P.msw_launched = true;
 	int max_t = 1;
 	for (size_t k = 0; k < P.n_mreq; ++k) max_t = std::max(max_t, (int)(P.mreq[k].re - P.mreq[k].rb));
 	MswReq *d_req = (MswReq *)W.mreq[P.slot].ensure(P.n_mreq * sizeof(MswReq));
@@ -188,8 +216,90 @@ void Call::mlaunch(Part &P)
 		           h_ml + 2 * b, d_ml + 2 * b, d_mt);
 	}
 	P.mev.stop(P.mst);
+	wave_launch(P);
 	HIP_OK(hipMemcpyAsync(P.mres, d_res, P.n_mreq * sizeof(MswRes), hipMemcpyDeviceToHost, P.mst));   // pinned: truly asynchronous
-	P.m_launched = true;
+}
+
+// (the work list's size moves from chunk to chunk: twice the first size seen, so that the buffers settle during the first calls.  Not
+// rounded to a power of two: the headline's 26 000 pairs a chunk sit at such a boundary, and one chunk in a few crossed it)
+static size_t roomy(size_t bytes)
+{
+	return std::max<size_t>(2 * bytes, (size_t)1 << 16);
+}
+
+// pair_wave_kernel over the part's work list, behind the mate-rescue kernel on its stream; the status bytes come back on the same
+// stream, so that mfinish's wait delivers them.  The lists are the host's own (after mem_sort_dedup_patch), packed with offsets.
+void Call::wave_launch(Part &P)
+{
+	const int nw = (int)P.work.size();
+	if (nw == 0) return;
+	const int s = P.slot;
+	size_t n_regs = 0;
+	int *loff = (int *)W.h_wloff[s].ensure(roomy(((size_t)2 * nw + 1) * 4 + 64));
+	loff[0] = 0;
+	for (int t = 0; t < nw; ++t)
+		for (int e = 0; e < 2; ++e) { n_regs += regs[2 * P.work[t] + e].size(); loff[2 * t + e + 1] = (int)n_regs; }
+	DevReg *hl = (DevReg *)W.h_wlists[s].ensure(roomy(n_regs * sizeof(DevReg) + 64));
+	parallel_for(n_thr, nw, 512, [&](int t) {
+		for (int e = 0; e < 2; ++e) {
+			const HRegV &v = regs[2 * P.work[t] + e];
+			DevReg *o = hl + loff[2 * t + e];
+			for (size_t j = 0; j < v.size(); ++j) {
+				const HReg &h = v[j];
+				DevReg d;
+				d.rb = h.rb; d.re = h.re; d.qb = h.qb; d.qe = h.qe; d.rid = h.rid; d.score = h.score; d.truesc = h.truesc; d.w = h.w;
+				d.seedcov = h.seedcov; d.seedlen0 = h.seedlen0; d.frac_rep = h.frac_rep; d.pad = 0;
+				o[j] = d;
+			}
+		}
+	});
+	int *hw = (int *)W.h_wwork[s].ensure(roomy((size_t)nw * 4 + 64));
+	unsigned *hm = (unsigned *)W.h_wmfirst[s].ensure(roomy((size_t)nw * 4 + 64));
+	int *ht = (int *)W.h_wtoff[s].ensure(roomy((size_t)(nw + 1) * 4 + 64));
+	int16_t *hg = (int16_t *)W.h_wtags[s].ensure(roomy(P.w_tags.size() * 2 + 64));
+	memcpy(hw, P.work.data(), (size_t)nw * 4); memcpy(hm, P.w_mfirst.data(), (size_t)nw * 4); memcpy(ht, P.w_toff.data(), (size_t)(nw + 1) * 4);
+	memcpy(hg, P.w_tags.data(), P.w_tags.size() * 2);
+	uint8_t *hs = (uint8_t *)W.h_wstatus[s].ensure(roomy((size_t)nw + 64));
+	int *d_work = (int *)W.wwork[s].ensure(roomy((size_t)nw * 4));
+	DevReg *d_lists = (DevReg *)W.wlists[s].ensure(roomy(n_regs * sizeof(DevReg) + 64));
+	int *d_loff = (int *)W.wloff[s].ensure(roomy(((size_t)2 * nw + 1) * 4));
+	unsigned *d_mf = (unsigned *)W.wmfirst[s].ensure(roomy((size_t)nw * 4));
+	int *d_toff = (int *)W.wtoff[s].ensure(roomy((size_t)(nw + 1) * 4));
+	short *d_tags = (short *)W.wtags[s].ensure(roomy(P.w_tags.size() * 2 + 64));
+	uint8_t *d_ws = (uint8_t *)W.wstatus[s].ensure(roomy((size_t)nw + 64));
+	AlnReq *d_rq = (AlnReq *)W.wreq[s].ensure(roomy((size_t)2 * nw * sizeof(AlnReq)));
+	SamDesc *d_ds = (SamDesc *)W.wdesc[s].ensure(roomy((size_t)2 * nw * sizeof(SamDesc)));
+	// (a part without a rescue request has no request or result array: the kernel reads neither, every tag says so)
+	const MswReq *d_req = (const MswReq *)W.mreq[s].ensure(std::max<size_t>(P.n_mreq, 1) * sizeof(MswReq));
+	const MswRes *d_res = (const MswRes *)W.mres[s].ensure(std::max<size_t>(P.n_mreq, 1) * sizeof(MswRes));
+	HIP_OK(hipMemcpyAsync(d_work, hw, (size_t)nw * 4, hipMemcpyHostToDevice, P.mst));
+	if (n_regs) HIP_OK(hipMemcpyAsync(d_lists, hl, n_regs * sizeof(DevReg), hipMemcpyHostToDevice, P.mst));
+	HIP_OK(hipMemcpyAsync(d_loff, loff, ((size_t)2 * nw + 1) * 4, hipMemcpyHostToDevice, P.mst));
+	HIP_OK(hipMemcpyAsync(d_mf, hm, (size_t)nw * 4, hipMemcpyHostToDevice, P.mst));
+	HIP_OK(hipMemcpyAsync(d_toff, ht, (size_t)(nw + 1) * 4, hipMemcpyHostToDevice, P.mst));
+	if (!P.w_tags.empty()) HIP_OK(hipMemcpyAsync(d_tags, hg, P.w_tags.size() * 2, hipMemcpyHostToDevice, P.mst));
+	HIP_OK(hipMemsetAsync(d_ws, 0, (size_t)nw, P.mst));
+	launch_pair_wave(P.mst, wave_pp, nw, d_work, d_lists, d_loff, D.d_len, d_req, d_res, d_mf, d_tags, d_toff, D.d_ann_off, d_wave_tab, d_wave_tab + wave_n_tab,
+	                 d_ws, d_rq, d_ds);
+	HIP_OK(hipMemcpyAsync(hs, d_ws, (size_t)nw, hipMemcpyDeviceToHost, P.mst));
+	P.wstatus = hs;
+}
+
+// The pairs pair_wave_kernel decided become units of the device: their requests and descriptors go into the chunk-wide arrays of the
+// deciding kernels, on the stream of the part's device job.  own_job (that job has already gone out and is back): the arrays are
+// cleared for the part first, and one more job of the same type runs over it — the wave's pairs alone.
+void Call::wave_records(Part &P, bool own_job)
+{
+	if (P.n_wave_dec == 0) return;
+	const int s = P.slot, nw = (int)P.work.size();
+	hipStream_t jst = C.d_streams[s];
+	launch_pair_wave_scatter(jst, nw, (const int *)W.wwork[s].p, (const uint8_t *)W.wstatus[s].p, (const AlnReq *)W.wreq[s].p, (const SamDesc *)W.wdesc[s].p,
+	                         const_cast<AlnReq *>(d_pr_req), const_cast<SamDesc *>(d_pr_desc), 2 * P.lo, own_job ? 2 * (P.hi - P.lo) : 0);
+	HIP_OK(hipGetLastError());
+	if (!own_job) return;
+	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
+	P.wave.small_used = small + 32; P.wave.small_cnt = small + 40;
+	job_launch(P.wave, W.wave_job[s], jst, P, d_pr_req + (size_t)P.lo * 2, (size_t)(P.hi - P.lo) * 2, nullptr, true, nullptr, const_cast<SamDesc *>(d_pr_desc));
 }
 
 void Call::mfinish(Part &P)
@@ -199,8 +309,14 @@ void Call::mfinish(Part &P)
 	double ta = now_ms();
 	stream_wait(P.mst);
 	HIP_OK(hipGetLastError());
-	STAT.k_msw_ms += P.mev.ms();
+	if (P.msw_launched) STAT.k_msw_ms += P.mev.ms();
 	STAT.n_msw += P.n_mreq;
+	for (size_t t = 0; t < P.work.size(); ++t) {   // pair_wave_kernel's decisions: its pairs are the device's from here on
+		const int i = P.work[t];
+		if (P.wstatus[t] == 1) { pstat_w[i] = 1; wave_dec[i] = 1; ++P.n_wave_dec; }
+		else if (P.wstatus[t]) pstat_w[i] = P.wstatus[t];   // (why not: for the statistics line)
+	}
+	n_wave += (uint64_t)P.n_wave_dec;
 	msw_ms += now_ms() - ta;
 }
 
@@ -223,14 +339,15 @@ void Call::collect(Part &P, int round)
 		for (int i = lo; i < hi; ++i) {
 			const int k = i - P.lo;
 			if (pstat && pstat[i] == 1) continue;   // decided on the device
-			const bool waits = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
+			const bool has_msw = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
+			const bool waits = has_msw || (dev_wave && wave_cand[i]);            // ... or pair_wave_kernel's word on whose pair it is
 			if (waits != (round == 1)) continue;
 			const size_t before = rq.size();
 			if (pe) {
 				MswCtx mc;
-				if (waits) { mc.req = P.mreq + P.mbase[k]; mc.res = P.mres + P.mbase[k]; mc.n = (int)(P.mbase[k + 1] - P.mbase[k]); }
+				if (has_msw) { mc.req = P.mreq + P.mbase[k]; mc.res = P.mres + P.mbase[k]; mc.n = (int)(P.mbase[k + 1] - P.mbase[k]); }
 				const unsigned long long c0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
-				sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[i << 1], &regs[i << 1], plans[i], waits ? &mc : nullptr,
+				sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[i << 1], &regs[i << 1], plans[i], has_msw ? &mc : nullptr,
 				            i << 1);
 				const unsigned long long c1 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
 				ctx.desc = gpu_sam ? &sdesc[i << 1] : nullptr;
@@ -330,7 +447,7 @@ static void fetch_records(Job &J)
 // Wait for a job and fetch what the host needs of it.  FETCH_ALWAYS: the CIGAR results, then the records (the host's units: REPLAY reads
 // the results).  FETCH_IF_HANDED_BACK: the records, and the CIGAR results only if a unit decided on the device comes back without a
 // record (CIGAR declined, row overflow): the host redoes that unit and needs them.
-void Call::job_fetch(Job &J, const Part &P, Fetch policy)
+void Call::job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units)
 {
 	if (!J.launched) return;
 	const double ta = now_ms();
@@ -344,7 +461,8 @@ void Call::job_fetch(Job &J, const Part &P, Fetch policy)
 		const int ends = pe ? 2 : 1;
 		bool any_back = false;
 		for (int k = 0; k < P.hi - P.lo && !any_back; ++k)
-			for (int e = 0; e < ends; ++e) any_back = any_back || (pstat[P.lo + k] == 1 && J.solen[ends * k + e] < 0);
+			for (int e = 0; e < ends; ++e)
+				any_back = any_back || (pstat[P.lo + k] == 1 && (!wave_units || wave_dec[P.lo + k]) && J.solen[ends * k + e] < 0);
 		if (any_back) fetch_results(J);
 	}
 	aln_wait_ms += now_ms() - ta;
@@ -357,7 +475,7 @@ void Call::launch_dev(Part &P)
 	stage(14);
 	if (!pstat || P.hi == P.lo) return;
 	const int ends = pe ? 2 : 1;   // reads (and requests) per unit
-	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(256);
+	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(512);
 	P.dev.small_used = small; P.dev.small_cnt = small + 8;
 	job_launch(P.dev, W.dev_job[P.slot], C.d_streams[P.slot], P, d_pr_req + (size_t)P.lo * ends, (size_t)(P.hi - P.lo) * ends, nullptr, true, nullptr,
 	           const_cast<SamDesc *>(d_pr_desc));
@@ -371,7 +489,7 @@ void Call::launch(Part &P)   // B (asynchronous)
 {
 	stage(16);
 	if (!gpu_aln || P.n_req == 0) return;
-	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(256);
+	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(512);
 	P.host.small_cnt = small + 16; P.host.small_used = small + 24;
 	// (gpu_sam: the records of the part's qualifying pairs, queued right behind their CIGARs)
 	SamDesc *d_desc = gpu_sam ? (SamDesc *)W.sdesc.ensure((size_t)n * sizeof(SamDesc)) : nullptr;
@@ -415,10 +533,11 @@ void Call::replay(Part &P, int which)
 		for (int k = k_lo; k < k_hi; ++k) {
 			const int i = P.lo + k, r = ends * i;   // the unit, its first read
 			const bool dev_k = pstat && pstat[i] == 1;
-			const Job &J = dev_k ? P.dev : P.host;
+			const bool own_k = dev_k && P.wave.launched && wave_dec[i];   // pair_wave_kernel's pair with the job of its own
+			const Job &J = own_k ? P.wave : dev_k ? P.dev : P.host;
 			bool written = J.solen != nullptr;   // every record of the unit was written by sam_emit_kernel
 			for (int e = 0; e < ends && written; ++e) written = J.solen[ends * k + e] >= 0;
-			const bool early = dev_k && written;   // pass 0's units
+			const bool early = dev_k && written && !own_k;   // pass 0's units
 			if (which != 2 && early != (which == 0)) continue;
 			if (written) {
 				const unsigned long long tq0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
@@ -430,9 +549,12 @@ void Call::replay(Part &P, int which)
 			AlnCtx ctx;
 			if (gpu_aln) { ctx.mode = AlnCtx::REPLAY; ctx.hdr = P.host.hdr; ctx.pool = P.host.pool; ctx.cursor = P.base[k]; }
 			// the device decided the unit but handed a record back: the host decides it again (the same `ends` requests, same order)
-			if (dev_k) { ctx.hdr = P.dev.hdr; ctx.pool = P.dev.pool; ctx.cursor = (size_t)ends * k; }
+			if (dev_k) { ctx.hdr = J.hdr; ctx.pool = J.pool; ctx.cursor = (size_t)ends * k; }
 			if (pe) {
-				if (dev_k) sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[r], &regs[r], plans[i], nullptr, r);
+				MswCtx mc;   // (pair_wave_kernel's pair: the rescue alignments are there)
+				const bool has_msw = dev_k && dev_wave && wave_dec[i] && P.msw_launched && P.mbase[k + 1] != P.mbase[k];
+				if (has_msw) { mc.req = P.mreq + P.mbase[k]; mc.res = P.mres + P.mbase[k]; mc.n = (int)(P.mbase[k + 1] - P.mbase[k]); }
+				if (dev_k) sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[r], &regs[r], plans[i], has_msw ? &mc : nullptr, r);
 				sam_pe_emit(opt, bns, pac, pes, &seqs[r], &regs[r], plans[i], gpu_aln ? &ctx : nullptr, r);
 			} else {
 				if (dev_k) mark_primary_se(opt, regs[i], n_processed + i);
@@ -472,6 +594,9 @@ void Call::sam_stage()
 	//   dev_mid    single-end, either            launch_dev (before or after collect, by dev_late), launch, FETCH, finish
 	// Exactly one of the three holds; replay 1 (the host's records) closes every part.
 	const bool dev_early = pe && !dev_late, dev_mid = !pe, dev_last = pe && dev_late;
+	// pair_wave_kernel: wherever pair_simple_kernel ran and mate rescue runs on the device.  MPIBWA_HOST_RESCUE=1 turns it off.
+	dev_wave = pe && pstat_w && gpu_msw && getenv("MPIBWA_HOST_RESCUE") == nullptr;
+	if (dev_wave) { wave_cand.assign(n_units, 0); wave_dec.assign(n_units, 0); }
 	for (int p = 0; p < n_parts; ++p) {   // (slot 0: the whole chunk or its first half)
 		parts[p].slot = p;
 		parts[p].lo = p ? n_units / 2 : 0;
@@ -484,6 +609,8 @@ void Call::sam_stage()
 		Part &P = parts[p];
 		if (dev_early) { finish_dev(P); replay(P, 0); }
 		collect(P, 0); mfinish(P); collect(P, 1);
+		// (the wave's pairs ride in the part's device job when it has not gone out yet, and get a job of their own behind it otherwise)
+		if (dev_wave) wave_records(P, !dev_late);
 		if (dev_late) launch_dev(P);
 		launch(P);
 	}
@@ -492,6 +619,7 @@ void Call::sam_stage()
 		if (dev_mid) { finish_dev(P); replay(P, 0); }
 		finish(P);
 		if (dev_last) { finish_dev(P); replay(P, 0); }
+		job_fetch(P.wave, P, FETCH_IF_HANDED_BACK, true);
 		if (n_parts == 1) hprof_report("decisions + request lists");
 		replay(P, 1);
 	}
@@ -508,7 +636,7 @@ void Call::report_decisions()
 	const uint8_t *codes = pstat ? pstat : se_codes;
 	uint64_t c[16] = {0};
 	for (int k = 0; k < n_units; ++k) ++c[codes[k] & 15];
-	if (pe) STAT.n_pair_dev = c[1];
+	if (pe) { STAT.n_pair_dev = c[1] - n_wave; STAT.n_pair_wave_dev = n_wave; }
 	else {
 		STAT.n_se_dev = c[1];
 		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu\n",
@@ -516,9 +644,10 @@ void Call::report_decisions()
 		                      (unsigned long long)c[SE_HOST_PATCH], (unsigned long long)c[SE_HOST_LENGTH], (unsigned long long)c[SE_HOST_ALT],
 		                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA]);
 	}
-	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu\n",
+	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
 	                      n_units, (unsigned long long)c[1], (unsigned long long)c[2], PR_MAXREG, (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[6],
-	                      (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11]);
+	                      (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11],
+	                      (unsigned long long)n_wave, (unsigned long long)c[PW_HOST_NO_RESULT], PW_MAXREG, (unsigned long long)c[PW_HOST_FULL], (unsigned long long)c[PW_HOST_TIE]);
 }
 
 } // namespace mbw

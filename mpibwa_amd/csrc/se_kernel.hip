@@ -79,7 +79,7 @@ se_simple_kernel(PairParams P, int n_reads, const DevReg *__restrict__ first, co
 	reqs[i] = q;
 	SamDesc d;
 	d.rb = R.d.rb; d.re = R.d.re; d.qb = R.d.qb; d.qe = R.d.qe; d.req = 0; d.rid = R.d.rid;
-	d.flag = 0; d.mapq = mapq_se(P, R, ltab) & 0xff; d.score = R.d.score; d.sub = R.sub;
+	d.flag = 0; d.mapq = mapq_se(P, R, ltab, 0) & 0xff; d.score = R.d.score; d.sub = R.sub;
 	desc[i] = d;
 	status[i] = SE_DECIDED;
 }
