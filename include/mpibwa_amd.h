@@ -328,6 +328,19 @@ int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint
                            int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
                            void *desc, void *req, int *n_align);
 
+/* The same sequence with the XA listing on: a pair whose chosen hits carry XA entries (mem_gen_alt, src/bwamem_extra.c:98-118: the
+ * hits i, in list order, with secondary_all = the chosen hit and score >= its score * XA_drop_ratio; 1 .. max_XA_hits of them) is
+ * decided too, with status 16 instead of code 11.  xa_cnt[2k + e] (2 n_pairs bytes): the entries of end e's record; xa_req
+ * (2 n_pairs * mi355x_pair_wave_xa_cap() requests of 40 bytes): entry j of end e at [(2k + e) * cap + j], the request mem_reg2aln would
+ * make for that hit, its contig in `pad`.  desc[2k + e].flag carries the count in bits 16-19 and desc[2k + 1].req = 1 + xa_cnt[2k]:
+ * the pair's requests in a job are [read 0's, its XA entries', read 1's, its XA entries'], which is how mi355x_sam_batch reads a
+ * descriptor with a count (the XA text behind the read group, "name,+-pos,CIGAR,NM;" per entry).  Status 1 still says "decided, both
+ * records without XA".  With max_XA_hits beyond the cap the entry behaves as mi355x_pair_wave_batch. */
+int mi355x_pair_wave_xa_cap(void);
+int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                              int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                              void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt);
+
 /* SAM text of the pairs decided on the device: the CIGAR kernel (aln_kernel) and sam_emit_kernel, queued on one stream as the
  * pipeline queues them, on chosen line descriptors.  2 n_pairs reads as nt4 codes (read r = reads[off[r] .. off[r+1])), their
  * qualities at the same places (or NULL: QUAL is '*'), their names back to back (read r = names[name_off[r] .. name_off[r+1])); the
@@ -419,6 +432,7 @@ typedef struct {
 	uint64_t n_pair_dev;                         /* pairs whose pairing decisions (mem_sam_pe) were taken on the device (pair_kernel.hip) */
 	uint64_t n_se_dev;                           /* single-end reads decided on the device (se_kernel.hip); their records count in n_sam_dev */
 	uint64_t n_pair_wave_dev;                    /* pairs with mate rescue or up to 64 hits per end decided on the device (pair_wave_kernel.hip); not counted in n_pair_dev */
+	uint64_t n_pair_xa_dev;                      /* pairs pair_wave_kernel decided because its XA listing is on: with an XA tag on a record, or left by pair_kernel.hip for its XA test alone and found to carry none; counted in neither of the two above */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

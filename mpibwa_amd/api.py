@@ -20,6 +20,7 @@ EXPORTS = [
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
+    "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap",
 ]
 
 
@@ -114,6 +115,8 @@ def load_library(build_if_missing=True):
     sig("mi355x_pair_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("mi355x_pair_wave_maxreg", C.c_int, [])
     sig("mi355x_pair_wave_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 8)
+    sig("mi355x_pair_wave_xa_cap", C.c_int, [])
+    sig("mi355x_pair_wave_xa_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 10)
     sig("mi355x_global_batch", C.c_int, [P(abi.mem_opt_t), C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 +
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_double)])
     sig("mi355x_sam_arena_bytes", C.c_size_t, [C.c_int, C.c_int])
@@ -390,7 +393,15 @@ class Engine:
             raise RuntimeError("mi355x_pair_batch: the kernel cannot use these insert-size statistics")
         return status, desc, req
 
-    def pairs_wave(self, opt, pes, reads, regs, n_processed=0):
+    PW_DECIDED_XA = 16
+
+    def pairs_wave_xa(self, opt, pes, reads, regs, n_processed=0):
+        """pairs_wave with the XA listing on (mi355x_pair_wave_xa_batch): status PW_DECIDED_XA = decided with an XA tag on a record.
+        -> status, desc, req, xa_req (per read an AREQ_DT array of its XA entries' requests, pad = the entry's contig), alignments run.
+        For sam_records the pair's requests are [req[2k], *xa_req[2k], req[2k + 1], *xa_req[2k + 1]]; desc already says so."""
+        return self.pairs_wave(opt, pes, reads, regs, n_processed, xa=True)
+
+    def pairs_wave(self, opt, pes, reads, regs, n_processed=0, xa=False):
         """pair_wave_kernel behind the pipeline's own rescue listing and mate-rescue kernel (mi355x_pair_wave_batch).  reads: 2 n_pairs nt4
         code arrays; regs: per read a REG_DT array of its regions after mem_sort_dedup_patch (at most mi355x_pair_wave_maxreg() are taken).
         -> status (n_pairs,) uint8, desc (2 n_pairs,) DESC_DT, req (2 n_pairs,) AREQ_DT, number of local alignments run"""
@@ -409,11 +420,20 @@ class Engine:
         desc = np.zeros(n, dtype=self.DESC_DT)
         req = np.zeros(n, dtype=self.AREQ_DT)
         n_align = C.c_int(0)
-        rc = self.lib.mi355x_pair_wave_batch(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), C.cast(pes, C.c_void_p), n_processed, n_pairs,
-                                             flat.ctypes.data, off.ctypes.data, allregs.ctypes.data, reg_off.ctypes.data, status.ctypes.data,
-                                             desc.ctypes.data, req.ctypes.data, C.cast(C.byref(n_align), C.c_void_p))
+        args = (opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), C.cast(pes, C.c_void_p), n_processed, n_pairs,
+                flat.ctypes.data, off.ctypes.data, allregs.ctypes.data, reg_off.ctypes.data, status.ctypes.data,
+                desc.ctypes.data, req.ctypes.data, C.cast(C.byref(n_align), C.c_void_p))
+        if xa:
+            cap = self.lib.mi355x_pair_wave_xa_cap()
+            xa_req = np.zeros((max(n, 1), cap), dtype=self.AREQ_DT)
+            xa_cnt = np.zeros(max(n, 1), dtype=np.uint8)
+            rc = self.lib.mi355x_pair_wave_xa_batch(*args, xa_req.ctypes.data, xa_cnt.ctypes.data)
+        else:
+            rc = self.lib.mi355x_pair_wave_batch(*args)
         if rc != 0:
             raise RuntimeError("mi355x_pair_wave_batch: the kernel cannot use these insert-size statistics")
+        if xa:
+            return status, desc, req, [xa_req[r, :xa_cnt[r]].copy() for r in range(n)], n_align.value
         return status, desc, req, n_align.value
 
     def singles(self, opt, regs, n_regs, max_len=150, n_processed=0):

@@ -232,8 +232,11 @@ struct SamDesc {                 // one output line: the chosen hit of a read as
 	int64_t rb, re;              // region in the doubled coordinate
 	int32_t qb, qe;
 	int32_t req;                 // its CIGAR request, relative to the first request of the pair; < 0: the line is not the device's
-	int32_t rid, flag, mapq, score, sub;
+	int32_t rid, flag, mapq, score, sub;   // flag: the SAM flag in bits 0-15; bits 16-19: the number of XA entries of the line, whose
+	                                       // requests follow the line's own (AlnReq::pad = the entry's contig)
 };
+#define SAM_XA_SHIFT 16
+#define SAM_XA_MASK 15
 struct SamParams {
 	int64_t l_pac;
 	int has_qual, rg_len;
@@ -270,13 +273,14 @@ void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const Chun
 // d_req_base[pair] = first CIGAR request of the pair in d_hdr; out_len[r] = bytes of the record at arena + out_off[r],
 // -1 = the host must format the pair, -2 = not a line of the device.  grid_blocks > 0 caps the number of workgroups (stage tests:
 // the grid-stride loop with a few thousand reads); 0 = the launcher's own choice
-void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+// d_req: the requests d_hdr answers (read by the lines with XA entries only; may be null when no descriptor has any)
+void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr,
                      const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                      uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
                      int grid_blocks = 0);
 // the single-end instantiation: a unit is one read (d_req_base[read]), no mate descriptor, a read is handed back alone
-void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr,
                         const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                         const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                         uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
@@ -324,15 +328,26 @@ extern "C" int mi355x_pair_wave_maxreg(void);
 #define PW_HOST_NO_RESULT 12      // a rescue alignment the replay needs is not on the device (not listed, flagged by msw2_kernel, host only)
 #define PW_HOST_FULL 13           // a list past PW_MAXREG
 #define PW_HOST_TIE 14            // the outcome depends on the reference's unstable sorts (equal end positions, equal (score, hash))
+#define PW_DECIDED_XA 16          // decided, and at least one of the two records carries an XA tag (status 1: decided, both records plain)
+#define PW_XA_CAP 8               // XA entries per record the kernel lists; a call with max_XA_hits beyond it runs without XA on the device
+extern "C" int mi355x_pair_wave_xa_cap(void);
 // tags per (end, candidate hit, orientation): >= 0 the alignment's number in the pair's slice of the mate-rescue requests
 #define PW_TAG_NO_WINDOW (-1)     // mem_matesw would align nothing there (src/bwamem_pair.c:150)
 #define PW_TAG_HOST (-2)          // not listed (explained by a mate hit before any rescue) or a window msw2_kernel does not take
 // work[t]: the pair's number in the chunk (reads 2 work[t], 2 work[t] + 1 of d_len); reqs / desc [2t + e] are written when
-// wstatus[t] = 1 and left alone otherwise; lists[loff[2t + e] .. loff[2t + e + 1]): end e's regions after mem_sort_dedup_patch;
+// wstatus[t] = 1 or PW_DECIDED_XA and left alone otherwise; lists[loff[2t + e] .. loff[2t + e + 1]): end e's regions after mem_sort_dedup_patch;
 // mreq / mres[mfirst[t] + tag]; tags[toff[t] ..]: 4 per candidate hit, end 0's candidates first
 void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
                       const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
-                      const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc);
+                      const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc,
+                      AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr);
+// d_xa_reqs given (and max_XA_hits <= PW_XA_CAP): a pair whose chosen hits carry XA entries (src/bwamem_extra.c:98-118) is decided too,
+// with status PW_DECIDED_XA: xa_cnt[2t + e] entries of end e, their requests (as mem_reg2aln would ask, pad = the hit's contig) at
+// xa_reqs[(2t + e) * PW_XA_CAP ..], desc[2t + e].flag bits 16-19 = the count, desc[2t].req = 0, desc[2t + 1].req = 1 + xa_cnt[2t].
+// The XA pairs' requests and descriptors to their places in a job of their own: dst[t] = first request of work item t's pair in
+// `reqs`, or < 0 (not an XA pair); [req of read 0, its XA requests, req of read 1, its XA requests]; desc: chunk-wide, by read
+void launch_pair_wave_xa_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                                 const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
 // the decided pairs' records into the chunk-wide arrays (reqs / desc [2 work[t] + e]); clear_n > 0: reads clear_r0 .. + clear_n are
 // marked "not the device's" first (the arrays then describe the wave's pairs alone)
 void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const uint8_t *d_wstatus, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,

@@ -474,7 +474,7 @@ void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const Chun
 	if (J.h_desc) HIP_OK(hipMemcpyAsync(J.d_desc + r0, J.h_desc + r0, (size_t)nr * sizeof(SamDesc), hipMemcpyHostToDevice, st));
 	HIP_OK(hipMemcpyAsync(J.d_base, J.h_base, (size_t)(nu + 1) * 4, hipMemcpyHostToDevice, st));
 	HIP_OK(hipMemsetAsync(J.d_used, 0, 64, st));
-	(J.ends == 2 ? launch_sam_emit : launch_sam_emit_se)(st, sp, nr, J.d_desc + r0, J.d_base, J.d_hdr, J.d_pool, D.d_seq, D.d_off + r0, D.d_len + r0, D.d_qual, D.d_names,
+	(J.ends == 2 ? launch_sam_emit : launch_sam_emit_se)(st, sp, nr, J.d_desc + r0, J.d_base, J.d_req, J.d_hdr, J.d_pool, D.d_seq, D.d_off + r0, D.d_len + r0, D.d_qual, D.d_names,
 	                                                   D.d_noff + r0, D.d_ann_off, D.d_ann_names, D.d_ann_noff, J.d_arena, J.arena_bytes, J.d_used, J.d_ooff, J.d_olen,
 	                                                   J.grid_blocks);
 }
@@ -629,10 +629,13 @@ extern "C" int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, cons
 // desc[2k], desc[2k + 1] (SamDesc) and req[2k], req[2k + 1] (AlnReq) are what mem_sam_pe's paired branch reports; else the code of the
 // test that left the pair to the host.  *n_align = mate-rescue alignments run.  Returns 0, or -1 when the insert-size statistics are not
 // usable by the kernel.
+// xa_req given: XA on (mi355x_pair_wave_xa_batch) — status PW_DECIDED_XA: decided with an XA tag on a record; xa_cnt[2k + e] entries of
+// end e, their requests at xa_req[(2k + e) * PW_XA_CAP ..] (AlnReq, pad = the entry's contig), the counts also in desc[].flag bits 16-19.
 extern "C" int mi355x_pair_wave_maxreg(void) { return PW_MAXREG; }
-extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
-                                      int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
-                                      void *desc, void *req, int *n_align)
+extern "C" int mi355x_pair_wave_xa_cap(void) { return PW_XA_CAP; }
+static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                           int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                           void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt)
 {
 	int nd = 0;
 	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
@@ -642,6 +645,7 @@ extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns,
 	memset(status, 0, (size_t)n_pairs);
 	memset(desc, 0xff, (size_t)n_reads * sizeof(SamDesc));
 	memset(req, 0xff, (size_t)n_reads * sizeof(AlnReq));
+	if (xa_req) { memset(xa_req, 0xff, (size_t)n_reads * PW_XA_CAP * sizeof(AlnReq)); memset(xa_cnt, 0, (size_t)n_reads); }
 	// (the calls whose pairs are all the host's, as for pair_simple_kernel: -P, -a, -V, -5, mapQ_coef_len 0)
 	if ((opt->flag & (MEM_F_NOPAIRING | MEM_F_ALL | MEM_F_REF_HDR | MEM_F_PRIMARY5)) || !(opt->mapQ_coef_len > 0)) return 0;
 	const int64_t l_pac = bns->l_pac;
@@ -678,7 +682,7 @@ extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns,
 		for (int e = 0; e < 2 && ok; ++e) {
 			for (int j = reg_off[2 * k + e]; j < reg_off[2 * k + e + 1]; ++j) {
 				const DevReg &d = hr[j];
-				if (d.rid < 0 || d.rid >= bns->n_seqs) die("mi355x_pair_wave_batch: bad contig in a region of pair %d", k);
+				if (d.rid < 0 || d.rid >= bns->n_seqs) die("%s: bad contig in a region of pair %d", who, k);
 				HReg h;
 				h.rb = d.rb; h.re = d.re; h.qb = d.qb; h.qe = d.qe; h.rid = d.rid; h.score = d.score; h.truesc = d.truesc; h.w = d.w;
 				h.seedcov = d.seedcov; h.seedlen0 = d.seedlen0; h.frac_rep = d.frac_rep; h.secondary = -1; h.is_alt = bns->anns[d.rid].is_alt;
@@ -748,8 +752,12 @@ extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns,
 	uint8_t *d_ws = (uint8_t *)up(nullptr, (size_t)n_work);
 	AlnReq *d_rq = (AlnReq *)up(nullptr, (size_t)2 * n_work * sizeof(AlnReq));
 	SamDesc *d_ds = (SamDesc *)up(nullptr, (size_t)2 * n_work * sizeof(SamDesc));
+	AlnReq *d_xr = xa_req ? (AlnReq *)up(nullptr, (size_t)2 * n_work * PW_XA_CAP * sizeof(AlnReq)) : nullptr;
+	uint8_t *d_xc = xa_req ? (uint8_t *)up(nullptr, (size_t)2 * n_work) : nullptr;
 	HIP_OK(hipMemset(d_ws, 0, (size_t)n_work));
-	launch_pair_wave(st, pp, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst, d_tags, d_toff, d_ao, d_tab, d_tab + n_tab, d_ws, d_rq, d_ds);
+	if (d_xc) HIP_OK(hipMemset(d_xc, 0, (size_t)2 * n_work));
+	launch_pair_wave(st, pp, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst, d_tags, d_toff, d_ao, d_tab, d_tab + n_tab, d_ws, d_rq, d_ds,
+	                 d_xr, d_xc);
 	HIP_OK(hipDeviceSynchronize());
 	HIP_OK(hipGetLastError());
 	std::vector<uint8_t> ws((size_t)n_work);
@@ -758,13 +766,40 @@ extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns,
 	std::vector<AlnReq> w_rq((size_t)2 * n_work);
 	HIP_OK(hipMemcpy(w_ds.data(), d_ds, w_ds.size() * sizeof(SamDesc), hipMemcpyDeviceToHost));
 	HIP_OK(hipMemcpy(w_rq.data(), d_rq, w_rq.size() * sizeof(AlnReq), hipMemcpyDeviceToHost));
+	std::vector<AlnReq> w_xr(xa_req ? (size_t)2 * n_work * PW_XA_CAP : 0);
+	std::vector<uint8_t> w_xc(xa_req ? (size_t)2 * n_work : 0);
+	if (xa_req) {
+		HIP_OK(hipMemcpy(w_xr.data(), d_xr, w_xr.size() * sizeof(AlnReq), hipMemcpyDeviceToHost));
+		HIP_OK(hipMemcpy(w_xc.data(), d_xc, w_xc.size(), hipMemcpyDeviceToHost));
+	}
 	for (int t = 0; t < n_work; ++t) {
 		status[work[t]] = ws[t];
-		if (ws[t] != 1) continue;
+		if (ws[t] != 1 && ws[t] != PW_DECIDED_XA) continue;
 		for (int e = 0; e < 2; ++e) { ((SamDesc *)desc)[2 * work[t] + e] = w_ds[2 * t + e]; ((AlnReq *)req)[2 * work[t] + e] = w_rq[2 * t + e]; }
+		if (ws[t] != PW_DECIDED_XA) continue;
+		for (int e = 0; e < 2; ++e) {
+			const int c = std::min<int>(w_xc[2 * t + e], PW_XA_CAP);
+			xa_cnt[2 * work[t] + e] = (uint8_t)c;
+			memcpy((AlnReq *)xa_req + (size_t)(2 * work[t] + e) * PW_XA_CAP, &w_xr[(size_t)(2 * t + e) * PW_XA_CAP], (size_t)c * sizeof(AlnReq));
+		}
 	}
 	for (void *d : owned) (void)hipFree(d);
 	return 0;
+}
+extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                      int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                      void *desc, void *req, int *n_align)
+{
+	return pair_wave_batch("mi355x_pair_wave_batch", opt, bns, pac, pes, n_processed, n_pairs, reads, off, regs, reg_off, status, desc, req, n_align, nullptr,
+	                       nullptr);
+}
+extern "C" int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                         int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                         void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt)
+{
+	if (!xa_req || !xa_cnt) die("mi355x_pair_wave_xa_batch: no room for the XA requests");
+	return pair_wave_batch("mi355x_pair_wave_xa_batch", opt, bns, pac, pes, n_processed, n_pairs, reads, off, regs, reg_off, status, desc, req, n_align, xa_req,
+	                       xa_cnt);
 }
 
 extern "C" int mi355x_smem_batch(const mem_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off, int cap,
@@ -1387,6 +1422,9 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 			const int q = req_base[k] + d.req;
 			if (q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != r) die("%s: bad descriptor %d", who, r);
 			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[r] || d.qb > d.qe) die("%s: bad region %d", who, r);
+			for (int j = 1; j <= (d.flag >> SAM_XA_SHIFT & SAM_XA_MASK); ++j)   // its XA entries' requests follow its own
+				if (q + j >= req_base[k + 1] || reqs[q + j].read != r || reqs[q + j].pad < 0 || reqs[q + j].pad >= bns->n_seqs || reqs[q + j].rb >= reqs[q + j].re)
+					die("%s: bad XA request %d of descriptor %d", who, j, r);
 		}
 	}
 	for (int q = 0; q < n_req; ++q) {

@@ -9,7 +9,8 @@
 //   mem_mark_primary_se   src/bwamem.c:493-569        (reads without ALT hits)
 //   mem_pair              src/bwamem_pair.c:182-243
 //   mem_approx_mapq_se    src/bwamem.c:952-976        (with csub: a rescued hit carries the score of its tandem copy)
-//   mem_gen_alt           src/bwamem_extra.c:98-118   (only "does the chosen hit get an XA string?")
+//   mem_gen_alt           src/bwamem_extra.c:98-118   (which hits the chosen hit's XA string lists: their CIGAR requests; the text is
+//                                                       sam_emit_kernel's)
 //   mem_reg2aln           src/bwamem.c:1089-1105      (the band of the final global alignment)
 // The pairs are the ones pair_simple_kernel leaves with "rescue", "more than eight hits" or "one end without a hit".  The host hands over
 // both ends' lists as they stand after mem_sort_dedup_patch (fixed points of the pass: HRegV::settled), at most PW_MAXREG regions each,
@@ -17,7 +18,7 @@
 // mate-rescue results, "the window is invalid: the reference aligns nothing", or "not on the device".
 //
 // One region per lane, both lists in LDS as one array per field (no bank conflicts, 2 x 64 x 64 B), mem_pair's keys behind them
-// (128 x 16 B) and the rescue candidates: 11 776 B of LDS per wave, 54 VGPRs, no scratch (the compiler's resource usage for gfx950).  The two sorts are rank sorts: mem_pair's keys are unique, so any sort gives the reference's array; two
+// (128 x 16 B) and the rescue candidates: 11 776 B of LDS per wave, 55 VGPRs, no scratch (the compiler's resource usage for gfx950).  The two sorts are rank sorts: mem_pair's keys are unique, so any sort gives the reference's array; two
 // hits with equal (score, hash) in mem_mark_primary_se — where the reference's unstable sort would decide — send the pair to the host.
 // The list u of mem_pair is never stored: only its maximum, the second-largest score and n_sub are used, so it is enumerated twice
 // and reduced.  Anything the wave cannot settle the way the reference does leaves the pair to the host with a code that says why.
@@ -247,11 +248,15 @@ __device__ __forceinline__ void pw_pairs_of(const PairParams &P, const Pair64 *V
 // work[t]: the pair (number in the chunk); its lists: lists[loff[2t + e] .. loff[2t + e + 1]); its mate-rescue alignments:
 // mreq / mres[mfirst[t] ..]; tags[toff[t] + 4 * (candidate) + orientation], the candidates of end 0 first, then end 1's (toff: n_work + 1 entries).
 // wstatus[t] = 1: reqs / desc [2t + e] are the pair's, as pair_simple_kernel writes them (reqs.read = 2 work[t] + e); else untouched.
+// xa_reqs given: a chosen hit with XA entries no longer sends the pair to the host.  wstatus[t] = PW_DECIDED_XA, xa_cnt[2t + e] entries
+// of end e with their requests at xa_reqs[(2t + e) * PW_XA_CAP ..], in list order; desc[2t + e].flag carries the count in bits 16-19 and
+// desc[2t + 1].req = 1 + xa_cnt[2t] (the pair's requests in a job: read 0's, its XA entries', read 1's, its XA entries').
 __global__ void __launch_bounds__(64)
 pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const DevReg *__restrict__ lists, const int *__restrict__ loff,
                  const int *__restrict__ len, const MswReq *__restrict__ mreq, const MswRes *__restrict__ mres, const unsigned *__restrict__ mfirst,
                  const short *__restrict__ tags, const int *__restrict__ toff, const i64 *__restrict__ ann_off, const double *__restrict__ ptab,
-                 const double *__restrict__ ltab, uint8_t *__restrict__ wstatus, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
+                 const double *__restrict__ ltab, uint8_t *__restrict__ wstatus, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc,
+                 AlnReq *__restrict__ xa_reqs, uint8_t *__restrict__ xa_cnt)
 {
 	__shared__ WList L[2];
 	__shared__ Pair64 V[2 * PW_MAXREG];
@@ -442,12 +447,27 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 		}
 	}
 	// ---- does the chosen hit get an XA string (src/bwamem_extra.c:105-118, no ALT hit here)?  Only with 1 .. max_XA_hits qualifying
-	// secondary hits under it; more than that and the reference writes none
+	// secondary hits under it; more than that and the reference writes none.  Its entries are those hits in list order (:115-131)
+	int n_xa[2];
+	u64 xa_hits[2];
 	for (int e = 0; e < 2; ++e) {
-		const int n_xa = __popcll(__ballot(lane < n[e] && L[e].secondary_all[lane] == z[e] &&
-		                                   L[e].score[lane] >= L[e].score[z[e]] * (double)P.XA_drop_ratio));
-		if (n_xa > 0 && n_xa <= P.max_XA_hits) PW_GIVE_UP(PW_HOST_XA);
+		xa_hits[e] = __ballot(lane < n[e] && L[e].secondary_all[lane] == z[e] && L[e].score[lane] >= L[e].score[z[e]] * (double)P.XA_drop_ratio);
+		n_xa[e] = __popcll(xa_hits[e]);
+		if (n_xa[e] > P.max_XA_hits) { n_xa[e] = 0; xa_hits[e] = 0; }
+		if (n_xa[e] > 0 && (!xa_reqs || n_xa[e] > PW_XA_CAP)) PW_GIVE_UP(PW_HOST_XA);
 	}
+	for (int e = 0; e < 2; ++e)   // a lane per listed hit: the request mem_reg2aln would make for it (src/bwamem.c:1089-1105)
+		if (xa_hits[e] >> lane & 1) {
+			const WReg R = wl_get(L[e], lane);
+			const int l1 = R.qe - R.qb, l2 = (int)(R.re - R.rb);
+			const int t2 = infer_bw(l1, l2, R.truesc, P.a, P.o_del, P.e_del);
+			int w2 = infer_bw(l1, l2, R.truesc, P.a, P.o_ins, P.e_ins);
+			w2 = w2 > t2 ? w2 : t2;
+			if (w2 > P.w) w2 = w2 < R.w ? w2 : R.w;
+			AlnReq q;
+			q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = R.rid;
+			xa_reqs[(size_t)(2 * t + e) * PW_XA_CAP + __popcll(xa_hits[e] & (((u64)1 << lane) - 1))] = q;
+		}
 	if (lane < 2) {
 		const int e = lane;
 		const WReg R = wl_get(L[e], z[e]);
@@ -460,21 +480,24 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 		q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = 0;
 		reqs[2 * t + e] = q;
 		SamDesc d;
-		d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = e; d.rid = R.rid;
-		d.flag = 0x40 << e | extra_flag; d.mapq = q_se[e] & 0xff; d.score = R.score;
+		d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = e ? 1 + n_xa[0] : 0; d.rid = R.rid;
+		d.flag = 0x40 << e | extra_flag | n_xa[e] << SAM_XA_SHIFT; d.mapq = q_se[e] & 0xff; d.score = R.score;
 		d.sub = sub_z[e] > R.csub ? sub_z[e] : R.csub;   // mem_reg2aln: sub = max(sub, csub)
 		desc[2 * t + e] = d;
+		if (xa_cnt) xa_cnt[2 * t + e] = (uint8_t)n_xa[e];
 	}
-	if (lane == 0) wstatus[t] = 1;
+	if (lane == 0) wstatus[t] = n_xa[0] + n_xa[1] ? PW_DECIDED_XA : 1;
 }
 
 void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
                       const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
-                      const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc)
+                      const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc,
+                      AlnReq *d_xa_reqs, uint8_t *d_xa_cnt)
 {
 	if (n_work <= 0) return;
+	if (!d_xa_cnt || P.max_XA_hits > PW_XA_CAP) d_xa_reqs = nullptr, d_xa_cnt = nullptr;   // (XA off: the kernel as it was)
 	hipLaunchKernelGGL(pair_wave_kernel, dim3(n_work), dim3(64), 0, (hipStream_t)stream, P, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst,
-	                   d_tags, d_toff, (const i64 *)d_ann_off, d_ptab, d_ltab, d_wstatus, d_reqs, d_desc);
+	                   d_tags, d_toff, (const i64 *)d_ann_off, d_ptab, d_ltab, d_wstatus, d_reqs, d_desc, d_xa_reqs, d_xa_cnt);
 }
 
 // the decided pairs' requests and descriptors into the chunk-wide arrays the CIGAR-and-SAM job reads
@@ -484,6 +507,11 @@ __global__ void pair_wave_clear_kernel(int r0, int n_reads, AlnReq *__restrict__
 	if (i >= n_reads) return;
 	reqs[r0 + i].read = -1;
 	desc[r0 + i].req = -1;
+}
+__global__ void pair_wave_clear_desc_kernel(int r0, int n_reads, SamDesc *__restrict__ desc)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n_reads) desc[r0 + i].req = -1;
 }
 __global__ void pair_wave_scatter_kernel(int n_work, const int *__restrict__ work, const uint8_t *__restrict__ wstatus, const AlnReq *__restrict__ w_reqs,
                                          const SamDesc *__restrict__ w_desc, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
@@ -502,6 +530,31 @@ void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const
 	if (n_work > 0)
 		hipLaunchKernelGGL(pair_wave_scatter_kernel, dim3((2 * n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_work, d_wstatus, d_w_reqs, d_w_desc,
 		                   d_reqs, d_desc);
+}
+
+
+// the XA pairs into the job of their own: a thread per work item
+__global__ void pair_wave_xa_scatter_kernel(int n_work, const int *__restrict__ work, const int *__restrict__ dst, const AlnReq *__restrict__ w_reqs,
+                                            const SamDesc *__restrict__ w_desc, const AlnReq *__restrict__ xa_reqs, const uint8_t *__restrict__ xa_cnt,
+                                            AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
+{
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= n_work || dst[t] < 0) return;
+	int at = dst[t];
+	for (int e = 0; e < 2; ++e) {
+		reqs[at++] = w_reqs[2 * t + e];
+		const int c = xa_cnt[2 * t + e] < PW_XA_CAP ? xa_cnt[2 * t + e] : PW_XA_CAP;
+		for (int j = 0; j < c; ++j) reqs[at++] = xa_reqs[(size_t)(2 * t + e) * PW_XA_CAP + j];
+		desc[2 * work[t] + e] = w_desc[2 * t + e];
+	}
+}
+void launch_pair_wave_xa_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                                 const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n)
+{
+	if (clear_n > 0) hipLaunchKernelGGL(pair_wave_clear_desc_kernel, dim3((clear_n + 255) / 256), dim3(256), 0, (hipStream_t)stream, clear_r0, clear_n, d_desc);
+	if (n_work > 0)
+		hipLaunchKernelGGL(pair_wave_xa_scatter_kernel, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_work, d_dst, d_w_reqs, d_w_desc,
+		                   d_xa_reqs, d_xa_cnt, d_reqs, d_desc);
 }
 
 } // namespace mbw

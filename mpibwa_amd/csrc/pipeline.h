@@ -239,6 +239,11 @@ struct ChunkBufs {
 	PinBuf h_wwork[2], h_wlists[2], h_wloff[2], h_wmfirst[2], h_wtags[2], h_wtoff[2], h_wstatus[2];
 	DevBuf wwork[2], wlists[2], wloff[2], wmfirst[2], wtags[2], wtoff[2], wstatus[2], wreq[2], wdesc[2];
 	JobBufs wave_job[2];  // their job when the device units' job of the part has already gone out
+	// the pairs it decided with an XA tag: the entries' requests and counts per work item, where each item's requests go in the job of
+	// these pairs, that job's requests, and its descriptors (chunk-wide, by read)
+	PinBuf h_wxcnt[2], h_wxdst[2];
+	DevBuf wxreq[2], wxcnt[2], wxdst[2], xa_req[2], xa_desc;
+	JobBufs xa_job[2];
 	PinBuf h_areq[2];     // the host's CIGAR requests of a part, as listed
 	JobBufs host_job[2];  // the host's units ...
 	JobBufs dev_job[2];   // ... and the units decided on the device, launched right behind the deciding kernel
@@ -312,6 +317,10 @@ struct Part {
 	const uint8_t *wstatus = nullptr;
 	int n_wave_dec = 0;
 	Job wave;                         // the job of the pairs it decided, when they do not ride in `dev`
+	const uint8_t *wxcnt = nullptr;   // XA entries per (work item, end), with the status bytes
+	int n_xa_dec = 0;                 // the pairs it decided with an XA tag, their request bases (per unit of the part) and their job
+	std::vector<uint32_t> xa_base;
+	Job xa;
 	// CIGAR requests while they are being listed: per block of 256 units, and where each unit's run starts
 	std::vector<std::vector<AlnReqH>> blk_req;
 	std::vector<uint32_t> u_first, u_cnt;
@@ -368,6 +377,9 @@ struct Call {
 	// ---- units decided on the device (sam_stage.hip) ----
 	uint8_t *pstat_w = nullptr;          // (pstat, writable: pair_wave_kernel's decisions are merged in)
 	bool dev_wave = false;               // pair_wave_kernel takes the pairs pair_simple_kernel leaves for rescue / long lists
+	bool dev_xa = false;                 // ... and the ones it leaves for an XA tag; it lists the tag's entries (MPIBWA_HOST_XA=1: off)
+	uint64_t n_xa_pairs = 0;             // decided with an XA tag, or handed over for the XA test alone and decided without one
+	uint64_t n_xa_plain = 0;             // (the latter: status 1, riding with the wave's other pairs)
 	std::vector<uint8_t> wave_cand, wave_dec;   // per pair: handed to pair_wave_kernel; decided by it
 	PairParams wave_pp;
 	const double *d_wave_tab = nullptr;  // the tables of decide_on_device, still on the device
@@ -395,13 +407,14 @@ struct Call {
 	void mfinish(Part &P);
 	void wave_launch(Part &P);        // pair_wave_kernel behind the mate-rescue kernel of the part (asynchronous)
 	void wave_records(Part &P, bool own_job);   // its pairs into the device units' arrays; own_job: and a job of their own
+	void xa_records(Part &P);         // its pairs with an XA tag: always a job of their own
 	void collect(Part &P, int round); // A: decisions + the list of CIGARs to compute
 	void launch_dev(Part &P);         // the job of the units decided on the device (asynchronous)
 	void finish_dev(Part &P);
 	void launch(Part &P);             // B: the job of the host's units (asynchronous)
 	void finish(Part &P);
 	void replay(Part &P, int which);  // C: the records
-	enum Fetch { FETCH_ALWAYS, FETCH_IF_HANDED_BACK };
+	enum Fetch { FETCH_ALWAYS, FETCH_IF_HANDED_BACK, FETCH_RECORDS };
 	void job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const AlnReq *d_req, size_t n_req, const uint32_t *base, bool with_sam,
 	                const SamDescH *h_desc, SamDesc *d_desc);
 	void job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units = false);

@@ -3,8 +3,9 @@
 // Device counterpart of the tail of mem_reg2aln (src/bwamem.c:1123-1157: position, strand, squeeze of a leading /
 // trailing deletion, soft clips) and of mem_aln2sam (src/bwamem.c:825-946) for the case that makes up the bulk of a
 // chunk: a pair that mem_sam_pe reports through its "paired" branch (src/bwamem_pair.c:315-345) with ONE line per read —
-// no supplementary / ALT line, no XA, no pa tag, no comment, no XR — and (round 3) the two records of a pair without any hit.  Everything else (unpaired ends, supplementary
-// lines, XA, -a, -C, -V) stays with the host's formatter (host_regs.cpp: aln2sam), and the host takes
+// no supplementary / ALT line, no pa tag, no comment, no XR; an XA tag when the descriptor lists its entries (mem_gen_alt,
+// src/bwamem_extra.c:115-131, for pair_wave_kernel's pairs) — and (round 3) the two records of a pair without any hit.  Everything else (unpaired ends, supplementary
+// lines, other XA, -a, -C, -V) stays with the host's formatter (host_regs.cpp: aln2sam), and the host takes
 // a pair back whenever the device flags one of its reads (CIGAR computed by the host, record longer than the staging
 // buffer).  The host decides WHICH records are written here and all their numbers that involve floating point
 // (MAPQ); the kernel turns numbers into bytes.  The single-end instantiation (sam_emit_kernel<false>) writes the one record of a
@@ -17,11 +18,15 @@
 //      back to back (an atomic per record, 1.3 M on one address, cost more than the rest of the kernel).
 //   2. the wave walks its records and copies each out across the lanes: QNAME, piece, RNAME, piece, SEQ, QUAL, piece, MD,
 //      piece, RG — 64 consecutive bytes per store.
+// The XA tag does not pass through the row (five entries are 140 bytes: with the short fields they would outgrow it).  Phase 1 adds up
+// its length, entry by entry, without storing a byte; phase 2 writes it behind the read group: a lane per entry prints ",±pos,CIGAR,NM;"
+// into a staging slot of XA_STAGE bytes in LDS, then the wave copies contig name and slot, entry after entry, into the arena.
 #include <hip/hip_runtime.h>
 #include "device.h"
 
 namespace mbw {
 
+#define XA_STAGE 64      // bytes of LDS per XA entry being written (",±pos,CIGAR,NM;": a CIGAR of a dozen operations fits), 16 entries
 #define SAM_ROW 260      // bytes of LDS scratch per lane (65 dwords: rows start in different banks); a record whose short
                          // fields outgrow it (a CIGAR of dozens of operations) goes back to the host
 
@@ -74,7 +79,8 @@ __device__ __forceinline__ SamAln sam_aln(const SamDesc &D, const AlnHdr *__rest
 struct Sink {
 	uint8_t *row;
 	int len;
-	__device__ __forceinline__ void ch(char c) { if (len < SAM_ROW) row[len] = (uint8_t)c; ++len; }
+	int cap = SAM_ROW;   // (0: the bytes are counted only)
+	__device__ __forceinline__ void ch(char c) { if (len < cap) row[len] = (uint8_t)c; ++len; }
 	__device__ __forceinline__ void lit(const char *s) { for (; *s; ++s) ch(*s); }
 	__device__ __forceinline__ void num32(uint32_t u)
 	{
@@ -107,6 +113,24 @@ struct Sink {
 	}
 };
 
+// XA entry j of the line D (its request follows the line's own): the alignment as mem_reg2aln leaves it, clips as S
+__device__ __forceinline__ SamAln xa_aln(const SamDesc &D, int j, const AlnReq *__restrict__ reqs, const AlnHdr *__restrict__ hdr, const uint8_t *__restrict__ pool,
+                                         int req_base, long long l_pac, const long long *__restrict__ ann_off, int l_query)
+{
+	const AlnReq q = reqs[req_base + D.req + 1 + j];
+	SamDesc X;
+	X.rb = q.rb; X.re = q.re; X.qb = q.qb; X.qe = q.qe; X.req = D.req + 1 + j; X.rid = q.pad;
+	X.flag = X.mapq = X.score = X.sub = 0;
+	return sam_aln(X, hdr, pool, req_base, l_pac, ann_off, l_query);
+}
+// the entry behind its contig name (src/bwamem_extra.c:122-129)
+__device__ __forceinline__ void xa_numbers(Sink &S, const SamAln &x)
+{
+	S.ch(','); S.ch(x.is_rev ? '-' : '+'); S.num(x.pos + 1);
+	S.ch(','); S.cigar(x);
+	S.ch(','); S.num32((uint32_t)x.NM); S.ch(';');
+}
+
 template <class T>
 __device__ __forceinline__ T bcast(T v, int src)   // the value lane `src` (wave-uniform) holds
 {
@@ -124,13 +148,15 @@ __device__ __forceinline__ T bcast(T v, int src)   // the value lane `src` (wave
 // back to the host together); !PE: single-end records (a unit is a read, "*\t0\t0" for the mate columns, a read goes back alone)
 template <bool PE>
 __global__ void __launch_bounds__(64)
-sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, const int *__restrict__ req_base, const AlnHdr *__restrict__ hdr,
+sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, const int *__restrict__ req_base, const AlnReq *__restrict__ reqs,
+                const AlnHdr *__restrict__ hdr,
                 const uint8_t *__restrict__ pool, const uint8_t *__restrict__ seq, const int64_t *__restrict__ off, const int *__restrict__ lens,
                 const uint8_t *__restrict__ qual, const uint8_t *__restrict__ names, const int *__restrict__ name_off,
                 const long long *__restrict__ ann_off, const char *__restrict__ ann_names, const int *__restrict__ ann_name_off,
                 uint8_t *__restrict__ arena, unsigned long long arena_bytes, unsigned long long *arena_used, unsigned long long *out_off, int *out_len)
 {
 	__shared__ uint8_t rows[64 * SAM_ROW];
+	__shared__ uint8_t xa_rows[(SAM_XA_MASK + 1) * XA_STAGE];
 	const int lane = threadIdx.x;
 	const int n_batch = (n_reads + 63) >> 6;
 	for (int bt = blockIdx.x; bt < n_batch; bt += gridDim.x) {
@@ -140,6 +166,7 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 		int total = 0;                   // bytes of the record
 		int e_a = 0, e_b = 0, e_c = 0, e_d = 0;   // ends of the four pieces in the row
 		int name_at = 0, name_len = 0, rn_at = 0, rn_len = 0, mn_at = 0, mn_len = 0, lq = 0, is_rev = 0, md_len = 0;
+		int n_xa = 0, xa_len = 0;        // entries and bytes of the XA tag
 		long long sq_at = 0;
 		const uint8_t *md = nullptr;
 		if (r < n_reads) {
@@ -211,9 +238,21 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 					if (D.sub >= 0) { S.lit("\tXS:i:"); S.num32(D.sub); }
 					if (P.rg_len) S.lit("\tRG:Z:");
 					is_rev = p.is_rev; sq_at = off[r];
-					if (S.len <= SAM_ROW) {
-						// QNAME a RNAME b [mate RNAME] c SEQ \t [QUAL] d MD rest RG \n
-						total = name_len + S.len + rn_len + mn_len + lq + 1 + (P.has_qual ? lq : 0) + md_len + P.rg_len + 1;
+					// the XA tag: "\tXA:Z:" and per entry "name,±pos,CIGAR,NM;", counted here; a declined CIGAR among them and the pair is the host's
+					bool xa_ok = true;
+					n_xa = reqs ? D.flag >> SAM_XA_SHIFT & SAM_XA_MASK : 0;
+					if (n_xa) xa_len = 6;
+					for (int j = 0; j < n_xa && xa_ok; ++j) {
+						const SamAln x = xa_aln(D, j, reqs, hdr, pool, req_base[unit], P.l_pac, ann_off, lq);
+						Sink C;
+						C.row = nullptr; C.len = 0; C.cap = 0;
+						xa_numbers(C, x);
+						xa_ok = x.ok && C.len <= XA_STAGE;
+						xa_len += ann_name_off[x.rid + 1] - ann_name_off[x.rid] + C.len;
+					}
+					if (S.len <= SAM_ROW && xa_ok) {
+						// QNAME a RNAME b [mate RNAME] c SEQ \t [QUAL] d MD rest RG [XA] \n
+						total = name_len + S.len + rn_len + mn_len + lq + 1 + (P.has_qual ? lq : 0) + md_len + P.rg_len + xa_len + 1;
 						status = total;
 					}
 				}
@@ -271,9 +310,34 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 			}
 			spread(ed - ec, [&](int k) { return row[ec + k]; });
 			{ const uint8_t *mdp = bcast(md, i); spread(bcast(md_len, i), [&](int k) { return mdp[k]; }); }
-			const int rest = bcast(status, i) - (int)(o - (arena + bcast(at_mine, i))) - P.rg_len - 1;   // what is left of the row
+			const int nx = bcast(n_xa, i);
+			const int rest = bcast(status, i) - (int)(o - (arena + bcast(at_mine, i))) - P.rg_len - bcast(xa_len, i) - 1;   // what is left of the row
 			spread(rest, [&](int k) { return row[ed + k]; });
-			spread(P.rg_len + 1, [&](int k) { return k < P.rg_len ? P.rg[k] : '\n'; });
+			if (nx == 0) { spread(P.rg_len + 1, [&](int k) { return k < P.rg_len ? P.rg[k] : '\n'; }); continue; }
+			// ---- the XA tag (src/bwamem.c:940 puts it behind RG / SA / pa): a lane per entry prints its numbers, the wave copies ----
+			spread(P.rg_len + 6, [&](int k) { return k < P.rg_len ? P.rg[k] : "\tXA:Z:"[k - P.rg_len]; });
+			const int ri = (bt << 6) + i;   // (wave-uniform: every lane reads the record's descriptor)
+			int x_len = 0, x_at = 0, x_nlen = 0;
+			if (lane < nx) {
+				const SamAln x = xa_aln(desc[ri], lane, reqs, hdr, pool, req_base[PE ? ri >> 1 : ri], P.l_pac, ann_off, l);
+				Sink T;
+				T.row = xa_rows + lane * XA_STAGE; T.len = 0; T.cap = XA_STAGE;
+				xa_numbers(T, x);
+				x_len = T.len; x_at = ann_name_off[x.rid]; x_nlen = ann_name_off[x.rid + 1] - x_at;
+			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			for (int j = 0; j < nx; ++j) {
+				const char *cn = ann_names + bcast(x_at, j);
+				spread(bcast(x_nlen, j), [&](int k) { return cn[k]; });
+				const uint8_t *xr = xa_rows + j * XA_STAGE;
+				spread(bcast(x_len, j), [&](int k) { return xr[k]; });
+			}
+			spread(1, [&](int) { return '\n'; });
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the staging slots are rewritten for the wave's next record with a tag
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		}
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the rows are rewritten by the wave's next batch
 		__builtin_amdgcn_wave_barrier();
@@ -289,7 +353,7 @@ size_t sam_arena_bytes(int n_reads, int max_len)
 }
 
 template <bool PE>
-static void launch_sam_emit_t(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+static void launch_sam_emit_t(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr,
                      const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                      uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
@@ -297,16 +361,16 @@ static void launch_sam_emit_t(void *stream, const SamParams &P, int n_reads, con
 {
 	if (n_reads <= 0) return;
 	const int n_batch = (n_reads + 63) >> 6;
-	int blocks = n_batch < 256 * 8 ? n_batch : 256 * 8;   // 16.6 KB of LDS per wave: nine waves per CU
+	int blocks = n_batch < 256 * 8 ? n_batch : 256 * 8;   // 17.7 KB of LDS per wave: nine waves per CU
 	if (grid_blocks > 0 && grid_blocks < blocks) blocks = grid_blocks;
-	hipLaunchKernelGGL(sam_emit_kernel<PE>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, P, n_reads, d_desc, d_req_base, d_hdr, d_pool, d_seq, d_off,
+	hipLaunchKernelGGL(sam_emit_kernel<PE>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, P, n_reads, d_desc, d_req_base, d_req, d_hdr, d_pool, d_seq, d_off,
 	                   d_len, d_qual, d_names, d_name_off, (const long long *)d_ann_off, d_ann_names, d_ann_name_off, d_arena,
 	                   (unsigned long long)arena_bytes, d_arena_used, d_out_off, d_out_len);
 }
 
-#define SAM_EMIT_ARGS stream, P, n_reads, d_desc, d_req_base, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_name_off, d_ann_off, d_ann_names, \
+#define SAM_EMIT_ARGS stream, P, n_reads, d_desc, d_req_base, d_req, d_hdr, d_pool, d_seq, d_off, d_len, d_qual, d_names, d_name_off, d_ann_off, d_ann_names, \
 	d_ann_name_off, d_arena, arena_bytes, d_arena_used, d_out_off, d_out_len, grid_blocks
-void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr,
                      const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                      const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                      uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
@@ -314,7 +378,7 @@ void launch_sam_emit(void *stream, const SamParams &P, int n_reads, const SamDes
 {
 	launch_sam_emit_t<true>(SAM_EMIT_ARGS);
 }
-void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnHdr *d_hdr,
+void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const SamDesc *d_desc, const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr,
                         const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off, const int *d_len, const uint8_t *d_qual,
                         const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                         uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,

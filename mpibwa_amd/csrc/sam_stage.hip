@@ -143,7 +143,8 @@ void Call::mcollect(Part &P)
 	const int nu = P.hi - P.lo, n_blk = (nu + 255) / 256;
 	std::vector<std::vector<MswReqH>> blk_req(n_blk);
 	std::vector<uint32_t> u_first(nu), u_cnt(nu);
-	// (dev_wave: the pairs pair_simple_kernel left for rescue, long lists or an end without a hit also get their tags, and are pair_wave_kernel's)
+	// (dev_wave: the pairs pair_simple_kernel left for rescue, long lists or an end without a hit also get their tags, and are pair_wave_kernel's;
+	// dev_xa: the ones it left for an XA tag too)
 	std::vector<std::vector<int16_t>> blk_tag(dev_wave ? n_blk : 0);
 	std::vector<std::vector<int>> blk_work(dev_wave ? n_blk : 0);   // (pair, first tag in blk_tag) ...
 	parallel_for(n_thr, n_blk, 1, [&](int blk) {
@@ -154,7 +155,7 @@ void Call::mcollect(Part &P)
 			const size_t before = rq.size();
 			if (!(pstat && pstat[i] == 1)) {
 				const bseq1_t *s = &seqs[i << 1];
-				const bool cand = dev_wave && (pstat[i] == 3 || pstat[i] == 7 || pstat[i] == 2) && !s[0].comment && !s[1].comment &&
+				const bool cand = dev_wave && (pstat[i] == 3 || pstat[i] == 7 || pstat[i] == 2 || (dev_xa && pstat[i] == 11)) && !s[0].comment && !s[1].comment &&
 				                  strcmp(s[0].name, s[1].name) == 0 && pair_wave_eligible(&regs[i << 1], PW_MAXREG);
 				if (cand) {
 					blk_work[blk].push_back(i); blk_work[blk].push_back((int)blk_tag[blk].size());
@@ -279,10 +280,46 @@ void Call::wave_launch(Part &P)
 	HIP_OK(hipMemcpyAsync(d_toff, ht, (size_t)(nw + 1) * 4, hipMemcpyHostToDevice, P.mst));
 	if (!P.w_tags.empty()) HIP_OK(hipMemcpyAsync(d_tags, hg, P.w_tags.size() * 2, hipMemcpyHostToDevice, P.mst));
 	HIP_OK(hipMemsetAsync(d_ws, 0, (size_t)nw, P.mst));
+	AlnReq *d_xr = nullptr;
+	uint8_t *d_xc = nullptr, *hx = nullptr;
+	if (dev_xa) {   // the XA entries' requests, PW_XA_CAP per (item, end), and their counts
+		d_xr = (AlnReq *)W.wxreq[s].ensure(roomy((size_t)2 * nw * PW_XA_CAP * sizeof(AlnReq)));
+		d_xc = (uint8_t *)W.wxcnt[s].ensure(roomy((size_t)2 * nw + 64));
+		hx = (uint8_t *)W.h_wxcnt[s].ensure(roomy((size_t)2 * nw + 64));
+		HIP_OK(hipMemsetAsync(d_xc, 0, (size_t)2 * nw, P.mst));
+	}
 	launch_pair_wave(P.mst, wave_pp, nw, d_work, d_lists, d_loff, D.d_len, d_req, d_res, d_mf, d_tags, d_toff, D.d_ann_off, d_wave_tab, d_wave_tab + wave_n_tab,
-	                 d_ws, d_rq, d_ds);
+	                 d_ws, d_rq, d_ds, d_xr, d_xc);
 	HIP_OK(hipMemcpyAsync(hs, d_ws, (size_t)nw, hipMemcpyDeviceToHost, P.mst));
-	P.wstatus = hs;
+	if (dev_xa) HIP_OK(hipMemcpyAsync(hx, d_xc, (size_t)2 * nw, hipMemcpyDeviceToHost, P.mst));
+	P.wstatus = hs; P.wxcnt = hx;
+}
+
+// The pairs pair_wave_kernel decided with an XA tag carry 3 to 2 + 2 PW_XA_CAP requests each, so they never ride in the part's device
+// job (two requests per pair, in place): the host lays out their request bases (no request for any other unit of the part), a kernel
+// moves requests and descriptors there, and one more CIGAR-and-SAM job runs over the part for these pairs alone.
+void Call::xa_records(Part &P)
+{
+	if (P.n_xa_dec == 0) return;
+	const int s = P.slot, nw = (int)P.work.size(), nu = P.hi - P.lo;
+	hipStream_t jst = C.d_streams[s];
+	int *dst = (int *)W.h_wxdst[s].ensure(roomy((size_t)nw * 4 + 64));
+	P.xa_base.assign(nu + 1, 0);
+	for (int t = 0; t < nw; ++t)
+		if (P.wstatus[t] == PW_DECIDED_XA) P.xa_base[P.work[t] - P.lo + 1] = 2 + std::min<int>(P.wxcnt[2 * t], PW_XA_CAP) + std::min<int>(P.wxcnt[2 * t + 1], PW_XA_CAP);
+	for (int k = 0; k < nu; ++k) P.xa_base[k + 1] += P.xa_base[k];
+	for (int t = 0; t < nw; ++t) dst[t] = P.wstatus[t] == PW_DECIDED_XA ? (int)P.xa_base[P.work[t] - P.lo] : -1;
+	const size_t n_req = P.xa_base[nu];
+	int *d_dst = (int *)W.wxdst[s].ensure(roomy((size_t)nw * 4));
+	AlnReq *d_rq = (AlnReq *)W.xa_req[s].ensure(roomy(n_req * sizeof(AlnReq)));
+	SamDesc *d_ds = (SamDesc *)W.xa_desc.ensure((size_t)n * sizeof(SamDesc));
+	HIP_OK(hipMemcpyAsync(d_dst, dst, (size_t)nw * 4, hipMemcpyHostToDevice, jst));
+	launch_pair_wave_xa_scatter(jst, nw, (const int *)W.wwork[s].p, d_dst, (const AlnReq *)W.wreq[s].p, (const SamDesc *)W.wdesc[s].p, (const AlnReq *)W.wxreq[s].p,
+	                            (const uint8_t *)W.wxcnt[s].p, d_rq, d_ds, 2 * P.lo, 2 * nu);
+	HIP_OK(hipGetLastError());
+	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
+	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
+	job_launch(P.xa, W.xa_job[s], jst, P, d_rq, n_req, P.xa_base.data(), true, nullptr, d_ds);
 }
 
 // The pairs pair_wave_kernel decided become units of the device: their requests and descriptors go into the chunk-wide arrays of the
@@ -311,12 +348,18 @@ void Call::mfinish(Part &P)
 	HIP_OK(hipGetLastError());
 	if (P.msw_launched) STAT.k_msw_ms += P.mev.ms();
 	STAT.n_msw += P.n_mreq;
+	uint64_t n_plain_from_xa = 0;
 	for (size_t t = 0; t < P.work.size(); ++t) {   // pair_wave_kernel's decisions: its pairs are the device's from here on
 		const int i = P.work[t];
-		if (P.wstatus[t] == 1) { pstat_w[i] = 1; wave_dec[i] = 1; ++P.n_wave_dec; }
+		// (pair_simple_kernel's XA test is coarse — any close secondary hit under any primary one —, so some of the pairs it left for XA
+		// come back plain: more than max_XA_hits entries, or entries under a hit that is not the chosen one)
+		if (P.wstatus[t] == 1) { if (pstat_w[i] == PW_HOST_XA) ++n_plain_from_xa; pstat_w[i] = 1; wave_dec[i] = 1; ++P.n_wave_dec; }
+		else if (P.wstatus[t] == PW_DECIDED_XA && dev_xa) { pstat_w[i] = PW_DECIDED_XA; ++P.n_xa_dec; }
 		else if (P.wstatus[t]) pstat_w[i] = P.wstatus[t];   // (why not: for the statistics line)
 	}
-	n_wave += (uint64_t)P.n_wave_dec;
+	n_wave += (uint64_t)P.n_wave_dec - n_plain_from_xa;
+	n_xa_plain += n_plain_from_xa;
+	n_xa_pairs += (uint64_t)P.n_xa_dec + n_plain_from_xa;
 	msw_ms += now_ms() - ta;
 }
 
@@ -338,7 +381,7 @@ void Call::collect(Part &P, int round)
 		unsigned long long tsc_plan_blk = 0, tsc_emitc_blk = 0;
 		for (int i = lo; i < hi; ++i) {
 			const int k = i - P.lo;
-			if (pstat && pstat[i] == 1) continue;   // decided on the device
+			if (pstat && (pstat[i] == 1 || pstat[i] == PW_DECIDED_XA)) continue;   // decided on the device
 			const bool has_msw = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
 			const bool waits = has_msw || (dev_wave && wave_cand[i]);            // ... or pair_wave_kernel's word on whose pair it is
 			if (waits != (round == 1)) continue;
@@ -455,7 +498,7 @@ void Call::job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units)
 	HIP_OK(hipGetLastError());
 	STAT.k_aln_ms += J.ev.ms();
 	STAT.n_aln += J.n_req;
-	if (policy == FETCH_ALWAYS) fetch_results(J);
+	if (policy == FETCH_ALWAYS) fetch_results(J);   // (FETCH_RECORDS: the records alone; the host redoes a unit handed back from scratch)
 	if (J.sam_launched) fetch_records(J);
 	if (policy == FETCH_IF_HANDED_BACK) {
 		const int ends = pe ? 2 : 1;
@@ -532,9 +575,10 @@ void Call::replay(Part &P, int which)
 		unsigned long long n_dev = 0, tsc = 0;
 		for (int k = k_lo; k < k_hi; ++k) {
 			const int i = P.lo + k, r = ends * i;   // the unit, its first read
-			const bool dev_k = pstat && pstat[i] == 1;
-			const bool own_k = dev_k && P.wave.launched && wave_dec[i];   // pair_wave_kernel's pair with the job of its own
-			const Job &J = own_k ? P.wave : dev_k ? P.dev : P.host;
+			const bool xa_k = pstat && pstat[i] == PW_DECIDED_XA;   // pair_wave_kernel's pair with an XA tag: the job of those
+			const bool dev_k = xa_k || (pstat && pstat[i] == 1);
+			const bool own_k = xa_k || (dev_k && P.wave.launched && wave_dec[i]);   // pair_wave_kernel's pair with the job of its own
+			const Job &J = xa_k ? P.xa : own_k ? P.wave : dev_k ? P.dev : P.host;
 			bool written = J.solen != nullptr;   // every record of the unit was written by sam_emit_kernel
 			for (int e = 0; e < ends && written; ++e) written = J.solen[ends * k + e] >= 0;
 			const bool early = dev_k && written && !own_k;   // pass 0's units
@@ -552,10 +596,12 @@ void Call::replay(Part &P, int which)
 			if (dev_k) { ctx.hdr = J.hdr; ctx.pool = J.pool; ctx.cursor = (size_t)ends * k; }
 			if (pe) {
 				MswCtx mc;   // (pair_wave_kernel's pair: the rescue alignments are there)
-				const bool has_msw = dev_k && dev_wave && wave_dec[i] && P.msw_launched && P.mbase[k + 1] != P.mbase[k];
+				const bool has_msw = dev_k && dev_wave && (wave_dec[i] || xa_k) && P.msw_launched && P.mbase[k + 1] != P.mbase[k];
 				if (has_msw) { mc.req = P.mreq + P.mbase[k]; mc.res = P.mres + P.mbase[k]; mc.n = (int)(P.mbase[k + 1] - P.mbase[k]); }
 				if (dev_k) sam_pe_plan(opt, bns, pac, pes, (uint64_t)((n_processed >> 1) + i), &seqs[r], &regs[r], plans[i], has_msw ? &mc : nullptr, r);
-				sam_pe_emit(opt, bns, pac, pes, &seqs[r], &regs[r], plans[i], gpu_aln ? &ctx : nullptr, r);
+				// (an XA pair handed back: the host lists the XA entries of every primary hit, in another order than the device's
+				// requests, so it aligns the few such pairs itself)
+				sam_pe_emit(opt, bns, pac, pes, &seqs[r], &regs[r], plans[i], gpu_aln && !xa_k ? &ctx : nullptr, r);
 			} else {
 				if (dev_k) mark_primary_se(opt, regs[i], n_processed + i);
 				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln ? &ctx : nullptr, i);
@@ -597,6 +643,8 @@ void Call::sam_stage()
 	// pair_wave_kernel: wherever pair_simple_kernel ran and mate rescue runs on the device.  MPIBWA_HOST_RESCUE=1 turns it off.
 	dev_wave = pe && pstat_w && gpu_msw && getenv("MPIBWA_HOST_RESCUE") == nullptr;
 	if (dev_wave) { wave_cand.assign(n_units, 0); wave_dec.assign(n_units, 0); }
+	// its XA listing: wherever it runs and the tags fit the kernel's side array.  MPIBWA_HOST_XA=1 turns it off.
+	dev_xa = dev_wave && gpu_sam && wave_pp.max_XA_hits <= PW_XA_CAP && getenv("MPIBWA_HOST_XA") == nullptr;
 	for (int p = 0; p < n_parts; ++p) {   // (slot 0: the whole chunk or its first half)
 		parts[p].slot = p;
 		parts[p].lo = p ? n_units / 2 : 0;
@@ -611,6 +659,7 @@ void Call::sam_stage()
 		collect(P, 0); mfinish(P); collect(P, 1);
 		// (the wave's pairs ride in the part's device job when it has not gone out yet, and get a job of their own behind it otherwise)
 		if (dev_wave) wave_records(P, !dev_late);
+		if (dev_xa) xa_records(P);
 		if (dev_late) launch_dev(P);
 		launch(P);
 	}
@@ -620,6 +669,7 @@ void Call::sam_stage()
 		finish(P);
 		if (dev_last) { finish_dev(P); replay(P, 0); }
 		job_fetch(P.wave, P, FETCH_IF_HANDED_BACK, true);
+		job_fetch(P.xa, P, FETCH_RECORDS);
 		if (n_parts == 1) hprof_report("decisions + request lists");
 		replay(P, 1);
 	}
@@ -634,9 +684,9 @@ void Call::report_decisions()
 {
 	if (!pstat && !se_codes) return;
 	const uint8_t *codes = pstat ? pstat : se_codes;
-	uint64_t c[16] = {0};
-	for (int k = 0; k < n_units; ++k) ++c[codes[k] & 15];
-	if (pe) { STAT.n_pair_dev = c[1] - n_wave; STAT.n_pair_wave_dev = n_wave; }
+	uint64_t c[32] = {0};
+	for (int k = 0; k < n_units; ++k) ++c[codes[k] & 31];
+	if (pe) { STAT.n_pair_dev = c[1] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs; }
 	else {
 		STAT.n_se_dev = c[1];
 		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu\n",
@@ -644,10 +694,10 @@ void Call::report_decisions()
 		                      (unsigned long long)c[SE_HOST_PATCH], (unsigned long long)c[SE_HOST_LENGTH], (unsigned long long)c[SE_HOST_ALT],
 		                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA]);
 	}
-	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
+	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them and %llu with an XA tag, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
 	                      n_units, (unsigned long long)c[1], (unsigned long long)c[2], PR_MAXREG, (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[6],
 	                      (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11],
-	                      (unsigned long long)n_wave, (unsigned long long)c[PW_HOST_NO_RESULT], PW_MAXREG, (unsigned long long)c[PW_HOST_FULL], (unsigned long long)c[PW_HOST_TIE]);
+	                      (unsigned long long)n_wave, (unsigned long long)n_xa_pairs, (unsigned long long)c[PW_HOST_NO_RESULT], PW_MAXREG, (unsigned long long)c[PW_HOST_FULL], (unsigned long long)c[PW_HOST_TIE]);
 }
 
 } // namespace mbw
