@@ -261,6 +261,14 @@ double mi355x_sa_dense_info(size_t *bytes);
 int mi355x_extend_batch(const mem_opt_t *opt, int n, const uint8_t *q, const int64_t *qoff,
                         const uint8_t *t, const int64_t *toff, const int *w, const int *h0,
                         const int *end_bonus, int *out6, double *kernel_ms, uint64_t *cells);
+/* The same through the row loop the chain-to-region kernel runs.  Per job: early[i] != 0 stops the rows as soon as nothing
+ * mem_chain2aln reads can change, given the clipping penalty clip[i] — then score, qle, tle, max_off and the local / global
+ * decision (gscore <= 0 || gscore <= score - clip) are the reference's, gscore and gtle too when the decision is "global";
+ * early[i] == 0: all six outputs are the reference's.  cells[i]: DP cells computed for job i. */
+int mi355x_extend_batch2(const mem_opt_t *opt, int n, const uint8_t *q, const int64_t *qoff,
+                         const uint8_t *t, const int64_t *toff, const int *w, const int *h0,
+                         const int *end_bonus, const int *early, const int *clip, int *out6,
+                         uint64_t *cells, double *kernel_ms);
 
 /* Chaining stage (mem_chain + mem_chain_flt, src/bwamem.c:251-385) for n_reads reads given by their seeds
  * (read r owns seeds seed_off[r] .. seed_off[r+1]: rbeg[], and qbeg/len interleaved in qbeg_len[]), computed by

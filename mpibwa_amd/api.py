@@ -17,7 +17,7 @@ EXPORTS = [
     "mem_process_seqs", "mem_opt_init", "bwa_fill_scmat", "bwa_idx_load_from_disk", "bwa_mem2idx", "bwa_idx_destroy",
     "mi355x_index_upload", "mi355x_index_alloc", "mi355x_index_buffers", "mi355x_index_d2d", "mi355x_index_commit",
     "mi355x_finalize", "mi355x_index_build", "mi355x_index_build_gpu",
-    "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
+    "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_extend_batch2", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
     "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap",
@@ -77,6 +77,7 @@ def load_library(build_if_missing=True):
     sig("mi355x_sa_batch2", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, P(C.c_double), C.c_int])
     sig("mi355x_sa_dense_info", C.c_double, [P(C.c_size_t)])
     sig("mi355x_extend_batch", C.c_int, [P(abi.mem_opt_t), C.c_int] + [C.c_void_p] * 8 + [P(C.c_double), P(C.c_uint64)])
+    sig("mi355x_extend_batch2", C.c_int, [P(abi.mem_opt_t), C.c_int] + [C.c_void_p] * 11 + [P(C.c_double)])
     sig("mi355x_chain_batch", C.c_int64, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p])
     sig("mi355x_c2a_batch", C.c_int64, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 3 +
         [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -581,3 +582,26 @@ class Engine:
                                      w.ctypes.data, h0.ctypes.data, eb.ctypes.data, out.ctypes.data, C.byref(ms),
                                      C.byref(cells))
         return out, ms.value, cells.value
+
+    def extend2(self, opt, qs, ts, w, h0, end_bonus, early, clip):
+        """extend() through the row loop of the chain-to-region kernel: `early` (0 / 1) and `clip` per job (or one value for all);
+        returns the six outputs per job, the kernel time and the cell count per job."""
+        n = len(qs)
+        qoff = np.zeros(n + 1, dtype=np.int64)
+        qoff[1:] = np.cumsum([len(s) for s in qs])
+        toff = np.zeros(n + 1, dtype=np.int64)
+        toff[1:] = np.cumsum([len(s) for s in ts])
+        qf = np.concatenate(qs).astype(np.uint8)
+        tf = np.concatenate(ts).astype(np.uint8)
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        h0 = np.ascontiguousarray(h0, dtype=np.int32)
+        eb = np.ascontiguousarray(end_bonus, dtype=np.int32)
+        early = np.ascontiguousarray(np.broadcast_to(np.asarray(early, dtype=np.int32), (n,)))
+        clip = np.ascontiguousarray(np.broadcast_to(np.asarray(clip, dtype=np.int32), (n,)))
+        out = np.zeros((n, 6), dtype=np.int32)
+        cells = np.zeros(n, dtype=np.uint64)
+        ms = C.c_double(0)
+        self.lib.mi355x_extend_batch2(opt, n, qf.ctypes.data, qoff.ctypes.data, tf.ctypes.data, toff.ctypes.data,
+                                      w.ctypes.data, h0.ctypes.data, eb.ctypes.data, early.ctypes.data, clip.ctypes.data,
+                                      out.ctypes.data, cells.ctypes.data, C.byref(ms))
+        return out, ms.value, cells

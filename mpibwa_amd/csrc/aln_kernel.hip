@@ -421,9 +421,7 @@ void launch_aln(void *stream, const AlnParams &P, const ExtParams &ep, int n_req
                 unsigned long long *d_counters, size_t pool_bytes, int max_len, int tcap, int *d_lists, bool wide_only)
 {
 	if (n_req <= 0) return;
-	WxParams X;
-	for (int i = 0; i < 25; ++i) X.mat[i] = ep.mat[i];
-	X.o_del = ep.o_del; X.e_del = ep.e_del; X.o_ins = ep.o_ins; X.e_ins = ep.e_ins; X.zdrop = ep.zdrop;
+	const WxParams X = wx_params(ep);
 	const size_t shmem = aln_lds_per_block(max_len, tcap);
 	const size_t shmem_small = shmem - (size_t)(aln_zcap(max_len) - aln_zcap_small(max_len)) * ALN_WAVES;
 	const size_t shmem_fast = ((size_t)2 * ((max_len + 3) & ~3) + ALN_MDCAP + 16) * ALN_WAVES;

@@ -52,6 +52,15 @@ __device__ __forceinline__ i64 uni64(i64 v)
 	return (i64)((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32 | (unsigned)__builtin_amdgcn_readfirstlane((int)u));
 }
 
+// The bases an extension walks over, in its own direction (dir = -1: the left flank, both sequences reversed).  The left and the
+// right extension share their types, so the row loop is compiled once per kind of target, not once per call site.
+struct QBase { const uint8_t *p; int dir; __device__ __forceinline__ int operator()(int j) const { return p[dir * j]; } };
+struct WinBase { const uint8_t *p; int dir; __device__ __forceinline__ int operator()(int t) const { return p[dir * t]; } };   // the chain's window in LDS
+struct PacBase {
+	const uint8_t *pac; i64 l_pac, p0; int dir;
+	__device__ __forceinline__ int operator()(int t) const { return ref_base(pac, l_pac, p0 + dir * t); }
+};
+
 #define C2A_WAVES 1
 #define SRT_MARK 0xFFFFFFFFu
 
@@ -147,10 +156,8 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 	}
 	int nav = 0;
-	unsigned long long cells = 0, n_ext = 0, n_diff = 0, n_closed = 0;
+	unsigned int cells = 0, n_ext = 0, n_diff = 0, n_closed = 0;   // (of one read or unit: they fit 32 bits)
 	const i64 l_pac = P.l_pac;
-	int max_sc = 1;   // largest entry of the scoring matrix: what one more column can add at most
-	for (int t = 0; t < 25; ++t) max_sc = X.mat[t] > max_sc ? X.mat[t] : max_sc;
 
 	// ---- extensions that need no DP ----
 	// When the flank matches the reference along the diagonal with at most ONE mismatch (no ambiguous base, the window at least
@@ -164,11 +171,9 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 	// (a + b <= zdrop).  The flank right behind a seed nearly always starts with the mismatch that ended the seed, so a read with
 	// one or two sequencing errors is extended without any DP.  tests/csrc/ungapped_extend_check.c restates the rule on the CPU
 	// against the oracle's ksw_extend2 (tests/test_ungapped_extend.py); MPIBWA_C2A_EARLY=2 checks every use in the kernel.
-	const int sc_a = X.mat[0], sc_b = -X.mat[1];
-	bool plain = sc_a > 0 && sc_b > 0;
-	for (int i = 0; i < 4; ++i)
-		for (int j = 0; j < 4; ++j) plain = plain && X.mat[i * 5 + j] == (i == j ? sc_a : -sc_b);
-	const int g1 = (X.o_del < X.o_ins ? X.o_del : X.o_ins) + (X.e_del < X.e_ins ? X.e_del : X.e_ins);
+	// (X.plain: the matrix is {a on the diagonal, -b off it}; X.g1 = min(o_del, o_ins) + min(e_del, e_ins): worked out once per launch)
+	const int sc_a = X.sc_a, sc_b = X.sc_b, g1 = X.g1;
+	const bool plain = X.plain != 0;
 	auto ungapped = [&](int qlen, int tlen, auto tf, int h0, WxResult &r) -> bool {
 		if (!plain || tlen < qlen || qlen <= 0) return false;
 		int mm = 0, p = -1;
@@ -199,23 +204,26 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 
 	// one ksw_extend2.  P.early: 1 = no DP when the closed form above applies, and row loops that stop as soon as nothing the code
 	// below reads can change (wave_ext.cuh); 0 = every row the reference computes; 2 = both, and count the extensions whose outputs differ
-	auto extend = [&](int qlen, auto qf, int tlen, auto tf, int wc, int h0, int clip) -> WxResult {
-		++n_ext;
+	auto extend = [&](int qlen, auto qf, int tlen, auto tf, int wc, int h0, int clip) __attribute__((always_inline)) -> WxResult {
 		for (int j = lane; j < qlen; j += 64) L.Qs[j] = (uint8_t)qf(j);
 		__builtin_amdgcn_wave_barrier();
-		if (P.early == 0) return wave_extend<false>(qlen, tlen, tf, X, wc, h0, L, cells, max_sc);
 		WxResult r;
-		const bool closed = ungapped(qlen, tlen, tf, h0, r);
-		if (closed) ++n_closed;
-		else r = wave_extend<true>(qlen, tlen, tf, X, wc, h0, L, cells, max_sc, clip);
-		if (P.early == 2) {
-			unsigned long long c2 = 0;
-			const WxResult f = wave_extend<false>(qlen, tlen, tf, X, wc, h0, L, c2, max_sc);
-			const bool loc_r = r.gscore <= 0 || r.gscore <= r.score - clip, loc_f = f.gscore <= 0 || f.gscore <= f.score - clip;
-			bool same = f.score == r.score && f.qle == r.qle && f.tle == r.tle && f.max_off == r.max_off && loc_r == loc_f;
-			if (same && (!loc_f || closed)) same = f.gtle == r.gtle && f.gscore == r.gscore;   // the closed form claims all six
-			if (!same) ++n_diff;
+		r.cells = 0;
+		bool closed = false, differ = false;
+		if (P.early == 0) r = wave_extend<false>(qlen, tlen, tf, X, wc, h0, L);
+		else {
+			closed = ungapped(qlen, tlen, tf, h0, r);
+			if (!closed) r = wave_extend<true>(qlen, tlen, tf, X, wc, h0, L, clip);
+			if (P.early == 2) {
+				const WxResult f = wave_extend<false>(qlen, tlen, tf, X, wc, h0, L);
+				const bool loc_r = r.gscore <= 0 || r.gscore <= r.score - clip, loc_f = f.gscore <= 0 || f.gscore <= f.score - clip;
+				bool same = f.score == r.score && f.qle == r.qle && f.tle == r.tle && f.max_off == r.max_off && loc_r == loc_f;
+				if (same && (!loc_f || closed)) same = f.gtle == r.gtle && f.gscore == r.gscore;   // the closed form claims all six
+				differ = !same;
+			}
 		}
+		// (the statistics in one place, without a branch: counted at the end of each path they end up in memory)
+		++n_ext; cells += r.cells; n_closed += closed; n_diff += differ;
 		return r;
 	};
 
@@ -252,7 +260,6 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 			__builtin_amdgcn_wave_barrier();
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		}
-		auto TB = [&](i64 pos) -> int { return st_w ? (int)winl[pos - rmax0] : ref_base(pac, l_pac, pos); };
 
 		for (int k = n - 1; k >= 0; --k) {
 			DevSeed s = SD(uni((int)ORD(k)));
@@ -316,7 +323,10 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 					int prev = a.score;
 					aw0 = P.w << i;
 					int wc = aw0 < bound5[qlen] ? aw0 : bound5[qlen];
-					r = extend(qlen, [&](int j) { return q[s.qbeg - 1 - j]; }, tlen, [&](int t) { return TB(s.rbeg - 1 - t); }, wc, s.len * P.a, P.pen_clip5);
+					const QBase qf{q + s.qbeg - 1, -1};
+					// (one path per extension: the window's bases in LDS, or — a window beyond the staging buffer — the pac itself)
+					r = st_w ? extend(qlen, qf, tlen, WinBase{winl + (int)tlen64 - 1, -1}, wc, s.len * P.a, P.pen_clip5)
+					         : extend(qlen, qf, tlen, PacBase{pac, l_pac, s.rbeg - 1, -1}, wc, s.len * P.a, P.pen_clip5);
 					a.score = r.score;
 					if (a.score == prev || r.max_off < (aw0 >> 1) + (aw0 >> 2)) break;
 				}
@@ -335,7 +345,9 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 					int prev = a.score;
 					aw1 = P.w << i;
 					int wc = aw1 < bound3[qlen] ? aw1 : bound3[qlen];
-					r = extend(qlen, [&](int j) { return q[qe + j]; }, tlen, [&](int t) { return TB(s.rbeg + s.len + t); }, wc, sc0, P.pen_clip3);
+					const QBase qf{q + qe, 1};
+					r = st_w ? extend(qlen, qf, tlen, WinBase{winl + (int)re, 1}, wc, sc0, P.pen_clip3)
+					         : extend(qlen, qf, tlen, PacBase{pac, l_pac, s.rbeg + s.len, 1}, wc, sc0, P.pen_clip3);
 					a.score = r.score;
 					if (a.score == prev || r.max_off < (aw1 >> 1) + (aw1 >> 2)) break;
 				}
@@ -366,10 +378,10 @@ c2a_kernel(C2aParams P, WxParams X, int n_reads, const uint8_t *__restrict__ seq
 		// address atomics), and two per read made that queue, not the DP, the length of this kernel (222 000 reads x 2 = 4.9 of
 		// 5.4 ms per launch, DP switched off or not): the counters are spread over C2A_STAT_SLOTS cache lines, the host adds them up
 		unsigned long long *st = counters + (size_t)(blockIdx.x % C2A_STAT_SLOTS) * 8;
-		if (cells) atomicAdd(&st[0], cells);
-		if (n_ext) atomicAdd(&st[1], n_ext);
-		if (n_closed) atomicAdd(&st[2], n_closed);
-		if (n_diff) atomicAdd(&st[3], n_diff);
+		if (cells) atomicAdd(&st[0], (unsigned long long)cells);
+		if (n_ext) atomicAdd(&st[1], (unsigned long long)n_ext);
+		if (n_closed) atomicAdd(&st[2], (unsigned long long)n_closed);
+		if (n_diff) atomicAdd(&st[3], (unsigned long long)n_diff);
 	}
 }
 
@@ -380,9 +392,7 @@ void launch_c2a(void *stream, const C2aParams &P, const ExtParams &ep, int n_rea
 {
 	C2aUnits U;
 	if (units) U = *units;
-	WxParams X;
-	for (int i = 0; i < 25; ++i) X.mat[i] = ep.mat[i];
-	X.o_del = ep.o_del; X.e_del = ep.e_del; X.o_ins = ep.o_ins; X.e_ins = ep.e_ins; X.zdrop = ep.zdrop;
+	const WxParams X = wx_params(ep);
 	size_t shmem = (size_t)C2A_WAVES * c2a_lds_bytes(max_len);
 	if (shmem > 64 * 1024 && hipFuncSetAttribute((const void *)c2a_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess)
 		die("c2a_kernel: cannot reserve %zu bytes of LDS", shmem);

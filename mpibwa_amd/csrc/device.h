@@ -122,6 +122,11 @@ struct ExtParams {
 void launch_extend(void *stream, const ExtParams &ep, int n, const uint8_t *d_q, const int64_t *d_qoff,
                    const uint8_t *d_t, const int64_t *d_toff, const int *d_w, const int *d_h0, const int *d_eb,
                    int *d_out6, unsigned long long *d_cells, int max_qlen);
+// per job: early != 0 = the row loop that stops as soon as nothing the caller of c2a_kernel reads can change, with the job's clipping
+// penalty; d_cells: one count per job
+void launch_extend2(void *stream, const ExtParams &ep, int n, const uint8_t *d_q, const int64_t *d_qoff,
+                    const uint8_t *d_t, const int64_t *d_toff, const int *d_w, const int *d_h0, const int *d_early, const int *d_clip,
+                    int *d_out6, unsigned long long *d_cells, int max_qlen);
 
 // ---- chain -> region kernel (c2a_kernel.hip) ----
 struct DevSeed { int64_t rbeg; int32_t qbeg, len; };           // 16 B

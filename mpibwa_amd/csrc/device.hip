@@ -954,6 +954,52 @@ extern "C" int mi355x_extend_batch(const mem_opt_t *opt, int n, const uint8_t *q
 	return 0;
 }
 
+extern "C" int mi355x_extend_batch2(const mem_opt_t *opt, int n, const uint8_t *q, const int64_t *qoff, const uint8_t *t,
+                                    const int64_t *toff, const int *w, const int *h0, const int *end_bonus, const int *early,
+                                    const int *clip, int *out6, uint64_t *cells, double *kernel_ms)
+{
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
+	if (n <= 0) return 0;
+	hipStream_t st = 0;
+	std::vector<int> wc(n);
+	int max_qlen = 0;
+	for (int i = 0; i < n; ++i) {
+		int ql = (int)(qoff[i + 1] - qoff[i]);
+		max_qlen = std::max(max_qlen, ql);
+		wc[i] = clamp_band(opt, ql, w[i], end_bonus[i]);
+	}
+	uint8_t *d_q, *d_t; int64_t *d_qo, *d_to; int *d_w, *d_h0, *d_early, *d_clip, *d_out; unsigned long long *d_cells;
+	HIP_OK(hipMalloc(&d_q, qoff[n] + 16)); HIP_OK(hipMalloc(&d_t, toff[n] + 16));
+	HIP_OK(hipMalloc(&d_qo, (size_t)(n + 1) * 8)); HIP_OK(hipMalloc(&d_to, (size_t)(n + 1) * 8));
+	HIP_OK(hipMalloc(&d_w, (size_t)n * 4)); HIP_OK(hipMalloc(&d_h0, (size_t)n * 4));
+	HIP_OK(hipMalloc(&d_early, (size_t)n * 4)); HIP_OK(hipMalloc(&d_clip, (size_t)n * 4));
+	HIP_OK(hipMalloc(&d_out, (size_t)n * 24)); HIP_OK(hipMalloc(&d_cells, (size_t)n * 8));
+	HIP_OK(hipMemcpy(d_q, q, qoff[n], hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_t, t, toff[n], hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_qo, qoff, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_to, toff, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_w, wc.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_h0, h0, (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_early, early, (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemcpy(d_clip, clip, (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_OK(hipMemset(d_cells, 0, (size_t)n * 8));
+	ExtParams ep;
+	memcpy(ep.mat, opt->mat, 25);
+	ep.o_del = opt->o_del; ep.e_del = opt->e_del; ep.o_ins = opt->o_ins; ep.e_ins = opt->e_ins; ep.zdrop = opt->zdrop;
+	Timer tm;
+	tm.start(st);
+	launch_extend2(st, ep, n, d_q, d_qo, d_t, d_to, d_w, d_h0, d_early, d_clip, d_out, d_cells, max_qlen);
+	double ms = tm.stop(st);
+	HIP_OK(hipGetLastError());
+	HIP_OK(hipMemcpy(cells, d_cells, (size_t)n * 8, hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(out6, d_out, (size_t)n * 24, hipMemcpyDeviceToHost));
+	(void)hipFree(d_q); (void)hipFree(d_t); (void)hipFree(d_qo); (void)hipFree(d_to); (void)hipFree(d_w);
+	(void)hipFree(d_h0); (void)hipFree(d_early); (void)hipFree(d_clip); (void)hipFree(d_out); (void)hipFree(d_cells);
+	if (kernel_ms) *kernel_ms = ms;
+	return 0;
+}
+
 namespace mbw {
 MswParams msw_params(const mem_opt_t *opt, int64_t l_pac)
 {
