@@ -17,15 +17,10 @@
 // which is the order the serial walk would have produced them in (the sorts that follow are unstable: the order is visible).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include "hip_util.h"
 #include "device.h"
 
 namespace mbw {
-
-#define HIP_OK(call)                                                                                             \
-	do {                                                                                                         \
-		hipError_t e_ = (call);                                                                                  \
-		if (e_ != hipSuccess) die("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-	} while (0)
 
 namespace {
 

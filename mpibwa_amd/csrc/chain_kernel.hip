@@ -26,15 +26,10 @@
 #include <mutex>
 #include <utility>
 #include <vector>
+#include "hip_util.h"
 #include "device.h"
 
 namespace mbw {
-
-#define HIP_OK(call)                                                                                             \
-	do {                                                                                                         \
-		hipError_t e_ = (call);                                                                                  \
-		if (e_ != hipSuccess) die("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-	} while (0)
 
 namespace {
 

@@ -1,4 +1,4 @@
-// device.h — host-visible interface of the HIP side (device.hip, fm_kernels.hip, ext_kernels.hip)
+// device.h — host-visible interface of the HIP side (device.hip, stage_entries.hip and the kernel files)
 #ifndef MBW_DEVICE_H
 #define MBW_DEVICE_H
 #include "internal.h"
@@ -84,6 +84,7 @@ struct DevBuf {
 struct PinBuf {
 	void *p = nullptr; size_t cap = 0;
 	void *ensure(size_t bytes);
+	void release();
 };
 // pipeline.hip: called when a device allocation has failed; true = something was freed or a call has ended: try again
 bool device_memory_pressure(size_t wanted);
@@ -119,6 +120,7 @@ struct ExtParams {
 	int8_t mat[25];
 	int o_del, e_del, o_ins, e_ins, zdrop;
 };
+ExtParams ext_params(const mem_opt_t *opt);
 void launch_extend(void *stream, const ExtParams &ep, int n, const uint8_t *d_q, const int64_t *d_qoff,
                    const uint8_t *d_t, const int64_t *d_toff, const int *d_w, const int *d_h0, const int *d_eb,
                    int *d_out6, unsigned long long *d_cells, int max_qlen);
@@ -162,6 +164,11 @@ struct C2aUnits {
 struct C2aGroupBufs {
 	PinBuf h_heavy, h_hoff, h_nunits;
 	DevBuf heavy, hoff, scratch, clist, ustart, unit_rd, unit_av, nunits, c_rabs, c_rcnt;
+	void release()   // every member above
+	{
+		for (PinBuf *b : {&h_heavy, &h_hoff, &h_nunits}) b->release();
+		for (DevBuf *b : {&heavy, &hoff, &scratch, &clist, &ustart, &unit_rd, &unit_av, &nunits, &c_rabs, &c_rcnt}) b->release();
+	}
 };
 // The units of the reads with more than heavy_t chains (chain_cnt: host copy of d_chain_cnt; n_chain_slots: size of the chain array):
 // launch_c2a_groups on `stream`, then one round trip for the number of units, which sizes launch_c2a's grid.  With units, d_nregs
@@ -252,7 +259,7 @@ SamParams sam_params(int64_t l_pac, bool has_qual);   // + the read group, bwa_r
 void contig_names(const bntseq_t *bns, std::vector<char> &names, std::vector<int> &name_off);
 size_t sam_arena_bytes(int n_reads, int max_len);   // the arena the pipeline gives n_reads records of reads of up to max_len bases
 // One CIGAR-and-SAM job: aln_kernel over n_req requests, then sam_emit_kernel over the records of n_reads reads, queued on one stream.
-// The SAM stage (sam_stage.hip: the host's units and the units decided on the device) and the stage entries (device.hip: sam_batch)
+// The SAM stage (sam_stage.hip: the host's units and the units decided on the device) and the stage entries (stage_entries.hip: sam_batch)
 // all queue it through queue_aln_sam().
 struct ChunkDev {                // what is resident of the chunk: packed reads, qualities, names, the contig table, the CIGAR gap table
 	const uint8_t *d_seq = nullptr; const int64_t *d_off = nullptr; const int *d_len = nullptr; int max_len = 0;

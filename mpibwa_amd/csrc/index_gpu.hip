@@ -24,18 +24,13 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "hip_util.h"
 #include "internal.h"
 
 namespace mbw {
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
-
-#define HIP_OK(call)                                                                                             \
-	do {                                                                                                         \
-		hipError_t e_ = (call);                                                                                  \
-		if (e_ != hipSuccess) die("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-	} while (0)
 
 #define KMER 29
 

@@ -17,15 +17,10 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "hip_util.h"
 #include "device.h"
 
 namespace mbw {
-
-#define HIP_OK(call)                                                                                             \
-	do {                                                                                                         \
-		hipError_t e_ = (call);                                                                                  \
-		if (e_ != hipSuccess) die("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-	} while (0)
 
 // the five RCCL entry points used, with the types of rccl.h (ncclUniqueId = 128 opaque bytes, ncclUint8 = 1)
 struct RcclId { char internal[128]; };

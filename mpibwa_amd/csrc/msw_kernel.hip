@@ -36,15 +36,10 @@
 // target window (2 bits per row) and one u16 per row for the b[] pass.  The work is VALU-bound: ~30 integer ops per cell.
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "hip_util.h"
 #include "device.h"
 
 namespace mbw {
-
-#define HIP_OK(call)                                                                                             \
-	do {                                                                                                         \
-		hipError_t e_ = (call);                                                                                  \
-		if (e_ != hipSuccess) die("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-	} while (0)
 
 namespace {
 

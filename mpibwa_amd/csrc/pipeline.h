@@ -21,18 +21,13 @@
 #include <sys/time.h>
 #include <unistd.h>
 
+#include "hip_util.h"
 #include "device.h"
 #include "host.h"
 #include "hprof.h"
 
 
 namespace mbw {
-
-#define HIP_OK(call)                                                                                             \
-	do {                                                                                                         \
-		hipError_t e_ = (call);                                                                                  \
-		if (e_ != hipSuccess) die("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-	} while (0)
 
 int usable_cpus();
 int host_threads(const mem_opt_t *opt);

@@ -1,0 +1,912 @@
+// stage_entries.hip — the stage-level C entry points (parity tests, micro-benchmarks): one kernel or one stage of the pipeline on inputs
+// chosen by the caller, with device arrays that live for the call (hip_util.h: DevArr).  The pipeline itself does not come through here.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "hip_util.h"
+#include "device.h"
+#include "host.h"
+
+using namespace mbw;
+
+static void need_index()
+{
+	if (!dev_index().ready) die("index not resident on the device: call mi355x_index_upload() first");
+}
+
+static void require_any_device()
+{
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) die("no HIP device visible (no CPU fallback)");
+}
+
+// Reads of a batch as the kernels expect them: read i in a 16-byte aligned slot from slot[i], true length lens[i], the unused bytes of
+// the slots and 16 bytes behind the last one (the kernels stage a read several bytes at a time) filled with `pad`
+struct PackedReads {
+	std::vector<int> lens;
+	std::vector<int64_t> slot;
+	std::vector<uint8_t> flat;
+	int max_len = 0;
+};
+static PackedReads pack_reads(int n, const uint8_t *reads, const int64_t *off, uint8_t pad)
+{
+	PackedReads R;
+	R.lens.resize(n);
+	R.slot.assign(n + 1, 0);
+	for (int i = 0; i < n; ++i) {
+		R.lens[i] = (int)(off[i + 1] - off[i]);
+		R.slot[i + 1] = R.slot[i] + ((R.lens[i] + 15) & ~15);
+		R.max_len = std::max(R.max_len, R.lens[i]);
+	}
+	R.flat.assign(R.slot[n] + 16, pad);
+	for (int i = 0; i < n; ++i) memcpy(R.flat.data() + R.slot[i], reads + off[i], (size_t)R.lens[i]);
+	return R;
+}
+
+// Stage entry of se_simple_kernel (se_kernel.hip) for parity tests: n_reads single-end reads given by their regions as they stand after
+// phase 1 (regs: PR_MAXREG DevReg records per read, n_regs per read); status[i] = 1: decided — desc[i] (SamDesc) and req[i] (AlnReq) are
+// what mem_reg2sam reports with one line; else the code of the test that sent the read to the host (device.h: SE_HOST_*).
+extern "C" int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_reads, const void *regs, const int *n_regs,
+                               int max_len, uint8_t *status, void *desc, void *req)
+{
+	require_any_device();
+	if (n_reads <= 0) return 0;
+	if (max_len <= 0) die("mi355x_se_batch: max_len must be positive");
+	PairParams pp;
+	mem_pestat_t pes[4];
+	se_params(opt, bns->l_pac, n_processed, max_len, pp, pes);
+	std::vector<double> tab((size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, 0, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt, ok((size_t)n_reads, 1);
+	contig_table(bns, ann_off, ann_alt);
+	const size_t n = (size_t)n_reads;
+	const DevReg *hr = (const DevReg *)regs;
+	for (size_t i = 0; i < n; ++i)   // nothing the kernel indexes with may point outside what is uploaded
+		for (int j = 0; j < n_regs[i] && j < PR_MAXREG; ++j)
+			if (hr[i * PR_MAXREG + j].rid < 0 || hr[i * PR_MAXREG + j].rid >= bns->n_seqs) die("mi355x_se_batch: bad contig in region %d of read %zu", j, i);
+	DevArr<DevReg> d_first(n * PR_MAXREG * sizeof(DevReg), regs);
+	DevArr<int> d_nf(n * 4, n_regs);
+	DevArr<uint8_t> d_ok(n, ok.data()), d_aa(ann_alt.size(), ann_alt.data()), d_st(n);
+	DevArr<double> d_tab(tab.size() * 8, tab.data());
+	DevArr<AlnReq> d_rq(n * sizeof(AlnReq));
+	DevArr<SamDesc> d_ds(n * sizeof(SamDesc));
+	launch_se_simple(0, pp, n_reads, d_first, d_nf, d_ok, d_aa, d_tab, d_st, d_rq, d_ds);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	d_st.download(status, n);
+	d_ds.download(desc, n * sizeof(SamDesc));
+	d_rq.download(req, n * sizeof(AlnReq));
+	return 0;
+}
+
+// Stage entry of pair_simple_kernel (pair_kernel.hip) for parity tests: n_pairs pairs given by the regions of their two ends
+// (regs: PR_MAXREG DevReg records per read, n_regs per read) as they stand after phase 1; status[k] = 1: decided — desc[2k], desc[2k+1]
+// (SamDesc) and req[2k], req[2k+1] (AlnReq) are what mem_sam_pe's paired branch reports; else the code of the test that sent the pair to
+// the host.  Returns 0, or -1 when the insert-size statistics are not usable by the kernel.
+extern "C" int mi355x_pair_maxreg(void) { return PR_MAXREG; }
+extern "C" int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], int64_t n_processed, int n_pairs,
+                                 const void *regs, const int *n_regs, int max_len, uint8_t *status, void *desc, void *req)
+{
+	require_any_device();
+	if (n_pairs <= 0) return 0;
+	PairParams pp;
+	size_t n_tab = 0;
+	if (!pair_params(opt, bns->l_pac, pes, n_processed, max_len, pp, &n_tab)) return -1;
+	std::vector<double> tab(n_tab + (size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, n_tab, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt, ok((size_t)n_pairs, 1);
+	contig_table(bns, ann_off, ann_alt);
+	const size_t n = (size_t)2 * n_pairs;
+	DevArr<DevReg> d_first(n * PR_MAXREG * sizeof(DevReg), regs);
+	DevArr<int> d_nf(n * 4, n_regs);
+	DevArr<uint8_t> d_ok(n_pairs, ok.data()), d_aa(ann_alt.size(), ann_alt.data()), d_st(n_pairs);
+	DevArr<int64_t> d_ao(ann_off.size() * 8, ann_off.data());
+	DevArr<double> d_tab(tab.size() * 8, tab.data());
+	DevArr<AlnReq> d_rq(n * sizeof(AlnReq));
+	DevArr<SamDesc> d_ds(n * sizeof(SamDesc));
+	launch_pair_simple(0, pp, n_pairs, d_first, d_nf, d_ok, d_ao, d_aa, d_tab, d_tab + n_tab, d_st, d_rq, d_ds);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	d_st.download(status, n_pairs);
+	d_ds.download(desc, n * sizeof(SamDesc));
+	d_rq.download(req, n * sizeof(AlnReq));
+	return 0;
+}
+
+// Stage entry of pair_wave_kernel (pair_wave_kernel.hip) for parity tests.  It runs the pipeline's own sequence — the host lists the
+// mate-rescue windows with their tags (sam_pe_msw_collect_tagged), launch_msw aligns them, pair_wave_kernel replays mem_sam_pe — on
+// n_pairs pairs given by their reads (nt4 codes, off[2 n_pairs + 1]) and both ends' regions as they stand after mem_sort_dedup_patch
+// (regs: DevReg records back to back, reg_off[2 n_pairs + 1]).  A pair whose lists are not fixed points of the redundancy pass, hold more
+// than PW_MAXREG regions or an ALT hit, or that has no region at all, is not handed to the kernel (status 0).  status[k] = 1: decided —
+// desc[2k], desc[2k + 1] (SamDesc) and req[2k], req[2k + 1] (AlnReq) are what mem_sam_pe's paired branch reports; else the code of the
+// test that left the pair to the host.  *n_align = mate-rescue alignments run.  Returns 0, or -1 when the insert-size statistics are not
+// usable by the kernel.
+// xa_req given: XA on (mi355x_pair_wave_xa_batch) — status PW_DECIDED_XA: decided with an XA tag on a record; xa_cnt[2k + e] entries of
+// end e, their requests at xa_req[(2k + e) * PW_XA_CAP ..] (AlnReq, pad = the entry's contig), the counts also in desc[].flag bits 16-19.
+extern "C" int mi355x_pair_wave_maxreg(void) { return PW_MAXREG; }
+extern "C" int mi355x_pair_wave_xa_cap(void) { return PW_XA_CAP; }
+static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                           int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                           void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt)
+{
+	require_any_device();
+	if (n_align) *n_align = 0;
+	if (n_pairs <= 0) return 0;
+	const int n_reads = 2 * n_pairs;
+	memset(status, 0, (size_t)n_pairs);
+	memset(desc, 0xff, (size_t)n_reads * sizeof(SamDesc));
+	memset(req, 0xff, (size_t)n_reads * sizeof(AlnReq));
+	if (xa_req) { memset(xa_req, 0xff, (size_t)n_reads * PW_XA_CAP * sizeof(AlnReq)); memset(xa_cnt, 0, (size_t)n_reads); }
+	// (the calls whose pairs are all the host's, as for pair_simple_kernel: -P, -a, -V, -5, mapQ_coef_len 0)
+	if ((opt->flag & (MEM_F_NOPAIRING | MEM_F_ALL | MEM_F_REF_HDR | MEM_F_PRIMARY5)) || !(opt->mapQ_coef_len > 0)) return 0;
+	const int64_t l_pac = bns->l_pac;
+	const PackedReads R = pack_reads(n_reads, reads, off, 4);
+	const std::vector<int> &lens = R.lens;
+	const int max_len = std::max(R.max_len, 1);
+	if ((int64_t)max_len * opt->a >= 8192 || msw_lds_bytes(max_len) > 160 * 1024) die("mate-rescue kernel: reads too long for the device path");
+	PairParams pp;
+	size_t n_tab = 0;
+	if (!pair_params(opt, l_pac, pes, n_processed, max_len, pp, &n_tab)) return -1;
+	std::vector<double> tab(n_tab + (size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, n_tab, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
+	// ---- the host's part: eligibility, windows, tags ----
+	const DevReg *hr = (const DevReg *)regs;
+	std::vector<int> work, loff(1, 0), toff;
+	std::vector<unsigned> mfirst;
+	std::vector<DevReg> lists;
+	std::vector<MswReqH> mreq;
+	std::vector<int16_t> tags;
+	std::vector<bseq1_t> s(2);
+	for (int k = 0; k < n_pairs; ++k) {
+		status[k] = 0;
+		HRegV a[2];
+		bool ok = true;
+		for (int e = 0; e < 2 && ok; ++e) {
+			for (int j = reg_off[2 * k + e]; j < reg_off[2 * k + e + 1]; ++j) {
+				const DevReg &d = hr[j];
+				if (d.rid < 0 || d.rid >= bns->n_seqs) die("%s: bad contig in a region of pair %d", who, k);
+				HReg h;
+				h.rb = d.rb; h.re = d.re; h.qb = d.qb; h.qe = d.qe; h.rid = d.rid; h.score = d.score; h.truesc = d.truesc; h.w = d.w;
+				h.seedcov = d.seedcov; h.seedlen0 = d.seedlen0; h.frac_rep = d.frac_rep; h.secondary = -1; h.is_alt = bns->anns[d.rid].is_alt;
+				a[e].push_back(h);
+			}
+			// settled = another redundancy pass without patching returns the list as it is
+			HRegV c;
+			for (size_t j = 0; j < a[e].size(); ++j) c.push_back(a[e][j]);
+			sort_dedup_patch(opt, 0, 0, 0, c);
+			ok = c.size() == a[e].size() && c.settled;
+			for (size_t j = 0; j < c.size() && ok; ++j) ok = c[j].rb == a[e][j].rb && c[j].re == a[e][j].re && c[j].qb == a[e][j].qb && c[j].score == a[e][j].score;
+			a[e].settled = ok;
+		}
+		if (!ok || !pair_wave_eligible(a, PW_MAXREG)) continue;
+		s[0].l_seq = lens[2 * k]; s[1].l_seq = lens[2 * k + 1];
+		work.push_back(k);
+		mfirst.push_back((unsigned)mreq.size());
+		toff.push_back((int)tags.size());
+		sam_pe_msw_collect_tagged(opt, bns, pes, s.data(), a, 2 * k, 4096, mreq, tags);
+		for (int e = 0; e < 2; ++e) {
+			lists.insert(lists.end(), hr + reg_off[2 * k + e], hr + reg_off[2 * k + e + 1]);
+			loff.push_back((int)lists.size());
+		}
+	}
+	const int n_work = (int)work.size();
+	toff.push_back((int)tags.size());
+	const size_t n_mreq = mreq.size();
+	if (n_align) *n_align = (int)n_mreq;
+	if (n_work == 0) return 0;
+	// ---- device: every array with PAD bytes behind what it holds ----
+	hipStream_t st = 0;
+	const size_t PAD = 64, nw = (size_t)n_work;
+	int max_t = 1;
+	for (size_t i = 0; i < n_mreq; ++i) max_t = std::max(max_t, (int)(mreq[i].re - mreq[i].rb));
+	DevArr<uint8_t> d_seq(R.flat.size() + PAD, R.flat.data(), R.flat.size()), d_pac((size_t)(l_pac / 4 + 1) + PAD, pac, (size_t)(l_pac / 4 + 1));
+	DevArr<int64_t> d_off((size_t)(n_reads + 1) * 8 + PAD, R.slot.data(), (size_t)(n_reads + 1) * 8);
+	DevArr<int> d_len((size_t)n_reads * 4 + PAD, lens.data(), (size_t)n_reads * 4);
+	DevArr<MswReq> d_mreq(n_mreq * sizeof(MswReq) + PAD, mreq.data(), n_mreq * sizeof(MswReq));
+	DevArr<MswRes> d_mres(n_mreq * sizeof(MswRes) + PAD);
+	DevArr<uint16_t> d_rows;
+	DevArr<int> d_list, d_tail;
+	if (n_mreq) {
+		d_rows = DevArr<uint16_t>(n_mreq * (size_t)max_t * 2 + PAD);
+		std::vector<int> h_list(2 * n_mreq + 16);
+		d_list = DevArr<int>((2 * n_mreq + 16) * sizeof(int) + PAD);
+		d_tail = DevArr<int>(msw_tail_ints(n_mreq) * sizeof(int) + PAD);
+		launch_msw(st, msw_params(opt, l_pac), (int)n_mreq, d_mreq, d_seq, d_off, d_len, d_pac, d_mres, d_rows, max_len, (const MswReq *)mreq.data(), lens.data(),
+		           h_list.data(), d_list, d_tail);
+		HIP_OK(hipStreamSynchronize(st));   // (h_list is read by the copy queued in launch_msw)
+	}
+	DevArr<int> d_work(nw * 4 + PAD, work.data(), nw * 4);
+	DevArr<DevReg> d_lists(lists.size() * sizeof(DevReg) + PAD, lists.data(), lists.size() * sizeof(DevReg));
+	DevArr<int> d_loff(loff.size() * 4 + PAD, loff.data(), loff.size() * 4);
+	DevArr<unsigned> d_mfirst(mfirst.size() * 4 + PAD, mfirst.data(), mfirst.size() * 4);
+	DevArr<short> d_tags(tags.size() * 2 + PAD, tags.data(), tags.size() * 2);
+	DevArr<int> d_toff(toff.size() * 4 + PAD, toff.data(), toff.size() * 4);
+	DevArr<int64_t> d_ao(ann_off.size() * 8 + PAD, ann_off.data(), ann_off.size() * 8);
+	DevArr<double> d_tab(tab.size() * 8 + PAD, tab.data(), tab.size() * 8);
+	DevArr<uint8_t> d_ws(nw + PAD), d_xc;
+	DevArr<AlnReq> d_rq(2 * nw * sizeof(AlnReq) + PAD), d_xr;
+	DevArr<SamDesc> d_ds(2 * nw * sizeof(SamDesc) + PAD);
+	if (xa_req) {
+		d_xr = DevArr<AlnReq>(2 * nw * PW_XA_CAP * sizeof(AlnReq) + PAD);
+		d_xc = DevArr<uint8_t>(2 * nw + PAD);
+	}
+	d_ws.fill(0, nw);
+	if (d_xc) d_xc.fill(0, 2 * nw);
+	launch_pair_wave(st, pp, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst, d_tags, d_toff, d_ao, d_tab, d_tab + n_tab, d_ws, d_rq, d_ds,
+	                 d_xr, d_xc);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	std::vector<uint8_t> ws(nw);
+	d_ws.download(ws.data(), nw);
+	std::vector<SamDesc> w_ds(2 * nw);
+	std::vector<AlnReq> w_rq(2 * nw);
+	d_ds.download(w_ds.data(), w_ds.size() * sizeof(SamDesc));
+	d_rq.download(w_rq.data(), w_rq.size() * sizeof(AlnReq));
+	std::vector<AlnReq> w_xr(xa_req ? 2 * nw * PW_XA_CAP : 0);
+	std::vector<uint8_t> w_xc(xa_req ? 2 * nw : 0);
+	if (xa_req) {
+		d_xr.download(w_xr.data(), w_xr.size() * sizeof(AlnReq));
+		d_xc.download(w_xc.data(), w_xc.size());
+	}
+	for (int t = 0; t < n_work; ++t) {
+		status[work[t]] = ws[t];
+		if (ws[t] != 1 && ws[t] != PW_DECIDED_XA) continue;
+		for (int e = 0; e < 2; ++e) { ((SamDesc *)desc)[2 * work[t] + e] = w_ds[2 * t + e]; ((AlnReq *)req)[2 * work[t] + e] = w_rq[2 * t + e]; }
+		if (ws[t] != PW_DECIDED_XA) continue;
+		for (int e = 0; e < 2; ++e) {
+			const int c = std::min<int>(w_xc[2 * t + e], PW_XA_CAP);
+			xa_cnt[2 * work[t] + e] = (uint8_t)c;
+			memcpy((AlnReq *)xa_req + (size_t)(2 * work[t] + e) * PW_XA_CAP, &w_xr[(size_t)(2 * t + e) * PW_XA_CAP], (size_t)c * sizeof(AlnReq));
+		}
+	}
+	return 0;
+}
+extern "C" int mi355x_pair_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                      int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                      void *desc, void *req, int *n_align)
+{
+	return pair_wave_batch("mi355x_pair_wave_batch", opt, bns, pac, pes, n_processed, n_pairs, reads, off, regs, reg_off, status, desc, req, n_align, nullptr,
+	                       nullptr);
+}
+extern "C" int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                         int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                         void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt)
+{
+	if (!xa_req || !xa_cnt) die("mi355x_pair_wave_xa_batch: no room for the XA requests");
+	return pair_wave_batch("mi355x_pair_wave_xa_batch", opt, bns, pac, pes, n_processed, n_pairs, reads, off, regs, reg_off, status, desc, req, n_align, xa_req,
+	                       xa_cnt);
+}
+
+extern "C" int mi355x_smem_batch(const mem_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off, int cap,
+                                 uint64_t *intv_out, int *n_out, double *kernel_ms, uint64_t *algo_bytes)
+{
+	need_index();
+	if (n <= 0) return 0;
+	hipStream_t st = 0;
+	const PackedReads R = pack_reads(n, seqs, off, 0);   // 16-byte aligned slots, as the kernel expects
+	const int max_len = R.max_len;
+	size_t total = off[n];
+	size_t per_quad = 0;
+	int n_quads = smem_grid_quads(max_len, &per_quad);
+	DevArr<uint8_t> d_seq(R.flat.size(), R.flat.data());
+	DevArr<int> d_len((size_t)n * 4, R.lens.data()), d_nout((size_t)n * 4);
+	DevArr<int64_t> d_off((size_t)(n + 1) * 8, R.slot.data());
+	DevArr<uint64_t> d_out((size_t)n * cap * 32);
+	DevArr<unsigned long long> d_cnt(256);
+	DevArr<void> d_scr(per_quad * n_quads);
+	d_cnt.zero();
+	d_nout.zero();
+	Timer tm;
+	tm.start(st);
+	const char *ce = getenv("MPIBWA_SMEM_COUNT");   // "0": the production variant of passes 1-2 (no block counting; *algo_bytes = 0)
+	const bool count_blocks = !(ce && atoi(ce) == 0);
+	launch_smem(st, dev_index().fm, smem_params(opt), n, d_seq, d_off, d_len, cap, d_out, d_nout, max_len, d_cnt, d_scr, per_quad, n_quads, count_blocks);
+	double ms = tm.stop(st);
+	HIP_OK(hipGetLastError());
+	unsigned long long cnt[32];
+	d_cnt.download(cnt, 256);
+	d_nout.download(n_out, (size_t)n * 4);
+	d_out.download(intv_out, (size_t)n * cap * 32);
+	// order by info (the reference sorts with an unstable introsort keyed on info only, src/bwamem.c:161;
+	// equal keys are identical records, so any order of ties is the same byte sequence)
+	uint64_t n_intv = 0;
+	for (int i = 0; i < n; ++i) {
+		int m = std::min(n_out[i], cap);
+		Intv *a = (Intv *)(intv_out + (size_t)i * cap * 4);
+		std::sort(a, a + m, [](const Intv &x, const Intv &y) { return x.info < y.info; });
+		n_intv += m;
+	}
+	if (kernel_ms) *kernel_ms = ms;
+	if (algo_bytes) *algo_bytes = count_blocks ? cnt[1] * 64 + total + n_intv * 32 : 0;   // 64 B per occ block + read + output
+	return cnt[2] ? -1 : 0;
+}
+
+extern "C" int mi355x_sa_batch(int n, const uint64_t *k, uint64_t *sa_out, double *kernel_ms, uint64_t *algo_bytes)
+{
+	need_index();
+	if (n <= 0) return 0;
+	hipStream_t st = 0;
+	DevArr<uint64_t> d_k((size_t)n * 8, k), d_o((size_t)n * 8);
+	DevArr<unsigned long long> d_cnt(64);
+	d_cnt.zero();
+	Timer tm;
+	tm.start(st);
+	launch_sa(st, dev_index().fm, n, d_k, d_o, d_cnt);
+	double ms = tm.stop(st);
+	HIP_OK(hipGetLastError());
+	unsigned long long cnt[8];
+	d_cnt.download(cnt, 64);
+	d_o.download(sa_out, (size_t)n * 8);
+	if (kernel_ms) *kernel_ms = ms;
+	if (algo_bytes) *algo_bytes = cnt[1] * 64 + (uint64_t)n * 8;   // 64 B per LF step + the sampled SA word
+	return 0;
+}
+
+// dense != 0: answer from the expanded table (fails if it is absent); dense == 0: LF walk on the sampled SA
+extern "C" int mi355x_sa_batch2(int n, const uint64_t *k, uint64_t *sa_out, double *kernel_ms, int dense)
+{
+	need_index();
+	if (!dense) return mi355x_sa_batch(n, k, sa_out, kernel_ms, nullptr);
+	if (!dev_index().fm.sa_full) return -1;
+	if (n <= 0) return 0;
+	DevArr<uint64_t> d_k((size_t)n * 8, k), d_o((size_t)n * 8);
+	Timer tm;
+	tm.start(0);
+	launch_sa_dense(0, dev_index().fm, n, d_k, d_o);
+	double ms = tm.stop(0);
+	HIP_OK(hipGetLastError());
+	d_o.download(sa_out, (size_t)n * 8);
+	if (kernel_ms) *kernel_ms = ms;
+	return 0;
+}
+extern "C" double mi355x_sa_dense_info(size_t *bytes) { if (bytes) *bytes = dev_index().sa_full_bytes; return dev_index().sa_expand_ms; }
+
+// mi355x_extend_batch (per_job = false: launch_extend, no early / clip, *cells = the total) and mi355x_extend_batch2 (per_job = true:
+// launch_extend2 with early[] and clip[], cells[] = one count per job)
+static int extend_batch(const mem_opt_t *opt, int n, const uint8_t *q, const int64_t *qoff, const uint8_t *t, const int64_t *toff, const int *w,
+                        const int *h0, const int *end_bonus, const int *early, const int *clip, bool per_job, int *out6, uint64_t *cells,
+                        double *kernel_ms)
+{
+	require_any_device();
+	if (n <= 0) return 0;
+	hipStream_t st = 0;
+	std::vector<int> wc(n);
+	int max_qlen = 0;
+	for (int i = 0; i < n; ++i) {
+		int ql = (int)(qoff[i + 1] - qoff[i]);
+		max_qlen = std::max(max_qlen, ql);
+		wc[i] = clamp_band(opt, ql, w[i], end_bonus[i]);
+	}
+	const size_t n4 = (size_t)n * 4, cell_bytes = per_job ? (size_t)n * 8 : 8;
+	DevArr<uint8_t> d_q(qoff[n] + 16, q, qoff[n]), d_t(toff[n] + 16, t, toff[n]);
+	DevArr<int64_t> d_qo((size_t)(n + 1) * 8, qoff), d_to((size_t)(n + 1) * 8, toff);
+	DevArr<int> d_w(n4, wc.data()), d_h0(n4, h0), d_early, d_clip, d_out((size_t)n * 24);
+	if (per_job) { d_early = DevArr<int>(n4, early); d_clip = DevArr<int>(n4, clip); }
+	DevArr<unsigned long long> d_cells(cell_bytes);
+	d_cells.zero();
+	const ExtParams ep = ext_params(opt);
+	Timer tm;
+	tm.start(st);
+	if (per_job) launch_extend2(st, ep, n, d_q, d_qo, d_t, d_to, d_w, d_h0, d_early, d_clip, d_out, d_cells, max_qlen);
+	else launch_extend(st, ep, n, d_q, d_qo, d_t, d_to, d_w, d_h0, nullptr, d_out, d_cells, max_qlen);
+	double ms = tm.stop(st);
+	HIP_OK(hipGetLastError());
+	unsigned long long c = 0;
+	d_cells.download(per_job ? (void *)cells : &c, cell_bytes);
+	d_out.download(out6, (size_t)n * 24);
+	if (kernel_ms) *kernel_ms = ms;
+	if (!per_job && cells) *cells = c;
+	return 0;
+}
+extern "C" int mi355x_extend_batch(const mem_opt_t *opt, int n, const uint8_t *q, const int64_t *qoff, const uint8_t *t,
+                                   const int64_t *toff, const int *w, const int *h0, const int *end_bonus, int *out6,
+                                   double *kernel_ms, uint64_t *cells)
+{
+	return extend_batch(opt, n, q, qoff, t, toff, w, h0, end_bonus, nullptr, nullptr, false, out6, cells, kernel_ms);
+}
+extern "C" int mi355x_extend_batch2(const mem_opt_t *opt, int n, const uint8_t *q, const int64_t *qoff, const uint8_t *t,
+                                    const int64_t *toff, const int *w, const int *h0, const int *end_bonus, const int *early,
+                                    const int *clip, int *out6, uint64_t *cells, double *kernel_ms)
+{
+	return extend_batch(opt, n, q, qoff, t, toff, w, h0, end_bonus, early, clip, true, out6, cells, kernel_ms);
+}
+
+// Stage-level entry point of the mate-rescue alignment (tests, micro-benchmarks): n_req windows [rb,re) of the packed
+// reference `pac` (doubled coordinate, 2 bits per base, l_pac bases) against reads of a batch given as nt4 codes.
+// out8 per request: score, te, qe, score2, te2, tb, qb, flags — kswr_t of ksw_align2 with mem_matesw's flags.
+extern "C" int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
+                                   int n_req, const int64_t *rb, const int64_t *re, const int *read, const int *is_rev, int *out8,
+                                   double *kernel_ms)
+{
+	require_any_device();
+	if (n_req <= 0) return 0;
+	hipStream_t st = 0;
+	const PackedReads R = pack_reads(n_reads, reads, off, 4);   // reads go into 16-byte slots as in the pipeline
+	const int max_len = R.max_len;
+	if ((int64_t)max_len * opt->a >= 8192 || msw_lds_bytes(max_len) > 160 * 1024) die("mate-rescue kernel: reads too long for the device path");
+	std::vector<MswReq> rq(n_req);
+	int max_t = 1;
+	for (int i = 0; i < n_req; ++i) {
+		rq[i].rb = rb[i]; rq[i].re = re[i]; rq[i].read = read[i]; rq[i].is_rev = is_rev[i];
+		if (re[i] < rb[i] || re[i] > 2 * l_pac || rb[i] < 0 || read[i] < 0 || read[i] >= n_reads) die("mi355x_matesw_batch: bad request %d", i);
+		max_t = std::max(max_t, (int)(re[i] - rb[i]));
+	}
+	DevArr<uint8_t> d_seq(R.flat.size(), R.flat.data()), d_pac(l_pac / 4 + 16, pac, l_pac / 4 + 1);
+	DevArr<int64_t> d_off((size_t)(n_reads + 1) * 8, R.slot.data());
+	DevArr<int> d_len((size_t)n_reads * 4, R.lens.data());
+	DevArr<MswReq> d_req((size_t)n_req * sizeof(MswReq), rq.data());
+	DevArr<MswRes> d_res((size_t)n_req * sizeof(MswRes));
+	DevArr<uint16_t> d_rows((size_t)n_req * max_t * 2);
+	std::vector<int> h_list(2 * (size_t)n_req + 16);
+	DevArr<int> d_list((2 * (size_t)n_req + 16) * sizeof(int)), d_tail(msw_tail_ints(n_req) * sizeof(int));
+	Timer tm;
+	tm.start(st);
+	launch_msw(st, msw_params(opt, l_pac), n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, d_rows, max_len, rq.data(), R.lens.data(), h_list.data(), d_list,
+	           d_tail);
+	double ms = tm.stop(st);
+	HIP_OK(hipGetLastError());
+	static_assert(sizeof(MswRes) == 32, "MswRes layout");
+	d_res.download(out8, (size_t)n_req * sizeof(MswRes));
+	if (kernel_ms) *kernel_ms = ms;
+	return 0;
+}
+
+// Stage-level entry point of the chaining stage (tests): seeds of n_reads reads -> filtered chains, computed by
+// chain_kernel (which = 0) or by the host path (which = 1).  Per read r the output is a run of int64 starting at
+// out[out_off[r]]: n_chains (-1 = the device declines the read), then per chain
+//   rid, n_seeds, far_beg, far_end, rmax0, rmax1, frac_rep (float bits), and n_seeds x (rbeg, qbeg, len) in visiting order.
+// out must hold 1 + 7 * 9... entries per read in the worst case; the caller sizes it as n_reads + 8 * total_seeds + ...
+extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const int *lens, const int *l_rep,
+                                      const int64_t *seed_off, const uint64_t *rbeg, const int32_t *qbeg_len, int which, int64_t *out,
+                                      int64_t out_cap, int64_t *out_off)
+{
+	const int64_t S = seed_off[n_reads];
+	int max_len = 0;
+	for (int i = 0; i < n_reads; ++i) max_len = std::max(max_len, lens[i]);
+	const int TS = max_len + 2;
+	std::vector<int> tab;
+	c2a_length_tables(opt, max_len, tab);
+	std::vector<int> nseeds(n_reads);
+	for (int i = 0; i < n_reads; ++i) nseeds[i] = (int)(seed_off[i + 1] - seed_off[i]);
+	std::vector<int> nch(n_reads, 0);
+	std::vector<DevChain> chains(std::max<int64_t>(S, 1));
+	std::vector<DevSeed> seeds(std::max<int64_t>(S, 1));
+	if (which == 0) {
+		require_any_device();
+		std::vector<int64_t> ann_off;
+		std::vector<uint8_t> ann_alt;
+		contig_table(bns, ann_off, ann_alt);
+		const size_t n4 = (size_t)n_reads * 4, s8 = (size_t)S * 8;
+		DevArr<int> d_len(n4 + 4, lens, n4), d_ns(n4 + 4, nseeds.data(), n4), d_lrep(n4 + 4, l_rep, n4), d_tab(tab.size() * 4, tab.data()), d_nch(n4 + 4);
+		DevArr<int64_t> d_so((size_t)(n_reads + 1) * 8, seed_off), d_ao(ann_off.size() * 8, ann_off.data());
+		DevArr<uint8_t> d_aa(ann_alt.size(), ann_alt.data());
+		DevArr<uint64_t> d_sa(s8 + 8, rbeg, s8);
+		DevArr<int32_t> d_qbl(s8 + 8, qbeg_len, s8);
+		DevArr<DevChain> d_ch((size_t)(S + 1) * sizeof(DevChain));
+		DevArr<DevSeed> d_sd((size_t)(S + 1) * sizeof(DevSeed));
+		DevArr<unsigned int> d_srt((size_t)(S + 1) * 4);
+		DevArr<void> d_scr(chain_scratch_bytes(n_reads));
+		launch_chain(0, chain_params(opt, bns->l_pac), n_reads, d_len, d_ns, d_lrep, d_so, d_sa, d_qbl, d_ao, d_aa, bns->n_seqs, d_tab, TS, d_ch, d_sd, d_srt, d_nch, d_scr);
+		HIP_OK(hipDeviceSynchronize());
+		d_nch.download(nch.data(), n4);
+		d_ch.download((void *)chains.data(), (size_t)S * sizeof(DevChain));
+		d_sd.download((void *)seeds.data(), (size_t)S * sizeof(DevSeed));
+	} else {
+		ChainScratch scr;
+		std::vector<HSeed> hs;
+		std::vector<HChain *> ch;
+		std::vector<uint64_t> key;
+		for (int i = 0; i < n_reads; ++i) {
+			const int ns = nseeds[i];
+			if (ns == 0) continue;
+			hs.resize(ns);
+			for (int k = 0; k < ns; ++k) {
+				const int64_t so = seed_off[i] + k;
+				hs[k].rbeg = (int64_t)rbeg[so]; hs[k].qbeg = qbeg_len[2 * so]; hs[k].len = hs[k].score = qbeg_len[2 * so + 1];
+			}
+			chains_from_seeds(opt, bns, lens[i], hs.data(), ns, l_rep[i], scr, ch);
+			chain_filter(opt, scr, ch);
+			int64_t cur = seed_off[i];
+			int c = 0;
+			for (const HChain *cp : ch) {
+				DevChain &d = chains[seed_off[i] + c];
+				pack_chain_for_device(bns, *cp, lens[i], tab.data(), key, d, seeds.data() + cur);
+				d.seed_beg = (int)cur;
+				cur += d.n_seeds;
+				++c;
+			}
+			nch[i] = c;
+		}
+	}
+	int64_t at = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		out_off[i] = at;
+		if (at + 1 > out_cap) return -1;
+		out[at++] = nch[i];
+		for (int c = 0; c < nch[i]; ++c) {
+			const DevChain &d = chains[seed_off[i] + c];
+			if (at + 7 + 3 * (int64_t)d.n_seeds > out_cap) return -1;
+			uint32_t fb;
+			memcpy(&fb, &d.frac_rep, 4);
+			out[at++] = d.rid; out[at++] = d.n_seeds; out[at++] = d.far_beg; out[at++] = d.far_end; out[at++] = d.rmax0; out[at++] = d.rmax1; out[at++] = fb;
+			for (int k = 0; k < d.n_seeds; ++k) {
+				const DevSeed &s = seeds[d.seed_beg + k];
+				out[at++] = s.rbeg; out[at++] = s.qbeg; out[at++] = s.len;
+			}
+		}
+	}
+	out_off[n_reads] = at;
+	return at;
+}
+
+// Stage-level entry point of chain -> regions (tests): see include/mpibwa_amd.h.  The chains are packed by the library's own
+// pack_chain_for_device and laid out as the pipeline lays out device-chained reads (layout 0: read r owns the slots from seed_off[r],
+// which leaves room behind its seeds as the seeding counts do) or host-chained ones (layout 1: dense, behind S slots); then the
+// pipeline's sequence: the length tables, the launch order, the chain groups with their round trip, c2a_kernel, reg_pack_kernel.
+extern "C" int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const uint8_t *reads, const int64_t *off,
+                                    const int *n_chains, const int *chain_rid, const float *chain_frac, const int *chain_nseeds,
+                                    const int64_t *seed_rbeg, const int *seed_qbeg, const int *seed_len, const int *seed_score,
+                                    int heavy_t, int early, int layout, int64_t *out, int64_t out_cap, int64_t *out_off,
+                                    uint64_t *stat4, int *n_units)
+{
+	need_index();
+	if (bns->l_pac != dev_index().l_pac) die("mi355x_c2a_batch: the index given is not the resident one");
+	if (layout != 0 && layout != 1) die("mi355x_c2a_batch: layout %d", layout);
+	if (n_reads <= 0) return 0;
+	const int64_t l_pac = bns->l_pac;
+	// the reads in 16-byte slots, 16 bytes of padding behind the last one (the kernel stages a read 4 bytes at a time)
+	const PackedReads R = pack_reads(n_reads, reads, off, 4);
+	const std::vector<int> &lens = R.lens;
+	const int max_len = R.max_len;
+	std::vector<int> tab;
+	c2a_length_tables(opt, max_len, tab);
+	const int TS = max_len + 2;
+	// the chains through the library's packing; every seed checked against what mem_chain guarantees, so that no window leaves the index
+	std::vector<int> cbeg(n_reads + 1, 0), sbeg(n_reads + 1, 0), nseeds(n_reads, 0);
+	int64_t NC = 0, NS = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		cbeg[i] = (int)NC; sbeg[i] = (int)NS;
+		for (int c = 0; c < n_chains[i]; ++c) nseeds[i] += chain_nseeds[NC + c];
+		NC += n_chains[i]; NS += nseeds[i];
+	}
+	cbeg[n_reads] = (int)NC; sbeg[n_reads] = (int)NS;
+	std::vector<DevChain> pch(std::max<int64_t>(NC, 1));
+	std::vector<DevSeed> psd(std::max<int64_t>(NS, 1));
+	{
+		HChain ch;
+		std::vector<uint64_t> key;
+		int64_t s = 0;
+		for (int i = 0; i < n_reads; ++i)
+			for (int c = cbeg[i]; c < cbeg[i + 1]; ++c) {
+				ch.rid = chain_rid[c]; ch.frac_rep = chain_frac[c];
+				ch.seeds.resize(chain_nseeds[c]);
+				if (ch.rid < 0 || ch.rid >= bns->n_seqs) die("mi355x_c2a_batch: chain %d: rid %d", c, ch.rid);
+				for (int k = 0; k < chain_nseeds[c]; ++k, ++s) {
+					HSeed &h = ch.seeds[k];
+					h.rbeg = seed_rbeg[s]; h.qbeg = seed_qbeg[s]; h.len = seed_len[s]; h.score = seed_score[s];
+					if (h.len <= 0 || h.qbeg < 0 || h.qbeg + h.len > lens[i] || h.rbeg < 0 || h.rbeg + h.len > 2 * l_pac)
+						die("mi355x_c2a_batch: read %d, chain %d: seed %d out of bounds", i, c, k);
+				}
+				DevChain &d = pch[c];
+				pack_chain_for_device(bns, ch, lens[i], tab.data(), key, d, psd.data() + (s - chain_nseeds[c]));
+				for (int k = 0; k < chain_nseeds[c]; ++k) {
+					const DevSeed &t = psd[s - chain_nseeds[c] + k];
+					if (t.rbeg < d.rmax0 || t.rbeg + t.len > d.rmax1) die("mi355x_c2a_batch: read %d, chain %d: a seed leaves the chain's contig or strand", i, c);
+				}
+			}
+	}
+	// slots: layout 0 gives read i the run seed_off[i] .. (its seeds, and a few more: the seeding stage counts the seeds before chaining)
+	// for chains, seeds and regions alike; layout 1 puts them densely behind a base, the chains and the seeds each from their own offset
+	std::vector<int> chain_beg(n_reads), chain_cnt(n_reads), reg_beg(n_reads);
+	std::vector<int64_t> seed_at(n_reads);
+	int64_t n_slots = 0, n_chain_slots = 0;
+	if (layout == 0) {
+		int64_t so = 0;
+		for (int i = 0; i < n_reads; ++i) {
+			chain_beg[i] = reg_beg[i] = (int)so; seed_at[i] = so;
+			so += std::max(nseeds[i], n_chains[i]) + (i % 3);
+		}
+		n_slots = n_chain_slots = so;
+	} else {
+		const int64_t base = NS + 5;
+		for (int i = 0; i < n_reads; ++i) { chain_beg[i] = (int)(base + cbeg[i]); reg_beg[i] = (int)(base + sbeg[i]); seed_at[i] = base + sbeg[i]; }
+		n_slots = base + NS; n_chain_slots = base + NC;
+	}
+	if (n_slots > 0x7fffffff) die("mi355x_c2a_batch: too many seeds");
+	std::vector<DevChain> hch(std::max<int64_t>(n_chain_slots, 1));
+	std::vector<DevSeed> hsd(std::max<int64_t>(n_slots, 1));
+	std::vector<unsigned int> hsrt(std::max<int64_t>(n_slots, 1), 0);
+	for (int i = 0; i < n_reads; ++i) {
+		chain_cnt[i] = n_chains[i];
+		int64_t at = seed_at[i];
+		for (int c = 0; c < n_chains[i]; ++c) {
+			DevChain d = pch[cbeg[i] + c];
+			const int64_t from = sbeg[i] + (at - seed_at[i]);
+			for (int k = 0; k < d.n_seeds; ++k) { hsd[at + k] = psd[from + k]; hsrt[at + k] = (unsigned int)k; }
+			d.seed_beg = (int)at;
+			at += d.n_seeds;
+			hch[chain_beg[i] + c] = d;
+		}
+	}
+	std::vector<int> order(n_reads);
+	c2a_launch_order(n_reads, nseeds.data(), order.data());
+
+	hipStream_t st = 0;
+	const size_t n4 = (size_t)n_reads * 4, tmp_bytes = reg_pack_tmp_bytes(n_reads);
+	DevArr<uint8_t> d_seq(R.flat.size(), R.flat.data());
+	DevArr<int64_t> d_off((size_t)(n_reads + 1) * 8, R.slot.data());
+	DevArr<int> d_len(n4, lens.data()), d_cbeg(n4, chain_beg.data()), d_ccnt(n4, chain_cnt.data()), d_rbeg(n4, reg_beg.data());
+	DevArr<int> d_nregs(n4 + 4), d_tab(tab.size() * 4, tab.data()), d_order(n4, order.data()), d_reg_pos(n4 + 4);
+	DevArr<DevChain> d_ch(hch.size() * sizeof(DevChain), hch.data());
+	DevArr<DevSeed> d_sd(hsd.size() * sizeof(DevSeed), hsd.data());
+	DevArr<unsigned int> d_srt(hsrt.size() * 4, hsrt.data());
+	DevArr<DevReg> d_regs(hsd.size() * sizeof(DevReg)), d_packed(hsd.size() * sizeof(DevReg));
+	DevArr<unsigned long long> d_stat(C2A_STAT_SLOTS * 64);
+	DevArr<void> d_tmp(tmp_bytes);
+	d_stat.zero();
+	{
+		C2aGroupBufs B;
+		const C2aUnits units = c2a_prepare_units(st, B, heavy_t, n_reads, chain_cnt.data(), (size_t)std::max<int64_t>(n_chain_slots, 1), d_cbeg, d_rbeg,
+		                                         d_ch, d_nregs);
+		C2aParams cp;
+		ExtParams ep;
+		c2a_params(opt, l_pac, early, cp, ep);
+		launch_c2a(st, cp, ep, n_reads, d_seq, d_off, d_len, d_cbeg, d_ccnt, d_ch, d_sd, d_srt, d_rbeg, d_regs, d_nregs, d_tab, TS,
+		           (const uint8_t *)dev_index().d_pac, d_stat, max_len, d_order, units.max_units > 0 ? &units : nullptr);
+		launch_reg_pack(st, n_reads, d_rbeg, d_nregs, d_reg_pos, d_regs, d_packed, d_tmp, tmp_bytes, units.max_units > 0 ? &units : nullptr, d_cbeg, d_ccnt);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		if (n_units) *n_units = units.max_units;
+		B.release();
+	}
+	std::vector<int> nregs(n_reads), reg_pos(n_reads + 1);
+	std::vector<unsigned long long> stat(C2A_STAT_SLOTS * 8);
+	d_nregs.download(nregs.data(), n4);
+	d_reg_pos.download(reg_pos.data(), n4 + 4);
+	d_stat.download(stat.data(), C2A_STAT_SLOTS * 64);
+	std::vector<DevReg> regs(std::max(reg_pos[n_reads], 1));
+	d_packed.download((void *)regs.data(), (size_t)reg_pos[n_reads] * sizeof(DevReg));
+	for (int k = 0; k < 4; ++k) {
+		uint64_t t = 0;
+		for (int sl = 0; sl < C2A_STAT_SLOTS; ++sl) t += stat[(size_t)sl * 8 + k];
+		if (stat4) stat4[k] = t;
+	}
+	int64_t at = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		out_off[i] = at;
+		if (at + 1 + 11 * (int64_t)nregs[i] > out_cap) return -1;
+		out[at++] = nregs[i];
+		for (int k = 0; k < nregs[i]; ++k) {
+			const DevReg &a = regs[reg_pos[i] + k];
+			uint32_t fb;
+			memcpy(&fb, &a.frac_rep, 4);
+			const int64_t v[11] = {a.rb, a.re, a.qb, a.qe, a.rid, a.score, a.truesc, a.w, a.seedcov, a.seedlen0, (int64_t)fb};
+			for (int f = 0; f < 11; ++f) out[at++] = v[f];
+		}
+	}
+	out_off[n_reads] = at;
+	return at;
+}
+
+// Stage-level entry point of the CIGAR / MD / NM kernel (tests): n_req regions of reads of a batch against windows of the
+// packed reference `pac`, through mem_reg2aln's band-doubling loop (src/bwamem.c:1106-1122) exactly as the SAM stage asks
+// for them.  which = 0: the product's dispatch (no-DP / narrow band / full size); 1: DP requests straight to the full-size
+// instantiation.  out_hdr5 per request: score, NM, n_cigar, md_len, flags.
+extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, int n_reads, const uint8_t *reads,
+                                   const int64_t *off, int n_req, const int64_t *rb, const int64_t *re, const int *read,
+                                   const int *qb, const int *qe, const int *w, const int *truesc, int which,
+                                   int *out_hdr5, uint32_t *cigar_out, int cigar_cap, char *md_out, int md_cap, double *kernel_ms)
+{
+	require_any_device();
+	if (n_req <= 0) return 0;
+	hipStream_t st = 0;
+	const PackedReads R = pack_reads(n_reads, reads, off, 4);
+	const int max_len = R.max_len;
+	std::vector<AlnReq> rq(n_req);
+	for (int i = 0; i < n_req; ++i) {
+		if (read[i] < 0 || read[i] >= n_reads || rb[i] < 0 || re[i] > 2 * l_pac) die("mi355x_global_batch: bad request %d", i);
+		rq[i].rb = rb[i]; rq[i].re = re[i]; rq[i].read = read[i]; rq[i].qb = qb[i]; rq[i].qe = qe[i]; rq[i].w2 = w[i]; rq[i].truesc = truesc[i];
+		rq[i].pad = 0;
+	}
+	std::vector<int> gaptab;
+	cigar_gap_table(opt, max_len, gaptab);
+	// (not aln_pool_bytes: a test may ask for nothing but long gapped alignments, whose CIGAR and MD outgrow the pipeline's 96-byte average)
+	const size_t pool_bytes = (size_t)n_req * (4 * 96 + 768) + ((size_t)48 << 20);
+	DevArr<uint8_t> d_seq(R.flat.size(), R.flat.data()), d_pac(l_pac / 4 + 16, pac, l_pac / 4 + 1), d_pool(pool_bytes);
+	DevArr<int64_t> d_off((size_t)(n_reads + 1) * 8, R.slot.data());
+	DevArr<AlnReq> d_req((size_t)n_req * sizeof(AlnReq), rq.data());
+	DevArr<AlnHdr> d_hdr((size_t)n_req * sizeof(AlnHdr));
+	DevArr<int> d_gap(gaptab.size() * 4, gaptab.data()), d_lists((size_t)n_req * 3 * 4);
+	DevArr<unsigned long long> d_cnt(256);
+	d_cnt.zero();
+	AlnParams ap;
+	ExtParams ep;
+	aln_params(opt, l_pac, ap, ep);
+	Timer tm;
+	tm.start(st);
+	launch_aln(st, ap, ep, n_req, d_req, d_seq, d_off, d_pac, d_gap, d_hdr, d_pool, d_cnt, pool_bytes, max_len, max_len + 256, d_lists, which != 0);
+	double ms = tm.stop(st);
+	HIP_OK(hipGetLastError());
+	std::vector<AlnHdr> hdr(n_req);
+	std::vector<uint8_t> pool(pool_bytes);
+	d_hdr.download((void *)hdr.data(), (size_t)n_req * sizeof(AlnHdr));
+	d_pool.download(pool.data(), pool_bytes);
+	int rc = 0;
+	for (int i = 0; i < n_req; ++i) {
+		const AlnHdr &h = hdr[i];
+		int *o = out_hdr5 + 5 * (size_t)i;
+		o[0] = h.score; o[1] = h.NM; o[2] = h.n_cigar; o[3] = h.md_len; o[4] = h.flags;
+		if (h.flags) continue;
+		if (h.n_cigar > cigar_cap || h.md_len > md_cap) { rc = -1; continue; }
+		memcpy(cigar_out + (size_t)cigar_cap * i, pool.data() + (size_t)h.pool_off * 4, (size_t)h.n_cigar * 4);
+		memcpy(md_out + (size_t)md_cap * i, pool.data() + (size_t)h.pool_off * 4 + (size_t)h.n_cigar * 4, (size_t)h.md_len);
+	}
+	if (kernel_ms) *kernel_ms = ms;
+	return rc;
+}
+
+// Stage-level entry point of the SAM text kernel (tests): the CIGAR kernel and sam_emit_kernel on chosen line descriptors, queued on one
+// stream through the pipeline's own queue_aln_sam().  Reads as nt4 codes in 16-byte
+// slots like the pipeline's, qualities (or none) at the same places, names back to back; the read group is bwa_rg_id.  The arena is
+// followed by SAM_GUARD bytes that no record may touch; arena and guard are filled with SAM_GUARD_BYTE before the launch.
+#define SAM_GUARD 4096
+#define SAM_GUARD_BYTE 0xA5
+extern "C" size_t mi355x_sam_arena_bytes(int n_reads, int max_len) { return sam_arena_bytes(n_reads, max_len); }
+// (ends = 2: a unit of req_base is a pair, the paired instantiation of the kernel; ends = 1: a unit is a read, the single-end one)
+static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_units, const uint8_t *reads,
+                     const int64_t *off, const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_,
+                     const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                     unsigned long long *cursor, void *hdr_out)
+{
+	require_any_device();
+	if (n_units <= 0) return 0;
+	hipStream_t st = 0;
+	const int n = ends * n_units, n_req = req_base[n_units];
+	const int64_t l_pac = bns->l_pac;
+	const SamDesc *desc = (const SamDesc *)desc_;
+	const AlnReq *reqs = (const AlnReq *)reqs_;
+	for (int i = 0; i < n; ++i)
+		if ((int)(off[i + 1] - off[i]) <= 0 || name_off[i + 1] < name_off[i]) die("%s: bad read %d", who, i);
+	const PackedReads R = pack_reads(n, reads, off, 4);
+	const std::vector<int> &lens = R.lens;
+	const int max_len = R.max_len;
+	// nothing the kernels index with may point outside what was uploaded
+	if (req_base[0] != 0 || n_req < 0) die("%s: bad req_base", who);
+	for (int k = 0; k < n_units; ++k) {
+		if (req_base[k + 1] < req_base[k]) die("%s: bad req_base at unit %d", who, k);
+		if (ends == 2 && (desc[2 * k].req >= 0) != (desc[2 * k + 1].req >= 0)) die("%s: pair %d has one record of the device's only", who, k);
+		for (int e = 0; e < ends; ++e) {
+			const int r = ends * k + e;
+			const SamDesc &d = desc[r];
+			if (d.req < 0) continue;
+			const int q = req_base[k] + d.req;
+			if (q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != r) die("%s: bad descriptor %d", who, r);
+			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[r] || d.qb > d.qe) die("%s: bad region %d", who, r);
+			for (int j = 1; j <= (d.flag >> SAM_XA_SHIFT & SAM_XA_MASK); ++j)   // its XA entries' requests follow its own
+				if (q + j >= req_base[k + 1] || reqs[q + j].read != r || reqs[q + j].pad < 0 || reqs[q + j].pad >= bns->n_seqs || reqs[q + j].rb >= reqs[q + j].re)
+					die("%s: bad XA request %d of descriptor %d", who, j, r);
+		}
+	}
+	for (int q = 0; q < n_req; ++q) {
+		const AlnReq &r = reqs[q];
+		if (r.read < 0) continue;
+		if (r.read >= n || r.rb < 0 || r.re > 2 * l_pac || r.rb > r.re || r.qb < 0 || r.qb > r.qe || r.qe > lens[r.read]) die("%s: bad request %d", who, q);
+	}
+	std::vector<int> gaptab;
+	cigar_gap_table(opt, max_len, gaptab);
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
+	std::vector<int> cno;
+	std::vector<char> cn;
+	contig_names(bns, cn, cno);
+	const SamParams sp = sam_params(l_pac, quals != nullptr);
+	if (!arena_bytes) arena_bytes = sam_arena_bytes(n, max_len);
+	const size_t req_slots = (size_t)std::max(n_req, 1), pool_bytes = aln_pool_bytes(req_slots), n_names = (size_t)name_off[n];
+	DevArr<uint8_t> d_seq(R.flat.size(), R.flat.data()), d_qual, d_pac(l_pac / 4 + 16, pac, l_pac / 4 + 1), d_pool(pool_bytes);
+	if (quals) d_qual = DevArr<uint8_t>(R.flat.size(), pack_reads(n, quals, off, 0).flat.data());   // the qualities in the reads' slots
+	DevArr<int64_t> d_off((size_t)(n + 1) * 8, R.slot.data()), d_ao(ann_off.size() * 8, ann_off.data());
+	DevArr<int> d_len((size_t)n * 4, lens.data()), d_gap(gaptab.size() * 4, gaptab.data()), d_lists(req_slots * 3 * 4);
+	DevArr<AlnReq> d_req(req_slots * sizeof(AlnReq), reqs, (size_t)n_req * sizeof(AlnReq));
+	DevArr<AlnHdr> d_hdr(req_slots * sizeof(AlnHdr));
+	DevArr<unsigned long long> d_cnt(256), d_used(64), d_ooff((size_t)n * 8);
+	DevArr<uint8_t> d_names(n_names + 64, names, n_names), d_arena(arena_bytes + SAM_GUARD);
+	DevArr<char> d_cn(cn.size() + 64, cn.data(), cn.size());
+	DevArr<int> d_noff((size_t)(n + 1) * 4, name_off), d_cno(cno.size() * 4, cno.data()), d_base((size_t)(n_units + 1) * 4), d_olen((size_t)n * 4);
+	DevArr<SamDesc> d_desc((size_t)n * sizeof(SamDesc), desc);
+	d_hdr.zero();
+	d_arena.fill(SAM_GUARD_BYTE);
+	d_ooff.zero();
+	d_olen.fill(0xff);
+	ChunkDev D;
+	D.d_seq = d_seq; D.d_off = d_off; D.d_len = d_len; D.max_len = max_len; D.d_pac = d_pac; D.d_gap = d_gap;
+	D.d_qual = d_qual; D.d_names = d_names; D.d_noff = d_noff; D.d_ann_off = d_ao; D.d_ann_names = d_cn; D.d_ann_noff = d_cno;
+	AlnSamJob J;
+	J.n_req = n_req; J.d_req = d_req; J.d_hdr = d_hdr; J.d_pool = d_pool; J.pool_bytes = pool_bytes; J.d_cnt = d_cnt; J.d_lists = d_lists;
+	J.ends = ends; J.n_reads = n; J.d_desc = d_desc; J.h_base = req_base; J.d_base = d_base;
+	J.d_arena = d_arena; J.arena_bytes = arena_bytes; J.d_used = d_used; J.d_ooff = d_ooff; J.d_olen = d_olen; J.grid_blocks = grid_blocks;
+	queue_aln_sam(st, opt, l_pac, D, sp, J);
+	HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	d_olen.download(out_len, (size_t)n * 4);
+	d_ooff.download(out_off, (size_t)n * 8);
+	d_arena.download(arena_out, arena_bytes + SAM_GUARD);
+	d_used.download(cursor, 8);
+	if (n_req) d_hdr.download(hdr_out, (size_t)n_req * sizeof(AlnHdr));
+	return 0;
+}
+
+extern "C" int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
+                                const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_, const int *req_base,
+                                size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                                unsigned long long *cursor, void *hdr_out)
+{
+	return sam_batch("mi355x_sam_batch", 2, opt, bns, pac, n_pairs, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
+	                 out_len, out_off, arena_out, cursor, hdr_out);
+}
+// The twin for single-end descriptors (mi355x_se_batch's): a unit of req_base is a read, the kernel's single-end instantiation runs
+extern "C" int mi355x_sam_se_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
+                                   const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_, const int *req_base,
+                                   size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
+                                   unsigned long long *cursor, void *hdr_out)
+{
+	return sam_batch("mi355x_sam_se_batch", 1, opt, bns, pac, n_reads, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
+	                 out_len, out_off, arena_out, cursor, hdr_out);
+}
+
+// Stage-level entry point of the seed enumeration between SMEM and SA lookup (tests): seed_prep_kernel, the pipeline's prefix sum over
+// the seed counts, seed_enum_kernel, on chosen intervals (read r: n_intv[r] records of (x0, x1, size, info) from intv[r * cap * 4], in any
+// order; n_intv[r] > cap: the kernels look at the first cap).  intv comes back sorted by info; rows / qbeg_len: per seed the BWT row
+// and (qbeg, len), read r from seed_off[r].  Returns the number of seeds, or -1 - that number when it exceeds seed_cap (then only
+// n_seeds, l_rep and seed_off are valid).
+extern "C" int64_t mi355x_seed_batch(int n_reads, int cap, int max_occ, uint64_t *intv, const int *n_intv, int *n_seeds, int *l_rep,
+                                     int64_t *seed_off, uint64_t *rows, int32_t *qbeg_len, int64_t seed_cap)
+{
+	require_any_device();
+	if (n_reads <= 0) return 0;
+	if (cap <= 0 || max_occ <= 0) die("mi355x_seed_batch: cap and max_occ must be positive");
+	hipStream_t st = 0;
+	const size_t n_words = (size_t)n_reads * cap * 4, n4 = (size_t)n_reads * 4;
+	DevArr<uint64_t> d_intv(n_words * 8, intv);
+	DevArr<int> d_nintv(n4, n_intv), d_ns(n4), d_lrep(n4);
+	DevArr<int64_t> d_so((size_t)(n_reads + 1) * 8);
+	launch_seed_prep(st, n_reads, cap, d_intv, d_nintv, max_occ, d_ns, d_lrep);
+	HIP_OK(hipStreamSynchronize(st));
+	HIP_OK(hipGetLastError());
+	d_ns.download(n_seeds, n4);
+	d_lrep.download(l_rep, n4);
+	d_intv.download(intv, n_words * 8);
+	seed_off[0] = 0;
+	for (int i = 0; i < n_reads; ++i) seed_off[i + 1] = seed_off[i] + n_seeds[i];
+	const int64_t S = seed_off[n_reads];
+	// the device buffers hold what the intervals themselves allow (min(size, max_occ) + 1 rows each), wherever the counts of
+	// seed_prep_kernel put a read: counts that are too small show as seeds of one read over those of the next, never as a write outside
+	const bool fits = S <= seed_cap;
+	int64_t room = S;
+	for (int i = 0; i < n_reads; ++i) {
+		if (n_seeds[i] < 0) die("mi355x_seed_batch: read %d counts %d seeds", i, n_seeds[i]);
+		int64_t most = 0;
+		const int m = std::min(n_intv[i], cap);
+		for (int k = 0; k < m; ++k) most += (int64_t)std::min<uint64_t>(intv[((size_t)i * cap + k) * 4 + 2], (uint64_t)max_occ) + 1;
+		room = std::max(room, seed_off[i] + most);
+	}
+	if (fits && S > 0) {
+		DevArr<uint64_t> d_rows((size_t)room * 8);
+		DevArr<int32_t> d_qbl((size_t)room * 8);
+		d_rows.fill(0xff);
+		d_qbl.fill(0xff);
+		HIP_OK(hipMemcpy(d_so, seed_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice));
+		launch_seed_enum(st, n_reads, cap, d_intv, d_nintv, max_occ, d_so, d_rows, d_qbl);
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipGetLastError());
+		d_rows.download(rows, (size_t)S * 8);
+		d_qbl.download(qbeg_len, (size_t)S * 8);
+	}
+	return fits ? S : -1 - S;
+}
