@@ -380,7 +380,18 @@ int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *p
 int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_reads, const void *regs, const int *n_regs,
                     int max_len, uint8_t *status, void *desc, void *req);
 
-/* mi355x_sam_batch's twin for single-end descriptors (the single-end instantiation of sam_emit_kernel): n_reads reads, read i owns
+/* The redundancy pass of mem_sort_dedup_patch (src/bwamem.c:437-489) on the device, on raw region lists as mem_chain2aln leaves them:
+ * 64-byte records back to back (the layout of mi355x_pair_wave_batch), read r owns regs[reg_off[r] .. reg_off[r+1]).  status[r] = 1: taken
+ * — m[r] regions survive and keep[reg_off[r] + k], k < m[r], is the place in the read's own list of the k-th region of the reference's
+ * result (after the second sort and the removal of exact duplicates); reads with 0 or 1 regions are taken with m = n.  3: more than
+ * mi355x_dedup_maxreg() regions; 4: two regions pass the cheap tests of mem_patch_reg (:411-423) and the reference would go on to its
+ * global alignment — such a read is the host's, m[r] = -1 and its span of keep is not written.  keep (reg_off[n_reads] ints) is sent to
+ * the device as the caller filled it and comes back as the device left it: nothing is written past k = m[r].  Returns 0. */
+int mi355x_dedup_maxreg(void);
+int mi355x_dedup_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const void *regs, const int *reg_off, uint8_t *status, int *m,
+                       int *keep, double *kernel_ms);
+
+/* mi355x_sam_batch's twin for single-end descriptors(the single-end instantiation of sam_emit_kernel): n_reads reads, read i owns
  * reqs[req_base[i] .. req_base[i+1]) (req_base: n_reads + 1 entries) and there is no mate: RNEXT PNEXT TLEN are "* 0 0", no MC tag,
  * FLAG is desc.flag | 0x10 on the reverse strand; a read is handed back (-1) alone.  Everything else — arena, guard, cursor,
  * grid_blocks, hdr_out — as above. */
@@ -441,6 +452,8 @@ typedef struct {
 	uint64_t n_se_dev;                           /* single-end reads decided on the device (se_kernel.hip); their records count in n_sam_dev */
 	uint64_t n_pair_wave_dev;                    /* pairs with mate rescue or up to 64 hits per end decided on the device (pair_wave_kernel.hip); not counted in n_pair_dev */
 	uint64_t n_pair_xa_dev;                      /* pairs pair_wave_kernel decided because its XA listing is on: with an XA tag on a record, or left by pair_kernel.hip for its XA test alone and found to carry none; counted in neither of the two above */
+	uint64_t n_dedup_dev;                        /* reads with two or more raw regions whose mem_sort_dedup_patch result was taken from the device (dedup_kernel.hip, MPIBWA_DEV_DEDUP=1) */
+	uint64_t n_dedup_host;                       /* ... and those the host sorted (all of them unless MPIBWA_DEV_DEDUP=1 enables the stage; then the ones the kernel declined) */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

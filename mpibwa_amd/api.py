@@ -20,7 +20,7 @@ EXPORTS = [
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_extend_batch2", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
-    "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap",
+    "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg",
 ]
 
 
@@ -124,6 +124,8 @@ def load_library(build_if_missing=True):
     sig("mi355x_sam_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_sam_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("mi355x_dedup_maxreg", C.c_int, [])
+    sig("mi355x_dedup_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [P(C.c_double)])
     sig("mi355x_seed_batch", C.c_int64, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64])
     _LIB = lib
     return lib
@@ -452,6 +454,31 @@ class Engine:
                                       status.ctypes.data, desc.ctypes.data, req.ctypes.data)
         assert rc == 0
         return status, desc, req
+
+    DD_TAKEN, DD_HOST_MAXREG, DD_HOST_PATCH = 1, 3, 4
+    DD_FILL = -0x5a5a5a5b
+
+    def dedup(self, opt, lists, fill=DD_FILL):
+        """The redundancy pass of mem_sort_dedup_patch on the device (mi355x_dedup_batch): lists = per read a REG_DT array of its raw regions.
+        -> status (n,) uint8, m (n,) int32 (-1: declined), keep: per read an int32 array as long as its list — the first m entries are the
+        places in the list of the regions the reference keeps, in its final order; the others still hold `fill`.
+        self.last_dedup_ms is the kernels' time."""
+        n = len(lists)
+        reg_off = np.zeros(n + 1, dtype=np.int32)
+        reg_off[1:] = np.cumsum([len(a) for a in lists])
+        allregs = np.zeros(max(1, int(reg_off[-1])), dtype=self.REG_DT)
+        for r, a in enumerate(lists):
+            if len(a):
+                allregs[reg_off[r]:reg_off[r + 1]] = np.asarray(a, dtype=self.REG_DT)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        m = np.full(max(n, 1), -1, dtype=np.int32)
+        keep = np.full(max(1, int(reg_off[-1])), fill, dtype=np.int32)
+        ms = C.c_double(0)
+        rc = self.lib.mi355x_dedup_batch(opt, C.cast(self.bns, C.c_void_p), n, allregs.ctypes.data, reg_off.ctypes.data, status.ctypes.data,
+                                         m.ctypes.data, keep.ctypes.data, C.byref(ms))
+        assert rc == 0
+        self.last_dedup_ms = ms.value
+        return status[:n], m[:n], [keep[reg_off[r]:reg_off[r + 1]].copy() for r in range(n)]
 
     HDR_DT = np.dtype([("score", "<i4"), ("NM", "<i4"), ("n_cigar", "<i4"), ("md_len", "<i4"), ("pool_off", "<u4"), ("flags", "<i4")])
     SAM_GUARD = 4096

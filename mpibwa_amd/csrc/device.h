@@ -383,6 +383,29 @@ void se_params(const mem_opt_t *opt, int64_t l_pac, int64_t n_processed, int max
 void launch_se_simple(void *stream, const PairParams &P, int n_reads, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,
                       const uint8_t *d_ann_alt, const double *d_ltab, uint8_t *d_status, AlnReq *d_reqs, SamDesc *d_desc);
 
+// ---- the redundancy pass of mem_sort_dedup_patch on the raw region lists (dedup_kernel.hip) ----
+#define DD_MAXREG 512             // regions per read dedup_wave_kernel takes (its LDS footprint)
+extern "C" int mi355x_dedup_maxreg(void);
+// status codes of the stage (the numbers of the SE_* codes where the test is the same)
+#define DD_HOST 0                 // not looked at
+#define DD_TAKEN 1                // keep[reg_pos[i] .. + m[i]) lists the survivors in the reference's final order
+#define DD_HOST_MAXREG 3          // more than DD_MAXREG regions
+#define DD_HOST_PATCH 4           // two regions mem_patch_reg would align across
+struct DedupParams {
+	int64_t l_pac;
+	int max_chain_gap, w;
+	float mask_level_redun;
+	int pad;
+};
+DedupParams dedup_params(const mem_opt_t *opt, int64_t l_pac);
+inline size_t dedup_list_ints(int n_reads) { return (size_t)n_reads + 4; }   // the wave kernel's reads, and their number behind them
+// d_packed / d_reg_pos / d_nregs as launch_reg_pack leaves them (read only).  Per read: status[i], m[i] (-1: declined); per region slot:
+// keep[reg_pos[i] + k], k < m[i] = the place in the read's raw list of the k-th region of mem_sort_dedup_patch's result.  Nothing else of
+// keep is written.  d_list: dedup_list_ints(n_reads) ints of scratch.  Two launches: a lane per read up to PR_MAXREG regions (which also
+// lists the longer reads), then a wavefront per listed read.
+void launch_dedup(void *stream, const DedupParams &D, int n_reads, const DevReg *d_packed, const int *d_reg_pos, const int *d_nregs, uint8_t *d_status,
+                  int *d_m, int *d_keep, int *d_list);
+
 // ---- mate-rescue local alignment on the device (msw_kernel.hip) ----
 struct MswReq {                  // one ksw_align2() call of mem_matesw (src/bwamem_pair.c:150-177)
 	int64_t rb, re;              // target window in the doubled coordinate, already clipped to the contig

@@ -6,6 +6,13 @@ namespace mbw {
 
 // MPIBWA_C2A_EARLY: 1 (default) the extension row loops stop early, 0 they run the reference's rows, 2 both with a fatal error on any difference
 static int c2a_early_mode() { const char *e = getenv("MPIBWA_C2A_EARLY"); return e ? atoi(e) : 1; }
+// MPIBWA_DEV_DEDUP=1: the redundancy pass of mem_sort_dedup_patch runs on the device (dedup_kernel.hip) and the host gathers its result;
+// without it, or with MPIBWA_HOST_DEDUP=1, nothing is launched and the host sorts every read (the default: DESIGN §4.3c has the numbers)
+static bool dev_dedup_on()
+{
+	const char *on = getenv("MPIBWA_DEV_DEDUP"), *off = getenv("MPIBWA_HOST_DEDUP");
+	return on && atoi(on) != 0 && !(off && atoi(off) != 0);
+}
 // The turns on the big kernels are taken in the order of arrival.  With a plain mutex a caller whose thread had to be scheduled
 // first (more runnable threads than cores) kept losing the turn to callers that were already running: now and then a chunk that
 // takes 0.6 s took 3 s with eight callers, the others none the faster for it.
@@ -313,6 +320,10 @@ void Call::phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t l
 	int *nregs = (int *)L.h_nregs.ensure((size_t)n_sb * 4 + 8);
 	std::vector<int> reg_pos(n_sb + 1, 0);   // where the regions of read i start in hregs
 	DevReg *hregs = nullptr;
+	// the redundancy pass on the device: status / survivors / their places in the raw list, per read of the sub-batch (null: not run)
+	const bool dev_dedup = dev_dedup_on();
+	const uint8_t *dd_status = nullptr;
+	const int *dd_m = nullptr, *dd_keep = nullptr;
 	if (n_slots == 0) {
 		memset(nregs, 0, (size_t)n_sb * 4);
 		// no read of the sub-batch has a seed: first_reg_kernel does not run, so the pairing kernel's slice of region counts must
@@ -349,6 +360,21 @@ void Call::phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t l
 		C2aParams cp;
 		ExtParams ep;
 		c2a_params(opt, bns->l_pac, c2a_early_mode(), cp, ep);
+		// (everything the turn needs is sized before it is taken: an allocation under the lock stalls every caller behind it)
+		const int64_t guess = std::min<int64_t>(n_slots, (int64_t)2 * n_sb + 1024);
+		uint8_t *d_dd_status = nullptr, *h_dd_status = nullptr;
+		int *d_dd_m = nullptr, *d_dd_keep = nullptr, *d_dd_list = nullptr, *h_dd_m = nullptr, *h_dd_keep = nullptr;
+		std::unique_ptr<EvTimer> ev_dd;
+		if (dev_dedup) {
+			ev_dd.reset(new EvTimer());
+			d_dd_status = (uint8_t *)L.dd_status.ensure((size_t)n_sb);
+			d_dd_m = (int *)L.dd_m.ensure((size_t)n_sb * 4);
+			d_dd_keep = (int *)L.dd_keep.ensure((size_t)n_slots * 4);
+			d_dd_list = (int *)L.dd_list.ensure(dedup_list_ints(n_sb) * 4);
+			h_dd_status = (uint8_t *)L.h_dd_status.ensure((size_t)n_sb + 8);
+			h_dd_m = (int *)L.h_dd_m.ensure((size_t)n_sb * 4 + 8);
+			h_dd_keep = (int *)L.h_dd_keep.ensure((size_t)guess * 4 + 8);
+		}
 		stage(50);
 		std::unique_lock<TurnLock> turn(g_c2a_turn, std::defer_lock);
 		if (take_turns) turn.lock();
@@ -361,17 +387,26 @@ void Call::phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t l
 		// the regions sit in sparse per-read slots: prefix-sum + pack on the device, queued behind the kernel, then one
 		// copy of what is usually enough (2 regions per read); the rare rest follows once the total is known
 		int *d_reg_pos = (int *)L.reg_pos.ensure((size_t)(n_sb + 1) * 4);
-		const int64_t guess = std::min<int64_t>(n_slots, (int64_t)2 * n_sb + 1024);
 		DevReg *d_packed = (DevReg *)L.regs_packed.ensure((size_t)n_slots * sizeof(DevReg));
 		const size_t tmp_bytes = reg_pack_tmp_bytes(n_sb);
 		void *d_tmp = L.pack_tmp.ensure(tmp_bytes);
 		launch_reg_pack(lst, n_sb, d_reg_beg, d_nregs, d_reg_pos, d_regs, d_packed, d_tmp, tmp_bytes, units.max_units > 0 ? &units : nullptr, d_chain_beg, d_chain_cnt);
 		if (d_pr_first) launch_first_reg(lst, n_sb, d_reg_pos, d_nregs, d_packed, d_pr_first + (size_t)lo * PR_MAXREG, d_pr_nfirst + lo);
+		if (dev_dedup) {   // reads the raw lists, writes none of them: first_reg_kernel and the copies below see what reg_pack left
+			ev_dd->start(lst);
+			launch_dedup(lst, dedup_params(opt, bns->l_pac), n_sb, d_packed, d_reg_pos, d_nregs, d_dd_status, d_dd_m, d_dd_keep, d_dd_list);
+			ev_dd->stop(lst);
+		}
 		hregs = (DevReg *)L.h_regs.ensure((size_t)guess * sizeof(DevReg) + 8);
 		unsigned long long *stat_h = (unsigned long long *)L.h_c2a_stat.ensure(C2A_STAT_SLOTS * 64);
 		HIP_OK(hipMemcpyAsync(stat_h, d_c2a_stat, C2A_STAT_SLOTS * 64, hipMemcpyDeviceToHost, lst));
 		HIP_OK(hipMemcpyAsync(nregs, d_nregs, (size_t)n_sb * 4, hipMemcpyDeviceToHost, lst));
 		HIP_OK(hipMemcpyAsync(hregs, d_packed, (size_t)guess * sizeof(DevReg), hipMemcpyDeviceToHost, lst));
+		if (dev_dedup) {
+			HIP_OK(hipMemcpyAsync(h_dd_status, d_dd_status, (size_t)n_sb, hipMemcpyDeviceToHost, lst));
+			HIP_OK(hipMemcpyAsync(h_dd_m, d_dd_m, (size_t)n_sb * 4, hipMemcpyDeviceToHost, lst));
+			HIP_OK(hipMemcpyAsync(h_dd_keep, d_dd_keep, (size_t)guess * 4, hipMemcpyDeviceToHost, lst));
+		}
 		stream_wait(lst);
 		HIP_OK(hipGetLastError());
 		if (take_turns) turn.unlock();
@@ -385,8 +420,23 @@ void Call::phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t l
 		if (NR > guess) {
 			DevReg *all = (DevReg *)L.h_regs2.ensure((size_t)NR * sizeof(DevReg) + 8);
 			HIP_OK(hipMemcpyAsync(all, d_packed, (size_t)NR * sizeof(DevReg), hipMemcpyDeviceToHost, lst));
+			if (dev_dedup) {
+				int *all_keep = (int *)L.h_dd_keep2.ensure((size_t)NR * 4 + 8);
+				HIP_OK(hipMemcpyAsync(all_keep, d_dd_keep, (size_t)NR * 4, hipMemcpyDeviceToHost, lst));
+				h_dd_keep = all_keep;
+			}
 			stream_wait(lst);
 			hregs = all;
+		}
+		if (dev_dedup) {
+			dd_status = h_dd_status; dd_m = h_dd_m; dd_keep = h_dd_keep;
+			ps.k_dedup = ev_dd->ms();
+			if (getenv("MPIBWA_CPUSEC")) {
+				unsigned long long c[5] = {0, 0, 0, 0, 0};
+				for (int i = 0; i < n_sb; ++i) ++c[dd_status[i] < 5 ? dd_status[i] : 0];
+				fprintf(stderr, "[dedup] kernels %.2f ms; reads taken %llu, more than %d regions %llu, to patch %llu\n", ps.k_dedup, c[DD_TAKEN], DD_MAXREG,
+				        c[DD_HOST_MAXREG], c[DD_HOST_PATCH]);
+			}
 		}
 	}
 	double t5 = now_ms();
@@ -400,16 +450,21 @@ void Call::phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t l
 	HReg *arena = (HReg *)reg_arena.ensure((size_t)slice[n_sb] * sizeof(HReg));
 	parallel_for(lane_thr, n_sb, 256, [&](int i) {
 		HRegV &v = regs[lo + i];
-		int m = nregs[i];
-		v.attach(arena + slice[i], (uint32_t)(m + SLACK));
+		const int n_raw = nregs[i];
+		// a read the device took: its survivors gathered in the reference's final order, nothing to sort; every other read from its raw list
+		const bool taken = dd_status && dd_status[i] == DD_TAKEN;
+		const int m = taken ? dd_m[i] : n_raw;
+		v.attach(arena + slice[i], (uint32_t)(n_raw + SLACK));
 		v.resize(m);
 		for (int k = 0; k < m; ++k) {
-			const DevReg &d = hregs[reg_pos[i] + k];
+			const DevReg &d = hregs[reg_pos[i] + (taken ? dd_keep[reg_pos[i] + k] : k)];
 			HReg &r = v[k];
 			r.rb = d.rb; r.re = d.re; r.qb = d.qb; r.qe = d.qe; r.rid = d.rid; r.score = d.score; r.truesc = d.truesc;
 			r.w = d.w; r.seedcov = d.seedcov; r.seedlen0 = d.seedlen0; r.frac_rep = d.frac_rep;
+			if (taken && n_raw > 1) r.n_comp = 1;
 		}
-		sort_dedup_patch(opt, bns, pac, (uint8_t *)seqs_r[i].seq, v);
+		if (taken) v.settled = true;
+		else sort_dedup_patch(opt, bns, pac, (uint8_t *)seqs_r[i].seq, v);
 		for (HReg &r : v)
 			if (r.rid >= 0 && bns->anns[r.rid].is_alt) r.is_alt = 1;
 	});
@@ -426,6 +481,8 @@ void Call::phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t l
 		for (int b = 0; b < nt; ++b)
 			for (size_t v = 0; v < hsz; ++v) pes_hist[v] += part[b][v];
 	}
+	for (int i = 0; i < n_sb; ++i)
+		if (nregs[i] > 1) ++(dd_status && dd_status[i] == DD_TAKEN ? ps.n_dedup_dev : ps.n_dedup_host);
 	double t6 = now_ms();
 	ps.smem = t2 - t1; ps.sa = t3 - t2; ps.chain = t4 - t3; ps.ext = t5 - t4; ps.regs = t6 - t5;
 }
@@ -482,6 +539,7 @@ void Call::phase1_all()
 	for (int k = 0; k < n_sub; ++k) {
 		STAT.k_smem_ms += ps[k].k_smem; STAT.k_sa_ms += ps[k].k_sa; STAT.k_ext_ms += ps[k].k_ext;
 		STAT.smem_bytes += ps[k].smem_bytes; STAT.smem_tab_bytes += ps[k].smem_tab_bytes; STAT.sa_bytes += ps[k].sa_bytes; STAT.ext_cells += ps[k].cells; STAT.n_ext += ps[k].n_ext;
+		STAT.n_dedup_dev += ps[k].n_dedup_dev; STAT.n_dedup_host += ps[k].n_dedup_host;
 		STAT.n_intv += ps[k].n_intv; STAT.n_seeds += ps[k].n_seeds; STAT.n_chains += ps[k].n_chains;
 		// per-stage wall times: the sub-batches of a lane run back to back and the lanes side by side, so sum / lanes
 		STAT.smem_ms += ps[k].smem / n_lanes; STAT.sa_ms += ps[k].sa / n_lanes;

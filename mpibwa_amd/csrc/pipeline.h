@@ -209,6 +209,10 @@ struct LaneBufs {
 	C2aGroupBufs grp;
 	DevBuf intv, nintv, cnt, scratch, nseeds, lrep, seed_off, rows, qbl, sa;
 	DevBuf chain_off, chains, seeds, srt, reg_off, regs, nregs, tab;
+	// the redundancy pass on the device (dedup_kernel.hip): status and survivor count per read, the survivors' places per region slot, the
+	// wave kernel's list; the host copies (the places come back in two steps, like the regions)
+	DevBuf dd_status, dd_m, dd_keep, dd_list;
+	PinBuf h_dd_status, h_dd_m, h_dd_keep, h_dd_keep2;
 };
 // One CIGAR-and-SAM job of the SAM stage (sam_stage.hip): requests (the host's: the units decided on the device bring their own array),
 // result headers and pool, counters, the kernel's lists; request base per unit, record arena, its cursor, record offsets and lengths
@@ -273,7 +277,7 @@ struct CallCtx {
 
 // ---- one call ----
 // what a sub-batch of phase 1 reports: kernel times, wall times per stage, counters
-struct P1 { double k_smem = 0, k_sa = 0, k_ext = 0, smem = 0, sa = 0, chain = 0, ext = 0, regs = 0; uint64_t smem_bytes = 0, smem_tab_bytes = 0, sa_bytes = 0, cells = 0, n_ext = 0, n_intv = 0, n_seeds = 0, n_chains = 0; };
+struct P1 { double k_smem = 0, k_sa = 0, k_ext = 0, k_dedup = 0, smem = 0, sa = 0, chain = 0, ext = 0, regs = 0; uint64_t smem_bytes = 0, smem_tab_bytes = 0, sa_bytes = 0, cells = 0, n_ext = 0, n_intv = 0, n_seeds = 0, n_chains = 0, n_dedup_dev = 0, n_dedup_host = 0; };
 
 // One CIGAR-and-SAM job in flight: what was launched, and the host copies of what came back
 struct Job {

@@ -81,6 +81,44 @@ extern "C" int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_
 	return 0;
 }
 
+// Stage entry of the redundancy pass on the device (dedup_kernel.hip) for parity tests: n_reads reads given by their raw region lists as
+// mem_chain2aln leaves them (regs: DevReg records back to back, read r owns regs[reg_off[r] .. reg_off[r + 1])), through the pipeline's own
+// launch sequence (launch_dedup: the lane-per-read kernel, which lists the longer reads, then the wave kernel).  status[r], m[r] as
+// device.h describes them (DD_*); keep (reg_off[n_reads] ints) goes up as the caller filled it and comes back as the device left it.
+extern "C" int mi355x_dedup_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const void *regs, const int *reg_off, uint8_t *status, int *m,
+                                  int *keep, double *kernel_ms)
+{
+	require_any_device();
+	if (kernel_ms) *kernel_ms = 0;
+	if (n_reads <= 0) return 0;
+	const size_t n = (size_t)n_reads;
+	if (reg_off[0] != 0) die("mi355x_dedup_batch: reg_off[0] must be 0");
+	std::vector<int> nregs(n);
+	for (size_t i = 0; i < n; ++i) {
+		if (reg_off[i + 1] < reg_off[i]) die("mi355x_dedup_batch: reg_off decreases at read %zu", i);
+		nregs[i] = reg_off[i + 1] - reg_off[i];
+	}
+	const size_t NR = (size_t)reg_off[n];
+	hipStream_t st = 0;
+	DevArr<DevReg> d_packed(std::max<size_t>(NR, 1) * sizeof(DevReg), regs, NR * sizeof(DevReg));
+	DevArr<int> d_pos((n + 1) * 4, reg_off), d_nr(n * 4, nregs.data()), d_m(n * 4), d_keep(std::max<size_t>(NR, 1) * 4, keep, NR * 4);
+	DevArr<int> d_list(dedup_list_ints(n_reads) * 4);
+	DevArr<uint8_t> d_st(n);
+	d_st.zero();
+	d_m.fill(0xff);
+	Timer tm;
+	tm.start(st);
+	launch_dedup(st, dedup_params(opt, bns->l_pac), n_reads, d_packed, d_pos, d_nr, d_st, d_m, d_keep, d_list);
+	const double ms = tm.stop(st);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	d_st.download(status, n);
+	d_m.download(m, n * 4);
+	if (NR) d_keep.download(keep, NR * 4);
+	if (kernel_ms) *kernel_ms = ms;
+	return 0;
+}
+
 // Stage entry of pair_simple_kernel (pair_kernel.hip) for parity tests: n_pairs pairs given by the regions of their two ends
 // (regs: PR_MAXREG DevReg records per read, n_regs per read) as they stand after phase 1; status[k] = 1: decided — desc[2k], desc[2k+1]
 // (SamDesc) and req[2k], req[2k+1] (AlnReq) are what mem_sam_pe's paired branch reports; else the code of the test that sent the pair to
