@@ -73,6 +73,75 @@ def repeat_like_interval_sets(rng, n_cases, l_pac, offs, n_seqs, n_copies=(100, 
     return cases
 
 
+SORTED_TAIL_SIZES = (25, 26, 27, 40, 64, 130, 255, 300, 700, 1100, 2000)
+SORTED_TAIL_SEED = 2605     # the families of the comb sort are generated under this seed
+SORTED_TAIL_LQ = 151
+
+
+def sorted_tail_weights(rng, n):
+    """n weights of single-seed chains (seed lengths 76 ... 150: all within the default drop_ratio of one another) that take
+    mem_chain_flt's sort (heavier first) out of its depth budget: the heaviest first, a body from 2-6 values in random order, then
+    2 * ceil(log2 n) strictly lighter and lighter ones below the body.  Every partition of the quicksort takes the range's last
+    element for its pivot and splits off nothing else, so the range that is left when the budget is spent goes to the comb sort.
+    Drawn again until the model (tests/introsort_model.py) says so, for a range of at least 17, and says that an insertion sort in
+    the comb sort's place would have left another order."""
+    import introsort_model as im
+    t = im.budget(n)
+    heavier = lambda x, y: x > y
+    while True:
+        top = int(rng.integers(75 + t, 121))
+        tail = sorted((int(v) for v in rng.choice(np.arange(76, top + 1), t, replace=False)), reverse=True)
+        vals = rng.choice(np.arange(top + 1, 150), int(rng.integers(2, 7)), replace=False)
+        w = [150] + [int(v) for v in rng.choice(vals, n - 1 - t)] + tail
+        if n - (t - 1) < 17:     # 25 chains: 16 are left when the budget is down to its last partition, and the final insertion sort takes them
+            return w
+        o, st = im.sort_keys(w, heavier)
+        if st.widest >= 17 and st.comb_swaps and im.sort_keys(w, heavier, comb=False)[0] != o:
+            return w
+
+
+def sorted_tail_chain_sets(rng, sizes, l_pac, offs, n_seqs, max_hits=400):
+    """Reads whose chains reach mem_chain_flt's sort in an order that ends in its comb sort (sorted_tail_weights): n single-seed chains
+    per read, so a chain's weight is its seed's length and its place among the chains is its position's.  Positions ascend through both
+    strands of every contig, 500 bases clear of contig ends and of the strand boundary, 400 or more apart (300 where n chains would
+    not fit otherwise): no seed is within w of another chain's diagonal, none is contained in another, all positions differ.  At most
+    max_hits (< max_occ) chains share one query interval.  Four reads per size up to 255 chains, two per larger size; the order of the
+    rows is the construction's and is not shuffled.  -> [(lq, [(qb, qe, hits)])] as reference_chains takes them"""
+    lq = SORTED_TAIL_LQ
+    spans = []
+    for k in range(n_seqs):
+        spans.append((offs[k] + 500, offs[k + 1] - 500 - lq))
+        spans.append((2 * l_pac - offs[k + 1] + 500, 2 * l_pac - offs[k] - 500 - lq))
+    spans.sort()
+    cases = []
+    for n in sizes:
+        for rep in range(4 if n <= 255 else 2):
+            step, jit = 500, 100
+            slots = [p for lo, hi in spans for p in range(lo, hi - jit, step)]
+            if len(slots) < n:
+                step, jit = 340, 40
+                slots = [p for lo, hi in spans for p in range(lo, hi - jit, step)]
+            assert len(slots) >= n, (n, len(slots))
+            first = int(rng.integers(0, len(slots) - n + 1)) if n <= 255 else 0
+            pick = slots[first:first + n] if n <= 255 else [slots[i] for i in np.sort(rng.choice(len(slots), n, replace=False))]
+            pos = [p + int(rng.integers(0, jit + 1)) for p in pick]
+            ivs, full = {}, lambda qb, ln: len(ivs.get((qb, qb + ln), ())) >= max_hits
+            for p, ln in zip(pos, sorted_tail_weights(rng, n)):
+                qb = int(rng.integers(0, lq - ln + 1))
+                while full(qb, ln):
+                    qb = (qb + 1) % (lq - ln + 1)
+                ivs.setdefault((qb, qb + ln), []).append(p)
+            cases.append((lq, [(qb, qe, h) for (qb, qe), h in ivs.items()]))
+    return cases
+
+
+def single_seed_weights(case):
+    """the weights of the chains of a read whose chains have one seed each, in the order mem_chain_flt's sort meets them (ascending
+    position)"""
+    lq, ivs = case
+    return [ln for _, ln in sorted((rb, qe - qb) for qb, qe, hits in ivs for rb in hits)]
+
+
 def reference_chains(ref, ropt, cases):
     """-> (read lengths, seeds per read in mem_chain's visiting order, expected chains [(rid, frac_rep bits, seeds)])"""
     lens, seedsets, want = [], [], []

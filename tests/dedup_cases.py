@@ -24,6 +24,9 @@ expect ("taken", "maxreg", "patch", or None: only the invariant of the stage tes
              (it merged), set by full_set()
   mixed      the clusters of same_span with a span of its own for every region: about half of these lists reach the patch tests
   random     the ends of pair_cases.adversarial_pairs, as in se_stage_cases.random_cases
+  sorted_re, sorted_score   lists that arrive in the order that takes the first (by `re`) or the second sort (by score, rb, qb) out of
+             its depth budget and into ks_introsort's comb sort, with equal keys whose order shows in the result (sorted_cases(), apart
+             from build_cases(): no other family gets there)
 """
 import ctypes as C
 
@@ -89,8 +92,9 @@ def _loci(ix, rng, n_loci):
     return loci
 
 
-def _cluster_rows(ix, rng, n, free_span):
-    loci = _loci(ix, rng, int(rng.integers(1, min(5, max(1, n // 2)) + 1)))
+def _cluster_rows(ix, rng, n, free_span, loci=None):
+    if loci is None:
+        loci = _loci(ix, rng, int(rng.integers(1, min(5, max(1, n // 2)) + 1)))
     qb0, qe0 = [(0, LQ), (5, 140), (30, 110), (0, 75)][int(rng.integers(4))]
     s0 = int(rng.choice([qe0 - qb0, qe0 - qb0 - 10, 60]))
     rows = []
@@ -177,6 +181,189 @@ def build_cases(ix, seed):
             rows.append((rb, rb + ln, qb, qe, last, int(rng.choice([ln, ln - 4, 40]))))
         add("junction", "n%d" % n, rows, None)
     return cases
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The families of the comb sort.  ks_introsort falls back to a comb sort of the range in hand when its depth budget 2 * ceil(log2 n) is
+# spent; an input that is already in order loses one element per partition and gets there from 26 elements on, shuffled or random
+# lists practically never do (tests/test_introsort_model.py counts it).  These lists arrive in the order that spends the budget —
+# they are NOT shuffled — and are built with the model of the sort (tests/introsort_model.py) in the loop.
+# ---------------------------------------------------------------------------------------------------------------------
+SORTED_SIZES = (25, 26, 27, 40, 64, 65, 130, 511, 512)
+SORTED_SEED = 2606         # list number s of a family (0: sorted_re, 1: sorted_score) and size n is drawn from the seed (SORTED_SEED, family, n, s)
+SORTED_PER_SIZE = 4
+# found by find_sorted_seeds() on the index of the suite's `genome` fixture (three contigs of 120 000)
+SORTED_SEEDS = {
+    ("sorted_re", 25): [0, 1, 2, 3], ("sorted_re", 26): [8, 15, 23, 46], ("sorted_re", 27): [0, 32, 37, 43],
+    ("sorted_re", 40): [0, 1, 19, 22], ("sorted_re", 64): [7, 12, 36, 46], ("sorted_re", 65): [4, 8, 14, 28],
+    ("sorted_re", 130): [24, 36, 39, 43], ("sorted_re", 511): [303, 596, 634, 847], ("sorted_re", 512): [55, 536, 732, 979],
+    ("sorted_score", 25): [0, 1, 2, 3], ("sorted_score", 26): [0, 1, 2, 3], ("sorted_score", 27): [0, 2, 4, 5],
+    ("sorted_score", 40): [0, 1, 2, 3], ("sorted_score", 64): [0, 1, 2, 3], ("sorted_score", 65): [0, 1, 2, 3],
+    ("sorted_score", 130): [0, 1, 2, 3], ("sorted_score", 511): [0, 1, 2, 3], ("sorted_score", 512): [0, 1, 2, 3],
+}
+_SORTED = {}               # the lists are built once per index geometry and left unchanged
+
+
+def can_run_out_of_depth(n):
+    """every partition takes at least one element off the range and ranges of 16 or fewer are left to the final insertion sort, so the
+    budget of n elements can only be spent on a range of 17 or more from n = 26 on (25: a budget of 10, 16 left after 9 partitions)"""
+    import introsort_model as im
+    return n - (im.budget(n) - 1) >= 17
+
+
+def model_pass(regs, max_chain_gap=MAX_GAP, mask_level_redun=0.95, comb=(True, True)):
+    """mem_sort_dedup_patch (src/bwamem.c:437-489) without mem_patch_reg — for lists whose regions all have one query span, which its
+    co-linearity test turns away — with the sorts of introsort_model, either with its fallback as comb[k] says
+    -> dict(kept: raw places in final order, first / second: the Stats of the two sorts, sorted: the survivors after the second sort)"""
+    import introsort_model as im
+    rb, re, qb, qe, rid, sc = (regs[f].tolist() for f in ("rb", "re", "qb", "qe", "rid", "score"))
+    n = len(rb)
+    o = list(range(n))
+    st1 = im.introsort(o, lambda x, y: re[x] < re[y], comb[0])
+    alive = [qe[k] > qb[k] for k in range(n)]
+    f, prod = np.float32(mask_level_redun), {}
+
+    def over(x, m):   # x > mask_level_redun * m in the reference's types: the int64 m goes to float, the product is a float, x goes to float
+        if m not in prod:
+            prod[m] = float(f * np.float32(m))
+        return float(np.float32(x)) > prod[m] if abs(x) >= 1 << 24 else x > prod[m]
+
+    for i in range(1, n):
+        p, j = o[i], i - 1
+        while j >= 0 and rid[p] == rid[o[j]] and rb[p] < re[o[j]] + max_chain_gap:
+            q = o[j]
+            j -= 1
+            if not alive[q]:
+                continue
+            orr = re[q] - rb[p]
+            oq = qe[q] - qb[p] if qb[q] < qb[p] else qe[p] - qb[q]
+            mr = min(re[q] - rb[q], re[p] - rb[p])
+            mq = min(qe[q] - qb[q], qe[p] - qb[p])
+            if over(orr, mr) and over(oq, mq):
+                if sc[p] < sc[q]:
+                    alive[p] = False
+                    break
+                alive[q] = False
+    surv = [k for k in o if alive[k]]
+    st2 = im.introsort(surv, lambda x, y: sc[x] > sc[y] or (sc[x] == sc[y] and (rb[x] < rb[y] or (rb[x] == rb[y] and qb[x] < qb[y]))), comb[1])
+    kept = [k for i, k in enumerate(surv) if i == 0 or (sc[k], rb[k], qb[k]) != (sc[surv[i - 1]], rb[surv[i - 1]], qb[surv[i - 1]])]
+    return dict(kept=kept, first=st1, second=st2, sorted=surv)
+
+
+def kept_rows(regs, kept):
+    return [tuple(int(regs[k][f]) for f in FIELDS) for k in kept]
+
+
+def twin_order(sorted_places, twins):
+    """per twin pair (a, b): does a stand before b?"""
+    at = {k: i for i, k in enumerate(sorted_places)}
+    return [at[a] < at[b] for a, b in twins]
+
+
+def _sorted_re_rows(ix, rng, n):
+    """first sort, by `re`: the least `re` first, a body of the same_span kind at one to three loci of one contig and strand, then
+    2 * ceil(log2 n) regions with strictly ascending `re` farther along the contig than any max_chain_gap"""
+    import introsort_model as im
+    t = im.budget(n)
+    c, rev = int(rng.integers(ix.n_seqs)), int(rng.integers(2))
+    lo, hi = _strand_range(ix, c, rev)
+    p0 = int(rng.integers(lo + 1000, hi - 60000))
+    steps = [170, 700, 2500, 15000]
+    loci = [(c, p0)] + [(c, p0 + steps[int(rng.integers(len(steps)))] + 3 * k) for k in range(1, int(rng.integers(1, 4)))]
+    body = _cluster_rows(ix, rng, n - 1 - t, False, loci)
+    qb, qe = body[0][2], body[0][3]
+    scores = [r[5] for r in body]
+    rows = [(p0 - 400, p0 - 400 + qe - qb, qb, qe, c, scores[int(rng.integers(len(scores)))])] + body
+    p = max(r[1] for r in body) + MAX_GAP + 5000 + int(rng.integers(0, 5000))
+    for k in range(t):
+        p += int(rng.choice([3, 40, 400]))
+        rows.append((p, p + qe - qb, qb, qe, c, scores[int(rng.integers(len(scores)))]))
+    assert rows[-1][1] < hi - 400
+    return rows
+
+
+def _sorted_score_rows(ix, rng, n):
+    """second sort, by score descending, then rb, then qb: regions nothing removes — one per slot, in ascending position, all with one
+    query span (so mem_patch_reg's co-linearity test turns every pair away where the slots are closer than max_chain_gap: the slots
+    of `far` are 12 000 apart, these as far as n of them fit, 800 or more) — with the highest score first, a body of scores from 2-6
+    values, and 2 * ceil(log2 n) strictly descending scores below the body's at the end.  The keys are unique but for the twins: body
+    regions followed by a copy equal in (score, rb, qb) under another rid and with a later `re`, which no scan reaches (it stops at
+    the other rid) and the removal of adjacent equal elements takes one of.  -> rows, [(raw place of a twin, of its copy)]"""
+    import introsort_model as im
+    t = im.budget(n)
+    n_tw = max(2, n // 10)
+    base = n - n_tw
+    spans = sorted(_strand_range(ix, c, rev) + (c,) for c in range(ix.n_seqs) for rev in (0, 1))
+    step = min(12000, sum(hi - lo - 2000 - LQ for lo, hi, c in spans) // (base + len(spans)))
+    assert step >= 1200
+    slots = [(c, p) for lo, hi, c in spans for p in range(lo + 1000, hi - 1000 - LQ - step // 3, step)]
+    assert len(slots) >= base
+    qb, qe = [(0, LQ), (5, 140), (30, 110), (0, 75)][int(rng.integers(4))]
+    ln = qe - qb
+    top = int(rng.integers(18 + t, min(ln - 8, 30 + t) + 1))
+    tail = sorted((int(v) for v in rng.choice(np.arange(19, top + 1), t, replace=False)), reverse=True)
+    vals = rng.choice(np.arange(top + 1, ln), int(rng.integers(2, 7)), replace=False)
+    score = [ln] + [int(v) for v in rng.choice(vals, base - 1 - t)] + tail
+    twin_at = set(int(k) for k in rng.choice(np.arange(1, base - t), n_tw, replace=False))
+    rows, twins = [], []
+    for j, s in enumerate(np.sort(rng.choice(len(slots), base, replace=False))):
+        c, p = slots[int(s)]
+        rb = p + int(rng.integers(0, step // 3))
+        rows.append((rb, rb + ln + int(rng.integers(-2, 3)), qb, qe, c, score[j]))
+        if j in twin_at:
+            twins.append((len(rows) - 1, len(rows)))
+            rows.append((rb, rows[-1][1] + 1 + int(rng.integers(0, 2)), qb, qe, (c + 1) % ix.n_seqs, score[j]))
+    return rows, twins
+
+
+def sorted_list(ix, family, n, s):
+    """list number s of a family and size -> a case, or None where the model turns it down: from 26 regions on a list counts only if
+    the sort it is built for hands a range of at least 17 to the comb sort, which swaps, and an insertion sort in the comb sort's
+    place would have changed the result — for sorted_re the regions the pass keeps, for sorted_score the relative order of a twin
+    pair.  Lists of 25 cannot spend the budget (can_run_out_of_depth): they are the edge and all count."""
+    k = ("sorted_re", "sorted_score").index(family)
+    rng = np.random.default_rng((SORTED_SEED, k, n, s))
+    rows, twins = (_sorted_re_rows(ix, rng, n), None) if k == 0 else _sorted_score_rows(ix, rng, n)
+    regs = _regs(rows)
+    if can_run_out_of_depth(n):
+        real = model_pass(regs)
+        st = real["second" if k else "first"]
+        if st.widest < 17 or not st.comb_swaps:
+            return None
+        mut = model_pass(regs, comb=(k == 1, k == 0))
+        if k == 0 and kept_rows(regs, mut["kept"]) == kept_rows(regs, real["kept"]):
+            return None
+        if k == 1 and (len(real["sorted"]) != n or twin_order(mut["sorted"], twins) == twin_order(real["sorted"], twins)):
+            return None
+    return dict(family=family, tag="n%d" % n, regs=regs, read=_read(rng), expect="taken", twins=twins)
+
+
+def find_sorted_seeds(ix, per_size=SORTED_PER_SIZE):
+    """the generation rule: per family and size the first per_size list numbers the model lets through -> what SORTED_SEEDS states"""
+    import itertools
+    found = {}
+    for family in ("sorted_re", "sorted_score"):
+        for n in SORTED_SIZES:
+            ok = (s for s in itertools.count() if sorted_list(ix, family, n, s) is not None)
+            found[family, n] = list(itertools.islice(ok, per_size))
+    return found
+
+
+def sorted_cases(ix):
+    """sorted_re and sorted_score: the lists SORTED_SEEDS names, SORTED_PER_SIZE per size and family, in the order of their
+    construction.  A list the model turns down on this index is an error, not a list left out."""
+    key = (tuple(ix.off), tuple(ix.len))
+    if key not in _SORTED:
+        cases = []
+        for n in SORTED_SIZES:
+            for family in ("sorted_re", "sorted_score"):
+                assert len(SORTED_SEEDS[family, n]) == SORTED_PER_SIZE
+                for s in SORTED_SEEDS[family, n]:
+                    cs = sorted_list(ix, family, n, s)
+                    assert cs is not None, (family, n, s, "the model turns this list down")
+                    cases.append(cs)
+        _SORTED[key] = cases
+    return _SORTED[key]
 
 
 def random_cases(ix, n_pairs, seed):

@@ -133,3 +133,32 @@ def test_dedup_stage_launch_shapes(stage):
             assert not tk and (status == eng.DD_HOST_MAXREG).all()
         else:
             assert tk
+
+
+@pytest.mark.parametrize("name", list(dc.OPTION_SETS))
+def test_dedup_wave_kernel_sorts_on_lists_that_reach_the_comb_sort(stage, name):
+    """dev_introsort where its depth budget runs out: the lists of dedup_cases.sorted_cases take the first (sorted_re) or the second
+    sort (sorted_score) of dedup_wave_kernel into ks_introsort's comb sort with equal keys in the range — the regions the pass keeps,
+    or the twin that stays, are the comb sort's order (tests/test_introsort_model.py).  Every list is taken and is the reference's
+    result in the reference's order.  The launch holds these lists alone, so a wavefront goes from one comb-sorted read to the next
+    over the same LDS arrays and frame stack; a second launch has them among the other families."""
+    eng = stage["eng"]
+    kw = dc.OPTION_SETS[name]
+    ix = dc.Index(stage["prefix"], stage["ref"].bns)
+    cases = dc.sorted_cases(ix)
+    want = dc.reference_results(stage["ref"], stage["ref"].opt(**kw), cases, True)
+    opt = eng.opt(**kw)
+    assert all(dc.SMALL < len(cs["regs"]) <= dc.CAP for cs in cases) and {cs["family"] for cs in cases} == {"sorted_re", "sorted_score"}
+    status, m, keep = run(stage, opt, cases)
+    for i, cs in enumerate(cases):
+        assert int(status[i]) == eng.DD_TAKEN, (name, cs["family"], cs["tag"], int(status[i]))
+    assert len(check(eng, cases, want, status, m, keep, name + " sorted only")) == len(cases)
+    _, others, want_o = the_set(stage, name)
+    idx = [i for i, cs in enumerate(others) if cs["family"] in ("same_span", "mixed", "far")][:120]
+    mixed, want_m = [], []
+    for k, cs in enumerate(cases):
+        mixed += [cs] + [others[i] for i in idx[3 * k % len(idx):][:2]]
+        want_m += [want[k]] + [want_o[i] for i in idx[3 * k % len(idx):][:2]]
+    status, m, keep = run(stage, opt, mixed)
+    taken = set(check(eng, mixed, want_m, status, m, keep, name + " sorted among others"))
+    assert all(i in taken for i, cs in enumerate(mixed) if cs["family"].startswith("sorted_"))

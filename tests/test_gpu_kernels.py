@@ -384,6 +384,32 @@ def test_chain_kernel_matches_the_reference_mem_chain(engine, genome):
     assert n_dev > 2800 and n_multi > 150 and n_big > 40 and n_heavy > 100 and n_heavy_l > 10
 
 
+@pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")
+def test_chain_heavy_kernel_sort_on_reads_that_reach_the_comb_sort(engine, genome):
+    """hv_introsort (chain_heavy_kernel<256 / 1024 / 4096>) where its depth budget runs out: the single-seed chains of
+    chain_cases.sorted_tail_chain_sets arrive at mem_chain_flt's sort in the order that ends in ks_introsort's comb sort, with equal
+    weights in the range (tests/test_introsort_model.py).  No read may be declined; every read's chains are the reference's own, in
+    its order, with every chain kept and with some dropped."""
+    import chain_cases as cc
+    ref = po.RefIndex(genome["prefix"])
+    l_pac = int(engine.bns.contents.l_pac)
+    n_seqs = int(engine.bns.contents.n_seqs)
+    offs = [int(engine.bns.contents.anns[k].offset) for k in range(n_seqs)] + [l_pac]
+    cases = cc.sorted_tail_chain_sets(np.random.default_rng(cc.SORTED_TAIL_SEED), cc.SORTED_TAIL_SIZES, l_pac, offs, n_seqs)
+    for kw in (dict(), dict(mask_level=0.3, drop_ratio=0.8)):
+        lens, seedsets, want = cc.reference_chains(ref, ref.opt(**kw), cases)
+        dev = engine.chains(engine.opt(**kw), lens, [0] * len(lens), seedsets, 0)
+        n_t = n_s = n_l = 0
+        for d, w, sd in zip(dev, want, seedsets):
+            assert d is not None, (kw, len(sd), "declined")
+            dd = [(c[0], c[5], c[6]) for c in d]
+            assert dd == w, (kw, "chain_heavy_kernel", len(sd), len(dd), len(w), [(a, b) for a, b in zip(dd, w) if a != b][:2])
+            n_t += 9 < len(sd) <= 255
+            n_s += 255 < len(sd) <= 1024
+            n_l += len(sd) > 1024
+        assert n_t >= 28 and n_s >= 4 and n_l >= 4, (n_t, n_s, n_l)
+
+
 def _pack2bit(ref):
     l_pac = len(ref)
     pac = np.zeros(l_pac // 4 + 1, dtype=np.uint8)

@@ -43,3 +43,27 @@ def test_host_chain_filter_on_reads_of_high_copy_repeats(genome):
         for h, w, sd in zip(host, want, seedsets):
             assert [(c[0], c[5], c[6]) for c in h] == w, kw
         assert max(len(sd) for sd in seedsets) > 500 and max(len(w) for w in want) >= 30   # hundreds of chains in, the cap of max_chain_extend out
+
+
+@pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")
+def test_host_chain_sort_on_reads_that_reach_the_comb_sort(genome):
+    """Chains that arrive at mem_chain_flt's sort in the order that spends ks_introsort's depth budget (chain_cases.sorted_tail_chain_sets;
+    tests/test_introsort_model.py shows that they do): the order of equal weights is the comb sort's.  Under the default options every
+    chain comes back; under the second set some are dropped and the kept ones must still stand in the reference's order."""
+    from mpibwa_amd import api
+    import chain_cases as cc
+    eng = api.Engine(genome["prefix"], upload=False)
+    ref = po.RefIndex(genome["prefix"])
+    l_pac = int(eng.bns.contents.l_pac)
+    n_seqs = int(eng.bns.contents.n_seqs)
+    offs = [int(eng.bns.contents.anns[k].offset) for k in range(n_seqs)] + [l_pac]
+    cases = cc.sorted_tail_chain_sets(np.random.default_rng(cc.SORTED_TAIL_SEED), cc.SORTED_TAIL_SIZES, l_pac, offs, n_seqs)
+    for kw in (dict(), dict(mask_level=0.3, drop_ratio=0.8)):
+        lens, seedsets, want = cc.reference_chains(ref, ref.opt(**kw), cases)
+        host = eng.chains(eng.opt(**kw), lens, [0] * len(lens), seedsets, 1)
+        n_all = 0
+        for h, w, sd in zip(host, want, seedsets):
+            assert [(c[0], c[5], c[6]) for c in h] == w, (kw, len(sd), len(w))
+            n_all += len(w) == len(sd)
+        print(kw, "reads", len(want), "with every chain kept", n_all)
+        assert n_all == (len(cases) if not kw else 0), (kw, n_all)

@@ -280,6 +280,27 @@ def test_host_dedup_patch_and_single_end_records_match_the_reference(repeat_geno
     assert n_xa > 20 or flag & abi.MEM_F_ALL, n_xa   # (-a prints the secondary hits as lines of their own instead of XA)
 
 
+@pytest.mark.skipif(not po.ref_available(), reason="oracle/_ref/libbwaref.so not present")
+def test_host_sort_dedup_patch_on_lists_that_reach_the_comb_sort(genome):
+    """The host's mem_sort_dedup_patch (host_regs.cpp: both sorts are sortutil.h's ks_introsort) on the lists of
+    dedup_cases.sorted_cases, which take the first or the second sort into the comb sort with equal keys in the range
+    (tests/test_introsort_model.py), against the reference's own, field for field, under the option sets of the stage test."""
+    import dedup_cases as dc
+    from mpibwa_amd import api
+    lib = api.load_library()
+    ref = po.RefIndex(genome["prefix"])
+    eng = api.Engine(genome["prefix"], upload=False)
+    cases = dc.sorted_cases(dc.Index(genome["prefix"], ref.bns))
+    for name, kw in dc.OPTION_SETS.items():
+        want = dc.reference_results(ref, ref.opt(**kw), cases, True)
+        opt = eng.opt(**kw)
+        for cs, w in zip(cases, want):
+            mine = np.array(cs["regs"], dtype=po.ALNREG_DT, copy=True)
+            sq = np.array(cs["read"], dtype=np.uint8, copy=True)
+            m = lib.mi355x_host_sort_dedup_patch(opt, ref.bns, C.cast(ref.pac, C.c_void_p), sq.ctypes.data, mine.ctypes.data, len(mine))
+            assert dc.same_lists(mine[:m], w), (name, cs["family"], cs["tag"], m, len(w))
+
+
 def test_host_pestat_matches_the_reference_mem_pestat(repeat_genome, capfd):
     """mem_pestat (src/bwamem_pair.c:46-109) of the library's host path — the counting form (max_ins up to 2^20) and the sorting form, on one
     and on several threads — against the reference's own on the regions of its mem_align1_core: libraries with one, two and four live
