@@ -12,7 +12,8 @@
 //  * the rest stays flagged (n_chains < 0) and takes the host path (host_chain.cpp): more than 4 096 seeds, two chains at one
 //    position (where the shape of the reference's tree shows), or long enough for mem_flt_chained_seeds to act (l_query >= ~700 bp).
 //
-// The unstable sort of mem_chain_flt is ks_introsort (src/ksort.h:176-226) statement by statement (ck_introsort).
+// The unstable sort of mem_chain_flt is ks_introsort (src/ksort.h:176-226) statement by statement (sortutil.h: its small form for the
+// at most 9 chains of a lane's read, the full sort with private frames in chain_heavy_kernel).
 // Floating-point compares (mask_level, drop_ratio, frac_rep) are IEEE single precision in the same expression shapes as
 // the reference (no contraction, no fast-math).
 //
@@ -28,6 +29,7 @@
 #include <vector>
 #include "hip_util.h"
 #include "device.h"
+#include "sortutil.h"
 
 namespace mbw {
 
@@ -100,81 +102,6 @@ __device__ __forceinline__ int ck_pos2rid(const i64 *__restrict__ ann_off, int n
 	return mid;
 }
 __device__ __forceinline__ i64 ck_depos(i64 l_pac, i64 pos) { return pos >= l_pac ? (l_pac << 1) - 1 - pos : pos; }
-
-// the unstable sort of mem_chain_flt for any n: ks_introsort (src/ksort.h:176-226) on the chain ids in ord[0, n), "less" =
-// heavier first — median-of-three quicksort with an explicit stack, ranges of <= 16 left to one final insertion sort, comb
-// sort when the depth budget runs out (sortutil.h is the host's statement of the same)
-template <int MAXCH, class LT>
-__device__ __forceinline__ void ck_insertion(const StoreLds<MAXCH> &L, int s, int t, LT lt)   // [s, t)
-{
-	for (int i = s + 1; i < t; ++i)
-		for (int j = i; j > s && lt(L.ord(j), L.ord(j - 1)); --j) { const uint8_t x = L.ord(j); L.ord(j) = L.ord(j - 1); L.ord(j - 1) = x; }
-}
-template <int MAXCH, class LT>
-__device__ __forceinline__ void ck_comb(const StoreLds<MAXCH> &L, int a, int n, LT lt)
-{
-	const double shrink = 1.2473309501039786540366528676643;
-	int gap = n;
-	bool swapped;
-	do {
-		if (gap > 2) {
-			gap = (int)((double)gap / shrink);
-			if (gap == 9 || gap == 10) gap = 11;
-		}
-		swapped = false;
-		for (int i = a; i < a + n - gap; ++i) {
-			const int j = i + gap;
-			if (lt(L.ord(j), L.ord(i))) { const uint8_t x = L.ord(i); L.ord(i) = L.ord(j); L.ord(j) = x; swapped = true; }
-		}
-	} while (swapped || gap > 2);
-	if (gap != 1) ck_insertion(L, a, a + n, lt);
-}
-template <int MAXCH, class LT>
-__device__ __forceinline__ void ck_introsort(const StoreLds<MAXCH> &L, int n, LT lt)
-{
-	if (n < 2) return;
-	if (n == 2) {
-		if (lt(L.ord(1), L.ord(0))) { const uint8_t x = L.ord(0); L.ord(0) = L.ord(1); L.ord(1) = x; }
-		return;
-	}
-	int d = 2;
-	while ((1 << d) < n) ++d;
-	int fs[16], ft[16], fd[16], sp = 0;   // only ranges of more than 16 elements are pushed, the smaller side is worked first
-	int s = 0, t = n - 1;
-	d <<= 1;
-	for (;;) {
-		if (s < t) {
-			if (--d == 0) {
-				ck_comb(L, s, t - s + 1, lt);
-				t = s;
-				continue;
-			}
-			int i = s, j = t, k = i + ((j - i) >> 1) + 1;
-			if (lt(L.ord(k), L.ord(i))) { if (lt(L.ord(k), L.ord(j))) k = j; }
-			else k = lt(L.ord(j), L.ord(i)) ? i : j;
-			const uint8_t pivot = L.ord(k);
-			if (k != t) { const uint8_t x = L.ord(k); L.ord(k) = L.ord(t); L.ord(t) = x; }
-			for (;;) {
-				do ++i; while (lt(L.ord(i), pivot));
-				do --j; while (i <= j && lt(pivot, L.ord(j)));
-				if (j <= i) break;
-				const uint8_t x = L.ord(i); L.ord(i) = L.ord(j); L.ord(j) = x;
-			}
-			{ const uint8_t x = L.ord(i); L.ord(i) = L.ord(t); L.ord(t) = x; }
-			if (i - s > t - i) {
-				if (i - s > 16) { fs[sp] = s; ft[sp] = i - 1; fd[sp] = d; ++sp; }
-				s = t - i > 16 ? i + 1 : t;
-			} else {
-				if (t - i > 16) { fs[sp] = i + 1; ft[sp] = t; fd[sp] = d; ++sp; }
-				t = i - s > 16 ? i - 1 : s;
-			}
-		} else {
-			if (sp == 0) { ck_insertion(L, 0, n, lt); return; }
-			--sp;
-			s = fs[sp]; t = ft[sp]; d = fd[sp];
-		}
-	}
-}
 
 // mem_chain + mem_chain_flt + emission for ONE read (one lane).  Returns the number of kept chains, or -1: host path.
 template <int MAXCH>
@@ -284,7 +211,10 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 		L.ord(n++) = (uint8_t)id;
 	}
 	if (n == 0) return 0;
-	ck_introsort(L, n, [&](int a_id, int b_id) -> bool { return (int)L.f(F_W, a_id) > (int)L.f(F_W, b_id); });   // "less" of the descending sort
+	// the unstable sort (:341), "less" = heavier first; n <= MAXCH chains (MapArray::put refuses one more): ks_introsort's small form
+	static_assert(MAXCH <= 16, "ks_small_introsort_at is ks_introsort for at most 16 elements");
+	ks_small_introsort_at(n, [&](int k) -> uint8_t & { return L.ord(k); },
+	                      [&](int a_id, int b_id) -> bool { return (int)L.f(F_W, a_id) > (int)L.f(F_W, b_id); });
 	// pairwise overlap marking; tmp holds the positions (in ord) of the chains kept so far
 	auto BEG = [&](int t) -> int { return (int)L.f(F_FIRST_Q, L.ord(t)); };
 	auto END = [&](int t) -> int { const int id = L.ord(t); return (int)L.f(F_LAST_Q, id) + (int)L.f(F_LAST_LEN, id); };
@@ -464,75 +394,15 @@ struct HvStore {   // what only the later phases read (HBM, the wave's slice): c
 	uint32_t *last_off;
 	uint16_t *first_q, *last_q, *last_len, *tail, *nmem;
 };
-// ks_introsort (src/ksort.h:176-226) of n words, "less" = the heavier chain first (the weight is the word's upper half)
+// "less" of mem_chain_flt's sort over the sort words: the heavier chain first (the weight is the word's upper half)
 __device__ __forceinline__ bool hv_lt(uint32_t a, uint32_t b) { return (a >> 16) > (b >> 16); }
-__device__ __forceinline__ void hv_insertion(uint32_t *a, int s, int t)
+#define HV_FRAMES 32   // private frame arrays of the sort, in registers
+// (a function of its own with the pointer by value: with the arrays in the kernel's body and `skey` captured by reference the register
+// allocator put all 96 frame ints into accumulator registers instead of 32)
+__device__ __forceinline__ void hv_sort(uint32_t *a, int n)
 {
-	for (int i = s + 1; i < t; ++i)
-		for (int j = i; j > s && hv_lt(a[j], a[j - 1]); --j) { const uint32_t x = a[j]; a[j] = a[j - 1]; a[j - 1] = x; }
-}
-__device__ __forceinline__ void hv_comb(uint32_t *a, int s0, int n)
-{
-	const double shrink = 1.2473309501039786540366528676643;
-	int gap = n;
-	bool swapped;
-	do {
-		if (gap > 2) {
-			gap = (int)((double)gap / shrink);
-			if (gap == 9 || gap == 10) gap = 11;
-		}
-		swapped = false;
-		for (int i = s0; i < s0 + n - gap; ++i) {
-			const int j = i + gap;
-			if (hv_lt(a[j], a[i])) { const uint32_t x = a[i]; a[i] = a[j]; a[j] = x; swapped = true; }
-		}
-	} while (swapped || gap > 2);
-	if (gap != 1) hv_insertion(a, s0, s0 + n);
-}
-__device__ __forceinline__ void hv_introsort(uint32_t *a, int n)
-{
-	if (n < 2) return;
-	if (n == 2) {
-		if (hv_lt(a[1], a[0])) { const uint32_t x = a[0]; a[0] = a[1]; a[1] = x; }
-		return;
-	}
-	int d = 2;
-	while ((1 << d) < n) ++d;
-	int fs[32], ft[32], fd[32], sp = 0;
-	int s = 0, t = n - 1;
-	d <<= 1;
-	for (;;) {
-		if (s < t) {
-			if (--d == 0) {
-				hv_comb(a, s, t - s + 1);
-				t = s;
-				continue;
-			}
-			int i = s, j = t, k = i + ((j - i) >> 1) + 1;
-			if (hv_lt(a[k], a[i])) { if (hv_lt(a[k], a[j])) k = j; }
-			else k = hv_lt(a[j], a[i]) ? i : j;
-			const uint32_t pivot = a[k];
-			if (k != t) { const uint32_t x = a[k]; a[k] = a[t]; a[t] = x; }
-			for (;;) {
-				do ++i; while (hv_lt(a[i], pivot));
-				do --j; while (i <= j && hv_lt(pivot, a[j]));
-				if (j <= i) break;
-				const uint32_t x = a[i]; a[i] = a[j]; a[j] = x;
-			}
-			{ const uint32_t x = a[i]; a[i] = a[t]; a[t] = x; }
-			if (i - s > t - i) {
-				if (i - s > 16) { fs[sp] = s; ft[sp] = i - 1; fd[sp] = d; ++sp; }
-				s = t - i > 16 ? i + 1 : t;
-			} else {
-				if (t - i > 16) { fs[sp] = i + 1; ft[sp] = t; fd[sp] = d; ++sp; }
-				t = i - s > 16 ? i - 1 : s;
-			}
-		} else {
-			if (sp == 0) { hv_insertion(a, 0, n); return; }
-			--sp;
-			s = fs[sp]; t = ft[sp]; d = fd[sp];
-		}
-	}
+	int fs[HV_FRAMES], ft[HV_FRAMES], fd[HV_FRAMES];
+	ks_introsort_at(n, [a](int k) -> uint32_t & { return a[k]; }, KsFramesAt{fs, ft, fd}, hv_lt);
 }
 __device__ __forceinline__ void hv_sync()
 {
@@ -725,7 +595,8 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 		hv_sync();
 		if (!ok) { if (lane == 0) n_chains[rd] = -2; continue; }
 		if (n == 0) { if (lane == 0) n_chains[rd] = 0; continue; }
-		if (lane == 0) hv_introsort(skey, n);
+		static_assert((unsigned long long)CAP <= 16ull << HV_FRAMES, "ks_introsort_at: n <= 16 << FRAMES");
+		if (lane == 0) hv_sort(skey, n);
 		hv_sync();
 		// ---------------- mem_chain_flt's pairwise pass: 64 kept chains per step ----------------
 		for (int t0 = 0; t0 < n; t0 += 64) {

@@ -8,8 +8,8 @@
 //  * reads with PR_MAXREG + 1 .. DD_MAXREG regions: a read per wavefront over that list (dedup_wave_kernel).  What the pass reads of a
 //    region lives in LDS as structure-of-arrays at the region's raw place — rb, re (8 bytes each), qb, qe, rid, score (4 each), an alive
 //    byte — with a 16-bit order array: 17.7 KB per workgroup of one wavefront, 9 workgroups per CU by LDS.
-//      - both sorts are ks_introsort on the order array (dev_introsort.cuh), lane 0: its order of equal keys shows in the result (equal
-//        `re` in the first sort; which of two (score, rb, qb)-equal hits is dropped after the second);
+//      - both sorts are ks_introsort on the order array (sortutil.h, its frame stack in LDS), lane 0: its order of equal keys shows in
+//        the result (equal `re` in the first sort; which of two (score, rb, qb)-equal hits is dropped after the second);
 //      - the scan is serial in i and lane-parallel in j.  For p = a[i] the inner loop of :451-474 visits the contiguous run
 //        J = {j < i : same rid, p.rb < a[j].re + max_chain_gap}, ending at the first j that fails whatever the alive marks say; p is
 //        alive at its turn (only earlier elements are ever marked) and unchanged until it dies.  So, a lane per j: R[j] = alive and
@@ -24,9 +24,11 @@
 #include <hip/hip_runtime.h>
 #include "hip_util.h"
 #include "pair_common.cuh"
-#include "dev_introsort.cuh"
+#include "sortutil.h"
 
 namespace mbw {
+
+#define DSORT_FRAMES 16
 
 extern "C" int mi355x_dedup_maxreg(void) { return DD_MAXREG; }
 
@@ -99,7 +101,10 @@ dedup_wave_kernel(DedupParams D, const int *__restrict__ list, const unsigned in
 	__shared__ int s_qb[DD_MAXREG], s_qe[DD_MAXREG], s_rid[DD_MAXREG], s_sc[DD_MAXREG];
 	__shared__ unsigned short s_ord[DD_MAXREG];
 	__shared__ unsigned char s_alive[DD_MAXREG];
-	__shared__ int s_stk[3 * DSORT_FRAMES];
+	__shared__ int s_stk[3 * DSORT_FRAMES];   // the sorts' frames, 16 per array, in LDS as before (private arrays were not tried in this kernel)
+	static_assert(DD_MAXREG <= 16 << DSORT_FRAMES, "ks_introsort_at: n <= 16 << FRAMES");
+	const KsFramesAt frames = {s_stk, s_stk + DSORT_FRAMES, s_stk + 2 * DSORT_FRAMES};
+	auto ord_at = [&](int k) -> unsigned short & { return s_ord[k]; };
 	const int lane = threadIdx.x;
 	const unsigned long long below = (1ull << lane) - 1;
 	unsigned int cnt = *list_n;
@@ -117,7 +122,7 @@ dedup_wave_kernel(DedupParams D, const int *__restrict__ list, const unsigned in
 			s_ord[k] = (unsigned short)k;
 		}
 		__syncthreads();
-		if (lane == 0) dev_introsort(s_ord, n, s_stk, [&](int x, int y) { return s_re[x] < s_re[y]; });   // by END position
+		if (lane == 0) ks_introsort_at(n, ord_at, frames, [&](int x, int y) { return s_re[x] < s_re[y]; });   // by END position
 		__syncthreads();
 		bool declined = false;
 		for (int i = 1; i < n && !declined; ++i) {
@@ -168,7 +173,7 @@ dedup_wave_kernel(DedupParams D, const int *__restrict__ list, const unsigned in
 		}
 		__syncthreads();
 		if (lane == 0)
-			dev_introsort(s_ord, m1, s_stk, [&](int x, int y) {   // by score, then position
+			ks_introsort_at(m1, ord_at, frames, [&](int x, int y) {   // by score, then position
 				return s_sc[x] > s_sc[y] || (s_sc[x] == s_sc[y] && (s_rb[x] < s_rb[y] || (s_rb[x] == s_rb[y] && s_qb[x] < s_qb[y])));
 			});
 		__syncthreads();

@@ -1,6 +1,6 @@
 // pair_common.cuh — device helpers shared by the pairing kernel (pair_kernel.hip) and the single-end decision kernel
 // (se_kernel.hip): the reference's region clean-up, primary marking and single-end MAPQ for the short region lists both look at.
-//   mem_sort_dedup_patch  src/bwamem.c:437-489   (dedup_small, with ks_introsort's order for up to 16 elements: small_introsort)
+//   mem_sort_dedup_patch  src/bwamem.c:437-489   (dedup_small, with ks_introsort's order for up to 16 elements: sortutil.h)
 //   mem_mark_primary_se   src/bwamem.c:493-569   (mark_primary, reads without ALT hits; hash_64: src/utils.h:98-109)
 //   mem_approx_mapq_se    src/bwamem.c:952-976   (mapq_se; the two short-list kernels pass csub = 0)
 //   infer_bw              src/bwamem.c:792-800   (the band of mem_reg2aln's global alignment)
@@ -9,6 +9,7 @@
 #define MBW_PAIR_COMMON_CUH
 #include <hip/hip_runtime.h>
 #include "device.h"
+#include "sortutil.h"
 
 namespace mbw {
 
@@ -18,42 +19,15 @@ typedef unsigned long long u64;
 
 // mem_sort_dedup_patch (src/bwamem.c:437-489) for n <= PR_MAXREG regions of one read.  Returns the number of regions left, or -1 when two regions pass the
 // cheap tests of mem_patch_reg (:411-423) and the reference would go on to align across them (the host's case).
-// ks_introsort (src/ksort.h:176-226) for 3 <= n <= 16 is ONE median-of-three partition of the whole range followed by an
-// insertion sort (no sub-range is long enough to be pushed); its order of equal keys is that of these very swaps.  `o` holds
-// the element numbers, lt compares two of them.
-template <class LT>
-__device__ __forceinline__ void small_introsort(int n, int *o, LT lt)
-{
-	if (n < 2) return;
-	if (n == 2) {
-		if (lt(o[1], o[0])) { const int x = o[0]; o[0] = o[1]; o[1] = x; }
-		return;
-	}
-	{
-		const int t = n - 1;
-		int i = 0, j = t, k = i + ((j - i) >> 1) + 1;
-		if (lt(o[k], o[i])) { if (lt(o[k], o[j])) k = j; }
-		else k = lt(o[j], o[i]) ? i : j;
-		const int pivot = o[k];
-		if (k != t) { const int x = o[k]; o[k] = o[t]; o[t] = x; }
-		for (;;) {
-			do ++i; while (lt(o[i], pivot));
-			do --j; while (i <= j && lt(pivot, o[j]));
-			if (j <= i) break;
-			const int x = o[i]; o[i] = o[j]; o[j] = x;
-		}
-		const int x = o[i]; o[i] = o[t]; o[t] = x;
-	}
-	for (int i = 1; i < n; ++i)
-		for (int j = i; j > 0 && lt(o[j], o[j - 1]); --j) { const int x = o[j]; o[j] = o[j - 1]; o[j - 1] = x; }
-}
+// The sorts are ks_introsort's small form (sortutil.h) over an order array: `o` holds the element numbers, lt compares two of them.
+static_assert(PR_MAXREG <= 16, "ks_small_introsort_at is ks_introsort for at most 16 elements");
 template <class LT>
 __device__ __forceinline__ void sort_regs(int n, DevReg *a, LT lt)
 {
 	int o[PR_MAXREG];
 	DevReg t[PR_MAXREG];
 	for (int i = 0; i < n; ++i) { o[i] = i; t[i] = a[i]; }
-	small_introsort(n, o, [&](int x, int y) { return lt(t[x], t[y]); });
+	ks_small_introsort_at(n, [&](int k) -> int & { return o[k]; }, [&](int x, int y) { return lt(t[x], t[y]); });
 	for (int i = 0; i < n; ++i) a[i] = t[o[i]];
 }
 
@@ -159,7 +133,7 @@ __device__ __forceinline__ void mark_primary(const PairParams &P, PReg *a, int n
 		int o[PR_MAXREG];
 		PReg t[PR_MAXREG];
 		for (int i = 0; i < n; ++i) { o[i] = i; t[i] = a[i]; }
-		small_introsort(n, o, [&](int x, int y) { return t[x].d.score > t[y].d.score || (t[x].d.score == t[y].d.score && t[x].hash < t[y].hash); });
+		ks_small_introsort_at(n, [&](int k) -> int & { return o[k]; }, [&](int x, int y) { return t[x].d.score > t[y].d.score || (t[x].d.score == t[y].d.score && t[x].hash < t[y].hash); });
 		for (int i = 0; i < n; ++i) a[i] = t[o[i]];
 	}
 	int tmp = P.a + P.b;

@@ -70,10 +70,11 @@ __device__ __forceinline__ bool pair_lt(const Pair64 &a, const Pair64 &b) { retu
 template <int CAP>
 __device__ __forceinline__ void sort_pairs(int n, Pair64 *v)
 {
+	static_assert(CAP <= 16, "ks_small_introsort_at is ks_introsort for at most 16 elements");
 	int o[CAP];
 	Pair64 t[CAP];
 	for (int i = 0; i < n; ++i) { o[i] = i; t[i] = v[i]; }
-	small_introsort(n, o, [&](int x, int y) { return pair_lt(t[x], t[y]); });
+	ks_small_introsort_at(n, [&](int k) -> int & { return o[k]; }, [&](int x, int y) { return pair_lt(t[x], t[y]); });
 	for (int i = 0; i < n; ++i) v[i] = t[o[i]];
 }
 
@@ -167,7 +168,7 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		}
 		y[v[i].y & 3] = i;
 	}
-	if (nu > PR_MAXPAIR) { status[k] = 3; return; }   // (small_introsort: at most 16 elements)
+	if (nu > PR_MAXPAIR) { status[k] = 3; return; }   // (ks_small_introsort_at: at most 16 elements)
 	if (nu == 0) { status[k] = 8; return; }   // no pair in a proper orientation and distance: the host reports the ends independently
 	int tmp = P.a + P.b;
 	tmp = tmp > P.o_del + P.e_del ? tmp : P.o_del + P.e_del;

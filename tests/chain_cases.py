@@ -159,3 +159,53 @@ def reference_chains(ref, ropt, cases):
             exp.append((rid, fb, [sd[i] for i in order]))
         want.append(exp)
     return lens, seedsets, want
+
+
+TIED_SMALL_SEED = 2611
+TIED_SMALL_PER_LAUNCH = 32
+# (seeds, chains) a read may have for each of the three lane-per-read launches: chain_kernel<16, 4>, <64, 9>, <255, 9>
+TIED_SMALL_LAUNCHES = (((3, 16), (3, 4)), ((17, 64), (3, 9)), ((65, 255), (3, 9)))
+
+
+def tied_small_launch(n_seeds, n_chains):
+    """which of the three launches takes a read with so many seeds and chains: the first whose UPPER bounds fit, as the kernels decide
+    it (a read of 5 seeds and 6 chains is the second launch's); None: none of them"""
+    for k, ((_, s_hi), (_, c_hi)) in enumerate(TIED_SMALL_LAUNCHES):
+        if n_seeds <= s_hi and n_chains <= c_hi:
+            return k
+    return None
+
+
+def tied_small_chain_sets(rng, l_pac, offs, n_seqs, per_launch=TIED_SMALL_PER_LAUNCH):
+    """Reads whose 3-9 chains reach mem_chain_flt's sort with TIES among their weights, not in sorted order: the sort of the one-node
+    path (chain_read: ks_introsort's small form).  A chain is m co-linear seeds (q0 + j, length L) at positions p + q0 + j, j < m: each
+    merges into the chain the first one opened, none is contained in it, and the chain weighs L + m - 1 on the query and on the
+    reference; m brings the read's seed count into its launch's range.  Chains lie 500 or more apart in ascending position on one
+    strand of one contig (so the sort meets them in the order built), weights are drawn from 2-3 values in 76...150 (all within the
+    default drop_ratio of one another; every seed at least min_seed_len long).  per_launch reads for each of TIED_SMALL_LAUNCHES.
+    -> ([(lq, [(qb, qe, hits)])], [(launch, weights in the order the sort meets them)])"""
+    lq = SORTED_TAIL_LQ
+    spans = [(offs[k] + 500, offs[k + 1] - 500 - lq) for k in range(n_seqs)]
+    cases, meta = [], []
+    for launch, ((s_lo, s_hi), (c_lo, c_hi)) in enumerate(TIED_SMALL_LAUNCHES):
+        for it in range(per_launch):
+            n = int(rng.integers(c_lo, c_hi + 1))
+            ns = int(rng.integers(max(s_lo, n), s_hi + 1))
+            m = [ns // n + (1 if c < ns % n else 0) for c in range(n)]            # seeds per chain, at most 85
+            while True:   # (every seed keeps min_seed_len = 19 bases: L = weight - m + 1)
+                vals = rng.choice(np.arange(max(76, m[0] + 18), 151), int(rng.integers(2, 4)), replace=False)
+                w = [int(v) for v in rng.choice(vals, n)]
+                if len(set(w)) < n and w != sorted(w, reverse=True):
+                    break
+            lo, hi = spans[int(rng.integers(0, len(spans)))]
+            first = int(rng.integers(lo, hi - 600 * n))
+            ivs = {}
+            for c in range(n):
+                p = first + 600 * c + int(rng.integers(0, 100))
+                L = w[c] - m[c] + 1
+                q0 = int(rng.integers(0, lq - w[c] + 1))
+                for j in range(m[c]):
+                    ivs.setdefault((q0 + j, q0 + j + L), []).append(p + q0 + j)
+            cases.append((lq, [(qb, qe, sorted(h)) for (qb, qe), h in ivs.items()]))
+            meta.append((launch, w))
+    return cases, meta

@@ -1,4 +1,4 @@
-"""ks_introsort as mpibwa_amd/csrc/sortutil.h states it, in Python, over an ORDER array: o holds element numbers, less(x, y) compares
+"""ks_introsort as mpibwa_amd/csrc/sortutil.h states it (ks_introsort_at: the one statement the host and the kernels share), in Python, over an ORDER array: o holds element numbers, less(x, y) compares
 two of them.  It reports what no compiled restatement can be asked: the ranges handed to the comb sort, the swaps the comb sort made
 and the deepest frame stack.  `comb=False` is the variant whose fallback is an insertion sort of the range in hand — what a restatement
 that forgot the comb sort would do.  Used to build and to count cases (tests/chain_cases.py, tests/dedup_cases.py,

@@ -137,7 +137,7 @@ def test_dedup_stage_launch_shapes(stage):
 
 @pytest.mark.parametrize("name", list(dc.OPTION_SETS))
 def test_dedup_wave_kernel_sorts_on_lists_that_reach_the_comb_sort(stage, name):
-    """dev_introsort where its depth budget runs out: the lists of dedup_cases.sorted_cases take the first (sorted_re) or the second
+    """ks_introsort_at in dedup_wave_kernel where its depth budget runs out: the lists of dedup_cases.sorted_cases take the first (sorted_re) or the second
     sort (sorted_score) of dedup_wave_kernel into ks_introsort's comb sort with equal keys in the range — the regions the pass keeps,
     or the twin that stays, are the comb sort's order (tests/test_introsort_model.py).  Every list is taken and is the reference's
     result in the reference's order.  The launch holds these lists alone, so a wavefront goes from one comb-sorted read to the next

@@ -386,7 +386,7 @@ def test_chain_kernel_matches_the_reference_mem_chain(engine, genome):
 
 @pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")
 def test_chain_heavy_kernel_sort_on_reads_that_reach_the_comb_sort(engine, genome):
-    """hv_introsort (chain_heavy_kernel<256 / 1024 / 4096>) where its depth budget runs out: the single-seed chains of
+    """ks_introsort_at in chain_heavy_kernel<256 / 1024 / 4096> where its depth budget runs out: the single-seed chains of
     chain_cases.sorted_tail_chain_sets arrive at mem_chain_flt's sort in the order that ends in ks_introsort's comb sort, with equal
     weights in the range (tests/test_introsort_model.py).  No read may be declined; every read's chains are the reference's own, in
     its order, with every chain kept and with some dropped."""
@@ -408,6 +408,32 @@ def test_chain_heavy_kernel_sort_on_reads_that_reach_the_comb_sort(engine, genom
             n_s += 255 < len(sd) <= 1024
             n_l += len(sd) > 1024
         assert n_t >= 28 and n_s >= 4 and n_l >= 4, (n_t, n_s, n_l)
+
+
+@pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")
+def test_chain_kernel_sort_on_tied_weights_of_3_to_9_chains(engine, genome):
+    """ks_small_introsort_at in chain_read (chain_kernel<16, 4>, <64, 9>, <255, 9>): the reads of chain_cases.tied_small_chain_sets reach
+    mem_chain_flt's sort with 3-9 chains, ties among the weights and not in sorted order (tests/test_introsort_model.py counts them, and
+    the reads on which a stable sort would differ).  No read may be declined; every read's chains are the reference's own, field for
+    field and in its order, on the device and on the host."""
+    import chain_cases as cc
+    ref = po.RefIndex(genome["prefix"])
+    l_pac = int(engine.bns.contents.l_pac)
+    n_seqs = int(engine.bns.contents.n_seqs)
+    offs = [int(engine.bns.contents.anns[k].offset) for k in range(n_seqs)] + [l_pac]
+    cases, meta = cc.tied_small_chain_sets(np.random.default_rng(cc.TIED_SMALL_SEED), l_pac, offs, n_seqs)
+    lens, seedsets, want = cc.reference_chains(ref, ref.opt(), cases)
+    dev = engine.chains(engine.opt(), lens, [0] * len(lens), seedsets, 0)
+    host = engine.chains(engine.opt(), lens, [0] * len(lens), seedsets, 1)
+    n_launch = [0, 0, 0]
+    for (launch, wt), d, h, w, sd in zip(meta, dev, host, want, seedsets):
+        assert d is not None, (launch, len(sd), "declined")
+        assert len(w) == len(wt) and cc.tied_small_launch(len(sd), len(w)) == launch
+        assert [(c[0], c[5], c[6]) for c in h] == w, ("host path", launch, len(sd))
+        dd = [(c[0], c[5], c[6]) for c in d]
+        assert dd == w, ("chain_kernel", launch, len(sd), wt, [(a, b) for a, b in zip(dd, w) if a != b][:2])
+        n_launch[launch] += 1
+    assert n_launch == [cc.TIED_SMALL_PER_LAUNCH] * 3, n_launch
 
 
 def _pack2bit(ref):

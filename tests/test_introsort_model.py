@@ -61,6 +61,32 @@ def test_model_gives_the_reference_order_and_sorted_tail_reaches_the_comb_sort(g
     assert all(sizes.count(n) == (4 if n <= 255 else 2) for n in cc.SORTED_TAIL_SIZES)
 
 
+@pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")
+def test_tied_small_family_reaches_the_one_node_sort_with_ties(genome):
+    """chain_cases.tied_small_chain_sets, the family of the sort in chain_read (ks_small_introsort_at over a lane's 3-9 chains): every
+    read has the seed and chain counts of the launch it is built for (none is declined for size), the reference returns all of its
+    chains with the weights built, in the model's order; per launch at least 8 reads whose sort sees 3 or more chains with a tie, and
+    at least one on which a stable sort of the same weights gives another order than ks_introsort."""
+    ref = po.RefIndex(genome["prefix"])
+    l_pac, offs, n_seqs = _geometry(ref)
+    cases, meta = cc.tied_small_chain_sets(np.random.default_rng(cc.TIED_SMALL_SEED), l_pac, offs, n_seqs)
+    lens, seedsets, want = cc.reference_chains(ref, ref.opt(), cases)
+    tied, unstable = [0, 0, 0], [0, 0, 0]
+    for (launch, w), (lq, ivs), sd, exp in zip(meta, cases, seedsets, want):
+        (s_lo, s_hi), (c_lo, c_hi) = cc.TIED_SMALL_LAUNCHES[launch]
+        assert s_lo <= len(sd) <= s_hi and c_lo <= len(w) <= c_hi and cc.tied_small_launch(len(sd), len(w)) == launch, (launch, len(sd), len(w))
+        raw = po.ref_chains(ref.opt(), ref.bns, lq, sorted(ivs, key=lambda t: (t[0] << 32) | t[1]))
+        o, st = im.sort_keys(w, HEAVIER)
+        assert not st.comb_ranges and st.max_frames == 0
+        pos = sorted(min(rb for rb, _, _ in c[5]) for c in raw)
+        assert len(raw) == len(exp) == len(w) and sum(len(c[5]) for c in raw) == len(sd), (launch, len(raw), len(w))
+        assert [c[1] for c in raw] == [w[k] for k in o] and [pos.index(min(rb for rb, _, _ in c[5])) for c in raw] == o, (launch, w, "the model's order is not the reference's")
+        tied[launch] += len(w) >= 3 and len(set(w)) < len(w) and w != sorted(w, reverse=True)
+        unstable[launch] += o != sorted(range(len(w)), key=lambda i: -w[i])
+    print("tied_small: reads with a tie per launch", tied, "reads where a stable sort differs", unstable)
+    assert min(tied) >= 8 and min(unstable) >= 1, (tied, unstable)
+
+
 @pytest.mark.skipif(not po.ref_available(), reason="oracle/_ref/libbwaref.so not present")
 def test_sorted_region_families_reach_the_comb_sort(genome):
     ref = po.RefIndex(genome["prefix"])
