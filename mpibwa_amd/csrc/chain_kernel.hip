@@ -8,12 +8,12 @@
 //    hits equal keys returns the first), state in LDS (StoreLds).  Three launches with growing LDS footprints
 //    (chain_kernel<seeds, chains, ...>: up to 16, 64 and 255 seeds);
 //  * the reads with more chains than one node holds, or with more than 255 seeds: one WAVEFRONT per read, the map as a sorted array
-//    in LDS (chain_heavy_kernel<256 / 1024 / 4096 seeds>, further down);
+//    in LDS (chain_heavy_kernel<256 / 1024 / 2048 / 4096 seeds>, further down);
 //  * the rest stays flagged (n_chains < 0) and takes the host path (host_chain.cpp): more than 4 096 seeds, two chains at one
 //    position (where the shape of the reference's tree shows), or long enough for mem_flt_chained_seeds to act (l_query >= ~700 bp).
 //
 // The unstable sort of mem_chain_flt is ks_introsort (src/ksort.h:176-226) statement by statement (sortutil.h: its small form for the
-// at most 9 chains of a lane's read, the full sort with private frames in chain_heavy_kernel).
+// at most 9 chains of a lane's read, the full sort with its frames in LDS in chain_heavy_kernel).
 // Floating-point compares (mask_level, drop_ratio, frac_rep) are IEEE single precision in the same expression shapes as
 // the reference (no contraction, no fast-math).
 //
@@ -23,6 +23,7 @@
 // Latency-bound integer work: ~1.5 k instructions per ordinary read, a few hundred bytes of HBM per read.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <utility>
@@ -378,14 +379,16 @@ chain_pick_kernel(int n_reads, const int *__restrict__ lens, const int *__restri
 //     kept chains (query span, weight, ALT flag, first shadowed chain) in the LDS the tree no longer needs, a break found by ballot;
 //   * emission as chain_read above, a kept chain per lane, output positions by a wave prefix sum.
 // Persistent waves take reads from a list (chain_pick_kernel) through a counter.  CAP = seeds (hence chains) a read may have in
-// the instantiation: 256 (7.5 KB of LDS per wave: the reads of up to 255 seeds with more than 9 chains), 1024 (26 KB) and 4096 (98 KB);
-// more seeds than that, or reads long enough for mem_flt_chained_seeds to act, stay with the host.
+// the instantiation: 256 (7.9 KB of LDS per wave: the reads of up to 255 seeds with more than 9 chains), 1024 (26 KB), 2048 (50 KB) and
+// 4096 (98 KB); more seeds than that, or reads long enough for mem_flt_chained_seeds to act, stay with the host.
 // ---------------------------------------------------------------------------------------------------------------------
 #define HV_NONE 0xFFFFu
 // LDS while the seeds are walked: the ordered map (chain positions in ascending order, 8 bytes, and whose they are, 2) and per chain
 // the last seed's offset from its position (4), first_q / last_q / last_len / tail / nmem (5 x 2) — everything test_and_merge reads;
-// afterwards the same bytes hold the filter's columns
-__host__ __device__ constexpr size_t hv_lds_bytes(int cap) { return (size_t)(cap + 64) * 24; }   // (+ 64: the map's shifts write one entry past its end)
+// afterwards the same bytes hold the filter's columns; behind them the three frame arrays of the sort
+#define HV_FRAMES 32   // frames of the sort per array, in LDS: only lane 0 sorts, and 96 private ints held every wave to one per SIMD
+__host__ __device__ constexpr size_t hv_map_bytes(int cap) { return (size_t)(cap + 64) * 24; }   // (+ 64: the map's shifts write one entry past its end)
+__host__ __device__ constexpr size_t hv_lds_bytes(int cap) { return hv_map_bytes(cap) + 3 * HV_FRAMES * 4; }
 __host__ __device__ constexpr size_t hv_scratch_bytes(int cap) { return (size_t)cap * (4 + 7 * 2 + 8 + 4) + 512; }
 struct HvStore {   // what only the later phases read (HBM, the wave's slice): contig and first seed of every chain, the seeds' links, the tree order
 	uint32_t *rid;
@@ -396,13 +399,11 @@ struct HvStore {   // what only the later phases read (HBM, the wave's slice): c
 };
 // "less" of mem_chain_flt's sort over the sort words: the heavier chain first (the weight is the word's upper half)
 __device__ __forceinline__ bool hv_lt(uint32_t a, uint32_t b) { return (a >> 16) > (b >> 16); }
-#define HV_FRAMES 32   // private frame arrays of the sort, in registers
-// (a function of its own with the pointer by value: with the arrays in the kernel's body and `skey` captured by reference the register
-// allocator put all 96 frame ints into accumulator registers instead of 32)
-__device__ __forceinline__ void hv_sort(uint32_t *a, int n)
+#define HV_SHIFT_K 4    // map entries a lane moves per LDS round trip when a new chain makes room
+// frames: 3 * HV_FRAMES ints of LDS (pushes are rare next to element compares)
+__device__ __forceinline__ void hv_sort(uint32_t *a, int n, int *frames)
 {
-	int fs[HV_FRAMES], ft[HV_FRAMES], fd[HV_FRAMES];
-	ks_introsort_at(n, [a](int k) -> uint32_t & { return a[k]; }, KsFramesAt{fs, ft, fd}, hv_lt);
+	ks_introsort_at(n, [a](int k) -> uint32_t & { return a[k]; }, KsFramesAt{frames, frames + HV_FRAMES, frames + 2 * HV_FRAMES}, hv_lt);
 }
 __device__ __forceinline__ void hv_sync()
 {
@@ -412,13 +413,18 @@ __device__ __forceinline__ void hv_sync()
 }
 __device__ __forceinline__ int hv_bcast(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// MPIBWA_CHAIN_PROF=1: where a read's time goes, as clock64() differences that lane 0 adds to a table [class][HV_P_N] at the phase
+// borders of every read (HV_P_SHIFT is part of HV_P_WALK: the loops that make room for a new chain), and what the class was handed:
+// reads, seeds, chains in the map, sort words.  The kernel gets a null pointer otherwise and only tests it.
+enum { HV_P_PRE = 0, HV_P_WALK, HV_P_SHIFT, HV_P_WEIGHT, HV_P_SORT, HV_P_PAIR, HV_P_EMIT, HV_P_READS, HV_P_SEEDS, HV_P_CHAINS, HV_P_WORDS, HV_P_N };
+
 template <int CAP>
 __global__ void __launch_bounds__(64)
 chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned int *__restrict__ list_n, unsigned int *work, int list_cap,
                    const int *__restrict__ lens, const int *__restrict__ n_seeds, const int *__restrict__ l_rep, const i64 *__restrict__ seed_off,
                    const unsigned long long *__restrict__ sa, const int32_t *__restrict__ qbl, const i64 *__restrict__ ann_off,
                    const uint8_t *__restrict__ ann_alt, int n_seqs, const int *__restrict__ gap, uint8_t *__restrict__ scratch,
-                   DevChain *__restrict__ chains, DevSeed *__restrict__ seeds, unsigned int *__restrict__ srt, int *__restrict__ n_chains)
+                   DevChain *__restrict__ chains, DevSeed *__restrict__ seeds, unsigned int *__restrict__ srt, int *__restrict__ n_chains, unsigned long long *prof)
 {
 	extern __shared__ uint8_t hv_lds[];
 	const int lane = threadIdx.x;
@@ -430,6 +436,11 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 	uint16_t *cbeg = (uint16_t *)(skey + CAP);           // [CAP] each
 	uint16_t *cend = cbeg + CAP, *kidx = cend + CAP, *kfirst = kidx + CAP;
 	uint8_t *calt = (uint8_t *)(kfirst + CAP), *ckept = calt + CAP;   // [CAP] each: 4 + 8 + 2 = 14 bytes per chain <= the 20.5 of the tree
+	// the sort's frames, behind both: phase A ends with sid at (CAP + 64) * 24 bytes, phases C-D with ckept at CAP * 14
+	int *frames = (int *)(hv_lds + hv_map_bytes(CAP));
+	static_assert((size_t)(CAP + 64) * 22 + (size_t)(CAP + 64) * 2 == hv_map_bytes(CAP) && (size_t)(CAP + 64) * 8 + (size_t)CAP * 14 <= (size_t)(CAP + 64) * 22 &&
+	              (size_t)CAP * 14 <= hv_map_bytes(CAP) && hv_map_bytes(CAP) % 4 == 0 && hv_lds_bytes(CAP) == hv_map_bytes(CAP) + 3 * HV_FRAMES * sizeof(int),
+	              "the frames lie behind the map and behind the filter's columns");
 	uint8_t *sb = scratch + (size_t)blockIdx.x * hv_scratch_bytes(CAP);
 	HvStore S;
 	S.rid = (uint32_t *)sb;
@@ -443,6 +454,11 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 	int *g_rid = (int *)(g_clo + CAP);
 	const i64 l_pac = P.l_pac;
 	const int n_list = (int)(*list_n < (unsigned int)list_cap ? *list_n : (unsigned int)list_cap);
+	i64 pf_last = 0, pf_shift = 0;
+	auto pf_add = [&](int what, i64 v) { if (lane == 0) atomicAdd(prof + what, (unsigned long long)v); };
+	auto pf_tick = [&](int phase) {   // the time since the last border goes to `phase`
+		if (prof) { const i64 now = clock64(); pf_add(phase, now - pf_last); pf_last = now; }
+	};
 	for (;;) {
 		int t = 0;
 		if (lane == 0) t = (int)atomicAdd(work, 1u);
@@ -455,6 +471,7 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 		auto S_Q = [&](int k) -> int { return qbl[2 * (so + k)]; };
 		auto S_L = [&](int k) -> int { return qbl[2 * (so + k) + 1]; };
 		if (ns > CAP) continue;   // (the list only holds reads that fit; n_chains stays -1: host)
+		if (prof) { pf_last = clock64(); pf_shift = 0; pf_add(HV_P_READS, 1); pf_add(HV_P_SEEDS, ns); }
 		// ---------------- mem_chain: the whole wave per seed ----------------
 		// The ordered map of src/bwamem.c:263 is only ever asked for the closest chain at or before a position and walked in order at
 		// the end; while all chain positions of the read are DISTINCT, a sorted array answers both exactly like the reference's B-tree
@@ -481,6 +498,7 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 				g_rid[k] = rid; g_clo[k] = lo;
 			}
 			hv_sync();
+			pf_tick(HV_P_PRE);
 			i64 nx_rb = S_R(0), nx_clo = g_clo[0];   // (the next seed is fetched while this one meets the map: the walk itself only touches LDS)
 			int nx_qb = S_Q(0), nx_len = S_L(0), nx_rid = g_rid[0];
 			for (int k = 0; k < ns; ++k) {
@@ -531,15 +549,29 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 				if (!merged) {
 					if (cnt > 0 && spos[cnt - 1] == rb) { ok = 0; break; }   // equal keys: the reference's tree decides, on the host
 					const int id = n_ch;
-					// room at position cnt: the entries behind it move up by one, the top 64 first
-					for (int hi = n_ch; hi > cnt; hi -= 64) {
-						const int e = hi - 1 - lane;
-						i64 v = 0; uint16_t w = 0;
-						if (e >= cnt) { v = spos[e]; w = sid[e]; }
+					// room at position cnt: the entries behind it move up by one, the top 64 * HV_SHIFT_K first, HV_SHIFT_K per lane and LDS round
+					// trip.  A batch is read whole before any of it is written, and the next one lies below everything this one wrote (it ends
+					// at hi - 64 K - 1, the lowest write went to hi - 64 K + 1).  The highest write is to entry n_ch, whatever K: only entries
+					// e <= hi - 1 = n_ch - 1 move, and n_ch < ns <= CAP here (a seed opens at most one chain) — inside the map's pad.
+					i64 pf_t0 = 0;
+					if (prof) pf_t0 = clock64();
+					for (int hi = n_ch; hi > cnt; hi -= 64 * HV_SHIFT_K) {
+						i64 v[HV_SHIFT_K]; uint16_t w[HV_SHIFT_K];
+#pragma unroll
+						for (int j = 0; j < HV_SHIFT_K; ++j) {
+							const int e = hi - 1 - (j * 64 + lane);
+							v[j] = 0; w[j] = 0;
+							if (e >= cnt) { v[j] = spos[e]; w[j] = sid[e]; }
+						}
 						hv_sync();
-						if (e >= cnt) { spos[e + 1] = v; sid[e + 1] = w; }
+#pragma unroll
+						for (int j = 0; j < HV_SHIFT_K; ++j) {
+							const int e = hi - 1 - (j * 64 + lane);
+							if (e >= cnt) { spos[e + 1] = v[j]; sid[e + 1] = w[j]; }
+						}
 						hv_sync();
 					}
+					if (prof) pf_shift += clock64() - pf_t0;
 					if (lane == 0) {
 						spos[cnt] = rb; sid[cnt] = (uint16_t)id;
 						S.last_off[id] = 0; S.rid[id] = (uint32_t)rid;
@@ -556,6 +588,7 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 		}
 		ok = hv_bcast(ok); n_ch = hv_bcast(n_ch);
 		hv_sync();
+		if (prof) { pf_tick(HV_P_WALK); pf_add(HV_P_SHIFT, pf_shift); pf_add(HV_P_CHAINS, n_ch); }
 		if (!ok) { if (lane == 0) n_chains[rd] = -2; continue; }
 		for (int id = lane; id < n_ch; id += 64) {   // hv_spill: query span and size of every chain, out of the LDS that is about to be reused
 			g_first_q[id] = S.first_q[id]; g_end_q[id] = (uint16_t)(S.last_q[id] + S.last_len[id]); g_nmem[id] = S.nmem[id];
@@ -593,11 +626,13 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 			n += __popcll(m);
 		}
 		hv_sync();
+		if (prof) { pf_tick(HV_P_WEIGHT); pf_add(HV_P_WORDS, n); }
 		if (!ok) { if (lane == 0) n_chains[rd] = -2; continue; }
 		if (n == 0) { if (lane == 0) n_chains[rd] = 0; continue; }
 		static_assert((unsigned long long)CAP <= 16ull << HV_FRAMES, "ks_introsort_at: n <= 16 << FRAMES");
-		if (lane == 0) hv_sort(skey, n);
+		if (lane == 0) hv_sort(skey, n, frames);
 		hv_sync();
+		pf_tick(HV_P_SORT);
 		// ---------------- mem_chain_flt's pairwise pass: 64 kept chains per step ----------------
 		for (int t0 = 0; t0 < n; t0 += 64) {
 			const int tt = t0 + lane;
@@ -666,6 +701,7 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 			}
 			hv_sync();
 		}
+		pf_tick(HV_P_PAIR);
 		// ---------------- emission: a kept chain per lane, where it goes by prefix sums ----------------
 		const float frac_rep = (float)l_rep[rd] / (float)lq;
 		int n_out = 0;
@@ -722,6 +758,7 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 		}
 		if (lane == 0) n_chains[rd] = n_out;
 		hv_sync();   // (the next read reuses the LDS)
+		pf_tick(HV_P_EMIT);
 	}
 }
 
@@ -773,16 +810,26 @@ void launch_reg_pack(void *stream, int n_reads, const int *d_reg_beg, const int 
 
 static size_t chain_lds_bytes(int maxs, int maxch) { return (size_t)F_NFIELDS * maxch * 64 * 4 + (size_t)(2 * (maxs + 1) + 16) * 64; }
 
-// scratch of launch_chain: [two retry lists][counters][two lists of reads with more than 255 seeds][the slices of chain_heavy_kernel's
-// persistent waves]
-#define HV_WAVES_T 4096   // waves of the 256-seed instantiation (5.3 KB of LDS each): the reads with more than 9 chains
-#define HV_WAVES_S 1024   // ... of the 1024-seed instantiation (21 KB: 7 per CU)
-#define HV_WAVES_L 256    // ... of the 4096-seed one (84 KB: one per CU)
-static size_t heavy_scratch_bytes() { return HV_WAVES_T * hv_scratch_bytes(256) + HV_WAVES_S * hv_scratch_bytes(1024) + HV_WAVES_L * hv_scratch_bytes(4096); }
-size_t chain_scratch_bytes(int n_reads) { return (size_t)n_reads * 8 + 512 + (size_t)n_reads * 8 + 256 + heavy_scratch_bytes(); }
+// scratch of launch_chain: [two retry lists][counters, 512 bytes][three lists of reads with more than 255 seeds][the slices of
+// chain_heavy_kernel's persistent waves]
+// The fixed grids are what 256 CUs with 160 KB of LDS each can hold of an instantiation (its registers allow 5 waves per SIMD): a wave
+// beyond that would only wait for a slot, and every wave has a slice of scratch.
+#define HV_CUS 256
+#define HV_WAVES_T (20 * HV_CUS)   // waves of the 256-seed instantiation (8 064 B of LDS each: 20 per CU): the reads with more than 9 chains
+#define HV_WAVES_S (6 * HV_CUS)    // ... of the 1024-seed instantiation (26 496 B: 6 per CU)
+#define HV_WAVES_M (3 * HV_CUS)    // ... of the 2048-seed one (51 072 B: 3 per CU)
+#define HV_WAVES_L (1 * HV_CUS)    // ... of the 4096-seed one (100 224 B: one per CU)
+static_assert(HV_WAVES_T / HV_CUS * hv_lds_bytes(256) <= 160 * 1024 && HV_WAVES_S / HV_CUS * hv_lds_bytes(1024) <= 160 * 1024 &&
+              HV_WAVES_M / HV_CUS * hv_lds_bytes(2048) <= 160 * 1024 && hv_lds_bytes(4096) <= 160 * 1024, "resident waves per CU by LDS");
+static size_t heavy_scratch_bytes()
+{
+	return HV_WAVES_T * hv_scratch_bytes(256) + HV_WAVES_S * hv_scratch_bytes(1024) + HV_WAVES_M * hv_scratch_bytes(2048) + HV_WAVES_L * hv_scratch_bytes(4096);
+}
+size_t chain_scratch_bytes(int n_reads) { return (size_t)n_reads * 8 + 512 + (size_t)n_reads * 12 + 256 + heavy_scratch_bytes(); }
 
-// two side streams of a call's stream (created once per stream), with the events that fork them off it and join them back
-struct ChainSide { hipStream_t s[2]; hipEvent_t fork, join[2]; };
+// three side streams of a call's stream (created once per stream), with the events that fork them off it and join them back
+#define HV_SIDES 3
+struct ChainSide { hipStream_t s[HV_SIDES]; hipEvent_t fork, join[HV_SIDES]; };
 static ChainSide chain_side_streams(hipStream_t st)
 {
 	static std::mutex side_mu;
@@ -790,7 +837,7 @@ static ChainSide chain_side_streams(hipStream_t st)
 	std::lock_guard<std::mutex> lk(side_mu);
 	for (auto &e : sides) if (e.first == st) return e.second;
 	ChainSide sd;
-	for (int k = 0; k < 2; ++k) { HIP_OK(hipStreamCreateWithFlags(&sd.s[k], hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(&sd.join[k], hipEventDisableTiming)); }
+	for (int k = 0; k < HV_SIDES; ++k) { HIP_OK(hipStreamCreateWithFlags(&sd.s[k], hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(&sd.join[k], hipEventDisableTiming)); }
 	HIP_OK(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
 	sides.emplace_back(st, sd);
 	return sd;
@@ -814,17 +861,26 @@ void launch_chain(void *stream, const ChainParams &P, int n_reads, const int *d_
 #define CHAIN_ARGS P, n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, n_seqs, d_tab, \
 	               tab_stride, d_chains, d_seeds, d_srt, d_nchains
 	// chain_heavy_kernel<CAP> on stream `s`: the reads of `list` (`n` of them, handed out through `work`), the slices of its waves at `scr`
-#define LAUNCH_HEAVY(CAP, waves, s, list, n, work, scr)                                                                                                       \
+#define LAUNCH_HEAVY(CAP, waves, s, list, n, work, scr, pf)                                                                                                     \
 	hipLaunchKernelGGL((chain_heavy_kernel<CAP>), dim3(waves), dim3(64), hv_lds_bytes(CAP), s, P, (const int *)(list), (const unsigned int *)(n), work,      \
 	                   n_reads, d_len, d_nseeds, d_lrep, (const i64 *)d_seed_off, (const unsigned long long *)d_sa, d_qbl, (const i64 *)d_ann_off, d_ann_alt, \
-	                   n_seqs, d_tab, scr, d_chains, d_seeds, d_srt, d_nchains)
+	                   n_seqs, d_tab, scr, d_chains, d_seeds, d_srt, d_nchains, pf)
 	const int big = getenv("MPIBWA_CHAIN_BIG") ? atoi(getenv("MPIBWA_CHAIN_BIG")) : 2;   // 0: up to 64 seeds only, 1: + 255 seeds, 2: + a wavefront per read
 	int *list_a = (int *)d_scratch, *list_b = list_a + n_reads;
-	unsigned int *count = (unsigned int *)(list_b + n_reads);   // [0] more than 9 chains, [1] 64-seed retry, [2] 255-seed retry, [4], [6] heavy: list sizes; [3], [5], [7] work counters
-	int *list_h1 = (int *)((uint8_t *)count + 512), *list_h2 = list_h1 + n_reads;
-	uint8_t *scr_t = (uint8_t *)(((uintptr_t)(list_h2 + n_reads) + 255) & ~(uintptr_t)255);
-	uint8_t *scr_s = scr_t + HV_WAVES_T * hv_scratch_bytes(256), *scr_l = scr_s + HV_WAVES_S * hv_scratch_bytes(1024);
-	HIP_OK(hipMemsetAsync(count, 0, 64, st));
+	unsigned int *count = (unsigned int *)(list_b + n_reads);   // [0] more than 9 chains, [1] 64-seed retry, [2] 255-seed retry, [4], [6], [8] heavy (up to 1024, 4096, 2048 seeds): list sizes; [3], [5], [7], [9] work counters
+	int *list_h1 = (int *)((uint8_t *)count + 512), *list_h2 = list_h1 + n_reads, *list_h3 = list_h2 + n_reads;
+	uint8_t *scr_t = (uint8_t *)(((uintptr_t)(list_h3 + n_reads) + 255) & ~(uintptr_t)255);
+	uint8_t *scr_s = scr_t + HV_WAVES_T * hv_scratch_bytes(256), *scr_m = scr_s + HV_WAVES_S * hv_scratch_bytes(1024);
+	uint8_t *scr_l = scr_m + HV_WAVES_M * hv_scratch_bytes(2048);
+	// MPIBWA_CHAIN_PROF=1: the phase table of chain_heavy_kernel, [class][HV_P_N] behind the counters (count[32] on: 8-byte aligned, as
+	// d_scratch and the two lists before it are); printed below, which waits for the launches
+	const bool s_prof = getenv("MPIBWA_CHAIN_PROF") && atoi(getenv("MPIBWA_CHAIN_PROF")) != 0;   // (read at every call, as MPIBWA_CHAIN_BIG is)
+	static const int prof_caps[] = {256, 1024, 2048, 4096};
+	constexpr int N_PROF = (int)(sizeof(prof_caps) / sizeof(prof_caps[0]));
+	static_assert(128 + N_PROF * HV_P_N * 8 <= 512, "the phase table lies in the 512 bytes of the counters");
+	unsigned long long *prof = s_prof ? (unsigned long long *)(count + 32) : nullptr;
+	auto prof_of = [&](int k) { return prof ? prof + k * HV_P_N : nullptr; };
+	HIP_OK(hipMemsetAsync(count, 0, s_prof ? 512 : 64, st));
 	// the reads declined so far with lo < seeds <= hi, listed for the launch that takes them
 	auto pick = [&](int lo, int hi, int *list, unsigned int *n) {
 		hipLaunchKernelGGL(chain_pick_kernel, dim3((n_reads + 255) / 256), dim3(256), 0, st, n_reads, d_len, d_nseeds, (const int *)d_nchains, d_tab + 5 * tab_stride, lo, hi,
@@ -842,7 +898,8 @@ void launch_chain(void *stream, const ChainParams &P, int n_reads, const int *d_
 		// third of the reads are of this kind)
 		int *list_t = list_a;   // (the 64-seed retry is done with it)
 		pick(0, CK_MAXSEEDS_BIG, list_t, count);
-		// ... and the reads with more than 255 seeds (high-copy repeats), two more LDS footprints; MPIBWA_CHAIN_HEAVY=0 leaves those to the host
+		// ... and the reads with more than 255 seeds (high-copy repeats), three more LDS footprints (max_occ = 500 makes them come as about
+		// 500 k seeds: the 2048 class keeps the reads of 1 000, 1 500 and 2 000 out of the one-wave-per-CU class); MPIBWA_CHAIN_HEAVY=0 leaves those to the host
 		const bool heavy = !(getenv("MPIBWA_CHAIN_HEAVY") && atoi(getenv("MPIBWA_CHAIN_HEAVY")) == 0);
 		ChainSide sd = {};
 		if (heavy) {
@@ -852,22 +909,39 @@ void launch_chain(void *stream, const ChainParams &P, int n_reads, const int *d_
 				s_attr2 = true;
 			}
 			pick(CK_MAXSEEDS_BIG, 1024, list_h1, count + 4);
-			pick(1024, 4096, list_h2, count + 6);
-			// The instantiations are latency-bound launches of a few hundred to a few thousand waves each: side by side on two side streams
+			pick(1024, 2048, list_h3, count + 8);
+			pick(2048, 4096, list_h2, count + 6);
+			// The instantiations are latency-bound launches of a few hundred to a few thousand waves each: side by side on three side streams
 			// of the call's stream instead of one after the other — 23 -> 10 ms per sub-batch with one call in flight.
 			sd = chain_side_streams(st);
 			HIP_OK(hipEventRecord(sd.fork, st));
-			for (int k = 0; k < 2; ++k) HIP_OK(hipStreamWaitEvent(sd.s[k], sd.fork, 0));
-			LAUNCH_HEAVY(4096, HV_WAVES_L, sd.s[0], list_h2, count + 6, count + 7, scr_l);
-			LAUNCH_HEAVY(1024, HV_WAVES_S, sd.s[1], list_h1, count + 4, count + 5, scr_s);
+			for (int k = 0; k < HV_SIDES; ++k) HIP_OK(hipStreamWaitEvent(sd.s[k], sd.fork, 0));
+			LAUNCH_HEAVY(4096, HV_WAVES_L, sd.s[0], list_h2, count + 6, count + 7, scr_l, prof_of(3));
+			LAUNCH_HEAVY(2048, HV_WAVES_M, sd.s[2], list_h3, count + 8, count + 9, scr_m, prof_of(2));
+			LAUNCH_HEAVY(1024, HV_WAVES_S, sd.s[1], list_h1, count + 4, count + 5, scr_s, prof_of(1));
 		}
-		LAUNCH_HEAVY(256, HV_WAVES_T, st, list_t, count, count + 3, scr_t);
+		LAUNCH_HEAVY(256, HV_WAVES_T, st, list_t, count, count + 3, scr_t, prof_of(0));
 		if (heavy)
-			for (int k = 0; k < 2; ++k) { HIP_OK(hipEventRecord(sd.join[k], sd.s[k])); HIP_OK(hipStreamWaitEvent(st, sd.join[k], 0)); }
+			for (int k = 0; k < HV_SIDES; ++k) { HIP_OK(hipEventRecord(sd.join[k], sd.s[k])); HIP_OK(hipStreamWaitEvent(st, sd.join[k], 0)); }
 	}
 #undef LAUNCH_HEAVY
 #undef CHAIN_ARGS
 	HIP_OK(hipGetLastError());
+	if (prof && big >= 2) {
+		unsigned long long h[N_PROF * HV_P_N];
+		HIP_OK(hipStreamSynchronize(st));
+		HIP_OK(hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost));
+		for (int k = 0; k < N_PROF; ++k) {
+			const unsigned long long *c = h + k * HV_P_N;
+			double all = 0;
+			for (int ph = HV_P_PRE; ph <= HV_P_EMIT; ++ph) if (ph != HV_P_SHIFT) all += (double)c[ph];
+			const double pc = all > 0 ? 100.0 / all : 0.0;
+			fprintf(stderr, "[chain] heavy<%d>: %llu reads, %llu seeds, %llu chains, %llu sort words; %.0f ticks of lane 0: contigs %.1f %%, walk %.1f %% "
+			        "(of it shifts %.1f %%), weight %.1f %%, sort %.1f %%, pairwise %.1f %%, emission %.1f %%\n", prof_caps[k], c[HV_P_READS], c[HV_P_SEEDS],
+			        c[HV_P_CHAINS], c[HV_P_WORDS], all, pc * c[HV_P_PRE], pc * c[HV_P_WALK], pc * c[HV_P_SHIFT], pc * c[HV_P_WEIGHT], pc * c[HV_P_SORT],
+			        pc * c[HV_P_PAIR], pc * c[HV_P_EMIT]);
+		}
+	}
 }
 
 } // namespace mbw
