@@ -20,7 +20,7 @@
 //        ballot arithmetic; the first element of the last compaction is always kept.
 //    Every trip count is wave-uniform (ballot results, n) and bounded by n; ballots stand outside divergent code.  No
 //    persistent loop, no work counter: a grid-stride walk over the list.
-// Floating point: the reference's expression (int64 against float * int64) in its types and order, as dedup_small states it.
+// Floating point: the reference's expression (int64 against float * int64) in its types and order, as pairmath.h states it for the host too.
 #include <hip/hip_runtime.h>
 #include "hip_util.h"
 #include "pair_common.cuh"
@@ -40,21 +40,6 @@ DedupParams dedup_params(const mem_opt_t *opt, int64_t l_pac)
 }
 
 namespace {
-
-// mem_patch_reg(x, y) up to its alignment (src/bwamem.c:411-423), x.rb < y.rb: true = the reference would align across the two
-__device__ __forceinline__ bool patch_would_align(const DedupParams &D, i64 x_rb, i64 x_re, int x_qb, int x_qe, i64 y_rb, i64 y_re, int y_qb, int y_qe)
-{
-	if (x_rb < D.l_pac && y_rb >= D.l_pac) return false;
-	if (x_qb >= y_qb || x_qe >= y_qe || x_re >= y_re) return false;   // not colinear
-	int w = (int)((x_re - y_rb) - (x_qe - y_qb));
-	w = w > 0 ? w : -w;
-	double r = (double)(x_re - y_rb) / (y_re - x_rb) - (double)(x_qe - y_qb) / (y_qe - x_qb);
-	r = r > 0. ? r : -r;
-	if (x_re < y_rb || x_qe < y_qb) {
-		if (w > D.w << 1 || r >= 0.05f) return false;
-	} else if (w > D.w << 2 || r >= 0.05f * 2) return false;
-	return true;
-}
 
 __global__ void __launch_bounds__(64)
 dedup_small_kernel(DedupParams D, int n_reads, const DevReg *__restrict__ packed, const int *__restrict__ reg_pos, const int *__restrict__ nregs,
@@ -139,15 +124,11 @@ dedup_wave_kernel(DedupParams D, const int *__restrict__ list, const unsigned in
 				const unsigned long long fail = __ballot(!in_loop);
 				const unsigned long long run = fail ? (1ull << (__ffsll((long long)fail) - 1)) - 1 : ~0ull;   // the lanes before the first that fails
 				const bool alive = ((run >> lane) & 1) && s_alive[qi];
-				const i64 orr = q_re - p_rb;
-				const i64 oq = q_qb < p_qb ? q_qe - p_qb : p_qe - q_qb;
-				const i64 mr = q_re - q_rb < p_re - p_rb ? q_re - q_rb : p_re - p_rb;
-				const i64 mq = q_qe - q_qb < p_qe - p_qb ? q_qe - q_qb : p_qe - p_qb;
-				const bool redun = alive && orr > D.mask_level_redun * mr && oq > D.mask_level_redun * mq;
+				const bool redun = alive && redundant_overlap(D.mask_level_redun, q_rb, q_re, q_qb, q_qe, p_rb, p_re, p_qb, p_qe);
 				const unsigned long long stop = __ballot(redun && p_sc < q_sc);
 				const unsigned long long vis = stop ? (1ull << (__ffsll((long long)stop) - 1)) - 1 : run;   // visited before the break
 				const bool visited = (vis >> lane) & 1;
-				const bool patch = visited && alive && !redun && q_rb < p_rb && patch_would_align(D, q_rb, q_re, q_qb, q_qe, p_rb, p_re, p_qb, p_qe);
+				const bool patch = visited && alive && !redun && q_rb < p_rb && patch_reg_w(D.l_pac, D.w, q_rb, q_re, q_qb, q_qe, p_rb, p_re, p_qb, p_qe) >= 0;
 				if (__ballot(patch)) { declined = true; break; }
 				if (visited && redun) s_alive[qi] = 0;
 				if (stop) { p_dies = true; break; }

@@ -415,10 +415,8 @@ void pair_tables(const mem_opt_t *opt, const mem_pestat_t pes[4], const PairPara
 {
 	for (int d = 0; d < 4; ++d)
 		if (!pes[d].failed)
-			for (int64_t dist = pes[d].low; dist <= pes[d].high; ++dist) {   // src/bwamem_pair.c:218-219, the double part of q
-				const double ns = (dist - pes[d].avg) / pes[d].std;
-				tab[pp.tab_off[d] + (dist - pes[d].low)] = .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * opt->a;
-			}
+			for (int64_t dist = pes[d].low; dist <= pes[d].high; ++dist)   // src/bwamem_pair.c:218-219, the double part of q
+				tab[pp.tab_off[d] + (dist - pes[d].low)] = pair_score_term(pes[d], dist, opt->a);
 	double *ltab = tab + n_tab;
 	ltab[0] = 1.;
 	for (int l = 1; l < pp.ltab_n; ++l) ltab[l] = l < opt->mapQ_coef_len ? 1. : opt->mapQ_coef_fac / log(l);   // src/bwamem.c:964

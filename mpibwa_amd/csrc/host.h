@@ -2,6 +2,8 @@
 #ifndef MBW_HOST_H
 #define MBW_HOST_H
 #include "internal.h"
+#include "pairmath.h"
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -254,11 +256,12 @@ bool pair_wave_eligible(const HRegV a[2], int max_reg);
 void sam_pe_emit(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], bseq1_t s[2], HRegV a[2],
                  const PairPlan &plan, AlnCtx *ctx, int read0);
 
-inline uint64_t hash_64(uint64_t key)   // Thomas Wang's 64-bit mix, as in src/utils.h:98-109
+// the double part of a candidate pair's score (src/bwamem_pair.c:218-219) for orientation statistics pe and insert size dist: mem_pair's
+// on the host, the entries of the device's pair-score table (pair_tables)
+static inline double pair_score_term(const mem_pestat_t &pe, int64_t dist, int a)
 {
-	key += ~(key << 32); key ^= (key >> 22); key += ~(key << 13); key ^= (key >> 8);
-	key += (key << 3);   key ^= (key >> 15); key += ~(key << 27); key ^= (key >> 31);
-	return key;
+	const double ns = (dist - pe.avg) / pe.std;
+	return .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * a;   // .721 = 1 / log(4)
 }
 
 } // namespace mbw

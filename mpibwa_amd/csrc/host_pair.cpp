@@ -23,26 +23,11 @@ bool gen_alt(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, cons
              std::vector<std::string> &xa, std::vector<char> &has, AlnCtx *ctx, int read_idx);
 char *sam_to_c(const std::string &s);
 
-// orientation (0 FF, 1 FR, 2 RF, 3 RR) and distance of two hits given in the doubled coordinate
-static inline int infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist)
-{
-	int r1 = (b1 >= l_pac), r2 = (b2 >= l_pac);
-	int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;   // mate projected on read 1's strand
-	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
-	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
 static int cal_sub(const mem_opt_t *opt, const HRegV &r)
 {
 	size_t j;
-	for (j = 1; j < r.size(); ++j) {
-		int b_max = r[j].qb > r[0].qb ? r[j].qb : r[0].qb;
-		int e_min = r[j].qe < r[0].qe ? r[j].qe : r[0].qe;
-		if (e_min > b_max) {
-			int min_l = r[j].qe - r[j].qb < r[0].qe - r[0].qb ? r[j].qe - r[j].qb : r[0].qe - r[0].qb;
-			if (e_min - b_max >= min_l * opt->mask_level) break;
-		}
-	}
+	for (j = 1; j < r.size(); ++j)
+		if (query_overlap(opt->mask_level, r[j].qb, r[j].qe, r[0].qb, r[0].qe)) break;
 	return j < r.size() ? r[j].score : opt->min_seed_len * opt->a;
 }
 
@@ -245,12 +230,7 @@ static bool insert_into_settled(const mem_opt_t *opt, HRegV &ma, const HReg &b)
 	int R_[48], nR = 0;
 	bool any_ge = false, tie = false;
 	auto redundant = [&](const HReg *q, const HReg *p) -> bool {   // q ends first; p looks back at it (src/bwamem.c:448-455)
-		if (!(p->rb < q->re + opt->max_chain_gap)) return false;
-		const int64_t orr = q->re - p->rb;
-		const int64_t oq = q->qb < p->qb ? q->qe - p->qb : p->qe - q->qb;
-		const int64_t mr = q->re - q->rb < p->re - p->rb ? q->re - q->rb : p->re - p->rb;
-		const int64_t mq = q->qe - q->qb < p->qe - p->qb ? q->qe - q->qb : p->qe - p->qb;
-		return orr > opt->mask_level_redun * mr && oq > opt->mask_level_redun * mq;
+		return p->rb < q->re + opt->max_chain_gap && redundant_overlap(opt->mask_level_redun, q->rb, q->re, q->qb, q->qe, p->rb, p->re, p->qb, p->qe);
 	};
 	for (int i = 0; i < n; ++i) {
 		const HReg &e = ma[i];
@@ -449,10 +429,7 @@ bool pair_wave_eligible(const HRegV a[2], int max_reg)
 	return true;
 }
 
-struct Pair64 { uint64_t x, y; };
-static inline bool pair_lt(const Pair64 &a, const Pair64 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
-
-static int pair_hits(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], HRegV a[2], int id, int *sub, int *n_sub,
+static int pair_hits(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], HRegV a[2], uint64_t id, int *sub, int *n_sub,
                      int z[2], int n_pri[2])
 {
 	HProf hp_(HP_PAIR);
@@ -463,40 +440,21 @@ static int pair_hits(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat
 	for (int r = 0; r < 2; ++r)
 		for (int i = 0; i < n_pri[r]; ++i) {
 			const HReg *e = &a[r][i];
-			Pair64 key;
-			key.x = e->rb < l_pac ? e->rb : (l_pac << 1) - 1 - e->rb;   // forward-strand position
-			key.x = (uint64_t)e->rid << 32 | (key.x - bns->anns[e->rid].offset);
-			key.y = (uint64_t)e->score << 32 | i << 2 | (e->rb >= l_pac) << 1 | r;
-			v.push_back(key);
+			v.push_back(pair_key(l_pac, e->rb, e->rid, bns->anns[e->rid].offset, e->score, i, r));
 		}
 	ks_introsort(v.size(), v.data(), pair_lt);
 	y[0] = y[1] = y[2] = y[3] = -1;
-	for (size_t i = 0; i < v.size(); ++i) {
-		for (int r = 0; r < 2; ++r) {
-			int dir = r << 1 | (v[i].y >> 1 & 1), which;
-			if (pes[dir].failed) continue;
-			which = r << 1 | ((v[i].y & 1) ^ 1);
-			if (y[which] < 0) continue;
-			for (int k = y[which]; k >= 0; --k) {
-				if ((int)(v[k].y & 3) != which) continue;
-				int64_t dist = (int64_t)v[i].x - v[k].x;
-				if (dist > pes[dir].high) break;
-				if (dist < pes[dir].low) continue;
-				double ns = (dist - pes[dir].avg) / pes[dir].std;
-				int q = (int)((v[i].y >> 32) + (v[k].y >> 32) + .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * opt->a + .499);
-				if (q < 0) q = 0;
-				Pair64 p;
-				p.y = (uint64_t)k << 32 | i;
-				p.x = (uint64_t)q << 32 | (hash_64(p.y ^ id << 8) & 0xffffffffU);
-				u.push_back(p);
-			}
-		}
-		y[v[i].y & 3] = (int)i;
+	int low[4], high[4], failed[4];
+	for (int d = 0; d < 4; ++d) { low[d] = pes[d].low; high[d] = pes[d].high; failed[d] = pes[d].failed; }
+	const int id_mix = pair_id_mix(id);
+	for (int i = 0; i < (int)v.size(); ++i) {
+		// y[which]: the last key of that kind before i, -1 = none: nothing is scanned (which keeps the scan off the quadratic case)
+		pair_candidates_of(v.data(), i, low, high, failed, id_mix, [&](int which) { return y[which]; },
+		                   [&](int dir, int64_t dist) { return pair_score_term(pes[dir], dist, opt->a); }, [&](const Pair64 &p) { u.push_back(p); });
+		y[v[i].y & 3] = i;
 	}
 	if (!u.empty()) {
-		int tmp = opt->a + opt->b;
-		tmp = tmp > opt->o_del + opt->e_del ? tmp : opt->o_del + opt->e_del;
-		tmp = tmp > opt->o_ins + opt->e_ins ? tmp : opt->o_ins + opt->e_ins;
+		const int tmp = sub_n_margin(opt->a, opt->b, opt->o_del, opt->e_del, opt->o_ins, opt->e_ins);
 		ks_introsort(u.size(), u.data(), pair_lt);
 		int i = (int)(u.back().y >> 32), k = (int)(u.back().y << 32 >> 32);
 		z[v[i].y & 1] = (int)(v[i].y << 32 >> 34);
@@ -509,8 +467,6 @@ static int pair_hits(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat
 	} else { ret = 0; *sub = 0; *n_sub = 0; }
 	return ret;
 }
-
-#define RAW_MAPQ(diff, a) ((int)(6.02 * (diff) / (a) + .499))
 
 // ---- decisions: mate rescue, primary marking, pairing, MAPQ (everything that mutates a[]) ----
 void sam_pe_plan(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], uint64_t id, bseq1_t s[2],
@@ -538,7 +494,7 @@ void sam_pe_plan(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, 
 	}
 	if ((opt->flag & MEM_F_NOPAIRING) || !P.n_pri[0] || !P.n_pri[1]) return;
 	int *z = P.z;
-	if ((o = pair_hits(opt, bns, pes, a, (int)id, &subo, &n_sub, z, P.n_pri)) <= 0) return;
+	if ((o = pair_hits(opt, bns, pes, a, id, &subo, &n_sub, z, P.n_pri)) <= 0) return;
 	int is_multi[2], q_pe, score_un, *q_se = P.q_se;
 	for (int i = 0; i < 2; ++i) {   // an end with several good primary hits is left to the single-end logic
 		int j;
@@ -549,24 +505,14 @@ void sam_pe_plan(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, 
 	if (is_multi[0] || is_multi[1]) return;
 	P.paired = true;
 	score_un = a[0][0].score + a[1][0].score - opt->pen_unpaired;
-	subo = subo > score_un ? subo : score_un;
-	q_pe = RAW_MAPQ(o - subo, opt->a);
-	if (n_sub > 0) q_pe -= (int)(4.343 * log(n_sub + 1) + .499);
-	if (q_pe < 0) q_pe = 0;
-	if (q_pe > 60) q_pe = 60;
-	q_pe = (int)(q_pe * (1. - .5 * (a[0][0].frac_rep + a[1][0].frac_rep)) + .499);
+	q_pe = mapq_pe(o, subo, score_un, n_sub > 0 ? (int)(4.343 * log(n_sub + 1) + .499) : 0, opt->a, a[0][0].frac_rep, a[1][0].frac_rep);
 	if (o > score_un) {   // the pair beats the two best single-end hits
 		HReg *c[2] = {&a[0][z[0]], &a[1][z[1]]};
 		for (int i = 0; i < 2; ++i) {
 			if (c[i]->secondary >= 0) { c[i]->sub = a[i][c[i]->secondary].score; c[i]->secondary = -2; }
-			q_se[i] = approx_mapq_se(opt, c[i]);
+			q_se[i] = mapq_se_in_pair(approx_mapq_se(opt, c[i]), q_pe, c[i]->score, c[i]->csub, opt->a);   // raised to q_pe, capped by the tandem-repeat score
 		}
-		q_se[0] = q_se[0] > q_pe ? q_se[0] : q_pe < q_se[0] + 40 ? q_pe : q_se[0] + 40;
-		q_se[1] = q_se[1] > q_pe ? q_se[1] : q_pe < q_se[1] + 40 ? q_pe : q_se[1] + 40;
 		P.extra_flag |= 2;
-		// cap by the tandem-repeat score
-		q_se[0] = q_se[0] < RAW_MAPQ(c[0]->score - c[0]->csub, opt->a) ? q_se[0] : RAW_MAPQ(c[0]->score - c[0]->csub, opt->a);
-		q_se[1] = q_se[1] < RAW_MAPQ(c[1]->score - c[1]->csub, opt->a) ? q_se[1] : RAW_MAPQ(c[1]->score - c[1]->csub, opt->a);
 	} else {
 		z[0] = z[1] = 0;
 		q_se[0] = approx_mapq_se(opt, &a[0][0]);

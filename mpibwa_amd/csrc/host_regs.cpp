@@ -31,15 +31,8 @@ static int patch_reg(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *p
 {
 	if (bns == 0 || pac == 0 || query == 0) return 0;
 	assert(a->rid == b->rid && a->rb <= b->rb);
-	if (a->rb < bns->l_pac && b->rb >= bns->l_pac) return 0;
-	if (a->qb >= b->qb || a->qe >= b->qe || a->re >= b->re) return 0;   // not colinear
-	int w = (int)((a->re - b->rb) - (a->qe - b->qb));
-	w = w > 0 ? w : -w;
-	double r = (double)(a->re - b->rb) / (b->re - a->rb) - (double)(a->qe - b->qb) / (b->qe - a->qb);
-	r = r > 0. ? r : -r;
-	if (a->re < b->rb || a->qe < b->qb) {
-		if (w > opt->w << 1 || r >= 0.05f) return 0;
-	} else if (w > opt->w << 2 || r >= 0.05f * 2) return 0;
+	int w = patch_reg_w(bns->l_pac, opt->w, a->rb, a->re, a->qb, a->qe, b->rb, b->re, b->qb, b->qe);   // the cheap tests (:411-423)
+	if (w < 0) return 0;
 	w += a->w + b->w;
 	w = w < opt->w << 2 ? w : opt->w << 2;
 	int score = 0;
@@ -67,12 +60,8 @@ int sort_dedup_patch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *p
 		for (int j = i - 1; j >= 0 && p->rid == a[j].rid && p->rb < a[j].re + opt->max_chain_gap; --j) {
 			HReg *q = &a[j];
 			if (q->qe == q->qb) continue;   // already excluded
-			int64_t orr = q->re - p->rb;
-			int64_t oq = q->qb < p->qb ? q->qe - p->qb : p->qe - q->qb;
-			int64_t mr = q->re - q->rb < p->re - p->rb ? q->re - q->rb : p->re - p->rb;
-			int64_t mq = q->qe - q->qb < p->qe - p->qb ? q->qe - q->qb : p->qe - p->qb;
 			int score, w;
-			if (orr > opt->mask_level_redun * mr && oq > opt->mask_level_redun * mq) {   // one of the two is redundant
+			if (redundant_overlap(opt->mask_level_redun, q->rb, q->re, q->qb, q->qe, p->rb, p->re, p->qb, p->qe)) {   // one of the two is redundant
 				if (p->score < q->score) { p->qe = p->qb; break; }
 				else q->qe = q->qb;
 			} else if (q->rb < p->rb && (score = patch_reg(opt, bns, pac, query, q, p, &w)) > 0) {   // merge q into p
@@ -109,24 +98,17 @@ int sort_dedup_patch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *p
 // ---------------------------------------------------------------------------
 static void mark_primary_core(const mem_opt_t *opt, int n, HReg *a, std::vector<int> &z)
 {
-	int tmp = opt->a + opt->b;
-	tmp = opt->o_del + opt->e_del > tmp ? opt->o_del + opt->e_del : tmp;
-	tmp = opt->o_ins + opt->e_ins > tmp ? opt->o_ins + opt->e_ins : tmp;
+	const int tmp = sub_n_margin(opt->a, opt->b, opt->o_del, opt->e_del, opt->o_ins, opt->e_ins);
 	z.clear();
 	z.push_back(0);
 	for (int i = 1; i < n; ++i) {
 		size_t k;
 		for (k = 0; k < z.size(); ++k) {
 			int j = z[k];
-			int b_max = a[j].qb > a[i].qb ? a[j].qb : a[i].qb;
-			int e_min = a[j].qe < a[i].qe ? a[j].qe : a[i].qe;
-			if (e_min > b_max) {
-				int min_l = a[i].qe - a[i].qb < a[j].qe - a[j].qb ? a[i].qe - a[i].qb : a[j].qe - a[j].qb;
-				if (e_min - b_max >= min_l * opt->mask_level) {   // significant overlap on the query
-					if (a[j].sub == 0) a[j].sub = a[i].score;
-					if (a[j].score - a[i].score <= tmp && (a[j].is_alt || !a[i].is_alt)) ++a[j].sub_n;
-					break;
-				}
+			if (query_overlap(opt->mask_level, a[i].qb, a[i].qe, a[j].qb, a[j].qe)) {
+				if (a[j].sub == 0) a[j].sub = a[i].score;
+				if (a[j].score - a[i].score <= tmp && (a[j].is_alt || !a[i].is_alt)) ++a[j].sub_n;
+				break;
 			}
 		}
 		if (k == z.size()) z.push_back(i);
@@ -177,28 +159,27 @@ int mark_primary_se(const mem_opt_t *opt, HRegV &v, int64_t id)
 	return n_pri;
 }
 
-// Single-end mapping quality of a hit from its score, the best competing score and how much of it its seeds cover.  The
-// double-precision expressions are the reference's, operation for operation (src/bwamem.c:952-975): a product evaluated in another
-// order rounds differently and moves a MAPQ by one.
+// Single-end mapping quality of a hit from its score, the best competing score and how much of it its seeds cover
+// (src/bwamem.c:952-975).  The length-scaled form (mapQ_coef_len > 0, the default) is pairmath.h's mapq_se_q with libm's two values; what
+// is stated here is the form of mapQ_coef_len = 0, operation for operation: a product evaluated in another order rounds differently
+// and moves a MAPQ by one.  Its head (the rival, the identity) and its tail (the sub_n penalty, the clamp, frac_rep) are the same lines
+// as mapq_se_q's, a second statement: a fix there has to be made here too.
 int approx_mapq_se(const mem_opt_t *opt, const HReg *a)
 {
+	const int q_span = a->qe - a->qb, r_span = (int)(a->re - a->rb);
+	const int span = q_span > r_span ? q_span : r_span;
+	if (opt->mapQ_coef_len > 0)
+		return mapq_se_q(a->score, a->sub, a->sub_n, a->csub, span, a->frac_rep, opt->a, opt->b, opt->min_seed_len,
+		                 span < opt->mapQ_coef_len ? 1. : opt->mapQ_coef_fac / log(span), a->sub_n > 0 ? (int)(4.343 * log(a->sub_n + 1) + .499) : 0);
 	// the competitor: the best overlapping hit, at least a minimal seed's worth, or the best other chain of the same region
 	int rival = a->sub ? a->sub : opt->min_seed_len * opt->a;
 	if (a->csub > rival) rival = a->csub;
 	if (rival >= a->score) return 0;
-	const int q_span = a->qe - a->qb, r_span = (int)(a->re - a->rb);
-	const int span = q_span > r_span ? q_span : r_span;
 	const double identity = 1. - (double)(span * opt->a - a->score) / (opt->a + opt->b) / span;
 	int q = 0;
 	if (a->score != 0) {
-		if (opt->mapQ_coef_len > 0) {   // -Q: the length-scaled form
-			double f = span < opt->mapQ_coef_len ? 1. : opt->mapQ_coef_fac / log(span);
-			f *= identity * identity;
-			q = (int)(6.02 * (a->score - rival) / opt->a * f * f + .499);
-		} else {
-			q = (int)(30.0 * (1. - (double)rival / a->score) * log(a->seedcov) + .499);
-			if (identity < 0.95) q = (int)(q * identity * identity + .499);
-		}
+		q = (int)(30.0 * (1. - (double)rival / a->score) * log(a->seedcov) + .499);
+		if (identity < 0.95) q = (int)(q * identity * identity + .499);
 	}
 	if (a->sub_n > 0) q -= (int)(4.343 * log(a->sub_n + 1) + .499);   // many equally good competitors
 	q = q > 60 ? 60 : q < 0 ? 0 : q;
@@ -301,14 +282,6 @@ bool gen_cigar2(const int8_t mat[25], int o_del, int e_del, int o_ins, int e_ins
 	return true;
 }
 
-static inline int infer_bw(int l1, int l2, int score, int a, int q, int r)
-{
-	if (l1 == l2 && l1 * a - score < (q + r - a) << 1) return 0;   // equal lengths need at least two gaps
-	int w = (int)((double)((l1 < l2 ? l1 : l2) * a - score - q) / r + 2.);
-	if (w < abs(l1 - l2)) w = abs(l1 - l2);
-	return w;
-}
-
 HAln reg2aln(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int l_query, const char *query_, const HReg *ar,
              AlnCtx *ctx, int read_idx, bool need_mapq)
 {
@@ -323,10 +296,7 @@ HAln reg2aln(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int 
 	const bool collecting = ctx && ctx->mode == AlnCtx::COLLECT;
 	if (!collecting && need_mapq) a.mapq = (ar->secondary < 0 ? approx_mapq_se(opt, ar) : 0) & 0xff;   // (logs: not needed to list the request)
 	if (ar->secondary >= 0) a.flag |= 0x100;
-	int tmp = infer_bw(qe - qb, (int)(re - rb), ar->truesc, opt->a, opt->o_del, opt->e_del);
-	int w2 = infer_bw(qe - qb, (int)(re - rb), ar->truesc, opt->a, opt->o_ins, opt->e_ins);
-	w2 = w2 > tmp ? w2 : tmp;
-	if (w2 > opt->w) w2 = w2 < ar->w ? w2 : ar->w;
+	int w2 = reg2aln_band(qe - qb, (int)(re - rb), ar->truesc, opt->a, opt->o_del, opt->e_del, opt->o_ins, opt->e_ins, opt->w, ar->w);
 	if (collecting) {   // only note that this region needs its CIGAR; decisions do not depend on it
 		AlnReqH rq;
 		rq.rb = rb; rq.re = re; rq.read = read_idx; rq.qb = qb; rq.qe = qe; rq.w2 = w2; rq.truesc = ar->truesc; rq.pad = 0;

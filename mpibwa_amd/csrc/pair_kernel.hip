@@ -19,7 +19,7 @@
 //
 // Floating point: the reference decides in double (and two float adds).  The expressions are evaluated here in the same
 // types and order (the library is built with -ffp-contract=off, IEEE division); the two transcendental sites are host-built
-// tables: .721 * log(2 * erfc(|ns| / sqrt 2)) * a per insert size and orientation (src/bwamem_pair.c:218-219), and
+// tables: the double term of a candidate pair's score per insert size and orientation (src/bwamem_pair.c:218-219, pair_score_term), and
 // mapQ_coef_fac / log(l) per length (src/bwamem.c:964).
 #include <hip/hip_runtime.h>
 #include "pair_common.cuh"
@@ -42,22 +42,13 @@ void launch_first_reg(void *stream, int n, const int *d_reg_pos, const int *d_nr
 	hipLaunchKernelGGL(first_reg_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, d_reg_pos, d_nregs, d_packed, d_first, d_nfirst);
 }
 
-
-// orientation (0 FF, 1 FR, 2 RF, 3 RR) and distance of two hits given in the doubled coordinate (src/bwamem_pair.c:23-30)
-__device__ __forceinline__ int infer_dir(i64 l_pac, i64 b1, i64 b2, i64 *dist)
-{
-	const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-	const i64 p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
-	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
 // true when mem_matesw(hit, the mate's hits) returns at once: every orientation failed or explained by a mate hit (:118-128)
 __device__ __forceinline__ bool no_rescue_needed(const PairParams &P, const DevReg &hit, const PReg *ma, int n_ma)
 {
 	int skip[4];
 	for (int r = 0; r < 4; ++r) skip[r] = P.failed[r] ? 1 : 0;
 	for (int i = 0; i < n_ma; ++i) {
-		i64 dist;
+		int64_t dist;
 		const int r = infer_dir(P.l_pac, hit.rb, ma[i].d.rb, &dist);
 		if (dist >= P.low[r] && dist <= P.high[r]) skip[r] = 1;
 	}
@@ -65,8 +56,6 @@ __device__ __forceinline__ bool no_rescue_needed(const PairParams &P, const DevR
 }
 
 #define PR_MAXPAIR 16
-struct Pair64 { u64 x, y; };
-__device__ __forceinline__ bool pair_lt(const Pair64 &a, const Pair64 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
 template <int CAP>
 __device__ __forceinline__ void sort_pairs(int n, Pair64 *v)
 {
@@ -137,42 +126,22 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 	for (int r = 0; r < 2; ++r)
 		for (int i = 0; i < n[r]; ++i) {
 			const DevReg &e = a[r][i].d;
-			Pair64 key;
-			key.x = (u64)(e.rb < P.l_pac ? e.rb : (P.l_pac << 1) - 1 - e.rb);
-			key.x = (u64)e.rid << 32 | (key.x - (u64)ann_off[e.rid]);
-			key.y = (u64)e.score << 32 | (u64)(i << 2 | (e.rb >= P.l_pac) << 1 | r);
-			v[nv++] = key;
+			v[nv++] = pair_key(P.l_pac, e.rb, e.rid, ann_off[e.rid], e.score, i, r);
 		}
 	sort_pairs<2 * PR_MAXREG>(nv, v);
 	int y[4] = {-1, -1, -1, -1};
-	const int idi = (int)((unsigned)(int)id << 8);
-	for (int i = 0; i < nv; ++i) {
-		for (int r = 0; r < 2; ++r) {
-			const int dir = r << 1 | (int)(v[i].y >> 1 & 1);
-			if (P.failed[dir]) continue;
-			const int which = r << 1 | (int)((v[i].y & 1) ^ 1);
-			if (y[which] < 0) continue;
-			for (int kk = y[which]; kk >= 0; --kk) {
-				if ((int)(v[kk].y & 3) != which) continue;
-				const i64 dist = (i64)v[i].x - (i64)v[kk].x;
-				if (dist > P.high[dir]) break;
-				if (dist < P.low[dir]) continue;
-				int q = (int)((double)((v[i].y >> 32) + (v[kk].y >> 32)) + ptab[P.tab_off[dir] + (int)(dist - P.low[dir])] + .499);
-				if (q < 0) q = 0;
-				Pair64 p;
-				p.y = (u64)kk << 32 | (u64)i;
-				p.x = (u64)q << 32 | (hash_64(p.y ^ (u64)(i64)idi) & 0xffffffffU);
-				if (nu < PR_MAXPAIR) u[nu] = p;
-				++nu;
-			}
-		}
+	const int idi = pair_id_mix(id);
+	for (int i = 0; i < nv; ++i) {   // (y[which]: the last key of that kind before i, -1 = none: nothing is scanned)
+		pair_candidates_of(v, i, P.low, P.high, P.failed, idi, [&](int which) { return y[which]; },
+		                   [&](int dir, i64 dist) { return ptab[P.tab_off[dir] + (int)(dist - P.low[dir])]; }, [&](const Pair64 &p) {
+			if (nu < PR_MAXPAIR) u[nu] = p;
+			++nu;
+		});
 		y[v[i].y & 3] = i;
 	}
 	if (nu > PR_MAXPAIR) { status[k] = 3; return; }   // (ks_small_introsort_at: at most 16 elements)
 	if (nu == 0) { status[k] = 8; return; }   // no pair in a proper orientation and distance: the host reports the ends independently
-	int tmp = P.a + P.b;
-	tmp = tmp > P.o_del + P.e_del ? tmp : P.o_del + P.e_del;
-	tmp = tmp > P.o_ins + P.e_ins ? tmp : P.o_ins + P.e_ins;
+	const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
 	sort_pairs<PR_MAXPAIR>(nu, u);
 	int z[2];
 	{
@@ -189,25 +158,15 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		for (int j = 1; j < n[e]; ++j)
 			if (a[e][j].secondary < 0 && a[e][j].d.score >= P.T) { status[k] = 10; return; }
 	const int score_un = a[0][0].d.score + a[1][0].d.score - P.pen_unpaired;
-	subo = subo > score_un ? subo : score_un;
-	int q_pe = RAW_MAPQ(o - subo, P.a);
-	if (n_sub > 0) q_pe -= P.lnq[n_sub];
-	if (q_pe < 0) q_pe = 0;
-	if (q_pe > 60) q_pe = 60;
-	q_pe = (int)(q_pe * (1. - .5 * (a[0][0].d.frac_rep + a[1][0].d.frac_rep)) + .499);
+	const int q_pe = mapq_pe(o, subo, score_un, P.lnq[n_sub], P.a, a[0][0].d.frac_rep, a[1][0].d.frac_rep);   // (n_sub < PR_MAXPAIR; lnq[0] = 0)
 	int q_se[2], extra_flag = 1;   // (0x1: PairPlan::extra_flag starts at 1)
 	if (o > score_un) {   // the pair beats the two best single-end hits
 		for (int e = 0; e < 2; ++e) {
 			PReg &c = a[e][z[e]];
 			if (c.secondary >= 0) { c.sub = a[e][c.secondary].d.score; c.secondary = -2; }
-			q_se[e] = mapq_se(P, c, ltab, 0);
+			q_se[e] = mapq_se_in_pair(mapq_se(P, c, ltab, 0), q_pe, c.d.score, 0, P.a);   // (the tandem-repeat cap with csub = 0)
 		}
-		q_se[0] = q_se[0] > q_pe ? q_se[0] : q_pe < q_se[0] + 40 ? q_pe : q_se[0] + 40;
-		q_se[1] = q_se[1] > q_pe ? q_se[1] : q_pe < q_se[1] + 40 ? q_pe : q_se[1] + 40;
 		extra_flag |= 2;
-		const int ca = RAW_MAPQ(a[0][z[0]].d.score, P.a), cb = RAW_MAPQ(a[1][z[1]].d.score, P.a);   // the tandem-repeat cap with csub = 0
-		q_se[0] = q_se[0] < ca ? q_se[0] : ca;
-		q_se[1] = q_se[1] < cb ? q_se[1] : cb;
 	} else {
 		z[0] = z[1] = 0;
 		q_se[0] = mapq_se(P, a[0][0], ltab, 0);
@@ -229,11 +188,7 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		}
 	for (int e = 0; e < 2; ++e) {
 		const PReg &R = a[e][z[e]];
-		const int l1 = R.d.qe - R.d.qb, l2 = (int)(R.d.re - R.d.rb);
-		const int t2 = infer_bw(l1, l2, R.d.truesc, P.a, P.o_del, P.e_del);
-		int w2 = infer_bw(l1, l2, R.d.truesc, P.a, P.o_ins, P.e_ins);
-		w2 = w2 > t2 ? w2 : t2;
-		if (w2 > P.w) w2 = w2 < R.d.w ? w2 : R.d.w;
+		const int w2 = reg2aln_band(R.d.qe - R.d.qb, (int)(R.d.re - R.d.rb), R.d.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.d.w);
 		AlnReq q;
 		q.rb = R.d.rb; q.re = R.d.re; q.read = 2 * k + e; q.qb = R.d.qb; q.qe = R.d.qe; q.w2 = w2; q.truesc = R.d.truesc; q.pad = 0;
 		reqs[2 * k + e] = q;

@@ -53,9 +53,6 @@ __device__ __forceinline__ void wl_put(WList &L, int i, const WReg &r)
 	L.csub[i] = r.csub; L.sub[i] = r.sub; L.sub_n[i] = r.sub_n; L.secondary[i] = r.secondary; L.secondary_all[i] = r.secondary_all; L.frac_rep[i] = r.frac_rep;
 }
 
-struct Pair64 { u64 x, y; };
-__device__ __forceinline__ bool pair_lt64(const Pair64 &a, const Pair64 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
-
 __device__ __forceinline__ i64 wave_max(i64 v)
 {
 	for (int d = 32; d; d >>= 1) { const i64 o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
@@ -77,23 +74,10 @@ __device__ __forceinline__ int wave_sum(int v)
 	return v;
 }
 
-__device__ __forceinline__ int pw_infer_dir(i64 l_pac, i64 b1, i64 b2, i64 *dist)   // src/bwamem_pair.c:23-30
-{
-	const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-	const i64 p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-	*dist = p2 > b1 ? p2 - b1 : b1 - p2;
-	return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
 // q ends first; p looks back at it (src/bwamem.c:448-455)
 __device__ __forceinline__ bool pw_redundant(const PairParams &P, i64 q_rb, i64 q_re, int q_qb, int q_qe, i64 p_rb, i64 p_re, int p_qb, int p_qe)
 {
-	if (!(p_rb < q_re + P.max_chain_gap)) return false;
-	const i64 orr = q_re - p_rb;
-	const i64 oq = q_qb < p_qb ? q_qe - p_qb : p_qe - q_qb;
-	const i64 mr = q_re - q_rb < p_re - p_rb ? q_re - q_rb : p_re - p_rb;
-	const i64 mq = q_qe - q_qb < p_qe - p_qb ? q_qe - q_qb : p_qe - p_qb;
-	return orr > P.mask_level_redun * mr && oq > P.mask_level_redun * mq;
+	return p_rb < q_re + P.max_chain_gap && redundant_overlap(P.mask_level_redun, q_rb, q_re, q_qb, q_qe, p_rb, p_re, p_qb, p_qe);
 }
 
 // The redundancy pass on "a fixed point of it + the new hit b" (host_pair.cpp insert_into_settled; the argument why this is
@@ -187,23 +171,12 @@ __device__ __forceinline__ bool pw_mark_primary(const PairParams &P, WList &A, i
 	__syncthreads();
 	if (lane < n) { me.sub = 0; me.secondary = me.secondary_all = -1; wl_put(A, rank, me); }
 	__syncthreads();
-	int tmp = P.a + P.b;
-	tmp = P.o_del + P.e_del > tmp ? P.o_del + P.e_del : tmp;
-	tmp = P.o_ins + P.e_ins > tmp ? P.o_ins + P.e_ins : tmp;
+	const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
 	int qb = 0, qe = 0, sc = 0, sub = 0, sub_n = 0, sec = -1;
 	if (lane < n) { qb = A.qb[lane]; qe = A.qe[lane]; sc = A.score[lane]; sub_n = A.sub_n[lane]; }
 	for (int i = 1; i < n; ++i) {   // hit i against the primary hits before it, in their order: the first it overlaps is its parent
 		const int qb_i = A.qb[i], qe_i = A.qe[i], sc_i = A.score[i];
-		bool ov = false;
-		if (lane < i && sec < 0) {
-			const int b_max = qb > qb_i ? qb : qb_i;
-			const int e_min = qe < qe_i ? qe : qe_i;
-			if (e_min > b_max) {
-				const int min_l = qe_i - qb_i < qe - qb ? qe_i - qb_i : qe - qb;
-				ov = e_min - b_max >= min_l * P.mask_level;   // significant overlap on the query
-			}
-		}
-		const u64 m = __ballot(ov);
+		const u64 m = __ballot(lane < i && sec < 0 && query_overlap(P.mask_level, qb_i, qe_i, qb, qe));
 		if (m) {
 			const int j = __ffsll((long long)m) - 1;
 			if (lane == j) {
@@ -218,29 +191,13 @@ __device__ __forceinline__ bool pw_mark_primary(const PairParams &P, WList &A, i
 	return true;
 }
 
-// the candidate pairs (v[kk], v[i]) of mem_pair for one i (src/bwamem_pair.c:203-227): f(p) for each of them, p as the reference builds it
+// the candidate pairs (v[kk], v[i]) of mem_pair for one i (pairmath.h) with the device's score table; the scan starts at i - 1 (the
+// reference starts at the last key of kind `which` before i: the ones between are skipped)
 template <class F>
 __device__ __forceinline__ void pw_pairs_of(const PairParams &P, const Pair64 *V, int i, int idi, const double *__restrict__ ptab, F f)
 {
-	const Pair64 vi = V[i];
-	for (int r = 0; r < 2; ++r) {
-		const int dir = r << 1 | (int)(vi.y >> 1 & 1);
-		if (P.failed[dir]) continue;
-		const int which = r << 1 | (int)((vi.y & 1) ^ 1);
-		for (int kk = i - 1; kk >= 0; --kk) {   // (the reference starts at the last key of kind `which` before i: the ones between are skipped here)
-			const Pair64 vk = V[kk];
-			if ((int)(vk.y & 3) != which) continue;
-			const i64 dist = (i64)vi.x - (i64)vk.x;
-			if (dist > P.high[dir]) break;
-			if (dist < P.low[dir]) continue;
-			int q = (int)((double)((vi.y >> 32) + (vk.y >> 32)) + ptab[P.tab_off[dir] + (int)(dist - P.low[dir])] + .499);
-			if (q < 0) q = 0;
-			Pair64 p;
-			p.y = (u64)kk << 32 | (u64)i;
-			p.x = (u64)q << 32 | (hash_64(p.y ^ (u64)(i64)idi) & 0xffffffffU);
-			f(p);
-		}
-	}
+	pair_candidates_of(V, i, P.low, P.high, P.failed, idi, [&](int) { return i - 1; },
+	                   [&](int dir, i64 dist) { return ptab[P.tab_off[dir] + (int)(dist - P.low[dir])]; }, f);
 }
 
 #define PW_GIVE_UP(code) do { if (lane == 0) wstatus[t] = (uint8_t)(code); return; } while (0)
@@ -301,8 +258,8 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 				// mem_matesw :118-128: the orientations that failed or that a hit of the mate's CURRENT list explains
 				int r_l = -1;
 				if (lane < n[ma]) {
-					i64 dist;
-					const int r = pw_infer_dir(P.l_pac, a_rb, L[ma].rb[lane], &dist);
+					int64_t dist;
+					const int r = infer_dir(P.l_pac, a_rb, L[ma].rb[lane], &dist);
 					if (dist >= P.low[r] && dist <= P.high[r]) r_l = r;
 				}
 				bool skip[4];
@@ -345,26 +302,23 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 		Pair64 key[2];
 		for (int r = 0; r < 2; ++r)
 			if (lane < n[r]) {
-				const i64 rb = L[r].rb[lane];
 				const int rid = L[r].rid[lane];
-				key[r].x = (u64)(rb < P.l_pac ? rb : (P.l_pac << 1) - 1 - rb);
-				key[r].x = (u64)rid << 32 | (key[r].x - (u64)ann_off[rid]);
-				key[r].y = (u64)L[r].score[lane] << 32 | (u64)(lane << 2 | (rb >= P.l_pac) << 1 | r);
+				key[r] = pair_key(P.l_pac, L[r].rb[lane], rid, ann_off[rid], L[r].score[lane], lane, r);
 				V[r * n[0] + lane] = key[r];
 			}
 		__syncthreads();
 		int rank[2] = {0, 0};
 		for (int j = 0; j < nv; ++j) {   // (unique keys: the rank is the place in the reference's sorted array)
 			const Pair64 o = V[j];
-			if (lane < n[0] && pair_lt64(o, key[0])) ++rank[0];
-			if (lane < n[1] && pair_lt64(o, key[1])) ++rank[1];
+			if (lane < n[0] && pair_lt(o, key[0])) ++rank[0];
+			if (lane < n[1] && pair_lt(o, key[1])) ++rank[1];
 		}
 		__syncthreads();
 		for (int r = 0; r < 2; ++r)
 			if (lane < n[r]) V[rank[r]] = key[r];
 		__syncthreads();
 	}
-	const int idi = (int)((unsigned)(int)id << 8);
+	const int idi = pair_id_mix(id);
 	// u is not stored: its maximum under (x, y), the second-largest score and n_sub are reductions
 	Pair64 best;
 	best.x = best.y = 0;
@@ -372,7 +326,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 	for (int i = lane; i < nv; i += 64)
 		pw_pairs_of(P, V, i, idi, ptab, [&](const Pair64 &p) {
 			if (cnt == 0) best = p;
-			else if (pair_lt64(best, p)) { const int qb_ = (int)(best.x >> 32); q2 = q2 > qb_ ? q2 : qb_; best = p; }
+			else if (pair_lt(best, p)) { const int qb_ = (int)(best.x >> 32); q2 = q2 > qb_ ? q2 : qb_; best = p; }
 			else { const int qp = (int)(p.x >> 32); q2 = q2 > qp ? q2 : qp; }
 			++cnt;
 		});
@@ -384,9 +338,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 	const bool mine = top_x && best.y == gy;
 	int subo = (int)wave_max((i64)(mine ? q2 : cnt ? (int)(best.x >> 32) : -1));
 	if (nu < 2) subo = 0;
-	int tmp = P.a + P.b;
-	tmp = tmp > P.o_del + P.e_del ? tmp : P.o_del + P.e_del;
-	tmp = tmp > P.o_ins + P.e_ins ? tmp : P.o_ins + P.e_ins;
+	const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
 	int n_sub = 0;
 	if (nu > 1) {
 		int c2 = 0;
@@ -410,13 +362,8 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 	for (int e = 0; e < 2; ++e)   // an end with several good primary hits is left to the single-end logic
 		if (__ballot(lane >= 1 && lane < n[e] && L[e].secondary[lane] < 0 && L[e].score[lane] >= P.T)) PW_GIVE_UP(PW_HOST_SUPP);
 	const int score_un = L[0].score[0] + L[1].score[0] - P.pen_unpaired;
-	subo = subo > score_un ? subo : score_un;
-	int q_pe = RAW_MAPQ(o - subo, P.a);
-	if (n_sub >= 40) PW_GIVE_UP(PW_HOST_LENGTH);   // (beyond the table of (int)(4.343 * log(n + 1) + .499))
-	if (n_sub > 0) q_pe -= P.lnq[n_sub];
-	if (q_pe < 0) q_pe = 0;
-	if (q_pe > 60) q_pe = 60;
-	q_pe = (int)(q_pe * (1. - .5 * (L[0].frac_rep[0] + L[1].frac_rep[0])) + .499);
+	if (n_sub >= 40) PW_GIVE_UP(PW_HOST_LENGTH);   // (beyond the table of (int)(4.343 * log(n + 1) + .499), whose entry 0 is 0)
+	const int q_pe = mapq_pe(o, subo, score_un, P.lnq[n_sub], P.a, L[0].frac_rep[0], L[1].frac_rep[0]);
 	int q_se[2], extra_flag = 1, sub_z[2];
 	const bool pair_wins = o > score_un;
 	if (!pair_wins) z[0] = z[1] = 0;
@@ -428,11 +375,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 		const int l = c.qe - c.qb > c.re - c.rb ? c.qe - c.qb : (int)(c.re - c.rb);
 		if (l >= P.ltab_n || l <= 0 || c.sub_n >= 40) PW_GIVE_UP(PW_HOST_LENGTH);
 		q_se[e] = mapq_se_of(P, c.score, sub, c.sub_n, c.csub, l, c.frac_rep, ltab);
-		if (pair_wins) {
-			q_se[e] = q_se[e] > q_pe ? q_se[e] : q_pe < q_se[e] + 40 ? q_pe : q_se[e] + 40;
-			const int cap = RAW_MAPQ(c.score - c.csub, P.a);   // the tandem-repeat cap
-			q_se[e] = q_se[e] < cap ? q_se[e] : cap;
-		}
+		if (pair_wins) q_se[e] = mapq_se_in_pair(q_se[e], q_pe, c.score, c.csub, P.a);
 	}
 	if (pair_wins) extra_flag |= 2;
 	__syncthreads();
@@ -459,11 +402,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 	for (int e = 0; e < 2; ++e)   // a lane per listed hit: the request mem_reg2aln would make for it (src/bwamem.c:1089-1105)
 		if (xa_hits[e] >> lane & 1) {
 			const WReg R = wl_get(L[e], lane);
-			const int l1 = R.qe - R.qb, l2 = (int)(R.re - R.rb);
-			const int t2 = infer_bw(l1, l2, R.truesc, P.a, P.o_del, P.e_del);
-			int w2 = infer_bw(l1, l2, R.truesc, P.a, P.o_ins, P.e_ins);
-			w2 = w2 > t2 ? w2 : t2;
-			if (w2 > P.w) w2 = w2 < R.w ? w2 : R.w;
+			const int w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);
 			AlnReq q;
 			q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = R.rid;
 			xa_reqs[(size_t)(2 * t + e) * PW_XA_CAP + __popcll(xa_hits[e] & (((u64)1 << lane) - 1))] = q;
@@ -471,11 +410,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 	if (lane < 2) {
 		const int e = lane;
 		const WReg R = wl_get(L[e], z[e]);
-		const int l1 = R.qe - R.qb, l2 = (int)(R.re - R.rb);
-		const int t2 = infer_bw(l1, l2, R.truesc, P.a, P.o_del, P.e_del);
-		int w2 = infer_bw(l1, l2, R.truesc, P.a, P.o_ins, P.e_ins);
-		w2 = w2 > t2 ? w2 : t2;
-		if (w2 > P.w) w2 = w2 < R.w ? w2 : R.w;   // (a rescued hit has w = 0)
+		const int w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);   // (a rescued hit has w = 0)
 		AlnReq q;
 		q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = 0;
 		reqs[2 * t + e] = q;

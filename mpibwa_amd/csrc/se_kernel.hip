@@ -12,7 +12,7 @@
 // (one record, no SA / XA / pa tag).  For such a read the kernel writes what the host's COLLECT pass would have listed — the request
 // for aln_kernel and the line descriptor for sam_emit_kernel — so its record is made without the host touching the read; every
 // other read is left to the host with its full logic (mem_mark_primary_se, mem_gen_alt, mem_reg2sam in host_regs.cpp).
-// The helpers (pair_common.cuh) are the pairing kernel's own; the floating-point expressions keep their types and order.
+// The helpers (pair_common.cuh) are the pairing kernel's own, the arithmetic (pairmath.h) the host's: its types and order are the reference's.
 #include <hip/hip_runtime.h>
 #include "pair_common.cuh"
 
@@ -69,11 +69,7 @@ se_simple_kernel(PairParams P, int n_reads, const DevReg *__restrict__ first, co
 		if (kk >= 0 && a[j].d.score >= a[kk].d.score * (double)P.XA_drop_ratio) { status[i] = SE_HOST_XA; return; }
 	}
 	const PReg &R = a[z];
-	const int l1 = R.d.qe - R.d.qb, l2 = (int)(R.d.re - R.d.rb);
-	const int t2 = infer_bw(l1, l2, R.d.truesc, P.a, P.o_del, P.e_del);
-	int w2 = infer_bw(l1, l2, R.d.truesc, P.a, P.o_ins, P.e_ins);
-	w2 = w2 > t2 ? w2 : t2;
-	if (w2 > P.w) w2 = w2 < R.d.w ? w2 : R.d.w;
+	const int w2 = reg2aln_band(R.d.qe - R.d.qb, (int)(R.d.re - R.d.rb), R.d.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.d.w);
 	AlnReq q;
 	q.rb = R.d.rb; q.re = R.d.re; q.read = i; q.qb = R.d.qb; q.qe = R.d.qe; q.w2 = w2; q.truesc = R.d.truesc; q.pad = 0;
 	reqs[i] = q;
