@@ -380,6 +380,23 @@ int mi355x_sam_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *p
 int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_reads, const void *regs, const int *n_regs,
                     int max_len, uint8_t *status, void *desc, void *req);
 
+/* The same decisions for the reads se_simple_kernel leaves because they carry more than mi355x_pair_maxreg() regions (code 3) or a
+ * secondary region with an XA entry (code 11): se_wave_kernel, a read per wavefront, 0 .. mi355x_pair_wave_maxreg() regions.  n_work
+ * reads given by their numbers in the chunk (read_no[t]: mem_mark_primary_se runs with id = n_processed + read_no[t], and req.read =
+ * read_no[t]) and their regions AFTER mem_sort_dedup_patch, 64-byte records back to back (the layout of mi355x_pair_wave_batch), work
+ * item t owns regs[reg_off[t] .. reg_off[t+1]): there is neither a redundancy pass nor a patch alignment on the device.  Everything
+ * comes back by work item.  status[t] = 1: decided with a plain record, desc[t] / req[t] as mi355x_se_batch returns them (desc.req = -3:
+ * the unmapped record, no request); 16: decided with an XA tag (mem_gen_alt, src/bwamem_extra.c:98-118: the hits i, in list order, with
+ * secondary_all = the line's hit and score >= its score * XA_drop_ratio; 1 .. max_XA_hits of them) — xa_cnt[t] entries, entry j's request
+ * (what mem_reg2aln would ask, its contig in `pad`) at xa_req[t * mi355x_pair_wave_xa_cap() + j], the count also in desc[t].flag bits
+ * 16-19: the read's requests in a job are [req[t], its XA entries'], which is how mi355x_sam_se_batch reads a descriptor with a count.
+ * Any other value: the host's read, desc[t].req = req[t].read = -1; 5 a region longer than the per-length table, 6 a region on an ALT
+ * contig, 10 a second primary region (supplementary line), 11 XA entries without room for them (xa_req == NULL: the kernel runs without
+ * the listing; or max_XA_hits beyond the cap), 13 more than mi355x_pair_wave_maxreg() regions, 14 two hits equal under (score, hash).
+ * Returns 0. */
+int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
+                         const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req);
+
 /* The redundancy pass of mem_sort_dedup_patch (src/bwamem.c:437-489) on the device, on raw region lists as mem_chain2aln leaves them:
  * 64-byte records back to back (the layout of mi355x_pair_wave_batch), read r owns regs[reg_off[r] .. reg_off[r+1]).  status[r] = 1: taken
  * — m[r] regions survive and keep[reg_off[r] + k], k < m[r], is the place in the read's own list of the k-th region of the reference's
@@ -449,11 +466,14 @@ typedef struct {
 	uint64_t smem_tab_bytes;                     /* the part of smem_bytes (64 B per occ block) that the third pass took from its jump table instead of fetching */
 	uint64_t n_sam_dev;                          /* SAM records written by sam_kernel (the rest are formatted by the host) */
 	uint64_t n_pair_dev;                         /* pairs whose pairing decisions (mem_sam_pe) were taken on the device (pair_kernel.hip) */
-	uint64_t n_se_dev;                           /* single-end reads decided on the device (se_kernel.hip); their records count in n_sam_dev */
+	uint64_t n_se_dev;                           /* single-end reads decided on the device with a plain record, by either kernel (se_kernel.hip, se_wave_kernel.hip); their records count in n_sam_dev */
 	uint64_t n_pair_wave_dev;                    /* pairs with mate rescue or up to 64 hits per end decided on the device (pair_wave_kernel.hip); not counted in n_pair_dev */
 	uint64_t n_pair_xa_dev;                      /* pairs pair_wave_kernel decided because its XA listing is on: with an XA tag on a record, or left by pair_kernel.hip for its XA test alone and found to carry none; counted in neither of the two above */
 	uint64_t n_dedup_dev;                        /* reads with two or more raw regions whose mem_sort_dedup_patch result was taken from the device (dedup_kernel.hip, MPIBWA_DEV_DEDUP=1) */
 	uint64_t n_dedup_host;                       /* ... and those the host sorted (all of them unless MPIBWA_DEV_DEDUP=1 enables the stage; then the ones the kernel declined) */
+	uint64_t n_se_wave_dev;                      /* the part of n_se_dev decided by se_wave_kernel (se_wave_kernel.hip): reads se_simple_kernel left for more than eight regions or for its XA test, whose record is plain */
+	uint64_t n_se_xa_dev;                        /* single-end reads se_wave_kernel decided with an XA tag on the record; counted neither in n_se_dev nor, their records, in n_sam_dev */
+	uint64_t n_se_xa_sam_dev;                    /* ... and how many of those records sam_kernel wrote (the rest came back and were aligned and formatted by the host) */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

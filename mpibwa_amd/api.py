@@ -20,7 +20,7 @@ EXPORTS = [
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_extend_batch2", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
-    "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg",
+    "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg", "mi355x_se_wave_batch",
 ]
 
 
@@ -124,6 +124,7 @@ def load_library(build_if_missing=True):
     sig("mi355x_sam_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_sam_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("mi355x_se_wave_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_dedup_maxreg", C.c_int, [])
     sig("mi355x_dedup_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [P(C.c_double)])
     sig("mi355x_seed_batch", C.c_int64, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64])
@@ -454,6 +455,35 @@ class Engine:
                                       status.ctypes.data, desc.ctypes.data, req.ctypes.data)
         assert rc == 0
         return status, desc, req
+
+    SE_DECIDED, SE_HOST_LENGTH, SE_HOST_ALT, SE_HOST_SUPP, SE_HOST_XA, SE_HOST_FULL, SE_HOST_TIE, SE_DECIDED_XA = 1, 5, 6, 10, 11, 13, 14, 16
+
+    def singles_wave(self, opt, read_no, regs, max_len=150, n_processed=0, xa=True):
+        """se_wave_kernel on single-end reads (mi355x_se_wave_batch).  read_no: the reads' numbers in the chunk (id = n_processed + number);
+        regs: per read a REG_DT array of its regions after mem_sort_dedup_patch.  Everything comes back by work item.
+        -> status (n,) uint8, desc (n,) DESC_DT, req (n,) AREQ_DT, xa_req (per read an AREQ_DT array of its XA entries' requests, pad = the
+        entry's contig; empty with xa=False: the kernel then runs without the listing).  For sam_records_se the read's requests are
+        [req[t], *xa_req[t]] (none for the unmapped record, desc.req = -3)."""
+        n = len(regs)
+        read_no = np.ascontiguousarray(read_no, dtype=np.int32)
+        assert len(read_no) == n
+        reg_off = np.zeros(n + 1, dtype=np.int32)
+        reg_off[1:] = np.cumsum([len(r) for r in regs])
+        allregs = np.zeros(max(1, int(reg_off[-1])), dtype=self.REG_DT)
+        for r, a in enumerate(regs):
+            if len(a):
+                allregs[reg_off[r]:reg_off[r + 1]] = np.asarray(a, dtype=self.REG_DT)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        desc = np.zeros(max(n, 1), dtype=self.DESC_DT)
+        req = np.zeros(max(n, 1), dtype=self.AREQ_DT)
+        cap = self.lib.mi355x_pair_wave_xa_cap()
+        xa_req = np.zeros((max(n, 1), cap), dtype=self.AREQ_DT)
+        xa_cnt = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = self.lib.mi355x_se_wave_batch(opt, C.cast(self.bns, C.c_void_p), n_processed, n, read_no.ctypes.data, allregs.ctypes.data,
+                                           reg_off.ctypes.data, max_len, status.ctypes.data, desc.ctypes.data, req.ctypes.data,
+                                           xa_cnt.ctypes.data if xa else None, xa_req.ctypes.data if xa else None)
+        assert rc == 0
+        return status[:n], desc[:n], req[:n], [xa_req[t, :xa_cnt[t]].copy() for t in range(n)]
 
     DD_TAKEN, DD_HOST_MAXREG, DD_HOST_PATCH = 1, 3, 4
     DD_FILL = -0x5a5a5a5b

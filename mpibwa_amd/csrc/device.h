@@ -308,7 +308,8 @@ struct PairParams {
 	int a, b, pen_unpaired, min_seed_len, w, o_del, e_del, o_ins, e_ins, max_chain_gap, T, max_matesw;
 	float mask_level_redun, mask_level, XA_drop_ratio;
 	uint64_t id0;             // number of the chunk's first pair (n_processed >> 1): the hash tie-breaks of src/bwamem.c:527, src/bwamem_pair.c:222
-	int lnq[40];              // (int)(4.343 * log(n + 1) + .499), src/bwamem.c:972, src/bwamem_pair.c:313
+	int lnq[64];              // (int)(4.343 * log(n + 1) + .499), src/bwamem.c:972, src/bwamem_pair.c:313 (the pairing kernels read the first 40,
+	                          // se_wave_kernel up to sub_n = PW_MAXREG - 1)
 	int no_rescue;            // MEM_F_NO_RESCUE or max_matesw <= 0: mem_sam_pe's rescue loop does not run
 	int low[4], high[4], failed[4];   // mem_pestat_t per orientation
 	int tab_off[4];           // start of each orientation's run in the pair-score table: entry [dist - low]
@@ -382,6 +383,26 @@ void se_params(const mem_opt_t *opt, int64_t l_pac, int64_t n_processed, int max
 // d_first / d_nfirst as launch_first_reg leaves them; d_ok[i] = 0: the host's read whatever its regions; reqs and desc: one record per read
 void launch_se_simple(void *stream, const PairParams &P, int n_reads, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,
                       const uint8_t *d_ann_alt, const double *d_ltab, uint8_t *d_status, AlnReq *d_reqs, SamDesc *d_desc);
+
+// ---- decisions of the single-end reads with up to PW_MAXREG regions or an XA tag (se_wave_kernel.hip), a read per wavefront ----
+// status codes of se_wave_kernel: se_simple_kernel's where the test is the same (5 length, 6 ALT, 10 second primary hit, 11 XA entries
+// without room for them), pair_wave_kernel's numbers for the three of its own
+#define SE_HOST_FULL 13           // a list past PW_MAXREG
+#define SE_HOST_TIE 14            // two hits equal under (score, hash): the reference's unstable sort decides
+#define SE_DECIDED_XA 16          // decided, and the record carries an XA tag (SE_DECIDED: the record is plain)
+static_assert(PW_MAXREG <= 64, "PairParams::lnq holds sub_n up to PW_MAXREG - 1");
+// work[t]: the read's number in the chunk (id = P.id0 + work[t]); lists[loff[t] .. loff[t + 1]): its regions after mem_sort_dedup_patch.
+// wstatus[t] = SE_DECIDED / SE_DECIDED_XA: desc[t] and reqs[t] (none for the unmapped record, desc.req = -3) are written as
+// se_simple_kernel writes them, else only wstatus[t].  d_xa_reqs and d_xa_cnt given (and max_XA_hits <= PW_XA_CAP): a read whose line
+// carries XA entries (src/bwamem_extra.c:98-118) is decided too: xa_cnt[t] entries, their requests (pad = the hit's contig) at
+// xa_reqs[t * PW_XA_CAP ..], desc[t].flag bits 16-19 = the count.  Without them such a read gets SE_HOST_XA.
+void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const uint8_t *d_ann_alt,
+                    const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc, AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr);
+// the decided reads' requests and descriptors to their places in a job of their own: dst[t] = first request of work item t's read in
+// `reqs`, or < 0 (not in the job); [the line's request, its XA requests]; desc: chunk-wide, by read; clear_n > 0: reads clear_r0 .. +
+// clear_n of desc are marked "not the device's" first
+void launch_se_wave_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                            const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
 
 // ---- the redundancy pass of mem_sort_dedup_patch on the raw region lists (dedup_kernel.hip) ----
 #define DD_MAXREG 512             // regions per read dedup_wave_kernel takes (its LDS footprint)

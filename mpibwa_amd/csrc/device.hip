@@ -391,7 +391,7 @@ bool pair_params(const mem_opt_t *opt, int64_t l_pac, const mem_pestat_t pes[4],
 	pp.o_del = opt->o_del; pp.e_del = opt->e_del; pp.o_ins = opt->o_ins; pp.e_ins = opt->e_ins;
 	pp.max_chain_gap = opt->max_chain_gap; pp.mask_level_redun = opt->mask_level_redun; pp.mask_level = opt->mask_level;
 	pp.XA_drop_ratio = opt->XA_drop_ratio; pp.T = opt->T; pp.max_matesw = opt->max_matesw; pp.id0 = (uint64_t)(n_processed >> 1);
-	for (int v = 0; v < 40; ++v) pp.lnq[v] = (int)(4.343 * log(v + 1) + .499);
+	for (int v = 0; v < 64; ++v) pp.lnq[v] = (int)(4.343 * log(v + 1) + .499);
 	pp.no_rescue = ((opt->flag & MEM_F_NO_RESCUE) || opt->max_matesw <= 0) ? 1 : 0;
 	bool usable = true;
 	size_t n_tab = 0;

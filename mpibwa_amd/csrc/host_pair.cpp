@@ -429,6 +429,14 @@ bool pair_wave_eligible(const HRegV a[2], int max_reg)
 	return true;
 }
 
+bool se_wave_eligible(const HRegV &a, int max_reg)
+{
+	if ((int)a.size() > max_reg || !(a.empty() || a.settled)) return false;
+	for (size_t j = 0; j < a.size(); ++j)
+		if (a[j].is_alt) return false;
+	return true;
+}
+
 static int pair_hits(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], HRegV a[2], uint64_t id, int *sub, int *n_sub,
                      int z[2], int n_pri[2])
 {

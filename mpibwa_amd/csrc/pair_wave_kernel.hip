@@ -17,6 +17,7 @@
 // none on an ALT contig, and per (end, candidate hit, orientation) a tag: the number of the alignment in the pair's slice of the
 // mate-rescue results, "the window is invalid: the reference aligns nothing", or "not on the device".
 //
+// The list in LDS, the wave reductions, mem_mark_primary_se and the XA listing are wave_common.cuh's, shared with se_wave_kernel.hip.
 // One region per lane, both lists in LDS as one array per field (no bank conflicts, 2 x 64 x 64 B), mem_pair's keys behind them
 // (128 x 16 B) and the rescue candidates: 11 776 B of LDS per wave, 55 VGPRs, no scratch (the compiler's resource usage for gfx950).  The two sorts are rank sorts: mem_pair's keys are unique, so any sort gives the reference's array; two
 // hits with equal (score, hash) in mem_mark_primary_se — where the reference's unstable sort would decide — send the pair to the host.
@@ -25,54 +26,9 @@
 //
 // Floating point: as in pair_kernel.hip — the reference's types and order, -ffp-contract=off, the two transcendental sites tabulated.
 #include <hip/hip_runtime.h>
-#include "pair_common.cuh"
+#include "wave_common.cuh"
 
 namespace mbw {
-
-struct WList {   // the regions of one end, one array per field of mem_alnreg_t that mem_sam_pe reads
-	i64 rb[PW_MAXREG], re[PW_MAXREG];
-	int qb[PW_MAXREG], qe[PW_MAXREG], rid[PW_MAXREG], score[PW_MAXREG], truesc[PW_MAXREG], w[PW_MAXREG], csub[PW_MAXREG];
-	int sub[PW_MAXREG], sub_n[PW_MAXREG], secondary[PW_MAXREG], secondary_all[PW_MAXREG];
-	float frac_rep[PW_MAXREG];
-};
-struct WReg {
-	i64 rb, re;
-	int qb, qe, rid, score, truesc, w, csub, sub, sub_n, secondary, secondary_all;
-	float frac_rep;
-};
-__device__ __forceinline__ WReg wl_get(const WList &L, int i)
-{
-	WReg r;
-	r.rb = L.rb[i]; r.re = L.re[i]; r.qb = L.qb[i]; r.qe = L.qe[i]; r.rid = L.rid[i]; r.score = L.score[i]; r.truesc = L.truesc[i]; r.w = L.w[i];
-	r.csub = L.csub[i]; r.sub = L.sub[i]; r.sub_n = L.sub_n[i]; r.secondary = L.secondary[i]; r.secondary_all = L.secondary_all[i]; r.frac_rep = L.frac_rep[i];
-	return r;
-}
-__device__ __forceinline__ void wl_put(WList &L, int i, const WReg &r)
-{
-	L.rb[i] = r.rb; L.re[i] = r.re; L.qb[i] = r.qb; L.qe[i] = r.qe; L.rid[i] = r.rid; L.score[i] = r.score; L.truesc[i] = r.truesc; L.w[i] = r.w;
-	L.csub[i] = r.csub; L.sub[i] = r.sub; L.sub_n[i] = r.sub_n; L.secondary[i] = r.secondary; L.secondary_all[i] = r.secondary_all; L.frac_rep[i] = r.frac_rep;
-}
-
-__device__ __forceinline__ i64 wave_max(i64 v)
-{
-	for (int d = 32; d; d >>= 1) { const i64 o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-	return v;
-}
-__device__ __forceinline__ i64 wave_min(i64 v)
-{
-	for (int d = 32; d; d >>= 1) { const i64 o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-	return v;
-}
-__device__ __forceinline__ u64 wave_maxu(u64 v)
-{
-	for (int d = 32; d; d >>= 1) { const u64 o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-	return v;
-}
-__device__ __forceinline__ int wave_sum(int v)
-{
-	for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-	return v;
-}
 
 // q ends first; p looks back at it (src/bwamem.c:448-455)
 __device__ __forceinline__ bool pw_redundant(const PairParams &P, i64 q_rb, i64 q_re, int q_qb, int q_qe, i64 p_rb, i64 p_re, int p_qb, int p_qe)
@@ -145,52 +101,6 @@ __device__ __forceinline__ int pw_insert(const PairParams &P, WList &M, int &n, 
 	return 0;
 }
 
-// mem_mark_primary_se (src/bwamem.c:521-569, its core :493-519) on one end, a hit per lane; H: 64 x 2 u64 of scratch.  false: two hits
-// compare equal in the sort by (score desc, hash)
-__device__ __forceinline__ bool pw_mark_primary(const PairParams &P, WList &A, int n, u64 id, Pair64 *H, int lane)
-{
-	if (n == 0) return true;
-	WReg me;
-	u64 h = 0;
-	if (lane < n) {
-		me = wl_get(A, lane);
-		h = hash_64(id + (u64)lane);
-		H[lane].x = h; H[lane].y = (u64)(unsigned)me.score;
-	}
-	__syncthreads();
-	int rank = 0;
-	bool tie = false;
-	if (lane < n)
-		for (int j = 0; j < n; ++j) {
-			const int sc = (int)H[j].y;
-			const u64 hj = H[j].x;
-			if (sc > me.score || (sc == me.score && hj < h)) ++rank;
-			else if (j != lane && sc == me.score && hj == h) tie = true;
-		}
-	if (__ballot(tie)) return false;
-	__syncthreads();
-	if (lane < n) { me.sub = 0; me.secondary = me.secondary_all = -1; wl_put(A, rank, me); }
-	__syncthreads();
-	const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
-	int qb = 0, qe = 0, sc = 0, sub = 0, sub_n = 0, sec = -1;
-	if (lane < n) { qb = A.qb[lane]; qe = A.qe[lane]; sc = A.score[lane]; sub_n = A.sub_n[lane]; }
-	for (int i = 1; i < n; ++i) {   // hit i against the primary hits before it, in their order: the first it overlaps is its parent
-		const int qb_i = A.qb[i], qe_i = A.qe[i], sc_i = A.score[i];
-		const u64 m = __ballot(lane < i && sec < 0 && query_overlap(P.mask_level, qb_i, qe_i, qb, qe));
-		if (m) {
-			const int j = __ffsll((long long)m) - 1;
-			if (lane == j) {
-				if (sub == 0) sub = sc_i;
-				if (sc - sc_i <= tmp) ++sub_n;
-			}
-			if (lane == i) sec = j;
-		}
-	}
-	if (lane < n) { A.sub[lane] = sub; A.sub_n[lane] = sub_n; A.secondary[lane] = sec; A.secondary_all[lane] = sec; }
-	__syncthreads();
-	return true;
-}
-
 // the candidate pairs (v[kk], v[i]) of mem_pair for one i (pairmath.h) with the device's score table; the scan starts at i - 1 (the
 // reference starts at the last key of kind `which` before i: the ones between are skipped)
 template <class F>
@@ -228,11 +138,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 		n[e] = loff[2 * t + e + 1] - b;
 		if (n[e] > PW_MAXREG) PW_GIVE_UP(PW_HOST_FULL);
 		if (lane < n[e]) {
-			const DevReg d = lists[b + lane];
-			WReg r;
-			r.rb = d.rb; r.re = d.re; r.qb = d.qb; r.qe = d.qe; r.rid = d.rid; r.score = d.score; r.truesc = d.truesc; r.w = d.w; r.frac_rep = d.frac_rep;
-			r.csub = r.sub = r.sub_n = 0; r.secondary = r.secondary_all = -1;
-			wl_put(L[e], lane, r);
+			wl_put(L[e], lane, wl_from(lists[b + lane]));
 		}
 	}
 	__syncthreads();
@@ -389,24 +295,12 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 			__syncthreads();
 		}
 	}
-	// ---- does the chosen hit get an XA string (src/bwamem_extra.c:105-118, no ALT hit here)?  Only with 1 .. max_XA_hits qualifying
-	// secondary hits under it; more than that and the reference writes none.  Its entries are those hits in list order (:115-131)
+	// ---- the XA entries of the two chosen hits and their requests (wave_common.cuh: pw_xa_list) ----
 	int n_xa[2];
-	u64 xa_hits[2];
 	for (int e = 0; e < 2; ++e) {
-		xa_hits[e] = __ballot(lane < n[e] && L[e].secondary_all[lane] == z[e] && L[e].score[lane] >= L[e].score[z[e]] * (double)P.XA_drop_ratio);
-		n_xa[e] = __popcll(xa_hits[e]);
-		if (n_xa[e] > P.max_XA_hits) { n_xa[e] = 0; xa_hits[e] = 0; }
-		if (n_xa[e] > 0 && (!xa_reqs || n_xa[e] > PW_XA_CAP)) PW_GIVE_UP(PW_HOST_XA);
+		n_xa[e] = pw_xa_list(P, L[e], n[e], z[e], 2 * k + e, xa_reqs ? xa_reqs + (size_t)(2 * t + e) * PW_XA_CAP : nullptr, lane);
+		if (n_xa[e] < 0) PW_GIVE_UP(PW_HOST_XA);
 	}
-	for (int e = 0; e < 2; ++e)   // a lane per listed hit: the request mem_reg2aln would make for it (src/bwamem.c:1089-1105)
-		if (xa_hits[e] >> lane & 1) {
-			const WReg R = wl_get(L[e], lane);
-			const int w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);
-			AlnReq q;
-			q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = R.rid;
-			xa_reqs[(size_t)(2 * t + e) * PW_XA_CAP + __popcll(xa_hits[e] & (((u64)1 << lane) - 1))] = q;
-		}
 	if (lane < 2) {
 		const int e = lane;
 		const WReg R = wl_get(L[e], z[e]);

@@ -386,6 +386,18 @@ struct Call {
 	uint64_t n_wave = 0;
 	const uint8_t *pstat = nullptr;      // status[k] = 1: the unit's requests and descriptors exist on the device
 	const uint8_t *se_codes = nullptr;   // the status codes of se_simple_kernel (pstat too, if it took any read)
+	// single-end reads se_simple_kernel left for more than eight regions or for its XA test: se_wave_kernel, once over
+	// the chunk on the call's stream.  Its buffers are slot 0's of pair_wave_kernel's (a call is either paired or single-end), its
+	// decided reads' job of every part is Part::xa with the request bases Part::xa_base, wave_dec marks the reads it decided
+	uint8_t *se_codes_w = nullptr;       // (se_codes, writable: se_wave_kernel's decisions are merged in)
+	bool dev_se_wave = false;            // MPIBWA_HOST_SE_WAVE=1: off
+	bool dev_se_xa = false;              // ... with its XA listing (MPIBWA_HOST_XA=1 or max_XA_hits > PW_XA_CAP: off)
+	std::vector<int> se_work;            // the reads handed to it (chunk numbering, ascending)
+	const uint8_t *se_wstatus = nullptr, *se_wxcnt = nullptr;   // per work item: its status byte, its XA entries
+	uint64_t n_se_wave = 0, n_se_xa = 0; // decided by it with a plain record / with an XA tag
+	std::atomic<unsigned long long> n_se_xa_sam{0};   // records with an XA tag taken from the device
+	void se_wave_decide();               // candidates, packed lists, the kernel, the merge of its decisions (synchronous)
+	void se_wave_records(Part &P);       // the job of the part's reads it decided (asynchronous)
 	const AlnReq *d_pr_req = nullptr;
 	const SamDesc *d_pr_desc = nullptr;
 	double pair_dev_ms = 0;

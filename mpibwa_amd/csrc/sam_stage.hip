@@ -125,7 +125,7 @@ void Call::decide_on_device(int ends)
 		stream_wait(st);
 		HIP_OK(hipGetLastError());
 		bool any_dev = ends == 2;   // (single-end, none taken: no device job over n empty requests)
-		if (ends == 1) se_codes = hs;
+		if (ends == 1) { se_codes = se_codes_w = hs; wave_pp = pp; d_wave_tab = d_tab; wave_n_tab = n_tab; }   // (se_wave_kernel: the same parameters and table)
 		for (int i = 0; i < nu && !any_dev; ++i) any_dev = hs[i] == SE_DECIDED;
 		if (any_dev) { pstat = hs; d_pr_req = d_rq; d_pr_desc = d_ds; }
 		if (any_dev && ends == 2) { pstat_w = hs; wave_pp = pp; d_wave_tab = d_tab; wave_n_tab = n_tab; }
@@ -228,6 +228,18 @@ static size_t roomy(size_t bytes)
 	return std::max<size_t>(2 * bytes, (size_t)1 << 16);
 }
 
+// a read's region list as the wave kernels take it: the fields of mem_alnreg_t the deciding stages read
+static void pack_list(const HRegV &v, DevReg *o)
+{
+	for (size_t j = 0; j < v.size(); ++j) {
+		const HReg &h = v[j];
+		DevReg d;
+		d.rb = h.rb; d.re = h.re; d.qb = h.qb; d.qe = h.qe; d.rid = h.rid; d.score = h.score; d.truesc = h.truesc; d.w = h.w;
+		d.seedcov = h.seedcov; d.seedlen0 = h.seedlen0; d.frac_rep = h.frac_rep; d.pad = 0;
+		o[j] = d;
+	}
+}
+
 // pair_wave_kernel over the part's work list, behind the mate-rescue kernel on its stream; the status bytes come back on the same
 // stream, so that mfinish's wait delivers them.  The lists are the host's own (after mem_sort_dedup_patch), packed with offsets.
 void Call::wave_launch(Part &P)
@@ -242,17 +254,7 @@ void Call::wave_launch(Part &P)
 		for (int e = 0; e < 2; ++e) { n_regs += regs[2 * P.work[t] + e].size(); loff[2 * t + e + 1] = (int)n_regs; }
 	DevReg *hl = (DevReg *)W.h_wlists[s].ensure(roomy(n_regs * sizeof(DevReg) + 64));
 	parallel_for(n_thr, nw, 512, [&](int t) {
-		for (int e = 0; e < 2; ++e) {
-			const HRegV &v = regs[2 * P.work[t] + e];
-			DevReg *o = hl + loff[2 * t + e];
-			for (size_t j = 0; j < v.size(); ++j) {
-				const HReg &h = v[j];
-				DevReg d;
-				d.rb = h.rb; d.re = h.re; d.qb = h.qb; d.qe = h.qe; d.rid = h.rid; d.score = h.score; d.truesc = h.truesc; d.w = h.w;
-				d.seedcov = h.seedcov; d.seedlen0 = h.seedlen0; d.frac_rep = h.frac_rep; d.pad = 0;
-				o[j] = d;
-			}
-		}
+		for (int e = 0; e < 2; ++e) pack_list(regs[2 * P.work[t] + e], hl + loff[2 * t + e]);
 	});
 	int *hw = (int *)W.h_wwork[s].ensure(roomy((size_t)nw * 4 + 64));
 	unsigned *hm = (unsigned *)W.h_wmfirst[s].ensure(roomy((size_t)nw * 4 + 64));
@@ -316,6 +318,107 @@ void Call::xa_records(Part &P)
 	HIP_OK(hipMemcpyAsync(d_dst, dst, (size_t)nw * 4, hipMemcpyHostToDevice, jst));
 	launch_pair_wave_xa_scatter(jst, nw, (const int *)W.wwork[s].p, d_dst, (const AlnReq *)W.wreq[s].p, (const SamDesc *)W.wdesc[s].p, (const AlnReq *)W.wxreq[s].p,
 	                            (const uint8_t *)W.wxcnt[s].p, d_rq, d_ds, 2 * P.lo, 2 * nu);
+	HIP_OK(hipGetLastError());
+	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
+	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
+	job_launch(P.xa, W.xa_job[s], jst, P, d_rq, n_req, P.xa_base.data(), true, nullptr, d_ds);
+}
+
+// ---- single-end reads with long lists or an XA tag: se_wave_kernel (se_wave_kernel.hip) ----
+// The reads se_simple_kernel left with "more than eight regions" or "a secondary region with an XA entry", once over the chunk: the
+// host's own lists (after mem_sort_dedup_patch) packed with offsets, the kernel on the call's stream, status bytes and XA counts back,
+// merged into the chunk's decisions.  MPIBWA_HOST_SE_WAVE=1 turns the path off; MPIBWA_HOST_XA=1 or max_XA_hits beyond the kernel's
+// side array only its XA listing (such a read comes back with SE_HOST_XA).
+void Call::se_wave_decide()
+{
+	dev_se_wave = !pe && dev_se && se_codes_w && getenv("MPIBWA_HOST_SE_WAVE") == nullptr;
+	if (!dev_se_wave) return;
+	const double tp0 = now_ms();
+	dev_se_xa = wave_pp.max_XA_hits <= PW_XA_CAP && getenv("MPIBWA_HOST_XA") == nullptr;
+	uint8_t *codes = se_codes_w;
+	wave_dec.assign(n, 0);
+	se_work.clear();
+	size_t n_regs = 0;
+	for (int i = 0; i < n; ++i)
+		if ((codes[i] == SE_HOST_MAXREG || codes[i] == SE_HOST_XA) && !seqs[i].comment && se_wave_eligible(regs[i], PW_MAXREG)) {
+			se_work.push_back(i);
+			n_regs += regs[i].size();
+		}
+	const int nw = (int)se_work.size();
+	if (nw == 0) return;
+	int *loff = (int *)W.h_wloff[0].ensure(roomy(((size_t)nw + 1) * 4 + 64));
+	loff[0] = 0;
+	for (int t = 0; t < nw; ++t) loff[t + 1] = loff[t] + (int)regs[se_work[t]].size();
+	DevReg *hl = (DevReg *)W.h_wlists[0].ensure(roomy(n_regs * sizeof(DevReg) + 64));
+	parallel_for(n_thr, nw, 512, [&](int t) { pack_list(regs[se_work[t]], hl + loff[t]); });
+	int *hw = (int *)W.h_wwork[0].ensure(roomy((size_t)nw * 4 + 64));
+	memcpy(hw, se_work.data(), (size_t)nw * 4);
+	uint8_t *hs = (uint8_t *)W.h_wstatus[0].ensure(roomy((size_t)nw + 64));
+	int *d_work = (int *)W.wwork[0].ensure(roomy((size_t)nw * 4));
+	DevReg *d_lists = (DevReg *)W.wlists[0].ensure(roomy(n_regs * sizeof(DevReg) + 64));
+	int *d_loff = (int *)W.wloff[0].ensure(roomy(((size_t)nw + 1) * 4));
+	uint8_t *d_ws = (uint8_t *)W.wstatus[0].ensure(roomy((size_t)nw + 64));
+	AlnReq *d_rq = (AlnReq *)W.wreq[0].ensure(roomy((size_t)nw * sizeof(AlnReq)));
+	SamDesc *d_ds = (SamDesc *)W.wdesc[0].ensure(roomy((size_t)nw * sizeof(SamDesc)));
+	HIP_OK(hipMemcpyAsync(d_work, hw, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+	if (n_regs) HIP_OK(hipMemcpyAsync(d_lists, hl, n_regs * sizeof(DevReg), hipMemcpyHostToDevice, st));
+	HIP_OK(hipMemcpyAsync(d_loff, loff, ((size_t)nw + 1) * 4, hipMemcpyHostToDevice, st));
+	HIP_OK(hipMemsetAsync(d_ws, 0, (size_t)nw, st));
+	AlnReq *d_xr = nullptr;
+	uint8_t *d_xc = nullptr, *hx = nullptr;
+	if (dev_se_xa) {   // the XA entries' requests, PW_XA_CAP per item, and their counts
+		d_xr = (AlnReq *)W.wxreq[0].ensure(roomy((size_t)nw * PW_XA_CAP * sizeof(AlnReq)));
+		d_xc = (uint8_t *)W.wxcnt[0].ensure(roomy((size_t)nw + 64));
+		hx = (uint8_t *)W.h_wxcnt[0].ensure(roomy((size_t)nw + 64));
+		HIP_OK(hipMemsetAsync(d_xc, 0, (size_t)nw, st));
+	}
+	launch_se_wave(st, wave_pp, nw, d_work, d_lists, d_loff, D.d_ann_alt, d_wave_tab + wave_n_tab, d_ws, d_rq, d_ds, d_xr, d_xc);
+	HIP_OK(hipMemcpyAsync(hs, d_ws, (size_t)nw, hipMemcpyDeviceToHost, st));
+	if (dev_se_xa) HIP_OK(hipMemcpyAsync(hx, d_xc, (size_t)nw, hipMemcpyDeviceToHost, st));
+	stream_wait(st);
+	HIP_OK(hipGetLastError());
+	se_wstatus = hs; se_wxcnt = hx;
+	for (int t = 0; t < nw; ++t) {   // its decisions: these reads are the device's from here on
+		const int i = se_work[t];
+		if (hs[t] == SE_DECIDED) { codes[i] = SE_DECIDED; wave_dec[i] = 1; ++n_se_wave; }
+		else if (hs[t] == SE_DECIDED_XA && dev_se_xa) { codes[i] = SE_DECIDED_XA; wave_dec[i] = 1; ++n_se_xa; }
+		else if (hs[t]) codes[i] = hs[t];   // (why not: for the statistics line)
+	}
+	if (n_se_wave + n_se_xa) pstat = codes;   // (se_simple_kernel may have taken none)
+	pair_dev_ms += now_ms() - tp0;
+}
+
+// The reads it decided carry 1 to 1 + PW_XA_CAP requests each, so they do not ride in the part's device job (one request per read, in
+// place): as for the XA pairs (xa_records), the host lays out their request bases (no request for any other read of the part), a kernel
+// moves requests and descriptors there, and one more CIGAR-and-SAM job runs over the part for these reads alone, queued before the
+// host plans the remaining reads.
+void Call::se_wave_records(Part &P)
+{
+	if (!dev_se_wave || n_se_wave + n_se_xa == 0) return;
+	const int s = P.slot, nw = (int)se_work.size(), nu = P.hi - P.lo;
+	P.xa_base.assign(nu + 1, 0);
+	int n_dec = 0;
+	for (int t = 0; t < nw; ++t) {
+		const int i = se_work[t];
+		if (i < P.lo || i >= P.hi || !wave_dec[i]) continue;
+		P.xa_base[i - P.lo + 1] = 1 + (se_wstatus[t] == SE_DECIDED_XA ? std::min<int>(se_wxcnt[t], PW_XA_CAP) : 0);
+		++n_dec;
+	}
+	if (n_dec == 0) return;
+	hipStream_t jst = C.d_streams[s];
+	for (int k = 0; k < nu; ++k) P.xa_base[k + 1] += P.xa_base[k];
+	int *dst = (int *)W.h_wxdst[s].ensure(roomy((size_t)nw * 4 + 64));
+	for (int t = 0; t < nw; ++t) {
+		const int i = se_work[t];
+		dst[t] = i >= P.lo && i < P.hi && wave_dec[i] ? (int)P.xa_base[i - P.lo] : -1;
+	}
+	const size_t n_req = P.xa_base[nu];
+	int *d_dst = (int *)W.wxdst[s].ensure(roomy((size_t)nw * 4));
+	AlnReq *d_rq = (AlnReq *)W.xa_req[s].ensure(roomy(n_req * sizeof(AlnReq)));
+	SamDesc *d_ds = (SamDesc *)W.xa_desc.ensure((size_t)n * sizeof(SamDesc));
+	HIP_OK(hipMemcpyAsync(d_dst, dst, (size_t)nw * 4, hipMemcpyHostToDevice, jst));
+	launch_se_wave_scatter(jst, nw, (const int *)W.wwork[0].p, d_dst, (const AlnReq *)W.wreq[0].p, (const SamDesc *)W.wdesc[0].p,
+	                       dev_se_xa ? (const AlnReq *)W.wxreq[0].p : nullptr, dev_se_xa ? (const uint8_t *)W.wxcnt[0].p : nullptr, d_rq, d_ds, P.lo, nu);
 	HIP_OK(hipGetLastError());
 	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
 	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
@@ -505,7 +608,8 @@ void Call::job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units)
 		bool any_back = false;
 		for (int k = 0; k < P.hi - P.lo && !any_back; ++k)
 			for (int e = 0; e < ends; ++e)
-				any_back = any_back || (pstat[P.lo + k] == 1 && (!wave_units || wave_dec[P.lo + k]) && J.solen[ends * k + e] < 0);
+				any_back = any_back || (pstat[P.lo + k] == 1 && (!wave_units || wave_dec[P.lo + k]) && !(dev_se_wave && wave_dec[P.lo + k]) &&
+				                        J.solen[ends * k + e] < 0);   // (se_wave_kernel's reads have a job of their own)
 		if (any_back) fetch_results(J);
 	}
 	aln_wait_ms += now_ms() - ta;
@@ -516,7 +620,7 @@ void Call::job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units)
 void Call::launch_dev(Part &P)
 {
 	stage(14);
-	if (!pstat || P.hi == P.lo) return;
+	if (!pstat || !d_pr_req || P.hi == P.lo) return;   // (!d_pr_req: a single-end chunk of which only se_wave_kernel took reads)
 	const int ends = pe ? 2 : 1;   // reads (and requests) per unit
 	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(512);
 	P.dev.small_used = small; P.dev.small_cnt = small + 8;
@@ -572,10 +676,11 @@ void Call::replay(Part &P, int which)
 	// (a single-end chunk without reads of the device's has no pass 0)
 	// per-block counters: a shared atomic bumped once per unit costs more than copying the unit's records
 	if (pe || which != 0 || pstat) parallel_blocks(n_thr, P.hi - P.lo, pe ? 128 : 256, [&](int, int, int k_lo, int k_hi) {
-		unsigned long long n_dev = 0, tsc = 0;
+		unsigned long long n_dev = 0, n_se_xa_w = 0, tsc = 0;
 		for (int k = k_lo; k < k_hi; ++k) {
 			const int i = P.lo + k, r = ends * i;   // the unit, its first read
-			const bool xa_k = pstat && pstat[i] == PW_DECIDED_XA;   // pair_wave_kernel's pair with an XA tag: the job of those
+			// pair_wave_kernel's pair with an XA tag, or se_wave_kernel's read (with or without one): the job of those
+			const bool xa_k = (pstat && pstat[i] == PW_DECIDED_XA) || (dev_se_wave && wave_dec[i]);
 			const bool dev_k = xa_k || (pstat && pstat[i] == 1);
 			const bool own_k = xa_k || (dev_k && P.wave.launched && wave_dec[i]);   // pair_wave_kernel's pair with the job of its own
 			const Job &J = xa_k ? P.xa : own_k ? P.wave : dev_k ? P.dev : P.host;
@@ -586,7 +691,8 @@ void Call::replay(Part &P, int which)
 			if (written) {
 				const unsigned long long tq0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
 				for (int e = 0; e < ends; ++e) take_record(r + e, J, ends * k + e);
-				n_dev += ends;
+				if (!pe && pstat[i] == SE_DECIDED_XA) ++n_se_xa_w;   // (counted apart: n_sam_dev stays the plain records of n_se_dev)
+				else n_dev += ends;
 				if (cpusec_on()) tsc += __builtin_ia32_rdtsc() - tq0;
 				continue;
 			}
@@ -604,10 +710,11 @@ void Call::replay(Part &P, int which)
 				sam_pe_emit(opt, bns, pac, pes, &seqs[r], &regs[r], plans[i], gpu_aln && !xa_k ? &ctx : nullptr, r);
 			} else {
 				if (dev_k) mark_primary_se(opt, regs[i], n_processed + i);
-				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln ? &ctx : nullptr, i);
+				// (se_wave_kernel's read handed back: up to 1 + PW_XA_CAP requests in the device's order, so the host aligns it itself)
+				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln && !xa_k ? &ctx : nullptr, i);
 			}
 		}
-		n_sam_dev += n_dev; tsc_devcopy += tsc;
+		n_sam_dev += n_dev; n_se_xa_sam += n_se_xa_w; tsc_devcopy += tsc;
 	});
 	emit_ms += now_ms() - ta;
 	cpu_emit += cpu_sec() - ca;
@@ -650,8 +757,15 @@ void Call::sam_stage()
 		parts[p].lo = p ? n_units / 2 : 0;
 		parts[p].hi = p == n_parts - 1 ? n_units : n_units / 2;
 	}
+	// single-end: se_wave_kernel on the reads se_simple_kernel left for long lists or an XA tag, before any job goes out (the host waits
+	// for its status bytes: behind the CIGAR kernel of 300 000 reads that wait was 5 ms per chunk, on an idle device it is not seen) ...
+	if (!pe) se_wave_decide();
 	if (!dev_late)
 		for (int p = 0; p < n_parts; ++p) launch_dev(parts[p]);
+	// ... and the job of the reads it decided, behind the device job of the part on the same stream: both run under the host's planning
+	// of the remaining reads
+	if (!pe)
+		for (int p = 0; p < n_parts; ++p) se_wave_records(parts[p]);
 	for (int p = 0; p < n_parts; ++p) { mcollect(parts[p]); mlaunch(parts[p]); }
 	for (int p = 0; p < n_parts; ++p) {   // (the mate-rescue kernels of all parts are running)
 		Part &P = parts[p];
@@ -688,11 +802,12 @@ void Call::report_decisions()
 	for (int k = 0; k < n_units; ++k) ++c[codes[k] & 31];
 	if (pe) { STAT.n_pair_dev = c[1] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs; }
 	else {
-		STAT.n_se_dev = c[1];
-		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu\n",
+		STAT.n_se_dev = c[SE_DECIDED]; STAT.n_se_wave_dev = n_se_wave; STAT.n_se_xa_dev = c[SE_DECIDED_XA]; STAT.n_se_xa_sam_dev = n_se_xa_sam.load();
+		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu; se_wave_kernel: handed %zu, decided plain %llu, decided with an XA tag %llu, XA records written %llu, list past %d %llu, tie %llu\n",
 		                      n_units, (unsigned long long)c[SE_DECIDED], (unsigned long long)c[SE_HOST_COMMENT], PR_MAXREG, (unsigned long long)c[SE_HOST_MAXREG],
 		                      (unsigned long long)c[SE_HOST_PATCH], (unsigned long long)c[SE_HOST_LENGTH], (unsigned long long)c[SE_HOST_ALT],
-		                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA]);
+		                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA], se_work.size(), (unsigned long long)n_se_wave,
+		                      (unsigned long long)c[SE_DECIDED_XA], n_se_xa_sam.load(), PW_MAXREG, (unsigned long long)c[SE_HOST_FULL], (unsigned long long)c[SE_HOST_TIE]);
 	}
 	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them and %llu with an XA tag, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
 	                      n_units, (unsigned long long)c[1], (unsigned long long)c[2], PR_MAXREG, (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[6],

@@ -321,6 +321,73 @@ extern "C" int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *b
 	                       xa_cnt);
 }
 
+// Stage entry of se_wave_kernel (se_wave_kernel.hip) for parity tests: n_work single-end reads given by their numbers in the chunk
+// (read_no[t]: id = n_processed + read_no[t], req.read = read_no[t]) and their regions as they stand after mem_sort_dedup_patch (regs:
+// DevReg records back to back, reg_off[n_work + 1]), through the pipeline's own launch function.  Everything is by work item t:
+// status[t] = 1 (SE_DECIDED): desc[t] (SamDesc) and req[t] (AlnReq; none for the unmapped record) are what mem_reg2sam reports with one
+// plain line; SE_DECIDED_XA (xa_req given): the line carries an XA tag of xa_cnt[t] entries, their requests at xa_req[t * PW_XA_CAP ..]
+// (pad = the entry's contig), the count also in desc[t].flag bits 16-19; else the code of the test that left the read to the host
+// (device.h: SE_HOST_*), desc[t].req = req[t].read = -1.  xa_req = NULL: without the XA listing.
+extern "C" int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
+                                    const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req)
+{
+	require_any_device();
+	if (n_work <= 0) return 0;
+	if (max_len <= 0) die("mi355x_se_wave_batch: max_len must be positive");
+	if (xa_req && !xa_cnt) die("mi355x_se_wave_batch: no room for the XA counts");
+	const size_t nw = (size_t)n_work;
+	memset(status, 0, nw);
+	memset(desc, 0xff, nw * sizeof(SamDesc));
+	memset(req, 0xff, nw * sizeof(AlnReq));
+	if (xa_cnt) memset(xa_cnt, 0, nw);
+	if (xa_req) memset(xa_req, 0xff, nw * PW_XA_CAP * sizeof(AlnReq));
+	// nothing the kernel indexes with may point outside what is uploaded
+	if (reg_off[0] != 0) die("mi355x_se_wave_batch: reg_off[0] must be 0");
+	for (size_t t = 0; t < nw; ++t) {
+		if (reg_off[t + 1] < reg_off[t]) die("mi355x_se_wave_batch: reg_off decreases at work item %zu", t);
+		if (read_no[t] < 0) die("mi355x_se_wave_batch: bad read number at work item %zu", t);
+	}
+	const size_t NR = (size_t)reg_off[nw];
+	const DevReg *hr = (const DevReg *)regs;
+	for (size_t j = 0; j < NR; ++j)
+		if (hr[j].rid < 0 || hr[j].rid >= bns->n_seqs) die("mi355x_se_wave_batch: bad contig in region %zu", j);
+	PairParams pp;
+	mem_pestat_t pes[4];
+	se_params(opt, bns->l_pac, n_processed, max_len, pp, pes);
+	std::vector<double> tab((size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, 0, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
+	const size_t PAD = 64;
+	DevArr<int> d_work(nw * 4 + PAD, read_no, nw * 4), d_loff((nw + 1) * 4 + PAD, reg_off, (nw + 1) * 4);
+	DevArr<DevReg> d_lists(NR * sizeof(DevReg) + PAD, regs, NR * sizeof(DevReg));
+	DevArr<uint8_t> d_aa(ann_alt.size() + PAD, ann_alt.data(), ann_alt.size()), d_ws(nw + PAD), d_xc;
+	DevArr<double> d_tab(tab.size() * 8 + PAD, tab.data(), tab.size() * 8);
+	DevArr<AlnReq> d_rq(nw * sizeof(AlnReq) + PAD), d_xr;
+	DevArr<SamDesc> d_ds(nw * sizeof(SamDesc) + PAD);
+	d_ws.fill(0, nw);
+	d_rq.fill(0xff, nw * sizeof(AlnReq));
+	d_ds.fill(0xff, nw * sizeof(SamDesc));
+	if (xa_req) {
+		d_xr = DevArr<AlnReq>(nw * PW_XA_CAP * sizeof(AlnReq) + PAD);
+		d_xc = DevArr<uint8_t>(nw + PAD);
+		d_xr.fill(0xff, nw * PW_XA_CAP * sizeof(AlnReq));
+		d_xc.fill(0, nw);
+	}
+	launch_se_wave(0, pp, n_work, d_work, d_lists, d_loff, d_aa, d_tab, d_ws, d_rq, d_ds, d_xr, d_xc);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	d_ws.download(status, nw);
+	d_ds.download(desc, nw * sizeof(SamDesc));
+	d_rq.download(req, nw * sizeof(AlnReq));
+	if (xa_req) {
+		d_xr.download(xa_req, nw * PW_XA_CAP * sizeof(AlnReq));
+		d_xc.download(xa_cnt, nw);
+	}
+	return 0;
+}
+
 extern "C" int mi355x_smem_batch(const mem_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off, int cap,
                                  uint64_t *intv_out, int *n_out, double *kernel_ms, uint64_t *algo_bytes)
 {

@@ -1,14 +1,15 @@
 """Single-end leg next to bench.py: trimmed single-end reads (BASELINE config 3: lengths uniform 50-300) through mem_process_seqs with
-the device path of the stage after the CIGAR kernel (se_simple_kernel, single-end sam_emit_kernel) and with MPIBWA_HOST_SE=1 (the host
-path: what the library did before it had one), alternately, on the same chunks.
+the device path of the stage after the CIGAR kernel (se_simple_kernel, se_wave_kernel, single-end sam_emit_kernel), with
+MPIBWA_HOST_SE_WAVE=1 (se_simple_kernel alone: reads with more than eight regions or an XA tag stay on the host) and with
+MPIBWA_HOST_SE=1 (the host path: what the library did before it had either), alternately, on the same chunks.
 
     python tools/bench_se.py [--reads N] [--chunks C] [--steps K] [--repeats R] [--genome-mbp M] [--out FILE]
 
 The reads come from the generator and the index cache bench.py uses (bigindex.make_or_get / simulate_pairs with 300-base reads; read 1 of
 every pair, cut to a seeded length in [50, 300]).  Every leg is a fresh child process under its own `timeout`; the run stops at the
 first leg that fails.  One JSON line per leg: Mreads/s, emit_ms and plan_ms per chunk, host CPU-seconds per chunk, n_se_dev / n_reads,
-n_sam_dev / n_reads and a hash of the SAM of all chunks, which must be the same in every leg.  A last child (one step, MPIBWA_CPUSEC=1)
-reports the status codes of se_simple_kernel."""
+n_sam_dev / n_reads, n_se_wave_dev, n_se_xa_dev and n_se_xa_sam_dev per chunk, and a hash of the SAM of all chunks, which must be the
+same in every leg.  A last child (one step, MPIBWA_CPUSEC=1) reports the status codes of the two deciding kernels."""
 import argparse
 import hashlib
 import json
@@ -68,6 +69,8 @@ def child(args):
         "host_cpu_s_per_chunk": round(cpu / n, 3),
         "se_dev_frac": round(acc.get("n_se_dev", 0) / max(1, acc.get("n_reads", 1)), 4),
         "sam_dev_frac": round(acc.get("n_sam_dev", 0) / max(1, acc.get("n_reads", 1)), 4),
+        "se_wave_dev_per_chunk": round(acc.get("n_se_wave_dev", 0) / n, 1), "se_xa_dev_per_chunk": round(acc.get("n_se_xa_dev", 0) / n, 1),
+        "se_xa_sam_dev_per_chunk": round(acc.get("n_se_xa_sam_dev", 0) / n, 1),
         "sam_sha256": h.hexdigest()}), flush=True)
 
 
@@ -84,7 +87,7 @@ def main():
     ap.add_argument("--workdir", default=os.environ.get("MPIBWA_BENCH_DIR", "/tmp/mpibwa_bench"))
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds a leg may take (index load included)")
     ap.add_argument("--out", help="also write the JSON lines to this file")
-    ap.add_argument("--leg", choices=["host", "dev", "codes"], help=argparse.SUPPRESS)
+    ap.add_argument("--leg", choices=["host", "nowave", "dev", "codes"], help=argparse.SUPPRESS)
     ap.add_argument("--rep", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
@@ -92,13 +95,16 @@ def main():
     lines = []
     passthrough = ["--reads", str(args.reads), "--chunks", str(args.chunks), "--seed", str(args.seed), "--genome-mbp", str(args.genome_mbp),
                    "--repeat-frac", str(args.repeat_frac), "--genome-model", args.genome_model, "--workdir", args.workdir]
-    legs = [(leg, rep) for rep in range(args.repeats) for leg in ("host", "dev")] + [("codes", 0)]
+    legs = [(leg, rep) for rep in range(args.repeats) for leg in ("host", "nowave", "dev")] + [("codes", 0)]
     for leg, rep in legs:
         env = dict(os.environ)
         env.pop("MPIBWA_HOST_SE", None)
+        env.pop("MPIBWA_HOST_SE_WAVE", None)
         env.pop("MPIBWA_CPUSEC", None)
         if leg == "host":
             env["MPIBWA_HOST_SE"] = "1"
+        if leg == "nowave":
+            env["MPIBWA_HOST_SE_WAVE"] = "1"
         if leg == "codes":
             env["MPIBWA_CPUSEC"] = "1"
         cmd = ["timeout", "-k", "10", str(args.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", leg, "--rep", str(rep),
@@ -112,16 +118,18 @@ def main():
         rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
         if leg == "codes":
             m = [ln for ln in p.stderr.splitlines() if ln.startswith("[se_kernel]")]
-            rec = {"leg": "status codes of se_simple_kernel, last chunk", "line": m[-1] if m else None, "sam_sha256": rec["sam_sha256"]}
+            rec = {"leg": "status codes of se_simple_kernel and se_wave_kernel, last chunk", "line": m[-1] if m else None, "sam_sha256": rec["sam_sha256"]}
             if m:
                 rec["counts"] = {k.strip(" ;:").replace("host: ", ""): int(v) for k, v in re.findall(r"([a-zA-Z>: ][a-zA-Z0-9>: ]*?) (\d+)(?=[,;]|$)", m[-1].split(":", 1)[1])}
         lines.append(rec)
         print(json.dumps(rec), flush=True)
     same = len({r["sam_sha256"] for r in lines}) == 1
-    by = {leg: [r for r in lines if r["leg"] == leg] for leg in ("host", "dev")}
+    by = {leg: [r for r in lines if r["leg"] == leg] for leg in ("host", "nowave", "dev")}
     summary = {"leg": "summary", "sam_identical_across_legs": same,
-               "host_mreads_s": [r["mreads_s"] for r in by["host"]], "dev_mreads_s": [r["mreads_s"] for r in by["dev"]],
-               "host_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["host"]], "dev_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["dev"]]}
+               "host_mreads_s": [r["mreads_s"] for r in by["host"]], "nowave_mreads_s": [r["mreads_s"] for r in by["nowave"]],
+               "dev_mreads_s": [r["mreads_s"] for r in by["dev"]],
+               "host_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["host"]],
+               "nowave_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["nowave"]], "dev_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["dev"]]}
     lines.append(summary)
     print(json.dumps(summary), flush=True)
     if args.out:
