@@ -524,6 +524,13 @@ int64_t mi355x_fixmate(bseq1_t *seqs, int n, const bntseq_t *bns);
 size_t  mi355x_bgzf_bound(size_t len);
 size_t  mi355x_bgzf_compress(const char *text, size_t len, int level, uint8_t *out, size_t cap);
 size_t  mi355x_bgzf_eof(uint8_t out[28]);
+/* The same blocks made on the device: the cuts and the contract of mi355x_bgzf_compress — out needs mi355x_bgzf_bound(len)
+ * bytes, returns the compressed size, 0 when cap is too small or len is 0 — with the device encoder's one setting instead of a level
+ * (LZ77 matches and dynamic Huffman codes, stored blocks where they are smaller).  The same text gives the same bytes on every call.
+ * Needs a usable MI355X, no CPU fallback; re-entrant, also beside mem_process_seqs calls in flight; mi355x_finalize() gives its
+ * buffers back.  mi355x_bgzf_dev_counts: blocks, blocks written stored, bytes of text, bytes of blocks — since load, all callers. */
+size_t  mi355x_bgzf_compress_dev(const char *text, size_t len, uint8_t *out, size_t cap);
+void    mi355x_bgzf_dev_counts(uint64_t out[4]);
 /* mpiBWAByChr's routing (src/mainParallelByChromosome.c:1340-1455, :3437-3486): the records of `sam` by destination — contig
  * 0 .. n_seqs-1 by RNAME, then "discordant" (only when discordant != 0; a record whose RNAME and RNEXT are two different contigs
  * goes to its contig AND there), last "unmapped" (RNAME '*').  out_text[d] (malloc, NULL when empty) / out_len[d] for

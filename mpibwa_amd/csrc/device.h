@@ -461,6 +461,19 @@ void launch_seed_prep(void *stream, int n_reads, int cap, uint64_t *d_intv, cons
 void launch_seed_enum(void *stream, int n_reads, int cap, const uint64_t *d_intv, const int *d_nintv, int max_occ,
                       const int64_t *d_seed_off, uint64_t *d_rows, int32_t *d_qbeg_len);
 
+// ---- BGZF blocks on the device (bgzf_kernel.hip, bgzf_stage.hip) ----
+#define BGZF_DEV_INPUT 0xff00     // text per block (sampost.cpp: BGZF_INPUT)
+// block b = d_text[d_cut[b] .. d_cut[b + 1]) (1 .. BGZF_DEV_INPUT bytes; d_text has 16 bytes of slack behind the last block) into the 64-KiB
+// slot d_slots + b * 65536 as one complete BGZF block of d_sizes[b] bytes; d_meta[1] += the blocks written stored.  `grid` workgroups of
+// one wavefront, each with BGZF_DEV_INPUT 16-bit words of d_tokens.
+void launch_bgzf_deflate(void *stream, const uint8_t *d_text, const uint32_t *d_cut, int n_blocks, uint8_t *d_slots, uint32_t *d_sizes,
+                         uint16_t *d_tokens, int grid, unsigned long long *d_meta);
+// the slots closed up into d_out; d_meta[0] = the bytes
+void launch_bgzf_gather(void *stream, const uint8_t *d_slots, const uint32_t *d_sizes, int n_blocks, uint8_t *d_out, unsigned long long *d_meta);
+void release_bgzf_contexts();     // the idle ones' buffers and streams (mi355x_finalize)
+// the calling thread on the device of the resident index, or, before any index, on device 0 after the checks of mi355x_init
+void use_device();
+
 SmemParams smem_params(const mem_opt_t *opt);
 int clamp_band(const mem_opt_t *opt, int qlen, int w, int end_bonus);
 

@@ -76,7 +76,8 @@ void PinBuf::release()
 	p = nullptr; cap = 0;
 }
 
-static void require_device(int local_rank)
+// the device of a rank, after the checks: a usable gfx950 (this thread is then on it)
+static int checked_device(int local_rank)
 {
 	int n = 0;
 	hipError_t e = hipGetDeviceCount(&n);
@@ -87,7 +88,21 @@ static void require_device(int local_rank)
 	HIP_OK(hipGetDeviceProperties(&prop, local_rank % n));
 	if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
 		die("device %d is %s; this library carries gfx950 (MI355X) code objects only", local_rank % n, prop.gcnArchName);
-	g_idx.device = local_rank % n;
+	return local_rank % n;
+}
+static void require_device(int local_rank) { g_idx.device = checked_device(local_rank); }
+
+void use_device()
+{
+	static std::atomic<int> checked(-1);   // device 0 after the checks, for calls before any index (or after mi355x_finalize)
+	int d = g_idx.device;
+	if (d < 0 && (d = checked.load()) < 0) {
+		static std::mutex mu;
+		std::lock_guard<std::mutex> lk(mu);
+		if (checked.load() < 0) checked = checked_device(0);
+		d = checked.load();
+	}
+	HIP_OK(hipSetDevice(d));
 }
 
 static uint64_t index_hash(const bwt_t *bwt, const bntseq_t *bns)
@@ -545,4 +560,5 @@ extern "C" void mi355x_finalize(void)
 	free_derived_tables();
 	g_idx = DevIndex();
 	release_idle_work_buffers();   // a process that is done with this index gives the HBM of its call contexts back too
+	release_bgzf_contexts();
 }

@@ -15,6 +15,9 @@ namespace mbw {
 void fill_cnt_table(uint32_t tab[256]);
 extern const uint8_t *const nt4_table_ptr;
 #define nt4_table nt4_table_ptr
+// sampost.cpp: where the BGZF blocks of `len` bytes of text start and end (cut[0] = 0 .. cut[n_blocks] = len), the one rule of the host
+// path and the device path (bgzf_stage.hip)
+void bgzf_cuts(const char *text, size_t len, std::vector<size_t> &cut);
 
 // ---- plain records exchanged between host stages and HIP kernels ----
 

@@ -340,6 +340,22 @@ extern "C" int64_t mi355x_fixmate(bseq1_t *seqs, int n, const bntseq_t *bns)
 }
 
 // ---- BGZF ----
+// The cuts of both BGZF paths (this file's and the device's, bgzf_stage.hip): at most BGZF_INPUT bytes per block, cut back to the last
+// record end where there is one.
+void mbw::bgzf_cuts(const char *text, size_t len, std::vector<size_t> &cut)
+{
+	cut.assign(1, 0);
+	for (size_t at = 0; at < len;) {
+		size_t n = std::min(BGZF_INPUT, len - at);
+		if (at + n < len) {
+			const void *nl = memrchr(text + at, '\n', n);
+			if (nl) n = (size_t)((const char *)nl - (text + at)) + 1;
+		}
+		at += n;
+		cut.push_back(at);
+	}
+}
+
 // room for the compressed form of `len` bytes of text
 extern "C" size_t mi355x_bgzf_bound(size_t len) { return (len / (BGZF_INPUT / 2) + 2) * BGZF_MAX; }
 
@@ -350,16 +366,8 @@ extern "C" size_t mi355x_bgzf_bound(size_t len) { return (len / (BGZF_INPUT / 2)
 extern "C" size_t mi355x_bgzf_compress(const char *text, size_t len, int level, uint8_t *out, size_t cap)
 {
 	if (level > 9 || level < 0) level = Z_DEFAULT_COMPRESSION;
-	std::vector<size_t> cut(1, 0);
-	for (size_t at = 0; at < len;) {
-		size_t n = std::min(BGZF_INPUT, len - at);
-		if (at + n < len) {
-			const void *nl = memrchr(text + at, '\n', n);
-			if (nl) n = (size_t)((const char *)nl - (text + at)) + 1;
-		}
-		at += n;
-		cut.push_back(at);
-	}
+	std::vector<size_t> cut;
+	bgzf_cuts(text, len, cut);
 	const size_t n_blocks = cut.size() - 1;
 	if (n_blocks * BGZF_MAX > cap) return 0;
 	std::vector<uint32_t> clen(n_blocks);

@@ -1,6 +1,6 @@
 /* mpibwa_gpu.c — a thin MPI host program around the C ABI of libmpibwa_amd.so: one rank per GPU,
  *
- *     mpiexec -n N mpibwa_gpu mem [bwa mem options] [-f] [-g | -b] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]
+ *     mpiexec -n N mpibwa_gpu mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]
  *
  * The `mem` options are the reference's (src/mainParallel.c:291-398: -k -w -A -B -O -E -L -U -T -c -d -r -D -m -s -G -N -W -y -X -h -Q -I -R -H
  * -P -a -M -S -Y -V -5 -q -j -C -v -t -K -x -o, and its output options -f (fixmate, :395), -g (BGZF, :299), -b (BGZF + EOF block under the
@@ -32,7 +32,9 @@
  * Behind the call (the caller's side; the passes are the library's, csrc/sampost.cpp): -f rewrites the lines of every pair with
  * the mate's fields and the MQ / MC / ms tags (src/fixmate.c:601-827), -g / -b compress a chunk's text into BGZF blocks of whole records
  * (src/parallel_aux.c:2941-3176; every record is written — the reference drops the last read of each thread's slice), --by-chr routes the
- * records by RNAME (src/mainParallelByChromosome.c:1340-1455, :3437-3486).
+ * records by RNAME (src/mainParallelByChromosome.c:1340-1455, :3437-3486).  --device-bgzf (with -g or -b): the chunks' blocks are made by the
+ * library's deflate kernel (mi355x_bgzf_compress_dev) instead of zlib on the rank's cores — same cuts, same text inside, other bytes;
+ * --level then has no effect; the header's blocks stay zlib's.
  *
  * Plain C99 + MPI + pthreads; built by mpibwa_amd/build.py when an MPI installation is found (mpibwa_amd/mpibwa_gpu).
  */
@@ -194,6 +196,7 @@ typedef struct {
 	int paired, lockstep, trimmed, copy_comment;
 	const mem_pestat_t *pes0;    /* -I */
 	int fixmate;                 /* -f */
+	int device_bgzf;             /* --device-bgzf: a chunk's blocks come from mi355x_bgzf_compress_dev */
 	int format, level;           /* 2 SAM text, 1 / 0 BGZF blocks (-b / -g: src/mainParallel.c:226, 298-299); zlib level (3: src/mainParallel.c:227) */
 	int by_chr, n_dest;          /* --by-chr: records go to dest[0 .. n_dest) (contigs, [discordant], unmapped) instead of `out` */
 	MPI_File *dest;
@@ -250,7 +253,7 @@ static void write_text(loop_t *L, MPI_File fh, const char *text, size_t len, voi
 	if (L->format != 2) {
 		const size_t cap = mi355x_bgzf_bound(len);
 		uint8_t *z = grown(zbuf, czbuf, cap);
-		n = mi355x_bgzf_compress(text, len, L->level, z, cap);
+		n = L->device_bgzf ? mi355x_bgzf_compress_dev(text, len, z, cap) : mi355x_bgzf_compress(text, len, L->level, z, cap);
 		if (len && !n) DIE("BGZF: %zu bytes of text do not fit their buffer", len);
 		out = (const char *)z;
 	}
@@ -365,6 +368,12 @@ static void *chunk_worker(void *arg)
 	return 0;
 }
 
+static void usage(const char *prog)
+{
+	if (g_rank == 0) fprintf(stderr, "usage: mpiexec -n N %s mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--level L] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]\n"
+	                         "  --device-bgzf   with -g or -b: compress the chunks' BGZF blocks on the GPU (one setting: --level has no effect on them)\n", prog);
+}
+
 int main(int argc, char **argv)
 {
 	int provided = MPI_THREAD_SINGLE;
@@ -373,14 +382,14 @@ int main(int argc, char **argv)
 	MPI_Comm_size(MPI_COMM_WORLD, &g_size);
 	int n_threads = 0, copy_comment = 0, dry = 0, n_workers = 6, prewarm = 1;
 	int dofixmate = 0, write_format = 2, compression_level = 3, by_chr = 0;   /* src/mainParallel.c:223-227 */
-	int ordered = 0;
+	int ordered = 0, device_bgzf = 0, level_given = 0;
 	int scale_a = 0, set_b = 0, set_T = 0, set_U = 0, set_d = 0, set_O = 0, set_E = 0, set_L = 0, set_k = 0, set_r = 0, set_W = 0;
 	const char *mode = 0;   /* -x: a preset of the options the user did not set (src/mainParallel.c:294, 398-428) */
 	int64_t K = 0;
 	const char *out_path = 0, *pos[4];
 	int n_pos = 0;
 	if (argc < 2 || strcmp(argv[1], "mem") != 0) {
-		if (g_rank == 0) fprintf(stderr, "usage: mpiexec -n N %s mem [bwa mem options] [-f] [-g | -b] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]\n", argv[0]);
+		usage(argv[0]);
 		MPI_Finalize();
 		return 1;
 	}
@@ -396,7 +405,8 @@ int main(int argc, char **argv)
 		if (!strcmp(a, "--no-prewarm")) { prewarm = 0; continue; }
 		if (!strcmp(a, "--by-chr")) { by_chr = 1; continue; }
 		if (!strcmp(a, "--ordered")) { ordered = 1; continue; }
-		if (!strcmp(a, "--level") && i + 1 < argc) { compression_level = atoi(argv[++i]); continue; }
+		if (!strcmp(a, "--device-bgzf")) { device_bgzf = 1; continue; }
+		if (!strcmp(a, "--level") && i + 1 < argc) { compression_level = atoi(argv[++i]); level_given = 1; continue; }
 		if (!strcmp(a, "--in-flight") && i + 1 < argc) { n_workers = atoi(argv[++i]); continue; }
 		if (a[0] != '-' || !a[1]) { if (n_pos < 3) pos[n_pos++] = a; continue; }
 		if (a[2]) DIE("unknown option %s (options take their value as the next argument)", a);
@@ -511,6 +521,13 @@ int main(int argc, char **argv)
 		if (!set_U) opt->pen_unpaired *= opt->a;
 	}
 	bwa_fill_scmat(opt->a, opt->b, opt->mat);
+	if (device_bgzf && write_format == 2) {   /* nothing to compress */
+		if (g_rank == 0) fprintf(stderr, "[mpibwa_gpu] --device-bgzf needs -g or -b\n");
+		usage(argv[0]);
+		MPI_Finalize();
+		return 1;
+	}
+	if (device_bgzf && level_given && g_rank == 0) fprintf(stderr, "[mpibwa_gpu] --level has no effect on the chunks' blocks with --device-bgzf (the device encoder has one setting)\n");
 	if (n_pos < 2 || (!out_path && !dry)) DIE("need -o OUT PREFIX R1 [R2]");
 	const char *prefix = pos[0];
 	const int paired = n_pos == 3;
@@ -721,7 +738,7 @@ int main(int argc, char **argv)
 	memset(&L, 0, sizeof L);
 	L.opt = opt; L.idx = idx; L.win = win; L.out = out; L.f1 = f1.fh; L.f2 = paired ? f2.fh : MPI_FILE_NULL;
 	L.tab = tab_all; L.n_chunks = n_chunks; L.paired = paired; L.lockstep = lockstep; L.trimmed = trimmed; L.copy_comment = copy_comment; L.pes0 = pes0;
-	L.fixmate = dofixmate; L.format = write_format; L.level = compression_level; L.by_chr = by_chr; L.n_dest = n_dest; L.dest = dest;
+	L.fixmate = dofixmate; L.device_bgzf = device_bgzf; L.format = write_format; L.level = compression_level; L.by_chr = by_chr; L.n_dest = n_dest; L.dest = dest;
 	L.serialize = provided < MPI_THREAD_MULTIPLE;
 	L.t_start = t_loop;
 	pthread_mutex_init(&L.mpi_mu, 0);
@@ -741,6 +758,15 @@ int main(int argc, char **argv)
 		const long long n_reads = (long long)f1.n_total * (paired ? 2 : 1);
 		fprintf(stderr, "[mpibwa_gpu] chunk loop: %lld reads in %lld chunks, %d rank(s) x %d chunks in flight, %.3f s = %.3f Mreads/s\n", n_reads, n_chunks, g_size,
 		        n_workers, dt, dt > 0 ? n_reads / dt * 1e-6 : 0.);
+	}
+	if (device_bgzf) {   /* what the device path did, over all ranks */
+		uint64_t dc[4];
+		unsigned long long mine[4], all[4] = {0, 0, 0, 0};
+		mi355x_bgzf_dev_counts(dc);
+		for (int k = 0; k < 4; ++k) mine[k] = (unsigned long long)dc[k];
+		MPI_OK(MPI_Reduce(mine, all, 4, MPI_UNSIGNED_LONG_LONG, MPI_SUM, 0, MPI_COMM_WORLD));
+		if (g_rank == 0 && bwa_verbose >= 3)
+			fprintf(stderr, "[mpibwa_gpu] device BGZF: %llu blocks (%llu stored), %llu bytes of text -> %llu bytes\n", all[0], all[1], all[2], all[3]);
 	}
 	if (write_format == 1 && g_rank == 0) {   /* the empty block that ends the file the reference calls BAM (src/mainParallel.c:1508-1516) */
 		uint8_t eof[28];
