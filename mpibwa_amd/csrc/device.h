@@ -322,8 +322,19 @@ bool pair_params(const mem_opt_t *opt, int64_t l_pac, const mem_pestat_t pes[4],
 void pair_tables(const mem_opt_t *opt, const mem_pestat_t pes[4], const PairParams &P, size_t n_tab, double *tab);
 // per read of a sub-batch: its first PR_MAXREG regions and its number of regions, into chunk-wide arrays (d_first: PR_MAXREG records per read)
 void launch_first_reg(void *stream, int n, const int *d_reg_pos, const int *d_nregs, const DevReg *d_packed, DevReg *d_first, int *d_nfirst);
-// status[k] = 1: pair k is decided; reqs[2k .. 2k+1] and desc[2k .. 2k+1] are what the host's COLLECT pass would have listed
-// (desc.req = 0 / 1, relative to the pair's first request); status 0: the host's pair (reqs marked read = -1)
+// status codes of pair_simple_kernel: PR_DECIDED, or the test that left the pair to the host (statistics, and which pairs pair_wave_kernel takes)
+#define PR_HOST 0                 // not looked at
+#define PR_DECIDED 1              // reqs[2k .. 2k+1] and desc[2k .. 2k+1] are what the host's COLLECT pass would have listed
+#define PR_HOST_NO_HIT 2          // an end without a hit, or a pair the host did not pass (comment column, unequal names)
+#define PR_HOST_MAXREG 3          // more than PR_MAXREG regions on an end, or more candidate pairs than the kernel sorts
+#define PR_HOST_PATCH 4           // two hits the host has to try to patch
+#define PR_HOST_LENGTH 6          // a hit on an ALT contig or longer than the per-length table
+#define PR_HOST_RESCUE 7          // the rescue loop would align something
+#define PR_HOST_NO_PAIR 8         // no pair in a proper orientation and distance: the ends are reported independently
+#define PR_HOST_SCORE 9           // the best pair scores nothing
+#define PR_HOST_SUPP 10           // an end with a second primary hit of at least T: the single-end logic's case
+#define PR_HOST_XA 11             // a secondary hit close enough to its primary for an XA entry
+// (desc.req = 0 / 1, relative to the pair's first request; the host's pairs: reqs marked read = -1)
 void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,
                         const int64_t *d_ann_off, const uint8_t *d_ann_alt, const double *d_ptab, const double *d_ltab, uint8_t *d_status,
                         AlnReq *d_reqs, SamDesc *d_desc);
@@ -331,24 +342,24 @@ void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const De
 // ---- pairing decisions of the pairs with mate rescue or up to PW_MAXREG hits per end (pair_wave_kernel.hip), a pair per wavefront ----
 #define PW_MAXREG 64              // regions per end, going in and while rescued hits are added
 extern "C" int mi355x_pair_wave_maxreg(void);
-// status codes of pair_wave_kernel: pair_simple_kernel's where the test is the same (6 ALT/length, 8 no proper pair, 9 score, 10 second
-// primary hit, 11 XA), and three of its own
-#define PW_HOST_LENGTH 6
-#define PW_HOST_NO_PAIR 8
-#define PW_HOST_SCORE 9
-#define PW_HOST_SUPP 10
-#define PW_HOST_XA 11
+// status codes of pair_wave_kernel: pair_simple_kernel's where the test is the same (PR_DECIDED too: decided, both records plain), and
+// four of its own
+#define PW_HOST_LENGTH PR_HOST_LENGTH
+#define PW_HOST_NO_PAIR PR_HOST_NO_PAIR
+#define PW_HOST_SCORE PR_HOST_SCORE
+#define PW_HOST_SUPP PR_HOST_SUPP
+#define PW_HOST_XA PR_HOST_XA
 #define PW_HOST_NO_RESULT 12      // a rescue alignment the replay needs is not on the device (not listed, flagged by msw2_kernel, host only)
 #define PW_HOST_FULL 13           // a list past PW_MAXREG
 #define PW_HOST_TIE 14            // the outcome depends on the reference's unstable sorts (equal end positions, equal (score, hash))
-#define PW_DECIDED_XA 16          // decided, and at least one of the two records carries an XA tag (status 1: decided, both records plain)
+#define PW_DECIDED_XA 16          // decided, and at least one of the two records carries an XA tag
 #define PW_XA_CAP 8               // XA entries per record the kernel lists; a call with max_XA_hits beyond it runs without XA on the device
 extern "C" int mi355x_pair_wave_xa_cap(void);
 // tags per (end, candidate hit, orientation): >= 0 the alignment's number in the pair's slice of the mate-rescue requests
 #define PW_TAG_NO_WINDOW (-1)     // mem_matesw would align nothing there (src/bwamem_pair.c:150)
 #define PW_TAG_HOST (-2)          // not listed (explained by a mate hit before any rescue) or a window msw2_kernel does not take
 // work[t]: the pair's number in the chunk (reads 2 work[t], 2 work[t] + 1 of d_len); reqs / desc [2t + e] are written when
-// wstatus[t] = 1 or PW_DECIDED_XA and left alone otherwise; lists[loff[2t + e] .. loff[2t + e + 1]): end e's regions after mem_sort_dedup_patch;
+// wstatus[t] = PR_DECIDED or PW_DECIDED_XA and left alone otherwise; lists[loff[2t + e] .. loff[2t + e + 1]): end e's regions after mem_sort_dedup_patch;
 // mreq / mres[mfirst[t] + tag]; tags[toff[t] ..]: 4 per candidate hit, end 0's candidates first
 void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
                       const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
@@ -357,10 +368,6 @@ void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *
 // d_xa_reqs given (and max_XA_hits <= PW_XA_CAP): a pair whose chosen hits carry XA entries (src/bwamem_extra.c:98-118) is decided too,
 // with status PW_DECIDED_XA: xa_cnt[2t + e] entries of end e, their requests (as mem_reg2aln would ask, pad = the hit's contig) at
 // xa_reqs[(2t + e) * PW_XA_CAP ..], desc[2t + e].flag bits 16-19 = the count, desc[2t].req = 0, desc[2t + 1].req = 1 + xa_cnt[2t].
-// The XA pairs' requests and descriptors to their places in a job of their own: dst[t] = first request of work item t's pair in
-// `reqs`, or < 0 (not an XA pair); [req of read 0, its XA requests, req of read 1, its XA requests]; desc: chunk-wide, by read
-void launch_pair_wave_xa_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
-                                 const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
 // the decided pairs' records into the chunk-wide arrays (reqs / desc [2 work[t] + e]); clear_n > 0: reads clear_r0 .. + clear_n are
 // marked "not the device's" first (the arrays then describe the wave's pairs alone)
 void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const uint8_t *d_wstatus, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
@@ -398,11 +405,14 @@ static_assert(PW_MAXREG <= 64, "PairParams::lnq holds sub_n up to PW_MAXREG - 1"
 // xa_reqs[t * PW_XA_CAP ..], desc[t].flag bits 16-19 = the count.  Without them such a read gets SE_HOST_XA.
 void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const uint8_t *d_ann_alt,
                     const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc, AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr);
-// the decided reads' requests and descriptors to their places in a job of their own: dst[t] = first request of work item t's read in
-// `reqs`, or < 0 (not in the job); [the line's request, its XA requests]; desc: chunk-wide, by read; clear_n > 0: reads clear_r0 .. +
-// clear_n of desc are marked "not the device's" first
-void launch_se_wave_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
-                            const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
+
+// ---- the units a wave kernel decided, into a CIGAR-and-SAM job of their own (wave_scatter_kernel, se_wave_kernel.hip) ----
+// ends = 2: pair_wave_kernel's work list, 1: se_wave_kernel's.  dst[t] = first request of work item t's unit in `reqs`, or < 0 (not in
+// the job); per end [the end's request (an unused slot for the unmapped single-end record), its min(xa_cnt, PW_XA_CAP) XA requests, none
+// without d_xa_cnt]; desc[ends * work[t] + e]: chunk-wide, by read; clear_n > 0: reads clear_r0 .. + clear_n of desc are marked "not
+// the device's" first
+void launch_wave_job_scatter(void *stream, int ends, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                             const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
 
 // ---- the redundancy pass of mem_sort_dedup_patch on the raw region lists (dedup_kernel.hip) ----
 #define DD_MAXREG 512             // regions per read dedup_wave_kernel takes (its LDS footprint)

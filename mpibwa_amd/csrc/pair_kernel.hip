@@ -67,7 +67,7 @@ __device__ __forceinline__ void sort_pairs(int n, Pair64 *v)
 	for (int i = 0; i < n; ++i) v[i] = t[o[i]];
 }
 
-// status[k]: 1 = decided here; 0 / 2..: the host's pair (the number says which test sent it there: statistics only)
+// status[k]: PR_DECIDED = decided here; else the host's pair (device.h: PR_HOST_* says which test sent it there)
 __global__ void __launch_bounds__(64)
 pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, const int *__restrict__ nfirst, const uint8_t *__restrict__ pair_ok,
                    const i64 *__restrict__ ann_off, const uint8_t *__restrict__ ann_alt, const double *__restrict__ ptab, const double *__restrict__ ltab,
@@ -79,9 +79,9 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 	none.rb = none.re = 0; none.read = -1; none.qb = none.qe = none.w2 = none.truesc = none.pad = 0;
 	reqs[2 * k] = none; reqs[2 * k + 1] = none;
 	desc[2 * k].req = -1; desc[2 * k + 1].req = -1;
-	status[k] = 0;
+	status[k] = PR_HOST;
 	int n[2] = {nfirst[2 * k], nfirst[2 * k + 1]};
-	if (!pair_ok[k]) { status[k] = 2; return; }
+	if (!pair_ok[k]) { status[k] = PR_HOST_NO_HIT; return; }
 	if (n[0] == 0 && n[1] == 0) {   // no hit on either end: the two "unmapped" records need no decision at all (src/bwamem_pair.c:363-391, flags 77 / 141)
 		for (int e = 0; e < 2; ++e) {
 			SamDesc d;
@@ -89,22 +89,22 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 			d.flag = 0x1 | 0x4 | 0x8 | 0x40 << e; d.mapq = 0; d.score = 0; d.sub = 0;
 			desc[2 * k + e] = d;
 		}
-		status[k] = 1;
+		status[k] = PR_DECIDED;
 		return;
 	}
-	if (n[0] < 1 || n[1] < 1) { status[k] = 2; return; }
-	if (n[0] > PR_MAXREG || n[1] > PR_MAXREG) { status[k] = 3; return; }
+	if (n[0] < 1 || n[1] < 1) { status[k] = PR_HOST_NO_HIT; return; }
+	if (n[0] > PR_MAXREG || n[1] > PR_MAXREG) { status[k] = PR_HOST_MAXREG; return; }
 	PReg a[2][PR_MAXREG];
 	for (int e = 0; e < 2; ++e) {
 		DevReg r[PR_MAXREG];
 		for (int j = 0; j < n[e]; ++j) r[j] = first[(size_t)(2 * k + e) * PR_MAXREG + j];
 		n[e] = dedup_small(P, r, n[e]);
-		if (n[e] < 0) { status[k] = 4; return; }   // two hits the host has to try to patch
+		if (n[e] < 0) { status[k] = PR_HOST_PATCH; return; }   // two hits the host has to try to patch
 		for (int j = 0; j < n[e]; ++j) {
 			a[e][j].d = r[j]; a[e][j].sub = a[e][j].sub_n = 0; a[e][j].secondary = a[e][j].secondary_all = -1; a[e][j].hash = 0;
-			if (ann_alt[r[j].rid]) { status[k] = 6; return; }
+			if (ann_alt[r[j].rid]) { status[k] = PR_HOST_LENGTH; return; }
 			const int l = r[j].qe - r[j].qb > r[j].re - r[j].rb ? r[j].qe - r[j].qb : (int)(r[j].re - r[j].rb);
-			if (l >= P.ltab_n || l <= 0) { status[k] = 6; return; }
+			if (l >= P.ltab_n || l <= 0) { status[k] = PR_HOST_LENGTH; return; }
 		}
 	}
 	// the rescue loop would not align anything (src/bwamem_pair.c:263-272): every candidate hit is explained by the mate's hits
@@ -114,7 +114,7 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 			for (int j = 0; j < n[e] && nb < P.max_matesw; ++j) {
 				if (a[e][j].d.score < a[e][0].d.score - P.pen_unpaired) continue;
 				++nb;
-				if (!no_rescue_needed(P, a[e][j].d, a[!e], n[!e])) { status[k] = 7; return; }
+				if (!no_rescue_needed(P, a[e][j].d, a[!e], n[!e])) { status[k] = PR_HOST_RESCUE; return; }
 			}
 		}
 	const u64 id = P.id0 + (u64)k;
@@ -139,8 +139,8 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		});
 		y[v[i].y & 3] = i;
 	}
-	if (nu > PR_MAXPAIR) { status[k] = 3; return; }   // (ks_small_introsort_at: at most 16 elements)
-	if (nu == 0) { status[k] = 8; return; }   // no pair in a proper orientation and distance: the host reports the ends independently
+	if (nu > PR_MAXPAIR) { status[k] = PR_HOST_MAXREG; return; }   // (ks_small_introsort_at: at most 16 elements)
+	if (nu == 0) { status[k] = PR_HOST_NO_PAIR; return; }   // no pair in a proper orientation and distance: the host reports the ends independently
 	const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
 	sort_pairs<PR_MAXPAIR>(nu, u);
 	int z[2];
@@ -153,10 +153,10 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 	int subo = nu > 1 ? (int)(u[nu - 2].x >> 32) : 0, n_sub = 0;
 	for (int j = nu - 2; j >= 0; --j)
 		if (subo - (int)(u[j].x >> 32) <= tmp) ++n_sub;
-	if (o <= 0) { status[k] = 9; return; }
+	if (o <= 0) { status[k] = PR_HOST_SCORE; return; }
 	for (int e = 0; e < 2; ++e)   // an end with several good primary hits is left to the single-end logic (src/bwamem_pair.c:303-309)
 		for (int j = 1; j < n[e]; ++j)
-			if (a[e][j].secondary < 0 && a[e][j].d.score >= P.T) { status[k] = 10; return; }
+			if (a[e][j].secondary < 0 && a[e][j].d.score >= P.T) { status[k] = PR_HOST_SUPP; return; }
 	const int score_un = a[0][0].d.score + a[1][0].d.score - P.pen_unpaired;
 	const int q_pe = mapq_pe(o, subo, score_un, P.lnq[n_sub], P.a, a[0][0].d.frac_rep, a[1][0].d.frac_rep);   // (n_sub < PR_MAXPAIR; lnq[0] = 0)
 	int q_se[2], extra_flag = 1;   // (0x1: PairPlan::extra_flag starts at 1)
@@ -184,7 +184,7 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 	for (int e = 0; e < 2; ++e)
 		for (int j = 0; j < n[e]; ++j) {
 			const int kk = a[e][j].secondary_all;
-			if (kk >= 0 && a[e][j].d.score >= a[e][kk].d.score * (double)P.XA_drop_ratio) { status[k] = 11; return; }
+			if (kk >= 0 && a[e][j].d.score >= a[e][kk].d.score * (double)P.XA_drop_ratio) { status[k] = PR_HOST_XA; return; }
 		}
 	for (int e = 0; e < 2; ++e) {
 		const PReg &R = a[e][z[e]];
@@ -197,7 +197,7 @@ pair_simple_kernel(PairParams P, int n_pairs, const DevReg *__restrict__ first, 
 		d.flag = 0x40 << e | extra_flag; d.mapq = q_se[e] & 0xff; d.score = R.d.score; d.sub = R.sub;
 		desc[2 * k + e] = d;
 	}
-	status[k] = 1;
+	status[k] = PR_DECIDED;
 }
 
 void launch_pair_simple(void *stream, const PairParams &P, int n_pairs, const DevReg *d_first, const int *d_nfirst, const uint8_t *d_ok,

@@ -114,7 +114,7 @@ __device__ __forceinline__ void pw_pairs_of(const PairParams &P, const Pair64 *V
 
 // work[t]: the pair (number in the chunk); its lists: lists[loff[2t + e] .. loff[2t + e + 1]); its mate-rescue alignments:
 // mreq / mres[mfirst[t] ..]; tags[toff[t] + 4 * (candidate) + orientation], the candidates of end 0 first, then end 1's (toff: n_work + 1 entries).
-// wstatus[t] = 1: reqs / desc [2t + e] are the pair's, as pair_simple_kernel writes them (reqs.read = 2 work[t] + e); else untouched.
+// wstatus[t] = PR_DECIDED: reqs / desc [2t + e] are the pair's, as pair_simple_kernel writes them (reqs.read = 2 work[t] + e); else untouched.
 // xa_reqs given: a chosen hit with XA entries no longer sends the pair to the host.  wstatus[t] = PW_DECIDED_XA, xa_cnt[2t + e] entries
 // of end e with their requests at xa_reqs[(2t + e) * PW_XA_CAP ..], in list order; desc[2t + e].flag carries the count in bits 16-19 and
 // desc[2t + 1].req = 1 + xa_cnt[2t] (the pair's requests in a job: read 0's, its XA entries', read 1's, its XA entries').
@@ -315,7 +315,7 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 		desc[2 * t + e] = d;
 		if (xa_cnt) xa_cnt[2 * t + e] = (uint8_t)n_xa[e];
 	}
-	if (lane == 0) wstatus[t] = n_xa[0] + n_xa[1] ? PW_DECIDED_XA : 1;
+	if (lane == 0) wstatus[t] = n_xa[0] + n_xa[1] ? PW_DECIDED_XA : PR_DECIDED;
 }
 
 void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
@@ -337,18 +337,13 @@ __global__ void pair_wave_clear_kernel(int r0, int n_reads, AlnReq *__restrict__
 	reqs[r0 + i].read = -1;
 	desc[r0 + i].req = -1;
 }
-__global__ void pair_wave_clear_desc_kernel(int r0, int n_reads, SamDesc *__restrict__ desc)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n_reads) desc[r0 + i].req = -1;
-}
 __global__ void pair_wave_scatter_kernel(int n_work, const int *__restrict__ work, const uint8_t *__restrict__ wstatus, const AlnReq *__restrict__ w_reqs,
                                          const SamDesc *__restrict__ w_desc, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= 2 * n_work) return;
 	const int t = i >> 1, e = i & 1;
-	if (wstatus[t] != 1) return;
+	if (wstatus[t] != PR_DECIDED) return;
 	reqs[2 * work[t] + e] = w_reqs[i];
 	desc[2 * work[t] + e] = w_desc[i];
 }
@@ -359,31 +354,6 @@ void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const
 	if (n_work > 0)
 		hipLaunchKernelGGL(pair_wave_scatter_kernel, dim3((2 * n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_work, d_wstatus, d_w_reqs, d_w_desc,
 		                   d_reqs, d_desc);
-}
-
-
-// the XA pairs into the job of their own: a thread per work item
-__global__ void pair_wave_xa_scatter_kernel(int n_work, const int *__restrict__ work, const int *__restrict__ dst, const AlnReq *__restrict__ w_reqs,
-                                            const SamDesc *__restrict__ w_desc, const AlnReq *__restrict__ xa_reqs, const uint8_t *__restrict__ xa_cnt,
-                                            AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
-{
-	const int t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= n_work || dst[t] < 0) return;
-	int at = dst[t];
-	for (int e = 0; e < 2; ++e) {
-		reqs[at++] = w_reqs[2 * t + e];
-		const int c = xa_cnt[2 * t + e] < PW_XA_CAP ? xa_cnt[2 * t + e] : PW_XA_CAP;
-		for (int j = 0; j < c; ++j) reqs[at++] = xa_reqs[(size_t)(2 * t + e) * PW_XA_CAP + j];
-		desc[2 * work[t] + e] = w_desc[2 * t + e];
-	}
-}
-void launch_pair_wave_xa_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
-                                 const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n)
-{
-	if (clear_n > 0) hipLaunchKernelGGL(pair_wave_clear_desc_kernel, dim3((clear_n + 255) / 256), dim3(256), 0, (hipStream_t)stream, clear_r0, clear_n, d_desc);
-	if (n_work > 0)
-		hipLaunchKernelGGL(pair_wave_xa_scatter_kernel, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_work, d_dst, d_w_reqs, d_w_desc,
-		                   d_xa_reqs, d_xa_cnt, d_reqs, d_desc);
 }
 
 } // namespace mbw

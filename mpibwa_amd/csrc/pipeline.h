@@ -11,6 +11,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <initializer_list>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -220,6 +221,15 @@ struct JobBufs {
 	DevBuf req, hdr, pool, cnt, lists, base, arena, used, ooff, olen;
 	PinBuf h_hdr, h_pool, h_base, h_arena, h_ooff, h_olen;
 };
+// One work list of a wave kernel: the units handed over (chunk numbering), their packed region lists and the lists' offsets, per pair
+// the first rescue request, the tags and their offsets, status bytes, the kernel's requests and descriptors, the XA entries' requests and
+// counts, and where each item's requests go in the job of the units it decided (dst).  pair_wave_kernel: one list per part of the
+// SAM stage, behind the part's mate-rescue kernel; se_wave_kernel: one over the chunk, in slot 0 (a call is either paired or
+// single-end), with dst still the part's slot: both parts' jobs are in flight at once.
+struct WaveBufs {
+	PinBuf h_work, h_lists, h_loff, h_mfirst, h_tags, h_toff, h_status, h_xcnt, h_dst;
+	DevBuf work, lists, loff, mfirst, tags, toff, status, req, desc, xreq, xcnt, dst;
+};
 // What belongs to the chunk as a whole: packed reads, the inputs of the SAM stage, the decisions made on the device, and per part of
 // the SAM stage the mate-rescue alignments and the two jobs
 struct ChunkBufs {
@@ -233,15 +243,12 @@ struct ChunkBufs {
 	PinBuf h_pr_ok, h_pr_status, h_pr_tab;
 	PinBuf h_mreq[2], h_mres[2], h_mlist[2];
 	DevBuf mreq[2], mres[2], mrows[2], mlist[2], mtail[2];
-	// pairs with mate rescue or long lists, decided by pair_wave_kernel behind the mate-rescue kernel of the part: work list, packed
-	// region lists and their offsets, first rescue request and tags per pair, status, the kernel's requests and descriptors
-	PinBuf h_wwork[2], h_wlists[2], h_wloff[2], h_wmfirst[2], h_wtags[2], h_wtoff[2], h_wstatus[2];
-	DevBuf wwork[2], wlists[2], wloff[2], wmfirst[2], wtags[2], wtoff[2], wstatus[2], wreq[2], wdesc[2];
-	JobBufs wave_job[2];  // their job when the device units' job of the part has already gone out
-	// the pairs it decided with an XA tag: the entries' requests and counts per work item, where each item's requests go in the job of
-	// these pairs, that job's requests, and its descriptors (chunk-wide, by read)
-	PinBuf h_wxcnt[2], h_wxdst[2];
-	DevBuf wxreq[2], wxcnt[2], wxdst[2], xa_req[2], xa_desc;
+	// the work lists of the wave kernels, the job of pair_wave_kernel's pairs when the device units' job of the part has already gone out,
+	// and the job of the units with requests of their own count (XA entries; se_wave_kernel's reads): its requests, and its descriptors
+	// (chunk-wide, by read)
+	WaveBufs wave[2];
+	JobBufs wave_job[2];
+	DevBuf xa_req[2], xa_desc;
 	JobBufs xa_job[2];
 	PinBuf h_areq[2];     // the host's CIGAR requests of a part, as listed
 	JobBufs host_job[2];  // the host's units ...
@@ -374,30 +381,37 @@ struct Call {
 	mem_pestat_t pes[4];
 
 	// ---- units decided on the device (sam_stage.hip) ----
-	uint8_t *pstat_w = nullptr;          // (pstat, writable: pair_wave_kernel's decisions are merged in)
+	uint8_t *ustat = nullptr;            // the deciding kernel's status byte per unit (PR_* / SE_*), the wave kernels' decisions merged in
+	bool dev_units = false;              // at least one unit is the device's (ustat[k] = *_DECIDED: its requests and descriptors exist there)
 	bool dev_wave = false;               // pair_wave_kernel takes the pairs pair_simple_kernel leaves for rescue / long lists
 	bool dev_xa = false;                 // ... and the ones it leaves for an XA tag; it lists the tag's entries (MPIBWA_HOST_XA=1: off)
 	uint64_t n_xa_pairs = 0;             // decided with an XA tag, or handed over for the XA test alone and decided without one
-	uint64_t n_xa_plain = 0;             // (the latter: status 1, riding with the wave's other pairs)
+	uint64_t n_xa_plain = 0;             // (the latter: status PR_DECIDED, riding with the wave's other pairs)
 	std::vector<uint8_t> wave_cand, wave_dec;   // per pair: handed to pair_wave_kernel; decided by it
 	PairParams wave_pp;
 	const double *d_wave_tab = nullptr;  // the tables of decide_on_device, still on the device
 	size_t wave_n_tab = 0;
 	uint64_t n_wave = 0;
-	const uint8_t *pstat = nullptr;      // status[k] = 1: the unit's requests and descriptors exist on the device
-	const uint8_t *se_codes = nullptr;   // the status codes of se_simple_kernel (pstat too, if it took any read)
 	// single-end reads se_simple_kernel left for more than eight regions or for its XA test: se_wave_kernel, once over
-	// the chunk on the call's stream.  Its buffers are slot 0's of pair_wave_kernel's (a call is either paired or single-end), its
-	// decided reads' job of every part is Part::xa with the request bases Part::xa_base, wave_dec marks the reads it decided
-	uint8_t *se_codes_w = nullptr;       // (se_codes, writable: se_wave_kernel's decisions are merged in)
+	// the chunk on the call's stream.  Its decided reads' job of every part is Part::xa with the request bases Part::xa_base, wave_dec
+	// marks the reads it decided
+	WaveBufs &se_bufs() { return W.wave[0]; }   // its work list (WaveBufs)
 	bool dev_se_wave = false;            // MPIBWA_HOST_SE_WAVE=1: off
 	bool dev_se_xa = false;              // ... with its XA listing (MPIBWA_HOST_XA=1 or max_XA_hits > PW_XA_CAP: off)
 	std::vector<int> se_work;            // the reads handed to it (chunk numbering, ascending)
-	const uint8_t *se_wstatus = nullptr, *se_wxcnt = nullptr;   // per work item: its status byte, its XA entries
+	const uint8_t *se_wxcnt = nullptr;   // per work item: its XA entries
 	uint64_t n_se_wave = 0, n_se_xa = 0; // decided by it with a plain record / with an XA tag
 	std::atomic<unsigned long long> n_se_xa_sam{0};   // records with an XA tag taken from the device
-	void se_wave_decide();               // candidates, packed lists, the kernel, the merge of its decisions (synchronous)
-	void se_wave_records(Part &P);       // the job of the part's reads it decided (asynchronous)
+	void se_wave_decide();               // candidates, the kernel over their work list, the merge of its decisions (synchronous)
+	// a wave kernel's work list, packed and queued: what the launch needs on the device, and where status bytes and XA counts come back
+	struct WaveList {
+		int *work; DevReg *lists; int *loff; uint8_t *status; AlnReq *req; SamDesc *desc; AlnReq *xreq; uint8_t *xcnt;
+		uint8_t *h_status, *h_xcnt;
+	};
+	struct Upload { void *dst; const void *src; size_t bytes; };
+	WaveList wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more = {});
+	// the units of the part a wave kernel decided with a request count of their own: a job of their own (asynchronous)
+	void own_job_records(Part &P, int ends, const WaveBufs &B, const std::vector<int> &items, const uint8_t *xcnt);
 	const AlnReq *d_pr_req = nullptr;
 	const SamDesc *d_pr_desc = nullptr;
 	double pair_dev_ms = 0;
@@ -418,7 +432,6 @@ struct Call {
 	void mfinish(Part &P);
 	void wave_launch(Part &P);        // pair_wave_kernel behind the mate-rescue kernel of the part (asynchronous)
 	void wave_records(Part &P, bool own_job);   // its pairs into the device units' arrays; own_job: and a job of their own
-	void xa_records(Part &P);         // its pairs with an XA tag: always a job of their own
 	void collect(Part &P, int round); // A: decisions + the list of CIGARs to compute
 	void launch_dev(Part &P);         // the job of the units decided on the device (asynchronous)
 	void finish_dev(Part &P);

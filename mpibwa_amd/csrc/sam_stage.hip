@@ -88,7 +88,7 @@ void Call::sam_inputs_body()
 
 // ---- units with one plain hit per read: decided on the device (pair_kernel.hip: pairs, ends = 2; se_kernel.hip: single-end reads
 // that end in one record, ends = 1) ----
-// status[k] = 1: the unit's CIGAR requests and line descriptors exist on the device; the host neither lists rescue alignments nor
+// status[k] = PR_DECIDED / SE_DECIDED: the unit's CIGAR requests and line descriptors exist on the device; the host neither lists rescue alignments nor
 // marks primary hits nor plans nor formats it (it only copies the finished records out, or takes the unit back if the device hands
 // a record back).
 void Call::decide_on_device(int ends)
@@ -125,10 +125,10 @@ void Call::decide_on_device(int ends)
 		stream_wait(st);
 		HIP_OK(hipGetLastError());
 		bool any_dev = ends == 2;   // (single-end, none taken: no device job over n empty requests)
-		if (ends == 1) { se_codes = se_codes_w = hs; wave_pp = pp; d_wave_tab = d_tab; wave_n_tab = n_tab; }   // (se_wave_kernel: the same parameters and table)
 		for (int i = 0; i < nu && !any_dev; ++i) any_dev = hs[i] == SE_DECIDED;
-		if (any_dev) { pstat = hs; d_pr_req = d_rq; d_pr_desc = d_ds; }
-		if (any_dev && ends == 2) { pstat_w = hs; wave_pp = pp; d_wave_tab = d_tab; wave_n_tab = n_tab; }
+		ustat = hs; dev_units = any_dev;
+		wave_pp = pp; d_wave_tab = d_tab; wave_n_tab = n_tab;   // (the wave kernels: the same parameters and table)
+		if (any_dev) { d_pr_req = d_rq; d_pr_desc = d_ds; }
 	}
 	pair_dev_ms = now_ms() - tp0;
 }
@@ -153,9 +153,9 @@ void Call::mcollect(Part &P)
 		const int lo = P.lo + blk * 256, hi = std::min(P.hi, lo + 256);
 		for (int i = lo; i < hi; ++i) {
 			const size_t before = rq.size();
-			if (!(pstat && pstat[i] == 1)) {
+			if (!(dev_units && ustat[i] == PR_DECIDED)) {
 				const bseq1_t *s = &seqs[i << 1];
-				const bool cand = dev_wave && (pstat[i] == 3 || pstat[i] == 7 || pstat[i] == 2 || (dev_xa && pstat[i] == 11)) && !s[0].comment && !s[1].comment &&
+				const bool cand = dev_wave && (ustat[i] == PR_HOST_MAXREG || ustat[i] == PR_HOST_RESCUE || ustat[i] == PR_HOST_NO_HIT || (dev_xa && ustat[i] == PR_HOST_XA)) && !s[0].comment && !s[1].comment &&
 				                  strcmp(s[0].name, s[1].name) == 0 && pair_wave_eligible(&regs[i << 1], PW_MAXREG);
 				if (cand) {
 					blk_work[blk].push_back(i); blk_work[blk].push_back((int)blk_tag[blk].size());
@@ -240,84 +240,105 @@ static void pack_list(const HRegV &v, DevReg *o)
 	}
 }
 
+// A wave kernel's work list on stream wst: `ends` region lists per item — the host's own (after mem_sort_dedup_patch), packed with
+// offsets —, status bytes and (xa) XA counts cleared, room for the kernel's requests, descriptors and XA requests (PW_XA_CAP per
+// (item, end)).  more: what else the kernel reads per item, uploaded behind the lists and before the clears.
+Call::WaveList Call::wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more)
+{
+	const int nw = (int)items.size(), nl = ends * nw;   // items, lists
+	size_t n_regs = 0;
+	int *loff = (int *)B.h_loff.ensure(roomy(((size_t)nl + 1) * 4 + 64));
+	loff[0] = 0;
+	for (int t = 0; t < nw; ++t)
+		for (int e = 0; e < ends; ++e) { n_regs += regs[ends * items[t] + e].size(); loff[ends * t + e + 1] = (int)n_regs; }
+	DevReg *hl = (DevReg *)B.h_lists.ensure(roomy(n_regs * sizeof(DevReg) + 64));
+	parallel_for(n_thr, nw, 512, [&](int t) {
+		for (int e = 0; e < ends; ++e) pack_list(regs[ends * items[t] + e], hl + loff[ends * t + e]);
+	});
+	int *hw = (int *)B.h_work.ensure(roomy((size_t)nw * 4 + 64));
+	memcpy(hw, items.data(), (size_t)nw * 4);
+	WaveList L;
+	L.h_status = (uint8_t *)B.h_status.ensure(roomy((size_t)nw + 64));
+	L.work = (int *)B.work.ensure(roomy((size_t)nw * 4));
+	L.lists = (DevReg *)B.lists.ensure(roomy(n_regs * sizeof(DevReg) + 64));
+	L.loff = (int *)B.loff.ensure(roomy(((size_t)nl + 1) * 4));
+	L.status = (uint8_t *)B.status.ensure(roomy((size_t)nw + 64));
+	L.req = (AlnReq *)B.req.ensure(roomy((size_t)nl * sizeof(AlnReq)));
+	L.desc = (SamDesc *)B.desc.ensure(roomy((size_t)nl * sizeof(SamDesc)));
+	HIP_OK(hipMemcpyAsync(L.work, hw, (size_t)nw * 4, hipMemcpyHostToDevice, wst));
+	if (n_regs) HIP_OK(hipMemcpyAsync(L.lists, hl, n_regs * sizeof(DevReg), hipMemcpyHostToDevice, wst));
+	HIP_OK(hipMemcpyAsync(L.loff, loff, ((size_t)nl + 1) * 4, hipMemcpyHostToDevice, wst));
+	for (const Upload &u : more)
+		if (u.bytes) HIP_OK(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, wst));
+	HIP_OK(hipMemsetAsync(L.status, 0, (size_t)nw, wst));
+	L.xreq = nullptr; L.xcnt = L.h_xcnt = nullptr;
+	if (xa) {
+		L.xreq = (AlnReq *)B.xreq.ensure(roomy((size_t)nl * PW_XA_CAP * sizeof(AlnReq)));
+		L.xcnt = (uint8_t *)B.xcnt.ensure(roomy((size_t)nl + 64));
+		L.h_xcnt = (uint8_t *)B.h_xcnt.ensure(roomy((size_t)nl + 64));
+		HIP_OK(hipMemsetAsync(L.xcnt, 0, (size_t)nl, wst));
+	}
+	return L;
+}
+
 // pair_wave_kernel over the part's work list, behind the mate-rescue kernel on its stream; the status bytes come back on the same
-// stream, so that mfinish's wait delivers them.  The lists are the host's own (after mem_sort_dedup_patch), packed with offsets.
+// stream, so that mfinish's wait delivers them.
 void Call::wave_launch(Part &P)
 {
 	const int nw = (int)P.work.size();
 	if (nw == 0) return;
 	const int s = P.slot;
-	size_t n_regs = 0;
-	int *loff = (int *)W.h_wloff[s].ensure(roomy(((size_t)2 * nw + 1) * 4 + 64));
-	loff[0] = 0;
-	for (int t = 0; t < nw; ++t)
-		for (int e = 0; e < 2; ++e) { n_regs += regs[2 * P.work[t] + e].size(); loff[2 * t + e + 1] = (int)n_regs; }
-	DevReg *hl = (DevReg *)W.h_wlists[s].ensure(roomy(n_regs * sizeof(DevReg) + 64));
-	parallel_for(n_thr, nw, 512, [&](int t) {
-		for (int e = 0; e < 2; ++e) pack_list(regs[2 * P.work[t] + e], hl + loff[2 * t + e]);
-	});
-	int *hw = (int *)W.h_wwork[s].ensure(roomy((size_t)nw * 4 + 64));
-	unsigned *hm = (unsigned *)W.h_wmfirst[s].ensure(roomy((size_t)nw * 4 + 64));
-	int *ht = (int *)W.h_wtoff[s].ensure(roomy((size_t)(nw + 1) * 4 + 64));
-	int16_t *hg = (int16_t *)W.h_wtags[s].ensure(roomy(P.w_tags.size() * 2 + 64));
-	memcpy(hw, P.work.data(), (size_t)nw * 4); memcpy(hm, P.w_mfirst.data(), (size_t)nw * 4); memcpy(ht, P.w_toff.data(), (size_t)(nw + 1) * 4);
+	WaveBufs &B = W.wave[s];
+	unsigned *hm = (unsigned *)B.h_mfirst.ensure(roomy((size_t)nw * 4 + 64));
+	int *ht = (int *)B.h_toff.ensure(roomy((size_t)(nw + 1) * 4 + 64));
+	int16_t *hg = (int16_t *)B.h_tags.ensure(roomy(P.w_tags.size() * 2 + 64));
+	memcpy(hm, P.w_mfirst.data(), (size_t)nw * 4); memcpy(ht, P.w_toff.data(), (size_t)(nw + 1) * 4);
 	memcpy(hg, P.w_tags.data(), P.w_tags.size() * 2);
-	uint8_t *hs = (uint8_t *)W.h_wstatus[s].ensure(roomy((size_t)nw + 64));
-	int *d_work = (int *)W.wwork[s].ensure(roomy((size_t)nw * 4));
-	DevReg *d_lists = (DevReg *)W.wlists[s].ensure(roomy(n_regs * sizeof(DevReg) + 64));
-	int *d_loff = (int *)W.wloff[s].ensure(roomy(((size_t)2 * nw + 1) * 4));
-	unsigned *d_mf = (unsigned *)W.wmfirst[s].ensure(roomy((size_t)nw * 4));
-	int *d_toff = (int *)W.wtoff[s].ensure(roomy((size_t)(nw + 1) * 4));
-	short *d_tags = (short *)W.wtags[s].ensure(roomy(P.w_tags.size() * 2 + 64));
-	uint8_t *d_ws = (uint8_t *)W.wstatus[s].ensure(roomy((size_t)nw + 64));
-	AlnReq *d_rq = (AlnReq *)W.wreq[s].ensure(roomy((size_t)2 * nw * sizeof(AlnReq)));
-	SamDesc *d_ds = (SamDesc *)W.wdesc[s].ensure(roomy((size_t)2 * nw * sizeof(SamDesc)));
+	unsigned *d_mf = (unsigned *)B.mfirst.ensure(roomy((size_t)nw * 4));
+	int *d_toff = (int *)B.toff.ensure(roomy((size_t)(nw + 1) * 4));
+	short *d_tags = (short *)B.tags.ensure(roomy(P.w_tags.size() * 2 + 64));
 	// (a part without a rescue request has no request or result array: the kernel reads neither, every tag says so)
 	const MswReq *d_req = (const MswReq *)W.mreq[s].ensure(std::max<size_t>(P.n_mreq, 1) * sizeof(MswReq));
 	const MswRes *d_res = (const MswRes *)W.mres[s].ensure(std::max<size_t>(P.n_mreq, 1) * sizeof(MswRes));
-	HIP_OK(hipMemcpyAsync(d_work, hw, (size_t)nw * 4, hipMemcpyHostToDevice, P.mst));
-	if (n_regs) HIP_OK(hipMemcpyAsync(d_lists, hl, n_regs * sizeof(DevReg), hipMemcpyHostToDevice, P.mst));
-	HIP_OK(hipMemcpyAsync(d_loff, loff, ((size_t)2 * nw + 1) * 4, hipMemcpyHostToDevice, P.mst));
-	HIP_OK(hipMemcpyAsync(d_mf, hm, (size_t)nw * 4, hipMemcpyHostToDevice, P.mst));
-	HIP_OK(hipMemcpyAsync(d_toff, ht, (size_t)(nw + 1) * 4, hipMemcpyHostToDevice, P.mst));
-	if (!P.w_tags.empty()) HIP_OK(hipMemcpyAsync(d_tags, hg, P.w_tags.size() * 2, hipMemcpyHostToDevice, P.mst));
-	HIP_OK(hipMemsetAsync(d_ws, 0, (size_t)nw, P.mst));
-	AlnReq *d_xr = nullptr;
-	uint8_t *d_xc = nullptr, *hx = nullptr;
-	if (dev_xa) {   // the XA entries' requests, PW_XA_CAP per (item, end), and their counts
-		d_xr = (AlnReq *)W.wxreq[s].ensure(roomy((size_t)2 * nw * PW_XA_CAP * sizeof(AlnReq)));
-		d_xc = (uint8_t *)W.wxcnt[s].ensure(roomy((size_t)2 * nw + 64));
-		hx = (uint8_t *)W.h_wxcnt[s].ensure(roomy((size_t)2 * nw + 64));
-		HIP_OK(hipMemsetAsync(d_xc, 0, (size_t)2 * nw, P.mst));
-	}
-	launch_pair_wave(P.mst, wave_pp, nw, d_work, d_lists, d_loff, D.d_len, d_req, d_res, d_mf, d_tags, d_toff, D.d_ann_off, d_wave_tab, d_wave_tab + wave_n_tab,
-	                 d_ws, d_rq, d_ds, d_xr, d_xc);
-	HIP_OK(hipMemcpyAsync(hs, d_ws, (size_t)nw, hipMemcpyDeviceToHost, P.mst));
-	if (dev_xa) HIP_OK(hipMemcpyAsync(hx, d_xc, (size_t)2 * nw, hipMemcpyDeviceToHost, P.mst));
-	P.wstatus = hs; P.wxcnt = hx;
+	const WaveList L = wave_list(B, P.mst, 2, P.work, dev_xa,
+	                             {{d_mf, hm, (size_t)nw * 4}, {d_toff, ht, (size_t)(nw + 1) * 4}, {d_tags, hg, P.w_tags.size() * 2}});
+	launch_pair_wave(P.mst, wave_pp, nw, L.work, L.lists, L.loff, D.d_len, d_req, d_res, d_mf, d_tags, d_toff, D.d_ann_off, d_wave_tab, d_wave_tab + wave_n_tab,
+	                 L.status, L.req, L.desc, L.xreq, L.xcnt);
+	HIP_OK(hipMemcpyAsync(L.h_status, L.status, (size_t)nw, hipMemcpyDeviceToHost, P.mst));
+	if (dev_xa) HIP_OK(hipMemcpyAsync(L.h_xcnt, L.xcnt, (size_t)2 * nw, hipMemcpyDeviceToHost, P.mst));
+	P.wstatus = L.h_status; P.wxcnt = L.h_xcnt;
 }
 
-// The pairs pair_wave_kernel decided with an XA tag carry 3 to 2 + 2 PW_XA_CAP requests each, so they never ride in the part's device
-// job (two requests per pair, in place): the host lays out their request bases (no request for any other unit of the part), a kernel
-// moves requests and descriptors there, and one more CIGAR-and-SAM job runs over the part for these pairs alone.
-void Call::xa_records(Part &P)
+// The units a wave kernel decided with a request count of their own — pair_wave_kernel's pairs with an XA tag (3 to 2 + 2 PW_XA_CAP
+// requests each), se_wave_kernel's reads (1 to 1 + PW_XA_CAP) — never ride in the part's device job (`ends` requests per unit, in place):
+// the host lays out their request bases (no request for any other unit of the part), a kernel moves requests and descriptors there, and
+// one more CIGAR-and-SAM job runs over the part for these units alone.  B, items: the work list; xcnt: its XA counts, or null.
+void Call::own_job_records(Part &P, int ends, const WaveBufs &B, const std::vector<int> &items, const uint8_t *xcnt)
 {
-	if (P.n_xa_dec == 0) return;
-	const int s = P.slot, nw = (int)P.work.size(), nu = P.hi - P.lo;
-	hipStream_t jst = C.d_streams[s];
-	int *dst = (int *)W.h_wxdst[s].ensure(roomy((size_t)nw * 4 + 64));
+	const int s = P.slot, nw = (int)items.size(), nu = P.hi - P.lo;
+	auto in_job = [&](int t) {
+		const int i = items[t];
+		return ends == 2 ? P.wstatus[t] == PW_DECIDED_XA : i >= P.lo && i < P.hi && wave_dec[i];
+	};
 	P.xa_base.assign(nu + 1, 0);
-	for (int t = 0; t < nw; ++t)
-		if (P.wstatus[t] == PW_DECIDED_XA) P.xa_base[P.work[t] - P.lo + 1] = 2 + std::min<int>(P.wxcnt[2 * t], PW_XA_CAP) + std::min<int>(P.wxcnt[2 * t + 1], PW_XA_CAP);
+	int n_dec = 0;
+	for (int t = 0; t < nw; ++t) {
+		if (!in_job(t)) continue;
+		for (int e = 0; e < ends; ++e) P.xa_base[items[t] - P.lo + 1] += 1 + (xcnt ? std::min<int>(xcnt[ends * t + e], PW_XA_CAP) : 0);
+		++n_dec;
+	}
+	if (n_dec == 0) return;
+	hipStream_t jst = C.d_streams[s];
 	for (int k = 0; k < nu; ++k) P.xa_base[k + 1] += P.xa_base[k];
-	for (int t = 0; t < nw; ++t) dst[t] = P.wstatus[t] == PW_DECIDED_XA ? (int)P.xa_base[P.work[t] - P.lo] : -1;
+	int *dst = (int *)W.wave[s].h_dst.ensure(roomy((size_t)nw * 4 + 64));   // (the part's: se_wave_kernel's one list serves both parts)
+	for (int t = 0; t < nw; ++t) dst[t] = in_job(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
 	const size_t n_req = P.xa_base[nu];
-	int *d_dst = (int *)W.wxdst[s].ensure(roomy((size_t)nw * 4));
+	int *d_dst = (int *)W.wave[s].dst.ensure(roomy((size_t)nw * 4));
 	AlnReq *d_rq = (AlnReq *)W.xa_req[s].ensure(roomy(n_req * sizeof(AlnReq)));
 	SamDesc *d_ds = (SamDesc *)W.xa_desc.ensure((size_t)n * sizeof(SamDesc));
 	HIP_OK(hipMemcpyAsync(d_dst, dst, (size_t)nw * 4, hipMemcpyHostToDevice, jst));
-	launch_pair_wave_xa_scatter(jst, nw, (const int *)W.wwork[s].p, d_dst, (const AlnReq *)W.wreq[s].p, (const SamDesc *)W.wdesc[s].p, (const AlnReq *)W.wxreq[s].p,
-	                            (const uint8_t *)W.wxcnt[s].p, d_rq, d_ds, 2 * P.lo, 2 * nu);
+	launch_wave_job_scatter(jst, ends, nw, (const int *)B.work.p, d_dst, (const AlnReq *)B.req.p, (const SamDesc *)B.desc.p, xcnt ? (const AlnReq *)B.xreq.p : nullptr,
+	                        xcnt ? (const uint8_t *)B.xcnt.p : nullptr, d_rq, d_ds, ends * P.lo, ends * nu);
 	HIP_OK(hipGetLastError());
 	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
 	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
@@ -325,104 +346,38 @@ void Call::xa_records(Part &P)
 }
 
 // ---- single-end reads with long lists or an XA tag: se_wave_kernel (se_wave_kernel.hip) ----
-// The reads se_simple_kernel left with "more than eight regions" or "a secondary region with an XA entry", once over the chunk: the
-// host's own lists (after mem_sort_dedup_patch) packed with offsets, the kernel on the call's stream, status bytes and XA counts back,
-// merged into the chunk's decisions.  MPIBWA_HOST_SE_WAVE=1 turns the path off; MPIBWA_HOST_XA=1 or max_XA_hits beyond the kernel's
-// side array only its XA listing (such a read comes back with SE_HOST_XA).
+// The reads se_simple_kernel left with "more than eight regions" or "a secondary region with an XA entry", once over the chunk: their
+// work list and the kernel on the call's stream, status bytes and XA counts back, merged into the chunk's decisions.
+// MPIBWA_HOST_SE_WAVE=1 turns the path off; MPIBWA_HOST_XA=1 or max_XA_hits beyond the kernel's side array only its XA listing (such a
+// read comes back with SE_HOST_XA).
 void Call::se_wave_decide()
 {
-	dev_se_wave = !pe && dev_se && se_codes_w && getenv("MPIBWA_HOST_SE_WAVE") == nullptr;
+	dev_se_wave = !pe && dev_se && ustat && getenv("MPIBWA_HOST_SE_WAVE") == nullptr;
 	if (!dev_se_wave) return;
 	const double tp0 = now_ms();
 	dev_se_xa = wave_pp.max_XA_hits <= PW_XA_CAP && getenv("MPIBWA_HOST_XA") == nullptr;
-	uint8_t *codes = se_codes_w;
 	wave_dec.assign(n, 0);
 	se_work.clear();
-	size_t n_regs = 0;
 	for (int i = 0; i < n; ++i)
-		if ((codes[i] == SE_HOST_MAXREG || codes[i] == SE_HOST_XA) && !seqs[i].comment && se_wave_eligible(regs[i], PW_MAXREG)) {
-			se_work.push_back(i);
-			n_regs += regs[i].size();
-		}
+		if ((ustat[i] == SE_HOST_MAXREG || ustat[i] == SE_HOST_XA) && !seqs[i].comment && se_wave_eligible(regs[i], PW_MAXREG)) se_work.push_back(i);
 	const int nw = (int)se_work.size();
 	if (nw == 0) return;
-	int *loff = (int *)W.h_wloff[0].ensure(roomy(((size_t)nw + 1) * 4 + 64));
-	loff[0] = 0;
-	for (int t = 0; t < nw; ++t) loff[t + 1] = loff[t] + (int)regs[se_work[t]].size();
-	DevReg *hl = (DevReg *)W.h_wlists[0].ensure(roomy(n_regs * sizeof(DevReg) + 64));
-	parallel_for(n_thr, nw, 512, [&](int t) { pack_list(regs[se_work[t]], hl + loff[t]); });
-	int *hw = (int *)W.h_wwork[0].ensure(roomy((size_t)nw * 4 + 64));
-	memcpy(hw, se_work.data(), (size_t)nw * 4);
-	uint8_t *hs = (uint8_t *)W.h_wstatus[0].ensure(roomy((size_t)nw + 64));
-	int *d_work = (int *)W.wwork[0].ensure(roomy((size_t)nw * 4));
-	DevReg *d_lists = (DevReg *)W.wlists[0].ensure(roomy(n_regs * sizeof(DevReg) + 64));
-	int *d_loff = (int *)W.wloff[0].ensure(roomy(((size_t)nw + 1) * 4));
-	uint8_t *d_ws = (uint8_t *)W.wstatus[0].ensure(roomy((size_t)nw + 64));
-	AlnReq *d_rq = (AlnReq *)W.wreq[0].ensure(roomy((size_t)nw * sizeof(AlnReq)));
-	SamDesc *d_ds = (SamDesc *)W.wdesc[0].ensure(roomy((size_t)nw * sizeof(SamDesc)));
-	HIP_OK(hipMemcpyAsync(d_work, hw, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-	if (n_regs) HIP_OK(hipMemcpyAsync(d_lists, hl, n_regs * sizeof(DevReg), hipMemcpyHostToDevice, st));
-	HIP_OK(hipMemcpyAsync(d_loff, loff, ((size_t)nw + 1) * 4, hipMemcpyHostToDevice, st));
-	HIP_OK(hipMemsetAsync(d_ws, 0, (size_t)nw, st));
-	AlnReq *d_xr = nullptr;
-	uint8_t *d_xc = nullptr, *hx = nullptr;
-	if (dev_se_xa) {   // the XA entries' requests, PW_XA_CAP per item, and their counts
-		d_xr = (AlnReq *)W.wxreq[0].ensure(roomy((size_t)nw * PW_XA_CAP * sizeof(AlnReq)));
-		d_xc = (uint8_t *)W.wxcnt[0].ensure(roomy((size_t)nw + 64));
-		hx = (uint8_t *)W.h_wxcnt[0].ensure(roomy((size_t)nw + 64));
-		HIP_OK(hipMemsetAsync(d_xc, 0, (size_t)nw, st));
-	}
-	launch_se_wave(st, wave_pp, nw, d_work, d_lists, d_loff, D.d_ann_alt, d_wave_tab + wave_n_tab, d_ws, d_rq, d_ds, d_xr, d_xc);
-	HIP_OK(hipMemcpyAsync(hs, d_ws, (size_t)nw, hipMemcpyDeviceToHost, st));
-	if (dev_se_xa) HIP_OK(hipMemcpyAsync(hx, d_xc, (size_t)nw, hipMemcpyDeviceToHost, st));
+	const WaveList L = wave_list(se_bufs(), st, 1, se_work, dev_se_xa);
+	launch_se_wave(st, wave_pp, nw, L.work, L.lists, L.loff, D.d_ann_alt, d_wave_tab + wave_n_tab, L.status, L.req, L.desc, L.xreq, L.xcnt);
+	HIP_OK(hipMemcpyAsync(L.h_status, L.status, (size_t)nw, hipMemcpyDeviceToHost, st));
+	if (dev_se_xa) HIP_OK(hipMemcpyAsync(L.h_xcnt, L.xcnt, (size_t)nw, hipMemcpyDeviceToHost, st));
 	stream_wait(st);
 	HIP_OK(hipGetLastError());
-	se_wstatus = hs; se_wxcnt = hx;
+	se_wxcnt = L.h_xcnt;
 	for (int t = 0; t < nw; ++t) {   // its decisions: these reads are the device's from here on
 		const int i = se_work[t];
-		if (hs[t] == SE_DECIDED) { codes[i] = SE_DECIDED; wave_dec[i] = 1; ++n_se_wave; }
-		else if (hs[t] == SE_DECIDED_XA && dev_se_xa) { codes[i] = SE_DECIDED_XA; wave_dec[i] = 1; ++n_se_xa; }
-		else if (hs[t]) codes[i] = hs[t];   // (why not: for the statistics line)
+		const uint8_t ws = L.h_status[t];
+		if (ws == SE_DECIDED) { ustat[i] = SE_DECIDED; wave_dec[i] = 1; ++n_se_wave; }
+		else if (ws == SE_DECIDED_XA && dev_se_xa) { ustat[i] = SE_DECIDED_XA; wave_dec[i] = 1; ++n_se_xa; }
+		else if (ws) ustat[i] = ws;   // (why not: for the statistics line)
 	}
-	if (n_se_wave + n_se_xa) pstat = codes;   // (se_simple_kernel may have taken none)
+	if (n_se_wave + n_se_xa) dev_units = true;   // (se_simple_kernel may have taken none)
 	pair_dev_ms += now_ms() - tp0;
-}
-
-// The reads it decided carry 1 to 1 + PW_XA_CAP requests each, so they do not ride in the part's device job (one request per read, in
-// place): as for the XA pairs (xa_records), the host lays out their request bases (no request for any other read of the part), a kernel
-// moves requests and descriptors there, and one more CIGAR-and-SAM job runs over the part for these reads alone, queued before the
-// host plans the remaining reads.
-void Call::se_wave_records(Part &P)
-{
-	if (!dev_se_wave || n_se_wave + n_se_xa == 0) return;
-	const int s = P.slot, nw = (int)se_work.size(), nu = P.hi - P.lo;
-	P.xa_base.assign(nu + 1, 0);
-	int n_dec = 0;
-	for (int t = 0; t < nw; ++t) {
-		const int i = se_work[t];
-		if (i < P.lo || i >= P.hi || !wave_dec[i]) continue;
-		P.xa_base[i - P.lo + 1] = 1 + (se_wstatus[t] == SE_DECIDED_XA ? std::min<int>(se_wxcnt[t], PW_XA_CAP) : 0);
-		++n_dec;
-	}
-	if (n_dec == 0) return;
-	hipStream_t jst = C.d_streams[s];
-	for (int k = 0; k < nu; ++k) P.xa_base[k + 1] += P.xa_base[k];
-	int *dst = (int *)W.h_wxdst[s].ensure(roomy((size_t)nw * 4 + 64));
-	for (int t = 0; t < nw; ++t) {
-		const int i = se_work[t];
-		dst[t] = i >= P.lo && i < P.hi && wave_dec[i] ? (int)P.xa_base[i - P.lo] : -1;
-	}
-	const size_t n_req = P.xa_base[nu];
-	int *d_dst = (int *)W.wxdst[s].ensure(roomy((size_t)nw * 4));
-	AlnReq *d_rq = (AlnReq *)W.xa_req[s].ensure(roomy(n_req * sizeof(AlnReq)));
-	SamDesc *d_ds = (SamDesc *)W.xa_desc.ensure((size_t)n * sizeof(SamDesc));
-	HIP_OK(hipMemcpyAsync(d_dst, dst, (size_t)nw * 4, hipMemcpyHostToDevice, jst));
-	launch_se_wave_scatter(jst, nw, (const int *)W.wwork[0].p, d_dst, (const AlnReq *)W.wreq[0].p, (const SamDesc *)W.wdesc[0].p,
-	                       dev_se_xa ? (const AlnReq *)W.wxreq[0].p : nullptr, dev_se_xa ? (const uint8_t *)W.wxcnt[0].p : nullptr, d_rq, d_ds, P.lo, nu);
-	HIP_OK(hipGetLastError());
-	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
-	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
-	job_launch(P.xa, W.xa_job[s], jst, P, d_rq, n_req, P.xa_base.data(), true, nullptr, d_ds);
 }
 
 // The pairs pair_wave_kernel decided become units of the device: their requests and descriptors go into the chunk-wide arrays of the
@@ -433,7 +388,7 @@ void Call::wave_records(Part &P, bool own_job)
 	if (P.n_wave_dec == 0) return;
 	const int s = P.slot, nw = (int)P.work.size();
 	hipStream_t jst = C.d_streams[s];
-	launch_pair_wave_scatter(jst, nw, (const int *)W.wwork[s].p, (const uint8_t *)W.wstatus[s].p, (const AlnReq *)W.wreq[s].p, (const SamDesc *)W.wdesc[s].p,
+	launch_pair_wave_scatter(jst, nw, (const int *)W.wave[s].work.p, (const uint8_t *)W.wave[s].status.p, (const AlnReq *)W.wave[s].req.p, (const SamDesc *)W.wave[s].desc.p,
 	                         const_cast<AlnReq *>(d_pr_req), const_cast<SamDesc *>(d_pr_desc), 2 * P.lo, own_job ? 2 * (P.hi - P.lo) : 0);
 	HIP_OK(hipGetLastError());
 	if (!own_job) return;
@@ -456,9 +411,9 @@ void Call::mfinish(Part &P)
 		const int i = P.work[t];
 		// (pair_simple_kernel's XA test is coarse — any close secondary hit under any primary one —, so some of the pairs it left for XA
 		// come back plain: more than max_XA_hits entries, or entries under a hit that is not the chosen one)
-		if (P.wstatus[t] == 1) { if (pstat_w[i] == PW_HOST_XA) ++n_plain_from_xa; pstat_w[i] = 1; wave_dec[i] = 1; ++P.n_wave_dec; }
-		else if (P.wstatus[t] == PW_DECIDED_XA && dev_xa) { pstat_w[i] = PW_DECIDED_XA; ++P.n_xa_dec; }
-		else if (P.wstatus[t]) pstat_w[i] = P.wstatus[t];   // (why not: for the statistics line)
+		if (P.wstatus[t] == PR_DECIDED) { if (ustat[i] == PR_HOST_XA) ++n_plain_from_xa; ustat[i] = PR_DECIDED; wave_dec[i] = 1; ++P.n_wave_dec; }
+		else if (P.wstatus[t] == PW_DECIDED_XA && dev_xa) { ustat[i] = PW_DECIDED_XA; ++P.n_xa_dec; }
+		else if (P.wstatus[t]) ustat[i] = P.wstatus[t];   // (why not: for the statistics line)
 	}
 	n_wave += (uint64_t)P.n_wave_dec - n_plain_from_xa;
 	n_xa_plain += n_plain_from_xa;
@@ -484,7 +439,7 @@ void Call::collect(Part &P, int round)
 		unsigned long long tsc_plan_blk = 0, tsc_emitc_blk = 0;
 		for (int i = lo; i < hi; ++i) {
 			const int k = i - P.lo;
-			if (pstat && (pstat[i] == 1 || pstat[i] == PW_DECIDED_XA)) continue;   // decided on the device
+			if (dev_units && (ustat[i] == PR_DECIDED || ustat[i] == PW_DECIDED_XA)) continue;   // decided on the device
 			const bool has_msw = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
 			const bool waits = has_msw || (dev_wave && wave_cand[i]);            // ... or pair_wave_kernel's word on whose pair it is
 			if (waits != (round == 1)) continue;
@@ -608,7 +563,7 @@ void Call::job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units)
 		bool any_back = false;
 		for (int k = 0; k < P.hi - P.lo && !any_back; ++k)
 			for (int e = 0; e < ends; ++e)
-				any_back = any_back || (pstat[P.lo + k] == 1 && (!wave_units || wave_dec[P.lo + k]) && !(dev_se_wave && wave_dec[P.lo + k]) &&
+				any_back = any_back || (ustat[P.lo + k] == PR_DECIDED && (!wave_units || wave_dec[P.lo + k]) && !(dev_se_wave && wave_dec[P.lo + k]) &&
 				                        J.solen[ends * k + e] < 0);   // (se_wave_kernel's reads have a job of their own)
 		if (any_back) fetch_results(J);
 	}
@@ -620,7 +575,7 @@ void Call::job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units)
 void Call::launch_dev(Part &P)
 {
 	stage(14);
-	if (!pstat || !d_pr_req || P.hi == P.lo) return;   // (!d_pr_req: a single-end chunk of which only se_wave_kernel took reads)
+	if (!dev_units || !d_pr_req || P.hi == P.lo) return;   // (!d_pr_req: a single-end chunk of which only se_wave_kernel took reads)
 	const int ends = pe ? 2 : 1;   // reads (and requests) per unit
 	unsigned long long *small = (unsigned long long *)W.h_small[P.slot].ensure(512);
 	P.dev.small_used = small; P.dev.small_cnt = small + 8;
@@ -675,13 +630,13 @@ void Call::replay(Part &P, int which)
 	const int ends = pe ? 2 : 1;
 	// (a single-end chunk without reads of the device's has no pass 0)
 	// per-block counters: a shared atomic bumped once per unit costs more than copying the unit's records
-	if (pe || which != 0 || pstat) parallel_blocks(n_thr, P.hi - P.lo, pe ? 128 : 256, [&](int, int, int k_lo, int k_hi) {
+	if (pe || which != 0 || dev_units) parallel_blocks(n_thr, P.hi - P.lo, pe ? 128 : 256, [&](int, int, int k_lo, int k_hi) {
 		unsigned long long n_dev = 0, n_se_xa_w = 0, tsc = 0;
 		for (int k = k_lo; k < k_hi; ++k) {
 			const int i = P.lo + k, r = ends * i;   // the unit, its first read
 			// pair_wave_kernel's pair with an XA tag, or se_wave_kernel's read (with or without one): the job of those
-			const bool xa_k = (pstat && pstat[i] == PW_DECIDED_XA) || (dev_se_wave && wave_dec[i]);
-			const bool dev_k = xa_k || (pstat && pstat[i] == 1);
+			const bool xa_k = (dev_units && ustat[i] == PW_DECIDED_XA) || (dev_se_wave && wave_dec[i]);
+			const bool dev_k = xa_k || (dev_units && ustat[i] == PR_DECIDED);
 			const bool own_k = xa_k || (dev_k && P.wave.launched && wave_dec[i]);   // pair_wave_kernel's pair with the job of its own
 			const Job &J = xa_k ? P.xa : own_k ? P.wave : dev_k ? P.dev : P.host;
 			bool written = J.solen != nullptr;   // every record of the unit was written by sam_emit_kernel
@@ -691,7 +646,7 @@ void Call::replay(Part &P, int which)
 			if (written) {
 				const unsigned long long tq0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
 				for (int e = 0; e < ends; ++e) take_record(r + e, J, ends * k + e);
-				if (!pe && pstat[i] == SE_DECIDED_XA) ++n_se_xa_w;   // (counted apart: n_sam_dev stays the plain records of n_se_dev)
+				if (!pe && ustat[i] == SE_DECIDED_XA) ++n_se_xa_w;   // (counted apart: n_sam_dev stays the plain records of n_se_dev)
 				else n_dev += ends;
 				if (cpusec_on()) tsc += __builtin_ia32_rdtsc() - tq0;
 				continue;
@@ -748,7 +703,7 @@ void Call::sam_stage()
 	// Exactly one of the three holds; replay 1 (the host's records) closes every part.
 	const bool dev_early = pe && !dev_late, dev_mid = !pe, dev_last = pe && dev_late;
 	// pair_wave_kernel: wherever pair_simple_kernel ran and mate rescue runs on the device.  MPIBWA_HOST_RESCUE=1 turns it off.
-	dev_wave = pe && pstat_w && gpu_msw && getenv("MPIBWA_HOST_RESCUE") == nullptr;
+	dev_wave = pe && dev_units && gpu_msw && getenv("MPIBWA_HOST_RESCUE") == nullptr;
 	if (dev_wave) { wave_cand.assign(n_units, 0); wave_dec.assign(n_units, 0); }
 	// its XA listing: wherever it runs and the tags fit the kernel's side array.  MPIBWA_HOST_XA=1 turns it off.
 	dev_xa = dev_wave && gpu_sam && wave_pp.max_XA_hits <= PW_XA_CAP && getenv("MPIBWA_HOST_XA") == nullptr;
@@ -764,8 +719,8 @@ void Call::sam_stage()
 		for (int p = 0; p < n_parts; ++p) launch_dev(parts[p]);
 	// ... and the job of the reads it decided, behind the device job of the part on the same stream: both run under the host's planning
 	// of the remaining reads
-	if (!pe)
-		for (int p = 0; p < n_parts; ++p) se_wave_records(parts[p]);
+	if (dev_se_wave)
+		for (int p = 0; p < n_parts; ++p) own_job_records(parts[p], 1, se_bufs(), se_work, se_wxcnt);
 	for (int p = 0; p < n_parts; ++p) { mcollect(parts[p]); mlaunch(parts[p]); }
 	for (int p = 0; p < n_parts; ++p) {   // (the mate-rescue kernels of all parts are running)
 		Part &P = parts[p];
@@ -773,7 +728,7 @@ void Call::sam_stage()
 		collect(P, 0); mfinish(P); collect(P, 1);
 		// (the wave's pairs ride in the part's device job when it has not gone out yet, and get a job of their own behind it otherwise)
 		if (dev_wave) wave_records(P, !dev_late);
-		if (dev_xa) xa_records(P);
+		if (dev_xa) own_job_records(P, 2, W.wave[P.slot], P.work, P.wxcnt);
 		if (dev_late) launch_dev(P);
 		launch(P);
 	}
@@ -796,11 +751,10 @@ void Call::sam_stage()
 // how many units the device decided, and (MPIBWA_CPUSEC) why the others went to the host
 void Call::report_decisions()
 {
-	if (!pstat && !se_codes) return;
-	const uint8_t *codes = pstat ? pstat : se_codes;
+	if (!ustat) return;
 	uint64_t c[32] = {0};
-	for (int k = 0; k < n_units; ++k) ++c[codes[k] & 31];
-	if (pe) { STAT.n_pair_dev = c[1] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs; }
+	for (int k = 0; k < n_units; ++k) ++c[ustat[k] & 31];
+	if (pe) { STAT.n_pair_dev = c[PR_DECIDED] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs; }
 	else {
 		STAT.n_se_dev = c[SE_DECIDED]; STAT.n_se_wave_dev = n_se_wave; STAT.n_se_xa_dev = c[SE_DECIDED_XA]; STAT.n_se_xa_sam_dev = n_se_xa_sam.load();
 		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu; se_wave_kernel: handed %zu, decided plain %llu, decided with an XA tag %llu, XA records written %llu, list past %d %llu, tie %llu\n",
@@ -810,8 +764,9 @@ void Call::report_decisions()
 		                      (unsigned long long)c[SE_DECIDED_XA], n_se_xa_sam.load(), PW_MAXREG, (unsigned long long)c[SE_HOST_FULL], (unsigned long long)c[SE_HOST_TIE]);
 	}
 	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them and %llu with an XA tag, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
-	                      n_units, (unsigned long long)c[1], (unsigned long long)c[2], PR_MAXREG, (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[6],
-	                      (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11],
+	                      n_units, (unsigned long long)c[PR_DECIDED], (unsigned long long)c[PR_HOST_NO_HIT], PR_MAXREG, (unsigned long long)c[PR_HOST_MAXREG],
+	                      (unsigned long long)c[PR_HOST_PATCH], (unsigned long long)c[PR_HOST_LENGTH], (unsigned long long)c[PR_HOST_RESCUE], (unsigned long long)c[PR_HOST_NO_PAIR],
+	                      (unsigned long long)c[PR_HOST_SCORE], (unsigned long long)c[PR_HOST_SUPP], (unsigned long long)c[PR_HOST_XA],
 	                      (unsigned long long)n_wave, (unsigned long long)n_xa_pairs, (unsigned long long)c[PW_HOST_NO_RESULT], PW_MAXREG, (unsigned long long)c[PW_HOST_FULL], (unsigned long long)c[PW_HOST_TIE]);
 }
 

@@ -97,40 +97,47 @@ void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_
 	                   d_reqs, d_desc, d_xa_reqs, d_xa_cnt);
 }
 
-// The decided reads' requests and descriptors into a job of their own: dst[t] = first request of work item t's read in `reqs`, or < 0
-// (not a read of the job); [the line's request (an unused slot for the unmapped record), its XA requests]; desc: chunk-wide, by read.
-__global__ void se_wave_clear_desc_kernel(int r0, int n_reads, SamDesc *__restrict__ desc)
+// ---- the units a wave kernel decided, into a CIGAR-and-SAM job of their own: pair_wave_kernel's pairs (ENDS = 2) and this file's reads ----
+// dst[t] = first request of work item t's unit in `reqs`, or < 0 (not a unit of the job); per end [the end's request, its XA requests
+// (none without xa_cnt)]; desc: chunk-wide, by read.  A thread per work item.
+__global__ void wave_desc_clear_kernel(int r0, int n_reads, SamDesc *__restrict__ desc)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n_reads) desc[r0 + i].req = -1;
 }
-__global__ void se_wave_scatter_kernel(int n_work, const int *__restrict__ work, const int *__restrict__ dst, const AlnReq *__restrict__ w_reqs,
-                                       const SamDesc *__restrict__ w_desc, const AlnReq *__restrict__ xa_reqs, const uint8_t *__restrict__ xa_cnt,
-                                       AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
+template <int ENDS>
+__global__ void wave_scatter_kernel(int n_work, const int *__restrict__ work, const int *__restrict__ dst, const AlnReq *__restrict__ w_reqs,
+                                    const SamDesc *__restrict__ w_desc, const AlnReq *__restrict__ xa_reqs, const uint8_t *__restrict__ xa_cnt,
+                                    AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc)
 {
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= n_work || dst[t] < 0) return;
 	int at = dst[t];
-	const SamDesc d = w_desc[t];
-	desc[work[t]] = d;
-	if (d.req < 0) {   // the unmapped record: its slot is an unused one (read = -1), as se_simple_kernel leaves it
-		AlnReq none;
-		none.rb = none.re = 0; none.read = -1; none.qb = none.qe = none.w2 = none.truesc = none.pad = 0;
-		reqs[at] = none;
-		return;
+	for (int e = 0; e < ENDS; ++e) {
+		const int x = ENDS * t + e;
+		const SamDesc d = w_desc[x];
+		desc[ENDS * work[t] + e] = d;
+		// the unmapped record (se_wave_kernel alone writes one: pair_wave_kernel leaves a pair with an end without a hit to the host): its
+		// slot is an unused one (read = -1), as se_simple_kernel leaves it
+		if (ENDS == 1 && d.req < 0) {
+			AlnReq none;
+			none.rb = none.re = 0; none.read = -1; none.qb = none.qe = none.w2 = none.truesc = none.pad = 0;
+			reqs[at] = none;
+			return;
+		}
+		reqs[at++] = w_reqs[x];
+		if (!xa_cnt) continue;
+		const int c = xa_cnt[x] < PW_XA_CAP ? xa_cnt[x] : PW_XA_CAP;
+		for (int j = 0; j < c; ++j) reqs[at++] = xa_reqs[(size_t)x * PW_XA_CAP + j];
 	}
-	reqs[at++] = w_reqs[t];
-	if (!xa_cnt) return;
-	const int c = xa_cnt[t] < PW_XA_CAP ? xa_cnt[t] : PW_XA_CAP;
-	for (int j = 0; j < c; ++j) reqs[at++] = xa_reqs[(size_t)t * PW_XA_CAP + j];
 }
-void launch_se_wave_scatter(void *stream, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
-                            const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n)
+void launch_wave_job_scatter(void *stream, int ends, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
+                             const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n)
 {
-	if (clear_n > 0) hipLaunchKernelGGL(se_wave_clear_desc_kernel, dim3((clear_n + 255) / 256), dim3(256), 0, (hipStream_t)stream, clear_r0, clear_n, d_desc);
+	if (clear_n > 0) hipLaunchKernelGGL(wave_desc_clear_kernel, dim3((clear_n + 255) / 256), dim3(256), 0, (hipStream_t)stream, clear_r0, clear_n, d_desc);
 	if (n_work > 0)
-		hipLaunchKernelGGL(se_wave_scatter_kernel, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_work, d_dst, d_w_reqs, d_w_desc,
-		                   d_xa_reqs, d_xa_cnt, d_reqs, d_desc);
+		hipLaunchKernelGGL(ends == 2 ? wave_scatter_kernel<2> : wave_scatter_kernel<1>, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work,
+		                   d_work, d_dst, d_w_reqs, d_w_desc, d_xa_reqs, d_xa_cnt, d_reqs, d_desc);
 }
 
 } // namespace mbw

@@ -294,7 +294,7 @@ static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t
 	}
 	for (int t = 0; t < n_work; ++t) {
 		status[work[t]] = ws[t];
-		if (ws[t] != 1 && ws[t] != PW_DECIDED_XA) continue;
+		if (ws[t] != PR_DECIDED && ws[t] != PW_DECIDED_XA) continue;
 		for (int e = 0; e < 2; ++e) { ((SamDesc *)desc)[2 * work[t] + e] = w_ds[2 * t + e]; ((AlnReq *)req)[2 * work[t] + e] = w_rq[2 * t + e]; }
 		if (ws[t] != PW_DECIDED_XA) continue;
 		for (int e = 0; e < 2; ++e) {
