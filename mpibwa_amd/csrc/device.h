@@ -463,6 +463,10 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 #define MSW_TAIL_BUCKETS 9
 inline size_t msw_tail_ints(size_t n_req) { return 16 + MSW_TAIL_BUCKETS * n_req; }   // bucket counters + a list of n_req per bucket
 MswParams msw_params(const mem_opt_t *opt, int64_t l_pac);
+// Can mate rescue run on the device under these options?  Not with o_ins = 0: the reference's lazy-F loop then ends after the first
+// position of every segment (its exit test f - e_ins <= max(h, f) - (o_ins + e_ins) holds at once), a carry across a segment border
+// raises that one position only, and the kernels' Ffull would carry it on.  Every other gap penalty is the kernels'.
+bool msw_on_device(const mem_opt_t *opt);
 
 // ---- seed enumeration between SMEM and SA lookup (fm_kernels.hip) ----
 // per read: sort intervals by info, l_rep (src/bwamem.c:265-272) and the number of SA rows to look up

@@ -466,6 +466,8 @@ MswParams msw_params(const mem_opt_t *opt, int64_t l_pac)
 	return P;
 }
 
+bool msw_on_device(const mem_opt_t *opt) { return opt->o_ins > 0; }
+
 // What upload and broadcast-and-commit end with: the three index buffers are filled — derive the tables (any earlier ones are dropped
 // first) and mark the index usable.  MPIBWA_DEBUG: a progress line per step.
 static void build_derived_tables(const char *who)

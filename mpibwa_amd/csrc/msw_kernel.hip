@@ -7,8 +7,10 @@
 //   * inside the main loop F only propagates within a segment (every lane starts a row with F = 0);
 //   * E(i+1,j) is computed there, from the H that main loop sees ("we disallow adjacent insertion and then
 //     deletion", src/ksw.c:176) — i.e. from Hpre = max(Hdiag + s, E, Fseg), not from the final H;
-//   * the lazy-F loop afterwards carries F across segment borders and only raises H (exactly: its early exit
-//     never drops a carry that could still matter);
+//   * the lazy-F loop afterwards carries F across segment borders and only raises H.  With o_ins > 0 its early exit
+//     (f - e_ins <= max(h, f) - (o_ins + e_ins) in every lane) never drops a carry that could still matter.  With o_ins = 0
+//     that test holds at once: the loop ends after the first position of every segment, a carry raises that position only,
+//     and what follows does NOT hold — msw_on_device (device.hip) keeps such options away from these kernels;
 //   * positions qlen .. slen*P-1 are padding that scores 0 against everything, and they do take part in the row maximum;
 //   * the row maximum feeds a run-length list b[] whose "consecutive row" test looks at the row stored in the last
 //     entry, not at the previous row.
@@ -17,7 +19,9 @@
 //     Hpre = max(Hdiag + s, E, Fseg)      H = max(Hpre, Ffull)
 //     E'   = max(E - e_del, Hpre - oe_del, 0)
 //     F*'  = max(F* - e_ins, Hpre - oe_ins, 0)
-// which is value-for-value what the striped kernel leaves in its H / E arrays once a row is finished.  No value can
+// which, for o_ins > 0, is value-for-value what the striped kernel leaves in its H / E arrays once a row is finished (held against the
+// reference under fifteen sets of scoring options by tests/test_gpu_msw_options.py; tests/msw_model.py is this recurrence in Python
+// and shows the departure under o_ins = 0).  No value can
 // saturate in the byte flavour (qlen * a < 250 and shift = -min(mat)); a request whose scores could reach the 8-bit
 // ceiling is flagged and recomputed on the host.
 //

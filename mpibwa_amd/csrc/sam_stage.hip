@@ -687,7 +687,7 @@ void Call::sam_stage()
 	n_parts = (gpu_aln && n_units >= 20000 && n_sub > 1) ? 2 : 1;
 	if (const char *e = getenv("MPIBWA_SAM_PARTS")) n_parts = std::max(1, std::min(2, atoi(e)));
 	gpu_msw = pe && !(opt->flag & MEM_F_NO_RESCUE) && getenv("MPIBWA_HOST_MATESW") == nullptr && (int64_t)max_len * opt->a < 8192 &&
-	          msw_lds_bytes(max_len) <= 160 * 1024;
+	          msw_lds_bytes(max_len) <= 160 * 1024 && msw_on_device(opt);
 	// When does the device units' job go out?  Alone, right behind the pairing kernel (its kernels and the copies of its records run
 	// under the host's work on the other pairs: 94.8-96.8 vs 98.7-102.8 ms per chunk); with other calls in flight, next to the host
 	// pairs' job (their kernels fill the gaps anyway and an early launch only delays their seeding: 12.0-12.7 vs 10.9-11.3 Mreads/s).

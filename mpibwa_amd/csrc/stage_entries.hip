@@ -166,6 +166,13 @@ extern "C" int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, cons
 // end e, their requests at xa_req[(2k + e) * PW_XA_CAP ..] (AlnReq, pad = the entry's contig), the counts also in desc[].flag bits 16-19.
 extern "C" int mi355x_pair_wave_maxreg(void) { return PW_MAXREG; }
 extern "C" int mi355x_pair_wave_xa_cap(void) { return PW_XA_CAP; }
+// the record of a mate-rescue request that the device does not answer
+static MswRes msw_host_request()
+{
+	MswRes r;
+	r.score = 0; r.te = r.qe = r.score2 = r.te2 = r.tb = r.qb = -1; r.flags = 1;
+	return r;
+}
 static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
                            int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
                            void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt)
@@ -255,9 +262,14 @@ static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t
 		std::vector<int> h_list(2 * n_mreq + 16);
 		d_list = DevArr<int>((2 * n_mreq + 16) * sizeof(int) + PAD);
 		d_tail = DevArr<int>(msw_tail_ints(n_mreq) * sizeof(int) + PAD);
-		launch_msw(st, msw_params(opt, l_pac), (int)n_mreq, d_mreq, d_seq, d_off, d_len, d_pac, d_mres, d_rows, max_len, (const MswReq *)mreq.data(), lens.data(),
-		           h_list.data(), d_list, d_tail);
-		HIP_OK(hipStreamSynchronize(st));   // (h_list is read by the copy queued in launch_msw)
+		if (msw_on_device(opt)) {
+			launch_msw(st, msw_params(opt, l_pac), (int)n_mreq, d_mreq, d_seq, d_off, d_len, d_pac, d_mres, d_rows, max_len, (const MswReq *)mreq.data(),
+			           lens.data(), h_list.data(), d_list, d_tail);
+			HIP_OK(hipStreamSynchronize(st));   // (h_list is read by the copy queued in launch_msw)
+		} else {   // options the kernels do not take: every request is the host's (flags = 1), as the pipeline would have kept them all
+			const std::vector<MswRes> back(n_mreq, msw_host_request());
+			HIP_OK(hipMemcpy(d_mres, back.data(), n_mreq * sizeof(MswRes), hipMemcpyHostToDevice));
+		}
 	}
 	DevArr<int> d_work(nw * 4 + PAD, work.data(), nw * 4);
 	DevArr<DevReg> d_lists(lists.size() * sizeof(DevReg) + PAD, lists.data(), lists.size() * sizeof(DevReg));
@@ -531,6 +543,13 @@ extern "C" int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 {
 	require_any_device();
 	if (n_req <= 0) return 0;
+	static_assert(sizeof(MswRes) == 32, "MswRes layout");
+	if (!msw_on_device(opt)) {   // options the kernels do not take: every request is handed back (flags = 1: recompute on the host)
+		const MswRes back = msw_host_request();
+		for (int i = 0; i < n_req; ++i) memcpy(out8 + 8 * (size_t)i, &back, sizeof(MswRes));
+		if (kernel_ms) *kernel_ms = 0;
+		return 0;
+	}
 	hipStream_t st = 0;
 	const PackedReads R = pack_reads(n_reads, reads, off, 4);   // reads go into 16-byte slots as in the pipeline
 	const int max_len = R.max_len;
@@ -556,7 +575,6 @@ extern "C" int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	           d_tail);
 	double ms = tm.stop(st);
 	HIP_OK(hipGetLastError());
-	static_assert(sizeof(MswRes) == 32, "MswRes layout");
 	d_res.download(out8, (size_t)n_req * sizeof(MswRes));
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;

@@ -243,3 +243,22 @@ def test_pair_wave_stage_on_long_synthetic_lists(stage, which_pes):
             assert got == {f: L[f] for f in got}, (k, e, got, L)
     print("synthetic long lists: pairs", len(lists), "reference-plain", n_plain, "taken", n_taken, "alignments", n_align, "status", np.bincount(status, minlength=16))
     assert n_plain >= 20 and n_taken * 2 >= n_plain, (n_plain, n_taken)
+
+
+def test_pair_wave_stage_without_insertion_open_penalty(stage):
+    """o_ins = 0: mate rescue is not the kernels' (msw_on_device), the stage entry answers every listed alignment with flags = 1, and a
+    pair whose replay needs one is left to the host (PW_HOST_NO_RESULT = 12); what the kernel still decides is the reference's."""
+    from mpibwa_amd import simulate
+    eng = stage["engine"]
+    kw = dict(o_ins=0)
+    reads = simulate.reads_to_ascii(pw.make_reads(stage["seqs"], stage["copies"], True)[:400])
+    opt, ropt, _ = _opts(stage, kw)
+    pairs, pes = pw.reference_side(stage["ref"], ropt, reads)
+    status, _, _, n_align = eng.pairs_wave(opt, pes, [r for P in pairs for r in P.reads], _device_regs(pairs))
+    assert n_align > 0 and (status == 12).sum() >= 10, (n_align, np.bincount(status, minlength=16))
+    _check(stage, kw, reads, "o_ins = 0")
+    # the same pairs under the defaults: the kernel reads its rescue results and decides more of them
+    opt, ropt, _ = _opts(stage, {})
+    pairs, pes = pw.reference_side(stage["ref"], ropt, reads)
+    status_d, _, _, _ = eng.pairs_wave(opt, pes, [r for P in pairs for r in P.reads], _device_regs(pairs))
+    assert (status_d == 1).sum() > (status == 1).sum(), (np.bincount(status_d, minlength=16), np.bincount(status, minlength=16))

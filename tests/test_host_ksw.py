@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from msw_cases import OPTION_SETS, fill_scmat
 from oracle import pyoracle as po
 
 MAT = np.array([1, -4, -4, -4, -1, -4, 1, -4, -4, -1, -4, -4, 1, -4, -1, -4, -4, -4, 1, -1, -1, -1, -1, -1, -1], dtype=np.int8)
@@ -14,7 +15,7 @@ class kswr_t(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("score", "te", "qe", "score2", "te2", "tb", "qb")]
 
 
-def _cases(n, seed):
+def _cases(n, seed, a=1, min_seed_len=19):
     rng = np.random.default_rng(seed)
     for it in range(n):
         ql = int(rng.choice([20, 75, 150, 151, 250, int(rng.integers(19, 260))]))
@@ -31,32 +32,41 @@ def _cases(n, seed):
                 t[p:p + ql] = m
         if rng.random() < 0.1:
             q[rng.integers(0, ql)] = 4
-        byte = XBYTE if ql < 250 else 0
-        xtra = XSUBO | XSTART | byte | 19
+        byte = XBYTE if ql * a < 250 else 0
+        xtra = XSUBO | XSTART | byte | min_seed_len * a
         if rng.random() < 0.15:
             xtra = XSTART | (byte if rng.random() < 0.5 else 0)
         yield q, t, xtra
 
 
-@pytest.mark.skipif(not po.ref_available(), reason="oracle/_ref/libbwaref.so not built")
+# the defaults and three other sets of tests/msw_cases.py: no gap-open penalty; unequal, larger penalties; a = 2, which moves the byte / word
+# boundary to 125 bases and the matrix with it
+OPTS = [OPTION_SETS[n] for n in ("default", "O0", "asym", "a2b3")]
+
+
 def test_align2_matches_reference(built):
+    # decided here, after `built` has built the reference library where its source is present (not at import, before it)
+    if not po.ref_available():
+        pytest.skip("oracle/_ref/libbwaref.so not built")
     from mpibwa_amd import api
     lib = api.load_library()
     ref = po.ref_lib()
     ref.ksw_align2.restype = kswr_t
     ref.ksw_align2.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
-    n = 0
-    for q, t, xtra in _cases(700, 31):
-        qq, tt = q.copy(), t.copy()
-        w = ref.ksw_align2(len(q), qq.ctypes.data, len(t), tt.ctypes.data, 5, MAT.ctypes.data, 6, 1, 6, 1, xtra, None)
-        want = np.array([w.score, w.te, w.qe, w.score2, w.te2, w.tb, w.qb])
-        for portable in (0, 1):
-            out = np.zeros(7, dtype=np.int32)
-            lib.mi355x_host_ksw_align2(len(q), q.ctypes.data, len(t), t.ctypes.data, MAT.ctypes.data, 6, 1, 6, 1, xtra, portable,
-                                       out.ctypes.data)
-            assert (out == want).all(), (portable, len(q), len(t), hex(xtra), out, want)
-        n += 1
-    assert n == 700
+    for a, b, o_del, e_del, o_ins, e_ins, msl in OPTS:
+        mat = fill_scmat(a, b)
+        n = 0
+        for q, t, xtra in _cases(700, 31, a, msl):
+            qq, tt = q.copy(), t.copy()
+            w = ref.ksw_align2(len(q), qq.ctypes.data, len(t), tt.ctypes.data, 5, mat.ctypes.data, o_del, e_del, o_ins, e_ins, xtra, None)
+            want = np.array([w.score, w.te, w.qe, w.score2, w.te2, w.tb, w.qb])
+            for portable in (0, 1):
+                out = np.zeros(7, dtype=np.int32)
+                lib.mi355x_host_ksw_align2(len(q), q.ctypes.data, len(t), t.ctypes.data, mat.ctypes.data, o_del, e_del, o_ins, e_ins, xtra, portable,
+                                           out.ctypes.data)
+                assert (out == want).all(), ((a, b, o_del, e_del, o_ins, e_ins), portable, len(q), len(t), hex(xtra), out, want)
+            n += 1
+        assert n == 700
 
 
 def test_align2_sse2_equals_portable(built):
