@@ -216,6 +216,23 @@ size_t chain_scratch_bytes(int n_reads);
 size_t reg_pack_tmp_bytes(int n_reads);
 void launch_reg_pack(void *stream, int n_reads, const int *d_reg_beg, const int *d_nregs, int *d_reg_pos, const DevReg *d_regs, DevReg *d_packed,
                      void *d_tmp, size_t tmp_bytes, const C2aUnits *units = nullptr, const int *d_chain_beg = nullptr, const int *d_chain_cnt = nullptr);
+// One chain -> regions job: c2a_kernel over the chains of n_reads reads, then the prefix sum and pack of their regions, queued on one
+// stream.  Phase 1 of the pipeline (phase1.hip: extend) and the stage entry (stage_entries.hip: mi355x_c2a_batch) both queue it through
+// queue_c2a(), which allocates nothing: every array is the caller's, sized before (the pipeline calls it while it holds a turn).
+struct C2aJob {
+	int n_reads = 0, max_len = 0;
+	const uint8_t *d_seq = nullptr; const int64_t *d_off = nullptr; const int *d_len = nullptr;   // the reads of the job
+	const int *d_chain_beg = nullptr, *d_chain_cnt = nullptr, *d_reg_beg = nullptr, *d_order = nullptr;   // per read; d_order: c2a_launch_order
+	const DevChain *d_chains = nullptr; const DevSeed *d_seeds = nullptr; unsigned int *d_srt = nullptr;
+	const int *d_tab = nullptr; int tab_stride = 0;   // c2a_length_tables
+	const uint8_t *d_pac = nullptr;
+	C2aUnits units;                                   // from c2a_prepare_units (a round trip: before the job is queued)
+	DevReg *d_regs = nullptr; int *d_nregs = nullptr;  // sparse per-read slots, n_reads + 1 counts
+	unsigned long long *d_stat = nullptr;              // C2A_STAT_SLOTS lines, zeroed by the caller
+	int *d_reg_pos = nullptr; DevReg *d_packed = nullptr; void *d_tmp = nullptr; size_t tmp_bytes = 0;   // reg_pack: n_reads + 1 places, the packed list, reg_pack_tmp_bytes(n_reads)
+};
+// on `stream`: [ev_a] c2a_kernel [ev_b], reg_pack.  early: C2aParams::early; ev_a / ev_b: hipEvent_t around the kernel, or null
+void queue_c2a(void *stream, const mem_opt_t *opt, int64_t l_pac, int early, const C2aJob &J, void *ev_a = nullptr, void *ev_b = nullptr);
 
 // ---- final global re-alignment on the device (aln_kernel.hip) ----
 struct AlnReq {                  // one call of mem_reg2aln's DP loop (src/bwamem.c:1106-1122)

@@ -386,6 +386,22 @@ void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const Chun
 	                                                   J.grid_blocks);
 }
 
+void queue_c2a(void *stream, const mem_opt_t *opt, int64_t l_pac, int early, const C2aJob &J, void *ev_a, void *ev_b)
+{
+	hipStream_t st = (hipStream_t)stream;
+	C2aParams cp;
+	ExtParams ep;
+	c2a_params(opt, l_pac, early, cp, ep);
+	const C2aUnits *units = J.units.max_units > 0 ? &J.units : nullptr;
+	if (ev_a) HIP_OK(hipEventRecord((hipEvent_t)ev_a, st));
+	// one wavefront per read (any read length)
+	launch_c2a(st, cp, ep, J.n_reads, J.d_seq, J.d_off, J.d_len, J.d_chain_beg, J.d_chain_cnt, J.d_chains, J.d_seeds, J.d_srt, J.d_reg_beg, J.d_regs, J.d_nregs,
+	           J.d_tab, J.tab_stride, J.d_pac, J.d_stat, J.max_len, J.d_order, units);
+	if (ev_b) HIP_OK(hipEventRecord((hipEvent_t)ev_b, st));
+	// the regions sit in sparse per-read slots: prefix sum + pack on the device, queued behind the kernel
+	launch_reg_pack(st, J.n_reads, J.d_reg_beg, J.d_nregs, J.d_reg_pos, J.d_regs, J.d_packed, J.d_tmp, J.tmp_bytes, units, J.d_chain_beg, J.d_chain_cnt);
+}
+
 // band clamp of src/ksw.c:395-407 (host side, double arithmetic as in the reference)
 int clamp_band(const mem_opt_t *opt, int qlen, int w, int end_bonus)
 {

@@ -222,6 +222,21 @@ void filter_chained_seeds(const mem_opt_t *opt, const bntseq_t *bns, const uint8
 struct DevChain;
 struct DevSeed;
 void pack_chain_for_device(const bntseq_t *bns, const HChain &ch, int l_query, const int *gap_h, std::vector<uint64_t> &key, DevChain &d, DevSeed *osd);
+// Host chaining of one read into the layout the extension kernels read; what a thread keeps from read to read, and (prof) the cycles
+// of its steps: seeds -> HSeed, chaining, filter, mem_flt_chained_seeds, pack; [5] seeds, [6] reads with more than 64 seeds
+struct HostChainer {
+	ChainScratch scr;
+	std::vector<HSeed> hs;
+	std::vector<HChain *> chains;
+	std::vector<uint64_t> key;
+	bool prof = false;
+	unsigned long long tsc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+// The read's ns seeds (SA values sa[k], (qbeg, len) pairs qbl[2k ..]) -> chains_from_seeds -> chain_filter -> filter_chained_seeds (query
+// given: the read's codes) -> pack_chain_for_device.  The kept chains are appended to och and their seeds, in visiting order, to osd;
+// seed_beg = the run's place in osd.  gap_h: row 0 of c2a_length_tables.  Returns the number of chains kept.
+int host_chain_read(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int l_query, const uint8_t *query, const uint64_t *sa, const int32_t *qbl,
+                    int ns, int l_rep, const int *gap_h, HostChainer &W, std::vector<DevChain> &och, std::vector<DevSeed> &osd);
 int  sort_dedup_patch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, uint8_t *query, HRegV &regs);
 int  mark_primary_se(const mem_opt_t *opt, HRegV &a, int64_t id);
 void reorder_primary5(int T, HRegV &a);

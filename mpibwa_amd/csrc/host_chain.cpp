@@ -468,6 +468,39 @@ void pack_chain_for_device(const bntseq_t *bns, const HChain &ch, int l_query, c
 	}
 }
 
+int host_chain_read(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int l_query, const uint8_t *query, const uint64_t *sa, const int32_t *qbl,
+                    int ns, int l_rep, const int *gap_h, HostChainer &W, std::vector<DevChain> &och, std::vector<DevSeed> &osd)
+{
+	if (ns == 0) return 0;
+	const bool prof = W.prof;
+	const unsigned long long c0 = prof ? __builtin_ia32_rdtsc() : 0;
+	W.hs.resize(ns);
+	for (int k = 0; k < ns; ++k) {
+		HSeed &h = W.hs[k];
+		h.rbeg = (int64_t)sa[k]; h.qbeg = qbl[2 * k]; h.len = h.score = qbl[2 * k + 1];
+	}
+	const unsigned long long c1 = prof ? __builtin_ia32_rdtsc() : 0;
+	chains_from_seeds(opt, bns, l_query, W.hs.data(), ns, l_rep, W.scr, W.chains);
+	const unsigned long long c2 = prof ? __builtin_ia32_rdtsc() : 0;
+	chain_filter(opt, W.scr, W.chains);
+	const unsigned long long c3 = prof ? __builtin_ia32_rdtsc() : 0;
+	if (query) filter_chained_seeds(opt, bns, pac, l_query, query, W.chains);
+	const unsigned long long c4 = prof ? __builtin_ia32_rdtsc() : 0;
+	for (const HChain *cp : W.chains) {
+		const size_t at = osd.size();
+		osd.resize(at + cp->seeds.size());
+		DevChain d;
+		pack_chain_for_device(bns, *cp, l_query, gap_h, W.key, d, osd.data() + at);
+		d.seed_beg = (int)at;
+		och.push_back(d);
+	}
+	if (prof) {
+		W.tsc[0] += c1 - c0; W.tsc[1] += c2 - c1; W.tsc[2] += c3 - c2; W.tsc[3] += c4 - c3; W.tsc[4] += __builtin_ia32_rdtsc() - c4;
+		W.tsc[5] += ns; W.tsc[6] += ns > 64;
+	}
+	return (int)W.chains.size();
+}
+
 int cal_max_gap(const mem_opt_t *opt, int qlen)
 {
 	int l_del = (int)((double)(qlen * opt->a - opt->o_del) / opt->e_del + 1.);

@@ -182,6 +182,31 @@ double cpu_sec();
 void stage(int id);
 // Wait for a stream without burning a core (pipeline.hip)
 void stream_wait(hipStream_t st);
+// MPIBWA_CPUSEC: the stages print where their host cycles and their work items went (read once per process)
+inline bool cpusec_on() { static const bool on = getenv("MPIBWA_CPUSEC") != nullptr; return on; }
+
+// The turns on the big kernels of phase 1 are taken in the order of arrival.  With a plain mutex a caller whose thread had to be
+// scheduled first (more runnable threads than cores) kept losing the turn to callers that were already running: now and then a chunk
+// that takes 0.6 s took 3 s with eight callers, the others none the faster for it.
+// Whoever holds a turn must not allocate: the code between lock() and unlock() is a function of plain pointers.
+class TurnLock {
+public:
+	void lock()
+	{
+		std::unique_lock<std::mutex> lk(m_);
+		const unsigned long long mine = next_++;
+		cv_.wait(lk, [&]() { return serving_ == mine; });
+	}
+	void unlock()
+	{
+		{ std::lock_guard<std::mutex> lk(m_); ++serving_; }
+		cv_.notify_all();
+	}
+private:
+	std::mutex m_;
+	std::condition_variable cv_;
+	unsigned long long next_ = 0, serving_ = 0;
+};
 
 struct EvTimer {
 	hipEvent_t a, b;
@@ -286,6 +311,40 @@ struct CallCtx {
 // what a sub-batch of phase 1 reports: kernel times, wall times per stage, counters
 struct P1 { double k_smem = 0, k_sa = 0, k_ext = 0, k_dedup = 0, smem = 0, sa = 0, chain = 0, ext = 0, regs = 0; uint64_t smem_bytes = 0, smem_tab_bytes = 0, sa_bytes = 0, cells = 0, n_ext = 0, n_intv = 0, n_seeds = 0, n_chains = 0, n_dedup_dev = 0, n_dedup_host = 0; };
 
+// What a sub-batch of phase 1 carries from stage to stage (phase1.hip): reads lo .. hi of the chunk on the lane's stream, with the lane's
+// buffers and up to lane_thr host threads; every pointer below is into those buffers (d_*: device; the others: page-locked host copies)
+struct SubBatch {
+	const int lo, hi, n_sb;
+	LaneBufs &L; HostBuf &reg_arena; const hipStream_t lst; const int lane_thr; P1 &ps;
+	// encode: a block of counters, the length tables of c2a_length_tables (row 0: cal_max_gap) and their stride
+	unsigned long long *d_cnt = nullptr, *cnt = nullptr;
+	std::vector<int> tab;
+	int *d_tab = nullptr, TS = 0;
+	// seed: the capacity per read that held every interval list, the lists and their lengths; seeds / l_rep / intervals per read
+	int cap = 0;
+	bool count_blocks = false;        // MPIBWA_SMEM_COUNT
+	uint64_t *d_intv = nullptr;
+	int *d_nintv = nullptr, *d_nseeds = nullptr, *d_lrep = nullptr, *nseeds = nullptr, *lrep = nullptr, *nintv = nullptr;
+	// sa_and_chain: read i's seeds are seed_off[i] .. seed_off[i + 1] of S; their SA values and (qbeg, len) pairs where the host chains
+	int64_t *seed_off = nullptr, S = 0;
+	uint64_t *sa = nullptr; int32_t *qbl = nullptr;
+	bool dev_chain = false;           // chain_kernel ran: nch[i] = chains it kept for read i, -1 = the host's read
+	int *nch = nullptr;
+	// host_chain: NC chains and NS kept seeds of the host-chained reads, behind `base` slots on the device; n_slots = size of the seed /
+	// order / region arrays there; per read its first chain, its chains, its first region slot
+	int64_t base = 0, n_slots = 0;
+	int NC = 0, NS = 0;
+	DevChain *hchains = nullptr; DevSeed *hseeds = nullptr; unsigned int *hsrt = nullptr;
+	int *chain_beg = nullptr, *chain_cnt = nullptr, *reg_beg = nullptr;
+	// extend: regions per read, where they start in hregs; the redundancy pass on the device: status / survivors / their places in the
+	// raw list, per read (null: not run)
+	int *nregs = nullptr;
+	std::vector<int> reg_pos;
+	DevReg *hregs = nullptr;
+	const uint8_t *dd_status = nullptr;
+	const int *dd_m = nullptr, *dd_keep = nullptr;
+};
+
 // One CIGAR-and-SAM job in flight: what was launched, and the host copies of what came back
 struct Job {
 	JobBufs *B = nullptr;
@@ -375,7 +434,14 @@ struct Call {
 	int *d_pr_nfirst = nullptr;
 	int n_sub = 1, n_lanes = 1;
 	void phase1_all();                // the sub-batches over the lanes
-	void phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t lst, int lane_thr, P1 &ps);
+	void phase1(int lo, int hi, LaneBufs &L, HostBuf &reg_arena, hipStream_t lst, int lane_thr, P1 &ps);   // the schedule of one sub-batch over:
+	void encode(SubBatch &B);         // nt4 codes in place and on the device, the length tables
+	void seed(SubBatch &B);           // SMEM seeding and the seed counts, under the seeding turn
+	void sa_and_chain(SubBatch &B);   // seed enumeration, SA lookup, chaining on the device, the seeds of the reads it declined
+	void host_chain(SubBatch &B);     // those reads chained by the host; the device layout of all chains
+	void extend(SubBatch &B);         // chain -> regions under the extension turn, the regions' way back
+	void regions(SubBatch &B);        // mem_sort_dedup_patch per read (or the device's survivors), into slices of the arena
+	void votes(SubBatch &B);          // the insert-size votes of the sub-batch
 
 	// ---- insert-size statistics ----
 	mem_pestat_t pes[4];

@@ -8,7 +8,6 @@ static_assert(sizeof(SamDesc) == sizeof(SamDescH), "host/device record layouts d
 static_assert(sizeof(MswReq) == sizeof(MswReqH) && sizeof(MswRes) == sizeof(MswResH), "host/device record layouts differ");
 static_assert(sizeof(AlnReq) == sizeof(AlnReqH) && sizeof(AlnHdr) == sizeof(AlnHdrH), "host/device record layouts differ");
 static const int MSW_MAX_T = 4096;
-static bool cpusec_on() { static const bool on = getenv("MPIBWA_CPUSEC") != nullptr; return on; }
 
 // ---- inputs of the SAM stage (names, qualities, contig names, the gap table of the CIGAR kernel): packed and uploaded by a
 // thread of their own on a side stream while phase 1 runs — 100 MB of qualities per chunk that nothing before the SAM stage reads

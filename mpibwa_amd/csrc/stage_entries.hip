@@ -621,30 +621,16 @@ extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns,
 		d_ch.download((void *)chains.data(), (size_t)S * sizeof(DevChain));
 		d_sd.download((void *)seeds.data(), (size_t)S * sizeof(DevSeed));
 	} else {
-		ChainScratch scr;
-		std::vector<HSeed> hs;
-		std::vector<HChain *> ch;
-		std::vector<uint64_t> key;
+		// the pipeline's host chaining of a read (without mem_flt_chained_seeds: no reads here), its run moved to the slots from seed_off[i]
+		HostChainer hc;
+		std::vector<DevChain> och;
+		std::vector<DevSeed> osd;
 		for (int i = 0; i < n_reads; ++i) {
-			const int ns = nseeds[i];
-			if (ns == 0) continue;
-			hs.resize(ns);
-			for (int k = 0; k < ns; ++k) {
-				const int64_t so = seed_off[i] + k;
-				hs[k].rbeg = (int64_t)rbeg[so]; hs[k].qbeg = qbeg_len[2 * so]; hs[k].len = hs[k].score = qbeg_len[2 * so + 1];
-			}
-			chains_from_seeds(opt, bns, lens[i], hs.data(), ns, l_rep[i], scr, ch);
-			chain_filter(opt, scr, ch);
-			int64_t cur = seed_off[i];
-			int c = 0;
-			for (const HChain *cp : ch) {
-				DevChain &d = chains[seed_off[i] + c];
-				pack_chain_for_device(bns, *cp, lens[i], tab.data(), key, d, seeds.data() + cur);
-				d.seed_beg = (int)cur;
-				cur += d.n_seeds;
-				++c;
-			}
-			nch[i] = c;
+			const int64_t so = seed_off[i];
+			och.clear(); osd.clear();
+			nch[i] = host_chain_read(opt, bns, nullptr, lens[i], nullptr, rbeg + so, qbeg_len + 2 * so, nseeds[i], l_rep[i], tab.data(), hc, och, osd);
+			for (int c = 0; c < nch[i]; ++c) { chains[so + c] = och[c]; chains[so + c].seed_beg += (int)so; }
+			std::copy(osd.begin(), osd.end(), seeds.begin() + so);
 		}
 	}
 	int64_t at = 0;
@@ -671,7 +657,7 @@ extern "C" int64_t mi355x_chain_batch(const mem_opt_t *opt, const bntseq_t *bns,
 // Stage-level entry point of chain -> regions (tests): see include/mpibwa_amd.h.  The chains are packed by the library's own
 // pack_chain_for_device and laid out as the pipeline lays out device-chained reads (layout 0: read r owns the slots from seed_off[r],
 // which leaves room behind its seeds as the seeding counts do) or host-chained ones (layout 1: dense, behind S slots); then the
-// pipeline's sequence: the length tables, the launch order, the chain groups with their round trip, c2a_kernel, reg_pack_kernel.
+// pipeline's sequence: the length tables, the launch order, the chain groups with their round trip, and the pipeline's own queue_c2a().
 extern "C" int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads, const uint8_t *reads, const int64_t *off,
                                     const int *n_chains, const int *chain_rid, const float *chain_frac, const int *chain_nseeds,
                                     const int64_t *seed_rbeg, const int *seed_qbeg, const int *seed_len, const int *seed_score,
@@ -775,17 +761,16 @@ extern "C" int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, i
 	d_stat.zero();
 	{
 		C2aGroupBufs B;
-		const C2aUnits units = c2a_prepare_units(st, B, heavy_t, n_reads, chain_cnt.data(), (size_t)std::max<int64_t>(n_chain_slots, 1), d_cbeg, d_rbeg,
-		                                         d_ch, d_nregs);
-		C2aParams cp;
-		ExtParams ep;
-		c2a_params(opt, l_pac, early, cp, ep);
-		launch_c2a(st, cp, ep, n_reads, d_seq, d_off, d_len, d_cbeg, d_ccnt, d_ch, d_sd, d_srt, d_rbeg, d_regs, d_nregs, d_tab, TS,
-		           (const uint8_t *)dev_index().d_pac, d_stat, max_len, d_order, units.max_units > 0 ? &units : nullptr);
-		launch_reg_pack(st, n_reads, d_rbeg, d_nregs, d_reg_pos, d_regs, d_packed, d_tmp, tmp_bytes, units.max_units > 0 ? &units : nullptr, d_cbeg, d_ccnt);
+		C2aJob J;
+		J.n_reads = n_reads; J.max_len = max_len; J.d_seq = d_seq; J.d_off = d_off; J.d_len = d_len;
+		J.d_chain_beg = d_cbeg; J.d_chain_cnt = d_ccnt; J.d_reg_beg = d_rbeg; J.d_order = d_order;
+		J.d_chains = d_ch; J.d_seeds = d_sd; J.d_srt = d_srt; J.d_tab = d_tab; J.tab_stride = TS; J.d_pac = (const uint8_t *)dev_index().d_pac;
+		J.units = c2a_prepare_units(st, B, heavy_t, n_reads, chain_cnt.data(), (size_t)std::max<int64_t>(n_chain_slots, 1), d_cbeg, d_rbeg, d_ch, d_nregs);
+		J.d_regs = d_regs; J.d_nregs = d_nregs; J.d_stat = d_stat; J.d_reg_pos = d_reg_pos; J.d_packed = d_packed; J.d_tmp = d_tmp; J.tmp_bytes = tmp_bytes;
+		queue_c2a(st, opt, l_pac, early, J);
 		HIP_OK(hipStreamSynchronize(st));
 		HIP_OK(hipGetLastError());
-		if (n_units) *n_units = units.max_units;
+		if (n_units) *n_units = J.units.max_units;
 		B.release();
 	}
 	std::vector<int> nregs(n_reads), reg_pos(n_reads + 1);
