@@ -274,15 +274,25 @@ __device__ __forceinline__ uint32_t msw_slo(const MswParams &P, int t) { return 
 __device__ __forceinline__ int msw_s4(const MswParams &P, int t) { return t == 0 ? P.s4[0] : t == 1 ? P.s4[1] : t == 2 ? P.s4[2] : P.s4[3]; }
 
 // tail_n[MSW_TAIL_BUCKETS] (zeroed before the launch) / tail_list[MSW_TAIL_BUCKETS][tail_cap]: the alignments msw_tail_kernel completes
+//
+// SLEN = 0: the general form — the row state in LDS, any segment length, the lengths of a wave may differ.
+// SLEN > 0: every work item of the launch has that segment length (launch_msw sorts them), so a lane's S = 4 SLEN positions are a
+// compile-time fact: the state words and the code words are register arrays, the cell loop is unrolled in full, a segment ends where
+// (kk + 1) % SLEN == 0 (F_seg restarts by assignment) and the three skew steps without a row are one branch around the sweep.  LDS
+// then holds the score table alone, and the eight lookups of a block are issued ahead of the block's arithmetic.  H and E of a position
+// are two packed 16-bit registers (TWO: no v_perm_b32 to unpack and repack them) where that leaves three waves per SIMD or measured
+// faster with two (SLEN <= 13), else four bytes in one register as in LDS (SLEN = 16: 146 instead of 206 VGPRs) — DESIGN 4.4.
+template <int SLEN>
 __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int n_req, const int *__restrict__ pairs, const MswReq *__restrict__ req,
                                                   const uint8_t *__restrict__ seq, const int64_t *__restrict__ off, const int *__restrict__ lens,
                                                   const uint8_t *__restrict__ pac, MswRes *__restrict__ res, uint16_t *__restrict__ rows, int s_max,
                                                   int *__restrict__ tail_n, int *__restrict__ tail_list, int tail_cap)
 {
+	constexpr bool REGS = SLEN > 0, TWO = REGS && SLEN < 16;
 	extern __shared__ uint32_t lds2[];
 	uint32_t *cell = lds2;                                   // [s_max][64]: H_A, E_A, H_B, E_B as bytes
 	uint32_t *codes = lds2 + (size_t)s_max * 64;             // [(s_max + 7) / 8][64]: eight 4-bit entries per dword: query code, bit 3 = end of a segment
-	uint32_t *stab = codes + (size_t)((s_max + 7) >> 3) * 64;   // [16][8]: (target base A, target base B) x query code -> the two scores, packed
+	uint32_t *stab = REGS ? lds2 : codes + (size_t)((s_max + 7) >> 3) * 64;   // [16][8]: (target base A, target base B) x query code -> the two scores, packed
 	const int lane = threadIdx.x, j = lane & 3;
 	for (int e = lane; e < 128; e += 64) {
 		const int ta = e >> 5, tb = (e >> 3) & 3, q = e & 7;
@@ -303,7 +313,24 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 	const int tnA = (int)(qa.re - qa.rb), tnB = (int)(qb.re - qb.rb);
 	const int slen = (qlen + 15) / 16, npos = slen * 16, S = npos >> 2;   // byte flavour: 16 segments
 	const uint8_t *ms = seq + (live ? off[qa.read] : 0);
-	if (live) {
+	// the register form's state: RS positions of this lane, and their query codes as byte offsets into a row of the score table
+	// (code * 4, four to a dword: the address of a lookup is one v_add_u32 with a byte select; no segment flags: the ends are known to
+	// the compiler)
+	constexpr int RS = REGS ? 4 * SLEN : 1, RC = RS / 4 + (RS % 4 != 0);
+	uint32_t st0[RS], st1[TWO ? RS : 1], cdreg[RC];
+	if constexpr (REGS) {
+#pragma unroll
+		for (int kk = 0; kk < RS; ++kk) st0[kk] = 0;
+#pragma unroll
+		for (int kk = 0; kk < (TWO ? RS : 1); ++kk) st1[kk] = 0;
+#pragma unroll
+		for (int c = 0; c < RC; ++c) {
+			uint32_t cd = 0;
+#pragma unroll
+			for (int u = 0; u < 4; ++u) cd |= msw_code(ms, qlen, qa.is_rev, j * RS + c * 4 + u) << (8 * u + 2);   // (not live: qlen = 0, padding)
+			cdreg[c] = cd;
+		}
+	} else if (live) {
 		for (int kk = 0; kk < S; ++kk) cell[kk * 64 + lane] = 0;
 		for (int c = 0; c * 8 < S; ++c) {
 			uint32_t cd = 0;
@@ -427,7 +454,102 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 			if (stop) run = false;
 		}
 	};
-	if (slen_u > 0) forward(std::true_type{}); else forward(std::false_type{});
+	// The same pass with the state in registers: the recurrence, the order of the cells and every key are those of `forward`.
+	auto forward_regs = [&]() {
+		constexpr int S = RS, SL = REGS ? SLEN : 1;
+		const int tn = tnA > tnB ? tnA : tnB;
+		bool run = live && tn > 0;
+		const msw_s2 oe_del = s2_splat(P.o_del + P.e_del), oe_ins = s2_splat(P.o_ins + P.e_ins), e_del = s2_splat(P.e_del), e_ins = s2_splat(P.e_ins);
+		const msw_s2 zero = s2_splat(0);
+		uint32_t co_diag = 0, co_fseg = 0, co_ffull = 0, co_key = 0;
+		auto base_at = [&](const MswReq &rq, int tnx, int i) -> int {
+			const int ii = i < tnx ? i : tnx - 1;
+			return ii >= 0 ? msw_base(pac, P.l_pac, rq.rb + ii) : 0;
+		};
+		int ta_next = (run && j == 0) ? base_at(qa, tnA, 0) : 0, tb_next = (run && j == 0) ? base_at(qb, tnB, 0) : 0;
+		uint16_t *rowsA = rows + rA, *rowsB = rows + (hasB ? rB : rA);
+		const msw_u2 posc0 = {(unsigned short)(248 - j * S), (unsigned short)(248 - j * S)};   // 255 - 7 - (first position of the lane)
+		for (int t = 0; __any(run); ++t) {
+			const int i = t - j;
+			const bool act = run && i >= 0 && i < tn;
+			const int ta = ta_next, tb = tb_next;
+			if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base_at(qa, tnA, i + 1); tb_next = base_at(qb, tnB, i + 1); }
+			const uint32_t *srow = stab + ((ta << 2 | tb) << 3);
+			const uint32_t ci_diag = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_diag), ci_fseg = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_fseg);
+			const uint32_t ci_ffull = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_ffull);
+			const uint32_t ci_key = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_key);
+			if (act) {   // (the skew steps in which a lane has no row: one branch, not a select per cell)
+				msw_s2 diag = s2_of(j ? ci_diag : 0u), fseg = s2_of(j ? ci_fseg : 0u), ffull = s2_of(j ? ci_ffull : 0u);
+				msw_u2 key = __builtin_bit_cast(msw_u2, j ? ci_key : 0u);   // per alignment: h * 256 + (255 - position), as in `forward`
+				msw_u2 c256 = {256, 256};
+				asm volatile("" : "+v"(c256));
+				// the score lookups of a block depend on the codes and the row's two bases only: all of a block's in flight ahead of its
+				// arithmetic, the next block's behind this one's
+				auto lookups = [&](int c, uint32_t *sv) {
+#pragma unroll
+					for (int u = 0; u < 8 && c * 8 + u < S; ++u)
+						sv[u] = *(const uint32_t *)((const char *)srow + __builtin_amdgcn_ubfe(cdreg[(c * 8 + u) >> 2], 8 * (u & 3), 8));
+					__builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of the arithmetic they were issued for)
+				};
+				auto step = [&](int kk, int u, uint32_t sq, msw_u2 &mblk) {
+					msw_s2 hd, e;
+					if constexpr (TWO) { hd = s2_of(st0[kk]); e = s2_of(st1[kk]); }
+					else {
+						hd = s2_of(__builtin_amdgcn_perm(0u, st0[kk], 0x0c020c00u));   // H_A | H_B << 16   (row i - 1)
+						e = s2_of(__builtin_amdgcn_perm(0u, st0[kk], 0x0c030c01u));    // E_A | E_B << 16
+					}
+					const msw_s2 h = s2_max(s2_max(diag + s2_of(sq), e), fseg);        // Hpre(i, k) of both
+					const msw_u2 rel = {(unsigned short)(7 - u), (unsigned short)(7 - u)};
+					mblk = __builtin_elementwise_max(mblk, __builtin_bit_cast(msw_u2, h) * c256 + rel);
+					const msw_s2 hfin = s2_max(h, ffull);
+					e = s2_max(s2_sub0(e, e_del), s2_sub0(h, oe_del));
+					const msw_s2 t2 = s2_sub0(h, oe_ins);
+					if ((kk + 1) % SL == 0) fseg = zero;   // the last position of a segment: F restarts
+					else fseg = s2_max(s2_sub0(fseg, e_ins), t2);
+					ffull = s2_max(s2_sub0(ffull, e_ins), t2);
+					diag = hd;
+					if constexpr (TWO) { st0[kk] = u_of(hfin); st1[kk] = u_of(e); }
+					else st0[kk] = __builtin_amdgcn_perm(u_of(e), u_of(hfin), 0x06020400u);   // bytes: H_A, E_A, H_B, E_B
+				};
+				constexpr int NB = (S + 7) / 8;   // blocks of eight cells, the last one may be half a block
+				// (the code words are opaque once per row, in place: else the S byte selects are hoisted into S registers held over the rows)
+#pragma unroll
+				for (int c = 0; c < RC; ++c) asm volatile("" : "+v"(cdreg[c]));
+				uint32_t sv[2][8];
+				lookups(0, sv[0]);
+#pragma unroll
+				for (int c = 0; c < NB; ++c) {
+					if (c + 1 < NB) lookups(c + 1, sv[(c + 1) & 1]);
+					msw_u2 mblk = {0, 0};
+#pragma unroll
+					for (int u = 0; u < 8 && c * 8 + u < S; ++u) step(c * 8 + u, u, sv[c & 1][u], mblk);
+					const msw_u2 blk0 = {(unsigned short)(8 * c), (unsigned short)(8 * c)};
+					key = __builtin_elementwise_max(key, mblk + (posc0 - blk0));
+				}
+				co_diag = u_of(diag); co_fseg = u_of(fseg); co_ffull = u_of(ffull); co_key = __builtin_bit_cast(uint32_t, key);
+			}
+			const uint32_t keyAB = co_key;
+			int stop = 0;
+			if (act && j == 3) {
+				if (i < tnA && !satA) {
+					const int imax = (int)(keyAB >> 8 & 0xff);
+					rowsA[(size_t)i * n_req] = (uint16_t)imax;
+					if (imax > gmaxA) { gmaxA = imax; teA = i; qeA = 255 - (int)(keyAB & 0xff); if (gmaxA >= sat_limit) satA = 1; }
+				}
+				if (i < tnB && !satB) {
+					const int imax = (int)(keyAB >> 24);
+					rowsB[(size_t)i * n_req] = (uint16_t)imax;
+					if (imax > gmaxB) { gmaxB = imax; teB = i; qeB = 255 - (int)(keyAB >> 16 & 0xff); if (gmaxB >= sat_limit) satB = 1; }
+				}
+				if ((i + 1 >= tnA || satA) && (i + 1 >= tnB || satB)) stop = 1;
+			}
+			stop = msw_dpp<MSW_QP(3, 3, 3, 3)>(stop);
+			if (stop) run = false;
+		}
+	};
+	if constexpr (REGS) forward_regs();
+	else if (slen_u > 0) forward(std::true_type{});
+	else forward(std::false_type{});
 	MswPassOut fA, fB;
 	fA.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxA); fA.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teA); fA.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeA);
 	fB.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxB); fB.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teB); fB.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeB);
@@ -598,6 +720,17 @@ static void msw_tail_census(void *stream, const MswParams &P, int n_req, int n_p
 	        minsc, (n_pairs + 15) / 16, waves_a, waves_b);
 }
 
+// The segment lengths msw2_kernel is instantiated for with its state in registers (reads of 65-80, 97-112, 113-128, 145-160, 193-208 and
+// 241-249 bp); the work items of every other length run in the general form.
+#define MSW_REGS_CLASSES 6
+static const int msw_regs_slen[MSW_REGS_CLASSES] = {5, 7, 8, 10, 13, 16};
+static int msw_regs_class(int slen)
+{
+	for (int c = 0; c < MSW_REGS_CLASSES; ++c)
+		if (msw_regs_slen[c] == slen) return c;
+	return MSW_REGS_CLASSES;
+}
+
 // h_req: the requests as the host holds them (for the pairing), or null: every request on its own.  h_list / d_list: room for
 // 2 n_req ints each (host side page-locked in the pipeline): the pairs first (2 ints each), then the single requests.
 void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req, const uint8_t *d_seq, const int64_t *d_off, const int *d_len,
@@ -613,22 +746,48 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 		s_attr = lds;
 	}
 	static const bool pairing = !(getenv("MPIBWA_MSW_PAIRS") && atoi(getenv("MPIBWA_MSW_PAIRS")) == 0);
+	static const bool regs_form = !(getenv("MPIBWA_MSW_REGS") && atoi(getenv("MPIBWA_MSW_REGS")) == 0);   // 0: every work item in the general form (the A/B)
 	int n_pairs = 0, n_single = n_req;
 	const int *d_single = nullptr;
 	if (pairing && h_req && h_len && h_list && d_list && d_tail && lds2 <= 160 * 1024 && lds_t <= 160 * 1024) {
 		// two requests next to each other for the same mate in the same orientation (mem_sam_pe lists an end's anchors one after the
 		// other: the windows of a repeat read's anchors are such runs), both in the byte flavour
 		// work items of msw2_kernel from the front of the list (two ints each; a byte-flavour request without a partner: (k, -1)), the
-		// requests of the word flavour (reads of 250 bp and more) for msw_kernel from its back
-		int *pl = h_list, np = 0, ns = 0, n_alone = 0;
+		// requests of the word flavour (reads of 250 bp and more) for msw_kernel from its back.
+		// The work items are laid out launch by launch: those of a segment length with a register instantiation (msw_regs_class), one
+		// launch per length present, the most frequent first; then those of the general form.  Two walks over the requests — count,
+		// then place — so that nothing but the list itself is needed.
+		int np = 0, ns = 0, n_alone = 0;
+		int cls_n[MSW_REGS_CLASSES + 1], cls_at[MSW_REGS_CLASSES + 1], order[MSW_REGS_CLASSES + 1];   // (class MSW_REGS_CLASSES: the general form)
 		int *sl_end = h_list + 2 * (size_t)n_req;
+		auto item = [&](int k, int &cls) -> int {   // the work item that starts at request k: 0 = word flavour, 1 = alone, 2 = a pair
+			const int qlen = h_len[h_req[k].read];
+			if (!(qlen * P.a < 250)) return 0;
+			cls = regs_form ? msw_regs_class((qlen + 15) / 16) : MSW_REGS_CLASSES;
+			return k + 1 < n_req && h_req[k].read == h_req[k + 1].read && h_req[k].is_rev == h_req[k + 1].is_rev && h_req[k].re > h_req[k].rb &&
+			       h_req[k + 1].re > h_req[k + 1].rb ? 2 : 1;
+		};
+		for (int c = 0; c <= MSW_REGS_CLASSES; ++c) cls_n[c] = 0;
 		for (int k = 0; k < n_req;) {
-			const bool byte_k = h_len[h_req[k].read] * P.a < 250;
-			if (!byte_k) { *--sl_end = k; ++ns; ++k; continue; }
-			if (k + 1 < n_req && h_req[k].read == h_req[k + 1].read && h_req[k].is_rev == h_req[k + 1].is_rev && h_req[k].re > h_req[k].rb &&
-			    h_req[k + 1].re > h_req[k + 1].rb) {
-				pl[2 * np] = k; pl[2 * np + 1] = k + 1; ++np; k += 2;
-			} else { pl[2 * np] = k; pl[2 * np + 1] = -1; ++np; ++n_alone; ++k; }
+			int cls = 0;
+			const int w = item(k, cls);
+			if (w) ++cls_n[cls];
+			k += w ? w : 1;
+		}
+		for (int c = 0; c < MSW_REGS_CLASSES; ++c) order[c] = c;
+		for (int a = 1; a < MSW_REGS_CLASSES; ++a)   // by falling count, ties in the order of the classes
+			for (int b = a; b > 0 && cls_n[order[b]] > cls_n[order[b - 1]]; --b) std::swap(order[b], order[b - 1]);
+		order[MSW_REGS_CLASSES] = MSW_REGS_CLASSES;
+		for (int o = 0, at = 0; o <= MSW_REGS_CLASSES; ++o) { cls_at[order[o]] = at; at += cls_n[order[o]]; }
+		int cur[MSW_REGS_CLASSES + 1];
+		for (int c = 0; c <= MSW_REGS_CLASSES; ++c) cur[c] = cls_at[c];
+		for (int k = 0; k < n_req;) {
+			int cls = 0;
+			const int w = item(k, cls);
+			if (!w) { *--sl_end = k; ++ns; ++k; continue; }
+			int *pl = h_list + 2 * (size_t)cur[cls]++;
+			pl[0] = k; pl[1] = w == 2 ? k + 1 : -1;
+			++np; n_alone += w == 1; k += w;
 		}
 		n_pairs = np; n_single = ns;
 		static const bool say = getenv("MPIBWA_CPUSEC") != nullptr;
@@ -637,7 +796,7 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 		d_single = d_list + (sl_end - h_list);
 		if (n_pairs) {
 			if (lds2 > s_attr2) {
-				HIP_OK(hipFuncSetAttribute((const void *)msw2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+				HIP_OK(hipFuncSetAttribute((const void *)msw2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
 				s_attr2 = lds2;
 			}
 			if (lds_t > s_attr_t) {
@@ -649,8 +808,25 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 			const int s_max = (max_len + 15) / 16 * 16 / 4;
 			int *d_tail_n = d_tail, *d_tail_list = d_tail + 16;
 			HIP_OK(hipMemsetAsync(d_tail_n, 0, MSW_TAIL_BUCKETS * sizeof(int), (hipStream_t)stream));
-			hipLaunchKernelGGL(msw2_kernel, dim3((n_pairs + 15) / 16), dim3(64), lds2, (hipStream_t)stream, P, n_pairs, n_req, (const int *)d_list, d_req, d_seq, d_off,
-			                   d_len, d_pac, d_res, d_rows, s_max, d_tail_n, d_tail_list, n_req);
+			for (int o = 0; o <= MSW_REGS_CLASSES; ++o) {
+				const int c = order[o], n = cls_n[c];
+				if (!n) continue;
+				const int *d_items = d_list + 2 * (size_t)cls_at[c];
+				const dim3 grid((n + 15) / 16);
+#define MSW2_LAUNCH(SLEN) \
+	hipLaunchKernelGGL(msw2_kernel<SLEN>, grid, dim3(64), (SLEN) ? 128 * sizeof(uint32_t) : lds2, (hipStream_t)stream, P, n, n_req, d_items, d_req, d_seq, d_off, d_len, \
+	                   d_pac, d_res, d_rows, s_max, d_tail_n, d_tail_list, n_req)
+				switch (c < MSW_REGS_CLASSES ? msw_regs_slen[c] : 0) {
+				case 5: MSW2_LAUNCH(5); break;
+				case 7: MSW2_LAUNCH(7); break;
+				case 8: MSW2_LAUNCH(8); break;
+				case 10: MSW2_LAUNCH(10); break;
+				case 13: MSW2_LAUNCH(13); break;
+				case 16: MSW2_LAUNCH(16); break;
+				default: MSW2_LAUNCH(0);
+				}
+#undef MSW2_LAUNCH
+			}
 			const int n_byte = 2 * n_pairs - n_alone;
 			hipLaunchKernelGGL(msw_tail_kernel, dim3((n_byte + 15) / 16), dim3(64), lds_t, (hipStream_t)stream, P, n_req, (const int *)d_tail_n,
 			                   (const int *)d_tail_list, n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, (const uint16_t *)d_rows);
