@@ -397,6 +397,23 @@ int mi355x_se_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_process
 int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
                          const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req);
 
+/* mi355x_se_wave_batch with the kernel's side arrays for reads whose record has several lines (mem_reg2sam, src/bwamem.c:1015-1032,
+ * without MEM_F_ALL and without ALT hits: every primary region of at least T, in list order, is a line).  status[t] = 17: decided with
+ * n_lines[t] = 2 .. mi355x_se_lines_cap() lines; desc[t] / req[t] / xa_cnt[t] are not written for such a read.  Line j sits in slot
+ * x = t * mi355x_se_lines_cap() + j of line_desc (48-byte descriptors), line_req (40-byte requests) and line_xa_cnt: the descriptor's
+ * flag is 0 for line 0, 0x800 behind it (0x100 under MEM_F_NO_MULTI, as mem_aln2sam prints 0x10000; the line is a supplementary one
+ * all the same), with the line's XA count in bits 16-19; mapq is mem_approx_mapq_se of the line's own region, lowered to line 0's
+ * behind it unless MEM_F_KEEP_SUPP_MAPQ (:1029); sub is the region's; every line's XA entries are mem_gen_alt's for its own region,
+ * entry i's request at line_xa_req[x * mi355x_pair_wave_xa_cap() + i].  desc.req is the line's request counted from the read's first when
+ * the read's requests are laid out as [line 0, its XA entries', line 1, its XA entries', ...], which is how mi355x_sam_se_lines_batch
+ * reads them.  More than mi355x_se_lines_cap() lines: 10 as before; line_xa_req == NULL or max_XA_hits beyond the cap: a read with 1 ..
+ * max_XA_hits entries on any line gets 11 (slots of line_xa_req may have been written for such a read; no count names them).
+ * n_lines == NULL: exactly mi355x_se_wave_batch.  Returns 0. */
+int mi355x_se_lines_cap(void);
+int mi355x_se_wave_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
+                               const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req,
+                               uint8_t *n_lines, void *line_desc, void *line_req, uint8_t *line_xa_cnt, void *line_xa_req);
+
 /* The redundancy pass of mem_sort_dedup_patch (src/bwamem.c:437-489) on the device, on raw region lists as mem_chain2aln leaves them:
  * 64-byte records back to back (the layout of mi355x_pair_wave_batch), read r owns regs[reg_off[r] .. reg_off[r+1]).  status[r] = 1: taken
  * — m[r] regions survive and keep[reg_off[r] + k], k < m[r], is the place in the read's own list of the k-th region of the reference's
@@ -416,6 +433,23 @@ int mi355x_sam_se_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t
                         const uint8_t *quals, const char *names, const int *name_off, const void *desc, const void *reqs, const int *req_base,
                         size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
                         unsigned long long *cursor, void *hdr_out);
+
+/* The text of single-end reads with several lines: aln_kernel, then sam_lines_kernel (a read per wavefront) on the descriptors of
+ * mi355x_se_wave_lines_batch.  n_lines[i] = 2 .. mi355x_se_lines_cap() (0: not a read of the device's, out_len[i] = -2); desc holds
+ * mi355x_se_lines_cap() descriptors per read, line j of read i at [i * cap + j]; read i owns reqs[req_base[i] .. req_base[i+1]), laid
+ * out as [line 0, its XA entries', line 1, ...] with reqs.read = i.  Every line is written as mem_aln2sam (src/bwamem.c:825-946) writes
+ * it for an entry of a list of n_lines: lines behind the first with H for the clips and SEQ / QUAL cut to the aligned part unless
+ * MEM_F_SOFTCLIP, every line with SA:Z: naming the others (CIGAR with S, MAPQ as in the descriptors, NM), then XA:Z:.  out_len[i] = the
+ * bytes of all the read's lines, which lie back to back at out_off[i]; -1: the host's read, whole (aln_kernel declined one of its
+ * requests; a line's short fields beyond mi355x_sam_lines_row() bytes, what the other lines' SA tags say of a line behind its contig name
+ * beyond mi355x_sam_lines_sa_stage() bytes, an XA entry beyond 64 bytes; the arena is full).  Arena, guard, cursor, grid_blocks and
+ * hdr_out as for mi355x_sam_se_batch. */
+int mi355x_sam_lines_row(void);
+int mi355x_sam_lines_sa_stage(void);
+int mi355x_sam_se_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
+                              const uint8_t *quals, const char *names, const int *name_off, const uint8_t *n_lines, const void *desc,
+                              const void *reqs, const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off,
+                              uint8_t *arena_out, unsigned long long *cursor, void *hdr_out);
 
 /* Seed enumeration between SMEM and SA lookup (src/bwamem.c:161, 265-283): seed_prep_kernel (sort of a read's intervals by info,
  * l_rep, number of seeds), the prefix sum over the counts, seed_enum_kernel (BWT row and (qbeg, len) of every seed, stepping through
@@ -474,6 +508,8 @@ typedef struct {
 	uint64_t n_se_wave_dev;                      /* the part of n_se_dev decided by se_wave_kernel (se_wave_kernel.hip): reads se_simple_kernel left for more than eight regions or for its XA test, whose record is plain */
 	uint64_t n_se_xa_dev;                        /* single-end reads se_wave_kernel decided with an XA tag on the record; counted neither in n_se_dev nor, their records, in n_sam_dev */
 	uint64_t n_se_xa_sam_dev;                    /* ... and how many of those records sam_kernel wrote (the rest came back and were aligned and formatted by the host) */
+	uint64_t n_se_supp_dev;                      /* single-end reads se_wave_kernel decided with more than one line (a primary and supplementary lines with SA tags); counted in none of n_se_dev, n_se_wave_dev, n_se_xa_dev, nor, their records, in n_sam_dev */
+	uint64_t n_se_supp_sam_dev;                  /* ... and how many of those reads' text sam_lines_kernel wrote (the rest came back and were aligned and formatted by the host) */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

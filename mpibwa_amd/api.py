@@ -21,6 +21,7 @@ EXPORTS = [
     "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
     "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg", "mi355x_se_wave_batch",
+    "mi355x_se_lines_cap", "mi355x_se_wave_lines_batch", "mi355x_sam_se_lines_batch", "mi355x_sam_lines_row", "mi355x_sam_lines_sa_stage",
 ]
 
 
@@ -127,6 +128,11 @@ def load_library(build_if_missing=True):
     sig("mi355x_sam_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("mi355x_se_wave_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5)
+    sig("mi355x_se_lines_cap", C.c_int, [])
+    sig("mi355x_se_wave_lines_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10)
+    sig("mi355x_sam_lines_row", C.c_int, [])
+    sig("mi355x_sam_lines_sa_stage", C.c_int, [])
+    sig("mi355x_sam_se_lines_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_dedup_maxreg", C.c_int, [])
     sig("mi355x_dedup_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [P(C.c_double)])
     sig("mi355x_seed_batch", C.c_int64, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64])
@@ -487,6 +493,44 @@ class Engine:
         assert rc == 0
         return status[:n], desc[:n], req[:n], [xa_req[t, :xa_cnt[t]].copy() for t in range(n)]
 
+    SE_DECIDED_LINES = 17
+
+    def singles_wave_lines(self, opt, read_no, regs, max_len=150, n_processed=0, xa=True, lines=True):
+        """se_wave_kernel with its side arrays for reads of several lines (mi355x_se_wave_lines_batch); arguments as singles_wave.
+        -> status, desc, req, xa_req as singles_wave returns them, and `lines`: per work item a list — empty unless status = 17
+        (SE_DECIDED_LINES) — of (desc, req, xa_req) per line in list order: a DESC_DT record, an AREQ_DT record and an AREQ_DT array.
+        For sam_records_se_lines the read's requests are [req, *xa_req] of line 0, then of line 1, ...  xa=False: both listings off;
+        lines=False: the side arrays are not handed over and the call is singles_wave's."""
+        n = len(regs)
+        read_no = np.ascontiguousarray(read_no, dtype=np.int32)
+        assert len(read_no) == n
+        reg_off = np.zeros(n + 1, dtype=np.int32)
+        reg_off[1:] = np.cumsum([len(r) for r in regs])
+        allregs = np.zeros(max(1, int(reg_off[-1])), dtype=self.REG_DT)
+        for r, a in enumerate(regs):
+            if len(a):
+                allregs[reg_off[r]:reg_off[r + 1]] = np.asarray(a, dtype=self.REG_DT)
+        m = max(n, 1)
+        cap, lcap = self.lib.mi355x_pair_wave_xa_cap(), self.lib.mi355x_se_lines_cap()
+        status = np.zeros(m, dtype=np.uint8)
+        desc = np.zeros(m, dtype=self.DESC_DT)
+        req = np.zeros(m, dtype=self.AREQ_DT)
+        xa_req = np.zeros((m, cap), dtype=self.AREQ_DT)
+        xa_cnt = np.zeros(m, dtype=np.uint8)
+        n_lines = np.zeros(m, dtype=np.uint8)
+        l_desc = np.zeros((m, lcap), dtype=self.DESC_DT)
+        l_req = np.zeros((m, lcap), dtype=self.AREQ_DT)
+        l_xc = np.zeros((m, lcap), dtype=np.uint8)
+        l_xr = np.zeros((m, lcap, cap), dtype=self.AREQ_DT)
+        ptr = lambda a, on: a.ctypes.data if on else None
+        rc = self.lib.mi355x_se_wave_lines_batch(opt, C.cast(self.bns, C.c_void_p), n_processed, n, read_no.ctypes.data, allregs.ctypes.data,
+                                                 reg_off.ctypes.data, max_len, status.ctypes.data, desc.ctypes.data, req.ctypes.data,
+                                                 ptr(xa_cnt, xa), ptr(xa_req, xa), ptr(n_lines, lines), ptr(l_desc, lines), ptr(l_req, lines),
+                                                 ptr(l_xc, lines), ptr(l_xr, lines and xa))
+        assert rc == 0
+        out = [[(l_desc[t, j].copy(), l_req[t, j].copy(), l_xr[t, j, :l_xc[t, j]].copy()) for j in range(int(n_lines[t]))] for t in range(n)]
+        return status[:n], desc[:n], req[:n], [xa_req[t, :xa_cnt[t]].copy() for t in range(n)], out
+
     DD_TAKEN, DD_HOST_MAXREG, DD_HOST_PATCH = 1, 3, 4
     DD_FILL = -0x5a5a5a5b
 
@@ -520,7 +564,17 @@ class Engine:
         """sam_records for single-end descriptors (mi355x_sam_se_batch): n_reads reads, desc (n_reads,), req_base (n_reads + 1,)."""
         return self.sam_records(opt, reads, quals, names, desc, reqs, req_base, arena_bytes, grid_blocks, ends=1)
 
-    def sam_records(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0, ends=2):
+    def sam_records_se_lines(self, opt, reads, quals, names, n_lines, desc, reqs, req_base, arena_bytes=0, grid_blocks=0):
+        """aln_kernel + sam_lines_kernel (mi355x_sam_se_lines_batch): n_reads single-end reads of n_lines[i] lines each (2 ..
+        mi355x_se_lines_cap(); 0: not the device's), desc (n_reads, cap) DESC_DT with line j of read i at [i, j], reqs per read
+        [line 0, its XA entries', line 1, ...] with read = i, req_base (n_reads + 1,).  -> sam_records' dict; out_len[i] covers all lines."""
+        lcap = self.lib.mi355x_se_lines_cap()
+        desc = np.ascontiguousarray(desc, dtype=self.DESC_DT).reshape(len(reads), lcap)
+        n_lines = np.ascontiguousarray(n_lines, dtype=np.uint8)
+        assert len(n_lines) == len(reads)
+        return self.sam_records(opt, reads, quals, names, desc, reqs, req_base, arena_bytes, grid_blocks, ends=1, n_lines=n_lines)
+
+    def sam_records(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0, ends=2, n_lines=None):
         """aln_kernel + sam_emit_kernel (mi355x_sam_batch) on chosen descriptors.  reads: 2 n_pairs nt4 code arrays; quals: as many byte
         strings or None; names: one byte string per read; desc (2 n_pairs,) DESC_DT; reqs AREQ_DT; req_base (n_pairs + 1,).
         -> dict: out_len, out_off, arena (arena_bytes of it), guard (the SAM_GUARD bytes behind it), arena_bytes, cursor, hdr (HDR_DT)"""
@@ -548,8 +602,11 @@ class Engine:
         cursor = np.zeros(1, dtype=np.uint64)
         hdr = np.zeros(max(len(reqs), 1), dtype=self.HDR_DT)
         fn = self.lib.mi355x_sam_batch if ends == 2 else self.lib.mi355x_sam_se_batch
+        lines = ()
+        if n_lines is not None:
+            fn, lines = self.lib.mi355x_sam_se_lines_batch, (n_lines.ctypes.data,)
         rc = fn(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), n // ends, flat.ctypes.data, off.ctypes.data,
-                                       fq.ctypes.data if fq is not None else None, nm.ctypes.data, noff.ctypes.data, desc.ctypes.data,
+                                       fq.ctypes.data if fq is not None else None, nm.ctypes.data, noff.ctypes.data, *lines, desc.ctypes.data,
                                        reqs.ctypes.data if len(reqs) else None, req_base.ctypes.data, arena_bytes, int(grid_blocks), out_len.ctypes.data,
                                        out_off.ctypes.data, arena.ctypes.data, cursor.ctypes.data, hdr.ctypes.data)
         assert rc == 0

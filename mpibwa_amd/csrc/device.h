@@ -294,9 +294,15 @@ struct AlnSamJob {
 	const int *h_base = nullptr; int *d_base = nullptr;   // first request of every unit (n_reads / ends + 1 entries), uploaded here
 	uint8_t *d_arena = nullptr; size_t arena_bytes = 0; unsigned long long *d_used = nullptr, *d_ooff = nullptr; int *d_olen = nullptr;
 	int grid_blocks = 0;
+	// the reads with several lines (sam_lines_kernel.hip; single-end jobs), whose chunk-wide descriptor says "not the device's": n_multi
+	// units, unit u = read d_mlist[u] of the chunk (null: r0 + u) with d_mlines[u] lines, their descriptors at d_mdesc[u * SE_LINES_CAP ..]
+	// and its requests from d_mbase[u] in d_req (d_mlines[u] = 0 or d_mbase[u] < 0: not a unit of this job).  All four live on the device
+	// already: in the pipeline they are se_wave_kernel's own work list and side arrays.
+	int n_multi = 0; const int *d_mlist = nullptr; const uint8_t *d_mlines = nullptr; const SamDesc *d_mdesc = nullptr; const int *d_mbase = nullptr;
 };
 // on `stream`: zero the counters, [ev_a] aln_kernel [ev_b] (when there are requests), then descriptors and request bases up, zero the
-// arena cursor, sam_emit_kernel.  ev_a / ev_b: hipEvent_t around the CIGAR kernel, or null
+// arena cursor, sam_emit_kernel, and sam_lines_kernel behind it on the same arena when the job lists reads with several lines.
+// ev_a / ev_b: hipEvent_t around the CIGAR kernel, or null
 void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const ChunkDev &D, const SamParams &sp, const AlnSamJob &J,
                    void *ev_a = nullptr, void *ev_b = nullptr);
 // d_req_base[pair] = first CIGAR request of the pair in d_hdr; out_len[r] = bytes of the record at arena + out_off[r],
@@ -314,6 +320,19 @@ void launch_sam_emit_se(void *stream, const SamParams &P, int n_reads, const Sam
                         const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off, const char *d_ann_names, const int *d_ann_name_off,
                         uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used, unsigned long long *d_out_off, int *d_out_len,
                         int grid_blocks = 0);
+// ---- SAM text of single-end reads with several lines (sam_lines_kernel.hip), a read per wavefront ----
+// Unit u: read rd = d_list ? d_list[u] - r0 : u of d_off / d_len / d_name_off / d_out_off / d_out_len, d_n_lines[u] lines (2 ..
+// SE_LINES_CAP) described by d_ldesc[u * SE_LINES_CAP ..] as se_wave_kernel leaves them (device.h: SeLines), its requests from
+// d_req_base[u] in d_req / d_hdr; d_n_lines[u] = 0 or d_req_base[u] < 0: not a unit of the job, nothing of it is touched.  out_len[rd] = bytes of all the read's lines, back to back at arena + out_off[rd], or -1: the host's
+// read (a declined CIGAR, short fields of a line beyond sam_lines_row() bytes, an SA entry beyond sam_lines_sa_stage() bytes, an XA
+// entry beyond XA_STAGE, a full arena).  The arena cursor is the one sam_emit_kernel advanced: not zeroed here.
+void launch_sam_lines(void *stream, const SamParams &P, bool softclip, int n_units, const int *d_list, int r0, const uint8_t *d_n_lines, const SamDesc *d_ldesc,
+                      const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr, const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off,
+                      const int *d_len, const uint8_t *d_qual, const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off,
+                      const char *d_ann_names, const int *d_ann_name_off, uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used,
+                      unsigned long long *d_out_off, int *d_out_len, int grid_blocks = 0);
+int sam_lines_row(void);
+int sam_lines_sa_stage(void);
 
 struct MswReq;
 struct MswRes;
@@ -420,8 +439,32 @@ static_assert(PW_MAXREG <= 64, "PairParams::lnq holds sub_n up to PW_MAXREG - 1"
 // se_simple_kernel writes them, else only wstatus[t].  d_xa_reqs and d_xa_cnt given (and max_XA_hits <= PW_XA_CAP): a read whose line
 // carries XA entries (src/bwamem_extra.c:98-118) is decided too: xa_cnt[t] entries, their requests (pad = the hit's contig) at
 // xa_reqs[t * PW_XA_CAP ..], desc[t].flag bits 16-19 = the count.  Without them such a read gets SE_HOST_XA.
+// Reads with supplementary lines (src/bwamem.c:1015-1032, without MEM_F_ALL and without ALT hits): with the side arrays of SeLines a read
+// whose record has 2 .. SE_LINES_CAP lines is decided with SE_DECIDED_LINES instead of SE_HOST_SUPP.  n_lines[t] lines in list order;
+// line j of work item t in slot x = t * SE_LINES_CAP + j: desc[x] (flag: 0 for line 0, supp_flag behind it, the XA count in bits 16-19;
+// mapq after the cap of :1029; req: the line's request relative to the read's first, requests laid out as [line 0, its XA entries,
+// line 1, its XA entries, ...]), reqs[x], xa_cnt[x] and the XA requests at xa_reqs[x * PW_XA_CAP ..].  desc[t] / reqs[t] / xa_cnt[t] of
+// the launch are not written for such a read.  xa_reqs = nullptr (or max_XA_hits > PW_XA_CAP): a read with 1 .. max_XA_hits XA entries
+// on any line gets SE_HOST_XA.  More than SE_LINES_CAP lines: SE_HOST_SUPP.  Without the arrays (desc = nullptr) nothing changes.
+#define SE_DECIDED_LINES 17
+#define SE_LINES_CAP 4
+extern "C" int mi355x_se_lines_cap(void);
+struct SeLines {
+	SamDesc *desc = nullptr;
+	AlnReq *reqs = nullptr;
+	uint8_t *n_lines = nullptr, *xa_cnt = nullptr;
+	AlnReq *xa_reqs = nullptr;
+	int supp_flag = 0x800;   // 0x100 under MEM_F_NO_MULTI: the 0x10000 of :1028 as mem_aln2sam prints it; the line is a supplementary one all the same
+	int keep_mapq = 0;       // MEM_F_KEEP_SUPP_MAPQ
+};
+inline void se_lines_options(const mem_opt_t *opt, SeLines &S)
+{
+	S.supp_flag = opt->flag & MEM_F_NO_MULTI ? 0x100 : 0x800;
+	S.keep_mapq = opt->flag & MEM_F_KEEP_SUPP_MAPQ ? 1 : 0;
+}
 void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const uint8_t *d_ann_alt,
-                    const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc, AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr);
+                    const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc, AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr,
+                    const SeLines *lines = nullptr);
 
 // ---- the units a wave kernel decided, into a CIGAR-and-SAM job of their own (wave_scatter_kernel, se_wave_kernel.hip) ----
 // ends = 2: pair_wave_kernel's work list, 1: se_wave_kernel's.  dst[t] = first request of work item t's unit in `reqs`, or < 0 (not in
@@ -430,6 +473,11 @@ void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_
 // the device's" first
 void launch_wave_job_scatter(void *stream, int ends, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
                              const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
+// its sibling for se_wave_kernel's reads of several lines: the requests of work item t with dst[t] >= 0 and n_lines[t] > 0 go to
+// reqs[dst[t] ..] as [line 0, its XA entries, line 1, ...] from the side arrays (device.h: SeLines); the line descriptors stay where
+// the kernel wrote them (sam_lines_kernel reads them there), and the chunk-wide descriptor of the read stays "not the device's"
+void launch_lines_job_scatter(void *stream, int n_work, const int *d_dst, const uint8_t *d_n_lines, const AlnReq *d_lreq, const uint8_t *d_lxcnt,
+                              const AlnReq *d_lxreq, AlnReq *d_reqs);
 
 // ---- the redundancy pass of mem_sort_dedup_patch on the raw region lists (dedup_kernel.hip) ----
 #define DD_MAXREG 512             // regions per read dedup_wave_kernel takes (its LDS footprint)

@@ -254,6 +254,10 @@ struct JobBufs {
 struct WaveBufs {
 	PinBuf h_work, h_lists, h_loff, h_mfirst, h_tags, h_toff, h_status, h_xcnt, h_dst;
 	DevBuf work, lists, loff, mfirst, tags, toff, status, req, desc, xreq, xcnt, dst;
+	// se_wave_kernel's reads of several lines (device.h: SeLines): line counts per item, and per (item, line) descriptors, requests, XA
+	// counts and XA requests; ldst: where such an item's requests go in the part's job (the part's slot, like dst)
+	PinBuf h_nlines, h_lxcnt, h_ldst;
+	DevBuf nlines, ldesc, lreq, lxcnt, lxreq, ldst;
 };
 // What belongs to the chunk as a whole: packed reads, the inputs of the SAM stage, the decisions made on the device, and per part of
 // the SAM stage the mate-rescue alignments and the two jobs
@@ -468,14 +472,22 @@ struct Call {
 	const uint8_t *se_wxcnt = nullptr;   // per work item: its XA entries
 	uint64_t n_se_wave = 0, n_se_xa = 0; // decided by it with a plain record / with an XA tag
 	std::atomic<unsigned long long> n_se_xa_sam{0};   // records with an XA tag taken from the device
+	// ... and the reads se_simple_kernel left for a second primary hit: 2 .. SE_LINES_CAP lines, written by sam_lines_kernel
+	bool dev_se_supp = false;            // MPIBWA_HOST_SUPP=1: off
+	const uint8_t *se_wnlines = nullptr, *se_wlxcnt = nullptr;   // per work item: its lines; per (item, line): the line's XA entries
+	uint64_t n_se_supp = 0;              // decided by it with several lines
+	std::atomic<unsigned long long> n_se_supp_sam{0};   // ... whose text was taken from the device
 	void se_wave_decide();               // candidates, the kernel over their work list, the merge of its decisions (synchronous)
 	// a wave kernel's work list, packed and queued: what the launch needs on the device, and where status bytes and XA counts come back
 	struct WaveList {
 		int *work; DevReg *lists; int *loff; uint8_t *status; AlnReq *req; SamDesc *desc; AlnReq *xreq; uint8_t *xcnt;
 		uint8_t *h_status, *h_xcnt;
+		SeLines lines;                   // (lines = true) the side arrays for reads of several lines
+		uint8_t *h_nlines, *h_lxcnt;
 	};
 	struct Upload { void *dst; const void *src; size_t bytes; };
-	WaveList wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more = {});
+	WaveList wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more = {},
+	                   bool lines = false);
 	// the units of the part a wave kernel decided with a request count of their own: a job of their own (asynchronous)
 	void own_job_records(Part &P, int ends, const WaveBufs &B, const std::vector<int> &items, const uint8_t *xcnt);
 	const AlnReq *d_pr_req = nullptr;
@@ -506,7 +518,7 @@ struct Call {
 	void replay(Part &P, int which);  // C: the records
 	enum Fetch { FETCH_ALWAYS, FETCH_IF_HANDED_BACK, FETCH_RECORDS };
 	void job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const AlnReq *d_req, size_t n_req, const uint32_t *base, bool with_sam,
-	                const SamDescH *h_desc, SamDesc *d_desc);
+	                const SamDescH *h_desc, SamDesc *d_desc, const WaveBufs *multi = nullptr, int n_multi = 0);
 	void job_fetch(Job &J, const Part &P, Fetch policy, bool wave_units = false);
 	void take_record(int read, const Job &J, int at);
 	void report_decisions();

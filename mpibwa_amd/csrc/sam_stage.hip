@@ -242,7 +242,8 @@ static void pack_list(const HRegV &v, DevReg *o)
 // A wave kernel's work list on stream wst: `ends` region lists per item — the host's own (after mem_sort_dedup_patch), packed with
 // offsets —, status bytes and (xa) XA counts cleared, room for the kernel's requests, descriptors and XA requests (PW_XA_CAP per
 // (item, end)).  more: what else the kernel reads per item, uploaded behind the lists and before the clears.
-Call::WaveList Call::wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more)
+// lines (se_wave_kernel): the side arrays for reads of several lines, SE_LINES_CAP slots per item, line counts cleared.
+Call::WaveList Call::wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more, bool lines)
 {
 	const int nw = (int)items.size(), nl = ends * nw;   // items, lists
 	size_t n_regs = 0;
@@ -276,6 +277,20 @@ Call::WaveList Call::wave_list(WaveBufs &B, hipStream_t wst, int ends, const std
 		L.xcnt = (uint8_t *)B.xcnt.ensure(roomy((size_t)nl + 64));
 		L.h_xcnt = (uint8_t *)B.h_xcnt.ensure(roomy((size_t)nl + 64));
 		HIP_OK(hipMemsetAsync(L.xcnt, 0, (size_t)nl, wst));
+	}
+	L.h_nlines = L.h_lxcnt = nullptr;
+	if (lines) {
+		const size_t ns = (size_t)nw * SE_LINES_CAP;   // line slots
+		L.lines.n_lines = (uint8_t *)B.nlines.ensure(roomy((size_t)nw + 64));
+		L.lines.desc = (SamDesc *)B.ldesc.ensure(roomy(ns * sizeof(SamDesc)));
+		L.lines.reqs = (AlnReq *)B.lreq.ensure(roomy(ns * sizeof(AlnReq)));
+		L.lines.xa_cnt = (uint8_t *)B.lxcnt.ensure(roomy(ns + 64));
+		L.lines.xa_reqs = xa ? (AlnReq *)B.lxreq.ensure(roomy(ns * PW_XA_CAP * sizeof(AlnReq))) : nullptr;
+		L.h_nlines = (uint8_t *)B.h_nlines.ensure(roomy((size_t)nw + 64));
+		L.h_lxcnt = (uint8_t *)B.h_lxcnt.ensure(roomy(ns + 64));
+		se_lines_options(opt, L.lines);
+		HIP_OK(hipMemsetAsync(L.lines.n_lines, 0, (size_t)nw, wst));
+		HIP_OK(hipMemsetAsync(L.lines.xa_cnt, 0, ns, wst));
 	}
 	return L;
 }
@@ -319,29 +334,44 @@ void Call::own_job_records(Part &P, int ends, const WaveBufs &B, const std::vect
 		const int i = items[t];
 		return ends == 2 ? P.wstatus[t] == PW_DECIDED_XA : i >= P.lo && i < P.hi && wave_dec[i];
 	};
+	// (se_wave_kernel's reads of several lines: a request per line and per XA entry of a line, from the counts that came back with the
+	// status bytes; they ride in the same job, and sam_lines_kernel writes them behind sam_emit_kernel)
+	auto n_lines_of = [&](int t) { return ends == 1 && dev_se_supp && se_wnlines ? (int)std::min<int>(se_wnlines[t], SE_LINES_CAP) : 0; };
 	P.xa_base.assign(nu + 1, 0);
-	int n_dec = 0;
+	int n_dec = 0, n_multi = 0;
 	for (int t = 0; t < nw; ++t) {
 		if (!in_job(t)) continue;
-		for (int e = 0; e < ends; ++e) P.xa_base[items[t] - P.lo + 1] += 1 + (xcnt ? std::min<int>(xcnt[ends * t + e], PW_XA_CAP) : 0);
+		const int nl = n_lines_of(t);
+		for (int j = 0; j < nl; ++j) P.xa_base[items[t] - P.lo + 1] += 1 + std::min<int>(se_wlxcnt[(size_t)t * SE_LINES_CAP + j], PW_XA_CAP);
+		for (int e = 0; e < ends && !nl; ++e) P.xa_base[items[t] - P.lo + 1] += 1 + (xcnt ? std::min<int>(xcnt[ends * t + e], PW_XA_CAP) : 0);
 		++n_dec;
+		n_multi += nl > 0;
 	}
 	if (n_dec == 0) return;
 	hipStream_t jst = C.d_streams[s];
 	for (int k = 0; k < nu; ++k) P.xa_base[k + 1] += P.xa_base[k];
 	int *dst = (int *)W.wave[s].h_dst.ensure(roomy((size_t)nw * 4 + 64));   // (the part's: se_wave_kernel's one list serves both parts)
-	for (int t = 0; t < nw; ++t) dst[t] = in_job(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
+	for (int t = 0; t < nw; ++t) dst[t] = in_job(t) && !n_lines_of(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
 	const size_t n_req = P.xa_base[nu];
 	int *d_dst = (int *)W.wave[s].dst.ensure(roomy((size_t)nw * 4));
+	int *d_ldst = nullptr;
+	if (n_multi) {
+		int *ldst = (int *)W.wave[s].h_ldst.ensure(roomy((size_t)nw * 4 + 64));
+		for (int t = 0; t < nw; ++t) ldst[t] = in_job(t) && n_lines_of(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
+		d_ldst = (int *)W.wave[s].ldst.ensure(roomy((size_t)nw * 4));
+		HIP_OK(hipMemcpyAsync(d_ldst, ldst, (size_t)nw * 4, hipMemcpyHostToDevice, C.d_streams[s]));
+	}
 	AlnReq *d_rq = (AlnReq *)W.xa_req[s].ensure(roomy(n_req * sizeof(AlnReq)));
 	SamDesc *d_ds = (SamDesc *)W.xa_desc.ensure((size_t)n * sizeof(SamDesc));
 	HIP_OK(hipMemcpyAsync(d_dst, dst, (size_t)nw * 4, hipMemcpyHostToDevice, jst));
 	launch_wave_job_scatter(jst, ends, nw, (const int *)B.work.p, d_dst, (const AlnReq *)B.req.p, (const SamDesc *)B.desc.p, xcnt ? (const AlnReq *)B.xreq.p : nullptr,
 	                        xcnt ? (const uint8_t *)B.xcnt.p : nullptr, d_rq, d_ds, ends * P.lo, ends * nu);
+	if (n_multi)
+		launch_lines_job_scatter(jst, nw, d_ldst, (const uint8_t *)B.nlines.p, (const AlnReq *)B.lreq.p, (const uint8_t *)B.lxcnt.p, (const AlnReq *)B.lxreq.p, d_rq);
 	HIP_OK(hipGetLastError());
 	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
 	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
-	job_launch(P.xa, W.xa_job[s], jst, P, d_rq, n_req, P.xa_base.data(), true, nullptr, d_ds);
+	job_launch(P.xa, W.xa_job[s], jst, P, d_rq, n_req, P.xa_base.data(), true, nullptr, d_ds, n_multi ? &B : nullptr, n_multi ? nw : 0);
 }
 
 // ---- single-end reads with long lists or an XA tag: se_wave_kernel (se_wave_kernel.hip) ----
@@ -355,27 +385,38 @@ void Call::se_wave_decide()
 	if (!dev_se_wave) return;
 	const double tp0 = now_ms();
 	dev_se_xa = wave_pp.max_XA_hits <= PW_XA_CAP && getenv("MPIBWA_HOST_XA") == nullptr;
+	// reads of several lines: on unless MPIBWA_HOST_SUPP is set to something other than 0
+	const char *hs = getenv("MPIBWA_HOST_SUPP");
+	dev_se_supp = !(hs && atoi(hs) != 0);
 	wave_dec.assign(n, 0);
 	se_work.clear();
 	for (int i = 0; i < n; ++i)
-		if ((ustat[i] == SE_HOST_MAXREG || ustat[i] == SE_HOST_XA) && !seqs[i].comment && se_wave_eligible(regs[i], PW_MAXREG)) se_work.push_back(i);
+		if ((ustat[i] == SE_HOST_MAXREG || ustat[i] == SE_HOST_XA || (dev_se_supp && ustat[i] == SE_HOST_SUPP)) && !seqs[i].comment &&
+		    se_wave_eligible(regs[i], PW_MAXREG))
+			se_work.push_back(i);
 	const int nw = (int)se_work.size();
 	if (nw == 0) return;
-	const WaveList L = wave_list(se_bufs(), st, 1, se_work, dev_se_xa);
-	launch_se_wave(st, wave_pp, nw, L.work, L.lists, L.loff, D.d_ann_alt, d_wave_tab + wave_n_tab, L.status, L.req, L.desc, L.xreq, L.xcnt);
+	const WaveList L = wave_list(se_bufs(), st, 1, se_work, dev_se_xa, {}, dev_se_supp);
+	launch_se_wave(st, wave_pp, nw, L.work, L.lists, L.loff, D.d_ann_alt, d_wave_tab + wave_n_tab, L.status, L.req, L.desc, L.xreq, L.xcnt,
+	               dev_se_supp ? &L.lines : nullptr);
 	HIP_OK(hipMemcpyAsync(L.h_status, L.status, (size_t)nw, hipMemcpyDeviceToHost, st));
 	if (dev_se_xa) HIP_OK(hipMemcpyAsync(L.h_xcnt, L.xcnt, (size_t)nw, hipMemcpyDeviceToHost, st));
+	if (dev_se_supp) {
+		HIP_OK(hipMemcpyAsync(L.h_nlines, L.lines.n_lines, (size_t)nw, hipMemcpyDeviceToHost, st));
+		HIP_OK(hipMemcpyAsync(L.h_lxcnt, L.lines.xa_cnt, (size_t)nw * SE_LINES_CAP, hipMemcpyDeviceToHost, st));
+	}
 	stream_wait(st);
 	HIP_OK(hipGetLastError());
-	se_wxcnt = L.h_xcnt;
+	se_wxcnt = L.h_xcnt; se_wnlines = L.h_nlines; se_wlxcnt = L.h_lxcnt;
 	for (int t = 0; t < nw; ++t) {   // its decisions: these reads are the device's from here on
 		const int i = se_work[t];
 		const uint8_t ws = L.h_status[t];
 		if (ws == SE_DECIDED) { ustat[i] = SE_DECIDED; wave_dec[i] = 1; ++n_se_wave; }
 		else if (ws == SE_DECIDED_XA && dev_se_xa) { ustat[i] = SE_DECIDED_XA; wave_dec[i] = 1; ++n_se_xa; }
+		else if (ws == SE_DECIDED_LINES && dev_se_supp) { ustat[i] = SE_DECIDED_LINES; wave_dec[i] = 1; ++n_se_supp; }
 		else if (ws) ustat[i] = ws;   // (why not: for the statistics line)
 	}
-	if (n_se_wave + n_se_xa) dev_units = true;   // (se_simple_kernel may have taken none)
+	if (n_se_wave + n_se_xa + n_se_supp) dev_units = true;   // (se_simple_kernel may have taken none)
 	pair_dev_ms += now_ms() - tp0;
 }
 
@@ -438,7 +479,7 @@ void Call::collect(Part &P, int round)
 		unsigned long long tsc_plan_blk = 0, tsc_emitc_blk = 0;
 		for (int i = lo; i < hi; ++i) {
 			const int k = i - P.lo;
-			if (dev_units && (ustat[i] == PR_DECIDED || ustat[i] == PW_DECIDED_XA)) continue;   // decided on the device
+			if (dev_units && (ustat[i] == PR_DECIDED || ustat[i] == PW_DECIDED_XA || (!pe && ustat[i] == SE_DECIDED_LINES))) continue;   // decided on the device
 			const bool has_msw = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
 			const bool waits = has_msw || (dev_wave && wave_cand[i]);            // ... or pair_wave_kernel's word on whose pair it is
 			if (waits != (round == 1)) continue;
@@ -480,7 +521,7 @@ void Call::collect(Part &P, int round)
 // the first request of every unit, or null: `ends` requests per unit.  with_sam: the records behind the CIGARs, from the descriptors
 // d_desc (of the chunk; h_desc given: the part's are uploaded first).
 void Call::job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const AlnReq *d_req, size_t n_req, const uint32_t *base, bool with_sam,
-                      const SamDescH *h_desc, SamDesc *d_desc)
+                      const SamDescH *h_desc, SamDesc *d_desc, const WaveBufs *multi, int n_multi)
 {
 	const int ends = pe ? 2 : 1;   // reads per unit
 	const int nu = P.hi - P.lo, nr = nu * ends;
@@ -505,6 +546,11 @@ void Call::job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const 
 		Q.d_used = (unsigned long long *)B.used.ensure(64);
 		Q.d_ooff = (unsigned long long *)B.ooff.ensure((size_t)nr * 8);
 		Q.d_olen = (int *)B.olen.ensure((size_t)nr * 4);
+		if (multi && n_multi > 0) {   // se_wave_kernel's reads of several lines: a unit per item of its work list, those of this job by ldst >= 0
+			const int s = P.slot;
+			Q.n_multi = n_multi; Q.d_mlist = (const int *)multi->work.p; Q.d_mlines = (const uint8_t *)multi->nlines.p;
+			Q.d_mdesc = (const SamDesc *)multi->ldesc.p; Q.d_mbase = (const int *)W.wave[s].ldst.p;
+		}
 	}
 	// (the results are fetched in job_fetch: a D2H copy into pageable memory would block the host here)
 	queue_aln_sam(jst, opt, bns->l_pac, D, sam_par, Q, J.ev.a, J.ev.b);
@@ -630,7 +676,7 @@ void Call::replay(Part &P, int which)
 	// (a single-end chunk without reads of the device's has no pass 0)
 	// per-block counters: a shared atomic bumped once per unit costs more than copying the unit's records
 	if (pe || which != 0 || dev_units) parallel_blocks(n_thr, P.hi - P.lo, pe ? 128 : 256, [&](int, int, int k_lo, int k_hi) {
-		unsigned long long n_dev = 0, n_se_xa_w = 0, tsc = 0;
+		unsigned long long n_dev = 0, n_se_xa_w = 0, n_se_supp_w = 0, tsc = 0;
 		for (int k = k_lo; k < k_hi; ++k) {
 			const int i = P.lo + k, r = ends * i;   // the unit, its first read
 			// pair_wave_kernel's pair with an XA tag, or se_wave_kernel's read (with or without one): the job of those
@@ -646,6 +692,7 @@ void Call::replay(Part &P, int which)
 				const unsigned long long tq0 = cpusec_on() ? __builtin_ia32_rdtsc() : 0;
 				for (int e = 0; e < ends; ++e) take_record(r + e, J, ends * k + e);
 				if (!pe && ustat[i] == SE_DECIDED_XA) ++n_se_xa_w;   // (counted apart: n_sam_dev stays the plain records of n_se_dev)
+				else if (!pe && ustat[i] == SE_DECIDED_LINES) ++n_se_supp_w;   // (its one string holds all the read's lines)
 				else n_dev += ends;
 				if (cpusec_on()) tsc += __builtin_ia32_rdtsc() - tq0;
 				continue;
@@ -668,7 +715,7 @@ void Call::replay(Part &P, int which)
 				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln && !xa_k ? &ctx : nullptr, i);
 			}
 		}
-		n_sam_dev += n_dev; n_se_xa_sam += n_se_xa_w; tsc_devcopy += tsc;
+		n_sam_dev += n_dev; n_se_xa_sam += n_se_xa_w; n_se_supp_sam += n_se_supp_w; tsc_devcopy += tsc;
 	});
 	emit_ms += now_ms() - ta;
 	cpu_emit += cpu_sec() - ca;
@@ -756,11 +803,13 @@ void Call::report_decisions()
 	if (pe) { STAT.n_pair_dev = c[PR_DECIDED] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs; }
 	else {
 		STAT.n_se_dev = c[SE_DECIDED]; STAT.n_se_wave_dev = n_se_wave; STAT.n_se_xa_dev = c[SE_DECIDED_XA]; STAT.n_se_xa_sam_dev = n_se_xa_sam.load();
-		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu; se_wave_kernel: handed %zu, decided plain %llu, decided with an XA tag %llu, XA records written %llu, list past %d %llu, tie %llu\n",
+		STAT.n_se_supp_dev = n_se_supp; STAT.n_se_supp_sam_dev = n_se_supp_sam.load();
+		if (cpusec_on()) fprintf(stderr, "[se_kernel] %d reads: decided %llu; host: comment %llu, > %d hits %llu, patch %llu, length %llu, ALT %llu, second primary hit %llu, XA %llu; se_wave_kernel: handed %zu, decided plain %llu, decided with an XA tag %llu, XA records written %llu, list past %d %llu, tie %llu, decided with several lines %llu, their text written %llu\n",
 		                      n_units, (unsigned long long)c[SE_DECIDED], (unsigned long long)c[SE_HOST_COMMENT], PR_MAXREG, (unsigned long long)c[SE_HOST_MAXREG],
 		                      (unsigned long long)c[SE_HOST_PATCH], (unsigned long long)c[SE_HOST_LENGTH], (unsigned long long)c[SE_HOST_ALT],
 		                      (unsigned long long)c[SE_HOST_SUPP], (unsigned long long)c[SE_HOST_XA], se_work.size(), (unsigned long long)n_se_wave,
-		                      (unsigned long long)c[SE_DECIDED_XA], n_se_xa_sam.load(), PW_MAXREG, (unsigned long long)c[SE_HOST_FULL], (unsigned long long)c[SE_HOST_TIE]);
+		                      (unsigned long long)c[SE_DECIDED_XA], n_se_xa_sam.load(), PW_MAXREG, (unsigned long long)c[SE_HOST_FULL], (unsigned long long)c[SE_HOST_TIE],
+		                      (unsigned long long)n_se_supp, n_se_supp_sam.load());
 	}
 	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them and %llu with an XA tag, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
 	                      n_units, (unsigned long long)c[PR_DECIDED], (unsigned long long)c[PR_HOST_NO_HIT], PR_MAXREG, (unsigned long long)c[PR_HOST_MAXREG],

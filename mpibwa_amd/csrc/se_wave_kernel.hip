@@ -14,9 +14,11 @@
 // redundancy pass nor a patch alignment here), at most PW_MAXREG regions.  It is pair_wave_kernel (pair_wave_kernel.hip) without the
 // rescue replay and without mem_pair: one region per lane, the list in LDS as one array per field, the rank-sort mem_mark_primary_se
 // and the XA listing of wave_common.cuh.  A read ends in one record — unmapped, plain, or with an XA tag of 1 .. PW_XA_CAP entries —
-// or is left to the host with a code that says why (device.h: SE_HOST_*).
+// or is left to the host with a code that says why (device.h: SE_HOST_*).  With the side arrays of device.h: SeLines a read whose record
+// has 2 .. SE_LINES_CAP lines (a primary line and supplementary lines, src/bwamem.c:1015-1032) is decided too, a lane per line: every
+// line's descriptor, MAPQ after the cap of :1029, request and XA requests; sam_lines_kernel.hip writes the text.
 //
-// 5 120 B of LDS per wave (the list 4 096 B, the sort keys 1 024 B), no scratch; the VGPR count is in DESIGN §4.5d.
+// 5 120 B of LDS per wave (the list 4 096 B, the sort keys 1 024 B), no scratch; the VGPR count is in DESIGN §4.5d / §4.5e.
 // Floating point: as in pair_kernel.hip — the reference's types and order, -ffp-contract=off, the transcendental sites tabulated.
 #include <hip/hip_runtime.h>
 #include "wave_common.cuh"
@@ -30,10 +32,14 @@ namespace mbw {
 // se_simple_kernel writes them; SE_DECIDED_XA (xa_reqs given): the same with xa_cnt[t] XA entries, their requests at
 // xa_reqs[t * PW_XA_CAP ..] in list order and the count in bits 16-19 of desc[t].flag; every other value: the host's read, nothing
 // but wstatus[t] is written.
+// LN.desc given: a read with 2 .. SE_LINES_CAP lines (src/bwamem.c:1015-1032) gets SE_DECIDED_LINES instead of SE_HOST_SUPP: LN.n_lines[t]
+// lines in list order, line j in slot x = t * SE_LINES_CAP + j of LN.desc / LN.reqs / LN.xa_cnt, its XA requests at
+// LN.xa_reqs[x * PW_XA_CAP ..]; desc[t], reqs[t] and xa_cnt[t] are left alone.  (LN.xa_reqs of a read that ends in another code may
+// have been written; no count says so.)
 __global__ void __launch_bounds__(64)
 se_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const DevReg *__restrict__ lists, const int *__restrict__ loff,
                const uint8_t *__restrict__ ann_alt, const double *__restrict__ ltab, uint8_t *__restrict__ wstatus, AlnReq *__restrict__ reqs,
-               SamDesc *__restrict__ desc, AlnReq *__restrict__ xa_reqs, uint8_t *__restrict__ xa_cnt)
+               SamDesc *__restrict__ desc, AlnReq *__restrict__ xa_reqs, uint8_t *__restrict__ xa_cnt, SeLines LN)
 {
 	__shared__ WList L;
 	__shared__ Pair64 H[PW_MAXREG];
@@ -68,7 +74,45 @@ se_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const Dev
 		}
 		return;
 	}
-	if (lines & (lines - 1)) SW_GIVE_UP(SE_HOST_SUPP);   // a supplementary line (SA tags, the MAPQ cap of :1029)
+	if (lines & (lines - 1)) {   // supplementary lines (:1027-1030): SA tags, the MAPQ cap
+		const int n_lines = __popcll(lines);
+		if (!LN.desc || n_lines > SE_LINES_CAP) SW_GIVE_UP(SE_HOST_SUPP);
+		// line j is lane j's: its hit and its XA entries (every line's string is mem_gen_alt's for its own hit); the loop is wave-uniform
+		int my_z = 0, my_xa = 0;
+		u64 rest = lines;
+		for (int j = 0; j < n_lines; ++j) {
+			const int z = __ffsll((long long)rest) - 1;
+			rest &= rest - 1;
+			const int c = pw_xa_list(P, L, n, z, k, LN.xa_reqs ? LN.xa_reqs + ((size_t)t * SE_LINES_CAP + j) * PW_XA_CAP : nullptr, lane);
+			if (c < 0) SW_GIVE_UP(SE_HOST_XA);
+			if (lane == j) { my_z = z; my_xa = c; }
+		}
+		const bool mine = lane < n_lines;
+		WReg R = wl_get(L, my_z);
+		const int l = R.qe - R.qb > R.re - R.rb ? R.qe - R.qb : (int)(R.re - R.rb);
+		int mq = mine ? mapq_se_of(P, R.score, R.sub, R.sub_n, 0, l, R.frac_rep, ltab) & 0xff : 0;
+		const int mq0 = __shfl(mq, 0);
+		int at = mine ? 1 + my_xa : 0;   // the line's request follows the requests of the lines before it and of their XA entries
+		for (int d = 1; d < SE_LINES_CAP; d <<= 1) {
+			const int up = __shfl_up(at, d);
+			if (lane >= d) at += up;
+		}
+		if (mine) {
+			if (lane && !LN.keep_mapq && mq > mq0) mq = mq0;   // (:1029; no ALT hit here)
+			const size_t x = (size_t)t * SE_LINES_CAP + lane;
+			AlnReq q;
+			q.rb = R.rb; q.re = R.re; q.read = k; q.qb = R.qb; q.qe = R.qe; q.truesc = R.truesc; q.pad = 0;
+			q.w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);
+			LN.reqs[x] = q;
+			SamDesc d;
+			d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = at - 1 - my_xa; d.rid = R.rid;
+			d.flag = (lane ? LN.supp_flag : 0) | my_xa << SAM_XA_SHIFT; d.mapq = mq; d.score = R.score; d.sub = R.sub;
+			LN.desc[x] = d;
+			LN.xa_cnt[x] = (uint8_t)my_xa;
+		}
+		if (lane == 0) { LN.n_lines[t] = (uint8_t)n_lines; wstatus[t] = SE_DECIDED_LINES; }
+		return;
+	}
 	const int z = __ffsll((long long)lines) - 1;
 	const int n_xa = pw_xa_list(P, L, n, z, k, xa_reqs ? xa_reqs + (size_t)t * PW_XA_CAP : nullptr, lane);
 	if (n_xa < 0) SW_GIVE_UP(SE_HOST_XA);
@@ -89,12 +133,15 @@ se_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const Dev
 }
 
 void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const uint8_t *d_ann_alt,
-                    const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc, AlnReq *d_xa_reqs, uint8_t *d_xa_cnt)
+                    const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc, AlnReq *d_xa_reqs, uint8_t *d_xa_cnt, const SeLines *lines)
 {
 	if (n_work <= 0) return;
 	if (!d_xa_cnt || !d_xa_reqs || P.max_XA_hits > PW_XA_CAP) d_xa_reqs = nullptr, d_xa_cnt = nullptr;   // (XA listing off)
+	SeLines LN;
+	if (lines && lines->desc && lines->reqs && lines->n_lines && lines->xa_cnt) LN = *lines;
+	if (P.max_XA_hits > PW_XA_CAP) LN.xa_reqs = nullptr;
 	hipLaunchKernelGGL(se_wave_kernel, dim3(n_work), dim3(64), 0, (hipStream_t)stream, P, n_work, d_work, d_lists, d_loff, d_ann_alt, d_ltab, d_wstatus,
-	                   d_reqs, d_desc, d_xa_reqs, d_xa_cnt);
+	                   d_reqs, d_desc, d_xa_reqs, d_xa_cnt, LN);
 }
 
 // ---- the units a wave kernel decided, into a CIGAR-and-SAM job of their own: pair_wave_kernel's pairs (ENDS = 2) and this file's reads ----
@@ -130,6 +177,27 @@ __global__ void wave_scatter_kernel(int n_work, const int *__restrict__ work, co
 		const int c = xa_cnt[x] < PW_XA_CAP ? xa_cnt[x] : PW_XA_CAP;
 		for (int j = 0; j < c; ++j) reqs[at++] = xa_reqs[(size_t)x * PW_XA_CAP + j];
 	}
+}
+__global__ void lines_scatter_kernel(int n_work, const int *__restrict__ dst, const uint8_t *__restrict__ n_lines, const AlnReq *__restrict__ lreq,
+                                     const uint8_t *__restrict__ lxcnt, const AlnReq *__restrict__ lxreq, AlnReq *__restrict__ reqs)
+{
+	const int t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= n_work || dst[t] < 0) return;
+	const int nl = n_lines[t] < SE_LINES_CAP ? n_lines[t] : SE_LINES_CAP;
+	int at = dst[t];
+	for (int j = 0; j < nl; ++j) {
+		const size_t x = (size_t)t * SE_LINES_CAP + j;
+		reqs[at++] = lreq[x];
+		const int c = lxcnt[x] < PW_XA_CAP ? lxcnt[x] : PW_XA_CAP;
+		for (int i = 0; i < c; ++i) reqs[at++] = lxreq[x * PW_XA_CAP + i];
+	}
+}
+void launch_lines_job_scatter(void *stream, int n_work, const int *d_dst, const uint8_t *d_n_lines, const AlnReq *d_lreq, const uint8_t *d_lxcnt,
+                              const AlnReq *d_lxreq, AlnReq *d_reqs)
+{
+	if (n_work > 0)
+		hipLaunchKernelGGL(lines_scatter_kernel, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_dst, d_n_lines, d_lreq, d_lxcnt, d_lxreq,
+		                   d_reqs);
 }
 void launch_wave_job_scatter(void *stream, int ends, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
                              const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n)

@@ -340,13 +340,18 @@ extern "C" int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *b
 // plain line; SE_DECIDED_XA (xa_req given): the line carries an XA tag of xa_cnt[t] entries, their requests at xa_req[t * PW_XA_CAP ..]
 // (pad = the entry's contig), the count also in desc[t].flag bits 16-19; else the code of the test that left the read to the host
 // (device.h: SE_HOST_*), desc[t].req = req[t].read = -1.  xa_req = NULL: without the XA listing.
-extern "C" int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
-                                    const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req)
+// n_lines given (mi355x_se_wave_lines_batch): the kernel runs with the side arrays of device.h: SeLines, all of them by (t, line) = slot
+// t * SE_LINES_CAP + line; line_xa_req = NULL: without the XA listing of the lines.
+extern "C" int mi355x_se_lines_cap(void) { return SE_LINES_CAP; }
+static int se_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
+                         const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req, uint8_t *n_lines,
+                         void *line_desc, void *line_req, uint8_t *line_xa_cnt, void *line_xa_req)
 {
 	require_any_device();
 	if (n_work <= 0) return 0;
-	if (max_len <= 0) die("mi355x_se_wave_batch: max_len must be positive");
-	if (xa_req && !xa_cnt) die("mi355x_se_wave_batch: no room for the XA counts");
+	if (max_len <= 0) die("%s: max_len must be positive", who);
+	if (xa_req && !xa_cnt) die("%s: no room for the XA counts", who);
+	if (n_lines && (!line_desc || !line_req || !line_xa_cnt)) die("%s: no room for the lines", who);
 	const size_t nw = (size_t)n_work;
 	memset(status, 0, nw);
 	memset(desc, 0xff, nw * sizeof(SamDesc));
@@ -354,15 +359,15 @@ extern "C" int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, i
 	if (xa_cnt) memset(xa_cnt, 0, nw);
 	if (xa_req) memset(xa_req, 0xff, nw * PW_XA_CAP * sizeof(AlnReq));
 	// nothing the kernel indexes with may point outside what is uploaded
-	if (reg_off[0] != 0) die("mi355x_se_wave_batch: reg_off[0] must be 0");
+	if (reg_off[0] != 0) die("%s: reg_off[0] must be 0", who);
 	for (size_t t = 0; t < nw; ++t) {
-		if (reg_off[t + 1] < reg_off[t]) die("mi355x_se_wave_batch: reg_off decreases at work item %zu", t);
-		if (read_no[t] < 0) die("mi355x_se_wave_batch: bad read number at work item %zu", t);
+		if (reg_off[t + 1] < reg_off[t]) die("%s: reg_off decreases at work item %zu", who, t);
+		if (read_no[t] < 0) die("%s: bad read number at work item %zu", who, t);
 	}
 	const size_t NR = (size_t)reg_off[nw];
 	const DevReg *hr = (const DevReg *)regs;
 	for (size_t j = 0; j < NR; ++j)
-		if (hr[j].rid < 0 || hr[j].rid >= bns->n_seqs) die("mi355x_se_wave_batch: bad contig in region %zu", j);
+		if (hr[j].rid < 0 || hr[j].rid >= bns->n_seqs) die("%s: bad contig in region %zu", who, j);
 	PairParams pp;
 	mem_pestat_t pes[4];
 	se_params(opt, bns->l_pac, n_processed, max_len, pp, pes);
@@ -387,7 +392,27 @@ extern "C" int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, i
 		d_xr.fill(0xff, nw * PW_XA_CAP * sizeof(AlnReq));
 		d_xc.fill(0, nw);
 	}
-	launch_se_wave(0, pp, n_work, d_work, d_lists, d_loff, d_aa, d_tab, d_ws, d_rq, d_ds, d_xr, d_xc);
+	const size_t nl = nw * SE_LINES_CAP;
+	DevArr<uint8_t> d_ln, d_lxc;
+	DevArr<SamDesc> d_lds;
+	DevArr<AlnReq> d_lrq, d_lxr;
+	SeLines LN;
+	if (n_lines) {
+		d_ln = DevArr<uint8_t>(nw + PAD); d_lxc = DevArr<uint8_t>(nl + PAD);
+		d_lds = DevArr<SamDesc>(nl * sizeof(SamDesc) + PAD);
+		d_lrq = DevArr<AlnReq>(nl * sizeof(AlnReq) + PAD);
+		d_ln.fill(0, nw); d_lxc.fill(0, nl);
+		d_lds.fill(0xff, nl * sizeof(SamDesc));
+		d_lrq.fill(0xff, nl * sizeof(AlnReq));
+		LN.desc = d_lds; LN.reqs = d_lrq; LN.n_lines = d_ln; LN.xa_cnt = d_lxc;
+		if (line_xa_req) {
+			d_lxr = DevArr<AlnReq>(nl * PW_XA_CAP * sizeof(AlnReq) + PAD);
+			d_lxr.fill(0xff, nl * PW_XA_CAP * sizeof(AlnReq));
+			LN.xa_reqs = d_lxr;
+		}
+		se_lines_options(opt, LN);
+	}
+	launch_se_wave(0, pp, n_work, d_work, d_lists, d_loff, d_aa, d_tab, d_ws, d_rq, d_ds, d_xr, d_xc, n_lines ? &LN : nullptr);
 	HIP_OK(hipDeviceSynchronize());
 	HIP_OK(hipGetLastError());
 	d_ws.download(status, nw);
@@ -397,7 +422,30 @@ extern "C" int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, i
 		d_xr.download(xa_req, nw * PW_XA_CAP * sizeof(AlnReq));
 		d_xc.download(xa_cnt, nw);
 	}
+	if (n_lines) {
+		d_ln.download(n_lines, nw);
+		d_lxc.download(line_xa_cnt, nl);
+		d_lds.download(line_desc, nl * sizeof(SamDesc));
+		d_lrq.download(line_req, nl * sizeof(AlnReq));
+		if (line_xa_req) d_lxr.download(line_xa_req, nl * PW_XA_CAP * sizeof(AlnReq));
+	}
 	return 0;
+}
+extern "C" int mi355x_se_wave_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
+                                    const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req)
+{
+	return se_wave_batch("mi355x_se_wave_batch", opt, bns, n_processed, n_work, read_no, regs, reg_off, max_len, status, desc, req, xa_cnt, xa_req, nullptr,
+	                     nullptr, nullptr, nullptr, nullptr);
+}
+// The same with the side arrays for reads of 2 .. mi355x_se_lines_cap() lines (status 17, SE_DECIDED_LINES): n_lines[t], and by
+// (t, line) line_desc, line_req, line_xa_cnt and line_xa_req (mi355x_pair_wave_xa_cap() requests each).  n_lines = NULL: exactly
+// mi355x_se_wave_batch.
+extern "C" int mi355x_se_wave_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, int64_t n_processed, int n_work, const int *read_no, const void *regs,
+                                          const int *reg_off, int max_len, uint8_t *status, void *desc, void *req, uint8_t *xa_cnt, void *xa_req,
+                                          uint8_t *n_lines, void *line_desc, void *line_req, uint8_t *line_xa_cnt, void *line_xa_req)
+{
+	return se_wave_batch("mi355x_se_wave_lines_batch", opt, bns, n_processed, n_work, read_no, regs, reg_off, max_len, status, desc, req, xa_cnt, xa_req,
+	                     n_lines, line_desc, line_req, line_xa_cnt, line_xa_req);
 }
 
 extern "C" int mi355x_smem_batch(const mem_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off, int cap,
@@ -870,14 +918,21 @@ extern "C" size_t mi355x_sam_arena_bytes(int n_reads, int max_len) { return sam_
 static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_units, const uint8_t *reads,
                      const int64_t *off, const uint8_t *quals, const char *names, const int *name_off, const void *desc_, const void *reqs_,
                      const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off, uint8_t *arena_out,
-                     unsigned long long *cursor, void *hdr_out)
+                     unsigned long long *cursor, void *hdr_out, const uint8_t *n_lines = nullptr)
 {
 	require_any_device();
 	if (n_units <= 0) return 0;
 	hipStream_t st = 0;
 	const int n = ends * n_units, n_req = req_base[n_units];
 	const int64_t l_pac = bns->l_pac;
-	const SamDesc *desc = (const SamDesc *)desc_;
+	// n_lines given (ends = 1): desc_ holds SE_LINES_CAP line descriptors per read for sam_lines_kernel, and the chunk-wide descriptors say
+	// "not the device's", as in the pipeline
+	SamDesc not_mine;
+	memset(&not_mine, 0, sizeof not_mine);
+	not_mine.req = -1;
+	const std::vector<SamDesc> none(n_lines ? (size_t)n : 0, not_mine);
+	const SamDesc *ldesc = n_lines ? (const SamDesc *)desc_ : nullptr;
+	const SamDesc *desc = n_lines ? none.data() : (const SamDesc *)desc_;
 	const AlnReq *reqs = (const AlnReq *)reqs_;
 	for (int i = 0; i < n; ++i)
 		if ((int)(off[i + 1] - off[i]) <= 0 || name_off[i + 1] < name_off[i]) die("%s: bad read %d", who, i);
@@ -899,6 +954,19 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 			for (int j = 1; j <= (d.flag >> SAM_XA_SHIFT & SAM_XA_MASK); ++j)   // its XA entries' requests follow its own
 				if (q + j >= req_base[k + 1] || reqs[q + j].read != r || reqs[q + j].pad < 0 || reqs[q + j].pad >= bns->n_seqs || reqs[q + j].rb >= reqs[q + j].re)
 					die("%s: bad XA request %d of descriptor %d", who, j, r);
+		}
+	}
+	for (int k = 0; n_lines && k < n_units; ++k) {
+		if (n_lines[k] == 0) continue;
+		if (n_lines[k] < 2 || n_lines[k] > SE_LINES_CAP) die("%s: read %d with %d lines", who, k, (int)n_lines[k]);
+		for (int j = 0; j < n_lines[k]; ++j) {
+			const SamDesc &d = ldesc[(size_t)k * SE_LINES_CAP + j];
+			const int q = req_base[k] + d.req;
+			if (d.req < 0 || q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != k) die("%s: bad descriptor of line %d of read %d", who, j, k);
+			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[k] || d.qb > d.qe) die("%s: bad region of line %d of read %d", who, j, k);
+			for (int x = 1; x <= (d.flag >> SAM_XA_SHIFT & SAM_XA_MASK); ++x)
+				if (q + x >= req_base[k + 1] || reqs[q + x].read != k || reqs[q + x].pad < 0 || reqs[q + x].pad >= bns->n_seqs || reqs[q + x].rb >= reqs[q + x].re)
+					die("%s: bad XA request %d of line %d of read %d", who, x, j, k);
 		}
 	}
 	for (int q = 0; q < n_req; ++q) {
@@ -935,7 +1003,14 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 	ChunkDev D;
 	D.d_seq = d_seq; D.d_off = d_off; D.d_len = d_len; D.max_len = max_len; D.d_pac = d_pac; D.d_gap = d_gap;
 	D.d_qual = d_qual; D.d_names = d_names; D.d_noff = d_noff; D.d_ann_off = d_ao; D.d_ann_names = d_cn; D.d_ann_noff = d_cno;
+	DevArr<uint8_t> d_ml;
+	DevArr<SamDesc> d_md;
 	AlnSamJob J;
+	if (n_lines) {
+		d_ml = DevArr<uint8_t>((size_t)n_units + 64, n_lines, (size_t)n_units);
+		d_md = DevArr<SamDesc>((size_t)n_units * SE_LINES_CAP * sizeof(SamDesc), ldesc);
+		J.n_multi = n_units; J.d_mlines = d_ml; J.d_mdesc = d_md; J.d_mbase = d_base;   // (every read a unit; its request base is the job's own)
+	}
 	J.n_req = n_req; J.d_req = d_req; J.d_hdr = d_hdr; J.d_pool = d_pool; J.pool_bytes = pool_bytes; J.d_cnt = d_cnt; J.d_lists = d_lists;
 	J.ends = ends; J.n_reads = n; J.d_desc = d_desc; J.h_base = req_base; J.d_base = d_base;
 	J.d_arena = d_arena; J.arena_bytes = arena_bytes; J.d_used = d_used; J.d_ooff = d_ooff; J.d_olen = d_olen; J.grid_blocks = grid_blocks;
@@ -967,6 +1042,22 @@ extern "C" int mi355x_sam_se_batch(const mem_opt_t *opt, const bntseq_t *bns, co
 	return sam_batch("mi355x_sam_se_batch", 1, opt, bns, pac, n_reads, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
 	                 out_len, out_off, arena_out, cursor, hdr_out);
 }
+
+// The twin for single-end reads of several lines (sam_lines_kernel.hip behind aln_kernel and an idle sam_emit_kernel<false>, as the pipeline
+// queues them): n_lines[r] = 2 .. mi355x_se_lines_cap() lines of read r (0: not a read of the device's, out_len = -2), desc_ = their
+// descriptors by (r, line) as mi355x_se_wave_lines_batch returns them (req relative to req_base[r]; requests laid out as [line 0, its
+// XA entries, line 1, ...]).  out_len[r] = bytes of all lines of the read, back to back at out_off[r]; -1: the host's read.
+extern "C" int mi355x_sam_se_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
+                                         const uint8_t *quals, const char *names, const int *name_off, const uint8_t *n_lines, const void *desc_,
+                                         const void *reqs_, const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off,
+                                         uint8_t *arena_out, unsigned long long *cursor, void *hdr_out)
+{
+	if (!n_lines) die("mi355x_sam_se_lines_batch: no line counts");
+	return sam_batch("mi355x_sam_se_lines_batch", 1, opt, bns, pac, n_reads, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
+	                 out_len, out_off, arena_out, cursor, hdr_out, n_lines);
+}
+extern "C" int mi355x_sam_lines_row(void) { return sam_lines_row(); }
+extern "C" int mi355x_sam_lines_sa_stage(void) { return sam_lines_sa_stage(); }
 
 // Stage-level entry point of the seed enumeration between SMEM and SA lookup (tests): seed_prep_kernel, the pipeline's prefix sum over
 // the seed counts, seed_enum_kernel, on chosen intervals (read r: n_intv[r] records of (x0, x1, size, info) from intv[r * cap * 4], in any

@@ -1,14 +1,18 @@
 """Single-end leg next to bench.py: trimmed single-end reads (BASELINE config 3: lengths uniform 50-300) through mem_process_seqs with
 the device path of the stage after the CIGAR kernel (se_simple_kernel, se_wave_kernel, single-end sam_emit_kernel), with
 MPIBWA_HOST_SE_WAVE=1 (se_simple_kernel alone: reads with more than eight regions or an XA tag stay on the host) and with
-MPIBWA_HOST_SE=1 (the host path: what the library did before it had either), alternately, on the same chunks.
+MPIBWA_HOST_SE=1 (the host path: what the library did before it had either), alternately, on the same chunks.  --legs chooses among
+them and "nosupp" (MPIBWA_HOST_SUPP=1: reads with supplementary lines stay on the host).
 
-    python tools/bench_se.py [--reads N] [--chunks C] [--steps K] [--repeats R] [--genome-mbp M] [--out FILE]
+    python tools/bench_se.py [--reads N] [--chunks C] [--steps K] [--repeats R] [--genome-mbp M] [--chimeric-frac F] [--legs a,b] [--out FILE]
+
+--chimeric-frac F makes that share of the reads chimeric: two or three segments of at least 40 bases, each cut from a read of the
+generator that lies elsewhere in the genome, every second one reverse-complemented — reads whose record has supplementary lines.
 
 The reads come from the generator and the index cache bench.py uses (bigindex.make_or_get / simulate_pairs with 300-base reads; read 1 of
 every pair, cut to a seeded length in [50, 300]).  Every leg is a fresh child process under its own `timeout`; the run stops at the
 first leg that fails.  One JSON line per leg: Mreads/s, emit_ms and plan_ms per chunk, host CPU-seconds per chunk, n_se_dev / n_reads,
-n_sam_dev / n_reads, n_se_wave_dev, n_se_xa_dev and n_se_xa_sam_dev per chunk, and a hash of the SAM of all chunks, which must be the
+n_sam_dev / n_reads, n_se_wave_dev, n_se_xa_dev, n_se_xa_sam_dev, n_se_supp_dev and n_se_supp_sam_dev per chunk, and a hash of the SAM of all chunks, which must be the
 same in every leg.  A last child (one step, MPIBWA_CPUSEC=1) reports the status codes of the two deciding kernels."""
 import argparse
 import hashlib
@@ -28,6 +32,36 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+_RC = bytes.maketrans(b"ACGTN", b"TGCAN")
+
+
+def chimeric(reads, lens, frac, rng):
+    """reads: [(name, ASCII read of 300 bases, None)], lens: the lengths they are cut to -> the cut reads, a share `frac` of them put
+    together from 2 or 3 segments (each at least 40 bases) of other reads of the chunk: other places, every second one the other strand"""
+    import numpy as np
+    out = []
+    n = len(reads)
+    for (name, a, _), ln in zip(reads, lens):
+        ln = int(ln)
+        k = 3 if ln >= 150 and rng.random() < 0.5 else 2
+        if frac <= 0 or rng.random() >= frac or ln < 40 * k:
+            out.append((name, a[:ln], None))
+            continue
+        if k == 2:
+            cuts = [int(rng.choice(np.arange(40, ln - 40 + 1, dtype=np.int64), size=1)[0])]
+        else:
+            c0 = int(rng.integers(40, ln - 80 + 1))
+            cuts = [c0, int(rng.integers(c0 + 40, ln - 40 + 1))]
+        edges = [0] + cuts + [ln]
+        parts = []
+        for j in range(k):
+            src = reads[int(rng.integers(n))][1] if j else a
+            seg = src[edges[j]:edges[j + 1]]
+            parts.append(seg[::-1].translate(_RC) if j % 2 else seg)
+        out.append((name, b"".join(parts), None))
+    return out
+
+
 def child(args):
     import numpy as np
     from mpibwa_amd import abi, api, bigindex
@@ -40,7 +74,7 @@ def child(args):
         rng = np.random.default_rng(args.seed + 100 + c)
         pairs = idx.simulate_pairs(args.reads, seed=args.seed + c, read_len=300, frag_mean=660.0)
         lens = rng.integers(50, 301, size=len(pairs))
-        batches.append(abi.SeqBatch(api.libc, [(n, a[:int(l)], None) for (n, a, _), l in zip(pairs, lens)]))
+        batches.append(abi.SeqBatch(api.libc, chimeric(pairs, lens, args.chimeric_frac, rng)))
     opt = eng.opt(flag=0, n_threads=int(lib.mi355x_host_cpus()))
     import ctypes as C
     C.c_int.in_dll(eng.lib, "bwa_verbose").value = 1
@@ -63,7 +97,8 @@ def child(args):
     n = max(1, args.steps)
     print(json.dumps({
         "leg": args.leg, "rep": args.rep, "workload": "single-end, lengths uniform 50-300, %d chunks x %d reads vs %d Mbp (%s)" %
-        (args.chunks, args.reads, int(args.genome_mbp), args.genome_model), "steps": args.steps,
+        (args.chunks, args.reads, int(args.genome_mbp), args.genome_model) + (", %g of the reads chimeric" % args.chimeric_frac if args.chimeric_frac > 0 else ""),
+        "steps": args.steps,
         "mreads_s": round(acc.get("n_reads", 0) / wall / 1e6, 4), "ms_per_chunk": round(wall / n * 1e3, 2),
         "emit_ms": round(acc.get("emit_ms", 0) / n, 2), "plan_ms": round(acc.get("plan_ms", 0) / n, 2),
         "host_cpu_s_per_chunk": round(cpu / n, 3),
@@ -71,6 +106,7 @@ def child(args):
         "sam_dev_frac": round(acc.get("n_sam_dev", 0) / max(1, acc.get("n_reads", 1)), 4),
         "se_wave_dev_per_chunk": round(acc.get("n_se_wave_dev", 0) / n, 1), "se_xa_dev_per_chunk": round(acc.get("n_se_xa_dev", 0) / n, 1),
         "se_xa_sam_dev_per_chunk": round(acc.get("n_se_xa_sam_dev", 0) / n, 1),
+        "se_supp_dev_per_chunk": round(acc.get("n_se_supp_dev", 0) / n, 1), "se_supp_sam_dev_per_chunk": round(acc.get("n_se_supp_sam_dev", 0) / n, 1),
         "sam_sha256": h.hexdigest()}), flush=True)
 
 
@@ -87,20 +123,28 @@ def main():
     ap.add_argument("--workdir", default=os.environ.get("MPIBWA_BENCH_DIR", "/tmp/mpibwa_bench"))
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds a leg may take (index load included)")
     ap.add_argument("--out", help="also write the JSON lines to this file")
-    ap.add_argument("--leg", choices=["host", "nowave", "dev", "codes"], help=argparse.SUPPRESS)
+    ap.add_argument("--chimeric-frac", type=float, default=0.0, help="share of the reads put together from 2 or 3 segments of different places and strands")
+    ap.add_argument("--legs", default="host,nowave,dev", help="the legs of a round, of host, nowave, nosupp, dev")
+    ap.add_argument("--leg", choices=["host", "nowave", "nosupp", "dev", "codes"], help=argparse.SUPPRESS)
     ap.add_argument("--rep", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.leg:
         return child(args)
     lines = []
     passthrough = ["--reads", str(args.reads), "--chunks", str(args.chunks), "--seed", str(args.seed), "--genome-mbp", str(args.genome_mbp),
-                   "--repeat-frac", str(args.repeat_frac), "--genome-model", args.genome_model, "--workdir", args.workdir]
-    legs = [(leg, rep) for rep in range(args.repeats) for leg in ("host", "nowave", "dev")] + [("codes", 0)]
+                   "--repeat-frac", str(args.repeat_frac), "--genome-model", args.genome_model, "--workdir", args.workdir, "--chimeric-frac", str(args.chimeric_frac)]
+    names = [x for x in args.legs.split(",") if x]
+    if not names or any(x not in ("host", "nowave", "nosupp", "dev") for x in names):
+        ap.error("--legs: a comma-separated choice of host, nowave, nosupp, dev")
+    legs = [(leg, rep) for rep in range(args.repeats) for leg in names] + [("codes", 0)]
     for leg, rep in legs:
         env = dict(os.environ)
         env.pop("MPIBWA_HOST_SE", None)
         env.pop("MPIBWA_HOST_SE_WAVE", None)
         env.pop("MPIBWA_CPUSEC", None)
+        env.pop("MPIBWA_HOST_SUPP", None)
+        if leg == "nosupp":
+            env["MPIBWA_HOST_SUPP"] = "1"
         if leg == "host":
             env["MPIBWA_HOST_SE"] = "1"
         if leg == "nowave":
@@ -124,12 +168,11 @@ def main():
         lines.append(rec)
         print(json.dumps(rec), flush=True)
     same = len({r["sam_sha256"] for r in lines}) == 1
-    by = {leg: [r for r in lines if r["leg"] == leg] for leg in ("host", "nowave", "dev")}
-    summary = {"leg": "summary", "sam_identical_across_legs": same,
-               "host_mreads_s": [r["mreads_s"] for r in by["host"]], "nowave_mreads_s": [r["mreads_s"] for r in by["nowave"]],
-               "dev_mreads_s": [r["mreads_s"] for r in by["dev"]],
-               "host_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["host"]],
-               "nowave_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["nowave"]], "dev_cpu_s_per_chunk": [r["host_cpu_s_per_chunk"] for r in by["dev"]]}
+    by = {leg: [r for r in lines if r["leg"] == leg] for leg in names}
+    summary = {"leg": "summary", "sam_identical_across_legs": same}
+    for leg in names:
+        summary[leg + "_mreads_s"] = [r["mreads_s"] for r in by[leg]]
+        summary[leg + "_cpu_s_per_chunk"] = [r["host_cpu_s_per_chunk"] for r in by[leg]]
     lines.append(summary)
     print(json.dumps(summary), flush=True)
     if args.out:
