@@ -349,6 +349,26 @@ int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *bns, const u
                               int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
                               void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt);
 
+/* mi355x_pair_wave_xa_batch with the kernel's side arrays for the pairs mem_sam_pe reports end by end through no_pairing:
+ * (src/bwamem_pair.c:371-392: an end without a hit, no pair of hits in a proper orientation and distance, a best pair that scores
+ * nothing, an end with a second primary hit of at least T).  status[k] = 17: decided that way instead of code 8 / 9 / 10; a pair
+ * without any region is looked at too (status 2 -> 17 with no line).  n_lines[2k + e] = 0 .. mi355x_se_lines_cap(): the lines of end
+ * e, the primary hits of at least T in list order (src/bwamem.c:1015-1032 without MEM_F_ALL); 0: the end's record is the unaligned one
+ * and has neither descriptor nor request.  Line j of end e sits in slot x = (2k + e) * mi355x_se_lines_cap() + j of line_desc, line_req
+ * and line_xa_cnt: flag = 0x40 << e | 1, | 2 when both ends have a top hit of at least T on one contig at a proper distance
+ * (src/bwamem_pair.c:382-387), | 0x800 behind the end's first line (0x100 under MEM_F_NO_MULTI), the line's XA count in bits 16-19;
+ * mapq is mem_approx_mapq_se of the line's own hit (with its csub), lowered to line 0's behind it unless MEM_F_KEEP_SUPP_MAPQ; sub =
+ * max(sub, csub); XA entry i's request at line_xa_req[x * mi355x_pair_wave_xa_cap() + i].  desc.req counts from the pair's first request
+ * when they are laid out as [end 0: line 0, its XA entries', line 1, ...; end 1: ...], which is how mi355x_sam_pe_lines_batch reads
+ * them; req.read = 2k + e.  desc / req / xa_cnt [2k + e] are not written for such a pair.  More than mi355x_se_lines_cap() lines on an
+ * end: 10 as before; line_xa_req == NULL or max_XA_hits beyond the cap: a pair with 1 .. max_XA_hits entries on a line gets 11; a line
+ * beyond the per-length or sub_n tables: 6.  xa_req == NULL: the paired branch runs without its XA listing.  Pairs the paired branch
+ * decides (1, 16) come back exactly as from mi355x_pair_wave_batch / _xa_batch. */
+int mi355x_pair_wave_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                 int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                 void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt, uint8_t *n_lines, void *line_desc,
+                                 void *line_req, uint8_t *line_xa_cnt, void *line_xa_req);
+
 /* SAM text of the pairs decided on the device: the CIGAR kernel (aln_kernel) and sam_emit_kernel, queued on one stream as the
  * pipeline queues them, on chosen line descriptors.  2 n_pairs reads as nt4 codes (read r = reads[off[r] .. off[r+1])), their
  * qualities at the same places (or NULL: QUAL is '*'), their names back to back (read r = names[name_off[r] .. name_off[r+1])); the
@@ -451,6 +471,22 @@ int mi355x_sam_se_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const u
                               const void *reqs, const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off,
                               uint8_t *arena_out, unsigned long long *cursor, void *hdr_out);
 
+/* The text of pairs that mem_sam_pe reports end by end (no_pairing:, src/bwamem_pair.c:371-392): aln_kernel, then the paired
+ * instantiation of sam_lines_kernel (a pair per wavefront) on the descriptors of mi355x_pair_wave_lines_batch.  Every pair is a unit;
+ * n_lines[2k + e] = 0 .. mi355x_se_lines_cap() lines of end e, desc holds mi355x_se_lines_cap() descriptors per read, line j of read r
+ * at [r * cap + j]; pair k owns reqs[req_base[k] .. req_base[k+1]), laid out as [end 0: line 0, its XA entries', line 1, ...; end 1:
+ * ...] with reqs.read = 2k + e.  Every line is written as mem_aln2sam writes it with a mate (src/bwamem.c:830-840, 856-867, 908): the
+ * mate of every line of end e is line 0 of the other end.  An end without a line is the unaligned record: with an aligned mate it takes
+ * the mate's contig, position and strand (flag 0x4, CIGAR *, RNEXT =, TLEN 0, MC:Z:, AS:i:0 XS:i:0), without one the columns are
+ * "* 0 0 * * 0 0".  A line whose mate is unaligned prints its own position as PNEXT, flag 0x8, TLEN 0, no MC.  On lines behind the first,
+ * and not under MEM_F_SOFTCLIP, MC:Z: prints the mate's clips as H.  An end of one line has no SA tag.  Tags: NM MD MC AS XS RG SA XA.
+ * out_len[r] = the bytes of all lines of read r at out_off[r]; -1: the host's pair, both reads (the reasons of
+ * mi355x_sam_se_lines_batch, on any line of either end).  Arena, guard, cursor, grid_blocks and hdr_out as for mi355x_sam_batch. */
+int mi355x_sam_pe_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
+                              const uint8_t *quals, const char *names, const int *name_off, const uint8_t *n_lines, const void *desc,
+                              const void *reqs, const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off,
+                              uint8_t *arena_out, unsigned long long *cursor, void *hdr_out);
+
 /* Seed enumeration between SMEM and SA lookup (src/bwamem.c:161, 265-283): seed_prep_kernel (sort of a read's intervals by info,
  * l_rep, number of seeds), the prefix sum over the counts, seed_enum_kernel (BWT row and (qbeg, len) of every seed, stepping through
  * intervals larger than max_occ).  Read r has n_intv[r] intervals (x0, x1, size, info) from intv[4 * cap * r], in any order; with
@@ -510,6 +546,8 @@ typedef struct {
 	uint64_t n_se_xa_sam_dev;                    /* ... and how many of those records sam_kernel wrote (the rest came back and were aligned and formatted by the host) */
 	uint64_t n_se_supp_dev;                      /* single-end reads se_wave_kernel decided with more than one line (a primary and supplementary lines with SA tags); counted in none of n_se_dev, n_se_wave_dev, n_se_xa_dev, nor, their records, in n_sam_dev */
 	uint64_t n_se_supp_sam_dev;                  /* ... and how many of those reads' text sam_lines_kernel wrote (the rest came back and were aligned and formatted by the host) */
+	uint64_t n_pair_lines_dev;                   /* pairs that mem_sam_pe reports end by end (no_pairing:) decided by pair_wave_kernel with 0 to 4 lines per end (MPIBWA_HOST_PAIR_LINES=1: off); counted in none of n_pair_dev, n_pair_wave_dev, n_pair_xa_dev, nor, their records, in n_sam_dev */
+	uint64_t n_pair_lines_sam_dev;               /* ... and how many of those pairs' text sam_lines_kernel wrote (the rest came back and were decided, aligned and formatted by the host) */
 } mi355x_stats_t;
 void mi355x_last_stats(mi355x_stats_t *st);
 

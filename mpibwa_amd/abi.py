@@ -90,7 +90,8 @@ class mi355x_stats_t(C.Structure):
                [(n, C.c_double) for n in ("plan_ms", "aln_ms", "k_aln_ms")] + [("n_aln", C.c_uint64), ("phase1_ms", C.c_double), ("msw_ms", C.c_double), ("k_msw_ms", C.c_double), ("n_msw", C.c_uint64), ("emit_ms", C.c_double), ("n_sub", C.c_uint64), ("smem_tab_bytes", C.c_uint64), ("n_sam_dev", C.c_uint64), ("n_pair_dev", C.c_uint64), ("n_se_dev", C.c_uint64), ("n_pair_wave_dev", C.c_uint64), ("n_pair_xa_dev", C.c_uint64),
                 ("n_dedup_dev", C.c_uint64), ("n_dedup_host", C.c_uint64),
                 ("n_se_wave_dev", C.c_uint64), ("n_se_xa_dev", C.c_uint64), ("n_se_xa_sam_dev", C.c_uint64),
-                ("n_se_supp_dev", C.c_uint64), ("n_se_supp_sam_dev", C.c_uint64)]
+                ("n_se_supp_dev", C.c_uint64), ("n_se_supp_sam_dev", C.c_uint64),
+                ("n_pair_lines_dev", C.c_uint64), ("n_pair_lines_sam_dev", C.c_uint64)]
 
 
 assert C.sizeof(mem_opt_t) == 168

@@ -22,6 +22,7 @@ EXPORTS = [
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
     "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg", "mi355x_se_wave_batch",
     "mi355x_se_lines_cap", "mi355x_se_wave_lines_batch", "mi355x_sam_se_lines_batch", "mi355x_sam_lines_row", "mi355x_sam_lines_sa_stage",
+    "mi355x_pair_wave_lines_batch", "mi355x_sam_pe_lines_batch",
 ]
 
 
@@ -121,6 +122,7 @@ def load_library(build_if_missing=True):
     sig("mi355x_pair_wave_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 8)
     sig("mi355x_pair_wave_xa_cap", C.c_int, [])
     sig("mi355x_pair_wave_xa_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 10)
+    sig("mi355x_pair_wave_lines_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 15)
     sig("mi355x_global_batch", C.c_int, [P(abi.mem_opt_t), C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 +
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_double)])
     sig("mi355x_sam_arena_bytes", C.c_size_t, [C.c_int, C.c_int])
@@ -133,6 +135,7 @@ def load_library(build_if_missing=True):
     sig("mi355x_sam_lines_row", C.c_int, [])
     sig("mi355x_sam_lines_sa_stage", C.c_int, [])
     sig("mi355x_sam_se_lines_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
+    sig("mi355x_sam_pe_lines_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_dedup_maxreg", C.c_int, [])
     sig("mi355x_dedup_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [P(C.c_double)])
     sig("mi355x_seed_batch", C.c_int64, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int64])
@@ -448,6 +451,54 @@ class Engine:
             return status, desc, req, [xa_req[r, :xa_cnt[r]].copy() for r in range(n)], n_align.value
         return status, desc, req, n_align.value
 
+    PW_DECIDED_LINES = 17
+
+    def pairs_wave_lines(self, opt, pes, reads, regs, n_processed=0, xa=True, lines=True):
+        """pair_wave_kernel with its side arrays for the pairs mem_sam_pe reports end by end (mi355x_pair_wave_lines_batch); arguments as
+        pairs_wave.  -> status, desc, req, xa_req as pairs_wave_xa returns them, n_lines (2 n_pairs,) uint8 — the lines of every read of a
+        pair with status 17 (PW_DECIDED_LINES), 0: the unaligned record —, `lines`: per read a list of (desc, req, xa_req) per line in list
+        order (a DESC_DT record, an AREQ_DT record and an AREQ_DT array), and the number of local alignments run.  For
+        sam_records_pe_lines the pair's requests are [req, *xa_req] of read 2k's line 0, of its line 1, ..., then read 2k + 1's.
+        xa=False: every XA listing off; lines=False: the side arrays are not handed over."""
+        n = len(reads)
+        assert n % 2 == 0 and len(regs) == n
+        n_pairs = n // 2
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint8) for r in reads])) if n else np.zeros(1, dtype=np.uint8)
+        reg_off = np.zeros(n + 1, dtype=np.int32)
+        reg_off[1:] = np.cumsum([len(r) for r in regs])
+        allregs = np.zeros(max(1, int(reg_off[-1])), dtype=self.REG_DT)
+        for r, a in enumerate(regs):
+            if len(a):
+                allregs[reg_off[r]:reg_off[r + 1]] = np.asarray(a, dtype=self.REG_DT)
+        m = max(n, 1)
+        cap, lcap = self.lib.mi355x_pair_wave_xa_cap(), self.lib.mi355x_se_lines_cap()
+        status = np.zeros(max(n_pairs, 1), dtype=np.uint8)
+        desc = np.zeros(m, dtype=self.DESC_DT)
+        req = np.zeros(m, dtype=self.AREQ_DT)
+        xa_req = np.zeros((m, cap), dtype=self.AREQ_DT)
+        xa_cnt = np.zeros(m, dtype=np.uint8)
+        n_lines = np.zeros(m, dtype=np.uint8)
+        l_desc = np.zeros((m, lcap), dtype=self.DESC_DT)
+        l_req = np.zeros((m, lcap), dtype=self.AREQ_DT)
+        l_xc = np.zeros((m, lcap), dtype=np.uint8)
+        l_xr = np.zeros((m, lcap, cap), dtype=self.AREQ_DT)
+        n_align = C.c_int(0)
+        ptr = lambda a, on: a.ctypes.data if on else None
+        fn = self.lib.mi355x_pair_wave_lines_batch if lines else self.lib.mi355x_pair_wave_xa_batch if xa else self.lib.mi355x_pair_wave_batch
+        args = (opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), C.cast(pes, C.c_void_p), n_processed, n_pairs,
+                flat.ctypes.data, off.ctypes.data, allregs.ctypes.data, reg_off.ctypes.data, status.ctypes.data,
+                desc.ctypes.data, req.ctypes.data, C.cast(C.byref(n_align), C.c_void_p))
+        if lines:
+            args += (ptr(xa_req, xa), ptr(xa_cnt, xa), n_lines.ctypes.data, l_desc.ctypes.data, l_req.ctypes.data, l_xc.ctypes.data, ptr(l_xr, xa))
+        elif xa:
+            args += (xa_req.ctypes.data, xa_cnt.ctypes.data)
+        if fn(*args) != 0:
+            raise RuntimeError("mi355x_pair_wave_lines_batch: the kernel cannot use these insert-size statistics")
+        out = [[(l_desc[r, j].copy(), l_req[r, j].copy(), l_xr[r, j, :l_xc[r, j]].copy()) for j in range(int(n_lines[r]))] for r in range(n)]
+        return status[:n_pairs], desc[:n], req[:n], [xa_req[r, :xa_cnt[r]].copy() for r in range(n)], n_lines[:n], out, n_align.value
+
     def singles(self, opt, regs, n_regs, max_len=150, n_processed=0):
         """se_simple_kernel on single-end reads given by their regions: regs (n_reads, mi355x_pair_maxreg()) of REG_DT, n_regs (n_reads).
         -> status (n_reads,) uint8, desc (n_reads,) DESC_DT, req (n_reads,) AREQ_DT"""
@@ -574,6 +625,17 @@ class Engine:
         assert len(n_lines) == len(reads)
         return self.sam_records(opt, reads, quals, names, desc, reqs, req_base, arena_bytes, grid_blocks, ends=1, n_lines=n_lines)
 
+    def sam_records_pe_lines(self, opt, reads, quals, names, n_lines, desc, reqs, req_base, arena_bytes=0, grid_blocks=0):
+        """aln_kernel + the paired instantiation of sam_lines_kernel (mi355x_sam_pe_lines_batch): 2 n_pairs reads of n_lines[r] lines each
+        (0 .. mi355x_se_lines_cap(); 0: the unaligned record), desc (2 n_pairs, cap) DESC_DT with line j of read r at [r, j], reqs per pair
+        [read 2k: line 0, its XA entries', line 1, ...; read 2k + 1: ...] with read = 2k + e, req_base (n_pairs + 1,).
+        -> sam_records' dict; out_len[r] covers all lines of read r."""
+        lcap = self.lib.mi355x_se_lines_cap()
+        desc = np.ascontiguousarray(desc, dtype=self.DESC_DT).reshape(len(reads), lcap)
+        n_lines = np.ascontiguousarray(n_lines, dtype=np.uint8)
+        assert len(n_lines) == len(reads)
+        return self.sam_records(opt, reads, quals, names, desc, reqs, req_base, arena_bytes, grid_blocks, ends=2, n_lines=n_lines)
+
     def sam_records(self, opt, reads, quals, names, desc, reqs, req_base, arena_bytes=0, grid_blocks=0, ends=2, n_lines=None):
         """aln_kernel + sam_emit_kernel (mi355x_sam_batch) on chosen descriptors.  reads: 2 n_pairs nt4 code arrays; quals: as many byte
         strings or None; names: one byte string per read; desc (2 n_pairs,) DESC_DT; reqs AREQ_DT; req_base (n_pairs + 1,).
@@ -604,7 +666,7 @@ class Engine:
         fn = self.lib.mi355x_sam_batch if ends == 2 else self.lib.mi355x_sam_se_batch
         lines = ()
         if n_lines is not None:
-            fn, lines = self.lib.mi355x_sam_se_lines_batch, (n_lines.ctypes.data,)
+            fn, lines = self.lib.mi355x_sam_se_lines_batch if ends == 1 else self.lib.mi355x_sam_pe_lines_batch, (n_lines.ctypes.data,)
         rc = fn(opt, C.cast(self.bns, C.c_void_p), C.cast(self.pac, C.c_void_p), n // ends, flat.ctypes.data, off.ctypes.data,
                                        fq.ctypes.data if fq is not None else None, nm.ctypes.data, noff.ctypes.data, *lines, desc.ctypes.data,
                                        reqs.ctypes.data if len(reqs) else None, req_base.ctypes.data, arena_bytes, int(grid_blocks), out_len.ctypes.data,

@@ -46,10 +46,11 @@ SZ(bwaidx_t, 48);
 OFF(bwaidx_t, bwt, 0); OFF(bwaidx_t, bns, 8); OFF(bwaidx_t, pac, 16); OFF(bwaidx_t, is_shm, 24); OFF(bwaidx_t, l_mem, 32); OFF(bwaidx_t, mem, 40);
 
 // the library's own statistics record: fields are only ever appended (mpibwa_amd/abi.py mirrors it)
-SZ(mi355x_stats_t, 344);
+SZ(mi355x_stats_t, 360);
 OFF(mi355x_stats_t, n_se_dev, 264); OFF(mi355x_stats_t, n_pair_wave_dev, 272);
 OFF(mi355x_stats_t, n_pair_xa_dev, 280); OFF(mi355x_stats_t, n_dedup_dev, 288); OFF(mi355x_stats_t, n_dedup_host, 296);
 OFF(mi355x_stats_t, n_se_wave_dev, 304); OFF(mi355x_stats_t, n_se_xa_dev, 312); OFF(mi355x_stats_t, n_se_xa_sam_dev, 320);
 OFF(mi355x_stats_t, n_se_supp_dev, 328); OFF(mi355x_stats_t, n_se_supp_sam_dev, 336);
+OFF(mi355x_stats_t, n_pair_lines_dev, 344); OFF(mi355x_stats_t, n_pair_lines_sam_dev, 352);
 
 extern "C" int mi355x_abi_version(void) { return 2; }   // bumped whenever include/mpibwa_amd.h changes incompatibly

@@ -294,10 +294,12 @@ struct AlnSamJob {
 	const int *h_base = nullptr; int *d_base = nullptr;   // first request of every unit (n_reads / ends + 1 entries), uploaded here
 	uint8_t *d_arena = nullptr; size_t arena_bytes = 0; unsigned long long *d_used = nullptr, *d_ooff = nullptr; int *d_olen = nullptr;
 	int grid_blocks = 0;
-	// the reads with several lines (sam_lines_kernel.hip; single-end jobs), whose chunk-wide descriptor says "not the device's": n_multi
-	// units, unit u = read d_mlist[u] of the chunk (null: r0 + u) with d_mlines[u] lines, their descriptors at d_mdesc[u * SE_LINES_CAP ..]
+	// the reads with several lines (sam_lines_kernel.hip), whose chunk-wide descriptor says "not the device's": n_multi units.  ends = 1:
+	// unit u = read d_mlist[u] of the chunk (null: r0 + u) with d_mlines[u] lines, their descriptors at d_mdesc[u * SE_LINES_CAP ..]
 	// and its requests from d_mbase[u] in d_req (d_mlines[u] = 0 or d_mbase[u] < 0: not a unit of this job).  All four live on the device
-	// already: in the pipeline they are se_wave_kernel's own work list and side arrays.
+	// already: in the pipeline they are se_wave_kernel's own work list and side arrays.  ends = 2: the units are pairs reported end by
+	// end (pair_wave_kernel: PW_DECIDED_LINES) — unit u = pair d_mlist[u] of the chunk (null: r0 / 2 + u), d_mlines[2u + e] lines of end
+	// e (0: the unaligned record) with their descriptors at d_mdesc[(2u + e) * SE_LINES_CAP ..]; d_mbase[u] < 0 alone says "not a unit".
 	int n_multi = 0; const int *d_mlist = nullptr; const uint8_t *d_mlines = nullptr; const SamDesc *d_mdesc = nullptr; const int *d_mbase = nullptr;
 };
 // on `stream`: zero the counters, [ev_a] aln_kernel [ev_b] (when there are requests), then descriptors and request bases up, zero the
@@ -330,7 +332,11 @@ void launch_sam_lines(void *stream, const SamParams &P, bool softclip, int n_uni
                       const int *d_req_base, const AlnReq *d_req, const AlnHdr *d_hdr, const uint8_t *d_pool, const uint8_t *d_seq, const int64_t *d_off,
                       const int *d_len, const uint8_t *d_qual, const uint8_t *d_names, const int *d_name_off, const int64_t *d_ann_off,
                       const char *d_ann_names, const int *d_ann_name_off, uint8_t *d_arena, size_t arena_bytes, unsigned long long *d_arena_used,
-                      unsigned long long *d_out_off, int *d_out_len, int grid_blocks = 0);
+                      unsigned long long *d_out_off, int *d_out_len, int grid_blocks = 0, bool pe = false);
+// pe: the paired instantiation: unit u = pair pr = d_list ? d_list[u] : u, whose reads are 2 pr - r0 + e of the arrays above; d_n_lines[2u + e]
+// lines of end e (0 .. SE_LINES_CAP; 0: the unaligned record) described by d_ldesc[(2u + e) * SE_LINES_CAP ..] as pair_wave_kernel
+// leaves them, the pair's requests from d_req_base[u]; d_req_base[u] < 0: not a unit.  The mate of every line is line 0 of the other
+// end, or the unaligned record.  out_len / out_off per read; a pair is handed back whole (both out_len = -1).
 int sam_lines_row(void);
 int sam_lines_sa_stage(void);
 
@@ -389,8 +395,10 @@ extern "C" int mi355x_pair_wave_maxreg(void);
 #define PW_HOST_FULL 13           // a list past PW_MAXREG
 #define PW_HOST_TIE 14            // the outcome depends on the reference's unstable sorts (equal end positions, equal (score, hash))
 #define PW_DECIDED_XA 16          // decided, and at least one of the two records carries an XA tag
+#define PW_DECIDED_LINES 17       // decided through no_pairing: (src/bwamem_pair.c:371-392): 0 .. SE_LINES_CAP lines per end (SE_DECIDED_LINES' number)
 #define PW_XA_CAP 8               // XA entries per record the kernel lists; a call with max_XA_hits beyond it runs without XA on the device
 extern "C" int mi355x_pair_wave_xa_cap(void);
+struct SeLines;
 // tags per (end, candidate hit, orientation): >= 0 the alignment's number in the pair's slice of the mate-rescue requests
 #define PW_TAG_NO_WINDOW (-1)     // mem_matesw would align nothing there (src/bwamem_pair.c:150)
 #define PW_TAG_HOST (-2)          // not listed (explained by a mate hit before any rescue) or a window msw2_kernel does not take
@@ -400,10 +408,18 @@ extern "C" int mi355x_pair_wave_xa_cap(void);
 void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
                       const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
                       const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc,
-                      AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr);
+                      AlnReq *d_xa_reqs = nullptr, uint8_t *d_xa_cnt = nullptr, const SeLines *lines = nullptr);
 // d_xa_reqs given (and max_XA_hits <= PW_XA_CAP): a pair whose chosen hits carry XA entries (src/bwamem_extra.c:98-118) is decided too,
 // with status PW_DECIDED_XA: xa_cnt[2t + e] entries of end e, their requests (as mem_reg2aln would ask, pad = the hit's contig) at
 // xa_reqs[(2t + e) * PW_XA_CAP ..], desc[2t + e].flag bits 16-19 = the count, desc[2t].req = 0, desc[2t + 1].req = 1 + xa_cnt[2t].
+// lines given (the side arrays of SeLines below, by (work item t, end e, line j): slot x = (2t + e) * SE_LINES_CAP + j of desc / reqs /
+// xa_cnt, the XA requests at xa_reqs[x * PW_XA_CAP ..], n_lines[2t + e]): a pair that mem_sam_pe reports end by end through no_pairing:
+// (src/bwamem_pair.c:371-392) with at most SE_LINES_CAP lines per end gets PW_DECIDED_LINES instead of PW_HOST_NO_PAIR / _SCORE / _SUPP.
+// n_lines = 0: the end's record is the unaligned one, without descriptor or request.  desc.flag = 0x40 << e | 1 (| 2: the top hits make
+// a proper pair, :382-387) | supp_flag behind the first line | the XA count in bits 16-19; desc.req counts from the pair's first
+// request, laid out as [end 0: line 0, its XA entries, line 1, ...; end 1: ...]; reqs.read = 2 work[t] + e.  reqs / desc / xa_cnt
+// [2t + e] of the launch are not written for such a pair.  lines->xa_reqs = nullptr (or max_XA_hits > PW_XA_CAP): a line with 1 ..
+// max_XA_hits XA entries gives PW_HOST_XA.  Without the arrays nothing changes.
 // the decided pairs' records into the chunk-wide arrays (reqs / desc [2 work[t] + e]); clear_n > 0: reads clear_r0 .. + clear_n are
 // marked "not the device's" first (the arrays then describe the wave's pairs alone)
 void launch_pair_wave_scatter(void *stream, int n_work, const int *d_work, const uint8_t *d_wstatus, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
@@ -473,10 +489,11 @@ void launch_se_wave(void *stream, const PairParams &P, int n_work, const int *d_
 // the device's" first
 void launch_wave_job_scatter(void *stream, int ends, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,
                              const AlnReq *d_xa_reqs, const uint8_t *d_xa_cnt, AlnReq *d_reqs, SamDesc *d_desc, int clear_r0, int clear_n);
-// its sibling for se_wave_kernel's reads of several lines: the requests of work item t with dst[t] >= 0 and n_lines[t] > 0 go to
+// its sibling for se_wave_kernel's reads of several lines (ends = 1) and pair_wave_kernel's pairs reported end by end (ends = 2, the
+// side arrays by (item, end): end 0's lines, then end 1's): the requests of work item t with dst[t] >= 0 go to
 // reqs[dst[t] ..] as [line 0, its XA entries, line 1, ...] from the side arrays (device.h: SeLines); the line descriptors stay where
 // the kernel wrote them (sam_lines_kernel reads them there), and the chunk-wide descriptor of the read stays "not the device's"
-void launch_lines_job_scatter(void *stream, int n_work, const int *d_dst, const uint8_t *d_n_lines, const AlnReq *d_lreq, const uint8_t *d_lxcnt,
+void launch_lines_job_scatter(void *stream, int ends, int n_work, const int *d_dst, const uint8_t *d_n_lines, const AlnReq *d_lreq, const uint8_t *d_lxcnt,
                               const AlnReq *d_lxreq, AlnReq *d_reqs);
 
 // ---- the redundancy pass of mem_sort_dedup_patch on the raw region lists (dedup_kernel.hip) ----

@@ -387,7 +387,7 @@ void queue_aln_sam(void *stream, const mem_opt_t *opt, int64_t l_pac, const Chun
 	if (J.n_multi > 0)
 		launch_sam_lines(st, sp, (opt->flag & MEM_F_SOFTCLIP) != 0, J.n_multi, J.d_mlist, r0, J.d_mlines, J.d_mdesc, J.d_mbase, J.d_req, J.d_hdr, J.d_pool, D.d_seq, D.d_off + r0,
 		                 D.d_len + r0, D.d_qual, D.d_names, D.d_noff + r0, D.d_ann_off, D.d_ann_names, D.d_ann_noff, J.d_arena, J.arena_bytes, J.d_used, J.d_ooff,
-		                 J.d_olen, J.grid_blocks);
+		                 J.d_olen, J.grid_blocks, J.ends == 2);
 }
 
 void queue_c2a(void *stream, const mem_opt_t *opt, int64_t l_pac, int early, const C2aJob &J, void *ev_a, void *ev_b)

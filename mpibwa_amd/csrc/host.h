@@ -266,8 +266,9 @@ void sam_pe_msw_collect(const mem_opt_t *opt, const bntseq_t *bns, const mem_pes
 void sam_pe_msw_collect_tagged(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], const bseq1_t s[2], const HRegV a[2], int read0,
                                int max_tlen, std::vector<MswReqH> &out, std::vector<int16_t> &tags);
 // may pair_wave_kernel look at the pair?  Both lists fixed points of mem_sort_dedup_patch (or empty, but not both), at most max_reg
-// regions each, none on an ALT contig
-bool pair_wave_eligible(const HRegV a[2], int max_reg);
+// regions each, none on an ALT contig.  lines: the kernel runs with the side arrays for the pairs of no_pairing: (device.h:
+// PW_DECIDED_LINES); a pair without any region is then its to report too
+bool pair_wave_eligible(const HRegV a[2], int max_reg, bool lines = false);
 // the same for the one list of a single-end read and se_wave_kernel (an empty list is fine: the unmapped record)
 bool se_wave_eligible(const HRegV &a, int max_reg);
 void sam_pe_emit(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], bseq1_t s[2], HRegV a[2],

@@ -418,9 +418,9 @@ void sam_pe_msw_collect_tagged(const mem_opt_t *opt, const bntseq_t *bns, const 
 	}
 }
 
-bool pair_wave_eligible(const HRegV a[2], int max_reg)
+bool pair_wave_eligible(const HRegV a[2], int max_reg, bool lines)
 {
-	if (a[0].empty() && a[1].empty()) return false;
+	if (a[0].empty() && a[1].empty() && !lines) return false;
 	for (int e = 0; e < 2; ++e) {
 		if ((int)a[e].size() > max_reg || !(a[e].empty() || a[e].settled)) return false;
 		for (size_t j = 0; j < a[e].size(); ++j)

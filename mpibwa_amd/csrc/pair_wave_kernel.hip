@@ -12,6 +12,9 @@
 //   mem_gen_alt           src/bwamem_extra.c:98-118   (which hits the chosen hit's XA string lists: their CIGAR requests; the text is
 //                                                       sam_emit_kernel's)
 //   mem_reg2aln           src/bwamem.c:1089-1105      (the band of the final global alignment)
+//   no_pairing:           src/bwamem_pair.c:371-392   (with the side arrays of device.h: SeLines — the pairs reported end by end: which hits
+//                                                       of each end become lines, src/bwamem.c:1015-1032, the proper-pair flag of :382-387;
+//                                                       sam_lines_kernel.hip writes the text)
 // The pairs are the ones pair_simple_kernel leaves with "rescue", "more than eight hits" or "one end without a hit".  The host hands over
 // both ends' lists as they stand after mem_sort_dedup_patch (fixed points of the pass: HRegV::settled), at most PW_MAXREG regions each,
 // none on an ALT contig, and per (end, candidate hit, orientation) a tag: the number of the alignment in the pair's slice of the
@@ -19,7 +22,7 @@
 //
 // The list in LDS, the wave reductions, mem_mark_primary_se and the XA listing are wave_common.cuh's, shared with se_wave_kernel.hip.
 // One region per lane, both lists in LDS as one array per field (no bank conflicts, 2 x 64 x 64 B), mem_pair's keys behind them
-// (128 x 16 B) and the rescue candidates: 11 776 B of LDS per wave, 55 VGPRs, no scratch (the compiler's resource usage for gfx950).  The two sorts are rank sorts: mem_pair's keys are unique, so any sort gives the reference's array; two
+// (128 x 16 B) and the rescue candidates: 11 776 B of LDS per wave, 63 VGPRs, no scratch (the compiler's resource usage for gfx950).  The two sorts are rank sorts: mem_pair's keys are unique, so any sort gives the reference's array; two
 // hits with equal (score, hash) in mem_mark_primary_se — where the reference's unstable sort would decide — send the pair to the host.
 // The list u of mem_pair is never stored: only its maximum, the second-largest score and n_sub are used, so it is enumerated twice
 // and reduced.  Anything the wave cannot settle the way the reference does leaves the pair to the host with a code that says why.
@@ -118,12 +121,20 @@ __device__ __forceinline__ void pw_pairs_of(const PairParams &P, const Pair64 *V
 // xa_reqs given: a chosen hit with XA entries no longer sends the pair to the host.  wstatus[t] = PW_DECIDED_XA, xa_cnt[2t + e] entries
 // of end e with their requests at xa_reqs[(2t + e) * PW_XA_CAP ..], in list order; desc[2t + e].flag carries the count in bits 16-19 and
 // desc[2t + 1].req = 1 + xa_cnt[2t] (the pair's requests in a job: read 0's, its XA entries', read 1's, its XA entries').
+// LN.desc given: a pair mem_sam_pe reports through no_pairing: (src/bwamem_pair.c:371-392: an end without a hit, no pair in a proper
+// orientation and distance, a best pair that scores nothing, an end with several primary hits of at least T) is decided too, instead of
+// PW_HOST_NO_PAIR / _SCORE / _SUPP: wstatus[t] = PW_DECIDED_LINES, LN.n_lines[2t + e] = the lines of end e (0: the unaligned record,
+// which has no descriptor; up to SE_LINES_CAP, more leave the pair with PW_HOST_SUPP), line j of end e in slot
+// x = (2t + e) * SE_LINES_CAP + j of LN.desc / LN.reqs / LN.xa_cnt with its XA requests at LN.xa_reqs[x * PW_XA_CAP ..].  desc.flag =
+// 0x40 << e | 1, | 2 when the two top hits make a proper pair (:382-387), | LN.supp_flag behind the first line, the XA count in bits
+// 16-19; desc.req counts from the pair's first request: [end 0: line 0, its XA entries, line 1, ...; end 1: ...]; reqs.read = 2 work[t] + e.
+// reqs / desc / xa_cnt [2t + e] are not written for such a pair.  LN.xa_reqs = nullptr: a line with XA entries gives PW_HOST_XA.
 __global__ void __launch_bounds__(64)
 pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const DevReg *__restrict__ lists, const int *__restrict__ loff,
                  const int *__restrict__ len, const MswReq *__restrict__ mreq, const MswRes *__restrict__ mres, const unsigned *__restrict__ mfirst,
                  const short *__restrict__ tags, const int *__restrict__ toff, const i64 *__restrict__ ann_off, const double *__restrict__ ptab,
                  const double *__restrict__ ltab, uint8_t *__restrict__ wstatus, AlnReq *__restrict__ reqs, SamDesc *__restrict__ desc,
-                 AlnReq *__restrict__ xa_reqs, uint8_t *__restrict__ xa_cnt)
+                 AlnReq *__restrict__ xa_reqs, uint8_t *__restrict__ xa_cnt, SeLines LN)
 {
 	__shared__ WList L[2];
 	__shared__ Pair64 V[2 * PW_MAXREG];
@@ -196,137 +207,176 @@ pair_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const D
 			}
 		}
 	}
-	if (n[0] == 0 || n[1] == 0) PW_GIVE_UP(PW_HOST_NO_PAIR);   // (n_pri = 0: the ends are reported independently)
-
 	const u64 id = P.id0 + (u64)k;
-	if (!pw_mark_primary(P, L[0], n[0], id << 1 | 0, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
-	if (!pw_mark_primary(P, L[1], n[1], id << 1 | 1, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
-
-	// ---- mem_pair (src/bwamem_pair.c:182-243) ----
-	const int nv = n[0] + n[1];
+	int why = PW_HOST_NO_PAIR;   // which of mem_sam_pe's exits to no_pairing: the pair takes (the code it has without the side arrays)
+	bool marked = false;
+	if (n[0] == 0 || n[1] == 0) goto no_pairing;   // (n_pri = 0: the ends are reported independently)
 	{
-		Pair64 key[2];
-		for (int r = 0; r < 2; ++r)
-			if (lane < n[r]) {
-				const int rid = L[r].rid[lane];
-				key[r] = pair_key(P.l_pac, L[r].rb[lane], rid, ann_off[rid], L[r].score[lane], lane, r);
-				V[r * n[0] + lane] = key[r];
+		if (!pw_mark_primary(P, L[0], n[0], id << 1 | 0, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
+		if (!pw_mark_primary(P, L[1], n[1], id << 1 | 1, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
+		marked = true;
+
+		// ---- mem_pair (src/bwamem_pair.c:182-243) ----
+		const int nv = n[0] + n[1];
+		{
+			Pair64 key[2];
+			for (int r = 0; r < 2; ++r)
+				if (lane < n[r]) {
+					const int rid = L[r].rid[lane];
+					key[r] = pair_key(P.l_pac, L[r].rb[lane], rid, ann_off[rid], L[r].score[lane], lane, r);
+					V[r * n[0] + lane] = key[r];
+				}
+			__syncthreads();
+			int rank[2] = {0, 0};
+			for (int j = 0; j < nv; ++j) {   // (unique keys: the rank is the place in the reference's sorted array)
+				const Pair64 o = V[j];
+				if (lane < n[0] && pair_lt(o, key[0])) ++rank[0];
+				if (lane < n[1] && pair_lt(o, key[1])) ++rank[1];
 			}
-		__syncthreads();
-		int rank[2] = {0, 0};
-		for (int j = 0; j < nv; ++j) {   // (unique keys: the rank is the place in the reference's sorted array)
-			const Pair64 o = V[j];
-			if (lane < n[0] && pair_lt(o, key[0])) ++rank[0];
-			if (lane < n[1] && pair_lt(o, key[1])) ++rank[1];
+			__syncthreads();
+			for (int r = 0; r < 2; ++r)
+				if (lane < n[r]) V[rank[r]] = key[r];
+			__syncthreads();
 		}
-		__syncthreads();
-		for (int r = 0; r < 2; ++r)
-			if (lane < n[r]) V[rank[r]] = key[r];
-		__syncthreads();
-	}
-	const int idi = pair_id_mix(id);
-	// u is not stored: its maximum under (x, y), the second-largest score and n_sub are reductions
-	Pair64 best;
-	best.x = best.y = 0;
-	int cnt = 0, q2 = -1;   // of this lane's candidates: how many, the best, the largest score among the others
-	for (int i = lane; i < nv; i += 64)
-		pw_pairs_of(P, V, i, idi, ptab, [&](const Pair64 &p) {
-			if (cnt == 0) best = p;
-			else if (pair_lt(best, p)) { const int qb_ = (int)(best.x >> 32); q2 = q2 > qb_ ? q2 : qb_; best = p; }
-			else { const int qp = (int)(p.x >> 32); q2 = q2 > qp ? q2 : qp; }
-			++cnt;
-		});
-	const int nu = wave_sum(cnt);
-	if (nu == 0) PW_GIVE_UP(PW_HOST_NO_PAIR);   // no pair in a proper orientation and distance
-	const u64 gx = wave_maxu(cnt ? best.x : 0);
-	const bool top_x = cnt && best.x == gx;
-	const u64 gy = wave_maxu(top_x ? best.y : 0);   // (several candidates can share x; y = (kk, i) is unique)
-	const bool mine = top_x && best.y == gy;
-	int subo = (int)wave_max((i64)(mine ? q2 : cnt ? (int)(best.x >> 32) : -1));
-	if (nu < 2) subo = 0;
-	const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
-	int n_sub = 0;
-	if (nu > 1) {
-		int c2 = 0;
+		const int idi = pair_id_mix(id);
+		// u is not stored: its maximum under (x, y), the second-largest score and n_sub are reductions
+		Pair64 best;
+		best.x = best.y = 0;
+		int cnt = 0, q2 = -1;   // of this lane's candidates: how many, the best, the largest score among the others
 		for (int i = lane; i < nv; i += 64)
 			pw_pairs_of(P, V, i, idi, ptab, [&](const Pair64 &p) {
-				if (!(p.x == gx && p.y == gy) && subo - (int)(p.x >> 32) <= tmp) ++c2;
+				if (cnt == 0) best = p;
+				else if (pair_lt(best, p)) { const int qb_ = (int)(best.x >> 32); q2 = q2 > qb_ ? q2 : qb_; best = p; }
+				else { const int qp = (int)(p.x >> 32); q2 = q2 > qp ? q2 : qp; }
+				++cnt;
 			});
-		n_sub = wave_sum(c2);
-	}
-	int z[2];
-	{
-		const int i = (int)(gy >> 32), kk = (int)(gy << 32 >> 32);
-		const Pair64 vi = V[i], vk = V[kk];
-		z[vi.y & 1] = (int)(vi.y << 32 >> 34);
-		z[vk.y & 1] = (int)(vk.y << 32 >> 34);
-	}
-	const int o = (int)(gx >> 32);
-	if (o <= 0) PW_GIVE_UP(PW_HOST_SCORE);
-
-	// ---- is_multi, q_pe, q_se, the caps, the swap (:289-339); every lane computes the same numbers ----
-	for (int e = 0; e < 2; ++e)   // an end with several good primary hits is left to the single-end logic
-		if (__ballot(lane >= 1 && lane < n[e] && L[e].secondary[lane] < 0 && L[e].score[lane] >= P.T)) PW_GIVE_UP(PW_HOST_SUPP);
-	const int score_un = L[0].score[0] + L[1].score[0] - P.pen_unpaired;
-	if (n_sub >= 40) PW_GIVE_UP(PW_HOST_LENGTH);   // (beyond the table of (int)(4.343 * log(n + 1) + .499), whose entry 0 is 0)
-	const int q_pe = mapq_pe(o, subo, score_un, P.lnq[n_sub], P.a, L[0].frac_rep[0], L[1].frac_rep[0]);
-	int q_se[2], extra_flag = 1, sub_z[2];
-	const bool pair_wins = o > score_un;
-	if (!pair_wins) z[0] = z[1] = 0;
-	for (int e = 0; e < 2; ++e) {
-		const WReg c = wl_get(L[e], z[e]);
-		int sub = c.sub;
-		if (pair_wins && c.secondary >= 0) sub = L[e].score[c.secondary];   // (c.secondary = -2 in the reference: it is not read again)
-		sub_z[e] = sub;
-		const int l = c.qe - c.qb > c.re - c.rb ? c.qe - c.qb : (int)(c.re - c.rb);
-		if (l >= P.ltab_n || l <= 0 || c.sub_n >= 40) PW_GIVE_UP(PW_HOST_LENGTH);
-		q_se[e] = mapq_se_of(P, c.score, sub, c.sub_n, c.csub, l, c.frac_rep, ltab);
-		if (pair_wins) q_se[e] = mapq_se_in_pair(q_se[e], q_pe, c.score, c.csub, P.a);
-	}
-	if (pair_wins) extra_flag |= 2;
-	__syncthreads();
-	for (int e = 0; e < 2; ++e) {   // the chosen hit was secondary: swap roles with its parent
-		const int kk = L[e].secondary_all[z[e]];
-		__syncthreads();
-		if (kk >= 0 && kk < n[e]) {
-			if (lane < n[e] && (L[e].secondary_all[lane] == kk || lane == kk)) L[e].secondary_all[lane] = z[e];
-			__syncthreads();
-			if (lane == 0) L[e].secondary_all[z[e]] = -1;
-			__syncthreads();
+		const int nu = wave_sum(cnt);
+		if (nu == 0) goto no_pairing;   // no pair in a proper orientation and distance
+		const u64 gx = wave_maxu(cnt ? best.x : 0);
+		const bool top_x = cnt && best.x == gx;
+		const u64 gy = wave_maxu(top_x ? best.y : 0);   // (several candidates can share x; y = (kk, i) is unique)
+		const bool mine = top_x && best.y == gy;
+		int subo = (int)wave_max((i64)(mine ? q2 : cnt ? (int)(best.x >> 32) : -1));
+		if (nu < 2) subo = 0;
+		const int tmp = sub_n_margin(P.a, P.b, P.o_del, P.e_del, P.o_ins, P.e_ins);
+		int n_sub = 0;
+		if (nu > 1) {
+			int c2 = 0;
+			for (int i = lane; i < nv; i += 64)
+				pw_pairs_of(P, V, i, idi, ptab, [&](const Pair64 &p) {
+					if (!(p.x == gx && p.y == gy) && subo - (int)(p.x >> 32) <= tmp) ++c2;
+				});
+			n_sub = wave_sum(c2);
 		}
+		int z[2];
+		{
+			const int i = (int)(gy >> 32), kk = (int)(gy << 32 >> 32);
+			const Pair64 vi = V[i], vk = V[kk];
+			z[vi.y & 1] = (int)(vi.y << 32 >> 34);
+			z[vk.y & 1] = (int)(vk.y << 32 >> 34);
+		}
+		const int o = (int)(gx >> 32);
+		if (o <= 0) { why = PW_HOST_SCORE; goto no_pairing; }
+
+		// ---- is_multi, q_pe, q_se, the caps, the swap (:289-339); every lane computes the same numbers ----
+		for (int e = 0; e < 2; ++e)   // an end with several good primary hits is left to the single-end logic
+			if (__ballot(lane >= 1 && lane < n[e] && L[e].secondary[lane] < 0 && L[e].score[lane] >= P.T)) { why = PW_HOST_SUPP; goto no_pairing; }
+		const int score_un = L[0].score[0] + L[1].score[0] - P.pen_unpaired;
+		if (n_sub >= 40) PW_GIVE_UP(PW_HOST_LENGTH);   // (beyond the table of (int)(4.343 * log(n + 1) + .499), whose entry 0 is 0)
+		const int q_pe = mapq_pe(o, subo, score_un, P.lnq[n_sub], P.a, L[0].frac_rep[0], L[1].frac_rep[0]);
+		int q_se[2], extra_flag = 1, sub_z[2];
+		const bool pair_wins = o > score_un;
+		if (!pair_wins) z[0] = z[1] = 0;
+		for (int e = 0; e < 2; ++e) {
+			const WReg c = wl_get(L[e], z[e]);
+			int sub = c.sub;
+			if (pair_wins && c.secondary >= 0) sub = L[e].score[c.secondary];   // (c.secondary = -2 in the reference: it is not read again)
+			sub_z[e] = sub;
+			const int l = c.qe - c.qb > c.re - c.rb ? c.qe - c.qb : (int)(c.re - c.rb);
+			if (l >= P.ltab_n || l <= 0 || c.sub_n >= 40) PW_GIVE_UP(PW_HOST_LENGTH);
+			q_se[e] = mapq_se_of(P, c.score, sub, c.sub_n, c.csub, l, c.frac_rep, ltab);
+			if (pair_wins) q_se[e] = mapq_se_in_pair(q_se[e], q_pe, c.score, c.csub, P.a);
+		}
+		if (pair_wins) extra_flag |= 2;
+		__syncthreads();
+		for (int e = 0; e < 2; ++e) {   // the chosen hit was secondary: swap roles with its parent
+			const int kk = L[e].secondary_all[z[e]];
+			__syncthreads();
+			if (kk >= 0 && kk < n[e]) {
+				if (lane < n[e] && (L[e].secondary_all[lane] == kk || lane == kk)) L[e].secondary_all[lane] = z[e];
+				__syncthreads();
+				if (lane == 0) L[e].secondary_all[z[e]] = -1;
+				__syncthreads();
+			}
+		}
+		// ---- the XA entries of the two chosen hits and their requests (wave_common.cuh: pw_xa_list) ----
+		int n_xa[2];
+		for (int e = 0; e < 2; ++e) {
+			n_xa[e] = pw_xa_list(P, L[e], n[e], z[e], 2 * k + e, xa_reqs ? xa_reqs + (size_t)(2 * t + e) * PW_XA_CAP : nullptr, lane);
+			if (n_xa[e] < 0) PW_GIVE_UP(PW_HOST_XA);
+		}
+		if (lane < 2) {
+			const int e = lane;
+			const WReg R = wl_get(L[e], z[e]);
+			const int w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);   // (a rescued hit has w = 0)
+			AlnReq q;
+			q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = 0;
+			reqs[2 * t + e] = q;
+			SamDesc d;
+			d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = e ? 1 + n_xa[0] : 0; d.rid = R.rid;
+			d.flag = 0x40 << e | extra_flag | n_xa[e] << SAM_XA_SHIFT; d.mapq = q_se[e] & 0xff; d.score = R.score;
+			d.sub = sub_z[e] > R.csub ? sub_z[e] : R.csub;   // mem_reg2aln: sub = max(sub, csub)
+			desc[2 * t + e] = d;
+			if (xa_cnt) xa_cnt[2 * t + e] = (uint8_t)n_xa[e];
+		}
+		if (lane == 0) wstatus[t] = n_xa[0] + n_xa[1] ? PW_DECIDED_XA : PR_DECIDED;
+		return;
 	}
-	// ---- the XA entries of the two chosen hits and their requests (wave_common.cuh: pw_xa_list) ----
-	int n_xa[2];
+
+no_pairing:
+	// ---- no_pairing: (src/bwamem_pair.c:371-392): each end goes through mem_reg2sam with the other end's top hit as its mate ----
+	if (!LN.desc) PW_GIVE_UP(why);
+	if (!marked)
+		for (int e = 0; e < 2; ++e)   // (an empty list is marked at once)
+			if (!pw_mark_primary(P, L[e], n[e], id << 1 | e, V, lane)) PW_GIVE_UP(PW_HOST_TIE);
+	u64 lines[2];
+	int nl[2];
+	for (int e = 0; e < 2; ++e) {   // the lines of mem_reg2sam (src/bwamem.c:1015-1032) without MEM_F_ALL: the primary hits of at least T
+		lines[e] = __ballot(lane < n[e] && L[e].secondary[lane] < 0 && L[e].score[lane] >= P.T);
+		nl[e] = __popcll(lines[e]);
+		if (nl[e] > SE_LINES_CAP) PW_GIVE_UP(PW_HOST_SUPP);
+	}
+	int extra_flag = 1;
+	// :382-387: both ends have a top hit of at least T (hit 0 of a marked list scores most), on one contig and at a proper distance
+	if ((lines[0] & lines[1] & 1) && L[0].rid[0] == L[1].rid[0]) {
+		int64_t dist;
+		const int d = infer_dir(P.l_pac, L[0].rb[0], L[1].rb[0], &dist);
+		if (!P.failed[d] && dist >= P.low[d] && dist <= P.high[d]) extra_flag |= 2;
+	}
+	int at = 0;   // the pair's requests: [end 0: line 0, its XA entries, line 1, ...; end 1: ...]
 	for (int e = 0; e < 2; ++e) {
-		n_xa[e] = pw_xa_list(P, L[e], n[e], z[e], 2 * k + e, xa_reqs ? xa_reqs + (size_t)(2 * t + e) * PW_XA_CAP : nullptr, lane);
-		if (n_xa[e] < 0) PW_GIVE_UP(PW_HOST_XA);
+		if (!nl[e]) continue;   // the unaligned record (:1033-1037) has neither request nor descriptor: it is the writer's
+		const int r = wave_lines<true>(P, LN, L[e], n[e], lines[e], nl[e], 2 * k + e, (size_t)(2 * t + e) * SE_LINES_CAP, at, 0x40 << e | extra_flag, ltab, lane);
+		if (r == -1) PW_GIVE_UP(PW_HOST_XA);
+		if (r < 0) PW_GIVE_UP(PW_HOST_LENGTH);
+		at += r;
 	}
-	if (lane < 2) {
-		const int e = lane;
-		const WReg R = wl_get(L[e], z[e]);
-		const int w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);   // (a rescued hit has w = 0)
-		AlnReq q;
-		q.rb = R.rb; q.re = R.re; q.read = 2 * k + e; q.qb = R.qb; q.qe = R.qe; q.w2 = w2; q.truesc = R.truesc; q.pad = 0;
-		reqs[2 * t + e] = q;
-		SamDesc d;
-		d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = e ? 1 + n_xa[0] : 0; d.rid = R.rid;
-		d.flag = 0x40 << e | extra_flag | n_xa[e] << SAM_XA_SHIFT; d.mapq = q_se[e] & 0xff; d.score = R.score;
-		d.sub = sub_z[e] > R.csub ? sub_z[e] : R.csub;   // mem_reg2aln: sub = max(sub, csub)
-		desc[2 * t + e] = d;
-		if (xa_cnt) xa_cnt[2 * t + e] = (uint8_t)n_xa[e];
-	}
-	if (lane == 0) wstatus[t] = n_xa[0] + n_xa[1] ? PW_DECIDED_XA : PR_DECIDED;
+	if (lane < 2) LN.n_lines[2 * t + lane] = (uint8_t)(lane ? nl[1] : nl[0]);
+	if (lane == 0) wstatus[t] = PW_DECIDED_LINES;
 }
 
 void launch_pair_wave(void *stream, const PairParams &P, int n_work, const int *d_work, const DevReg *d_lists, const int *d_loff, const int *d_len,
                       const MswReq *d_mreq, const MswRes *d_mres, const unsigned *d_mfirst, const short *d_tags, const int *d_toff,
                       const int64_t *d_ann_off, const double *d_ptab, const double *d_ltab, uint8_t *d_wstatus, AlnReq *d_reqs, SamDesc *d_desc,
-                      AlnReq *d_xa_reqs, uint8_t *d_xa_cnt)
+                      AlnReq *d_xa_reqs, uint8_t *d_xa_cnt, const SeLines *lines)
 {
 	if (n_work <= 0) return;
 	if (!d_xa_cnt || P.max_XA_hits > PW_XA_CAP) d_xa_reqs = nullptr, d_xa_cnt = nullptr;   // (XA off: the kernel as it was)
+	SeLines LN;   // (no side arrays: the pairs of no_pairing: are the host's, as they were)
+	if (lines && lines->desc && lines->reqs && lines->n_lines && lines->xa_cnt) LN = *lines;
+	if (P.max_XA_hits > PW_XA_CAP) LN.xa_reqs = nullptr;
 	hipLaunchKernelGGL(pair_wave_kernel, dim3(n_work), dim3(64), 0, (hipStream_t)stream, P, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst,
-	                   d_tags, d_toff, (const i64 *)d_ann_off, d_ptab, d_ltab, d_wstatus, d_reqs, d_desc, d_xa_reqs, d_xa_cnt);
+	                   d_tags, d_toff, (const i64 *)d_ann_off, d_ptab, d_ltab, d_wstatus, d_reqs, d_desc, d_xa_reqs, d_xa_cnt, LN);
 }
 
 // the decided pairs' requests and descriptors into the chunk-wide arrays the CIGAR-and-SAM job reads

@@ -387,6 +387,8 @@ struct Part {
 	int n_wave_dec = 0;
 	Job wave;                         // the job of the pairs it decided, when they do not ride in `dev`
 	const uint8_t *wxcnt = nullptr;   // XA entries per (work item, end), with the status bytes
+	const uint8_t *wnlines = nullptr, *wlxcnt = nullptr;   // (dev_pair_lines) lines per (work item, end); XA entries per (work item, end, line)
+	int n_lines_dec = 0;              // the pairs it decided end by end (PW_DECIDED_LINES): they ride in the job of the XA pairs
 	int n_xa_dec = 0;                 // the pairs it decided with an XA tag, their request bases (per unit of the part) and their job
 	std::vector<uint32_t> xa_base;
 	Job xa;
@@ -455,6 +457,9 @@ struct Call {
 	bool dev_units = false;              // at least one unit is the device's (ustat[k] = *_DECIDED: its requests and descriptors exist there)
 	bool dev_wave = false;               // pair_wave_kernel takes the pairs pair_simple_kernel leaves for rescue / long lists
 	bool dev_xa = false;                 // ... and the ones it leaves for an XA tag; it lists the tag's entries (MPIBWA_HOST_XA=1: off)
+	bool dev_pair_lines = false;         // ... and the ones mem_sam_pe reports end by end (MPIBWA_HOST_PAIR_LINES=1: off)
+	uint64_t n_pair_lines = 0;           // decided that way
+	std::atomic<unsigned long long> n_pair_lines_sam{0};   // ... whose text was taken from the device
 	uint64_t n_xa_pairs = 0;             // decided with an XA tag, or handed over for the XA test alone and decided without one
 	uint64_t n_xa_plain = 0;             // (the latter: status PR_DECIDED, riding with the wave's other pairs)
 	std::vector<uint8_t> wave_cand, wave_dec;   // per pair: handed to pair_wave_kernel; decided by it

@@ -1,6 +1,7 @@
 // sam_common.cuh — what the two SAM text kernels share (sam_kernel.hip: sam_emit_kernel, records of one line, a lane per record;
 // sam_lines_kernel.hip: records of several lines, a wavefront per read): the alignment fields of a line as mem_reg2aln leaves them
-// (src/bwamem.c:1123-1157), the lane's byte sink, the numbers of an XA entry (src/bwamem_extra.c:122-129) and the lane broadcast.
+// (src/bwamem.c:1123-1157), the lane's byte sink, TLEN (src/bwamem.c:861-865), the numbers of an XA entry (src/bwamem_extra.c:122-129)
+// and the lane broadcast.
 #ifndef MBW_SAM_COMMON_CUH
 #define MBW_SAM_COMMON_CUH
 #include <hip/hip_runtime.h>
@@ -94,6 +95,14 @@ struct Sink {
 		if (a.clip3) { num32(a.clip3); ch('S'); }
 	}
 };
+
+// TLEN of a line p whose mate m lies on the same contig (src/bwamem.c:861-865); n_p, n_m: the operations of the two CIGARs as printed
+__device__ __forceinline__ void sam_tlen(Sink &S, const SamAln &p, int n_p, const SamAln &m, int n_m)
+{
+	const long long p0 = p.pos + (p.is_rev ? p.rlen - 1 : 0), p1 = m.pos + (m.is_rev ? m.rlen - 1 : 0);
+	if (n_m == 0 || n_p == 0) S.ch('0');
+	else S.num(-(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
+}
 
 // XA entry j of the line D (its request follows the line's own): the alignment as mem_reg2aln leaves it, clips as S
 __device__ __forceinline__ SamAln xa_aln(const SamDesc &D, int j, const AlnReq *__restrict__ reqs, const AlnHdr *__restrict__ hdr, const uint8_t *__restrict__ pool,

@@ -97,11 +97,8 @@ sam_emit_kernel(SamParams P, int n_reads, const SamDesc *__restrict__ desc, cons
 						else { mn_at = ann_name_off[m.rid]; mn_len = ann_name_off[m.rid + 1] - mn_at; }
 						e_b = S.len;
 						S.ch('\t'); S.num(m.pos + 1); S.ch('\t');
-						if (p.rid == m.rid) {
-							const long long p0 = p.pos + (p.is_rev ? p.rlen - 1 : 0), p1 = m.pos + (m.is_rev ? m.rlen - 1 : 0);
-							if (n_m == 0 || n_p == 0) S.ch('0');
-							else S.num(-(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
-						} else S.ch('0');
+						if (p.rid == m.rid) sam_tlen(S, p, n_p, m, n_m);
+						else S.ch('0');
 						S.ch('\t');
 					} else {
 						S.ch('*');

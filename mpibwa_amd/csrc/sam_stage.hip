@@ -143,7 +143,7 @@ void Call::mcollect(Part &P)
 	std::vector<std::vector<MswReqH>> blk_req(n_blk);
 	std::vector<uint32_t> u_first(nu), u_cnt(nu);
 	// (dev_wave: the pairs pair_simple_kernel left for rescue, long lists or an end without a hit also get their tags, and are pair_wave_kernel's;
-	// dev_xa: the ones it left for an XA tag too)
+	// dev_xa: the ones it left for an XA tag too; dev_pair_lines: and the ones it left for no_pairing:, codes 8 / 9 / 10)
 	std::vector<std::vector<int16_t>> blk_tag(dev_wave ? n_blk : 0);
 	std::vector<std::vector<int>> blk_work(dev_wave ? n_blk : 0);   // (pair, first tag in blk_tag) ...
 	parallel_for(n_thr, n_blk, 1, [&](int blk) {
@@ -154,8 +154,9 @@ void Call::mcollect(Part &P)
 			const size_t before = rq.size();
 			if (!(dev_units && ustat[i] == PR_DECIDED)) {
 				const bseq1_t *s = &seqs[i << 1];
-				const bool cand = dev_wave && (ustat[i] == PR_HOST_MAXREG || ustat[i] == PR_HOST_RESCUE || ustat[i] == PR_HOST_NO_HIT || (dev_xa && ustat[i] == PR_HOST_XA)) && !s[0].comment && !s[1].comment &&
-				                  strcmp(s[0].name, s[1].name) == 0 && pair_wave_eligible(&regs[i << 1], PW_MAXREG);
+				const bool cand = dev_wave && (ustat[i] == PR_HOST_MAXREG || ustat[i] == PR_HOST_RESCUE || ustat[i] == PR_HOST_NO_HIT || (dev_xa && ustat[i] == PR_HOST_XA) ||
+				                               (dev_pair_lines && (ustat[i] == PR_HOST_NO_PAIR || ustat[i] == PR_HOST_SCORE || ustat[i] == PR_HOST_SUPP))) &&
+				                  !s[0].comment && !s[1].comment && strcmp(s[0].name, s[1].name) == 0 && pair_wave_eligible(&regs[i << 1], PW_MAXREG, dev_pair_lines);
 				if (cand) {
 					blk_work[blk].push_back(i); blk_work[blk].push_back((int)blk_tag[blk].size());
 					sam_pe_msw_collect_tagged(opt, bns, pes, s, &regs[i << 1], i << 1, MSW_MAX_T, rq, blk_tag[blk]);
@@ -242,7 +243,8 @@ static void pack_list(const HRegV &v, DevReg *o)
 // A wave kernel's work list on stream wst: `ends` region lists per item — the host's own (after mem_sort_dedup_patch), packed with
 // offsets —, status bytes and (xa) XA counts cleared, room for the kernel's requests, descriptors and XA requests (PW_XA_CAP per
 // (item, end)).  more: what else the kernel reads per item, uploaded behind the lists and before the clears.
-// lines (se_wave_kernel): the side arrays for reads of several lines, SE_LINES_CAP slots per item, line counts cleared.
+// lines: the side arrays by line (se_wave_kernel's reads of several lines, pair_wave_kernel's pairs reported end by end), SE_LINES_CAP
+// slots per list, line counts cleared.
 Call::WaveList Call::wave_list(WaveBufs &B, hipStream_t wst, int ends, const std::vector<int> &items, bool xa, std::initializer_list<Upload> more, bool lines)
 {
 	const int nw = (int)items.size(), nl = ends * nw;   // items, lists
@@ -280,16 +282,16 @@ Call::WaveList Call::wave_list(WaveBufs &B, hipStream_t wst, int ends, const std
 	}
 	L.h_nlines = L.h_lxcnt = nullptr;
 	if (lines) {
-		const size_t ns = (size_t)nw * SE_LINES_CAP;   // line slots
-		L.lines.n_lines = (uint8_t *)B.nlines.ensure(roomy((size_t)nw + 64));
+		const size_t ns = (size_t)nl * SE_LINES_CAP;   // line slots
+		L.lines.n_lines = (uint8_t *)B.nlines.ensure(roomy((size_t)nl + 64));
 		L.lines.desc = (SamDesc *)B.ldesc.ensure(roomy(ns * sizeof(SamDesc)));
 		L.lines.reqs = (AlnReq *)B.lreq.ensure(roomy(ns * sizeof(AlnReq)));
 		L.lines.xa_cnt = (uint8_t *)B.lxcnt.ensure(roomy(ns + 64));
 		L.lines.xa_reqs = xa ? (AlnReq *)B.lxreq.ensure(roomy(ns * PW_XA_CAP * sizeof(AlnReq))) : nullptr;
-		L.h_nlines = (uint8_t *)B.h_nlines.ensure(roomy((size_t)nw + 64));
+		L.h_nlines = (uint8_t *)B.h_nlines.ensure(roomy((size_t)nl + 64));
 		L.h_lxcnt = (uint8_t *)B.h_lxcnt.ensure(roomy(ns + 64));
 		se_lines_options(opt, L.lines);
-		HIP_OK(hipMemsetAsync(L.lines.n_lines, 0, (size_t)nw, wst));
+		HIP_OK(hipMemsetAsync(L.lines.n_lines, 0, (size_t)nl, wst));
 		HIP_OK(hipMemsetAsync(L.lines.xa_cnt, 0, ns, wst));
 	}
 	return L;
@@ -315,12 +317,16 @@ void Call::wave_launch(Part &P)
 	const MswReq *d_req = (const MswReq *)W.mreq[s].ensure(std::max<size_t>(P.n_mreq, 1) * sizeof(MswReq));
 	const MswRes *d_res = (const MswRes *)W.mres[s].ensure(std::max<size_t>(P.n_mreq, 1) * sizeof(MswRes));
 	const WaveList L = wave_list(B, P.mst, 2, P.work, dev_xa,
-	                             {{d_mf, hm, (size_t)nw * 4}, {d_toff, ht, (size_t)(nw + 1) * 4}, {d_tags, hg, P.w_tags.size() * 2}});
+	                             {{d_mf, hm, (size_t)nw * 4}, {d_toff, ht, (size_t)(nw + 1) * 4}, {d_tags, hg, P.w_tags.size() * 2}}, dev_pair_lines);
 	launch_pair_wave(P.mst, wave_pp, nw, L.work, L.lists, L.loff, D.d_len, d_req, d_res, d_mf, d_tags, d_toff, D.d_ann_off, d_wave_tab, d_wave_tab + wave_n_tab,
-	                 L.status, L.req, L.desc, L.xreq, L.xcnt);
+	                 L.status, L.req, L.desc, L.xreq, L.xcnt, dev_pair_lines ? &L.lines : nullptr);
 	HIP_OK(hipMemcpyAsync(L.h_status, L.status, (size_t)nw, hipMemcpyDeviceToHost, P.mst));
 	if (dev_xa) HIP_OK(hipMemcpyAsync(L.h_xcnt, L.xcnt, (size_t)2 * nw, hipMemcpyDeviceToHost, P.mst));
-	P.wstatus = L.h_status; P.wxcnt = L.h_xcnt;
+	if (dev_pair_lines) {
+		HIP_OK(hipMemcpyAsync(L.h_nlines, L.lines.n_lines, (size_t)2 * nw, hipMemcpyDeviceToHost, P.mst));
+		HIP_OK(hipMemcpyAsync(L.h_lxcnt, L.lines.xa_cnt, (size_t)2 * nw * SE_LINES_CAP, hipMemcpyDeviceToHost, P.mst));
+	}
+	P.wstatus = L.h_status; P.wxcnt = L.h_xcnt; P.wnlines = L.h_nlines; P.wlxcnt = L.h_lxcnt;
 }
 
 // The units a wave kernel decided with a request count of their own — pair_wave_kernel's pairs with an XA tag (3 to 2 + 2 PW_XA_CAP
@@ -332,32 +338,40 @@ void Call::own_job_records(Part &P, int ends, const WaveBufs &B, const std::vect
 	const int s = P.slot, nw = (int)items.size(), nu = P.hi - P.lo;
 	auto in_job = [&](int t) {
 		const int i = items[t];
-		return ends == 2 ? P.wstatus[t] == PW_DECIDED_XA : i >= P.lo && i < P.hi && wave_dec[i];
+		return ends == 2 ? (P.wstatus[t] == PW_DECIDED_XA && dev_xa) || (P.wstatus[t] == PW_DECIDED_LINES && dev_pair_lines) : i >= P.lo && i < P.hi && wave_dec[i];
 	};
 	// (se_wave_kernel's reads of several lines: a request per line and per XA entry of a line, from the counts that came back with the
 	// status bytes; they ride in the same job, and sam_lines_kernel writes them behind sam_emit_kernel)
-	auto n_lines_of = [&](int t) { return ends == 1 && dev_se_supp && se_wnlines ? (int)std::min<int>(se_wnlines[t], SE_LINES_CAP) : 0; };
+	// (pair_wave_kernel's pairs reported end by end: the same per end, 0 .. SE_LINES_CAP lines each; a pair of two unaligned records has
+	// no request and is a unit of sam_lines_kernel all the same)
+	const bool by_line = ends == 1 ? dev_se_supp && se_wnlines : dev_pair_lines && P.wnlines;
+	const uint8_t *nlines = ends == 1 ? se_wnlines : P.wnlines, *lxcnt = ends == 1 ? se_wlxcnt : P.wlxcnt;
+	auto lines_unit = [&](int t) { return by_line && (ends == 1 ? nlines[t] > 0 : P.wstatus[t] == PW_DECIDED_LINES); };
+	auto n_lines_of = [&](int x) { return (int)std::min<int>(nlines[x], SE_LINES_CAP); };   // x: the list, ends * t + e
 	P.xa_base.assign(nu + 1, 0);
 	int n_dec = 0, n_multi = 0;
 	for (int t = 0; t < nw; ++t) {
 		if (!in_job(t)) continue;
-		const int nl = n_lines_of(t);
-		for (int j = 0; j < nl; ++j) P.xa_base[items[t] - P.lo + 1] += 1 + std::min<int>(se_wlxcnt[(size_t)t * SE_LINES_CAP + j], PW_XA_CAP);
-		for (int e = 0; e < ends && !nl; ++e) P.xa_base[items[t] - P.lo + 1] += 1 + (xcnt ? std::min<int>(xcnt[ends * t + e], PW_XA_CAP) : 0);
+		const bool lu = lines_unit(t);
+		for (int e = 0; e < ends; ++e) {
+			const int x = ends * t + e;
+			if (!lu) { P.xa_base[items[t] - P.lo + 1] += 1 + (xcnt ? std::min<int>(xcnt[x], PW_XA_CAP) : 0); continue; }
+			for (int j = 0; j < n_lines_of(x); ++j) P.xa_base[items[t] - P.lo + 1] += 1 + std::min<int>(lxcnt[(size_t)x * SE_LINES_CAP + j], PW_XA_CAP);
+		}
 		++n_dec;
-		n_multi += nl > 0;
+		n_multi += lu;
 	}
 	if (n_dec == 0) return;
 	hipStream_t jst = C.d_streams[s];
 	for (int k = 0; k < nu; ++k) P.xa_base[k + 1] += P.xa_base[k];
 	int *dst = (int *)W.wave[s].h_dst.ensure(roomy((size_t)nw * 4 + 64));   // (the part's: se_wave_kernel's one list serves both parts)
-	for (int t = 0; t < nw; ++t) dst[t] = in_job(t) && !n_lines_of(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
+	for (int t = 0; t < nw; ++t) dst[t] = in_job(t) && !lines_unit(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
 	const size_t n_req = P.xa_base[nu];
 	int *d_dst = (int *)W.wave[s].dst.ensure(roomy((size_t)nw * 4));
 	int *d_ldst = nullptr;
 	if (n_multi) {
 		int *ldst = (int *)W.wave[s].h_ldst.ensure(roomy((size_t)nw * 4 + 64));
-		for (int t = 0; t < nw; ++t) ldst[t] = in_job(t) && n_lines_of(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
+		for (int t = 0; t < nw; ++t) ldst[t] = in_job(t) && lines_unit(t) ? (int)P.xa_base[items[t] - P.lo] : -1;
 		d_ldst = (int *)W.wave[s].ldst.ensure(roomy((size_t)nw * 4));
 		HIP_OK(hipMemcpyAsync(d_ldst, ldst, (size_t)nw * 4, hipMemcpyHostToDevice, C.d_streams[s]));
 	}
@@ -367,7 +381,7 @@ void Call::own_job_records(Part &P, int ends, const WaveBufs &B, const std::vect
 	launch_wave_job_scatter(jst, ends, nw, (const int *)B.work.p, d_dst, (const AlnReq *)B.req.p, (const SamDesc *)B.desc.p, xcnt ? (const AlnReq *)B.xreq.p : nullptr,
 	                        xcnt ? (const uint8_t *)B.xcnt.p : nullptr, d_rq, d_ds, ends * P.lo, ends * nu);
 	if (n_multi)
-		launch_lines_job_scatter(jst, nw, d_ldst, (const uint8_t *)B.nlines.p, (const AlnReq *)B.lreq.p, (const uint8_t *)B.lxcnt.p, (const AlnReq *)B.lxreq.p, d_rq);
+		launch_lines_job_scatter(jst, ends, nw, d_ldst, (const uint8_t *)B.nlines.p, (const AlnReq *)B.lreq.p, (const uint8_t *)B.lxcnt.p, (const AlnReq *)B.lxreq.p, d_rq);
 	HIP_OK(hipGetLastError());
 	unsigned long long *small = (unsigned long long *)W.h_small[s].ensure(512);
 	P.xa.small_used = small + 48; P.xa.small_cnt = small + 56;
@@ -453,8 +467,10 @@ void Call::mfinish(Part &P)
 		// come back plain: more than max_XA_hits entries, or entries under a hit that is not the chosen one)
 		if (P.wstatus[t] == PR_DECIDED) { if (ustat[i] == PR_HOST_XA) ++n_plain_from_xa; ustat[i] = PR_DECIDED; wave_dec[i] = 1; ++P.n_wave_dec; }
 		else if (P.wstatus[t] == PW_DECIDED_XA && dev_xa) { ustat[i] = PW_DECIDED_XA; ++P.n_xa_dec; }
+		else if (P.wstatus[t] == PW_DECIDED_LINES && dev_pair_lines) { ustat[i] = PW_DECIDED_LINES; ++P.n_lines_dec; }
 		else if (P.wstatus[t]) ustat[i] = P.wstatus[t];   // (why not: for the statistics line)
 	}
+	n_pair_lines += (uint64_t)P.n_lines_dec;
 	n_wave += (uint64_t)P.n_wave_dec - n_plain_from_xa;
 	n_xa_plain += n_plain_from_xa;
 	n_xa_pairs += (uint64_t)P.n_xa_dec + n_plain_from_xa;
@@ -479,7 +495,7 @@ void Call::collect(Part &P, int round)
 		unsigned long long tsc_plan_blk = 0, tsc_emitc_blk = 0;
 		for (int i = lo; i < hi; ++i) {
 			const int k = i - P.lo;
-			if (dev_units && (ustat[i] == PR_DECIDED || ustat[i] == PW_DECIDED_XA || (!pe && ustat[i] == SE_DECIDED_LINES))) continue;   // decided on the device
+			if (dev_units && (ustat[i] == PR_DECIDED || ustat[i] == PW_DECIDED_XA || ustat[i] == SE_DECIDED_LINES)) continue;   // decided on the device (17 is PW_DECIDED_LINES too)
 			const bool has_msw = P.m_launched && P.mbase[k + 1] != P.mbase[k];   // needs results of the mate-rescue kernel
 			const bool waits = has_msw || (dev_wave && wave_cand[i]);            // ... or pair_wave_kernel's word on whose pair it is
 			if (waits != (round == 1)) continue;
@@ -546,7 +562,7 @@ void Call::job_launch(Job &J, JobBufs &B, hipStream_t jst, const Part &P, const 
 		Q.d_used = (unsigned long long *)B.used.ensure(64);
 		Q.d_ooff = (unsigned long long *)B.ooff.ensure((size_t)nr * 8);
 		Q.d_olen = (int *)B.olen.ensure((size_t)nr * 4);
-		if (multi && n_multi > 0) {   // se_wave_kernel's reads of several lines: a unit per item of its work list, those of this job by ldst >= 0
+		if (multi && n_multi > 0) {   // a wave kernel's units of several lines: a unit per item of its work list, those of this job by ldst >= 0
 			const int s = P.slot;
 			Q.n_multi = n_multi; Q.d_mlist = (const int *)multi->work.p; Q.d_mlines = (const uint8_t *)multi->nlines.p;
 			Q.d_mdesc = (const SamDesc *)multi->ldesc.p; Q.d_mbase = (const int *)W.wave[s].ldst.p;
@@ -676,11 +692,12 @@ void Call::replay(Part &P, int which)
 	// (a single-end chunk without reads of the device's has no pass 0)
 	// per-block counters: a shared atomic bumped once per unit costs more than copying the unit's records
 	if (pe || which != 0 || dev_units) parallel_blocks(n_thr, P.hi - P.lo, pe ? 128 : 256, [&](int, int, int k_lo, int k_hi) {
-		unsigned long long n_dev = 0, n_se_xa_w = 0, n_se_supp_w = 0, tsc = 0;
+		unsigned long long n_dev = 0, n_se_xa_w = 0, n_se_supp_w = 0, n_pair_lines_w = 0, tsc = 0;
 		for (int k = k_lo; k < k_hi; ++k) {
 			const int i = P.lo + k, r = ends * i;   // the unit, its first read
 			// pair_wave_kernel's pair with an XA tag, or se_wave_kernel's read (with or without one): the job of those
-			const bool xa_k = (dev_units && ustat[i] == PW_DECIDED_XA) || (dev_se_wave && wave_dec[i]);
+			const bool lines_k = pe && dev_units && ustat[i] == PW_DECIDED_LINES;   // pair_wave_kernel's pair reported end by end: the same job
+			const bool xa_k = (dev_units && ustat[i] == PW_DECIDED_XA) || lines_k || (dev_se_wave && wave_dec[i]);
 			const bool dev_k = xa_k || (dev_units && ustat[i] == PR_DECIDED);
 			const bool own_k = xa_k || (dev_k && P.wave.launched && wave_dec[i]);   // pair_wave_kernel's pair with the job of its own
 			const Job &J = xa_k ? P.xa : own_k ? P.wave : dev_k ? P.dev : P.host;
@@ -693,6 +710,7 @@ void Call::replay(Part &P, int which)
 				for (int e = 0; e < ends; ++e) take_record(r + e, J, ends * k + e);
 				if (!pe && ustat[i] == SE_DECIDED_XA) ++n_se_xa_w;   // (counted apart: n_sam_dev stays the plain records of n_se_dev)
 				else if (!pe && ustat[i] == SE_DECIDED_LINES) ++n_se_supp_w;   // (its one string holds all the read's lines)
+				else if (lines_k) ++n_pair_lines_w;   // (counted apart too: n_sam_dev stays what it is without the path)
 				else n_dev += ends;
 				if (cpusec_on()) tsc += __builtin_ia32_rdtsc() - tq0;
 				continue;
@@ -715,7 +733,7 @@ void Call::replay(Part &P, int which)
 				reg2sam(opt, bns, pac, &seqs[i], regs[i], 0, 0, gpu_aln && !xa_k ? &ctx : nullptr, i);
 			}
 		}
-		n_sam_dev += n_dev; n_se_xa_sam += n_se_xa_w; n_se_supp_sam += n_se_supp_w; tsc_devcopy += tsc;
+		n_sam_dev += n_dev; n_se_xa_sam += n_se_xa_w; n_se_supp_sam += n_se_supp_w; n_pair_lines_sam += n_pair_lines_w; tsc_devcopy += tsc;
 	});
 	emit_ms += now_ms() - ta;
 	cpu_emit += cpu_sec() - ca;
@@ -753,6 +771,10 @@ void Call::sam_stage()
 	if (dev_wave) { wave_cand.assign(n_units, 0); wave_dec.assign(n_units, 0); }
 	// its XA listing: wherever it runs and the tags fit the kernel's side array.  MPIBWA_HOST_XA=1 turns it off.
 	dev_xa = dev_wave && gpu_sam && wave_pp.max_XA_hits <= PW_XA_CAP && getenv("MPIBWA_HOST_XA") == nullptr;
+	// the pairs reported end by end: wherever it runs and the device writes records; on unless MPIBWA_HOST_PAIR_LINES is set
+	// to something other than 0.  The XA listing of their lines goes with dev_xa.
+	const char *hpl = getenv("MPIBWA_HOST_PAIR_LINES");
+	dev_pair_lines = dev_wave && gpu_sam && !(hpl && atoi(hpl) != 0);
 	for (int p = 0; p < n_parts; ++p) {   // (slot 0: the whole chunk or its first half)
 		parts[p].slot = p;
 		parts[p].lo = p ? n_units / 2 : 0;
@@ -774,7 +796,7 @@ void Call::sam_stage()
 		collect(P, 0); mfinish(P); collect(P, 1);
 		// (the wave's pairs ride in the part's device job when it has not gone out yet, and get a job of their own behind it otherwise)
 		if (dev_wave) wave_records(P, !dev_late);
-		if (dev_xa) own_job_records(P, 2, W.wave[P.slot], P.work, P.wxcnt);
+		if (dev_xa || dev_pair_lines) own_job_records(P, 2, W.wave[P.slot], P.work, dev_xa ? P.wxcnt : nullptr);
 		if (dev_late) launch_dev(P);
 		launch(P);
 	}
@@ -800,7 +822,10 @@ void Call::report_decisions()
 	if (!ustat) return;
 	uint64_t c[32] = {0};
 	for (int k = 0; k < n_units; ++k) ++c[ustat[k] & 31];
-	if (pe) { STAT.n_pair_dev = c[PR_DECIDED] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs; }
+	if (pe) {
+		STAT.n_pair_dev = c[PR_DECIDED] - n_wave - n_xa_plain; STAT.n_pair_wave_dev = n_wave; STAT.n_pair_xa_dev = n_xa_pairs;
+		STAT.n_pair_lines_dev = n_pair_lines; STAT.n_pair_lines_sam_dev = n_pair_lines_sam.load();
+	}
 	else {
 		STAT.n_se_dev = c[SE_DECIDED]; STAT.n_se_wave_dev = n_se_wave; STAT.n_se_xa_dev = c[SE_DECIDED_XA]; STAT.n_se_xa_sam_dev = n_se_xa_sam.load();
 		STAT.n_se_supp_dev = n_se_supp; STAT.n_se_supp_sam_dev = n_se_supp_sam.load();
@@ -811,11 +836,12 @@ void Call::report_decisions()
 		                      (unsigned long long)c[SE_DECIDED_XA], n_se_xa_sam.load(), PW_MAXREG, (unsigned long long)c[SE_HOST_FULL], (unsigned long long)c[SE_HOST_TIE],
 		                      (unsigned long long)n_se_supp, n_se_supp_sam.load());
 	}
-	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them and %llu with an XA tag, left: rescue result not on the device %llu, list past %d %llu, tie %llu\n",
+	if (pe && cpusec_on()) fprintf(stderr, "[pair_kernel] %d pairs: decided %llu; host: no/unnamed hit %llu, > %d hits %llu, patch %llu, ALT/length %llu, rescue %llu, no proper pair %llu, score %llu, second primary hit %llu, XA %llu; pair_wave_kernel decided %llu of them and %llu with an XA tag, left: rescue result not on the device %llu, list past %d %llu, tie %llu; reported end by end: decided %llu, their text written %llu\n",
 	                      n_units, (unsigned long long)c[PR_DECIDED], (unsigned long long)c[PR_HOST_NO_HIT], PR_MAXREG, (unsigned long long)c[PR_HOST_MAXREG],
 	                      (unsigned long long)c[PR_HOST_PATCH], (unsigned long long)c[PR_HOST_LENGTH], (unsigned long long)c[PR_HOST_RESCUE], (unsigned long long)c[PR_HOST_NO_PAIR],
 	                      (unsigned long long)c[PR_HOST_SCORE], (unsigned long long)c[PR_HOST_SUPP], (unsigned long long)c[PR_HOST_XA],
-	                      (unsigned long long)n_wave, (unsigned long long)n_xa_pairs, (unsigned long long)c[PW_HOST_NO_RESULT], PW_MAXREG, (unsigned long long)c[PW_HOST_FULL], (unsigned long long)c[PW_HOST_TIE]);
+	                      (unsigned long long)n_wave, (unsigned long long)n_xa_pairs, (unsigned long long)c[PW_HOST_NO_RESULT], PW_MAXREG, (unsigned long long)c[PW_HOST_FULL], (unsigned long long)c[PW_HOST_TIE],
+	                      (unsigned long long)n_pair_lines, n_pair_lines_sam.load());
 }
 
 } // namespace mbw

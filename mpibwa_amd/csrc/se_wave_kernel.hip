@@ -77,39 +77,8 @@ se_wave_kernel(PairParams P, int n_work, const int *__restrict__ work, const Dev
 	if (lines & (lines - 1)) {   // supplementary lines (:1027-1030): SA tags, the MAPQ cap
 		const int n_lines = __popcll(lines);
 		if (!LN.desc || n_lines > SE_LINES_CAP) SW_GIVE_UP(SE_HOST_SUPP);
-		// line j is lane j's: its hit and its XA entries (every line's string is mem_gen_alt's for its own hit); the loop is wave-uniform
-		int my_z = 0, my_xa = 0;
-		u64 rest = lines;
-		for (int j = 0; j < n_lines; ++j) {
-			const int z = __ffsll((long long)rest) - 1;
-			rest &= rest - 1;
-			const int c = pw_xa_list(P, L, n, z, k, LN.xa_reqs ? LN.xa_reqs + ((size_t)t * SE_LINES_CAP + j) * PW_XA_CAP : nullptr, lane);
-			if (c < 0) SW_GIVE_UP(SE_HOST_XA);
-			if (lane == j) { my_z = z; my_xa = c; }
-		}
-		const bool mine = lane < n_lines;
-		WReg R = wl_get(L, my_z);
-		const int l = R.qe - R.qb > R.re - R.rb ? R.qe - R.qb : (int)(R.re - R.rb);
-		int mq = mine ? mapq_se_of(P, R.score, R.sub, R.sub_n, 0, l, R.frac_rep, ltab) & 0xff : 0;
-		const int mq0 = __shfl(mq, 0);
-		int at = mine ? 1 + my_xa : 0;   // the line's request follows the requests of the lines before it and of their XA entries
-		for (int d = 1; d < SE_LINES_CAP; d <<= 1) {
-			const int up = __shfl_up(at, d);
-			if (lane >= d) at += up;
-		}
-		if (mine) {
-			if (lane && !LN.keep_mapq && mq > mq0) mq = mq0;   // (:1029; no ALT hit here)
-			const size_t x = (size_t)t * SE_LINES_CAP + lane;
-			AlnReq q;
-			q.rb = R.rb; q.re = R.re; q.read = k; q.qb = R.qb; q.qe = R.qe; q.truesc = R.truesc; q.pad = 0;
-			q.w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);
-			LN.reqs[x] = q;
-			SamDesc d;
-			d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = at - 1 - my_xa; d.rid = R.rid;
-			d.flag = (lane ? LN.supp_flag : 0) | my_xa << SAM_XA_SHIFT; d.mapq = mq; d.score = R.score; d.sub = R.sub;
-			LN.desc[x] = d;
-			LN.xa_cnt[x] = (uint8_t)my_xa;
-		}
+		// a lane per line (wave_common.cuh: wave_lines, shared with pair_wave_kernel)
+		if (wave_lines<false>(P, LN, L, n, lines, n_lines, k, (size_t)t * SE_LINES_CAP, 0, 0, ltab, lane) < 0) SW_GIVE_UP(SE_HOST_XA);
 		if (lane == 0) { LN.n_lines[t] = (uint8_t)n_lines; wstatus[t] = SE_DECIDED_LINES; }
 		return;
 	}
@@ -178,25 +147,30 @@ __global__ void wave_scatter_kernel(int n_work, const int *__restrict__ work, co
 		for (int j = 0; j < c; ++j) reqs[at++] = xa_reqs[(size_t)x * PW_XA_CAP + j];
 	}
 }
+// (ENDS = 2: pair_wave_kernel's pairs reported end by end, the lines of end 0, then those of end 1; an end may have none)
+template <int ENDS>
 __global__ void lines_scatter_kernel(int n_work, const int *__restrict__ dst, const uint8_t *__restrict__ n_lines, const AlnReq *__restrict__ lreq,
                                      const uint8_t *__restrict__ lxcnt, const AlnReq *__restrict__ lxreq, AlnReq *__restrict__ reqs)
 {
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= n_work || dst[t] < 0) return;
-	const int nl = n_lines[t] < SE_LINES_CAP ? n_lines[t] : SE_LINES_CAP;
 	int at = dst[t];
-	for (int j = 0; j < nl; ++j) {
-		const size_t x = (size_t)t * SE_LINES_CAP + j;
-		reqs[at++] = lreq[x];
-		const int c = lxcnt[x] < PW_XA_CAP ? lxcnt[x] : PW_XA_CAP;
-		for (int i = 0; i < c; ++i) reqs[at++] = lxreq[x * PW_XA_CAP + i];
+	for (int e = 0; e < ENDS; ++e) {
+		const size_t l = (size_t)ENDS * t + e;
+		const int nl = n_lines[l] < SE_LINES_CAP ? n_lines[l] : SE_LINES_CAP;
+		for (int j = 0; j < nl; ++j) {
+			const size_t x = l * SE_LINES_CAP + j;
+			reqs[at++] = lreq[x];
+			const int c = lxcnt[x] < PW_XA_CAP ? lxcnt[x] : PW_XA_CAP;
+			for (int i = 0; i < c; ++i) reqs[at++] = lxreq[x * PW_XA_CAP + i];
+		}
 	}
 }
-void launch_lines_job_scatter(void *stream, int n_work, const int *d_dst, const uint8_t *d_n_lines, const AlnReq *d_lreq, const uint8_t *d_lxcnt,
+void launch_lines_job_scatter(void *stream, int ends, int n_work, const int *d_dst, const uint8_t *d_n_lines, const AlnReq *d_lreq, const uint8_t *d_lxcnt,
                               const AlnReq *d_lxreq, AlnReq *d_reqs)
 {
 	if (n_work > 0)
-		hipLaunchKernelGGL(lines_scatter_kernel, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_dst, d_n_lines, d_lreq, d_lxcnt, d_lxreq,
+		hipLaunchKernelGGL(ends == 2 ? lines_scatter_kernel<2> : lines_scatter_kernel<1>, dim3((n_work + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_work, d_dst, d_n_lines, d_lreq, d_lxcnt, d_lxreq,
 		                   d_reqs);
 }
 void launch_wave_job_scatter(void *stream, int ends, int n_work, const int *d_work, const int *d_dst, const AlnReq *d_w_reqs, const SamDesc *d_w_desc,

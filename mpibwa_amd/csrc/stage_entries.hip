@@ -175,12 +175,22 @@ static MswRes msw_host_request()
 }
 static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
                            int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
-                           void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt)
+                           void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt, uint8_t *n_lines = nullptr, void *line_desc = nullptr,
+                           void *line_req = nullptr, uint8_t *line_xa_cnt = nullptr, void *line_xa_req = nullptr)
 {
 	require_any_device();
 	if (n_align) *n_align = 0;
 	if (n_pairs <= 0) return 0;
+	if (n_lines && (!line_desc || !line_req || !line_xa_cnt)) die("%s: no room for the lines", who);
 	const int n_reads = 2 * n_pairs;
+	const size_t n_slots = (size_t)n_reads * SE_LINES_CAP;
+	if (n_lines) {
+		memset(n_lines, 0, (size_t)n_reads);
+		memset(line_xa_cnt, 0, n_slots);
+		memset(line_desc, 0xff, n_slots * sizeof(SamDesc));
+		memset(line_req, 0xff, n_slots * sizeof(AlnReq));
+		if (line_xa_req) memset(line_xa_req, 0xff, n_slots * PW_XA_CAP * sizeof(AlnReq));
+	}
 	memset(status, 0, (size_t)n_pairs);
 	memset(desc, 0xff, (size_t)n_reads * sizeof(SamDesc));
 	memset(req, 0xff, (size_t)n_reads * sizeof(AlnReq));
@@ -229,7 +239,7 @@ static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t
 			for (size_t j = 0; j < c.size() && ok; ++j) ok = c[j].rb == a[e][j].rb && c[j].re == a[e][j].re && c[j].qb == a[e][j].qb && c[j].score == a[e][j].score;
 			a[e].settled = ok;
 		}
-		if (!ok || !pair_wave_eligible(a, PW_MAXREG)) continue;
+		if (!ok || !pair_wave_eligible(a, PW_MAXREG, n_lines != nullptr)) continue;
 		s[0].l_seq = lens[2 * k]; s[1].l_seq = lens[2 * k + 1];
 		work.push_back(k);
 		mfirst.push_back((unsigned)mreq.size());
@@ -288,8 +298,28 @@ static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t
 	}
 	d_ws.fill(0, nw);
 	if (d_xc) d_xc.fill(0, 2 * nw);
+	const size_t nl = 2 * nw * SE_LINES_CAP;   // the side arrays by (work item, end, line)
+	DevArr<uint8_t> d_ln, d_lxc;
+	DevArr<SamDesc> d_lds;
+	DevArr<AlnReq> d_lrq, d_lxr;
+	SeLines LN;
+	if (n_lines) {
+		d_ln = DevArr<uint8_t>(2 * nw + PAD); d_lxc = DevArr<uint8_t>(nl + PAD);
+		d_lds = DevArr<SamDesc>(nl * sizeof(SamDesc) + PAD);
+		d_lrq = DevArr<AlnReq>(nl * sizeof(AlnReq) + PAD);
+		d_ln.fill(0, 2 * nw); d_lxc.fill(0, nl);
+		d_lds.fill(0xff, nl * sizeof(SamDesc));
+		d_lrq.fill(0xff, nl * sizeof(AlnReq));
+		LN.desc = d_lds; LN.reqs = d_lrq; LN.n_lines = d_ln; LN.xa_cnt = d_lxc;
+		if (line_xa_req) {
+			d_lxr = DevArr<AlnReq>(nl * PW_XA_CAP * sizeof(AlnReq) + PAD);
+			d_lxr.fill(0xff, nl * PW_XA_CAP * sizeof(AlnReq));
+			LN.xa_reqs = d_lxr;
+		}
+		se_lines_options(opt, LN);
+	}
 	launch_pair_wave(st, pp, n_work, d_work, d_lists, d_loff, d_len, d_mreq, d_mres, d_mfirst, d_tags, d_toff, d_ao, d_tab, d_tab + n_tab, d_ws, d_rq, d_ds,
-	                 d_xr, d_xc);
+	                 d_xr, d_xc, n_lines ? &LN : nullptr);
 	HIP_OK(hipDeviceSynchronize());
 	HIP_OK(hipGetLastError());
 	std::vector<uint8_t> ws(nw);
@@ -304,8 +334,31 @@ static int pair_wave_batch(const char *who, const mem_opt_t *opt, const bntseq_t
 		d_xr.download(w_xr.data(), w_xr.size() * sizeof(AlnReq));
 		d_xc.download(w_xc.data(), w_xc.size());
 	}
+	std::vector<uint8_t> w_ln(n_lines ? 2 * nw : 0), w_lxc(n_lines ? nl : 0);
+	std::vector<SamDesc> w_lds(n_lines ? nl : 0);
+	std::vector<AlnReq> w_lrq(n_lines ? nl : 0), w_lxr(line_xa_req ? nl * PW_XA_CAP : 0);
+	if (n_lines) {
+		d_ln.download(w_ln.data(), w_ln.size());
+		d_lxc.download(w_lxc.data(), w_lxc.size());
+		d_lds.download(w_lds.data(), w_lds.size() * sizeof(SamDesc));
+		d_lrq.download(w_lrq.data(), w_lrq.size() * sizeof(AlnReq));
+		if (line_xa_req) d_lxr.download(w_lxr.data(), w_lxr.size() * sizeof(AlnReq));
+	}
 	for (int t = 0; t < n_work; ++t) {
 		status[work[t]] = ws[t];
+		if (ws[t] == PW_DECIDED_LINES && n_lines)
+			for (int e = 0; e < 2; ++e) {   // slot (2t + e, line) of the work list -> slot (2 work[t] + e, line) of the call
+				const size_t from = (size_t)(2 * t + e) * SE_LINES_CAP, to = (size_t)(2 * work[t] + e) * SE_LINES_CAP;
+				const int c = std::min<int>(w_ln[2 * t + e], SE_LINES_CAP);
+				n_lines[2 * work[t] + e] = (uint8_t)c;
+				for (int j = 0; j < c; ++j) {
+					const int x = std::min<int>(w_lxc[from + j], PW_XA_CAP);
+					((SamDesc *)line_desc)[to + j] = w_lds[from + j];
+					((AlnReq *)line_req)[to + j] = w_lrq[from + j];
+					line_xa_cnt[to + j] = (uint8_t)x;
+					if (line_xa_req) memcpy((AlnReq *)line_xa_req + (to + j) * PW_XA_CAP, &w_lxr[(from + j) * PW_XA_CAP], (size_t)x * sizeof(AlnReq));
+				}
+			}
 		if (ws[t] != PR_DECIDED && ws[t] != PW_DECIDED_XA) continue;
 		for (int e = 0; e < 2; ++e) { ((SamDesc *)desc)[2 * work[t] + e] = w_ds[2 * t + e]; ((AlnReq *)req)[2 * work[t] + e] = w_rq[2 * t + e]; }
 		if (ws[t] != PW_DECIDED_XA) continue;
@@ -331,6 +384,20 @@ extern "C" int mi355x_pair_wave_xa_batch(const mem_opt_t *opt, const bntseq_t *b
 	if (!xa_req || !xa_cnt) die("mi355x_pair_wave_xa_batch: no room for the XA requests");
 	return pair_wave_batch("mi355x_pair_wave_xa_batch", opt, bns, pac, pes, n_processed, n_pairs, reads, off, regs, reg_off, status, desc, req, n_align, xa_req,
 	                       xa_cnt);
+}
+// The same with the side arrays for the pairs mem_sam_pe reports end by end through no_pairing: (status 17, PW_DECIDED_LINES; device.h):
+// n_lines[2k + e] lines of end e (0: the unaligned record), and by (read 2k + e, line) = slot (2k + e) * mi355x_se_lines_cap() + line
+// line_desc, line_req, line_xa_cnt and line_xa_req (mi355x_pair_wave_xa_cap() requests each).  A pair without any region is handed to
+// the kernel too.  xa_req = NULL: without the XA listing of the paired branch; line_xa_req = NULL: without that of the lines.
+extern "C" int mi355x_pair_wave_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, const mem_pestat_t pes[4], int64_t n_processed,
+                                            int n_pairs, const uint8_t *reads, const int64_t *off, const void *regs, const int *reg_off, uint8_t *status,
+                                            void *desc, void *req, int *n_align, void *xa_req, uint8_t *xa_cnt, uint8_t *n_lines, void *line_desc,
+                                            void *line_req, uint8_t *line_xa_cnt, void *line_xa_req)
+{
+	if (xa_req && !xa_cnt) die("mi355x_pair_wave_lines_batch: no room for the XA counts");
+	if (!n_lines) die("mi355x_pair_wave_lines_batch: no room for the line counts");
+	return pair_wave_batch("mi355x_pair_wave_lines_batch", opt, bns, pac, pes, n_processed, n_pairs, reads, off, regs, reg_off, status, desc, req, n_align,
+	                       xa_req, xa_req ? xa_cnt : nullptr, n_lines, line_desc, line_req, line_xa_cnt, line_xa_req);
 }
 
 // Stage entry of se_wave_kernel (se_wave_kernel.hip) for parity tests: n_work single-end reads given by their numbers in the chunk
@@ -925,8 +992,8 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 	hipStream_t st = 0;
 	const int n = ends * n_units, n_req = req_base[n_units];
 	const int64_t l_pac = bns->l_pac;
-	// n_lines given (ends = 1): desc_ holds SE_LINES_CAP line descriptors per read for sam_lines_kernel, and the chunk-wide descriptors say
-	// "not the device's", as in the pipeline
+	// n_lines given (one count per read): desc_ holds SE_LINES_CAP line descriptors per read for sam_lines_kernel (ends = 2: its paired
+	// instantiation, every pair a unit), and the chunk-wide descriptors say "not the device's", as in the pipeline
 	SamDesc not_mine;
 	memset(&not_mine, 0, sizeof not_mine);
 	not_mine.req = -1;
@@ -956,17 +1023,18 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 					die("%s: bad XA request %d of descriptor %d", who, j, r);
 		}
 	}
-	for (int k = 0; n_lines && k < n_units; ++k) {
-		if (n_lines[k] == 0) continue;
-		if (n_lines[k] < 2 || n_lines[k] > SE_LINES_CAP) die("%s: read %d with %d lines", who, k, (int)n_lines[k]);
-		for (int j = 0; j < n_lines[k]; ++j) {
-			const SamDesc &d = ldesc[(size_t)k * SE_LINES_CAP + j];
+	for (int r = 0; n_lines && r < n; ++r) {   // (ends = 2: n_lines by read, 0 = the unaligned record; the lines of pair k count from req_base[k])
+		const int k = r / ends;
+		if (n_lines[r] == 0) continue;
+		if ((ends == 1 && n_lines[r] < 2) || n_lines[r] > SE_LINES_CAP) die("%s: read %d with %d lines", who, r, (int)n_lines[r]);
+		for (int j = 0; j < n_lines[r]; ++j) {
+			const SamDesc &d = ldesc[(size_t)r * SE_LINES_CAP + j];
 			const int q = req_base[k] + d.req;
-			if (d.req < 0 || q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != k) die("%s: bad descriptor of line %d of read %d", who, j, k);
-			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[k] || d.qb > d.qe) die("%s: bad region of line %d of read %d", who, j, k);
+			if (d.req < 0 || q >= req_base[k + 1] || d.rid < 0 || d.rid >= bns->n_seqs || reqs[q].read != r) die("%s: bad descriptor of line %d of read %d", who, j, r);
+			if (d.rb < 0 || d.re > 2 * l_pac || d.rb >= d.re || d.qb < 0 || d.qe > lens[r] || d.qb > d.qe) die("%s: bad region of line %d of read %d", who, j, r);
 			for (int x = 1; x <= (d.flag >> SAM_XA_SHIFT & SAM_XA_MASK); ++x)
-				if (q + x >= req_base[k + 1] || reqs[q + x].read != k || reqs[q + x].pad < 0 || reqs[q + x].pad >= bns->n_seqs || reqs[q + x].rb >= reqs[q + x].re)
-					die("%s: bad XA request %d of line %d of read %d", who, x, j, k);
+				if (q + x >= req_base[k + 1] || reqs[q + x].read != r || reqs[q + x].pad < 0 || reqs[q + x].pad >= bns->n_seqs || reqs[q + x].rb >= reqs[q + x].re)
+					die("%s: bad XA request %d of line %d of read %d", who, x, j, r);
 		}
 	}
 	for (int q = 0; q < n_req; ++q) {
@@ -1007,8 +1075,8 @@ static int sam_batch(const char *who, int ends, const mem_opt_t *opt, const bnts
 	DevArr<SamDesc> d_md;
 	AlnSamJob J;
 	if (n_lines) {
-		d_ml = DevArr<uint8_t>((size_t)n_units + 64, n_lines, (size_t)n_units);
-		d_md = DevArr<SamDesc>((size_t)n_units * SE_LINES_CAP * sizeof(SamDesc), ldesc);
+		d_ml = DevArr<uint8_t>((size_t)n + 64, n_lines, (size_t)n);
+		d_md = DevArr<SamDesc>((size_t)n * SE_LINES_CAP * sizeof(SamDesc), ldesc);
 		J.n_multi = n_units; J.d_mlines = d_ml; J.d_mdesc = d_md; J.d_mbase = d_base;   // (every read a unit; its request base is the job's own)
 	}
 	J.n_req = n_req; J.d_req = d_req; J.d_hdr = d_hdr; J.d_pool = d_pool; J.pool_bytes = pool_bytes; J.d_cnt = d_cnt; J.d_lists = d_lists;
@@ -1054,6 +1122,19 @@ extern "C" int mi355x_sam_se_lines_batch(const mem_opt_t *opt, const bntseq_t *b
 {
 	if (!n_lines) die("mi355x_sam_se_lines_batch: no line counts");
 	return sam_batch("mi355x_sam_se_lines_batch", 1, opt, bns, pac, n_reads, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
+	                 out_len, out_off, arena_out, cursor, hdr_out, n_lines);
+}
+// The twin for pairs reported end by end (the paired instantiation of sam_lines_kernel behind aln_kernel and an idle sam_emit_kernel<true>):
+// every pair is a unit; n_lines[2k + e] = 0 .. mi355x_se_lines_cap() lines of end e (0: the unaligned record), desc_ = the descriptors by
+// (read, line) as mi355x_pair_wave_lines_batch returns them (req relative to req_base[k]; requests laid out as [end 0: line 0, its XA
+// entries, line 1, ...; end 1: ...], reqs.read = 2k + e).  out_len[r] = bytes of all lines of read r; -1: the host's pair, both reads.
+extern "C" int mi355x_sam_pe_lines_batch(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int n_pairs, const uint8_t *reads, const int64_t *off,
+                                         const uint8_t *quals, const char *names, const int *name_off, const uint8_t *n_lines, const void *desc_,
+                                         const void *reqs_, const int *req_base, size_t arena_bytes, int grid_blocks, int *out_len, unsigned long long *out_off,
+                                         uint8_t *arena_out, unsigned long long *cursor, void *hdr_out)
+{
+	if (!n_lines) die("mi355x_sam_pe_lines_batch: no line counts");
+	return sam_batch("mi355x_sam_pe_lines_batch", 2, opt, bns, pac, n_pairs, reads, off, quals, names, name_off, desc_, reqs_, req_base, arena_bytes, grid_blocks,
 	                 out_len, out_off, arena_out, cursor, hdr_out, n_lines);
 }
 extern "C" int mi355x_sam_lines_row(void) { return sam_lines_row(); }

@@ -1,8 +1,9 @@
 // wave_common.cuh — what the two wave-per-unit deciding kernels share (pair_wave_kernel.hip: a pair per wavefront; se_wave_kernel.hip:
-// a single-end read per wavefront): a region list in LDS with one region per lane, the wave reductions, and the two steps both replay
+// a single-end read per wavefront): a region list in LDS with one region per lane, the wave reductions, and the steps both replay
 //   mem_mark_primary_se   src/bwamem.c:493-569        (reads without ALT hits; a rank sort, one hit per lane)
 //   mem_gen_alt           src/bwamem_extra.c:98-118   (which hits the chosen hit's XA string lists, and their CIGAR requests)
 //   mem_reg2aln           src/bwamem.c:1089-1105      (the band of the final global alignment)
+//   mem_reg2sam           src/bwamem.c:1015-1032      (the lines of a read with supplementary lines: wave_lines)
 // The arithmetic is pairmath.h's through pair_common.cuh, as in every deciding kernel.
 #ifndef MBW_WAVE_COMMON_CUH
 #define MBW_WAVE_COMMON_CUH
@@ -128,6 +129,56 @@ __device__ __forceinline__ int pw_xa_list(const PairParams &P, const WList &L, i
 		slots[__popcll(hits & (((u64)1 << lane) - 1))] = q;
 	}
 	return n_xa;
+}
+
+// The lines of one read as mem_reg2sam makes them (src/bwamem.c:1015-1032 without MEM_F_ALL, no ALT hit): `lines` = the n_lines (1 ..
+// SE_LINES_CAP) primary hits of at least T of the marked list L, in list order.  Line j is lane j's: its XA listing (every line's string
+// is mem_gen_alt's for its own hit), MAPQ with the cap of :1029, band, request and descriptor go to slot slot0 + j of LN.desc / LN.reqs /
+// LN.xa_cnt, its XA requests to LN.xa_reqs[(slot0 + j) * PW_XA_CAP ..].  The requests are laid out as [line 0, its XA entries, line 1,
+// ...] from req0 on (SamDesc::req), `read` is their read, flag0 goes on every line and LN.supp_flag on the lines behind the first.
+// PAIR: the read is an end of a pair — MAPQ and sub take the hit's csub (a rescued hit carries one; a single-end list has none) and the
+// limits of the per-length and sub_n tables are tested per line, as pair_wave_kernel tests them for its chosen hits.
+// Returns the number of requests (lines and XA entries), -1: XA entries without room for them, -2 (PAIR): a line beyond the tables.
+// Every call in it is wave-uniform: the ballots of pw_xa_list stay outside divergent code.
+template <bool PAIR>
+__device__ __forceinline__ int wave_lines(const PairParams &P, const SeLines &LN, const WList &L, int n, u64 lines, int n_lines, int read, size_t slot0,
+                                          int req0, int flag0, const double *__restrict__ ltab, int lane)
+{
+	int my_z = 0, my_xa = 0;
+	u64 rest = lines;
+	for (int j = 0; j < n_lines; ++j) {
+		const int z = __ffsll((long long)rest) - 1;
+		rest &= rest - 1;
+		const int c = pw_xa_list(P, L, n, z, read, LN.xa_reqs ? LN.xa_reqs + (slot0 + j) * PW_XA_CAP : nullptr, lane);
+		if (c < 0) return -1;
+		if (lane == j) { my_z = z; my_xa = c; }
+	}
+	const bool mine = lane < n_lines;
+	WReg R = wl_get(L, my_z);
+	const int l = R.qe - R.qb > R.re - R.rb ? R.qe - R.qb : (int)(R.re - R.rb);
+	if (PAIR && __ballot(mine && (l >= P.ltab_n || l <= 0 || R.sub_n >= 40))) return -2;
+	int mq = mine ? mapq_se_of(P, R.score, R.sub, R.sub_n, PAIR ? R.csub : 0, l, R.frac_rep, ltab) & 0xff : 0;
+	const int mq0 = __shfl(mq, 0);
+	int at = mine ? 1 + my_xa : 0;   // the line's request follows the requests of the lines before it and of their XA entries
+	for (int d = 1; d < SE_LINES_CAP; d <<= 1) {
+		const int up = __shfl_up(at, d);
+		if (lane >= d) at += up;
+	}
+	if (mine) {
+		if (lane && !LN.keep_mapq && mq > mq0) mq = mq0;   // (:1029; no ALT hit here)
+		const size_t x = slot0 + lane;
+		AlnReq q;
+		q.rb = R.rb; q.re = R.re; q.read = read; q.qb = R.qb; q.qe = R.qe; q.truesc = R.truesc; q.pad = 0;
+		q.w2 = reg2aln_band(R.qe - R.qb, (int)(R.re - R.rb), R.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, R.w);
+		LN.reqs[x] = q;
+		SamDesc d;
+		d.rb = R.rb; d.re = R.re; d.qb = R.qb; d.qe = R.qe; d.req = req0 + at - 1 - my_xa; d.rid = R.rid;
+		d.flag = flag0 | (lane ? LN.supp_flag : 0) | my_xa << SAM_XA_SHIFT; d.mapq = mq; d.score = R.score;
+		d.sub = PAIR && R.csub > R.sub ? R.csub : R.sub;   // mem_reg2aln: sub = max(sub, csub)
+		LN.desc[x] = d;
+		LN.xa_cnt[x] = (uint8_t)my_xa;
+	}
+	return __shfl(at, SE_LINES_CAP - 1);
 }
 
 } // namespace mbw
