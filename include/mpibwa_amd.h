@@ -208,6 +208,8 @@ typedef struct {
 int  mi355x_init(int local_rank, const bwaidx_t *idx, const mi355x_comm_t *comm);
 /* GPUs visible to this process (a host program that starts more ranks than that lets ranks share a device) */
 int  mi355x_device_count(void);
+/* compute units of the current device, as the kernel launchers read them to size their grids; 0 on failure */
+int  mi355x_device_cus(void);
 /* free / total bytes of HBM on the device the index lives on; 0 on success */
 int  mi355x_device_memory(size_t *free_bytes, size_t *total_bytes);
 /* (re)allocations of device / page-locked work buffers since the library was loaded: they stall every stream of the device, so
@@ -303,11 +305,16 @@ int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, int n_reads,
  * which: 0 = the product's dispatch (no-DP shortcut / narrow-band instantiation with hand-off to the full-size one),
  * 1 = DP requests straight to the full-size instantiation.
  * Per request out_hdr gets score, NM, n_cigar, md_len, flags (1 = the device declined: band matrix beyond its budget);
- * cigar (BAM-encoded u32) goes to cigar_out[cigar_cap * i ..], MD text to md_out[md_cap * i ..]. */
+ * cigar (BAM-encoded u32) goes to cigar_out[cigar_cap * i ..], MD text to md_out[md_cap * i ..].
+ * read[i] == -1 marks an unused slot of the request array; it, and a request that no instantiation of the kernel answered,
+ * comes back with flags = -1 (the headers are filled with -1 before the launch).
+ * mi355x_global_batch_counts: of the last call, the final lengths of the three request lists (no-DP, narrow band, full size)
+ * and the bytes of the result pool handed out. */
 int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, int n_reads, const uint8_t *reads,
                         const int64_t *off, int n_req, const int64_t *rb, const int64_t *re, const int *read,
                         const int *qb, const int *qe, const int *w, const int *truesc, int which,
                         int *out_hdr5, uint32_t *cigar_out, int cigar_cap, char *md_out, int md_cap, double *kernel_ms);
+void mi355x_global_batch_counts(uint64_t out[4]);
 
 /* Pairing decisions of mem_sam_pe (src/bwamem_pair.c:250-393 with mem_sort_dedup_patch src/bwamem.c:437-489, the test of
  * mem_matesw :118-128, mem_mark_primary_se src/bwamem.c:493-569, mem_pair :182-243, mem_approx_mapq_se src/bwamem.c:952-976,

@@ -18,7 +18,7 @@ EXPORTS = [
     "mi355x_index_upload", "mi355x_index_alloc", "mi355x_index_buffers", "mi355x_index_d2d", "mi355x_index_commit",
     "mi355x_finalize", "mi355x_index_build", "mi355x_index_build_gpu",
     "mi355x_smem_batch", "mi355x_sa_batch", "mi355x_sa_batch2", "mi355x_sa_dense_info", "mi355x_extend_batch", "mi355x_extend_batch2", "mi355x_matesw_batch", "mi355x_chain_batch", "mi355x_c2a_batch", "mi355x_pair_batch", "mi355x_pair_maxreg", "mi355x_fastq_scan", "mi355x_fastq_chunks", "mi355x_fastq_fill", "mi355x_last_stats", "mi355x_host_cpus", "mi355x_collect_sam", "mi355x_collect_sam_into", "mi355x_host_ksw_align2",
-    "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_device_count", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
+    "bwa_set_rg", "bwa_insert_header", "bwa_idx2mem", "mi355x_write_map", "mi355x_init", "mi355x_rank_host_threads", "mi355x_index_checksums", "mi355x_init_bcast_seconds", "mi355x_global_batch", "mi355x_global_batch_counts", "mi355x_device_count", "mi355x_device_cus", "mi355x_device_memory", "mi355x_buffer_growths", "mi355x_prewarm", "mi355x_max_calls",
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
     "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg", "mi355x_se_wave_batch",
     "mi355x_se_lines_cap", "mi355x_se_wave_lines_batch", "mi355x_sam_se_lines_batch", "mi355x_sam_lines_row", "mi355x_sam_lines_sa_stage",
@@ -115,6 +115,7 @@ def load_library(build_if_missing=True):
     sig("mi355x_init_bcast_seconds", C.c_double, [])
     sig("mi355x_index_checksums", C.c_int, [C.c_void_p])
     sig("mi355x_device_count", C.c_int, [])
+    sig("mi355x_device_cus", C.c_int, [])
     sig("mi355x_device_memory", C.c_int, [P(C.c_size_t), P(C.c_size_t)])
     sig("mi355x_buffer_growths", C.c_ulonglong, [])
     sig("mi355x_pair_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -125,6 +126,7 @@ def load_library(build_if_missing=True):
     sig("mi355x_pair_wave_lines_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 15)
     sig("mi355x_global_batch", C.c_int, [P(abi.mem_opt_t), C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 +
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_double)])
+    sig("mi355x_global_batch_counts", None, [P(C.c_uint64)])
     sig("mi355x_sam_arena_bytes", C.c_size_t, [C.c_int, C.c_int])
     sig("mi355x_sam_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
     sig("mi355x_sam_se_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_size_t, C.c_int] + [C.c_void_p] * 5)
@@ -741,6 +743,13 @@ class Engine:
         cigs = [cig[i, :hdr[i, 2]].copy() for i in range(nr)]
         mds = [md[i, :hdr[i, 3]].tobytes() for i in range(nr)]
         return hdr, cigs, mds, ms.value
+
+    def global_align_counts(self):
+        """Of the last global_align(): the final lengths of aln_kernel's three request lists (no-DP, narrow band, full size) and
+        the bytes of the result pool handed out."""
+        c = (C.c_uint64 * 4)()
+        self.lib.mi355x_global_batch_counts(c)
+        return [int(x) for x in c]
 
     def extend(self, opt, qs, ts, w, h0, end_bonus):
         n = len(qs)

@@ -67,8 +67,7 @@ __device__ __forceinline__ int put_num(uint8_t *md, int len, int v, int lane)
 //           band outgrows that in one of mem_reg2aln's rounds is marked (flags = 2) and left to
 //   KIND 2  the full-size variant, which starts those requests again from the first round.
 #define ALN_PENDING 2
-// counters[]: [0] bytes of the result pool handed out, [ALN_CNT + k] length of the request list of kind k
-#define ALN_CNT 8
+// counters[]: [0] bytes of the result pool handed out, [ALN_CNT + k] length of the request list of kind k (ALN_CNT: device.h)
 #define ALN_SLAB 1024u
 
 __device__ __forceinline__ bool aln_invalid(const AlnParams &P, const AlnReq &R, int max_len, int tcap)

@@ -245,6 +245,7 @@ struct AlnHdr {                  // result header; cigar (n_cigar x u32) and MD 
 	int32_t flags;               // 1 = not done on the device (band matrix too large / caps): the host recomputes it
 };
 struct AlnParams { int64_t l_pac; int a, w; };
+#define ALN_CNT 8                // launch_aln's d_counters: [0] pool bytes handed out, [ALN_CNT + k] length of the request list of kind k
 void aln_params(const mem_opt_t *opt, int64_t l_pac, AlnParams &ap, ExtParams &ep);
 // the result pool of n_req requests: 96 bytes each + room for the partly used last slab of every wave (aln_kernel.hip: ALN_SLAB)
 inline size_t aln_pool_bytes(size_t n_req) { return n_req * 96 + ((size_t)48 << 20); }

@@ -515,6 +515,15 @@ extern "C" int mi355x_device_count(void)
 	return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 
+// compute units of the current device (hipDeviceProp_t::multiProcessorCount: what the launchers size their grids by); 0 on failure
+extern "C" int mi355x_device_cus(void)
+{
+	int dev = 0;
+	hipDeviceProp_t prop;
+	if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+	return prop.multiProcessorCount;
+}
+
 // free / total bytes of the device the index lives on (0 on success), through this library's own HIP runtime
 extern "C" int mi355x_device_memory(size_t *free_bytes, size_t *total_bytes)
 {

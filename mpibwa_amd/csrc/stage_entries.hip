@@ -1,6 +1,7 @@
 // stage_entries.hip — the stage-level C entry points (parity tests, micro-benchmarks): one kernel or one stage of the pipeline on inputs
 // chosen by the caller, with device arrays that live for the call (hip_util.h: DevArr).  The pipeline itself does not come through here.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -920,7 +921,14 @@ extern "C" int64_t mi355x_c2a_batch(const mem_opt_t *opt, const bntseq_t *bns, i
 // Stage-level entry point of the CIGAR / MD / NM kernel (tests): n_req regions of reads of a batch against windows of the
 // packed reference `pac`, through mem_reg2aln's band-doubling loop (src/bwamem.c:1106-1122) exactly as the SAM stage asks
 // for them.  which = 0: the product's dispatch (no-DP / narrow band / full size); 1: DP requests straight to the full-size
-// instantiation.  out_hdr5 per request: score, NM, n_cigar, md_len, flags.
+// instantiation.  out_hdr5 per request: score, NM, n_cigar, md_len, flags.  read[i] == -1 is an unused slot of the request array, as
+// the pipeline leaves them (aln_classify_kernel); the headers are filled with -1 before the launch, so such a slot, and any live
+// request that no instantiation answered, comes back with flags = -1.
+static std::atomic<uint64_t> g_aln_counts[4];   // of the last call: lengths of the three request lists, pool bytes handed out
+extern "C" void mi355x_global_batch_counts(uint64_t out[4])
+{
+	for (int k = 0; k < 4; ++k) out[k] = g_aln_counts[k].load();
+}
 extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, int n_reads, const uint8_t *reads,
                                    const int64_t *off, int n_req, const int64_t *rb, const int64_t *re, const int *read,
                                    const int *qb, const int *qe, const int *w, const int *truesc, int which,
@@ -933,7 +941,7 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	const int max_len = R.max_len;
 	std::vector<AlnReq> rq(n_req);
 	for (int i = 0; i < n_req; ++i) {
-		if (read[i] < 0 || read[i] >= n_reads || rb[i] < 0 || re[i] > 2 * l_pac) die("mi355x_global_batch: bad request %d", i);
+		if (read[i] != -1 && (read[i] < 0 || read[i] >= n_reads || rb[i] < 0 || re[i] > 2 * l_pac)) die("mi355x_global_batch: bad request %d", i);
 		rq[i].rb = rb[i]; rq[i].re = re[i]; rq[i].read = read[i]; rq[i].qb = qb[i]; rq[i].qe = qe[i]; rq[i].w2 = w[i]; rq[i].truesc = truesc[i];
 		rq[i].pad = 0;
 	}
@@ -948,6 +956,7 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	DevArr<int> d_gap(gaptab.size() * 4, gaptab.data()), d_lists((size_t)n_req * 3 * 4);
 	DevArr<unsigned long long> d_cnt(256);
 	d_cnt.zero();
+	d_hdr.fill(0xff);   // flags = -1: written by nobody
 	AlnParams ap;
 	ExtParams ep;
 	aln_params(opt, l_pac, ap, ep);
@@ -960,6 +969,12 @@ extern "C" int mi355x_global_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	std::vector<uint8_t> pool(pool_bytes);
 	d_hdr.download((void *)hdr.data(), (size_t)n_req * sizeof(AlnHdr));
 	d_pool.download(pool.data(), pool_bytes);
+	{
+		unsigned long long cnt[ALN_CNT + 3];
+		d_cnt.download(cnt, sizeof cnt);
+		for (int k = 0; k < 3; ++k) g_aln_counts[k] = cnt[ALN_CNT + k];
+		g_aln_counts[3] = cnt[0];
+	}
 	int rc = 0;
 	for (int i = 0; i < n_req; ++i) {
 		const AlnHdr &h = hdr[i];

@@ -271,6 +271,20 @@ class RefIndex:
                 break
         return res
 
+    def reg2aln(self, opt, read, reg):
+        """The reference's own mem_reg2aln (src/bwamem.c:1089-1159) on one region (an ALNREG_DT record) of `read` (nt4 codes) on the
+        loaded index: (cigar u32[] with its clips and without the squeezed deletion, NM, MD bytes, pos, is_rev)"""
+        lib = self.lib
+        lib.mem_reg2aln.restype = mem_aln_t
+        lib.mem_reg2aln.argtypes = [C.POINTER(abi.mem_opt_t), C.POINTER(abi.bntseq_t), C.POINTER(C.c_uint8), C.c_int, C.c_void_p, C.c_void_p]
+        sq = np.ascontiguousarray(read, dtype=np.uint8)
+        rg = np.ascontiguousarray(reg, dtype=ALNREG_DT).reshape(1)
+        a = lib.mem_reg2aln(opt, self.bns, self.pac, len(sq), sq.ctypes.data, rg.ctypes.data)
+        cig = np.ctypeslib.as_array(C.cast(a.cigar, C.POINTER(C.c_uint32)), shape=(a.n_cigar,)).copy()
+        md = C.string_at(a.cigar + 4 * a.n_cigar)
+        libc.free(C.c_void_p(a.cigar))
+        return cig, a.NM, md, a.pos, a.is_rev
+
     def set_rg(self, line):
         """the reference's own bwa_set_rg (None: no read group); the ID it kept"""
         return set_rg(self.lib, line)
