@@ -510,6 +510,9 @@ int64_t mi355x_seed_batch(int n_reads, int cap, int max_occ, uint64_t *intv, con
 int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, int n_reads, const uint8_t *reads,
                         const int64_t *off, int n_req, const int64_t *rb, const int64_t *re, const int *read,
                         const int *is_rev, int *out8, double *kernel_ms);
+/* Of the last mi355x_matesw_batch: what the second pass (b[] scan and reverse pass) ran — quads of two alignments of one class,
+ * quads of one (the odd last member of a class), work items of a register launch, work items of the general launch. */
+void mi355x_matesw_batch_counts(uint64_t out[4]);
 
 /* ---- the caller's side of the boundary: FASTQ text -> mpiBWA's chunks -> bseq1_t[] ----
  * Record scan (find_reads_size_and_offsets, src/parallel_aux.c:682-832): offsets of the record starts

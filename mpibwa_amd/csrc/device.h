@@ -539,12 +539,23 @@ size_t msw_lds_bytes(int max_len);
 // d_rows: scratch of n_req * (longest window) u16
 // h_req / h_len (read lengths) / h_list / d_list (2 n_req ints each) / d_tail (msw_tail_ints(n_req) ints) given: requests next to each
 // other for the same mate and orientation are aligned two per quad in packed 16-bit arithmetic (msw2_kernel), and the alignments that
-// need the reverse pass get it in a launch of their own behind it (msw_tail_kernel); otherwise every request on its own
+// need the reverse pass get it in a launch of their own behind it, sorted by class and again two per quad (msw_rev2_kernel;
+// MPIBWA_MSW_REV2=0: one per quad, msw_tail_kernel); otherwise every request on its own
 void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req, const uint8_t *d_seq, const int64_t *d_off, const int *d_len,
                 const uint8_t *d_pac, MswRes *d_res, uint16_t *d_rows, int max_len, const MswReq *h_req = nullptr, const int *h_len = nullptr,
                 int *h_list = nullptr, int *d_list = nullptr, int *d_tail = nullptr);
-#define MSW_TAIL_BUCKETS 9
-inline size_t msw_tail_ints(size_t n_req) { return 16 + MSW_TAIL_BUCKETS * n_req; }   // bucket counters + a list of n_req per bucket
+// d_tail: the lists of the second pass, all of it sized before the launch — the class offsets in members and in work items
+// (MSW_OFF_INTS each), the request indices sorted by class, the class bytes, the sort's histograms per block of MSW_SORT_CHUNK requests
+#define MSW_NCLS 48               // 16 segment lengths of the reverse pass x 3 score classes
+#define MSW_SORT_CHUNK 4096
+#define MSW_OFF_INTS 64
+inline size_t msw_tail_ints(size_t n_req)
+{
+	return 2 * MSW_OFF_INTS + n_req + (n_req + 3) / 4 + (n_req + MSW_SORT_CHUNK - 1) / MSW_SORT_CHUNK * MSW_NCLS;
+}
+// what the second pass of the last launch_msw with this d_tail ran (waits for nothing: call it behind the stream): pairs of
+// msw_rev2_kernel, alone-riders, work items of a register launch, of the general launch
+void msw_tail_counts(const int *d_tail, uint64_t out[4]);
 MswParams msw_params(const mem_opt_t *opt, int64_t l_pac);
 // Can mate rescue run on the device under these options?  Not with o_ins = 0: the reference's lazy-F loop then ends after the first
 // position of every segment (its exit test f - e_ins <= max(h, f) - (o_ins + e_ins) holds at once), a carry across a segment border

@@ -39,6 +39,7 @@
 // wave touch 64 consecutive dwords (no bank conflicts) and the whole DP runs out of LDS and registers.  HBM traffic is the
 // target window (2 bits per row) and one u16 per row for the b[] pass.  The work is VALU-bound: ~30 integer ops per cell.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <type_traits>
 #include "hip_util.h"
 #include "device.h"
@@ -246,7 +247,8 @@ __global__ __launch_bounds__(64) void msw_kernel(MswParams P, int n_work, int n_
 // query code, the two substitution scores as a packed pair.  The row state of a position is one dword: H and E of both alignments
 // as four bytes, unpacked and repacked with one v_perm_b32 each.  Row maxima, best cell, saturation are kept per alignment as in
 // msw_pass.  The kernel ends with the forward pass: an alignment that needs no second pass gets its final record here, the others
-// (score >= minsc, not saturated) are listed for msw_tail_kernel, which runs the b[] scan and the reverse pass densely behind it.
+// (score >= minsc, not saturated) get a class byte; a sort makes lists of them and msw_rev2_kernel runs the b[] scan and the reverse
+// pass densely behind it, two of a class per quad.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef short msw_s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ msw_s2 s2_of(uint32_t v) { return __builtin_bit_cast(msw_s2, v); }
@@ -260,20 +262,45 @@ __device__ __forceinline__ msw_s2 s2_sub0(msw_s2 a, msw_s2 b)
 	return __builtin_bit_cast(msw_s2, __builtin_elementwise_sub_sat(__builtin_bit_cast(msw_u2, a), __builtin_bit_cast(msw_u2, b)));
 }
 
-// The lists of alignments that need the second pass (msw_tail_kernel), by the length of that pass: rows ~ score / a (three classes),
-// cells per lane ~ qe (three classes); bucket MSW_TAIL_BUCKETS - 1 holds the longest.
-__device__ __forceinline__ int msw_tail_bucket(int score, int qe, int a)
-{
-	const int sb = score >= 80 * a ? 2 : score >= 40 * a ? 1 : 0;
-	const int qb = qe >= 96 ? 2 : qe >= 48 ? 1 : 0;
-	return sb * 3 + qb;
-}
-
 // scores of target base t against query codes 0..3 / code 4, without indexing the parameter block at run time (no scratch copy of it)
 __device__ __forceinline__ uint32_t msw_slo(const MswParams &P, int t) { return t == 0 ? P.slo[0] : t == 1 ? P.slo[1] : t == 2 ? P.slo[2] : P.slo[3]; }
 __device__ __forceinline__ int msw_s4(const MswParams &P, int t) { return t == 0 ? P.s4[0] : t == 1 ? P.s4[1] : t == 2 ? P.s4[2] : P.s4[3]; }
 
-// tail_n[MSW_TAIL_BUCKETS] (zeroed before the launch) / tail_list[MSW_TAIL_BUCKETS][tail_cap]: the alignments msw_tail_kernel completes
+// The class of an alignment that needs the second pass, one byte per request (0: it needs none): the segment length of
+// its reverse pass, slen2 = ceil((qe + 1) / 16) = 1..16 — which fixes the positions per lane, the segment ends and the hand-over points
+// of a quad, so that two alignments of one class can share a quad whatever reads they belong to — and the score class of
+// the forward score (below 40 a, below 80 a, from there on: rows ~ score / a), which keeps a wave's lockstep length uniform.  A larger class is a longer pass.
+__device__ __forceinline__ int msw_rev_class(int score, int qe, int a)
+{
+	const int sb = score >= 80 * a ? 2 : score >= 40 * a ? 1 : 0;
+	return 1 + (qe >> 4) * 3 + sb;
+}
+
+// One cell of the packed recurrence for the two alignments of a quad, with the row state in LDS: w = H, E of both as four bytes, s =
+// the two substitution scores as a packed pair (the caller's lookup: one table of pairs where the two share the query, two tables
+// or'ed where they do not).  seg_end (UNI) or bit 3 of entry u of cd: the last position of a segment.
+struct Msw2Gap { msw_s2 oe_del, oe_ins, e_del, e_ins; };
+template <bool UNI>
+__device__ __forceinline__ void msw2_cell(uint32_t &w, msw_s2 s, uint32_t cd, int u, bool seg_end, const Msw2Gap &G, msw_u2 c256, msw_s2 &diag,
+                                          msw_s2 &fseg, msw_s2 &ffull, msw_u2 &mblk)
+{
+	const msw_s2 hd = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c020c00u));   // H_A | H_B << 16   (row i - 1)
+	msw_s2 e = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c030c01u));          // E_A | E_B << 16
+	const msw_s2 h = s2_max(s2_max(diag + s, e), fseg);                    // Hpre(i, k) of both
+	const msw_u2 rel = {(unsigned short)(7 - u), (unsigned short)(7 - u)};
+	mblk = __builtin_elementwise_max(mblk, __builtin_bit_cast(msw_u2, h) * c256 + rel);
+	const msw_s2 hfin = s2_max(h, ffull);
+	e = s2_max(s2_sub0(e, G.e_del), s2_sub0(h, G.oe_del));
+	const msw_s2 t2 = s2_sub0(h, G.oe_ins);
+	fseg = s2_max(s2_sub0(fseg, G.e_ins), t2);
+	if constexpr (UNI) fseg = seg_end ? s2_splat(0) : fseg;
+	else fseg = s2_of(u_of(fseg) & ~(uint32_t)__builtin_amdgcn_sbfe((int)cd, 4 * u + 3, 1));   // -1 at the last position of a segment
+	ffull = s2_max(s2_sub0(ffull, G.e_ins), t2);
+	diag = hd;
+	w = __builtin_amdgcn_perm(u_of(e), u_of(hfin), 0x06020400u);            // bytes: H_A, E_A, H_B, E_B
+}
+
+// cls[n_req] (zeroed before the launch): the class of every alignment that msw_rev2_kernel / msw_tail_kernel completes
 //
 // SLEN = 0: the general form — the row state in LDS, any segment length, the lengths of a wave may differ.
 // SLEN > 0: every work item of the launch has that segment length (launch_msw sorts them), so a lane's S = 4 SLEN positions are a
@@ -286,7 +313,7 @@ template <int SLEN>
 __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int n_req, const int *__restrict__ pairs, const MswReq *__restrict__ req,
                                                   const uint8_t *__restrict__ seq, const int64_t *__restrict__ off, const int *__restrict__ lens,
                                                   const uint8_t *__restrict__ pac, MswRes *__restrict__ res, uint16_t *__restrict__ rows, int s_max,
-                                                  int *__restrict__ tail_n, int *__restrict__ tail_list, int tail_cap)
+                                                  uint8_t *__restrict__ cls)
 {
 	constexpr bool REGS = SLEN > 0, TWO = REGS && SLEN < 16;
 	extern __shared__ uint32_t lds2[];
@@ -361,8 +388,7 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 		constexpr bool UNI = decltype(uniform_segments)::value;
 		const int tn = tnA > tnB ? tnA : tnB;
 		bool run = live && tn > 0 && S > 0;
-		const msw_s2 oe_del = s2_splat(P.o_del + P.e_del), oe_ins = s2_splat(P.o_ins + P.e_ins), e_del = s2_splat(P.e_del), e_ins = s2_splat(P.e_ins);
-		const msw_s2 zero = s2_splat(0);
+		const Msw2Gap G = {s2_splat(P.o_del + P.e_del), s2_splat(P.o_ins + P.e_ins), s2_splat(P.e_del), s2_splat(P.e_ins)};
 		int Swave = run ? S : 0;
 		for (int o = 32; o; o >>= 1) Swave = max(Swave, __shfl_xor(Swave, o));
 		uint32_t co_diag = 0, co_fseg = 0, co_ffull = 0, co_key = 0;
@@ -395,23 +421,9 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 			// end of a segment as a wave-uniform fact — slen_u > 0: every live quad of the wave has that segment length, which is the rule
 			// (the reads of a chunk are of one length) — or bit 3 of the position's code)
 			auto step = [&](uint32_t &w, uint32_t cd, int u, bool seg_end, msw_u2 &mblk) {
-				const msw_s2 hd = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c020c00u));   // H_A | H_B << 16   (row i - 1)
-				msw_s2 e = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c030c01u));          // E_A | E_B << 16
 				uint32_t q = __builtin_amdgcn_ubfe(cd, 4 * u, 3);
 				asm("" : "+v"(q));   // (opaque: v_bfe_u32 + v_lshl_add_u32 for the table address; folded, it is shift + and + add)
-				const msw_s2 s = s2_of(srow[q]);
-				const msw_s2 h = s2_max(s2_max(diag + s, e), fseg);                    // Hpre(i, k) of both
-				const msw_u2 rel = {(unsigned short)(7 - u), (unsigned short)(7 - u)};
-				mblk = __builtin_elementwise_max(mblk, __builtin_bit_cast(msw_u2, h) * c256 + rel);
-				const msw_s2 hfin = s2_max(h, ffull);
-				e = s2_max(s2_sub0(e, e_del), s2_sub0(h, oe_del));
-				const msw_s2 t2 = s2_sub0(h, oe_ins);
-				fseg = s2_max(s2_sub0(fseg, e_ins), t2);
-				if constexpr (UNI) fseg = seg_end ? zero : fseg;
-				else fseg = s2_of(u_of(fseg) & ~(uint32_t)__builtin_amdgcn_sbfe((int)cd, 4 * u + 3, 1));   // -1 at the last position of a segment
-				ffull = s2_max(s2_sub0(ffull, e_ins), t2);
-				diag = hd;
-				w = __builtin_amdgcn_perm(u_of(e), u_of(hfin), 0x06020400u);            // bytes: H_A, E_A, H_B, E_B
+				msw2_cell<UNI>(w, s2_of(srow[q]), cd, u, seg_end, G, c256, diag, fseg, ffull, mblk);
 			};
 			int seg_pos = 0;   // position inside the segment (a lane's quarter is four whole segments: the same in every lane)
 			const msw_u2 eight = {8, 8};
@@ -555,8 +567,8 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 	fB.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxB); fB.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teB); fB.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeB);
 	satA = msw_dpp<MSW_QP(3, 3, 3, 3)>(satA); satB = msw_dpp<MSW_QP(3, 3, 3, 3)>(satB);
 	// Every alignment gets its record as msw_tail would leave it without a second pass (lane 0: A, lane 1: B).  One that reaches minsc
-	// unsaturated needs the b[] scan and the reverse pass: its request index goes to one of the MSW_TAIL_BUCKETS lists of msw_tail_kernel
-	// (wave-aggregated appends), which completes the record.
+	// unsaturated needs the b[] scan and the reverse pass: it gets its class byte, from which the sort kernels below make the lists of
+	// msw_rev2_kernel, which completes the record.  No list is appended to here: the lists are a function of the results alone.
 	const int minsc = P.min_seed_len * P.a;
 	const bool mineA = live && j == 0, mineB = live && hasB && j == 1;
 	const MswPassOut f = j == 0 ? fA : fB;
@@ -566,30 +578,81 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 		MswRes out;
 		out.score = f.score; out.te = f.te; out.qe = f.qe; out.score2 = -1; out.te2 = -1; out.tb = -1; out.qb = -1; out.flags = sat;
 		res[j == 0 ? rA : rB] = out;
+		if (tail) cls[j == 0 ? rA : rB] = (uint8_t)msw_rev_class(f.score, f.qe, P.a);   // (qe < qlen <= 249: slen2 <= 16)
 	}
-	const int bucket = msw_tail_bucket(f.score, f.qe, P.a);
-#pragma unroll
-	for (int b = 0; b < MSW_TAIL_BUCKETS; ++b) {
-		const bool in = tail && bucket == b;
-		const unsigned long long m = __builtin_amdgcn_ballot_w64(in);
-		if (!m) continue;
-		const int leader = __ffsll((long long)m) - 1;
-		int at = 0;
-		if (lane == leader) at = atomicAdd(&tail_n[b], __popcll(m));
-		at = __shfl(at, leader);
-		if (in) tail_list[(size_t)b * tail_cap + at + __popcll(m & ((1ull << lane) - 1))] = j == 0 ? rA : rB;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The lists of the second pass: a stable counting sort of the requests by class byte, the largest class (the longest pass) first, in
+// three small kernels without atomics — per block of MSW_SORT_CHUNK requests a histogram; one wave that turns the histograms into
+// every block's first place per class and the class offsets; the scatter.  A wave ranks its 64 requests with one ballot per class
+// present, lane c - 1 keeps the count of class c.  What comes out, in d_tail (msw_tail_ints):
+//   off[o], o = 0..MSW_NCLS: where the members of class MSW_NCLS - o start in sorted[] (off[MSW_NCLS]: how many there are)
+//   ioff[o]: the same in work items of msw_rev2_kernel: consecutive members of a class are a pair, an odd last one rides alone
+//   sorted[]: the request indices, every class in request order
+// ---------------------------------------------------------------------------------------------------------------------
+template <bool SCATTER>
+__global__ __launch_bounds__(64) void msw_cls_sort_kernel(int n_req, const uint8_t *__restrict__ cls, int *__restrict__ hist, const int *__restrict__ off,
+                                                          int *__restrict__ sorted)
+{
+	const int lane = threadIdx.x;
+	const int k0 = blockIdx.x * MSW_SORT_CHUNK, k1 = min(n_req, k0 + MSW_SORT_CHUNK);
+	// lane c - 1: how many of class c so far (histogram), or where the next one of class c goes (scatter)
+	int mine = 0;
+	if (SCATTER && lane < MSW_NCLS) mine = off[MSW_NCLS - 1 - lane] + hist[(size_t)blockIdx.x * MSW_NCLS + lane];
+	for (int kb = k0; kb < k1; kb += 64) {
+		const int k = kb + lane;
+		const int c = k < k1 ? (int)cls[k] : 0;
+		unsigned long long todo = __builtin_amdgcn_ballot_w64(c > 0 && c <= MSW_NCLS);
+		while (todo) {
+			const int cl = __shfl(c, __ffsll((long long)todo) - 1);
+			const unsigned long long m = __builtin_amdgcn_ballot_w64(c == cl);
+			if (SCATTER) {
+				const int at = __shfl(mine, cl - 1);
+				if (c == cl) sorted[at + __popcll(m & ((1ull << lane) - 1))] = k;
+			}
+			if (lane == cl - 1) mine += __popcll(m);
+			todo &= ~m;
+		}
+	}
+	if (!SCATTER && lane < MSW_NCLS) hist[(size_t)blockIdx.x * MSW_NCLS + lane] = mine;
+}
+
+// hist[b][c]: the count of class c + 1 in block b -> how many of that class the blocks before b hold; off[] / ioff[]
+__global__ __launch_bounds__(64) void msw_cls_scan_kernel(int n_blocks, int *__restrict__ hist, int *__restrict__ off, int *__restrict__ ioff)
+{
+	__shared__ int tot[MSW_NCLS];
+	const int lane = threadIdx.x;
+	if (lane < MSW_NCLS) {
+		int run = 0;
+		for (int b = 0; b < n_blocks; ++b) {
+			const int t = hist[(size_t)b * MSW_NCLS + lane];
+			hist[(size_t)b * MSW_NCLS + lane] = run;
+			run += t;
+		}
+		tot[lane] = run;
+	}
+	__syncthreads();
+	if (lane == 0) {
+		int at = 0, iat = 0;
+		for (int o = 0; o < MSW_NCLS; ++o) {
+			off[o] = at; ioff[o] = iat;
+			const int n = tot[MSW_NCLS - 1 - o];
+			at += n; iat += (n + 1) >> 1;
+		}
+		off[MSW_NCLS] = at; ioff[MSW_NCLS] = iat;
 	}
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // msw_tail_kernel: what follows the forward pass of the alignments msw2_kernel listed (score >= minsc, not saturated) — score2 / te2
 // from the row maxima and the reverse pass that finds where the alignment starts — 16 alignments per wave, one per quad, all of them
-// live.  A wave runs in lockstep as long as its longest reverse pass (rows ~ score / a, cells ~ qe), so msw2_kernel sorts the
-// alignments into buckets by score and qe and this kernel takes the buckets one after the other, the long ones first.
+// live.  A wave runs in lockstep as long as its longest reverse pass (rows ~ score / a, cells ~ qe), so it takes the alignments in
+// the order of the class sort, the long ones first.  This is the path of MPIBWA_MSW_REV2=0; msw_rev2_kernel is the default.
 // b[] scan: each lane of a quad fetches 16 of the next 64 row maxima (independent loads, all in flight at once), the quad parks them in
 // LDS and every lane applies the sequential run rule of src/ksw.c:196-226 to the 64 values in row order.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, const int *__restrict__ tail_n, const int *__restrict__ tail_list, int tail_cap,
+__global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, const int *__restrict__ cls_off, const int *__restrict__ sorted,
                                                       const MswReq *__restrict__ req, const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
                                                       const int *__restrict__ lens, const uint8_t *__restrict__ pac, MswRes *__restrict__ res,
                                                       const uint16_t *__restrict__ rows)
@@ -598,16 +661,11 @@ __global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, co
 	uint16_t *blk = (uint16_t *)lds_t;                       // [16 quads][64 rows]: the row maxima of the b[] block in hand
 	uint32_t *cell = lds_t + 16 * 64 / 2;                    // msw_pass's layout
 	const int lane = threadIdx.x, j = lane & 3, quad = lane >> 2;
-	// the slot in the concatenation of the buckets, long reverse passes first
-	int slot = blockIdx.x * 16 + quad, b = MSW_TAIL_BUCKETS - 1;
-	for (; b >= 0; --b) {
-		const int n = tail_n[b];
-		if (slot < n) break;
-		slot -= n;
-	}
-	const bool live = b >= 0;
+	// the slot in the sorted list, long reverse passes first
+	const int slot = blockIdx.x * 16 + quad;
+	const bool live = slot < cls_off[MSW_NCLS];
 	if (!__any(live)) return;
-	const int r = live ? tail_list[(size_t)b * tail_cap + slot] : 0;
+	const int r = live ? sorted[slot] : 0;
 	MswReq rq;
 	rq.rb = rq.re = 0; rq.read = 0; rq.is_rev = 0;
 	MswRes out;
@@ -679,6 +737,229 @@ __global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, co
 	if (live && j == 0) res[r] = out;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// msw_rev2_kernel: what msw_tail_kernel does, for TWO alignments of one class per quad, the reverse passes in the packed arithmetic of
+// msw2_kernel's forward pass (msw2_cell).  The two rarely share a query — the query of a reverse pass is the reversed prefix 0..qe of
+// its own mate — but they share slen2, and with it S2, the segment ends and the hand-over points.  So every half has its own request,
+// its own te and qe from res[], its own code set (codesA / codesB, positions qe .. 0 padded to 16 slen2 with MSW_PAD; the segment flags
+// in codesA alone) and its own target bases, and the score of a cell is two lookups or'ed together: (target base, code) of A in a
+// table that holds the score in the low half, of B in one that holds it in the high half.  Half X has te_X + 1 rows (row i reads
+// rb_X + te_X - i); past them it repeats its last row and nothing of it is kept.  KSW_XSTOP is per half: once a row raises X's maximum
+// to its forward score (or to the 8-bit ceiling: flags = 1 for X alone) X is done and frozen; the quad stops when both are done or out of
+// rows.  The b[] scan is msw_tail_kernel's, run for A and then for B; its block of row maxima shares LDS with the pass's row state.
+// A work item is (class, pair): slot -> class by ioff[], the pair's members are neighbours in sorted[].
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void msw_rev2_kernel(MswParams P, int n_req, const int *__restrict__ cls_off, const int *__restrict__ cls_ioff,
+                                                      const int *__restrict__ sorted, const MswReq *__restrict__ req, const uint8_t *__restrict__ seq,
+                                                      const int64_t *__restrict__ off, const int *__restrict__ lens, const uint8_t *__restrict__ pac,
+                                                      MswRes *__restrict__ res, const uint16_t *__restrict__ rows, int s_max)
+{
+	extern __shared__ uint32_t lds_r[];
+	const int cell_words = max(s_max * 64, 16 * 64 / 2), code_words = ((s_max + 7) >> 3) * 64;
+	uint32_t *cell = lds_r;                                  // [s_max][64]: H_A, E_A, H_B, E_B as bytes
+	uint16_t *blk = (uint16_t *)lds_r;                       // [16 quads][64 rows]: the b[] block in hand (before the pass)
+	uint32_t *codesA = lds_r + cell_words, *codesB = codesA + code_words;   // eight 4-bit entries per dword, as in msw2_kernel
+	uint32_t *tabA = codesB + code_words, *tabB = tabA + 32;                // [4 target bases][8 codes] -> score (low half), score << 16
+	const int lane = threadIdx.x, j = lane & 3, quad = lane >> 2;
+	if (lane < 32) {
+		const int t = lane >> 3, q = lane & 7;
+		const int s = q < 4 ? (int)(int8_t)(msw_slo(P, t) >> (8 * q)) : q == 4 ? msw_s4(P, t) : 0;
+		tabA[lane] = (uint32_t)(uint16_t)(int16_t)s;
+		tabB[lane] = (uint32_t)(uint16_t)(int16_t)s << 16;
+	}
+	// the work item: slot -> class (the largest first) -> two neighbours of the class's stretch of sorted[]
+	const int slot = blockIdx.x * 16 + quad;
+	const bool live = slot < cls_ioff[MSW_NCLS];
+	if (!__any(live)) return;
+	int o = 0;
+	if (live) while (slot >= cls_ioff[o + 1]) ++o;
+	const int m0 = live ? cls_off[o] + 2 * (slot - cls_ioff[o]) : 0;
+	const bool hasB = live && m0 + 1 < cls_off[o + 1];
+	const int rA = live ? sorted[m0] : 0, rB = hasB ? sorted[m0 + 1] : 0;
+	MswReq qa, qb;
+	qa.rb = qa.re = 0; qa.read = 0; qa.is_rev = 0; qb = qa;
+	MswRes oA, oB;
+	oA.score = 0; oA.te = -1; oA.qe = -1; oA.score2 = -1; oA.te2 = -1; oA.tb = -1; oA.qb = -1; oA.flags = 0; oB = oA;
+	if (live) { qa = req[rA]; oA = res[rA]; }
+	if (hasB) { qb = req[rB]; oB = res[rB]; }
+	const int qlenA = live ? lens[qa.read] : 0, qlenB = hasB ? lens[qb.read] : 0;
+	const uint8_t *msA = seq + (live ? off[qa.read] : 0), *msB = seq + (hasB ? off[qb.read] : 0);
+	const int minsc = P.min_seed_len * P.a;
+	const int sat_limit = 255 - P.shift;
+	// ---- b[]: runs of rows whose maximum reaches minsc; second best = best run outside te +- ceil(score / max) ----
+	uint16_t *qblk = blk + quad * 64;
+	auto scan = [&](bool has, int r, int tlen, MswRes &out) {
+		const int d = (out.score + P.max_sc - 1) / P.max_sc;
+		const int low = out.te - d, high = out.te + d;
+		int last_sc = -1, last_i = -1, sc2 = -1, te2 = -1;
+		int twave = has ? tlen : 0;
+		for (int s = 32; s; s >>= 1) twave = max(twave, __shfl_xor(twave, s));
+		for (int i0 = 0; i0 < twave; i0 += 64) {
+			uint16_t v[16];
+#pragma unroll
+			for (int u = 0; u < 16; ++u) {
+				const int i = i0 + u * 4 + j;
+				v[u] = has && i < tlen ? rows[(size_t)i * n_req + r] : (uint16_t)0;
+			}
+			bool any = false;
+#pragma unroll
+			for (int u = 0; u < 16; ++u) {
+				qblk[u * 4 + j] = v[u];
+				any |= has && i0 + u * 4 + j < tlen && (int)v[u] >= minsc;
+			}
+			if (!__any(any)) continue;
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			const int kend = has ? min(64, tlen - i0) : 0;
+			for (int k = 0; k < kend; ++k) {
+				const int i = i0 + k, im = qblk[k];
+				if (im < minsc) continue;
+				if (last_i < 0 || last_i + 1 != i) {
+					if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
+					last_sc = im; last_i = i;
+				} else if (last_sc < im) { last_sc = im; last_i = i; }
+			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		}
+		if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
+		out.score2 = sc2; out.te2 = te2;
+	};
+	scan(live, rA, (int)(qa.re - qa.rb), oA);
+	scan(hasB, rB, (int)(qb.re - qb.rb), oB);
+	// ---- set-up of the reverse pass: the codes of positions qe .. 0 of each half, padded, dealt to the quad; H and E cleared ----
+	int qlen2A = live ? oA.qe + 1 : 0, qlen2B = hasB ? oB.qe + 1 : 0;
+	if (oA.qe >= qlenA) qlen2A = 0;   // cannot happen (the maximum of a row is reached on a real base first); stay in bounds
+	if (oB.qe >= qlenB) qlen2B = 0;
+	const int slen2 = (max(qlen2A, qlen2B) + 15) / 16, S2 = slen2 * 4;   // (one class: the same for both)
+	const int tnA = qlen2A > 0 ? oA.te + 1 : 0, tnB = qlen2B > 0 ? oB.te + 1 : 0;
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	if (live) {
+		for (int kk = 0; kk < S2; ++kk) cell[kk * 64 + lane] = 0;
+		for (int c = 0; c * 8 < S2; ++c) {
+			uint32_t ca = 0, cb = 0;
+			for (int u = 0; u < 8 && c * 8 + u < S2; ++u) {
+				const int k = j * S2 + c * 8 + u;
+				const uint32_t a = k < qlen2A ? msw_code(msA, qlenA, qa.is_rev, qlen2A - 1 - k) : MSW_PAD;
+				const uint32_t b = k < qlen2B ? msw_code(msB, qlenB, qb.is_rev, qlen2B - 1 - k) : MSW_PAD;
+				ca |= (a | ((k + 1) % slen2 == 0 ? 8u : 0u)) << (4 * u);
+				cb |= b << (4 * u);
+			}
+			codesA[c * 64 + lane] = ca; codesB[c * 64 + lane] = cb;
+		}
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	// the segment length when every live quad of the wave has the same one (the rule: a wave is of one class but where two meet)
+	int slen_u = 0;
+	{
+		const unsigned long long lv = __builtin_amdgcn_ballot_w64(live);
+		const int first = __builtin_amdgcn_readlane(slen2, __ffsll((long long)lv) - 1);
+		slen_u = __builtin_amdgcn_ballot_w64(live && slen2 != first) ? 0 : first;
+	}
+	// ---- the reverse pass of both ----
+	int gmaxA = 0, teA = -1, qeA = -1, gmaxB = 0, teB = -1, qeB = -1, satA = 0, satB = 0;
+	auto reverse = [&](auto uniform_segments) {
+		constexpr bool UNI = decltype(uniform_segments)::value;
+		const int tn = tnA > tnB ? tnA : tnB;
+		bool run = live && tn > 0 && S2 > 0;
+		const Msw2Gap G = {s2_splat(P.o_del + P.e_del), s2_splat(P.o_ins + P.e_ins), s2_splat(P.e_del), s2_splat(P.e_ins)};
+		int Swave = run ? S2 : 0;
+		for (int s = 32; s; s >>= 1) Swave = max(Swave, __shfl_xor(Swave, s));
+		uint32_t co_diag = 0, co_fseg = 0, co_ffull = 0, co_key = 0;
+		auto base_at = [&](const MswReq &rq, int tnx, int i) -> int {   // (rows past the end of the shorter pass: its last row again, results unused)
+			const int ii = i < tnx ? i : tnx - 1;
+			return ii >= 0 ? msw_base(pac, P.l_pac, rq.rb + (tnx - 1 - ii)) : 0;   // row i of the reverse pass: rb + te - i
+		};
+		int ta_next = (run && j == 0) ? base_at(qa, tnA, 0) : 0, tb_next = (run && j == 0) ? base_at(qb, tnB, 0) : 0;
+		bool doneA = tnA <= 0, doneB = tnB <= 0;
+		for (int t = 0; __any(run); ++t) {
+			const int i = t - j;
+			const bool act = run && i >= 0 && i < tn;
+			const int ta = ta_next, tb = tb_next;
+			if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base_at(qa, tnA, i + 1); tb_next = base_at(qb, tnB, i + 1); }
+			const uint32_t *srowA = tabA + (ta << 3), *srowB = tabB + (tb << 3);
+			const uint32_t ci_diag = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_diag), ci_fseg = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_fseg);
+			const uint32_t ci_ffull = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_ffull);
+			const uint32_t ci_key = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_key);
+			msw_s2 diag = s2_of(j ? ci_diag : 0u), fseg = s2_of(j ? ci_fseg : 0u), ffull = s2_of(j ? ci_ffull : 0u);
+			msw_u2 key = __builtin_bit_cast(msw_u2, j ? ci_key : 0u);   // per alignment: h * 256 + (255 - position), as in msw2_kernel
+			msw_u2 c256 = {256, 256};
+			asm volatile("" : "+v"(c256));
+			msw_u2 poscv = {(unsigned short)(248 - j * S2), (unsigned short)(248 - j * S2)};
+			const int kmax = act ? S2 : 0;
+			auto step = [&](uint32_t &w, uint32_t cda, uint32_t cdb, int u, bool seg_end, msw_u2 &mblk) {
+				uint32_t qA = __builtin_amdgcn_ubfe(cda, 4 * u, 3), qB = __builtin_amdgcn_ubfe(cdb, 4 * u, 3);
+				asm("" : "+v"(qA));
+				asm("" : "+v"(qB));
+				msw2_cell<UNI>(w, s2_of(srowA[qA] | srowB[qB]), cda, u, seg_end, G, c256, diag, fseg, ffull, mblk);
+			};
+			int seg_pos = 0;
+			const msw_u2 eight = {8, 8};
+			for (int c = 0; c * 8 < Swave; ++c, poscv -= eight) {
+				const uint32_t cda = c * 8 < kmax ? codesA[c * 64 + lane] : 0u, cdb = c * 8 < kmax ? codesB[c * 64 + lane] : 0u;
+				msw_u2 mblk = {0, 0};
+#pragma unroll
+				for (int u = 0; u < 8; u += 2) {
+					const int k = c * 8 + u;
+					bool end0 = false, end1 = false;
+					if constexpr (UNI) {
+						end0 = ++seg_pos == slen_u; if (end0) seg_pos = 0;
+						end1 = ++seg_pos == slen_u; if (end1) seg_pos = 0;
+					}
+					if (k < kmax) {
+						uint32_t w0 = cell[k * 64 + lane], w1 = cell[(k + 1) * 64 + lane];
+						step(w0, cda, cdb, u, end0, mblk); step(w1, cda, cdb, u + 1, end1, mblk);
+						cell[k * 64 + lane] = w0; cell[(k + 1) * 64 + lane] = w1;
+					}
+				}
+				if (c * 8 < kmax) key = __builtin_elementwise_max(key, mblk + poscv);
+			}
+			const uint32_t keyAB = __builtin_bit_cast(uint32_t, key);
+			if (act) { co_diag = u_of(diag); co_fseg = u_of(fseg); co_ffull = u_of(ffull); co_key = keyAB; }
+			int stop = 0;
+			if (act && j == 3) {
+				if (i < tnA && !doneA) {
+					const int imax = (int)(keyAB >> 8 & 0xff);
+					if (imax > gmaxA) {
+						gmaxA = imax; teA = i; qeA = 255 - (int)(keyAB & 0xff);
+						if (gmaxA >= sat_limit) { satA = 1; doneA = true; }
+						if (gmaxA >= oA.score) doneA = true;   // KSW_XSTOP at the forward score
+					}
+				}
+				if (i < tnB && !doneB) {
+					const int imax = (int)(keyAB >> 24);
+					if (imax > gmaxB) {
+						gmaxB = imax; teB = i; qeB = 255 - (int)(keyAB >> 16 & 0xff);
+						if (gmaxB >= sat_limit) { satB = 1; doneB = true; }
+						if (gmaxB >= oB.score) doneB = true;
+					}
+				}
+				if ((i + 1 >= tnA || doneA) && (i + 1 >= tnB || doneB)) stop = 1;
+			}
+			stop = msw_dpp<MSW_QP(3, 3, 3, 3)>(stop);
+			if (stop) run = false;
+		}
+	};
+	if (slen_u > 0) reverse(std::true_type{});
+	else reverse(std::false_type{});
+	// ---- the records: lane 0 completes A's, lane 1 B's ----
+	gmaxA = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxA); teA = msw_dpp<MSW_QP(3, 3, 3, 3)>(teA); qeA = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeA);
+	gmaxB = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxB); teB = msw_dpp<MSW_QP(3, 3, 3, 3)>(teB); qeB = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeB);
+	satA = msw_dpp<MSW_QP(3, 3, 3, 3)>(satA); satB = msw_dpp<MSW_QP(3, 3, 3, 3)>(satB);
+	auto complete = [&](MswRes &out, int qlen2, int gs, int gte, int gqe, int gsat) {
+		if (qlen2 > 0 && gs == out.score) { out.tb = out.te - gte; out.qb = out.qe - gqe; }
+		if (qlen2 == 0 || gsat) out.flags = 1;
+	};
+	if (live && j == 0) { complete(oA, qlen2A, gmaxA, teA, qeA, satA); res[rA] = oA; }
+	if (hasB && j == 1) { complete(oB, qlen2B, gmaxB, teB, qeB, satB); res[rB] = oB; }
+}
+
 } // namespace
 
 size_t msw_lds_bytes(int max_len)
@@ -697,10 +978,17 @@ size_t msw_tail_lds_bytes(int max_len)
 	return 16 * 64 * sizeof(uint16_t) + msw_lds_bytes(max_len);   // the b[] block of every quad + msw_pass's rows
 }
 
+size_t msw_rev2_lds_bytes(int max_len)
+{
+	const int s_max = (max_len + 15) / 16 * 16 / 4;
+	// the row state (the b[] block of every quad before it, in the same place), two code sets, two score tables
+	return ((size_t)std::max(s_max * 64, 16 * 64 / 2) + 2 * (size_t)((s_max + 7) / 8) * 64 + 64) * 4;
+}
+
 // MPIBWA_CPUSEC diagnostic (waits for the launch): how many alignments of msw2_kernel's work items reach min_seed_len * a — those go
 // through the b[] scan and the reverse pass — and how many waves of 16 work items hold at least one such alignment as their first (A)
 // or second (B) request, i.e. would run that tail in lockstep if the tails ran in the forward kernel
-static void msw_tail_census(void *stream, const MswParams &P, int n_req, int n_pairs, const int *h_list, const MswRes *d_res)
+static void msw_tail_census(void *stream, const MswParams &P, int n_req, int n_pairs, const int *h_list, const MswRes *d_res, const int *d_tail)
 {
 	std::vector<MswRes> res((size_t)n_req);
 	HIP_OK(hipStreamSynchronize((hipStream_t)stream));
@@ -718,6 +1006,39 @@ static void msw_tail_census(void *stream, const MswParams &P, int n_req, int n_p
 	}
 	fprintf(stderr, "[msw] packed work items: %ld + %ld alignments reach min_seed_len*a (%d); of %d waves, %ld hold an A hit, %ld a B hit\n", hits_a, hits_b,
 	        minsc, (n_pairs + 15) / 16, waves_a, waves_b);
+	// the second passes by class, as the device sorted them: members by slen2 and by score class, pairs and alone-riders
+	int off[MSW_NCLS + 1], ioff[MSW_NCLS + 1];
+	HIP_OK(hipMemcpy(off, d_tail, sizeof(off), hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(ioff, d_tail + MSW_OFF_INTS, sizeof(ioff), hipMemcpyDeviceToHost));
+	long by_sc[3] = {0, 0, 0};
+	fprintf(stderr, "[msw] second passes: %d in %d quads (%d pairs, %d alone); by slen2 1..16:", off[MSW_NCLS], ioff[MSW_NCLS], off[MSW_NCLS] - ioff[MSW_NCLS],
+	        2 * ioff[MSW_NCLS] - off[MSW_NCLS]);
+	for (int sl = 1; sl <= 16; ++sl) {
+		long n = 0;
+		for (int sb = 0; sb < 3; ++sb) {
+			const int o = MSW_NCLS - (1 + (sl - 1) * 3 + sb);
+			n += off[o + 1] - off[o]; by_sc[sb] += off[o + 1] - off[o];
+		}
+		fprintf(stderr, " %ld", n);
+	}
+	fprintf(stderr, "; by score class: %ld %ld %ld\n", by_sc[0], by_sc[1], by_sc[2]);
+}
+
+// MPIBWA_MSW_REV2=0: every second pass on its own quad through msw_tail_kernel (the A/B of msw_rev2_kernel); read once per process
+static bool msw_rev2_on()
+{
+	static const bool on = !(getenv("MPIBWA_MSW_REV2") && atoi(getenv("MPIBWA_MSW_REV2")) == 0);
+	return on;
+}
+
+void msw_tail_counts(const int *d_tail, uint64_t out[4])
+{
+	int off[MSW_NCLS + 1], ioff[MSW_NCLS + 1];
+	HIP_OK(hipMemcpy(off, d_tail, sizeof(off), hipMemcpyDeviceToHost));
+	HIP_OK(hipMemcpy(ioff, d_tail + MSW_OFF_INTS, sizeof(ioff), hipMemcpyDeviceToHost));
+	const uint64_t members = (uint64_t)off[MSW_NCLS], items = msw_rev2_on() ? (uint64_t)ioff[MSW_NCLS] : members;
+	out[0] = members - items; out[1] = 2 * items - members;   // members = 2 pairs + alone, items = pairs + alone
+	out[2] = 0; out[3] = items;                               // (no second pass has a register form)
 }
 
 // The segment lengths msw2_kernel is instantiated for with its state in registers (reads of 65-80, 97-112, 113-128, 145-160, 193-208 and
@@ -739,17 +1060,19 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 {
 	if (n_req <= 0) return;
 	const size_t lds = msw_lds_bytes(max_len), lds2 = msw2_lds_bytes(max_len), lds_t = msw_tail_lds_bytes(max_len);
+	const size_t lds_r = msw_rev2_lds_bytes(max_len);
 	if (lds > 160 * 1024) die("mate-rescue kernel: reads of %d bp do not fit the LDS row buffers", max_len);
-	static size_t s_attr = 0, s_attr2 = 0, s_attr_t = 0;
+	static size_t s_attr = 0, s_attr2 = 0, s_attr_t = 0, s_attr_r = 0;
 	if (lds > s_attr) {
 		HIP_OK(hipFuncSetAttribute((const void *)msw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		s_attr = lds;
 	}
 	static const bool pairing = !(getenv("MPIBWA_MSW_PAIRS") && atoi(getenv("MPIBWA_MSW_PAIRS")) == 0);
 	static const bool regs_form = !(getenv("MPIBWA_MSW_REGS") && atoi(getenv("MPIBWA_MSW_REGS")) == 0);   // 0: every work item in the general form (the A/B)
+	const bool rev2 = msw_rev2_on();
 	int n_pairs = 0, n_single = n_req;
 	const int *d_single = nullptr;
-	if (pairing && h_req && h_len && h_list && d_list && d_tail && lds2 <= 160 * 1024 && lds_t <= 160 * 1024) {
+	if (pairing && h_req && h_len && h_list && d_list && d_tail && lds2 <= 160 * 1024 && lds_t <= 160 * 1024 && lds_r <= 160 * 1024) {
 		// two requests next to each other for the same mate in the same orientation (mem_sam_pe lists an end's anchors one after the
 		// other: the windows of a repeat read's anchors are such runs), both in the byte flavour
 		// work items of msw2_kernel from the front of the list (two ints each; a byte-flavour request without a partner: (k, -1)), the
@@ -803,11 +1126,19 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 				HIP_OK(hipFuncSetAttribute((const void *)msw_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
 				s_attr_t = lds_t;
 			}
+			if (lds_r > s_attr_r) {
+				HIP_OK(hipFuncSetAttribute((const void *)msw_rev2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
+				s_attr_r = lds_r;
+			}
 			// the forward passes, then — same stream, before the next batch reuses d_rows — the second passes of the alignments they
-			// listed: at most one per byte-flavour request, so (2 n_pairs - n_alone) / 16 waves are enough; the ones without work return
+			// gave a class: the class bytes sorted into lists (three small launches), then two of a class per quad (msw_rev2_kernel).
+			// Grids from the worst case — every byte-flavour request has a class, and every class an odd member — nothing is read
+			// back; the waves without work return.
 			const int s_max = (max_len + 15) / 16 * 16 / 4;
-			int *d_tail_n = d_tail, *d_tail_list = d_tail + 16;
-			HIP_OK(hipMemsetAsync(d_tail_n, 0, MSW_TAIL_BUCKETS * sizeof(int), (hipStream_t)stream));
+			int *d_coff = d_tail, *d_cioff = d_tail + MSW_OFF_INTS, *d_sorted = d_tail + 2 * MSW_OFF_INTS;
+			uint8_t *d_cls = (uint8_t *)(d_sorted + n_req);
+			int *d_hist = d_sorted + n_req + ((size_t)n_req + 3) / 4;
+			HIP_OK(hipMemsetAsync(d_cls, 0, (size_t)n_req, (hipStream_t)stream));
 			for (int o = 0; o <= MSW_REGS_CLASSES; ++o) {
 				const int c = order[o], n = cls_n[c];
 				if (!n) continue;
@@ -815,7 +1146,7 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 				const dim3 grid((n + 15) / 16);
 #define MSW2_LAUNCH(SLEN) \
 	hipLaunchKernelGGL(msw2_kernel<SLEN>, grid, dim3(64), (SLEN) ? 128 * sizeof(uint32_t) : lds2, (hipStream_t)stream, P, n, n_req, d_items, d_req, d_seq, d_off, d_len, \
-	                   d_pac, d_res, d_rows, s_max, d_tail_n, d_tail_list, n_req)
+	                   d_pac, d_res, d_rows, s_max, d_cls)
 				switch (c < MSW_REGS_CLASSES ? msw_regs_slen[c] : 0) {
 				case 5: MSW2_LAUNCH(5); break;
 				case 7: MSW2_LAUNCH(7); break;
@@ -827,9 +1158,18 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 				}
 #undef MSW2_LAUNCH
 			}
-			const int n_byte = 2 * n_pairs - n_alone;
-			hipLaunchKernelGGL(msw_tail_kernel, dim3((n_byte + 15) / 16), dim3(64), lds_t, (hipStream_t)stream, P, n_req, (const int *)d_tail_n,
-			                   (const int *)d_tail_list, n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, (const uint16_t *)d_rows);
+			const int n_byte = 2 * n_pairs - n_alone, n_blocks = (n_req + MSW_SORT_CHUNK - 1) / MSW_SORT_CHUNK;
+			hipLaunchKernelGGL(msw_cls_sort_kernel<false>, dim3(n_blocks), dim3(64), 0, (hipStream_t)stream, n_req, (const uint8_t *)d_cls, d_hist,
+			                   (const int *)d_coff, d_sorted);
+			hipLaunchKernelGGL(msw_cls_scan_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, n_blocks, d_hist, d_coff, d_cioff);
+			hipLaunchKernelGGL(msw_cls_sort_kernel<true>, dim3(n_blocks), dim3(64), 0, (hipStream_t)stream, n_req, (const uint8_t *)d_cls, d_hist,
+			                   (const int *)d_coff, d_sorted);
+			if (rev2)
+				hipLaunchKernelGGL(msw_rev2_kernel, dim3((n_byte / 2 + MSW_NCLS + 15) / 16), dim3(64), lds_r, (hipStream_t)stream, P, n_req, (const int *)d_coff,
+				                   (const int *)d_cioff, (const int *)d_sorted, d_req, d_seq, d_off, d_len, d_pac, d_res, (const uint16_t *)d_rows, s_max);
+			else
+				hipLaunchKernelGGL(msw_tail_kernel, dim3((n_byte + 15) / 16), dim3(64), lds_t, (hipStream_t)stream, P, n_req, (const int *)d_coff,
+				                   (const int *)d_sorted, d_req, d_seq, d_off, d_len, d_pac, d_res, (const uint16_t *)d_rows);
 		}
 	}
 	if (n_single)
@@ -837,7 +1177,7 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 		                   d_res, d_rows);
 	HIP_OK(hipGetLastError());
 	static const bool say = getenv("MPIBWA_CPUSEC") != nullptr;
-	if (say && n_pairs) msw_tail_census(stream, P, n_req, n_pairs, h_list, d_res);
+	if (say && n_pairs) msw_tail_census(stream, P, n_req, n_pairs, h_list, d_res, d_tail);
 }
 
 } // namespace mbw

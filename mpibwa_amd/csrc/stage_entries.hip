@@ -653,11 +653,19 @@ extern "C" int mi355x_extend_batch2(const mem_opt_t *opt, int n, const uint8_t *
 // Stage-level entry point of the mate-rescue alignment (tests, micro-benchmarks): n_req windows [rb,re) of the packed
 // reference `pac` (doubled coordinate, 2 bits per base, l_pac bases) against reads of a batch given as nt4 codes.
 // out8 per request: score, te, qe, score2, te2, tb, qb, flags — kswr_t of ksw_align2 with mem_matesw's flags.
+// what the second pass of the last mi355x_matesw_batch ran: pairs, alone-riders, work items of a register launch, of the general launch
+static uint64_t g_matesw_counts[4];
+extern "C" void mi355x_matesw_batch_counts(uint64_t out[4])
+{
+	for (int i = 0; i < 4; ++i) out[i] = g_matesw_counts[i];
+}
+
 extern "C" int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, int n_reads, const uint8_t *reads, const int64_t *off,
                                    int n_req, const int64_t *rb, const int64_t *re, const int *read, const int *is_rev, int *out8,
                                    double *kernel_ms)
 {
 	require_any_device();
+	for (int i = 0; i < 4; ++i) g_matesw_counts[i] = 0;
 	if (n_req <= 0) return 0;
 	static_assert(sizeof(MswRes) == 32, "MswRes layout");
 	if (!msw_on_device(opt)) {   // options the kernels do not take: every request is handed back (flags = 1: recompute on the host)
@@ -685,12 +693,14 @@ extern "C" int mi355x_matesw_batch(const mem_opt_t *opt, int64_t l_pac, const ui
 	DevArr<uint16_t> d_rows((size_t)n_req * max_t * 2);
 	std::vector<int> h_list(2 * (size_t)n_req + 16);
 	DevArr<int> d_list((2 * (size_t)n_req + 16) * sizeof(int)), d_tail(msw_tail_ints(n_req) * sizeof(int));
+	d_tail.fill(0, 2 * MSW_OFF_INTS * sizeof(int));   // (a call without a packed launch leaves the class offsets alone: nothing ran)
 	Timer tm;
 	tm.start(st);
 	launch_msw(st, msw_params(opt, l_pac), n_req, d_req, d_seq, d_off, d_len, d_pac, d_res, d_rows, max_len, rq.data(), R.lens.data(), h_list.data(), d_list,
 	           d_tail);
 	double ms = tm.stop(st);
 	HIP_OK(hipGetLastError());
+	msw_tail_counts(d_tail, g_matesw_counts);
 	d_res.download(out8, (size_t)n_req * sizeof(MswRes));
 	if (kernel_ms) *kernel_ms = ms;
 	return 0;
