@@ -615,6 +615,23 @@ size_t  mi355x_bgzf_eof(uint8_t out[28]);
  * buffers back.  mi355x_bgzf_dev_counts: blocks, blocks written stored, bytes of text, bytes of blocks — since load, all callers. */
 size_t  mi355x_bgzf_compress_dev(const char *text, size_t len, uint8_t *out, size_t cap);
 void    mi355x_bgzf_dev_counts(uint64_t out[4]);
+/* BGZF input.  A BGZF file is a chain of independent gzip members of at most 64 KiB, each with its size in the header
+ * (BSIZE) and its text's size in the trailer (ISIZE), so a file can be entered anywhere and its blocks inflated side by side.
+ * mi355x_bgzf_find_block: the first offset of buf at which a block starts — a header (1f 8b 08 04 .. XLEN 6, 'B' 'C' 02 00, BSIZE) from
+ * which the BSIZE hops meet two more headers or, with at_eof, the end of buf exactly; -1 when there is none, -2 when more bytes are
+ * needed to decide.  mi355x_bgzf_scan: the headers from offset 0, at most cap blocks: blk_off[i] = start of block i, blk_off[n] = end of
+ * the last whole block, text_off[i] = sum of the ISIZEs before block i (arrays of cap + 1); returns n, or -(offset) - 1 of a header that
+ * is not one.  mi355x_bgzf_inflate: whole blocks to their text in out[cap] by zlib on the rank's host threads, every block's CRC32 and
+ * ISIZE checked; returns the text's size, -(offset of the first failing block) - 1, or 0 with nothing written when cap is too small.
+ * mi355x_bgzf_inflate_dev: the same results from the device decoder (one wavefront per block).  Needs a usable MI355X, no CPU
+ * fallback; re-entrant, with or without a resident index, also beside mem_process_seqs and mi355x_bgzf_compress_dev calls in flight;
+ * mi355x_finalize() gives its buffers back.  mi355x_bgzf_inflate_dev_counts: blocks, blocks that failed, compressed bytes, text bytes
+ * — since load, all callers. */
+int64_t mi355x_bgzf_find_block(const uint8_t *buf, int64_t len, int at_eof);
+int64_t mi355x_bgzf_scan(const uint8_t *buf, int64_t len, int64_t cap, int64_t *blk_off, int64_t *text_off);
+int64_t mi355x_bgzf_inflate(const uint8_t *in, size_t len, char *out, size_t cap);
+int64_t mi355x_bgzf_inflate_dev(const uint8_t *in, size_t len, char *out, size_t cap);
+void    mi355x_bgzf_inflate_dev_counts(uint64_t out[4]);
 /* mpiBWAByChr's routing (src/mainParallelByChromosome.c:1340-1455, :3437-3486): the records of `sam` by destination — contig
  * 0 .. n_seqs-1 by RNAME, then "discordant" (only when discordant != 0; a record whose RNAME and RNEXT are two different contigs
  * goes to its contig AND there), last "unmapped" (RNAME '*').  out_text[d] (malloc, NULL when empty) / out_len[d] for

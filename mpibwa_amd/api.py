@@ -104,6 +104,11 @@ def load_library(build_if_missing=True):
     sig("mi355x_bgzf_eof", C.c_size_t, [C.c_void_p])
     sig("mi355x_bgzf_compress_dev", C.c_size_t, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t])
     sig("mi355x_bgzf_dev_counts", None, [P(C.c_uint64)])
+    sig("mi355x_bgzf_find_block", C.c_int64, [C.c_char_p, C.c_int64, C.c_int])
+    sig("mi355x_bgzf_scan", C.c_int64, [C.c_char_p, C.c_int64, C.c_int64, P(C.c_int64), P(C.c_int64)])
+    sig("mi355x_bgzf_inflate", C.c_int64, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t])
+    sig("mi355x_bgzf_inflate_dev", C.c_int64, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t])
+    sig("mi355x_bgzf_inflate_dev_counts", None, [P(C.c_uint64)])
     sig("mi355x_route_by_chr", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_int, P(C.c_void_p), P(C.c_size_t)])
     sig("bwa_set_rg", C.c_void_p, [C.c_char_p])
     sig("bwa_insert_header", C.c_void_p, [C.c_char_p, C.c_void_p])

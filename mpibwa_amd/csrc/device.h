@@ -579,6 +579,13 @@ void launch_bgzf_deflate(void *stream, const uint8_t *d_text, const uint32_t *d_
 // the slots closed up into d_out; d_meta[0] = the bytes
 void launch_bgzf_gather(void *stream, const uint8_t *d_slots, const uint32_t *d_sizes, int n_blocks, uint8_t *d_out, unsigned long long *d_meta);
 void release_bgzf_contexts();     // the idle ones' buffers and streams (mi355x_finalize)
+// ---- BGZF blocks inflated on the device (bgzf_inflate_kernel.hip, bgzf_in_stage.hip) ----
+// block b = d_comp[d_blk_off[b] .. d_blk_off[b + 1]) (a whole BGZF block: header, deflate stream, CRC32, ISIZE; d_comp holds comp_len bytes)
+// to d_text[d_text_off[b] .. d_text_off[b + 1]) (the ISIZEs' prefix sums, below text_cap); d_status[b] = 0 or inflate_util.h's error.
+// n_blocks workgroups of one wavefront.
+void launch_bgzf_inflate(void *stream, const uint8_t *d_comp, uint32_t comp_len, const uint32_t *d_blk_off, const uint32_t *d_text_off, int n_blocks,
+                         uint8_t *d_text, uint32_t text_cap, uint32_t *d_status);
+void release_bgzf_in_contexts();  // the idle ones' buffers and streams (mi355x_finalize)
 // the calling thread on the device of the resident index, or, before any index, on device 0 after the checks of mi355x_init
 void use_device();
 

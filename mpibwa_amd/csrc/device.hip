@@ -592,4 +592,5 @@ extern "C" void mi355x_finalize(void)
 	g_idx = DevIndex();
 	release_idle_work_buffers();   // a process that is done with this index gives the HBM of its call contexts back too
 	release_bgzf_contexts();
+	release_bgzf_in_contexts();
 }

@@ -18,6 +18,10 @@ extern const uint8_t *const nt4_table_ptr;
 // sampost.cpp: where the BGZF blocks of `len` bytes of text start and end (cut[0] = 0 .. cut[n_blocks] = len), the one rule of the host
 // path and the device path (bgzf_stage.hip)
 void bgzf_cuts(const char *text, size_t len, std::vector<size_t> &cut);
+// sampost.cpp: the block table of `len` bytes of BGZF for both inflate paths (this host path and bgzf_in_stage.hip): blk_off[0 .. n] and
+// text_off[0 .. n] as mi355x_bgzf_scan gives them; returns the offset at which the walk stopped short of len (a header that is not one,
+// a block that the buffer cuts off), or -1 when the whole blocks end at len
+int64_t bgzf_in_plan(const uint8_t *in, size_t len, std::vector<int64_t> &blk_off, std::vector<int64_t> &text_off);
 
 // ---- plain records exchanged between host stages and HIP kernels ----
 

@@ -20,6 +20,7 @@
 #include <zlib.h>
 
 #include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -386,6 +387,116 @@ extern "C" size_t mi355x_bgzf_eof(uint8_t out[28])
 	static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	memcpy(out, eof, 28);
 	return 28;
+}
+
+// ---- BGZF input ----
+// Is there a BGZF block header at p (18 bytes are there)?  1f 8b 08 04, six bytes that any writer may fill (MTIME, XFL, OS), XLEN = 6,
+// the 'BC' field of two bytes, and a BSIZE that leaves room for the header and the trailer.  Returns the block's size or 0.
+static inline int64_t bgzf_header_at(const uint8_t *p)
+{
+	if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4 || p[10] != 6 || p[11] != 0 || p[12] != 'B' || p[13] != 'C' || p[14] != 2 || p[15] != 0) return 0;
+	const int64_t total = (int64_t)(p[16] | p[17] << 8) + 1;
+	return total >= (int64_t)(BGZF_HEAD + BGZF_TAIL) ? total : 0;
+}
+
+// The first offset of buf[0 .. len) at which a BGZF block starts, for a rank that enters a file in the middle; at_eof: buf ends where
+// the file ends.  -1: none; -2: the first candidate cannot be decided without more bytes.
+// The ten fixed bytes of a header do occur inside compressed payload (and a stored block can hold any bytes, a BGZF file for one), so a
+// header alone is no start.  A start is a header from which the BSIZE hops meet TWO more headers (or the end of the file exactly):
+// three headers are 30 fixed bytes at places that the first two name, which no payload has by accident; one more link would not help
+// against a payload built on purpose (a stored block can carry a chain of any length), and the inflate's CRC catches that case.
+extern "C" int64_t mi355x_bgzf_find_block(const uint8_t *buf, int64_t len, int at_eof)
+{
+	for (int64_t o = 0; o < len; ++o) {
+		if (buf[o] != 0x1f) continue;
+		int64_t at = o;
+		int links = 0;
+		for (; links < 3; ++links) {
+			if (at == len && at_eof && links > 0) { links = 3; break; }
+			if (at + (int64_t)BGZF_HEAD > len) {
+				if (!at_eof) return -2;
+				break;
+			}
+			const int64_t total = bgzf_header_at(buf + at);
+			if (!total) break;
+			at += total;
+		}
+		if (links == 3) return o;
+	}
+	return -1;
+}
+
+// The headers of buf[0 .. len) from offset 0, at most cap blocks: blk_off[i] = where block i starts, blk_off[n] = where the last whole
+// block ends; text_off[i] = the ISIZEs of the blocks before i, text_off[n] = the text's size (both arrays: cap + 1 entries).  Returns n,
+// or -(offset) - 1 of 18 bytes that are no header or of a block whose ISIZE is above 64 KiB.  A block that buf cuts off ends the walk
+// without an error.  Blocks of ISIZE 0 (the 28-byte EOF block, wherever it stands) are blocks like any other.
+extern "C" int64_t mi355x_bgzf_scan(const uint8_t *buf, int64_t len, int64_t cap, int64_t *blk_off, int64_t *text_off)
+{
+	int64_t n = 0, at = 0, text = 0;
+	blk_off[0] = 0; text_off[0] = 0;
+	while (n < cap && at + (int64_t)BGZF_HEAD <= len) {
+		const int64_t total = bgzf_header_at(buf + at);
+		if (!total) return -at - 1;
+		if (at + total > len) break;
+		const uint8_t *t = buf + at + total - 4;
+		const int64_t isize = (int64_t)((uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24);
+		if (isize > (int64_t)BGZF_MAX) return -at - 1;
+		at += total; text += isize; ++n;
+		blk_off[n] = at; text_off[n] = text;
+	}
+	return n;
+}
+
+int64_t mbw::bgzf_in_plan(const uint8_t *in, size_t len, std::vector<int64_t> &blk_off, std::vector<int64_t> &text_off)
+{
+	const int64_t cap = (int64_t)(len / (BGZF_HEAD + BGZF_TAIL)) + 1;
+	blk_off.resize((size_t)cap + 1); text_off.resize((size_t)cap + 1);
+	int64_t n = mi355x_bgzf_scan(in, (int64_t)len, cap, blk_off.data(), text_off.data());
+	int64_t bad = -1;
+	if (n < 0) {   // the blocks before the bad header still count: one of them may fail first
+		bad = -n - 1;
+		n = bad ? mi355x_bgzf_scan(in, bad, cap, blk_off.data(), text_off.data()) : 0;
+	} else if ((size_t)blk_off[n] != len) bad = blk_off[n];
+	blk_off.resize((size_t)n + 1); text_off.resize((size_t)n + 1);
+	return bad;
+}
+
+// `len` bytes of whole BGZF blocks to their text in out[cap], a block per task on this rank's host threads (zlib's raw inflate); every
+// block's CRC32 and ISIZE are checked.  Returns the text's size, -(offset of the first block that fails) - 1, or 0 with nothing written
+// when cap is smaller than the text.  No GPU.
+extern "C" int64_t mi355x_bgzf_inflate(const uint8_t *in, size_t len, char *out, size_t cap)
+{
+	std::vector<int64_t> blk, txt;
+	const int64_t bad = bgzf_in_plan(in, len, blk, txt);
+	const int64_t n = (int64_t)blk.size() - 1;
+	if ((uint64_t)txt[n] > cap) return 0;
+	std::atomic<int64_t> first_bad(INT64_MAX);
+	run_parallel(n, 16, [&](int64_t lo, int64_t hi) {
+		for (int64_t b = lo; b < hi; ++b) {
+			const uint8_t *p = in + blk[b];
+			const size_t total = (size_t)(blk[b + 1] - blk[b]), isize = (size_t)(txt[b + 1] - txt[b]);
+			const uint8_t *t = p + total - 8;
+			const uint32_t crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+			z_stream zs;
+			memset(&zs, 0, sizeof zs);
+			bool ok = inflateInit2(&zs, -15) == Z_OK;
+			if (ok) {
+				uint8_t none = 0;
+				zs.next_in = (Bytef *)(p + BGZF_HEAD); zs.avail_in = (uInt)(total - BGZF_HEAD - BGZF_TAIL);
+				zs.next_out = isize ? (Bytef *)out + txt[b] : &none; zs.avail_out = (uInt)isize;
+				ok = inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.total_out == isize;
+				inflateEnd(&zs);
+				ok = ok && (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)out + txt[b], (uInt)isize) == crc;
+			}
+			if (!ok) {
+				int64_t cur = first_bad.load();
+				while (blk[b] < cur && !first_bad.compare_exchange_weak(cur, blk[b])) {}
+			}
+		}
+	});
+	if (first_bad.load() != INT64_MAX) return -first_bad.load() - 1;
+	if (bad >= 0) return -bad - 1;
+	return txt[n];
 }
 
 // ---- mpiBWAByChr's routing ----

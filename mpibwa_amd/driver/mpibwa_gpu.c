@@ -1,6 +1,6 @@
 /* mpibwa_gpu.c — a thin MPI host program around the C ABI of libmpibwa_amd.so: one rank per GPU,
  *
- *     mpiexec -n N mpibwa_gpu mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]
+ *     mpiexec -n N mpibwa_gpu mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--device-inflate] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq[.gz] [R2.fastq[.gz]]
  *
  * The `mem` options are the reference's (src/mainParallel.c:291-398: -k -w -A -B -O -E -L -U -T -c -d -r -D -m -s -G -N -W -y -X -h -Q -I -R -H
  * -P -a -M -S -Y -V -5 -q -j -C -v -t -K -x -o, and its output options -f (fixmate, :395), -g (BGZF, :299), -b (BGZF + EOF block under the
@@ -36,6 +36,14 @@
  * library's deflate kernel (mi355x_bgzf_compress_dev) instead of zlib on the rank's cores — same cuts, same text inside, other bytes;
  * --level then has no effect; the header's blocks stay zlib's.
  *
+ * Compressed input: a FASTQ file that starts with a BGZF header (what bgzip writes, and -g here) is read as BGZF, R1 and R2 each by its
+ * own first bytes; anything else is plain text as before, and gzip without the 'BC' field is refused.  A compressed file IS its text:
+ * the ranks build the file's block table (compressed offset and text offset per block) from their byte slices and all-gather it, and
+ * sizes, record offsets, the chunk table and the lockstep test are text coordinates, so the chunks and the records are those of the
+ * unpacked files.  read_text() reads the covering blocks, inflates them — zlib on the cores (mi355x_bgzf_inflate), or the library's
+ * inflate kernel with --device-inflate (mi355x_bgzf_inflate_dev) — and trims the ends.  The file is inflated twice, once for the slice
+ * scan and once in the chunk loop, as the plain path reads it twice.  --dry-run uses the cores whatever the option says.
+ *
  * Plain C99 + MPI + pthreads; built by mpibwa_amd/build.py when an MPI installation is found (mpibwa_amd/mpibwa_gpu).
  */
 #define _GNU_SOURCE
@@ -60,14 +68,21 @@
 static int g_rank, g_size;
 
 /* ---- one FASTQ file as this rank sees it ---- */
+/* A file is its TEXT: size, the record offsets and everything that is decided from them are text coordinates.  A BGZF file
+ * (bgzf != 0) carries the table that takes a text range to the blocks that hold it. */
 typedef struct {
 	MPI_File fh;
-	MPI_Offset size;
+	MPI_Offset size;        /* bytes of text */
 	int64_t n_local;        /* records that start in this rank's slice */
 	int64_t first_index;    /* global index of the first of them */
 	int64_t n_total;
 	int64_t *off;           /* absolute offset of every local record, + the end of the last one */
 	int32_t *bases;
+	int bgzf;               /* the file is BGZF blocks */
+	const char *path;
+	MPI_Offset csize;       /* bgzf: bytes of the file */
+	int64_t n_blk;          /* bgzf: blocks of the whole file; boff / toff[0 .. n_blk]: where block i starts in the file / in the text */
+	long long *boff, *toff;
 } fq_t;
 
 static void read_at(MPI_File fh, MPI_Offset at, char *buf, int64_t len)
@@ -77,6 +92,50 @@ static void read_at(MPI_File fh, MPI_Offset at, char *buf, int64_t len)
 		MPI_Status st;
 		MPI_OK(MPI_File_read_at(fh, at, buf, piece, MPI_BYTE, &st));
 		at += piece; buf += piece; len -= piece;
+	}
+}
+
+/* blocks and bytes inflated on the cores by this rank: blocks, compressed bytes, text bytes */
+static unsigned long long g_host_inflated[3];
+#define INFLATE_GROUP 2048   /* blocks per inflate call: at most 128 MiB of text in the thread's buffer */
+
+/* len bytes of the file's text from text offset `at`.  Plain text: read_at.  BGZF: the covering blocks are read, inflated — on the
+ * device when dev != 0 (--device-inflate), else by zlib on the cores — and the ends trimmed.  mpi_mu: held inside MPI only (MPI_THREAD_SERIALIZED). */
+static void read_text(const fq_t *f, int dev, pthread_mutex_t *mpi_mu, MPI_Offset at, char *buf, int64_t len)
+{
+	static __thread char *zin, *ztext;
+	static __thread size_t czin, cztext;
+	if (!f->bgzf) {
+		if (mpi_mu) pthread_mutex_lock(mpi_mu);
+		read_at(f->fh, at, buf, len);
+		if (mpi_mu) pthread_mutex_unlock(mpi_mu);
+		return;
+	}
+	if (len <= 0) return;
+	if (at < 0 || at + len > f->size) DIE("%s: text bytes %lld .. %lld are not in the file", f->path, (long long)at, (long long)(at + len));
+	int64_t lo = 0, hi = f->n_blk;   /* the last block that starts at or before `at` */
+	while (hi - lo > 1) { const int64_t mid = (lo + hi) / 2; if (f->toff[mid] <= at) lo = mid; else hi = mid; }
+	for (int64_t b0 = lo; b0 < f->n_blk && f->toff[b0] < at + len;) {
+		int64_t b1 = b0 + INFLATE_GROUP < f->n_blk ? b0 + INFLATE_GROUP : f->n_blk;
+		while (b1 - 1 > b0 && f->toff[b1 - 1] >= at + len) --b1;   /* (blocks behind the range) */
+		const size_t cbytes = (size_t)(f->boff[b1] - f->boff[b0]), tbytes = (size_t)(f->toff[b1] - f->toff[b0]);
+		if (cbytes > czin) { free(zin); zin = malloc(czin = cbytes + (cbytes >> 2)); }
+		if (tbytes + 1 > cztext) { free(ztext); ztext = malloc(cztext = tbytes + (tbytes >> 2) + 1); }
+		if (!zin || !ztext) DIE("out of memory");
+		if (mpi_mu) pthread_mutex_lock(mpi_mu);
+		read_at(f->fh, f->boff[b0], zin, (int64_t)cbytes);
+		if (mpi_mu) pthread_mutex_unlock(mpi_mu);
+		const int64_t r = dev ? mi355x_bgzf_inflate_dev((const uint8_t *)zin, cbytes, ztext, tbytes) : mi355x_bgzf_inflate((const uint8_t *)zin, cbytes, ztext, tbytes);
+		if (r < 0) DIE("%s: the BGZF block at byte %lld does not inflate", f->path, (long long)(f->boff[b0] - r - 1));
+		if ((size_t)r != tbytes) DIE("%s: the blocks from byte %lld hold %lld bytes of text, not %lld", f->path, (long long)f->boff[b0], (long long)r, (long long)tbytes);
+		if (!dev) {
+			__sync_fetch_and_add(&g_host_inflated[0], (unsigned long long)(b1 - b0));
+			__sync_fetch_and_add(&g_host_inflated[1], (unsigned long long)cbytes);
+			__sync_fetch_and_add(&g_host_inflated[2], (unsigned long long)tbytes);
+		}
+		const int64_t t0 = f->toff[b0], t1 = f->toff[b1], c0 = t0 > at ? t0 : at, c1 = t1 < at + len ? t1 : at + len;
+		if (c1 > c0) memcpy(buf + (c0 - at), ztext + (c0 - t0), (size_t)(c1 - c0));
+		b0 = b1;
 	}
 }
 
@@ -98,8 +157,10 @@ static int record_at(const char *p, const char *end)
 }
 
 /* first record starting at or after `lo` (absolute offset); `size` if there is none */
-static MPI_Offset first_record_from(MPI_File fh, MPI_Offset size, MPI_Offset lo)
+/* (small probing reads: always the host path) */
+static MPI_Offset first_record_from(const fq_t *f, MPI_Offset lo)
 {
+	const MPI_Offset size = f->size;
 	int64_t window = 1 << 16;
 	if (lo <= 0) return 0;
 	if (lo >= size) return size;
@@ -109,7 +170,7 @@ static MPI_Offset first_record_from(MPI_File fh, MPI_Offset size, MPI_Offset lo)
 		const int64_t len = size - w0 < window ? (int64_t)(size - w0) : window;
 		const int at_eof = w0 + len >= size;
 		char *buf = malloc((size_t)len + 1);
-		read_at(fh, w0, buf, len);
+		read_text(f, 0, 0, w0, buf, len);
 		int undecided = 0;
 		MPI_Offset found = -1;
 		for (int64_t i = 0; i + 1 < len; ++i) {
@@ -126,13 +187,83 @@ static MPI_Offset first_record_from(MPI_File fh, MPI_Offset size, MPI_Offset lo)
 	}
 }
 
-static void fq_open(fq_t *f, const char *path)
+/* The block table of a BGZF file: every rank enters its byte slice of the file at the first block start in it (mi355x_bgzf_find_block),
+ * walks the headers up to the next rank's start (mi355x_bgzf_scan), and the parts are all-gathered: 16 bytes per block. */
+static void bgzf_table(fq_t *f)
+{
+	MPI_Offset lo = f->csize / g_size * g_rank, start = g_rank == 0 ? 0 : -1;
+	for (int64_t window = 1 << 18; start < 0; window *= 4) {
+		const int64_t len = f->csize - lo < window ? (int64_t)(f->csize - lo) : window;
+		const int at_eof = lo + len >= f->csize;
+		uint8_t *buf = malloc((size_t)len + 1);
+		read_at(f->fh, lo, (char *)buf, len);
+		const int64_t r = mi355x_bgzf_find_block(buf, len, at_eof);
+		free(buf);
+		if (r >= 0) start = lo + r;
+		else if (r == -1 || at_eof) start = f->csize;   /* no block starts in this slice */
+	}
+	long long s = (long long)start, *all = malloc(sizeof(long long) * (size_t)(g_size + 1));
+	MPI_OK(MPI_Allgather(&s, 1, MPI_LONG_LONG, all, 1, MPI_LONG_LONG, MPI_COMM_WORLD));
+	all[g_size] = (long long)f->csize;
+	MPI_Offset next = (MPI_Offset)all[g_rank + 1];
+	if (next < start) next = start;
+	free(all);
+	const int64_t len = next - start, cap = len / 26 + 1;
+	uint8_t *buf = malloc((size_t)len + 1);
+	int64_t *bo = malloc(sizeof(int64_t) * (size_t)(cap + 1)), *to = malloc(sizeof(int64_t) * (size_t)(cap + 1));
+	read_at(f->fh, start, (char *)buf, len);
+	const int64_t n = mi355x_bgzf_scan(buf, len, cap, bo, to);
+	if (n < 0) DIE("%s: no BGZF block header at byte %lld", f->path, (long long)(start - n - 1));
+	if (bo[n] != len) DIE("%s: the BGZF block at byte %lld is cut off", f->path, (long long)(start + bo[n]));
+	free(buf);
+	if (n > 0x3fffffff) DIE("%s: too many BGZF blocks in one slice", f->path);
+	/* everybody's counts and text sizes, then the parts */
+	long long mine[2] = {n, to[n]}, *cnt = malloc(sizeof(long long) * 2 * (size_t)g_size);
+	MPI_OK(MPI_Allgather(mine, 2, MPI_LONG_LONG, cnt, 2, MPI_LONG_LONG, MPI_COMM_WORLD));
+	int *rc = malloc(sizeof(int) * (size_t)g_size), *rd = malloc(sizeof(int) * (size_t)g_size);
+	long long total = 0, text_before = 0, text_total = 0;
+	for (int r = 0; r < g_size; ++r) {
+		if (total + cnt[2 * r] > 0x3fffffff) DIE("%s: too many BGZF blocks", f->path);
+		rc[r] = (int)(2 * cnt[2 * r]); rd[r] = (int)(2 * total);
+		total += cnt[2 * r];
+		if (r < g_rank) text_before += cnt[2 * r + 1];
+		text_total += cnt[2 * r + 1];
+	}
+	long long *part = malloc(sizeof(long long) * 2 * (size_t)(n + 1)), *table = malloc(sizeof(long long) * 2 * (size_t)(total + 1));
+	for (int64_t i = 0; i < n; ++i) { part[2 * i] = (long long)start + bo[i]; part[2 * i + 1] = text_before + to[i]; }
+	MPI_OK(MPI_Allgatherv(part, (int)(2 * n), MPI_LONG_LONG, table, rc, rd, MPI_LONG_LONG, MPI_COMM_WORLD));
+	f->n_blk = total;
+	f->boff = malloc(sizeof(long long) * (size_t)(total + 1));
+	f->toff = malloc(sizeof(long long) * (size_t)(total + 1));
+	for (long long i = 0; i < total; ++i) { f->boff[i] = table[2 * i]; f->toff[i] = table[2 * i + 1]; }
+	f->boff[total] = (long long)f->csize; f->toff[total] = text_total;
+	f->size = (MPI_Offset)text_total;
+	free(bo); free(to); free(cnt); free(rc); free(rd); free(part); free(table);
+}
+
+/* dev: BGZF blocks are inflated on the device (--device-inflate) for the slice scan */
+static void fq_open(fq_t *f, const char *path, int dev)
 {
 	memset(f, 0, sizeof *f);
+	f->path = path;
 	MPI_OK(MPI_File_open(MPI_COMM_WORLD, path, MPI_MODE_RDONLY, MPI_INFO_NULL, &f->fh));
 	MPI_OK(MPI_File_get_size(f->fh, &f->size));
+	/* a file that starts with a BGZF header is BGZF; gzip without the 'BC' field cannot be entered in the middle and is refused */
+	if (f->size >= 2) {
+		uint8_t head[18] = {0};
+		read_at(f->fh, 0, (char *)head, f->size < 18 ? (int64_t)f->size : 18);
+		if (head[0] == 0x1f && head[1] == 0x8b) {
+			if (f->size < 18 || mi355x_bgzf_find_block(head, 18, 0) != -2 || mi355x_bgzf_scan(head, 18, 1, (int64_t[2]){0, 0}, (int64_t[2]){0, 0}) < 0) {
+				if (g_rank == 0) DIE("%s is gzip without BGZF blocks: recompress it with bgzip, or unpack it", path);
+				MPI_Barrier(MPI_COMM_WORLD);   /* (rank 0 ends the run) */
+			}
+			f->bgzf = 1;
+			f->csize = f->size;
+			bgzf_table(f);
+		}
+	}
 	/* byte slices -> record slices: every rank finds the first record of its slice, its slice ends where the next one starts */
-	MPI_Offset lo = f->size / g_size * g_rank, start = first_record_from(f->fh, f->size, lo), next;
+	MPI_Offset lo = f->size / g_size * g_rank, start = first_record_from(f, lo), next;
 	long long s = (long long)start, *all = malloc(sizeof(long long) * (size_t)(g_size + 1));
 	MPI_OK(MPI_Allgather(&s, 1, MPI_LONG_LONG, all, 1, MPI_LONG_LONG, MPI_COMM_WORLD));
 	all[g_size] = (long long)f->size;
@@ -142,7 +273,7 @@ static void fq_open(fq_t *f, const char *path)
 	/* scan the slice */
 	int64_t len = next - start, cap = len / 8 + 16;
 	char *buf = malloc((size_t)len + 1);
-	read_at(f->fh, start, buf, len);
+	read_text(f, dev, 0, start, buf, len);
 	f->off = malloc(sizeof(int64_t) * (size_t)(cap + 1));
 	f->bases = malloc(sizeof(int32_t) * (size_t)cap);
 	int64_t n = mi355x_fastq_scan(buf, len, cap, f->off, f->bases);
@@ -190,7 +321,9 @@ typedef struct {
 	const mem_opt_t *opt;
 	bwaidx_t *idx;
 	MPI_Win win;
-	MPI_File out, f1, f2;
+	MPI_File out;
+	const fq_t *q1, *q2;         /* the FASTQ files: read_text() */
+	int device_inflate;          /* --device-inflate: BGZF input is inflated by mi355x_bgzf_inflate_dev */
 	const long long *tab;        /* per chunk: first record, byte offset in R1, byte offset in R2 (+ one closing row) */
 	long long n_chunks;
 	int paired, lockstep, trimmed, copy_comment;
@@ -221,18 +354,34 @@ static void *warm_main(void *arg)
 	w->secs = mi355x_prewarm(w->opt, w->idx->bwt, w->idx->bns, w->idx->pac, w->n_reads, w->len, w->n_calls);
 	return 0;
 }
-/* bases of the first record of a FASTQ file (0: not one) */
+/* bases of the first record of a FASTQ file, plain or BGZF (0: not one) */
 static int first_read_len(const char *path)
 {
 	FILE *fp = fopen(path, "r");
 	if (!fp) return 0;
 	char *line = malloc(1 << 20);
 	int len = 0;
-	if (fgets(line, 1 << 20, fp) && line[0] == '@' && fgets(line, 1 << 20, fp)) {
-		len = (int)strcspn(line, "\r\n");
-	}
-	free(line);
+	const size_t got = fread(line, 1, 1 << 18, fp);
 	fclose(fp);
+	const char *text = line, *end = line + got;
+	char *plain = 0;
+	if (got >= 18 && (uint8_t)line[0] == 0x1f && (uint8_t)line[1] == 0x8b) {   /* the whole blocks of the file's first 256 KiB, on the cores */
+		int64_t bo[9], to[9];
+		const int64_t n = mi355x_bgzf_scan((const uint8_t *)line, (int64_t)got, 8, bo, to);
+		plain = malloc((size_t)(n > 0 ? to[n] : 0) + 1);
+		const int64_t t = n > 0 ? mi355x_bgzf_inflate((const uint8_t *)line, (size_t)bo[n], plain, (size_t)to[n]) : 0;
+		text = plain; end = plain + (t > 0 ? t : 0);
+	}
+	if (text < end && *text == '@') {
+		const char *l1 = memchr(text, '\n', (size_t)(end - text));
+		if (l1) {
+			const char *l2 = memchr(l1 + 1, '\n', (size_t)(end - l1 - 1));
+			len = (int)((l2 ? l2 : end) - (l1 + 1));
+			if (len > 0 && l1[len] == '\r') --len;
+		}
+	}
+	free(plain);
+	free(line);
 	return len;
 }
 
@@ -312,10 +461,8 @@ static void *chunk_worker(void *arg)
 		const double t0 = MPI_Wtime();
 		int64_t len1 = tab[3 * (c + 1) + 1] - tab[3 * c + 1], len2 = paired ? tab[3 * (c + 1) + 2] - tab[3 * c + 2] : 0;
 		char *buf1 = grown(&pb1, &cb1, (size_t)len1 + 1), *buf2 = paired ? grown(&pb2, &cb2, (size_t)len2 + 1) : 0;
-		MPI_ENTER(L);
-		read_at(L->f1, tab[3 * c + 1], buf1, len1);
-		if (paired) read_at(L->f2, tab[3 * c + 2], buf2, len2);
-		MPI_LEAVE(L);
+		read_text(L->q1, L->device_inflate, L->serialize ? &L->mpi_mu : 0, tab[3 * c + 1], buf1, len1);
+		if (paired) read_text(L->q2, L->device_inflate, L->serialize ? &L->mpi_mu : 0, tab[3 * c + 2], buf2, len2);
 		buf1[len1] = 0;
 		if (paired) buf2[len2] = 0;
 		const double t1 = MPI_Wtime();
@@ -370,8 +517,9 @@ static void *chunk_worker(void *arg)
 
 static void usage(const char *prog)
 {
-	if (g_rank == 0) fprintf(stderr, "usage: mpiexec -n N %s mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--level L] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]\n"
-	                         "  --device-bgzf   with -g or -b: compress the chunks' BGZF blocks on the GPU (one setting: --level has no effect on them)\n", prog);
+	if (g_rank == 0) fprintf(stderr, "usage: mpiexec -n N %s mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--device-inflate] [--level L] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]\n"
+	                         "  --device-bgzf   with -g or -b: compress the chunks' BGZF blocks on the GPU (one setting: --level has no effect on them)\n"
+	                         "  --device-inflate  FASTQ files that are BGZF (bgzip) are inflated on the GPU instead of the cores; no effect on plain files\n", prog);
 }
 
 int main(int argc, char **argv)
@@ -382,7 +530,7 @@ int main(int argc, char **argv)
 	MPI_Comm_size(MPI_COMM_WORLD, &g_size);
 	int n_threads = 0, copy_comment = 0, dry = 0, n_workers = 6, prewarm = 1;
 	int dofixmate = 0, write_format = 2, compression_level = 3, by_chr = 0;   /* src/mainParallel.c:223-227 */
-	int ordered = 0, device_bgzf = 0, level_given = 0;
+	int ordered = 0, device_bgzf = 0, level_given = 0, want_device_inflate = 0;
 	int scale_a = 0, set_b = 0, set_T = 0, set_U = 0, set_d = 0, set_O = 0, set_E = 0, set_L = 0, set_k = 0, set_r = 0, set_W = 0;
 	const char *mode = 0;   /* -x: a preset of the options the user did not set (src/mainParallel.c:294, 398-428) */
 	int64_t K = 0;
@@ -406,6 +554,7 @@ int main(int argc, char **argv)
 		if (!strcmp(a, "--by-chr")) { by_chr = 1; continue; }
 		if (!strcmp(a, "--ordered")) { ordered = 1; continue; }
 		if (!strcmp(a, "--device-bgzf")) { device_bgzf = 1; continue; }
+		if (!strcmp(a, "--device-inflate")) { want_device_inflate = 1; continue; }
 		if (!strcmp(a, "--level") && i + 1 < argc) { compression_level = atoi(argv[++i]); level_given = 1; continue; }
 		if (!strcmp(a, "--in-flight") && i + 1 < argc) { n_workers = atoi(argv[++i]); continue; }
 		if (a[0] != '-' || !a[1]) { if (n_pos < 3) pos[n_pos++] = a; continue; }
@@ -601,9 +750,10 @@ int main(int argc, char **argv)
 
 	/* ---- partition ---- */
 	fq_t f1, f2;
-	fq_open(&f1, pos[1]);
+	const int device_inflate = want_device_inflate && !dry;   /* (--dry-run never touches the GPU) */
+	fq_open(&f1, pos[1], device_inflate);
 	if (paired) {
-		fq_open(&f2, pos[2]);
+		fq_open(&f2, pos[2], device_inflate);
 		if (f1.n_total != f2.n_total) DIE("the two FASTQ files hold %lld and %lld reads", (long long)f1.n_total, (long long)f2.n_total);
 	}
 	/* the reference takes the equal-size branch when both files have the same byte size (src/mainParallel.c:703-728) */
@@ -736,7 +886,7 @@ int main(int argc, char **argv)
 	const double t_loop = MPI_Wtime();
 	loop_t L;
 	memset(&L, 0, sizeof L);
-	L.opt = opt; L.idx = idx; L.win = win; L.out = out; L.f1 = f1.fh; L.f2 = paired ? f2.fh : MPI_FILE_NULL;
+	L.opt = opt; L.idx = idx; L.win = win; L.out = out; L.q1 = &f1; L.q2 = paired ? &f2 : 0; L.device_inflate = device_inflate;
 	L.tab = tab_all; L.n_chunks = n_chunks; L.paired = paired; L.lockstep = lockstep; L.trimmed = trimmed; L.copy_comment = copy_comment; L.pes0 = pes0;
 	L.fixmate = dofixmate; L.device_bgzf = device_bgzf; L.format = write_format; L.level = compression_level; L.by_chr = by_chr; L.n_dest = n_dest; L.dest = dest;
 	L.serialize = provided < MPI_THREAD_MULTIPLE;
@@ -758,6 +908,17 @@ int main(int argc, char **argv)
 		const long long n_reads = (long long)f1.n_total * (paired ? 2 : 1);
 		fprintf(stderr, "[mpibwa_gpu] chunk loop: %lld reads in %lld chunks, %d rank(s) x %d chunks in flight, %.3f s = %.3f Mreads/s\n", n_reads, n_chunks, g_size,
 		        n_workers, dt, dt > 0 ? n_reads / dt * 1e-6 : 0.);
+	}
+	if (f1.bgzf || (paired && f2.bgzf)) {   /* BGZF input: what each path inflated (the slice scan and the chunk reads), over all ranks */
+		uint64_t dc[4];
+		unsigned long long mine[6], all[6] = {0, 0, 0, 0, 0, 0};
+		mi355x_bgzf_inflate_dev_counts(dc);
+		mine[0] = (unsigned long long)dc[0]; mine[1] = (unsigned long long)dc[2]; mine[2] = (unsigned long long)dc[3];
+		for (int k = 0; k < 3; ++k) mine[3 + k] = g_host_inflated[k];
+		MPI_OK(MPI_Reduce(mine, all, 6, MPI_UNSIGNED_LONG_LONG, MPI_SUM, 0, MPI_COMM_WORLD));
+		if (g_rank == 0)
+			fprintf(stderr, "[mpibwa_gpu] BGZF input: device %llu blocks, %llu bytes -> %llu bytes of text; host %llu blocks, %llu bytes -> %llu bytes of text\n",
+			        all[0], all[1], all[2], all[3], all[4], all[5]);
 	}
 	if (device_bgzf) {   /* what the device path did, over all ranks */
 		uint64_t dc[4];
