@@ -1,4 +1,5 @@
-// hip_util.h — what the .hip files share on the host side: the error check, an event timer and an owning device array.
+// hip_util.h — what the .hip files share on the host side: the error check, an event timer and an owning device array;
+// on the device side the LDS hand-over inside a wave.
 // (.hip files only: it pulls in the HIP runtime header)
 #ifndef MBW_HIP_UTIL_H
 #define MBW_HIP_UTIL_H
@@ -12,6 +13,14 @@
 	} while (0)
 
 namespace mbw {
+
+// What the lanes of a wave stored to LDS becomes visible to the wave's other lanes (a workgroup of one wave: no s_barrier)
+__device__ __forceinline__ void wave_lds_sync()
+{
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 struct Timer {
 	hipEvent_t a, b;

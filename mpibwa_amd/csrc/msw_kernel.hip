@@ -25,22 +25,21 @@
 // saturate in the byte flavour (qlen * a < 250 and shift = -min(mat)); a request whose scores could reach the 8-bit
 // ceiling is flagged and recomputed on the host.
 //
-// Mapping (round 2): one request per QUAD of lanes, 16 requests per wave, one wave per workgroup.  The query positions of a
+// Mapping: one request per QUAD of lanes, 16 requests per wave, one wave per workgroup.  The query positions of a
 // request are dealt to its four lanes in contiguous quarters, and the quad works as a skewed pipeline: lane j computes its
 // quarter of target row i at step i + j.  What a quarter needs from its left neighbour is what the neighbour held after the
 // last cell of the same row one step earlier — H(i-1) of that cell (the diagonal), both running F values and the running
 // row maximum — four registers handed over with DPP quad_perm, no LDS.  Lane 3 sees the finished row: row maximum into the
-// b[] scratch, best score / te / qe, the stop conditions (broadcast back through the quad).  Compared with the lane-per-
-// request mapping of round 1 (445 waves of 40 KB LDS for a launch of 28 000 requests: fewer waves than SIMDs, one wave per
-// SIMD, launch time = one lane's serial latency) a launch is four times as many waves of a quarter of the serial length
-// and 10 KB of LDS each, so every SIMD has work and several waves to hide LDS latency behind.
+// b[] scratch, best score / te / qe, the stop conditions (broadcast back through the quad).  A wave's serial length is a
+// quarter of a request's and its LDS 10 KB for reads of 150 bp, so a launch of 28 000 requests gives every SIMD work and
+// several waves to hide LDS latency behind.
 // The row state of a position — H(i-1,k), E(i,k), the query base of position k and a segment-end flag packed in one dword
 // (13 + 13 + 3 bits, bit 31) — lives in LDS as cell[kk][lane] (kk = position inside the lane's quarter), so the 64 lanes of a
 // wave touch 64 consecutive dwords (no bank conflicts) and the whole DP runs out of LDS and registers.  HBM traffic is the
 // target window (2 bits per row) and one u16 per row for the b[] pass.  The work is VALU-bound: ~30 integer ops per cell.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <type_traits>
+#include <climits>
 #include "hip_util.h"
 #include "device.h"
 
@@ -64,6 +63,15 @@ struct MswPassOut { int score, te, qe; };
 #define MSW_QP(a, b, c, d) ((a) | (b) << 2 | (c) << 4 | (d) << 6)
 template <int CTRL>
 __device__ __forceinline__ int msw_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
+__device__ __forceinline__ int msw_from_lane3(int v) { return msw_dpp<MSW_QP(3, 3, 3, 3)>(v); }
+
+// the result of a pass, which lane 3 holds, in every lane of the quad
+__device__ __forceinline__ MswPassOut msw_quad_result(int gmax, int te, int qe)
+{
+	MswPassOut o;
+	o.score = msw_from_lane3(gmax); o.te = msw_from_lane3(te); o.qe = msw_from_lane3(qe);
+	return o;
+}
 
 // query code of position k of a request: the mate as it is or reverse-complemented, N = 4, beyond the read = padding
 __device__ __forceinline__ uint32_t msw_code(const uint8_t *__restrict__ ms, int qlen, int is_rev, int k)
@@ -143,66 +151,119 @@ __device__ __forceinline__ MswPassOut msw_pass(uint32_t *cell, const MswParams &
 			}
 			if (i + 1 >= tn) stop = 1;
 		}
-		stop = msw_dpp<MSW_QP(3, 3, 3, 3)>(stop);
+		stop = msw_from_lane3(stop);
 		if (stop) run = false;
 	}
-	MswPassOut o;
-	o.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmax); o.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(te); o.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qe);
-	*sat_hit = msw_dpp<MSW_QP(3, 3, 3, 3)>(*sat_hit);
-	return o;
+	*sat_hit = msw_from_lane3(*sat_hit);
+	return msw_quad_result(gmax, te, qe);
 }
 
-// What follows the forward pass of one request: score2 / te2 from the row maxima (the b[] list of src/ksw.c:196-226 rebuilt), the
-// reverse pass that finds where the best local alignment starts (KSW_XSTART, src/ksw.c:344-352), the result record.  `cell` is
-// re-initialised for the reverse pass (layout of msw_pass).  All four lanes of the quad call it with the same arguments.
-__device__ __forceinline__ void msw_tail(uint32_t *cell, const MswParams &P, const uint8_t *__restrict__ pac, bool live, const MswReq &rq, int qlen,
-                                         const uint8_t *__restrict__ ms, int r, int n_req, MswPassOut f, int sat, uint16_t *__restrict__ rows,
-                                         MswRes *__restrict__ res)
+// The b[] list of src/ksw.c:196-226, rebuilt from the row maxima in row order: runs of consecutive rows whose maximum reaches minsc,
+// each run kept as its best row, where "consecutive" looks at the row kept for the run, not at the previous row.  The second-best hit
+// (sc2, te2) is the best run whose kept row lies outside te +- ceil(score / max_sc).
+struct MswRuns {
+	int last_sc = -1, last_i = -1, sc2 = -1, te2 = -1, low, high, minsc;
+	__device__ __forceinline__ MswRuns(int score, int te, int max_sc, int minsc_) : minsc(minsc_)
+	{
+		const int d = (score + max_sc - 1) / max_sc;
+		low = te - d; high = te + d;
+	}
+	__device__ __forceinline__ void row(int i, int im)
+	{
+		if (im < minsc) return;
+		if (last_i < 0 || last_i + 1 != i) { finish(); last_sc = im; last_i = i; }
+		else if (last_sc < im) { last_sc = im; last_i = i; }
+	}
+	__device__ __forceinline__ void finish()   // the run in hand is complete
+	{
+		if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
+	}
+};
+
+// score2 / te2 of request r (if `has`) into `out`, the quad working together: each lane fetches 16 of the next 64 row maxima
+// (independent loads, all in flight at once), the quad parks them in its block `qblk` of 64 LDS entries and every lane applies MswRuns
+// to them in row order.  All 64 lanes call it together: the trip count is the wave's longest window, and a block in which no quad has
+// a row at minsc is skipped.
+__device__ __forceinline__ void msw_scan_rows(uint16_t *qblk, const uint16_t *__restrict__ rows, int n_req, int r, int tlen, bool has, int minsc,
+                                              int max_sc, MswRes &out)
+{
+	const int j = threadIdx.x & 3;
+	if (!has) tlen = 0;
+	MswRuns b(out.score, out.te, max_sc, minsc);
+	int twave = tlen;
+	for (int o = 32; o; o >>= 1) twave = max(twave, __shfl_xor(twave, o));
+	for (int i0 = 0; i0 < twave; i0 += 64) {
+		uint16_t v[16];
+#pragma unroll
+		for (int u = 0; u < 16; ++u) {
+			const int i = i0 + u * 4 + j;
+			v[u] = i < tlen ? rows[(size_t)i * n_req + r] : (uint16_t)0;
+		}
+		bool any = false;
+#pragma unroll
+		for (int u = 0; u < 16; ++u) {
+			qblk[u * 4 + j] = v[u];
+			any |= i0 + u * 4 + j < tlen && (int)v[u] >= minsc;
+		}
+		if (!__any(any)) continue;
+		wave_lds_sync();
+		const int kend = min(64, tlen - i0);
+		for (int k = 0; k < kend; ++k) b.row(i0 + k, qblk[k]);
+		wave_lds_sync();
+	}
+	b.finish();
+	out.score2 = b.sc2; out.te2 = b.te2;
+}
+
+// The reverse pass of one request on its quad and the end of its record: where does the best local alignment start (KSW_XSTART,
+// src/ksw.c:344-352) — the forward pass again over the reversed prefixes, query positions qe .. 0 against rows te .. 0, until the
+// forward score is reached.  `second`: the request has such a pass; `cell` is laid out anew for it (layout of msw_pass).  All four
+// lanes of the quad call it with the same arguments; lane 0 stores the record of a live request.
+__device__ __forceinline__ void msw_reverse_one(uint32_t *cell, const MswParams &P, const uint8_t *__restrict__ pac, bool live, bool second,
+                                                const MswReq &rq, int qlen, const uint8_t *__restrict__ ms, MswRes &out, MswRes *__restrict__ res, int r)
 {
 	const int lane = threadIdx.x, j = lane & 3;
-	const int tlen = (int)(rq.re - rq.rb);
 	const bool byte_flavour = qlen * P.a < 250;
 	const int PP = byte_flavour ? 16 : 8;
-	const int minsc = P.min_seed_len * P.a;              // KSW_XSUBO | min_seed_len * a
 	const int sat_limit = byte_flavour ? 255 - P.shift : 0x10000;
-	MswRes out;
-	out.score = f.score; out.te = f.te; out.qe = f.qe; out.score2 = -1; out.te2 = -1; out.tb = -1; out.qb = -1; out.flags = sat;
-	// b[]: runs of rows whose maximum reaches minsc; second best = best run outside te +- ceil(score / max)
-	// (the quad's own stores to rows[]: same wave, same addresses, program order)
-	// (a window whose best row stays below minsc has no such row at all — nine rescue windows in ten of a repeat read's anchors: the
-	// scan of its 600 row maxima, one dependent global load each, was as long as the forward pass itself)
-	if (live && j == 0 && !sat && f.te >= 0 && f.score >= minsc) {
-		const int d = (f.score + P.max_sc - 1) / P.max_sc;
-		const int low = f.te - d, high = f.te + d;
-		int last_sc = -1, last_i = -1;
-		const int rows_done = f.te >= 0 ? tlen : 0;   // the forward pass never stops early (no KSW_XSTOP, no saturation)
-		for (int i = 0; i < rows_done; ++i) {
-			const int im = rows[(size_t)i * n_req + r];
-			if (im < minsc) continue;
-			if (last_i < 0 || last_i + 1 != i) {
-				if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > out.score2) { out.score2 = last_sc; out.te2 = last_i; }
-				last_sc = im; last_i = i;
-			} else if (last_sc < im) { last_sc = im; last_i = i; }
-		}
-		if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > out.score2) { out.score2 = last_sc; out.te2 = last_i; }
-	}
-	// second pass over the reversed prefixes: where does the best local alignment start (KSW_XSTART)
-	const bool second = live && !sat && f.score >= minsc && f.qe >= 0 && f.te >= 0;
-	int qlen2 = second ? f.qe + 1 : 0;
-	if (second && f.qe >= qlen) qlen2 = 0;   // cannot happen (the maximum of a row is reached on a real base first); stay in bounds
+	int qlen2 = second ? out.qe + 1 : 0;
+	if (second && out.qe >= qlen) qlen2 = 0;   // cannot happen (the maximum of a row is reached on a real base first); stay in bounds
 	const int slen2 = (qlen2 + PP - 1) / PP, npos2 = slen2 * PP, S2 = npos2 >> 2;
-	if (qlen2 > 0)   // the codes of positions qe .. 0, padded, dealt to the quad again; H and E cleared
+	if (qlen2 > 0)   // the codes of positions qe .. 0, padded, dealt to the quad; H and E cleared
 		for (int kk = 0; kk < S2; ++kk) {
 			const int k = j * S2 + kk;
 			const uint32_t c = k < qlen2 ? msw_code(ms, qlen, rq.is_rev, qlen2 - 1 - k) : MSW_PAD;
 			cell[kk * 64 + lane] = c << 26 | ((k + 1) % slen2 == 0 ? 0x80000000u : 0u);
 		}
 	int sat2 = 0;
-	MswPassOut g = msw_pass(cell, P, pac, qlen2 > 0, S2, f.te + 1, rq.rb + f.te, -1, f.score, sat_limit, nullptr, 0, &sat2);
-	if (qlen2 > 0 && g.score == f.score) { out.tb = f.te - g.te; out.qb = f.qe - g.qe; }
+	const MswPassOut g = msw_pass(cell, P, pac, qlen2 > 0, S2, out.te + 1, rq.rb + out.te, -1, out.score, sat_limit, nullptr, 0, &sat2);
+	if (qlen2 > 0 && g.score == out.score) { out.tb = out.te - g.te; out.qb = out.qe - g.qe; }
 	if (second && qlen2 == 0) out.flags = 1;
 	if (sat2) out.flags = 1;
 	if (live && j == 0) res[r] = out;
+}
+
+// What follows the forward pass of one request in msw_kernel: score2 / te2 from the row maxima, the reverse pass, the record.  All
+// four lanes of the quad call it with the same arguments.
+__device__ __forceinline__ void msw_tail(uint32_t *cell, const MswParams &P, const uint8_t *__restrict__ pac, bool live, const MswReq &rq, int qlen,
+                                         const uint8_t *__restrict__ ms, int r, int n_req, MswPassOut f, int sat, uint16_t *__restrict__ rows,
+                                         MswRes *__restrict__ res)
+{
+	const int j = threadIdx.x & 3;
+	const int tlen = (int)(rq.re - rq.rb);
+	const int minsc = P.min_seed_len * P.a;              // KSW_XSUBO | min_seed_len * a
+	MswRes out;
+	out.score = f.score; out.te = f.te; out.qe = f.qe; out.score2 = -1; out.te2 = -1; out.tb = -1; out.qb = -1; out.flags = sat;
+	// lane 0 walks the rows on its own (the quad's own stores to rows[]: same wave, same addresses, program order; the forward pass
+	// never stops early — no KSW_XSTOP, no saturation — so all tlen rows are there).  A window whose best row stays below minsc has no
+	// row for b[] at all — nine rescue windows in ten of a repeat read's anchors — and is not walked.
+	if (live && j == 0 && !sat && f.te >= 0 && f.score >= minsc) {
+		MswRuns b(f.score, f.te, P.max_sc, minsc);
+		for (int i = 0; i < tlen; ++i) b.row(i, rows[(size_t)i * n_req + r]);
+		b.finish();
+		out.score2 = b.sc2; out.te2 = b.te2;
+	}
+	msw_reverse_one(cell, P, pac, live, live && !sat && f.score >= minsc && f.qe >= 0 && f.te >= 0, rq, qlen, ms, out, res, r);
 }
 
 // list: the requests this launch works on (null: all of them, in order)
@@ -238,7 +299,7 @@ __global__ __launch_bounds__(64) void msw_kernel(MswParams P, int n_work, int n_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// msw2_kernel (round 4): TWO requests of the same mate in the same orientation per quad — the rescue windows of a repeat read's
+// msw2_kernel: TWO requests of the same mate in the same orientation per quad — the rescue windows of a repeat read's
 // anchors: 50 windows for one mate — in the byte flavour (qlen * a < 250: every H, E, F below 256).  The forward pass (the whole
 // window; four fifths of the work) runs both alignments in the two 16-bit halves of every register: v_pk_add_i16 / v_pk_sub_i16 /
 // v_pk_max_i16 on {H, E, Fseg, Ffull}, 13 vector instructions per cell instead of 25.  What makes that cheap is what the two share:
@@ -276,28 +337,215 @@ __device__ __forceinline__ int msw_rev_class(int score, int qe, int a)
 	return 1 + (qe >> 4) * 3 + sb;
 }
 
-// One cell of the packed recurrence for the two alignments of a quad, with the row state in LDS: w = H, E of both as four bytes, s =
-// the two substitution scores as a packed pair (the caller's lookup: one table of pairs where the two share the query, two tables
-// or'ed where they do not).  seg_end (UNI) or bit 3 of entry u of cd: the last position of a segment.
-struct Msw2Gap { msw_s2 oe_del, oe_ins, e_del, e_ins; };
-template <bool UNI>
-__device__ __forceinline__ void msw2_cell(uint32_t &w, msw_s2 s, uint32_t cd, int u, bool seg_end, const Msw2Gap &G, msw_u2 c256, msw_s2 &diag,
-                                          msw_s2 &fseg, msw_s2 &ffull, msw_u2 &mblk)
+// ---- the packed arithmetic: two alignments of a quad in the 16-bit halves of every register (msw2_kernel, msw_rev2_kernel) ----
+struct Msw2Gap {
+	msw_s2 oe_del, oe_ins, e_del, e_ins;
+	__device__ __forceinline__ explicit Msw2Gap(const MswParams &P)
+		: oe_del(s2_splat(P.o_del + P.e_del)), oe_ins(s2_splat(P.o_ins + P.e_ins)), e_del(s2_splat(P.e_del)), e_ins(s2_splat(P.e_ins)) {}
+};
+
+// One cell of the recurrence at the top of this file, for both alignments: hd = H(i-1,k), e = E(i,k) (becomes E(i+1,k)), s = the two
+// substitution scores; diag / fseg / ffull run along the row.  H(i,k) is returned.  H, E, both F and h = Hpre are never negative, so
+// "max(x - c, 0)" is one saturating subtraction.  mblk: the maximum of the block of eight cells and the first of them to reach it as
+// one 16-bit key per alignment, h * 256 + 7 - u (u = the cell's place in the block; c256: see msw2_pass_lds).  seg_end(F_seg): what
+// is left of F_seg behind this cell — nothing behind the last position of a segment.
+template <class SegEnd>
+__device__ __forceinline__ msw_s2 msw2_recur(msw_s2 hd, msw_s2 &e, msw_s2 s, int u, const Msw2Gap &G, msw_u2 c256, msw_s2 &diag, msw_s2 &fseg,
+                                             msw_s2 &ffull, msw_u2 &mblk, SegEnd seg_end)
 {
-	const msw_s2 hd = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c020c00u));   // H_A | H_B << 16   (row i - 1)
-	msw_s2 e = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c030c01u));          // E_A | E_B << 16
 	const msw_s2 h = s2_max(s2_max(diag + s, e), fseg);                    // Hpre(i, k) of both
 	const msw_u2 rel = {(unsigned short)(7 - u), (unsigned short)(7 - u)};
 	mblk = __builtin_elementwise_max(mblk, __builtin_bit_cast(msw_u2, h) * c256 + rel);
 	const msw_s2 hfin = s2_max(h, ffull);
 	e = s2_max(s2_sub0(e, G.e_del), s2_sub0(h, G.oe_del));
 	const msw_s2 t2 = s2_sub0(h, G.oe_ins);
-	fseg = s2_max(s2_sub0(fseg, G.e_ins), t2);
-	if constexpr (UNI) fseg = seg_end ? s2_splat(0) : fseg;
-	else fseg = s2_of(u_of(fseg) & ~(uint32_t)__builtin_amdgcn_sbfe((int)cd, 4 * u + 3, 1));   // -1 at the last position of a segment
+	fseg = seg_end(s2_max(s2_sub0(fseg, G.e_ins), t2));
 	ffull = s2_max(s2_sub0(ffull, G.e_ins), t2);
 	diag = hd;
+	return hfin;
+}
+
+// The same cell with the row state in one dword, as it lies in LDS: w = H, E of both as four bytes, unpacked and repacked with one
+// v_perm_b32 each.  The last position of a segment: seg_end, a wave-uniform fact (UNI), or bit 3 of entry u of cd.
+template <bool UNI>
+__device__ __forceinline__ void msw2_cell(uint32_t &w, msw_s2 s, uint32_t cd, int u, bool seg_end, const Msw2Gap &G, msw_u2 c256, msw_s2 &diag,
+                                          msw_s2 &fseg, msw_s2 &ffull, msw_u2 &mblk)
+{
+	const msw_s2 hd = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c020c00u));   // H_A | H_B << 16   (row i - 1)
+	msw_s2 e = s2_of(__builtin_amdgcn_perm(0u, w, 0x0c030c01u));          // E_A | E_B << 16
+	const msw_s2 hfin = msw2_recur(hd, e, s, u, G, c256, diag, fseg, ffull, mblk, [&](msw_s2 f) {
+		if constexpr (UNI) return seg_end ? s2_splat(0) : f;
+		else return s2_of(u_of(f) & ~(uint32_t)__builtin_amdgcn_sbfe((int)cd, 4 * u + 3, 1));   // -1 at the last position of a segment
+	});
 	w = __builtin_amdgcn_perm(u_of(e), u_of(hfin), 0x06020400u);            // bytes: H_A, E_A, H_B, E_B
+}
+
+// The target base of row i of a window of tn rows at rb — read upwards, or downwards from its last row (a reverse pass: row i is
+// rb + tn - 1 - i).  Rows past the end of the shorter window of a quad: its last row again, results unused.
+__device__ __forceinline__ int msw2_base_at(const uint8_t *__restrict__ pac, int64_t l_pac, int64_t rb, int tn, int i, bool down)
+{
+	const int ii = i < tn ? i : tn - 1;
+	return ii >= 0 ? msw_base(pac, l_pac, rb + (down ? tn - 1 - ii : ii)) : 0;
+}
+
+// What a lane holds after its last cell of a row and hands to its right neighbour: the diagonal, both F and the row's key so far
+struct Msw2Carry {
+	uint32_t diag = 0, fseg = 0, ffull = 0, key = 0;
+	__device__ __forceinline__ Msw2Carry from_left() const   // the left neighbour's, one step ago (every lane takes part: DPP)
+	{
+		Msw2Carry ci;
+		ci.diag = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)diag); ci.fseg = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)fseg);
+		ci.ffull = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)ffull);
+		ci.key = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)key);
+		return ci;
+	}
+	// the start of lane j's quarter of a row: lane 0 starts the row itself
+	__device__ __forceinline__ void open(int j, msw_s2 &d, msw_s2 &fs, msw_s2 &ff, msw_u2 &k) const
+	{
+		d = s2_of(j ? diag : 0u); fs = s2_of(j ? fseg : 0u); ff = s2_of(j ? ffull : 0u);
+		k = __builtin_bit_cast(msw_u2, j ? key : 0u);
+	}
+	__device__ __forceinline__ void close(msw_s2 d, msw_s2 fs, msw_s2 ff, msw_u2 k)
+	{
+		diag = u_of(d); fseg = u_of(fs); ffull = u_of(ff); key = __builtin_bit_cast(uint32_t, k);
+	}
+};
+
+// One alignment of a quad as lane 3 follows it over the rows of a pass: the best cell so far, and whether it is finished ahead of
+// its rows — at the 8-bit ceiling (sat), or with a row that raises the maximum to stop_score (KSW_XSTOP; INT_MAX: never)
+struct Msw2Half {
+	int gmax = 0, te = -1, qe = -1;
+	bool done = false;
+	__device__ __forceinline__ void take(int imax, int pos, int i, int sat_limit, int stop_score)   // row i: maximum imax, first at position pos
+	{
+		if (imax > gmax) {
+			gmax = imax; te = i; qe = pos;
+			if (gmax >= sat_limit || gmax >= stop_score) done = true;
+		}
+	}
+	// (the maximum moves in take() alone and stays once it is there: no flag of its own to carry over the rows)
+	__device__ __forceinline__ int sat(int sat_limit) const { return gmax >= sat_limit; }
+};
+
+// Lane 3's verdict on row i of both alignments.  keyAB: per alignment the row maximum * 256 + (255 - first position reaching it) —
+// the byte flavour has h < 250 and at most 256 positions.  Alignment X takes part while it has rows (tnX of them) and is not done;
+// KEEP_ROWS: its row maxima go to rowsX for the b[] scan, one per row at stride n_req.  True: neither has anything left to do.
+template <bool KEEP_ROWS>
+__device__ __forceinline__ bool msw2_row_verdict(Msw2Half &A, Msw2Half &B, uint32_t keyAB, int i, int tnA, int tnB, int sat_limit, int stopA, int stopB,
+                                                 uint16_t *rowsA, uint16_t *rowsB, int n_req)
+{
+	auto half = [&](Msw2Half &X, uint32_t key, int tn, int stop_score, uint16_t *rows) -> bool {
+		if (i < tn && !X.done) {
+			const int imax = (int)(key >> 8 & 0xff);
+			if constexpr (KEEP_ROWS) rows[(size_t)i * n_req] = (uint16_t)imax;
+			X.take(imax, 255 - (int)(key & 0xff), i, sat_limit, stop_score);
+		}
+		return i + 1 >= tn || X.done;
+	};
+	const bool a = half(A, keyAB, tnA, stopA, rowsA), b = half(B, keyAB >> 16, tnB, stopB, rowsB);
+	return a && b;
+}
+
+// The query side of a packed pass with the row state in LDS — where a cell's two scores come from:
+//   row(ta, tb)    the target bases of the row in hand
+//   block(c, on)   the code word(s) of the lane's block c of eight positions (eight 4-bit entries: query code, bit 3 = end of a segment)
+//   flags()        the code word that carries the segment ends
+//   score(u)       the two scores of position u of the block, as a packed pair
+// Msw2SharedQuery (msw2_kernel): both alignments have the same query — one code set, and per pair of target bases a row of eight
+// packed pairs in a 128-entry table.  Msw2OwnQueries (msw_rev2_kernel): each has its own — two code sets (the segment flags in A's
+// alone) and two tables of four rows, A's with the score in the low half and B's in the high half, or'ed together.
+struct Msw2SharedQuery {
+	const uint32_t *codes, *stab, *srow;
+	uint32_t cd;
+	__device__ __forceinline__ void row(int ta, int tb) { srow = stab + ((ta << 2 | tb) << 3); }
+	__device__ __forceinline__ void block(int c, bool on) { cd = on ? codes[c * 64 + (int)threadIdx.x] : 0u; }
+	__device__ __forceinline__ uint32_t flags() const { return cd; }
+	__device__ __forceinline__ msw_s2 score(int u) const
+	{
+		uint32_t q = __builtin_amdgcn_ubfe(cd, 4 * u, 3);
+		asm("" : "+v"(q));   // (opaque: v_bfe_u32 + v_lshl_add_u32 for the table address; folded, it is shift + and + add)
+		return s2_of(srow[q]);
+	}
+};
+struct Msw2OwnQueries {
+	const uint32_t *codesA, *codesB, *tabA, *tabB, *srowA, *srowB;
+	uint32_t cda, cdb;
+	__device__ __forceinline__ void row(int ta, int tb) { srowA = tabA + (ta << 3); srowB = tabB + (tb << 3); }
+	__device__ __forceinline__ void block(int c, bool on)
+	{
+		const int lane = threadIdx.x;
+		cda = on ? codesA[c * 64 + lane] : 0u; cdb = on ? codesB[c * 64 + lane] : 0u;
+	}
+	__device__ __forceinline__ uint32_t flags() const { return cda; }
+	__device__ __forceinline__ msw_s2 score(int u) const
+	{
+		uint32_t qA = __builtin_amdgcn_ubfe(cda, 4 * u, 3), qB = __builtin_amdgcn_ubfe(cdb, 4 * u, 3);
+		asm("" : "+v"(qA));
+		asm("" : "+v"(qB));
+		return s2_of(srowA[qA] | srowB[qB]);
+	}
+};
+
+// One packed pass for the 16 quads of the wave with the row state in LDS: the skewed pipeline of msw_pass, two alignments per quad.
+// cell[kk * 64 + lane]: H, E of both at position kk of the lane's S (cleared by the caller); tn rows (the longer of the two);
+// base(half, i): the target base of row i of alignment `half`; lane 3 gives verdict(i, keyAB) on every finished row, true = the quad
+// stops.  UNI: every live quad of the wave has segment length slen_u, the ends are known to the scalar unit; else bit 3 of the codes
+// decides — two copies of the pass, so that neither has a branch per cell.
+template <bool UNI, class Query, class Base, class Verdict>
+__device__ __forceinline__ void msw2_pass_lds(uint32_t *cell, const MswParams &P, bool live, int S, int tn, int slen_u, Query query, Base base,
+                                              Verdict verdict)
+{
+	const int lane = threadIdx.x, j = lane & 3;
+	bool run = live && tn > 0 && S > 0;
+	const Msw2Gap G(P);
+	int Swave = run ? S : 0;   // uniform trip count of the cell loop: the longest quarter in the wave
+	for (int o = 32; o; o >>= 1) Swave = max(Swave, __shfl_xor(Swave, o));
+	Msw2Carry co;
+	int ta_next = (run && j == 0) ? base(0, 0) : 0, tb_next = (run && j == 0) ? base(1, 0) : 0;
+	for (int t = 0; __any(run); ++t) {
+		const int i = t - j;                                   // the row this lane works on in this step
+		const bool act = run && i >= 0 && i < tn;
+		const int ta = ta_next, tb = tb_next;
+		if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base(0, i + 1); tb_next = base(1, i + 1); }   // in flight during this step
+		query.row(ta, tb);
+		const Msw2Carry ci = co.from_left();
+		msw_s2 diag, fseg, ffull;
+		msw_u2 key;
+		ci.open(j, diag, fseg, ffull, key);
+		// the key of a cell is taken relative to its block of eight (one packed multiply-add with constants and one packed maximum per
+		// cell), the block's offset is added once per block
+		msw_u2 c256 = {256, 256};
+		asm volatile("" : "+v"(c256));   // (opaque: h * 256 + rel is to be one v_pk_mad_u16, not a shift and an or)
+		msw_u2 poscv = {(unsigned short)(248 - j * S), (unsigned short)(248 - j * S)};   // 255 - 7 - (first position of the block)
+		const int kmax = act ? S : 0;
+		int seg_pos = 0;   // position inside the segment (a lane's quarter is four whole segments: the same in every lane)
+		const msw_u2 eight = {8, 8};
+		for (int c = 0; c * 8 < Swave; ++c, poscv -= eight) {
+			query.block(c, c * 8 < kmax);
+			msw_u2 mblk = {0, 0};
+#pragma unroll
+			for (int u = 0; u < 8; u += 2) {   // (quarters are even)
+				const int k = c * 8 + u;
+				bool end0 = false, end1 = false;
+				if constexpr (UNI) {
+					end0 = ++seg_pos == slen_u; if (end0) seg_pos = 0;
+					end1 = ++seg_pos == slen_u; if (end1) seg_pos = 0;
+				}
+				if (k < kmax) {
+					uint32_t w0 = cell[k * 64 + lane], w1 = cell[(k + 1) * 64 + lane];
+					msw2_cell<UNI>(w0, query.score(u), query.flags(), u, end0, G, c256, diag, fseg, ffull, mblk);
+					msw2_cell<UNI>(w1, query.score(u + 1), query.flags(), u + 1, end1, G, c256, diag, fseg, ffull, mblk);
+					cell[k * 64 + lane] = w0; cell[(k + 1) * 64 + lane] = w1;
+				}
+			}
+			if (c * 8 < kmax) key = __builtin_elementwise_max(key, mblk + poscv);
+		}
+		if (act) co.close(diag, fseg, ffull, key);
+		int stop = 0;
+		if (act && j == 3) stop = verdict(i, __builtin_bit_cast(uint32_t, key));
+		stop = msw_from_lane3(stop);
+		if (stop) run = false;
+	}
 }
 
 // cls[n_req] (zeroed before the launch): the class of every alignment that msw_rev2_kernel / msw_tail_kernel completes
@@ -368,163 +616,57 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 			codes[c * 64 + lane] = cd;
 		}
 	}
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	wave_lds_sync();
 	const int sat_limit = 255 - P.shift;
-	// the segment length when every live quad of the wave has the same one (else 0: the flags in the codes decide)
-	int slen_u = 0;
-	{
-		const unsigned long long lv = __builtin_amdgcn_ballot_w64(live);
-		if (lv) {
-			const int first = __builtin_amdgcn_readlane(slen, __ffsll((long long)lv) - 1);
-			slen_u = __builtin_amdgcn_ballot_w64(live && slen != first) ? 0 : first;
-		}
-	}
-	// ---- the forward pass of both ----
-	int gmaxA = 0, teA = -1, qeA = -1, gmaxB = 0, teB = -1, qeB = -1, satA = 0, satB = 0;
-	// (two copies of the pass — segment ends known to the scalar unit, or read from the codes — so that neither has a branch per cell)
-	auto forward = [&](auto uniform_segments) {
-		constexpr bool UNI = decltype(uniform_segments)::value;
-		const int tn = tnA > tnB ? tnA : tnB;
-		bool run = live && tn > 0 && S > 0;
-		const Msw2Gap G = {s2_splat(P.o_del + P.e_del), s2_splat(P.o_ins + P.e_ins), s2_splat(P.e_del), s2_splat(P.e_ins)};
-		int Swave = run ? S : 0;
-		for (int o = 32; o; o >>= 1) Swave = max(Swave, __shfl_xor(Swave, o));
-		uint32_t co_diag = 0, co_fseg = 0, co_ffull = 0, co_key = 0;
-		auto base_at = [&](const MswReq &rq, int tnx, int i) -> int {   // (rows past the end of the shorter window: its last row again, results unused)
-			const int ii = i < tnx ? i : tnx - 1;
-			return ii >= 0 ? msw_base(pac, P.l_pac, rq.rb + ii) : 0;
-		};
-		int ta_next = (run && j == 0) ? base_at(qa, tnA, 0) : 0, tb_next = (run && j == 0) ? base_at(qb, tnB, 0) : 0;
-		uint16_t *rowsA = rows + rA, *rowsB = rows + (hasB ? rB : rA);
-		for (int t = 0; __any(run); ++t) {
-			const int i = t - j;
-			const bool act = run && i >= 0 && i < tn;
-			const int ta = ta_next, tb = tb_next;
-			if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base_at(qa, tnA, i + 1); tb_next = base_at(qb, tnB, i + 1); }
-			const uint32_t *srow = stab + ((ta << 2 | tb) << 3);
-			const uint32_t ci_diag = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_diag), ci_fseg = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_fseg);
-			const uint32_t ci_ffull = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_ffull);
-			const uint32_t ci_key = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_key);
-			msw_s2 diag = s2_of(j ? ci_diag : 0u), fseg = s2_of(j ? ci_fseg : 0u), ffull = s2_of(j ? ci_ffull : 0u);
-			// the row maximum of each alignment and the first position that reaches it as ONE 16-bit key per alignment: h * 256 + (255 -
-			// position) — the byte flavour has h < 250 and at most 256 positions.  Inside a block of eight cells the key is taken relative
-			// to the block (h * 256 + 7 - u: one packed multiply-add with constants and one packed maximum per cell), the block's offset is
-			// added once per block.
-			msw_u2 key = __builtin_bit_cast(msw_u2, j ? ci_key : 0u);
-			msw_u2 c256 = {256, 256};
-			asm volatile("" : "+v"(c256));   // (opaque: h * 256 + rel is to be one v_pk_mad_u16, not a shift and an or)
-			msw_u2 poscv = {(unsigned short)(248 - j * S), (unsigned short)(248 - j * S)};   // 255 - 7 - (first position of the block)
-			const int kmax = act ? S : 0;
-			// (H, E and both F are never negative and h = Hpre is not either: "max(x - c, 0)" is one saturating subtraction.  seg_end: the
-			// end of a segment as a wave-uniform fact — slen_u > 0: every live quad of the wave has that segment length, which is the rule
-			// (the reads of a chunk are of one length) — or bit 3 of the position's code)
-			auto step = [&](uint32_t &w, uint32_t cd, int u, bool seg_end, msw_u2 &mblk) {
-				uint32_t q = __builtin_amdgcn_ubfe(cd, 4 * u, 3);
-				asm("" : "+v"(q));   // (opaque: v_bfe_u32 + v_lshl_add_u32 for the table address; folded, it is shift + and + add)
-				msw2_cell<UNI>(w, s2_of(srow[q]), cd, u, seg_end, G, c256, diag, fseg, ffull, mblk);
-			};
-			int seg_pos = 0;   // position inside the segment (a lane's quarter is four whole segments: the same in every lane)
-			const msw_u2 eight = {8, 8};
-			for (int c = 0; c * 8 < Swave; ++c, poscv -= eight) {
-				const uint32_t cd = c * 8 < kmax ? codes[c * 64 + lane] : 0u;
-				msw_u2 mblk = {0, 0};
-#pragma unroll
-				for (int u = 0; u < 8; u += 2) {
-					const int k = c * 8 + u;
-					bool end0 = false, end1 = false;
-					if constexpr (UNI) {
-						end0 = ++seg_pos == slen_u; if (end0) seg_pos = 0;
-						end1 = ++seg_pos == slen_u; if (end1) seg_pos = 0;
-					}
-					if (k < kmax) {
-						uint32_t w0 = cell[k * 64 + lane], w1 = cell[(k + 1) * 64 + lane];
-						step(w0, cd, u, end0, mblk); step(w1, cd, u + 1, end1, mblk);
-						cell[k * 64 + lane] = w0; cell[(k + 1) * 64 + lane] = w1;
-					}
-				}
-				if (c * 8 < kmax) key = __builtin_elementwise_max(key, mblk + poscv);
-			}
-			const uint32_t keyAB = __builtin_bit_cast(uint32_t, key);
-			if (act) { co_diag = u_of(diag); co_fseg = u_of(fseg); co_ffull = u_of(ffull); co_key = keyAB; }
-			int stop = 0;
-			if (act && j == 3) {
-				if (i < tnA && !satA) {
-					const int imax = (int)(keyAB >> 8 & 0xff);
-					rowsA[(size_t)i * n_req] = (uint16_t)imax;
-					if (imax > gmaxA) { gmaxA = imax; teA = i; qeA = 255 - (int)(keyAB & 0xff); if (gmaxA >= sat_limit) satA = 1; }
-				}
-				if (i < tnB && !satB) {
-					const int imax = (int)(keyAB >> 24);
-					rowsB[(size_t)i * n_req] = (uint16_t)imax;
-					if (imax > gmaxB) { gmaxB = imax; teB = i; qeB = 255 - (int)(keyAB >> 16 & 0xff); if (gmaxB >= sat_limit) satB = 1; }
-				}
-				if ((i + 1 >= tnA || satA) && (i + 1 >= tnB || satB)) stop = 1;
-			}
-			stop = msw_dpp<MSW_QP(3, 3, 3, 3)>(stop);
-			if (stop) run = false;
-		}
+	// ---- the forward pass of both: every row of the longer window (no KSW_XSTOP), the row maxima kept for the b[] scan ----
+	const int tn = tnA > tnB ? tnA : tnB;
+	Msw2Half hA, hB;
+	uint16_t *rowsA = rows + rA, *rowsB = rows + (hasB ? rB : rA);
+	auto base = [&](int half, int i) -> int {
+		return half ? msw2_base_at(pac, P.l_pac, qb.rb, tnB, i, false) : msw2_base_at(pac, P.l_pac, qa.rb, tnA, i, false);
 	};
-	// The same pass with the state in registers: the recurrence, the order of the cells and every key are those of `forward`.
-	auto forward_regs = [&]() {
-		constexpr int S = RS, SL = REGS ? SLEN : 1;
-		const int tn = tnA > tnB ? tnA : tnB;
+	auto verdict = [&](int i, uint32_t keyAB) -> bool {
+		return msw2_row_verdict<true>(hA, hB, keyAB, i, tnA, tnB, sat_limit, INT_MAX, INT_MAX, rowsA, rowsB, n_req);
+	};
+	if constexpr (REGS) {
+		// The pass of msw2_pass_lds with the state in registers: the recurrence, the order of the cells and every key are the same.
 		bool run = live && tn > 0;
-		const msw_s2 oe_del = s2_splat(P.o_del + P.e_del), oe_ins = s2_splat(P.o_ins + P.e_ins), e_del = s2_splat(P.e_del), e_ins = s2_splat(P.e_ins);
-		const msw_s2 zero = s2_splat(0);
-		uint32_t co_diag = 0, co_fseg = 0, co_ffull = 0, co_key = 0;
-		auto base_at = [&](const MswReq &rq, int tnx, int i) -> int {
-			const int ii = i < tnx ? i : tnx - 1;
-			return ii >= 0 ? msw_base(pac, P.l_pac, rq.rb + ii) : 0;
-		};
-		int ta_next = (run && j == 0) ? base_at(qa, tnA, 0) : 0, tb_next = (run && j == 0) ? base_at(qb, tnB, 0) : 0;
-		uint16_t *rowsA = rows + rA, *rowsB = rows + (hasB ? rB : rA);
-		const msw_u2 posc0 = {(unsigned short)(248 - j * S), (unsigned short)(248 - j * S)};   // 255 - 7 - (first position of the lane)
+		const Msw2Gap G(P);
+		Msw2Carry co;
+		int ta_next = (run && j == 0) ? base(0, 0) : 0, tb_next = (run && j == 0) ? base(1, 0) : 0;
+		const msw_u2 posc0 = {(unsigned short)(248 - j * RS), (unsigned short)(248 - j * RS)};   // 255 - 7 - (first position of the lane)
 		for (int t = 0; __any(run); ++t) {
 			const int i = t - j;
 			const bool act = run && i >= 0 && i < tn;
 			const int ta = ta_next, tb = tb_next;
-			if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base_at(qa, tnA, i + 1); tb_next = base_at(qb, tnB, i + 1); }
+			if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base(0, i + 1); tb_next = base(1, i + 1); }
 			const uint32_t *srow = stab + ((ta << 2 | tb) << 3);
-			const uint32_t ci_diag = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_diag), ci_fseg = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_fseg);
-			const uint32_t ci_ffull = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_ffull);
-			const uint32_t ci_key = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_key);
+			const Msw2Carry ci = co.from_left();
 			if (act) {   // (the skew steps in which a lane has no row: one branch, not a select per cell)
-				msw_s2 diag = s2_of(j ? ci_diag : 0u), fseg = s2_of(j ? ci_fseg : 0u), ffull = s2_of(j ? ci_ffull : 0u);
-				msw_u2 key = __builtin_bit_cast(msw_u2, j ? ci_key : 0u);   // per alignment: h * 256 + (255 - position), as in `forward`
+				msw_s2 diag, fseg, ffull;
+				msw_u2 key;
+				ci.open(j, diag, fseg, ffull, key);
 				msw_u2 c256 = {256, 256};
 				asm volatile("" : "+v"(c256));
 				// the score lookups of a block depend on the codes and the row's two bases only: all of a block's in flight ahead of its
 				// arithmetic, the next block's behind this one's
 				auto lookups = [&](int c, uint32_t *sv) {
 #pragma unroll
-					for (int u = 0; u < 8 && c * 8 + u < S; ++u)
+					for (int u = 0; u < 8 && c * 8 + u < RS; ++u)
 						sv[u] = *(const uint32_t *)((const char *)srow + __builtin_amdgcn_ubfe(cdreg[(c * 8 + u) >> 2], 8 * (u & 3), 8));
 					__builtin_amdgcn_sched_barrier(0);   // (the reads stay ahead of the arithmetic they were issued for)
 				};
 				auto step = [&](int kk, int u, uint32_t sq, msw_u2 &mblk) {
-					msw_s2 hd, e;
-					if constexpr (TWO) { hd = s2_of(st0[kk]); e = s2_of(st1[kk]); }
-					else {
-						hd = s2_of(__builtin_amdgcn_perm(0u, st0[kk], 0x0c020c00u));   // H_A | H_B << 16   (row i - 1)
-						e = s2_of(__builtin_amdgcn_perm(0u, st0[kk], 0x0c030c01u));    // E_A | E_B << 16
-					}
-					const msw_s2 h = s2_max(s2_max(diag + s2_of(sq), e), fseg);        // Hpre(i, k) of both
-					const msw_u2 rel = {(unsigned short)(7 - u), (unsigned short)(7 - u)};
-					mblk = __builtin_elementwise_max(mblk, __builtin_bit_cast(msw_u2, h) * c256 + rel);
-					const msw_s2 hfin = s2_max(h, ffull);
-					e = s2_max(s2_sub0(e, e_del), s2_sub0(h, oe_del));
-					const msw_s2 t2 = s2_sub0(h, oe_ins);
-					if ((kk + 1) % SL == 0) fseg = zero;   // the last position of a segment: F restarts
-					else fseg = s2_max(s2_sub0(fseg, e_ins), t2);
-					ffull = s2_max(s2_sub0(ffull, e_ins), t2);
-					diag = hd;
-					if constexpr (TWO) { st0[kk] = u_of(hfin); st1[kk] = u_of(e); }
-					else st0[kk] = __builtin_amdgcn_perm(u_of(e), u_of(hfin), 0x06020400u);   // bytes: H_A, E_A, H_B, E_B
+					const bool seg_end = (kk + 1) % SLEN == 0;   // (known to the compiler: F_seg restarts by assignment)
+					if constexpr (TWO) {
+						msw_s2 e = s2_of(st1[kk]);
+						st0[kk] = u_of(msw2_recur(s2_of(st0[kk]), e, s2_of(sq), u, G, c256, diag, fseg, ffull, mblk,
+						                          [&](msw_s2 f) { return seg_end ? s2_splat(0) : f; }));
+						st1[kk] = u_of(e);
+					} else msw2_cell<true>(st0[kk], s2_of(sq), 0u, u, seg_end, G, c256, diag, fseg, ffull, mblk);
 				};
-				constexpr int NB = (S + 7) / 8;   // blocks of eight cells, the last one may be half a block
-				// (the code words are opaque once per row, in place: else the S byte selects are hoisted into S registers held over the rows)
+				constexpr int NB = (RS + 7) / 8;   // blocks of eight cells, the last one may be half a block
+				// (the code words are opaque once per row, in place: else the RS byte selects are hoisted into RS registers held over the rows)
 #pragma unroll
 				for (int c = 0; c < RC; ++c) asm volatile("" : "+v"(cdreg[c]));
 				uint32_t sv[2][8];
@@ -534,38 +676,32 @@ __global__ __launch_bounds__(64) void msw2_kernel(MswParams P, int n_pairs, int 
 					if (c + 1 < NB) lookups(c + 1, sv[(c + 1) & 1]);
 					msw_u2 mblk = {0, 0};
 #pragma unroll
-					for (int u = 0; u < 8 && c * 8 + u < S; ++u) step(c * 8 + u, u, sv[c & 1][u], mblk);
+					for (int u = 0; u < 8 && c * 8 + u < RS; ++u) step(c * 8 + u, u, sv[c & 1][u], mblk);
 					const msw_u2 blk0 = {(unsigned short)(8 * c), (unsigned short)(8 * c)};
 					key = __builtin_elementwise_max(key, mblk + (posc0 - blk0));
 				}
-				co_diag = u_of(diag); co_fseg = u_of(fseg); co_ffull = u_of(ffull); co_key = __builtin_bit_cast(uint32_t, key);
+				co.close(diag, fseg, ffull, key);
 			}
-			const uint32_t keyAB = co_key;
 			int stop = 0;
-			if (act && j == 3) {
-				if (i < tnA && !satA) {
-					const int imax = (int)(keyAB >> 8 & 0xff);
-					rowsA[(size_t)i * n_req] = (uint16_t)imax;
-					if (imax > gmaxA) { gmaxA = imax; teA = i; qeA = 255 - (int)(keyAB & 0xff); if (gmaxA >= sat_limit) satA = 1; }
-				}
-				if (i < tnB && !satB) {
-					const int imax = (int)(keyAB >> 24);
-					rowsB[(size_t)i * n_req] = (uint16_t)imax;
-					if (imax > gmaxB) { gmaxB = imax; teB = i; qeB = 255 - (int)(keyAB >> 16 & 0xff); if (gmaxB >= sat_limit) satB = 1; }
-				}
-				if ((i + 1 >= tnA || satA) && (i + 1 >= tnB || satB)) stop = 1;
-			}
-			stop = msw_dpp<MSW_QP(3, 3, 3, 3)>(stop);
+			if (act && j == 3) stop = verdict(i, co.key);
+			stop = msw_from_lane3(stop);
 			if (stop) run = false;
 		}
-	};
-	if constexpr (REGS) forward_regs();
-	else if (slen_u > 0) forward(std::true_type{});
-	else forward(std::false_type{});
-	MswPassOut fA, fB;
-	fA.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxA); fA.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teA); fA.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeA);
-	fB.score = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxB); fB.te = msw_dpp<MSW_QP(3, 3, 3, 3)>(teB); fB.qe = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeB);
-	satA = msw_dpp<MSW_QP(3, 3, 3, 3)>(satA); satB = msw_dpp<MSW_QP(3, 3, 3, 3)>(satB);
+	} else {
+		// the segment length when every live quad of the wave has the same one — the rule: the reads of a chunk are of one length —
+		// else 0: the flags in the codes decide
+		int slen_u = 0;
+		const unsigned long long lv = __builtin_amdgcn_ballot_w64(live);
+		if (lv) {
+			const int first = __builtin_amdgcn_readlane(slen, __ffsll((long long)lv) - 1);
+			slen_u = __builtin_amdgcn_ballot_w64(live && slen != first) ? 0 : first;
+		}
+		const Msw2SharedQuery query = {codes, stab, stab, 0u};
+		if (slen_u > 0) msw2_pass_lds<true>(cell, P, live, S, tn, slen_u, query, base, verdict);
+		else msw2_pass_lds<false>(cell, P, live, S, tn, slen_u, query, base, verdict);
+	}
+	const MswPassOut fA = msw_quad_result(hA.gmax, hA.te, hA.qe), fB = msw_quad_result(hB.gmax, hB.te, hB.qe);
+	const int satA = msw_from_lane3(hA.sat(sat_limit)), satB = msw_from_lane3(hB.sat(sat_limit));
 	// Every alignment gets its record as msw_tail would leave it without a second pass (lane 0: A, lane 1: B).  One that reaches minsc
 	// unsaturated needs the b[] scan and the reverse pass: it gets its class byte, from which the sort kernels below make the lists of
 	// msw_rev2_kernel, which completes the record.  No list is appended to here: the lists are a function of the results alone.
@@ -649,8 +785,6 @@ __global__ __launch_bounds__(64) void msw_cls_scan_kernel(int n_blocks, int *__r
 // from the row maxima and the reverse pass that finds where the alignment starts — 16 alignments per wave, one per quad, all of them
 // live.  A wave runs in lockstep as long as its longest reverse pass (rows ~ score / a, cells ~ qe), so it takes the alignments in
 // the order of the class sort, the long ones first.  This is the path of MPIBWA_MSW_REV2=0; msw_rev2_kernel is the default.
-// b[] scan: each lane of a quad fetches 16 of the next 64 row maxima (independent loads, all in flight at once), the quad parks them in
-// LDS and every lane applies the sequential run rule of src/ksw.c:196-226 to the 64 values in row order.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, const int *__restrict__ cls_off, const int *__restrict__ sorted,
                                                       const MswReq *__restrict__ req, const uint8_t *__restrict__ seq, const int64_t *__restrict__ off,
@@ -660,7 +794,7 @@ __global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, co
 	extern __shared__ uint32_t lds_t[];
 	uint16_t *blk = (uint16_t *)lds_t;                       // [16 quads][64 rows]: the row maxima of the b[] block in hand
 	uint32_t *cell = lds_t + 16 * 64 / 2;                    // msw_pass's layout
-	const int lane = threadIdx.x, j = lane & 3, quad = lane >> 2;
+	const int quad = threadIdx.x >> 2;
 	// the slot in the sorted list, long reverse passes first
 	const int slot = blockIdx.x * 16 + quad;
 	const bool live = slot < cls_off[MSW_NCLS];
@@ -674,79 +808,20 @@ __global__ __launch_bounds__(64) void msw_tail_kernel(MswParams P, int n_req, co
 	const int qlen = live ? lens[rq.read] : 0;
 	const int tlen = live ? (int)(rq.re - rq.rb) : 0;
 	const uint8_t *ms = seq + (live ? off[rq.read] : 0);
-	const bool byte_flavour = qlen * P.a < 250;
-	const int PP = byte_flavour ? 16 : 8;
-	const int minsc = P.min_seed_len * P.a;
-	const int sat_limit = byte_flavour ? 255 - P.shift : 0x10000;
-	// ---- b[]: runs of rows whose maximum reaches minsc; second best = best run outside te +- ceil(score / max) ----
-	{
-		const int d = (out.score + P.max_sc - 1) / P.max_sc;
-		const int low = out.te - d, high = out.te + d;
-		int last_sc = -1, last_i = -1, sc2 = -1, te2 = -1;
-		int twave = tlen;
-		for (int o = 32; o; o >>= 1) twave = max(twave, __shfl_xor(twave, o));
-		uint16_t *qb = blk + quad * 64;
-		for (int i0 = 0; i0 < twave; i0 += 64) {
-			uint16_t v[16];
-#pragma unroll
-			for (int u = 0; u < 16; ++u) {
-				const int i = i0 + u * 4 + j;
-				v[u] = i < tlen ? rows[(size_t)i * n_req + r] : (uint16_t)0;
-			}
-			bool any = false;
-#pragma unroll
-			for (int u = 0; u < 16; ++u) {
-				qb[u * 4 + j] = v[u];
-				any |= i0 + u * 4 + j < tlen && (int)v[u] >= minsc;
-			}
-			if (!__any(any)) continue;
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-			const int kend = min(64, tlen - i0);
-			for (int k = 0; k < kend; ++k) {
-				const int i = i0 + k, im = qb[k];
-				if (im < minsc) continue;
-				if (last_i < 0 || last_i + 1 != i) {
-					if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
-					last_sc = im; last_i = i;
-				} else if (last_sc < im) { last_sc = im; last_i = i; }
-			}
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-		}
-		if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
-		out.score2 = sc2; out.te2 = te2;
-	}
-	// ---- the reverse pass over the reversed prefixes: where does the best local alignment start (KSW_XSTART) ----
-	int qlen2 = live ? out.qe + 1 : 0;
-	if (live && out.qe >= qlen) qlen2 = 0;   // cannot happen (the maximum of a row is reached on a real base first); stay in bounds
-	const int slen2 = (qlen2 + PP - 1) / PP, npos2 = slen2 * PP, S2 = npos2 >> 2;
-	if (qlen2 > 0)   // the codes of positions qe .. 0, padded, dealt to the quad; H and E cleared
-		for (int kk = 0; kk < S2; ++kk) {
-			const int k = j * S2 + kk;
-			const uint32_t c = k < qlen2 ? msw_code(ms, qlen, rq.is_rev, qlen2 - 1 - k) : MSW_PAD;
-			cell[kk * 64 + lane] = c << 26 | ((k + 1) % slen2 == 0 ? 0x80000000u : 0u);
-		}
-	int sat2 = 0;
-	const MswPassOut g = msw_pass(cell, P, pac, qlen2 > 0, S2, out.te + 1, rq.rb + out.te, -1, out.score, sat_limit, nullptr, 0, &sat2);
-	if (qlen2 > 0 && g.score == out.score) { out.tb = out.te - g.te; out.qb = out.qe - g.qe; }
-	if (live && qlen2 == 0) out.flags = 1;
-	if (sat2) out.flags = 1;
-	if (live && j == 0) res[r] = out;
+	msw_scan_rows(blk + quad * 64, rows, n_req, r, tlen, live, P.min_seed_len * P.a, P.max_sc, out);
+	msw_reverse_one(cell, P, pac, live, live, rq, qlen, ms, out, res, r);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // msw_rev2_kernel: what msw_tail_kernel does, for TWO alignments of one class per quad, the reverse passes in the packed arithmetic of
-// msw2_kernel's forward pass (msw2_cell).  The two rarely share a query — the query of a reverse pass is the reversed prefix 0..qe of
+// msw2_kernel's forward pass (msw2_pass_lds with Msw2OwnQueries).  The two rarely share a query — the query of a reverse pass is the reversed prefix 0..qe of
 // its own mate — but they share slen2, and with it S2, the segment ends and the hand-over points.  So every half has its own request,
 // its own te and qe from res[], its own code set (codesA / codesB, positions qe .. 0 padded to 16 slen2 with MSW_PAD; the segment flags
 // in codesA alone) and its own target bases, and the score of a cell is two lookups or'ed together: (target base, code) of A in a
 // table that holds the score in the low half, of B in one that holds it in the high half.  Half X has te_X + 1 rows (row i reads
 // rb_X + te_X - i); past them it repeats its last row and nothing of it is kept.  KSW_XSTOP is per half: once a row raises X's maximum
 // to its forward score (or to the 8-bit ceiling: flags = 1 for X alone) X is done and frozen; the quad stops when both are done or out of
-// rows.  The b[] scan is msw_tail_kernel's, run for A and then for B; its block of row maxima shares LDS with the pass's row state.
+// rows.  The b[] scan (msw_scan_rows) runs for A and then for B; its block of row maxima shares LDS with the pass's row state.
 // A work item is (class, pair): slot -> class by ioff[], the pair's members are neighbours in sorted[].
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void msw_rev2_kernel(MswParams P, int n_req, const int *__restrict__ cls_off, const int *__restrict__ cls_ioff,
@@ -786,58 +861,15 @@ __global__ __launch_bounds__(64) void msw_rev2_kernel(MswParams P, int n_req, co
 	const uint8_t *msA = seq + (live ? off[qa.read] : 0), *msB = seq + (hasB ? off[qb.read] : 0);
 	const int minsc = P.min_seed_len * P.a;
 	const int sat_limit = 255 - P.shift;
-	// ---- b[]: runs of rows whose maximum reaches minsc; second best = best run outside te +- ceil(score / max) ----
-	uint16_t *qblk = blk + quad * 64;
-	auto scan = [&](bool has, int r, int tlen, MswRes &out) {
-		const int d = (out.score + P.max_sc - 1) / P.max_sc;
-		const int low = out.te - d, high = out.te + d;
-		int last_sc = -1, last_i = -1, sc2 = -1, te2 = -1;
-		int twave = has ? tlen : 0;
-		for (int s = 32; s; s >>= 1) twave = max(twave, __shfl_xor(twave, s));
-		for (int i0 = 0; i0 < twave; i0 += 64) {
-			uint16_t v[16];
-#pragma unroll
-			for (int u = 0; u < 16; ++u) {
-				const int i = i0 + u * 4 + j;
-				v[u] = has && i < tlen ? rows[(size_t)i * n_req + r] : (uint16_t)0;
-			}
-			bool any = false;
-#pragma unroll
-			for (int u = 0; u < 16; ++u) {
-				qblk[u * 4 + j] = v[u];
-				any |= has && i0 + u * 4 + j < tlen && (int)v[u] >= minsc;
-			}
-			if (!__any(any)) continue;
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-			const int kend = has ? min(64, tlen - i0) : 0;
-			for (int k = 0; k < kend; ++k) {
-				const int i = i0 + k, im = qblk[k];
-				if (im < minsc) continue;
-				if (last_i < 0 || last_i + 1 != i) {
-					if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
-					last_sc = im; last_i = i;
-				} else if (last_sc < im) { last_sc = im; last_i = i; }
-			}
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-		}
-		if (last_i >= 0 && (last_i < low || last_i > high) && last_sc > sc2) { sc2 = last_sc; te2 = last_i; }
-		out.score2 = sc2; out.te2 = te2;
-	};
-	scan(live, rA, (int)(qa.re - qa.rb), oA);
-	scan(hasB, rB, (int)(qb.re - qb.rb), oB);
+	msw_scan_rows(blk + quad * 64, rows, n_req, rA, (int)(qa.re - qa.rb), live, minsc, P.max_sc, oA);
+	msw_scan_rows(blk + quad * 64, rows, n_req, rB, (int)(qb.re - qb.rb), hasB, minsc, P.max_sc, oB);
 	// ---- set-up of the reverse pass: the codes of positions qe .. 0 of each half, padded, dealt to the quad; H and E cleared ----
 	int qlen2A = live ? oA.qe + 1 : 0, qlen2B = hasB ? oB.qe + 1 : 0;
 	if (oA.qe >= qlenA) qlen2A = 0;   // cannot happen (the maximum of a row is reached on a real base first); stay in bounds
 	if (oB.qe >= qlenB) qlen2B = 0;
 	const int slen2 = (max(qlen2A, qlen2B) + 15) / 16, S2 = slen2 * 4;   // (one class: the same for both)
 	const int tnA = qlen2A > 0 ? oA.te + 1 : 0, tnB = qlen2B > 0 ? oB.te + 1 : 0;
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	wave_lds_sync();
 	if (live) {
 		for (int kk = 0; kk < S2; ++kk) cell[kk * 64 + lane] = 0;
 		for (int c = 0; c * 8 < S2; ++c) {
@@ -852,9 +884,7 @@ __global__ __launch_bounds__(64) void msw_rev2_kernel(MswParams P, int n_req, co
 			codesA[c * 64 + lane] = ca; codesB[c * 64 + lane] = cb;
 		}
 	}
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	wave_lds_sync();
 	// the segment length when every live quad of the wave has the same one (the rule: a wave is of one class but where two meet)
 	int slen_u = 0;
 	{
@@ -862,114 +892,42 @@ __global__ __launch_bounds__(64) void msw_rev2_kernel(MswParams P, int n_req, co
 		const int first = __builtin_amdgcn_readlane(slen2, __ffsll((long long)lv) - 1);
 		slen_u = __builtin_amdgcn_ballot_w64(live && slen2 != first) ? 0 : first;
 	}
-	// ---- the reverse pass of both ----
-	int gmaxA = 0, teA = -1, qeA = -1, gmaxB = 0, teB = -1, qeB = -1, satA = 0, satB = 0;
-	auto reverse = [&](auto uniform_segments) {
-		constexpr bool UNI = decltype(uniform_segments)::value;
-		const int tn = tnA > tnB ? tnA : tnB;
-		bool run = live && tn > 0 && S2 > 0;
-		const Msw2Gap G = {s2_splat(P.o_del + P.e_del), s2_splat(P.o_ins + P.e_ins), s2_splat(P.e_del), s2_splat(P.e_ins)};
-		int Swave = run ? S2 : 0;
-		for (int s = 32; s; s >>= 1) Swave = max(Swave, __shfl_xor(Swave, s));
-		uint32_t co_diag = 0, co_fseg = 0, co_ffull = 0, co_key = 0;
-		auto base_at = [&](const MswReq &rq, int tnx, int i) -> int {   // (rows past the end of the shorter pass: its last row again, results unused)
-			const int ii = i < tnx ? i : tnx - 1;
-			return ii >= 0 ? msw_base(pac, P.l_pac, rq.rb + (tnx - 1 - ii)) : 0;   // row i of the reverse pass: rb + te - i
-		};
-		int ta_next = (run && j == 0) ? base_at(qa, tnA, 0) : 0, tb_next = (run && j == 0) ? base_at(qb, tnB, 0) : 0;
-		bool doneA = tnA <= 0, doneB = tnB <= 0;
-		for (int t = 0; __any(run); ++t) {
-			const int i = t - j;
-			const bool act = run && i >= 0 && i < tn;
-			const int ta = ta_next, tb = tb_next;
-			if (run && i + 1 >= 0 && i + 1 < tn) { ta_next = base_at(qa, tnA, i + 1); tb_next = base_at(qb, tnB, i + 1); }
-			const uint32_t *srowA = tabA + (ta << 3), *srowB = tabB + (tb << 3);
-			const uint32_t ci_diag = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_diag), ci_fseg = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_fseg);
-			const uint32_t ci_ffull = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_ffull);
-			const uint32_t ci_key = (uint32_t)msw_dpp<MSW_QP(0, 0, 1, 2)>((int)co_key);
-			msw_s2 diag = s2_of(j ? ci_diag : 0u), fseg = s2_of(j ? ci_fseg : 0u), ffull = s2_of(j ? ci_ffull : 0u);
-			msw_u2 key = __builtin_bit_cast(msw_u2, j ? ci_key : 0u);   // per alignment: h * 256 + (255 - position), as in msw2_kernel
-			msw_u2 c256 = {256, 256};
-			asm volatile("" : "+v"(c256));
-			msw_u2 poscv = {(unsigned short)(248 - j * S2), (unsigned short)(248 - j * S2)};
-			const int kmax = act ? S2 : 0;
-			auto step = [&](uint32_t &w, uint32_t cda, uint32_t cdb, int u, bool seg_end, msw_u2 &mblk) {
-				uint32_t qA = __builtin_amdgcn_ubfe(cda, 4 * u, 3), qB = __builtin_amdgcn_ubfe(cdb, 4 * u, 3);
-				asm("" : "+v"(qA));
-				asm("" : "+v"(qB));
-				msw2_cell<UNI>(w, s2_of(srowA[qA] | srowB[qB]), cda, u, seg_end, G, c256, diag, fseg, ffull, mblk);
-			};
-			int seg_pos = 0;
-			const msw_u2 eight = {8, 8};
-			for (int c = 0; c * 8 < Swave; ++c, poscv -= eight) {
-				const uint32_t cda = c * 8 < kmax ? codesA[c * 64 + lane] : 0u, cdb = c * 8 < kmax ? codesB[c * 64 + lane] : 0u;
-				msw_u2 mblk = {0, 0};
-#pragma unroll
-				for (int u = 0; u < 8; u += 2) {
-					const int k = c * 8 + u;
-					bool end0 = false, end1 = false;
-					if constexpr (UNI) {
-						end0 = ++seg_pos == slen_u; if (end0) seg_pos = 0;
-						end1 = ++seg_pos == slen_u; if (end1) seg_pos = 0;
-					}
-					if (k < kmax) {
-						uint32_t w0 = cell[k * 64 + lane], w1 = cell[(k + 1) * 64 + lane];
-						step(w0, cda, cdb, u, end0, mblk); step(w1, cda, cdb, u + 1, end1, mblk);
-						cell[k * 64 + lane] = w0; cell[(k + 1) * 64 + lane] = w1;
-					}
-				}
-				if (c * 8 < kmax) key = __builtin_elementwise_max(key, mblk + poscv);
-			}
-			const uint32_t keyAB = __builtin_bit_cast(uint32_t, key);
-			if (act) { co_diag = u_of(diag); co_fseg = u_of(fseg); co_ffull = u_of(ffull); co_key = keyAB; }
-			int stop = 0;
-			if (act && j == 3) {
-				if (i < tnA && !doneA) {
-					const int imax = (int)(keyAB >> 8 & 0xff);
-					if (imax > gmaxA) {
-						gmaxA = imax; teA = i; qeA = 255 - (int)(keyAB & 0xff);
-						if (gmaxA >= sat_limit) { satA = 1; doneA = true; }
-						if (gmaxA >= oA.score) doneA = true;   // KSW_XSTOP at the forward score
-					}
-				}
-				if (i < tnB && !doneB) {
-					const int imax = (int)(keyAB >> 24);
-					if (imax > gmaxB) {
-						gmaxB = imax; teB = i; qeB = 255 - (int)(keyAB >> 16 & 0xff);
-						if (gmaxB >= sat_limit) { satB = 1; doneB = true; }
-						if (gmaxB >= oB.score) doneB = true;
-					}
-				}
-				if ((i + 1 >= tnA || doneA) && (i + 1 >= tnB || doneB)) stop = 1;
-			}
-			stop = msw_dpp<MSW_QP(3, 3, 3, 3)>(stop);
-			if (stop) run = false;
-		}
+	// ---- the reverse pass of both: rows te_X .. 0, each until its forward score is reached (KSW_XSTOP) ----
+	Msw2Half hA, hB;
+	hA.done = tnA <= 0; hB.done = tnB <= 0;
+	auto base = [&](int half, int i) -> int {
+		return half ? msw2_base_at(pac, P.l_pac, qb.rb, tnB, i, true) : msw2_base_at(pac, P.l_pac, qa.rb, tnA, i, true);
 	};
-	if (slen_u > 0) reverse(std::true_type{});
-	else reverse(std::false_type{});
+	auto verdict = [&](int i, uint32_t keyAB) -> bool {
+		return msw2_row_verdict<false>(hA, hB, keyAB, i, tnA, tnB, sat_limit, oA.score, oB.score, nullptr, nullptr, 0);
+	};
+	const Msw2OwnQueries query = {codesA, codesB, tabA, tabB, tabA, tabB, 0u, 0u};
+	if (slen_u > 0) msw2_pass_lds<true>(cell, P, live, S2, max(tnA, tnB), slen_u, query, base, verdict);
+	else msw2_pass_lds<false>(cell, P, live, S2, max(tnA, tnB), slen_u, query, base, verdict);
 	// ---- the records: lane 0 completes A's, lane 1 B's ----
-	gmaxA = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxA); teA = msw_dpp<MSW_QP(3, 3, 3, 3)>(teA); qeA = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeA);
-	gmaxB = msw_dpp<MSW_QP(3, 3, 3, 3)>(gmaxB); teB = msw_dpp<MSW_QP(3, 3, 3, 3)>(teB); qeB = msw_dpp<MSW_QP(3, 3, 3, 3)>(qeB);
-	satA = msw_dpp<MSW_QP(3, 3, 3, 3)>(satA); satB = msw_dpp<MSW_QP(3, 3, 3, 3)>(satB);
-	auto complete = [&](MswRes &out, int qlen2, int gs, int gte, int gqe, int gsat) {
-		if (qlen2 > 0 && gs == out.score) { out.tb = out.te - gte; out.qb = out.qe - gqe; }
+	const MswPassOut gA = msw_quad_result(hA.gmax, hA.te, hA.qe), gB = msw_quad_result(hB.gmax, hB.te, hB.qe);
+	const int satA = msw_from_lane3(hA.sat(sat_limit)), satB = msw_from_lane3(hB.sat(sat_limit));
+	auto complete = [&](MswRes &out, int qlen2, const MswPassOut &g, int gsat) {
+		if (qlen2 > 0 && g.score == out.score) { out.tb = out.te - g.te; out.qb = out.qe - g.qe; }
 		if (qlen2 == 0 || gsat) out.flags = 1;
 	};
-	if (live && j == 0) { complete(oA, qlen2A, gmaxA, teA, qeA, satA); res[rA] = oA; }
-	if (hasB && j == 1) { complete(oB, qlen2B, gmaxB, teB, qeB, satB); res[rB] = oB; }
+	if (live && j == 0) { complete(oA, qlen2A, gA, satA); res[rA] = oA; }
+	if (hasB && j == 1) { complete(oB, qlen2B, gB, satB); res[rB] = oB; }
 }
 
 } // namespace
 
+// positions per lane for the longest read: a quarter of the padded query (padding to 16 covers both lane widths)
+static int msw_s_max(int max_len) { return (max_len + 15) / 16 * 16 / 4; }
+
 size_t msw_lds_bytes(int max_len)
 {
-	return (size_t)((max_len + 15) / 16 * 16 / 4) * 64 * 4;   // a quarter of the padded query per lane (padding to 16 covers both lane widths)
+	return (size_t)msw_s_max(max_len) * 64 * 4;
 }
 
 size_t msw2_lds_bytes(int max_len)
 {
-	const int s_max = (max_len + 15) / 16 * 16 / 4;
+	const int s_max = msw_s_max(max_len);
 	return ((size_t)s_max * 64 + (size_t)((s_max + 7) / 8) * 64 + 128) * 4;
 }
 
@@ -980,7 +938,7 @@ size_t msw_tail_lds_bytes(int max_len)
 
 size_t msw_rev2_lds_bytes(int max_len)
 {
-	const int s_max = (max_len + 15) / 16 * 16 / 4;
+	const int s_max = msw_s_max(max_len);
 	// the row state (the b[] block of every quad before it, in the same place), two code sets, two score tables
 	return ((size_t)std::max(s_max * 64, 16 * 64 / 2) + 2 * (size_t)((s_max + 7) / 8) * 64 + 64) * 4;
 }
@@ -1063,10 +1021,13 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 	const size_t lds_r = msw_rev2_lds_bytes(max_len);
 	if (lds > 160 * 1024) die("mate-rescue kernel: reads of %d bp do not fit the LDS row buffers", max_len);
 	static size_t s_attr = 0, s_attr2 = 0, s_attr_t = 0, s_attr_r = 0;
-	if (lds > s_attr) {
-		HIP_OK(hipFuncSetAttribute((const void *)msw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		s_attr = lds;
-	}
+	// a kernel's dynamic LDS limit follows the longest read seen so far
+	auto allow_lds = [](const void *kernel, size_t bytes, size_t &allowed) {
+		if (bytes <= allowed) return;
+		HIP_OK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+		allowed = bytes;
+	};
+	allow_lds((const void *)msw_kernel, lds, s_attr);
 	static const bool pairing = !(getenv("MPIBWA_MSW_PAIRS") && atoi(getenv("MPIBWA_MSW_PAIRS")) == 0);
 	static const bool regs_form = !(getenv("MPIBWA_MSW_REGS") && atoi(getenv("MPIBWA_MSW_REGS")) == 0);   // 0: every work item in the general form (the A/B)
 	const bool rev2 = msw_rev2_on();
@@ -1118,23 +1079,14 @@ void launch_msw(void *stream, const MswParams &P, int n_req, const MswReq *d_req
 		HIP_OK(hipMemcpyAsync(d_list, h_list, (size_t)2 * n_req * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
 		d_single = d_list + (sl_end - h_list);
 		if (n_pairs) {
-			if (lds2 > s_attr2) {
-				HIP_OK(hipFuncSetAttribute((const void *)msw2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-				s_attr2 = lds2;
-			}
-			if (lds_t > s_attr_t) {
-				HIP_OK(hipFuncSetAttribute((const void *)msw_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-				s_attr_t = lds_t;
-			}
-			if (lds_r > s_attr_r) {
-				HIP_OK(hipFuncSetAttribute((const void *)msw_rev2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
-				s_attr_r = lds_r;
-			}
+			allow_lds((const void *)msw2_kernel<0>, lds2, s_attr2);
+			allow_lds((const void *)msw_tail_kernel, lds_t, s_attr_t);
+			allow_lds((const void *)msw_rev2_kernel, lds_r, s_attr_r);
 			// the forward passes, then — same stream, before the next batch reuses d_rows — the second passes of the alignments they
 			// gave a class: the class bytes sorted into lists (three small launches), then two of a class per quad (msw_rev2_kernel).
 			// Grids from the worst case — every byte-flavour request has a class, and every class an odd member — nothing is read
 			// back; the waves without work return.
-			const int s_max = (max_len + 15) / 16 * 16 / 4;
+			const int s_max = msw_s_max(max_len);
 			int *d_coff = d_tail, *d_cioff = d_tail + MSW_OFF_INTS, *d_sorted = d_tail + 2 * MSW_OFF_INTS;
 			uint8_t *d_cls = (uint8_t *)(d_sorted + n_req);
 			int *d_hist = d_sorted + n_req + ((size_t)n_req + 3) / 4;
