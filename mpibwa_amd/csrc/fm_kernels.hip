@@ -145,13 +145,14 @@ __global__ void __launch_bounds__(256) kmt_build_kernel(FmDev fm, int L, uint4 *
 	if (L == 1) { x0 = fm.L2[b] + 1; x2 = fm.L2[b + 1] - fm.L2[b]; x1 = fm.L2[3 - b] + 1; }
 	else {
 		kmt_unpack(tab[kmt_first(L - 1) + (u32)(code >> 2)], x0, x1, x2);
-		if (x2 == 0) x0 = x1 = 0;   // (no sweep ever asks for a string whose prefix does not occur)
-		else {
-			const int csel = 3 - b;
-			u64 oa, omir, os;
-			lane_extend<false>(fm, (const char *)fm.occ32 + 16 * csel, lds_sb + csel, x1, x0, x2, oa, omir, os);
-			x1 = oa; x0 = omir; x2 = os;
-		}
+		// A prefix that does not occur (x2 == 0) is extended like any other: a sweep that starts on a base the text lacks walks on
+		// with an empty interval to the end of the read (src/bwt.c:299-311 stops on a CHANGE of size only), reports it, and goes on
+		// extending past the tables' depth from what it took from them — so the entry holds what the steps give (row numbers of
+		// 1 .. seq_len + 1, as for every string), never a row 0 that lane_extend would turn into row -1.
+		const int csel = 3 - b;
+		u64 oa, omir, os;
+		lane_extend<false>(fm, (const char *)fm.occ32 + 16 * csel, lds_sb + csel, x1, x0, x2, oa, omir, os);
+		x1 = oa; x0 = omir; x2 = os;
 	}
 	tab[kmt_first(L) + (u32)code] = kmt_pack(x0, x1, x2);
 }

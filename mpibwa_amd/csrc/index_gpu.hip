@@ -337,6 +337,13 @@ extern "C" int mi355x_index_build_gpu(int device, const uint8_t *pac, int64_t l_
 	// bucket on the first kb symbols so that a bucket stays below ~384 M suffixes
 	int kb = 1;
 	while (kb < 4 && (N >> (2 * kb)) > (384ull << 20)) ++kb;
+	// MPIBWA_IDX_KB=1..4 forces it (tests: 2, 3 and 4 are otherwise taken beyond 1.5 G symbols only).  bucket_count_kernel's loc[256] and
+	// its threadIdx.x < 4^kb guard hold up to kb = 4 with the 256 threads of its launch, and no further.
+	if (const char *e = getenv("MPIBWA_IDX_KB")) {
+		const int v = atoi(e);
+		if (v < 1 || v > 4) die("MPIBWA_IDX_KB=%s: the round-0 buckets take 1 to 4 leading symbols", e);
+		kb = v;
+	}
 	const u32 n_buckets = 1u << (2 * kb);
 	Buf d_counts(256 * 8);
 	HIP_OK(hipMemset(d_counts.p, 0, 256 * 8));
