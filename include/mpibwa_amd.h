@@ -637,6 +637,30 @@ void    mi355x_bgzf_inflate_dev_counts(uint64_t out[4]);
  * goes to its contig AND there), last "unmapped" (RNAME '*').  out_text[d] (malloc, NULL when empty) / out_len[d] for
  * d < n_seqs + 1 + (discordant != 0).  Returns the number of records or -(offset of a malformed line) - 1. */
 int64_t mi355x_route_by_chr(const char *sam, size_t len, const bntseq_t *bns, int discordant, char **out_text, size_t *out_len);
+/* BAM output: a chunk's SAM text as BAM records — int32 block_size, the 32-byte core (refID, pos, l_read_name, mapq, bin,
+ * n_cigar_op, flag, l_seq, next_refID, next_pos, tlen), QNAME NUL, CIGAR words, SEQ nibbles, QUAL - 33, tags in the smallest type that
+ * holds them (csrc/bam_util.h states the layout once for host and device).  All return a size, 0 with nothing written when cap is too
+ * small, or -(offset of the first malformed line) - 1: fewer than 11 fields, an RNAME / RNEXT that bns does not have, a non-digit in a
+ * number, QUAL of another length than SEQ, a last line without '\n', a value no BAM record holds.
+ * mi355x_bam_header: "BAM\1", l_text, the SAM header text, n_ref and bns's contigs (name, length).  Host only.
+ * mi355x_bam_bound: room for the records of sam_len bytes of SAM text.
+ * mi355x_sam_to_bam: the records back to back, on the rank's host threads; *n_records (may be NULL) = their number.
+ * mi355x_bam_compress: the records as BGZF blocks at zlib's level, a block holds as many whole records as fit 0xff00 bytes; out of
+ * mi355x_bgzf_bound(mi355x_bam_bound(len)) bytes always suffices.
+ * mi355x_sam_to_bam_dev / mi355x_bam_compress_dev: the same records from the device encoder (csrc/bam_kernel.hip), the latter through
+ * the device deflate of mi355x_bgzf_compress_dev, with that call's contract: needs a usable MI355X, no CPU fallback for a missing GPU;
+ * re-entrant, also beside mem_process_seqs calls in flight; the same text gives the same bytes on every call; mi355x_finalize() gives
+ * the buffers back.  A piece of text with a line the device declines ('B' tags, floats with an exponent, records above 0xff00 bytes) is
+ * encoded by the host encoder: the records are the same bytes.
+ * mi355x_bam_dev_counts: records, records encoded by the host because the device declined their piece, SAM bytes, BAM bytes, blocks,
+ * compressed bytes — since load, all callers. */
+int64_t mi355x_bam_header(const char *text, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap);
+int64_t mi355x_bam_bound(size_t sam_len);
+int64_t mi355x_sam_to_bam(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap, int64_t *n_records);
+int64_t mi355x_sam_to_bam_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap, int64_t *n_records);
+int64_t mi355x_bam_compress(const char *sam, size_t len, const bntseq_t *bns, int level, uint8_t *out, size_t cap);
+int64_t mi355x_bam_compress_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap);
+void    mi355x_bam_dev_counts(uint64_t out[6]);
 
 #ifdef __cplusplus
 }

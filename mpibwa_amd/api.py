@@ -109,6 +109,13 @@ def load_library(build_if_missing=True):
     sig("mi355x_bgzf_inflate", C.c_int64, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t])
     sig("mi355x_bgzf_inflate_dev", C.c_int64, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t])
     sig("mi355x_bgzf_inflate_dev_counts", None, [P(C.c_uint64)])
+    sig("mi355x_bam_header", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_void_p, C.c_size_t])
+    sig("mi355x_bam_bound", C.c_int64, [C.c_size_t])
+    sig("mi355x_sam_to_bam", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_void_p, C.c_size_t, P(C.c_int64)])
+    sig("mi355x_sam_to_bam_dev", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_void_p, C.c_size_t, P(C.c_int64)])
+    sig("mi355x_bam_compress", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_int, C.c_void_p, C.c_size_t])
+    sig("mi355x_bam_compress_dev", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_void_p, C.c_size_t])
+    sig("mi355x_bam_dev_counts", None, [P(C.c_uint64)])
     sig("mi355x_route_by_chr", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_int, P(C.c_void_p), P(C.c_size_t)])
     sig("bwa_set_rg", C.c_void_p, [C.c_char_p])
     sig("bwa_insert_header", C.c_void_p, [C.c_char_p, C.c_void_p])

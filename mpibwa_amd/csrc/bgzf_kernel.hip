@@ -140,10 +140,11 @@ __device__ void build_code(BzShared &S, uint32_t *freq, int n, int max_len, uint
 
 __global__ __launch_bounds__(64) void bgzf_deflate_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ cut, int n_blocks,
                                                           uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes, uint16_t *__restrict__ tokens,
-                                                          unsigned long long *__restrict__ meta)
+                                                          unsigned long long *__restrict__ meta, const uint32_t *__restrict__ n_dev)
 {
 	__shared__ BzShared S;
 	const int lane = (int)threadIdx.x;
+	if (n_dev) n_blocks = (int)*n_dev;   // (the BAM stage: the cuts were made on the device, bam_kernel.hip)
 	uint16_t *const tok = tokens + (size_t)blockIdx.x * BGZF_DEV_INPUT;
 	if (lane < 32) {
 		uint32_t p = 0x40000000u;   // x^1
@@ -325,10 +326,12 @@ __global__ __launch_bounds__(64) void bgzf_deflate_kernel(const uint8_t *__restr
 
 // block b's bytes from its slot to their place in the packed stream: behind the blocks before it
 __global__ __launch_bounds__(256) void bgzf_gather_kernel(const uint8_t *__restrict__ slots, const uint32_t *__restrict__ sizes, int n_blocks,
-                                                          uint8_t *__restrict__ out, unsigned long long *__restrict__ meta)
+                                                          uint8_t *__restrict__ out, unsigned long long *__restrict__ meta, const uint32_t *__restrict__ n_dev)
 {
 	__shared__ unsigned long long off;
 	const int b = (int)blockIdx.x;
+	if (n_dev) n_blocks = (int)*n_dev;
+	if (b >= n_blocks) return;
 	if (threadIdx.x == 0) off = 0;
 	__syncthreads();
 	unsigned long long mine = 0;
@@ -345,18 +348,20 @@ __global__ __launch_bounds__(256) void bgzf_gather_kernel(const uint8_t *__restr
 } // namespace
 
 void launch_bgzf_deflate(void *stream, const uint8_t *d_text, const uint32_t *d_cut, int n_blocks, uint8_t *d_slots, uint32_t *d_sizes,
-                         uint16_t *d_tokens, int grid, unsigned long long *d_meta)
+                         uint16_t *d_tokens, int grid, unsigned long long *d_meta, const uint32_t *d_n_blocks)
 {
 	if (n_blocks <= 0) return;
 	if (grid > n_blocks) grid = n_blocks;
-	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, d_text, d_cut, n_blocks, d_slots, d_sizes, d_tokens, d_meta);
+	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, d_text, d_cut, n_blocks, d_slots, d_sizes, d_tokens, d_meta,
+	                   d_n_blocks);
 	HIP_OK(hipGetLastError());
 }
 
-void launch_bgzf_gather(void *stream, const uint8_t *d_slots, const uint32_t *d_sizes, int n_blocks, uint8_t *d_out, unsigned long long *d_meta)
+void launch_bgzf_gather(void *stream, const uint8_t *d_slots, const uint32_t *d_sizes, int n_blocks, uint8_t *d_out, unsigned long long *d_meta,
+                        const uint32_t *d_n_blocks)
 {
 	if (n_blocks <= 0) return;
-	hipLaunchKernelGGL(bgzf_gather_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, d_slots, d_sizes, n_blocks, d_out, d_meta);
+	hipLaunchKernelGGL(bgzf_gather_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, d_slots, d_sizes, n_blocks, d_out, d_meta, d_n_blocks);
 	HIP_OK(hipGetLastError());
 }
 

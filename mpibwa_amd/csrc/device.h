@@ -573,12 +573,47 @@ void launch_seed_enum(void *stream, int n_reads, int cap, const uint64_t *d_intv
 #define BGZF_DEV_INPUT 0xff00     // text per block (sampost.cpp: BGZF_INPUT)
 // block b = d_text[d_cut[b] .. d_cut[b + 1]) (1 .. BGZF_DEV_INPUT bytes; d_text has 16 bytes of slack behind the last block) into the 64-KiB
 // slot d_slots + b * 65536 as one complete BGZF block of d_sizes[b] bytes; d_meta[1] += the blocks written stored.  `grid` workgroups of
-// one wavefront, each with BGZF_DEV_INPUT 16-bit words of d_tokens.
+// one wavefront, each with BGZF_DEV_INPUT 16-bit words of d_tokens.  With d_n_blocks the number of blocks is read on the device (at most
+// n_blocks, which then only sizes the launch): the BAM stage makes its cuts there.
 void launch_bgzf_deflate(void *stream, const uint8_t *d_text, const uint32_t *d_cut, int n_blocks, uint8_t *d_slots, uint32_t *d_sizes,
-                         uint16_t *d_tokens, int grid, unsigned long long *d_meta);
+                         uint16_t *d_tokens, int grid, unsigned long long *d_meta, const uint32_t *d_n_blocks = nullptr);
 // the slots closed up into d_out; d_meta[0] = the bytes
-void launch_bgzf_gather(void *stream, const uint8_t *d_slots, const uint32_t *d_sizes, int n_blocks, uint8_t *d_out, unsigned long long *d_meta);
+void launch_bgzf_gather(void *stream, const uint8_t *d_slots, const uint32_t *d_sizes, int n_blocks, uint8_t *d_out, unsigned long long *d_meta,
+                        const uint32_t *d_n_blocks = nullptr);
 void release_bgzf_contexts();     // the idle ones' buffers and streams (mi355x_finalize)
+// ---- SAM text to BAM records on the device (bam_kernel.hip, bam_stage.hip; bam_util.h) ----
+#define BAM_DEV_TEXT (24u << 20)                 // SAM text per piece
+#define BAM_DEV_LINES (BAM_DEV_TEXT / 64)        // lines per piece: a piece of shorter lines goes to the host
+#define BAM_DEV_BLOCKS 512                       // BGZF blocks per piece (bgzf_stage.hip: BZ_PIECE)
+#define BAM_DEV_BYTES (BAM_DEV_BLOCKS * BGZF_DEV_INPUT)   // BAM bytes per piece
+#define BAM_DEV_CHUNK 4096                       // text per workgroup of the line-start kernels
+struct BamDevCtl {          // one per piece, in device memory; zeroed but for err before the launch
+	uint32_t n_lines;       // of the piece
+	uint32_t n_write;       // n_lines, or 0 when the piece is the host's (an error, a declined line, too many lines, bytes or blocks)
+	uint32_t err;           // the smallest offset of a malformed line, 0xffffffff: none
+	uint32_t decline;
+	uint32_t bam_bytes;     // of the records
+	uint32_t n_blocks;      // of the cuts
+};
+struct BamDevBufs {
+	const uint8_t *text; uint32_t text_len;      // whole lines, the last byte is '\n'
+	const void *contigs;                         // bam_util.h's blob
+	uint32_t *chunk_cnt;                         // text_len / BAM_DEV_CHUNK + 2
+	uint32_t *line_start;                        // BAM_DEV_LINES + 1
+	void *plan;                                  // BAM_DEV_LINES x bam::LinePlan
+	uint32_t *group;                             // BAM_DEV_LINES / 64 + 1
+	uint32_t *rec_off;                           // BAM_DEV_LINES + 1
+	uint32_t *next;                              // BAM_DEV_LINES
+	uint8_t *bam;                                // BAM_DEV_BYTES + 16
+	uint32_t *cut;                               // BAM_DEV_BLOCKS + 1
+	BamDevCtl *ctl;
+};
+// the records of the piece into B.bam, their offsets into B.rec_off (all of it queued on the stream, nothing comes back)
+void launch_bam_encode(void *stream, const BamDevBufs &B);
+// the blocks' cuts of the records into B.cut and B.ctl->n_blocks
+void launch_bam_cuts(void *stream, const BamDevBufs &B);
+size_t bam_plan_bytes();
+void release_bam_contexts();      // the idle ones' buffers and streams (mi355x_finalize)
 // ---- BGZF blocks inflated on the device (bgzf_inflate_kernel.hip, bgzf_in_stage.hip) ----
 // block b = d_comp[d_blk_off[b] .. d_blk_off[b + 1]) (a whole BGZF block: header, deflate stream, CRC32, ISIZE; d_comp holds comp_len bytes)
 // to d_text[d_text_off[b] .. d_text_off[b + 1]) (the ISIZEs' prefix sums, below text_cap); d_status[b] = 0 or inflate_util.h's error.

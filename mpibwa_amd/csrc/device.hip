@@ -593,4 +593,5 @@ extern "C" void mi355x_finalize(void)
 	release_idle_work_buffers();   // a process that is done with this index gives the HBM of its call contexts back too
 	release_bgzf_contexts();
 	release_bgzf_in_contexts();
+	release_bam_contexts();
 }

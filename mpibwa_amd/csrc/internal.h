@@ -22,6 +22,13 @@ void bgzf_cuts(const char *text, size_t len, std::vector<size_t> &cut);
 // text_off[0 .. n] as mi355x_bgzf_scan gives them; returns the offset at which the walk stopped short of len (a header that is not one,
 // a block that the buffer cuts off), or -1 when the whole blocks end at len
 int64_t bgzf_in_plan(const uint8_t *in, size_t len, std::vector<int64_t> &blk_off, std::vector<int64_t> &text_off);
+// sampost.cpp, for both BAM paths (this host path and bam_stage.hip): the contig table of bam_util.h as one blob; the records of the
+// whole lines of sam[0 .. len) into out (16 bytes of slack behind them) with their offsets (rec_off[0 .. n], rec_off[n] = the size),
+// returns the size or -(offset of the first malformed line) - 1; and the blocks' cuts from those offsets
+namespace bam { struct ContigTable; }
+void bam_contig_blob(const bntseq_t *bns, std::vector<uint8_t> &blob);
+int64_t bam_encode_host(const char *sam, size_t len, const bam::ContigTable &tab, std::vector<uint8_t> &out, std::vector<uint64_t> *rec_off);
+void bam_cuts(const std::vector<uint64_t> &rec_off, std::vector<size_t> &cut);
 
 // ---- plain records exchanged between host stages and HIP kernels ----
 

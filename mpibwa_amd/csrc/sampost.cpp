@@ -16,9 +16,11 @@
 // and copies the tags literally.  The reference's compressed writers drop the last read of every thread's slice
 // (`end_index = ... - 1`, src/parallel_aux.c:2953-2956) — here every record is written: the decompressed stream is the SAM text.
 #include "internal.h"
+#include "bam_util.h"
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -364,6 +366,20 @@ extern "C" size_t mi355x_bgzf_bound(size_t len) { return (len / (BGZF_INPUT / 2)
 // writer packs whole reads' records, src/parallel_aux.c:3003-3017), the blocks are compressed side by side and the result does
 // not depend on the number of threads.  level: zlib's (-1 = default, as src/bgzf.c:95).  Returns the compressed size, 0 when cap is
 // too small.
+// the blocks bytes[cut[b] .. cut[b + 1]) side by side into out (n_blocks * BGZF_MAX bytes are there), closed up; returns their size
+static size_t bgzf_blocks_at(const uint8_t *bytes, const std::vector<size_t> &cut, int level, uint8_t *out)
+{
+	const size_t n_blocks = cut.size() - 1;
+	std::vector<uint32_t> clen(n_blocks);
+	// every block into its own 64-KiB slot, then the slots are closed up
+	run_parallel((int64_t)n_blocks, 16, [&](int64_t lo, int64_t hi) {
+		for (int64_t b = lo; b < hi; ++b) clen[b] = (uint32_t)bgzf_block(bytes + cut[b], cut[b + 1] - cut[b], level, out + (size_t)b * BGZF_MAX);
+	});
+	size_t w = 0;
+	for (size_t b = 0; b < n_blocks; ++b) { memmove(out + w, out + b * BGZF_MAX, clen[b]); w += clen[b]; }
+	return w;
+}
+
 extern "C" size_t mi355x_bgzf_compress(const char *text, size_t len, int level, uint8_t *out, size_t cap)
 {
 	if (level > 9 || level < 0) level = Z_DEFAULT_COMPRESSION;
@@ -371,14 +387,7 @@ extern "C" size_t mi355x_bgzf_compress(const char *text, size_t len, int level, 
 	bgzf_cuts(text, len, cut);
 	const size_t n_blocks = cut.size() - 1;
 	if (n_blocks * BGZF_MAX > cap) return 0;
-	std::vector<uint32_t> clen(n_blocks);
-	// every block into its own 64-KiB slot, then the slots are closed up
-	run_parallel((int64_t)n_blocks, 16, [&](int64_t lo, int64_t hi) {
-		for (int64_t b = lo; b < hi; ++b) clen[b] = (uint32_t)bgzf_block((const uint8_t *)text + cut[b], cut[b + 1] - cut[b], level, out + (size_t)b * BGZF_MAX);
-	});
-	size_t w = 0;
-	for (size_t b = 0; b < n_blocks; ++b) { memmove(out + w, out + b * BGZF_MAX, clen[b]); w += clen[b]; }
-	return w;
+	return bgzf_blocks_at((const uint8_t *)text, cut, level, out);
 }
 
 // the empty block that ends a BGZF file (src/mainParallel.c:1510: the 28 bytes the reference appends to its .bam)
@@ -585,4 +594,195 @@ extern "C" int64_t mi355x_route_by_chr(const char *sam, size_t len, const bntseq
 		}
 	});
 	return n_lines;
+}
+
+// ---- BAM records (bam_util.h) ----
+// The contig table of bam_util.h: the names sorted, equal names by index.
+void mbw::bam_contig_blob(const bntseq_t *bns, std::vector<uint8_t> &blob)
+{
+	const int n = bns->n_seqs;
+	std::vector<int32_t> order((size_t)n);
+	for (int i = 0; i < n; ++i) order[(size_t)i] = i;
+	std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+		const char *x = bns->anns[a].name, *y = bns->anns[b].name;
+		const int c = bam::name_cmp((const uint8_t *)x, (uint32_t)strlen(x), (const uint8_t *)y, (uint32_t)strlen(y));
+		return c ? c < 0 : a < b;
+	});
+	size_t bytes = 0;
+	for (int i = 0; i < n; ++i) bytes += strlen(bns->anns[i].name);
+	blob.assign(4 + 4 * (size_t)n + 4 * ((size_t)n + 1) + bytes, 0);
+	int32_t *w = (int32_t *)blob.data();
+	w[0] = n;
+	uint32_t *off = (uint32_t *)(w + 1 + n);
+	uint8_t *names = (uint8_t *)(off + n + 1);
+	uint32_t at = 0;
+	for (int k = 0; k < n; ++k) {
+		const char *nm = bns->anns[order[(size_t)k]].name;
+		const uint32_t l = (uint32_t)strlen(nm);
+		w[1 + k] = order[(size_t)k];
+		off[k] = at;
+		memcpy(names + at, nm, l);
+		at += l;
+	}
+	off[n] = at;
+}
+
+namespace {
+
+struct BamSeg {
+	size_t lo = 0, hi = 0;
+	std::vector<size_t> at;               // where every line starts
+	std::vector<bam::LinePlan> plan;
+	uint64_t bytes = 0, base = 0;         // of the segment's records; where they start in the stream
+	int64_t bad = -1;
+};
+
+// The size pass over the whole lines of sam[0 .. len) in segments, side by side.  Returns the records' bytes, or -(offset) - 1 of the
+// first malformed line (a last line without '\n' is one).
+int64_t bam_plan(const char *sam, size_t len, const bam::ContigTable &tab, std::vector<BamSeg> &segs, int64_t &n_records)
+{
+	constexpr size_t SEG = 4u << 20;
+	const void *last_nl = len ? memrchr(sam, '\n', len) : nullptr;
+	const size_t body = last_nl ? (size_t)((const char *)last_nl - sam) + 1 : 0;   // the whole lines
+	segs.clear();
+	for (size_t at = 0; at < body;) {
+		size_t hi = std::min(body, at + SEG);
+		if (hi < body) hi = (size_t)((const char *)memchr(sam + hi - 1, '\n', body - hi + 1) - sam) + 1;
+		BamSeg g;
+		g.lo = at; g.hi = hi;
+		segs.push_back(std::move(g));
+		at = hi;
+	}
+	run_parallel((int64_t)segs.size(), 1, [&](int64_t s0, int64_t s1) {
+		for (int64_t si = s0; si < s1; ++si) {
+			BamSeg &g = segs[(size_t)si];
+			g.at.reserve((g.hi - g.lo) / 200 + 16);
+			g.plan.reserve((g.hi - g.lo) / 200 + 16);
+			for (size_t at = g.lo; at < g.hi;) {
+				const char *nl = (const char *)memchr(sam + at, '\n', g.hi - at);
+				const size_t n = (size_t)(nl - (sam + at));
+				bam::LinePlan P;
+				if (n > 0xffffffffu || bam::plan_line((const uint8_t *)sam + at, (uint32_t)n, tab, P) != bam::BAM_OK) { g.bad = (int64_t)at; break; }
+				g.at.push_back(at);
+				g.plan.push_back(P);
+				g.bytes += P.size;
+				at += n + 1;
+			}
+		}
+	});
+	uint64_t total = 0;
+	n_records = 0;
+	for (BamSeg &g : segs) {
+		if (g.bad >= 0) return -g.bad - 1;
+		g.base = total;
+		total += g.bytes;
+		n_records += (int64_t)g.plan.size();
+	}
+	if (body < len) return -(int64_t)body - 1;
+	return (int64_t)total;
+}
+
+void bam_write(const char *sam, const std::vector<BamSeg> &segs, uint8_t *out)
+{
+	run_parallel((int64_t)segs.size(), 1, [&](int64_t s0, int64_t s1) {
+		for (int64_t si = s0; si < s1; ++si) {
+			const BamSeg &g = segs[(size_t)si];
+			uint64_t w = g.base;
+			for (size_t k = 0; k < g.plan.size(); ++k) {
+				bam::write_record((const uint8_t *)sam + g.at[k], g.plan[k], out + w);
+				w += g.plan[k].size;
+			}
+		}
+	});
+}
+
+void bam_offsets(const std::vector<BamSeg> &segs, std::vector<uint64_t> &off)
+{
+	off.clear();
+	uint64_t w = 0;
+	for (const BamSeg &g : segs)
+		for (const bam::LinePlan &P : g.plan) { off.push_back(w); w += P.size; }
+	off.push_back(w);
+}
+
+} // namespace
+
+// The cuts of both BAM paths from the records' offsets (off[0 .. n], off[n] = the stream's size): bam::last_fit's rule; a record
+// that alone is larger than a block is cut into blocks of BGZF_INPUT bytes, as bgzf_cuts cuts a line without a newline in reach.
+void mbw::bam_cuts(const std::vector<uint64_t> &off, std::vector<size_t> &cut)
+{
+	const uint32_t n = (uint32_t)(off.size() - 1);
+	cut.assign(1, 0);
+	for (uint32_t i = 0; i < n;) {
+		const uint32_t j = bam::last_fit(off.data(), n, i);
+		if (j > i) { cut.push_back((size_t)off[j]); i = j; continue; }
+		for (uint64_t at = off[i]; at < off[i + 1];) {   // the oversized record alone
+			at = std::min(off[i + 1], at + BGZF_INPUT);
+			cut.push_back((size_t)at);
+		}
+		++i;
+	}
+}
+
+int64_t mbw::bam_encode_host(const char *sam, size_t len, const bam::ContigTable &tab, std::vector<uint8_t> &out, std::vector<uint64_t> *rec_off)
+{
+	std::vector<BamSeg> segs;
+	int64_t n_rec = 0;
+	const int64_t total = bam_plan(sam, len, tab, segs, n_rec);
+	if (total < 0) return total;
+	out.resize((size_t)total + 16);   // (slack for the device deflate's dword loads)
+	bam_write(sam, segs, out.data());
+	if (rec_off) bam_offsets(segs, *rec_off);
+	return total;
+}
+
+// "BAM\1", the header text, the contigs of bns (include/mpibwa_amd.h)
+extern "C" int64_t mi355x_bam_header(const char *text, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap)
+{
+	size_t need = 4 + 4 + len + 4;
+	for (int i = 0; i < bns->n_seqs; ++i) need += 4 + strlen(bns->anns[i].name) + 1 + 4;
+	if (need > cap) return 0;
+	uint8_t *w = out;
+	memcpy(w, "BAM\1", 4); w += 4;
+	bam::put32(w, (uint32_t)len); w += 4;
+	if (len) memcpy(w, text, len);
+	w += len;
+	bam::put32(w, (uint32_t)bns->n_seqs); w += 4;
+	for (int i = 0; i < bns->n_seqs; ++i) {
+		const uint32_t l = (uint32_t)strlen(bns->anns[i].name) + 1;
+		bam::put32(w, l); w += 4;
+		memcpy(w, bns->anns[i].name, l); w += l;
+		bam::put32(w, (uint32_t)bns->anns[i].len); w += 4;
+	}
+	return (int64_t)need;
+}
+
+extern "C" int64_t mi355x_bam_bound(size_t sam_len) { return (int64_t)bam::records_bound(sam_len); }
+
+extern "C" int64_t mi355x_sam_to_bam(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap, int64_t *n_records)
+{
+	std::vector<uint8_t> blob;
+	bam_contig_blob(bns, blob);
+	std::vector<BamSeg> segs;
+	int64_t n_rec = 0;
+	const int64_t total = bam_plan(sam, len, bam::contig_table_at(blob.data()), segs, n_rec);
+	if (total < 0) return total;
+	if ((uint64_t)total > cap) return 0;
+	bam_write(sam, segs, out);
+	if (n_records) *n_records = n_rec;
+	return total;
+}
+
+extern "C" int64_t mi355x_bam_compress(const char *sam, size_t len, const bntseq_t *bns, int level, uint8_t *out, size_t cap)
+{
+	if (level > 9 || level < 0) level = Z_DEFAULT_COMPRESSION;
+	std::vector<uint8_t> blob, recs;
+	bam_contig_blob(bns, blob);
+	std::vector<uint64_t> off;
+	const int64_t total = bam_encode_host(sam, len, bam::contig_table_at(blob.data()), recs, &off);
+	if (total < 0) return total;
+	std::vector<size_t> cut;
+	bam_cuts(off, cut);
+	if ((cut.size() - 1) * BGZF_MAX > cap) return 0;
+	return (int64_t)bgzf_blocks_at(recs.data(), cut, level, out);
 }

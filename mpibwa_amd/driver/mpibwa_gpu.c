@@ -1,6 +1,6 @@
 /* mpibwa_gpu.c — a thin MPI host program around the C ABI of libmpibwa_amd.so: one rank per GPU,
  *
- *     mpiexec -n N mpibwa_gpu mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--device-inflate] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq[.gz] [R2.fastq[.gz]]
+ *     mpiexec -n N mpibwa_gpu mem [bwa mem options] [-f] [-g | -b | --bam] [--device-bgzf] [--device-inflate] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq[.gz] [R2.fastq[.gz]]
  *
  * The `mem` options are the reference's (src/mainParallel.c:291-398: -k -w -A -B -O -E -L -U -T -c -d -r -D -m -s -G -N -W -y -X -h -Q -I -R -H
  * -P -a -M -S -Y -V -5 -q -j -C -v -t -K -x -o, and its output options -f (fixmate, :395), -g (BGZF, :299), -b (BGZF + EOF block under the
@@ -34,7 +34,11 @@
  * (src/parallel_aux.c:2941-3176; every record is written — the reference drops the last read of each thread's slice), --by-chr routes the
  * records by RNAME (src/mainParallelByChromosome.c:1340-1455, :3437-3486).  --device-bgzf (with -g or -b): the chunks' blocks are made by the
  * library's deflate kernel (mi355x_bgzf_compress_dev) instead of zlib on the rank's cores — same cuts, same text inside, other bytes;
- * --level then has no effect; the header's blocks stay zlib's.
+ * --level then has no effect; the header's blocks stay zlib's.  --bam (instead of -g / -b, which keep the reference's meaning: BGZF blocks of
+ * SAM text): the file is real BAM — rank 0 writes the binary header (mi355x_bam_header: the SAM header text and the contigs) as BGZF blocks,
+ * every chunk's text becomes BAM records in BGZF blocks of whole records (mi355x_bam_compress at --level, or with --device-bgzf
+ * mi355x_bam_compress_dev: the record encoder kernels in front of the deflate kernel), the 28-byte empty block ends the file.  -f runs on
+ * the text before the encoder; under --by-chr every file, discordant and unmapped included, is a complete BAM with the header.
  *
  * Compressed input: a FASTQ file that starts with a BGZF header (what bgzip writes, and -g here) is read as BGZF, R1 and R2 each by its
  * own first bytes; anything else is plain text as before, and gzip without the 'BC' field is refused.  A compressed file IS its text:
@@ -330,7 +334,7 @@ typedef struct {
 	const mem_pestat_t *pes0;    /* -I */
 	int fixmate;                 /* -f */
 	int device_bgzf;             /* --device-bgzf: a chunk's blocks come from mi355x_bgzf_compress_dev */
-	int format, level;           /* 2 SAM text, 1 / 0 BGZF blocks (-b / -g: src/mainParallel.c:226, 298-299); zlib level (3: src/mainParallel.c:227) */
+	int format, level;           /* 2 SAM text, 1 / 0 BGZF blocks of it (-b / -g: src/mainParallel.c:226, 298-299), 3 BAM records in BGZF blocks (--bam); zlib level (3: src/mainParallel.c:227) */
 	int by_chr, n_dest;          /* --by-chr: records go to dest[0 .. n_dest) (contigs, [discordant], unmapped) instead of `out` */
 	MPI_File *dest;
 	int serialize;               /* MPI_THREAD_SERIALIZED: one thread inside MPI at a time */
@@ -399,7 +403,16 @@ static void write_text(loop_t *L, MPI_File fh, const char *text, size_t len, voi
 {
 	const char *out = text;
 	size_t n = len;
-	if (L->format != 2) {
+	if (L->format == 3) {
+		const size_t cap = mi355x_bgzf_bound((size_t)mi355x_bam_bound(len));
+		uint8_t *z = grown(zbuf, czbuf, cap);
+		const bntseq_t *bns = L->idx->bns;
+		const int64_t r = L->device_bgzf ? mi355x_bam_compress_dev(text, len, bns, z, cap) : mi355x_bam_compress(text, len, bns, L->level, z, cap);
+		if (r < 0) DIE("BAM: the SAM line at offset %lld of a chunk's text is malformed", (long long)(-r - 1));
+		if (len && !r) DIE("BAM: %zu bytes of text do not fit their buffer", len);
+		n = (size_t)r;
+		out = (const char *)z;
+	} else if (L->format != 2) {
 		const size_t cap = mi355x_bgzf_bound(len);
 		uint8_t *z = grown(zbuf, czbuf, cap);
 		n = L->device_bgzf ? mi355x_bgzf_compress_dev(text, len, z, cap) : mi355x_bgzf_compress(text, len, L->level, z, cap);
@@ -517,8 +530,11 @@ static void *chunk_worker(void *arg)
 
 static void usage(const char *prog)
 {
-	if (g_rank == 0) fprintf(stderr, "usage: mpiexec -n N %s mem [bwa mem options] [-f] [-g | -b] [--device-bgzf] [--device-inflate] [--level L] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]\n"
-	                         "  --device-bgzf   with -g or -b: compress the chunks' BGZF blocks on the GPU (one setting: --level has no effect on them)\n"
+	if (g_rank == 0) fprintf(stderr, "usage: mpiexec -n N %s mem [bwa mem options] [-f] [-g | -b | --bam] [--device-bgzf] [--device-inflate] [--level L] [--by-chr] [--ordered] [-K bases] [--in-flight chunks] [--no-prewarm] [--dry-run] -o OUT PREFIX R1.fastq [R2.fastq]\n"
+	                         "  -g | -b         the SAM text as BGZF blocks (-b: ended by the empty block, named .bam as the reference names it)\n"
+	                         "  --bam           real BAM: binary header and records in BGZF blocks; not together with -g or -b; a read with more than 65535 CIGAR\n"
+	                         "                  operations or a name above 254 bytes ends the run (no BAM record holds it)\n"
+	                         "  --device-bgzf   with -g, -b or --bam: make the chunks' BGZF blocks (with --bam the BAM records too) on the GPU (one setting: --level has no effect on them)\n"
 	                         "  --device-inflate  FASTQ files that are BGZF (bgzip) are inflated on the GPU instead of the cores; no effect on plain files\n", prog);
 }
 
@@ -530,7 +546,7 @@ int main(int argc, char **argv)
 	MPI_Comm_size(MPI_COMM_WORLD, &g_size);
 	int n_threads = 0, copy_comment = 0, dry = 0, n_workers = 6, prewarm = 1;
 	int dofixmate = 0, write_format = 2, compression_level = 3, by_chr = 0;   /* src/mainParallel.c:223-227 */
-	int ordered = 0, device_bgzf = 0, level_given = 0, want_device_inflate = 0;
+	int ordered = 0, device_bgzf = 0, level_given = 0, want_device_inflate = 0, bam = 0, gb_given = 0;
 	int scale_a = 0, set_b = 0, set_T = 0, set_U = 0, set_d = 0, set_O = 0, set_E = 0, set_L = 0, set_k = 0, set_r = 0, set_W = 0;
 	const char *mode = 0;   /* -x: a preset of the options the user did not set (src/mainParallel.c:294, 398-428) */
 	int64_t K = 0;
@@ -554,6 +570,7 @@ int main(int argc, char **argv)
 		if (!strcmp(a, "--by-chr")) { by_chr = 1; continue; }
 		if (!strcmp(a, "--ordered")) { ordered = 1; continue; }
 		if (!strcmp(a, "--device-bgzf")) { device_bgzf = 1; continue; }
+		if (!strcmp(a, "--bam")) { bam = 1; continue; }
 		if (!strcmp(a, "--device-inflate")) { want_device_inflate = 1; continue; }
 		if (!strcmp(a, "--level") && i + 1 < argc) { compression_level = atoi(argv[++i]); level_given = 1; continue; }
 		if (!strcmp(a, "--in-flight") && i + 1 < argc) { n_workers = atoi(argv[++i]); continue; }
@@ -573,8 +590,8 @@ int main(int argc, char **argv)
 			else if (c == 'j') ignore_alt = 1;
 			else if (c == 'C') copy_comment = 1;
 			else if (c == 'f') dofixmate = 1;          /* src/mainParallel.c:395 */
-			else if (c == 'b') write_format = 1;       /* :298 */
-			else if (c == 'g') write_format = 0;       /* :299 */
+			else if (c == 'b') { write_format = 1; gb_given = 1; }       /* :298 */
+			else if (c == 'g') { write_format = 0; gb_given = 1; }       /* :299 */
 			continue;
 		}
 		if (!strchr("kwABTUtcdvrDmsGNWyKXhQOELRHIox", c)) DIE("unknown or unsupported option %s", a);
@@ -670,8 +687,15 @@ int main(int argc, char **argv)
 		if (!set_U) opt->pen_unpaired *= opt->a;
 	}
 	bwa_fill_scmat(opt->a, opt->b, opt->mat);
+	if (bam && gb_given) {   /* three formats, one per run */
+		if (g_rank == 0) fprintf(stderr, "[mpibwa_gpu] --bam is a format of its own: not together with -g or -b\n");
+		usage(argv[0]);
+		MPI_Finalize();
+		return 1;
+	}
+	if (bam) write_format = 3;
 	if (device_bgzf && write_format == 2) {   /* nothing to compress */
-		if (g_rank == 0) fprintf(stderr, "[mpibwa_gpu] --device-bgzf needs -g or -b\n");
+		if (g_rank == 0) fprintf(stderr, "[mpibwa_gpu] --device-bgzf needs -g, -b or --bam\n");
 		usage(argv[0]);
 		MPI_Finalize();
 		return 1;
@@ -837,10 +861,22 @@ int main(int argc, char **argv)
 	size_t hdr_n = hdr_len;
 	uint8_t *hdr_z = 0;
 	if (write_format != 2 && g_rank == 0) {
-		const size_t cap = mi355x_bgzf_bound(hdr_len);
+		const char *plain = hdr;
+		size_t plain_n = hdr_len;
+		uint8_t *bam_hdr = 0;
+		if (write_format == 3) {   /* the binary header: magic, the text, the contigs */
+			size_t bcap = 16 + hdr_len;
+			for (int i = 0; i < idx->bns->n_seqs; ++i) bcap += 9 + strlen(idx->bns->anns[i].name);
+			bam_hdr = malloc(bcap);
+			const int64_t r = mi355x_bam_header(hdr, hdr_len, idx->bns, bam_hdr, bcap);
+			if (r <= 0) DIE("BAM: the header does not fit its buffer");
+			plain = (const char *)bam_hdr; plain_n = (size_t)r;
+		}
+		const size_t cap = mi355x_bgzf_bound(plain_n);
 		hdr_z = malloc(cap);
-		hdr_n = mi355x_bgzf_compress(hdr, hdr_len, compression_level, hdr_z, cap);
+		hdr_n = mi355x_bgzf_compress(plain, plain_n, compression_level, hdr_z, cap);
 		hdr_bytes = hdr_z;
+		free(bam_hdr);
 	}
 	if (!by_chr) {
 		if (g_rank == 0) create_with_header(out_path, hdr_bytes, hdr_n);
@@ -848,8 +884,9 @@ int main(int argc, char **argv)
 		MPI_OK(MPI_File_open(MPI_COMM_WORLD, (char *)out_path, MPI_MODE_WRONLY | MPI_MODE_APPEND, MPI_INFO_NULL, &out));
 	} else {
 		/* mpiBWAByChr (src/mainParallelByChromosome.c:983-1047): <directory of OUT>/<contig>.sam for every contig, discordant.sam for
-		 * pairs without -f, unmapped.sam; .bam / .gz with -b / -g.  The contig files start with the header; as text the other two do
-		 * not (create_sam_header_by_chr_file covers the contigs only, src/parallel_aux.c:2650-2723), compressed they do. */
+		 * pairs without -f, unmapped.sam; .bam / .gz with -b / -g, .bam with --bam.  The contig files start with the header; as text the other two do
+		 * not (create_sam_header_by_chr_file covers the contigs only, src/parallel_aux.c:2650-2723), compressed they do — with --bam they must:
+		 * a BAM without its header is not a BAM. */
 		struct stat sb;
 		char *dir = strdup(out_path);
 		if (!(stat(out_path, &sb) == 0 && S_ISDIR(sb.st_mode))) {
@@ -859,7 +896,7 @@ int main(int argc, char **argv)
 		const int disc = paired && !dofixmate;
 		n_dest = idx->bns->n_seqs + 1 + disc;
 		dest = malloc(sizeof(MPI_File) * (size_t)n_dest);
-		const char *ext = write_format == 2 ? "sam" : write_format == 1 ? "bam" : "gz";
+		const char *ext = write_format == 2 ? "sam" : write_format == 0 ? "gz" : "bam";
 		char **paths = malloc(sizeof(char *) * (size_t)n_dest);
 		for (int d = 0; d < n_dest; ++d) {
 			const char *nm = d < idx->bns->n_seqs ? idx->bns->anns[d].name : (disc && d == idx->bns->n_seqs) ? "discordant" : "unmapped";
@@ -920,7 +957,16 @@ int main(int argc, char **argv)
 			fprintf(stderr, "[mpibwa_gpu] BGZF input: device %llu blocks, %llu bytes -> %llu bytes of text; host %llu blocks, %llu bytes -> %llu bytes of text\n",
 			        all[0], all[1], all[2], all[3], all[4], all[5]);
 	}
-	if (device_bgzf) {   /* what the device path did, over all ranks */
+	if (device_bgzf && write_format == 3) {   /* what the device BAM path did, over all ranks */
+		uint64_t dc[6];
+		unsigned long long mine[6], all[6] = {0, 0, 0, 0, 0, 0};
+		mi355x_bam_dev_counts(dc);
+		for (int k = 0; k < 6; ++k) mine[k] = (unsigned long long)dc[k];
+		MPI_OK(MPI_Reduce(mine, all, 6, MPI_UNSIGNED_LONG_LONG, MPI_SUM, 0, MPI_COMM_WORLD));
+		if (g_rank == 0 && bwa_verbose >= 3)
+			fprintf(stderr, "[mpibwa_gpu] device BAM: %llu records (%llu by the host encoder), %llu bytes of SAM -> %llu bytes of BAM in %llu blocks -> %llu bytes\n",
+			        all[0], all[1], all[2], all[3], all[4], all[5]);
+	} else if (device_bgzf) {   /* what the device path did, over all ranks */
 		uint64_t dc[4];
 		unsigned long long mine[4], all[4] = {0, 0, 0, 0};
 		mi355x_bgzf_dev_counts(dc);
@@ -929,7 +975,7 @@ int main(int argc, char **argv)
 		if (g_rank == 0 && bwa_verbose >= 3)
 			fprintf(stderr, "[mpibwa_gpu] device BGZF: %llu blocks (%llu stored), %llu bytes of text -> %llu bytes\n", all[0], all[1], all[2], all[3]);
 	}
-	if (write_format == 1 && g_rank == 0) {   /* the empty block that ends the file the reference calls BAM (src/mainParallel.c:1508-1516) */
+	if ((write_format == 1 || write_format == 3) && g_rank == 0) {   /* the empty block that ends a BAM, and the file the reference calls BAM (src/mainParallel.c:1508-1516) */
 		uint8_t eof[28];
 		MPI_Status st;
 		mi355x_bgzf_eof(eof);
