@@ -661,6 +661,37 @@ int64_t mi355x_sam_to_bam_dev(const char *sam, size_t len, const bntseq_t *bns, 
 int64_t mi355x_bam_compress(const char *sam, size_t len, const bntseq_t *bns, int level, uint8_t *out, size_t cap);
 int64_t mi355x_bam_compress_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, size_t cap);
 void    mi355x_bam_dev_counts(uint64_t out[6]);
+/* Coordinate-sorted BAM: a complete BAM file in memory (BGZF blocks, with or without the empty end block) to a complete
+ * BAM file in samtools' coordinate order — refID (-1 behind every contig), pos + 1, the reverse-strand bit, ties in input order; the
+ * @HD line of the header text says SO:coordinate (csrc/bam_sort_util.h states the hop, the validation, the key and the header rule once
+ * for host and device).  The header goes out in BGZF blocks of its own, the records in blocks of whole records of at most 0xff00 bytes
+ * (a larger record alone, cut into such blocks), then the 28-byte empty block.
+ * mi355x_bam_sort_bound: the bytes out needs, from the blocks' ISIZEs; -(offset) - 1 for a file whose blocks do not scan.
+ * mi355x_bam_sort: on the rank's host threads (MPIBWA_SAMPOST_THREADS), zlib at `level`.  Returns the size written; 0 with nothing
+ * written when cap is below mi355x_bam_sort_bound(bam, len); -(offset) - 1 for input that is not a BAM file or fails validation, where
+ * the offset is an INPUT FILE offset for a bad BGZF block (a header that is none, a block the file cuts off, a failed inflate, CRC or
+ * ISIZE) and an offset into the INFLATED STREAM for a bad header (the magic: 0) or record (block_size < 32, a record that runs past the
+ * end, refID < -1 or >= n_ref, pos < -1).  Bad blocks are reported before bad records.
+ * mi355x_bam_sort_dev: the same from the device — inflate, record walk, radix sort, record gather and deflate kernels: the same return
+ * codes, the same record stream and cuts (every block inflates to the bytes of the host path's block of the same number), the device
+ * deflate's one setting, the same bytes on every call.  Needs a usable MI355X, no CPU fallback for a missing GPU; re-entrant (one sort
+ * holds the device's sort buffers at a time, other callers wait), also beside mem_process_seqs calls in flight; mi355x_finalize() gives
+ * the buffers back.  INT64_MIN with nothing written: the file does not fit the device's free memory (the inflated stream, 40 bytes a
+ * record and about 0.4 GB of fixed buffers, less a margin of 256 MiB; MPIBWA_BAM_SORT_MAX_BYTES=<bytes> caps what is admitted).
+ * mi355x_bam_sort_dev_counts: calls, records, calls whose record walk the host did (a foreign writer's blocks: records that span
+ * blocks), inflated bytes, input blocks, output blocks, compressed bytes out, calls refused for memory — since load, all callers.
+ * A file of 2^31 - 2 records or more is refused in the same way (the sort's indices are 32-bit).
+ * mi355x_bam_sort_dev_refused_need: the bytes of device memory, the margin included, that the last refused call needed (0: none).
+ * mi355x_bam_sort_dev_stage_ms: for tools/bench_bam_sort.py — the last finished call's wall ms of inflate, walk, sort, emit and the
+ * whole call, the record gather kernels' summed device ms and the bytes they moved, 0.  With MPIBWA_BAM_SORT_GATHER_ALONE set (a
+ * measurement aid, slower) a call drains its other stream before every gather launch, so that those device ms are of a kernel that
+ * has the device to itself. */
+int64_t mi355x_bam_sort_bound(const uint8_t *bam, size_t len);
+int64_t mi355x_bam_sort(const uint8_t *bam, size_t len, int level, uint8_t *out, size_t cap);
+int64_t mi355x_bam_sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap);
+void    mi355x_bam_sort_dev_counts(uint64_t out[8]);
+void    mi355x_bam_sort_dev_stage_ms(double out[8]);
+uint64_t mi355x_bam_sort_dev_refused_need(void);
 
 #ifdef __cplusplus
 }

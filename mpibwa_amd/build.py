@@ -61,6 +61,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
     build_driver(force=force, verbose=verbose)
     build_idx_tool(force=force, verbose=verbose)
+    build_sort_tool(force=force, verbose=verbose)
     return OUT
 
 
@@ -69,6 +70,20 @@ def build_idx_tool(force=False, verbose=False):
     --build for the files themselves.  Plain C on include/mpibwa_amd.h, no MPI."""
     src = os.path.join(HERE, "driver", "mpibwa_idx.c")
     exe = os.path.join(HERE, "mpibwa_idx")
+    if force or _stale(exe, [src, OUT, os.path.join(HERE, "..", "include", "mpibwa_amd.h")]):
+        cmd = ["gcc", "-O2", "-std=gnu99", "-Wall", "-I", os.path.join(HERE, "..", "include"), src, "-o", exe, "-L", HERE, "-lmpibwa_amd",
+               "-Wl,-rpath,/usr/lib/x86_64-linux-gnu:$ORIGIN", "-Wl,-rpath-link,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+    return exe
+
+
+def build_sort_tool(force=False, verbose=False):
+    """mpibwa_amd/mpibwa_sort: a finished BAM file to coordinate order (driver/mpibwa_sort.c), the counterpart of the
+    reference's companion mpiSORT.  Plain C on include/mpibwa_amd.h, no MPI; built the way mpibwa_idx is."""
+    src = os.path.join(HERE, "driver", "mpibwa_sort.c")
+    exe = os.path.join(HERE, "mpibwa_sort")
     if force or _stale(exe, [src, OUT, os.path.join(HERE, "..", "include", "mpibwa_amd.h")]):
         cmd = ["gcc", "-O2", "-std=gnu99", "-Wall", "-I", os.path.join(HERE, "..", "include"), src, "-o", exe, "-L", HERE, "-lmpibwa_amd",
                "-Wl,-rpath,/usr/lib/x86_64-linux-gnu:$ORIGIN", "-Wl,-rpath-link,/opt/rocm/lib"]

@@ -1,0 +1,384 @@
+// bam_sort_stage.hip — mi355x_bam_sort_dev: a finished BAM file to coordinate order on the device, with the record stream, the cuts and
+// the return codes of mi355x_bam_sort (bam_sort.cpp).  DESIGN §8.5.
+//
+// The stages of a call, all queued on the call's two streams:
+//   inflate   the file's blocks go up in groups of BS_GROUP (two groups in flight), bgzf_inflate_kernel writes every group to its place in
+//             ONE resident buffer of the whole inflated stream (launch_bgzf_inflate's offsets are 32-bit: a group is placed by pointer);
+//             the host inflates only the leading blocks, to parse the header;
+//   walk      a lane per block counts and validates its chain, a scan, a second pass writes offset, size and key (bam_sort_kernel.hip).
+//             A stream whose blocks do not all end on a record boundary is a foreign writer's: the host then inflates on the cores,
+//             hops once and uploads offsets, sizes and keys — the same bytes come out, the counts say who walked;
+//   sort      hipCUB's stable radix sort of (key, index) over the key's bits, the sorted sizes, their exclusive sum;
+//   emit      the sorted sizes come back (4 bytes a record), the host makes bam_cuts' cuts and groups them into pieces of at most
+//             BAM_DEV_BLOCKS blocks; per piece, alternating the streams: the record gather kernel, bgzf_deflate_kernel, bgzf_gather_kernel,
+//             and only compressed bytes come back.  The header's blocks are pieces like the others, their bytes come from the host.
+// The sorted stream is never materialised: device memory is the inflated stream, 40 bytes a record and the two piece contexts.
+//
+// One sort holds the buffers at a time (a mutex); they only grow, so a second call of the same size allocates nothing.  Before it
+// allocates, a call compares what it needs with what hipMemGetInfo reports free (plus what the buffers already hold), less BS_MARGIN for
+// the other calls' contexts that may grow meanwhile; MPIBWA_BAM_SORT_MAX_BYTES caps the admitted bytes (the tests' way to a refusal).
+// The records' arrays can only be sized after the count pass, so there are two such checks; a refusal returns INT64_MIN and has written
+// nothing to out.
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
+#include "hip_util.h"
+#include "device.h"
+#include "bam_sort_util.h"
+
+namespace mbw {
+namespace {
+
+constexpr int BS_GROUP = 512;                                    // blocks per inflate launch
+constexpr size_t BS_GROUP_BYTES = (size_t)BS_GROUP * 0x10000;    // their compressed bytes at their largest
+constexpr size_t BS_SLOT_BYTES = 0x10000, BS_SLACK = 16;
+constexpr size_t BS_MARGIN = 256u << 20;
+constexpr size_t BS_REC_BYTES = 40;                              // offset 8, size 4, key 8 (later the place in the sorted stream), key' 8, index 4, index' 4, sorted size 4
+
+struct SortCtx {
+	bool ready = false;
+	hipStream_t st[2] = {nullptr, nullptr};
+	hipEvent_t ev[2] = {nullptr, nullptr}, ev_g[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+	// of one size whatever the file
+	DevBuf d_comp[2], d_goff[2], d_piece[2], d_cut[2], d_slots[2], d_sizes[2], d_out[2], d_meta[2], d_tokens[2], d_flag;
+	PinBuf h_comp[2], h_goff[2], h_cut[2], h_out[2], h_meta[2], h_flag;
+	// grow with the file
+	DevBuf d_u, d_text_off, d_status, d_cnt, d_first, d_off, d_size, d_key, d_key2, d_idx, d_idx2, d_ssize, d_tmp;
+	PinBuf h_status, h_ssize;
+	std::vector<DevBuf *> all()
+	{
+		std::vector<DevBuf *> v = {&d_flag, &d_u, &d_text_off, &d_status, &d_cnt, &d_first, &d_off, &d_size, &d_key, &d_key2, &d_idx, &d_idx2, &d_ssize, &d_tmp};
+		for (int s = 0; s < 2; ++s)
+			for (DevBuf *b : {&d_comp[s], &d_goff[s], &d_piece[s], &d_cut[s], &d_slots[s], &d_sizes[s], &d_out[s], &d_meta[s], &d_tokens[s]}) v.push_back(b);
+		return v;
+	}
+	static size_t fixed_bytes()
+	{
+		return 2 * (BS_GROUP_BYTES + sizeof(uint32_t) * 2 * (BS_GROUP + 1) + (BAM_DEV_BYTES + BS_SLACK) + sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1) +
+		            2 * BAM_DEV_BLOCKS * BS_SLOT_BYTES + sizeof(uint32_t) * BAM_DEV_BLOCKS + 16 + sizeof(uint16_t) * (size_t)BAM_DEV_BYTES) + 16;
+	}
+	size_t held()
+	{
+		size_t n = 0;
+		for (DevBuf *b : all()) n += b->cap;
+		return n;
+	}
+	void init()
+	{
+		d_flag.ensure(16); h_flag.ensure(16);
+		for (int s = 0; s < 2; ++s) {
+			HIP_OK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
+			HIP_OK(hipEventCreateWithFlags(&ev[s], hipEventDisableTiming));
+			for (int k = 0; k < 2; ++k) HIP_OK(hipEventCreate(&ev_g[s][k]));
+			d_comp[s].ensure(BS_GROUP_BYTES);
+			d_goff[s].ensure(sizeof(uint32_t) * 2 * (BS_GROUP + 1));
+			d_piece[s].ensure(BAM_DEV_BYTES + BS_SLACK);
+			d_cut[s].ensure(sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1));
+			d_slots[s].ensure(BAM_DEV_BLOCKS * BS_SLOT_BYTES);
+			d_sizes[s].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS);
+			d_out[s].ensure(BAM_DEV_BLOCKS * BS_SLOT_BYTES);
+			d_meta[s].ensure(2 * sizeof(unsigned long long));
+			d_tokens[s].ensure(sizeof(uint16_t) * (size_t)BAM_DEV_BYTES);
+			h_comp[s].ensure(BS_GROUP_BYTES);
+			h_goff[s].ensure(sizeof(uint32_t) * 2 * (BS_GROUP + 1));
+			h_cut[s].ensure(sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1));
+			h_out[s].ensure(BAM_DEV_BLOCKS * BS_SLOT_BYTES);
+			h_meta[s].ensure(2 * sizeof(unsigned long long));
+		}
+		ready = true;
+	}
+	void release()
+	{
+		for (DevBuf *b : all()) b->release();
+		for (PinBuf *b : {&h_flag, &h_status, &h_ssize}) b->release();
+		for (int s = 0; s < 2; ++s) {
+			for (PinBuf *b : {&h_comp[s], &h_goff[s], &h_cut[s], &h_out[s], &h_meta[s]}) b->release();
+			if (st[s]) (void)hipStreamDestroy(st[s]);
+			if (ev[s]) (void)hipEventDestroy(ev[s]);
+			for (int k = 0; k < 2; ++k) { if (ev_g[s][k]) (void)hipEventDestroy(ev_g[s][k]); ev_g[s][k] = nullptr; }
+			st[s] = nullptr; ev[s] = nullptr;
+		}
+		ready = false;
+	}
+};
+
+SortCtx g_bs;
+std::mutex g_bs_mu;                       // one sort at a time holds g_bs
+std::atomic<uint64_t> g_bs_counts[8];     // calls, records, calls whose walk the host did, inflated bytes, input blocks, output blocks, compressed bytes out, calls refused for memory
+std::mutex g_bs_ms_mu;
+double g_bs_ms[8];                        // the last call: inflate, walk, sort, emit, all of it (wall ms); the gather kernels (event ms), their bytes; 0
+std::atomic<uint64_t> g_bs_refused_need;  // the bytes (margin included) that the last refused call needed
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// does a call that needs `need` bytes of device memory in g_bs's buffers fit?  (a refusal is counted and its need kept for the caller's message)
+bool admitted(size_t need)
+{
+	size_t free_b = 0, total_b = 0;
+	HIP_OK(hipMemGetInfo(&free_b, &total_b));
+	size_t have = free_b + g_bs.held();
+	if (const char *e = getenv("MPIBWA_BAM_SORT_MAX_BYTES")) have = std::min<size_t>(have, (size_t)strtoull(e, nullptr, 10));
+	if (need + BS_MARGIN <= have) return true;
+	g_bs_counts[7] += 1;
+	g_bs_refused_need = need + BS_MARGIN;
+	return false;
+}
+
+// what the host path answers for a file whose header the leading blocks do not give: the first bad block (mi355x_bgzf_inflate over the
+// whole file also reports what bgzf_in_plan found: a header that is none, a block that the file cuts off), else the header's code
+int64_t header_code(const uint8_t *bam, size_t len, uint64_t u)
+{
+	std::vector<uint8_t> text((size_t)u + 1);
+	const int64_t r = mi355x_bgzf_inflate(bam, len, (char *)text.data(), (size_t)u + 1);
+	if (r < 0) return r;
+	bsort::Header h;
+	const int64_t hs = bsort::parse_header(text.data(), u, h);
+	return hs < 0 ? hs : -(int64_t)u - 1;
+}
+
+int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
+{
+	const auto t_all = std::chrono::steady_clock::now();
+	std::vector<int64_t> blk, txt;
+	const int64_t bad = bgzf_in_plan(bam, len, blk, txt);
+	const size_t n_blk = blk.size() - 1;
+	const uint64_t u = (uint64_t)txt[n_blk];
+	if (n_blk >= (size_t)INT_MAX) die("mi355x_bam_sort_dev: %zu blocks", n_blk);
+
+	// the header, from as many leading blocks as it takes (1, 2, 4, ...)
+	bsort::Header h;
+	std::vector<uint8_t> lead;
+	for (size_t k = 1;; k *= 2) {
+		const size_t nb = std::min(k, n_blk);
+		lead.resize((size_t)txt[nb] + 1);
+		const int64_t r = nb ? mi355x_bgzf_inflate(bam, (size_t)blk[nb], (char *)lead.data(), lead.size()) : 0;
+		if (r < 0) return r;   // (the first bad block of the file: every block before it is among these)
+		const int64_t hs = bsort::parse_header(lead.data(), (uint64_t)txt[nb], h);
+		if (hs == 0) break;
+		if (hs < 0 || nb == n_blk) return header_code(bam, len, u);
+	}
+	std::vector<uint8_t> head;
+	bsort::coordinate_header(lead.data(), h, head);
+	const uint64_t hn = head.size();
+	std::vector<uint8_t>().swap(lead);
+
+	use_device();
+	std::lock_guard<std::mutex> hold(g_bs_mu);
+	SortCtx &C = g_bs;
+	const size_t need1 = SortCtx::fixed_bytes() + (size_t)u + bsort::BAM_SORT_SLACK + (n_blk + 1) * (sizeof(uint64_t) + 3 * sizeof(uint32_t));
+	if (!admitted(need1)) return INT64_MIN;
+	if (!C.ready) C.init();
+	C.d_u.ensure((size_t)u + bsort::BAM_SORT_SLACK);
+	C.d_text_off.ensure((n_blk + 1) * sizeof(uint64_t));
+	C.d_status.ensure((n_blk + 1) * sizeof(uint32_t));
+	C.d_cnt.ensure((n_blk + 1) * sizeof(uint32_t));
+	C.d_first.ensure((n_blk + 1) * sizeof(uint32_t));
+	C.h_status.ensure((n_blk + 1) * sizeof(uint32_t));
+	uint8_t *const d_u = (uint8_t *)C.d_u.p;
+
+	// ---- inflate ----
+	auto t0 = std::chrono::steady_clock::now();
+	HIP_OK(hipMemsetAsync(d_u + u, 0, bsort::BAM_SORT_SLACK, C.st[0]));
+	const size_t n_groups = (n_blk + BS_GROUP - 1) / BS_GROUP;
+	for (size_t g = 0; g < n_groups; ++g) {
+		const int s = (int)(g & 1);
+		const size_t b0 = g * BS_GROUP, b1 = std::min(n_blk, b0 + BS_GROUP);
+		const int nb = (int)(b1 - b0);
+		const size_t cbytes = (size_t)(blk[b1] - blk[b0]), tbytes = (size_t)(txt[b1] - txt[b0]);   // (each at most BS_GROUP_BYTES)
+		if (g >= 2) HIP_OK(hipEventSynchronize(C.ev[s]));   // the group before last on this stream has left the page-locked buffers
+		memcpy(C.h_comp[s].p, bam + blk[b0], cbytes);
+		uint32_t *ho = (uint32_t *)C.h_goff[s].p, *hb = ho, *ht = ho + (BS_GROUP + 1);
+		for (int k = 0; k <= nb; ++k) { hb[k] = (uint32_t)(blk[b0 + k] - blk[b0]); ht[k] = (uint32_t)(txt[b0 + k] - txt[b0]); }
+		uint32_t *dof = (uint32_t *)C.d_goff[s].p;
+		HIP_OK(hipMemcpyAsync(C.d_comp[s].p, C.h_comp[s].p, cbytes, hipMemcpyHostToDevice, C.st[s]));
+		HIP_OK(hipMemcpyAsync(dof, ho, sizeof(uint32_t) * 2 * (BS_GROUP + 1), hipMemcpyHostToDevice, C.st[s]));
+		HIP_OK(hipEventRecord(C.ev[s], C.st[s]));
+		launch_bgzf_inflate(C.st[s], (const uint8_t *)C.d_comp[s].p, (uint32_t)cbytes, dof, dof + (BS_GROUP + 1), nb, d_u + txt[b0], (uint32_t)tbytes,
+		                    (uint32_t *)C.d_status.p + b0);
+	}
+	HIP_OK(hipStreamSynchronize(C.st[1]));
+	if (n_blk) HIP_OK(hipMemcpyAsync(C.h_status.p, C.d_status.p, n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
+	HIP_OK(hipStreamSynchronize(C.st[0]));
+	for (size_t b = 0; b < n_blk; ++b)
+		if (((const uint32_t *)C.h_status.p)[b]) return -blk[b] - 1;
+	if (bad >= 0) return -bad - 1;
+	const double ms_inflate = ms_since(t0);
+
+	// ---- walk ----
+	t0 = std::chrono::steady_clock::now();
+	HIP_OK(hipMemcpyAsync(C.d_text_off.p, txt.data(), (n_blk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
+	HIP_OK(hipMemsetAsync(C.d_flag.p, 0, 16, C.st[0]));
+	C.d_tmp.ensure(bam_sort_temp_bytes(0, (int)n_blk));
+	launch_bam_sort_count(C.st[0], d_u, (const uint64_t *)C.d_text_off.p, (int)n_blk, h.end, h.n_ref, (uint32_t *)C.d_cnt.p, (uint32_t *)C.d_flag.p);
+	launch_bam_sort_scan(C.st[0], C.d_tmp.p, C.d_tmp.cap, (const uint32_t *)C.d_cnt.p, (uint32_t *)C.d_first.p, (int)n_blk);
+	uint32_t *hf = (uint32_t *)C.h_flag.p;
+	HIP_OK(hipMemcpyAsync(hf, C.d_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
+	HIP_OK(hipMemcpyAsync(hf + 1, (const uint32_t *)C.d_first.p + n_blk, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
+	HIP_OK(hipStreamSynchronize(C.st[0]));
+	const bool host_walk = hf[0] != 0;
+	size_t n_rec = hf[1];
+	std::vector<uint64_t> h_off, h_key;
+	std::vector<uint32_t> h_size;
+	if (host_walk) {   // a foreign writer's blocks, or a malformed record: the host's hop decides which
+		std::vector<uint8_t> text((size_t)u + 1);
+		const int64_t r = mi355x_bgzf_inflate(bam, len, (char *)text.data(), (size_t)u + 1);
+		if (r < 0) return r;
+		const int64_t ws = bam_sort_walk(text.data(), h.end, u, h.n_ref, h_off, h_size, h_key);
+		if (ws < 0) return ws;
+		n_rec = h_off.size();
+	}
+	if ((uint64_t)cap < bam_sort_bound_of(u)) return 0;
+	if (n_rec >= (size_t)INT_MAX - 1) {   // beyond the sort's 32-bit indices: refused like a file that does not fit
+		g_bs_counts[7] += 1;
+		g_bs_refused_need = need1 + BS_REC_BYTES * (n_rec + 1) + BS_MARGIN;
+		return INT64_MIN;
+	}
+	const size_t tmp_bytes = bam_sort_temp_bytes((uint32_t)n_rec, (int)n_blk);
+	if (!admitted(need1 + BS_REC_BYTES * (n_rec + 1) + tmp_bytes)) return INT64_MIN;
+	C.d_off.ensure((n_rec + 1) * sizeof(uint64_t));
+	C.d_size.ensure((n_rec + 1) * sizeof(uint32_t));
+	C.d_key.ensure((n_rec + 1) * sizeof(uint64_t));
+	C.d_key2.ensure((n_rec + 1) * sizeof(uint64_t));
+	C.d_idx.ensure((n_rec + 1) * sizeof(uint32_t));
+	C.d_idx2.ensure((n_rec + 1) * sizeof(uint32_t));
+	C.d_ssize.ensure((n_rec + 1) * sizeof(uint32_t));
+	C.h_ssize.ensure((n_rec + 1) * sizeof(uint32_t));
+	C.d_tmp.ensure(tmp_bytes);
+	if (host_walk) {
+		if (n_rec) {
+			HIP_OK(hipMemcpyAsync(C.d_off.p, h_off.data(), n_rec * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
+			HIP_OK(hipMemcpyAsync(C.d_size.p, h_size.data(), n_rec * sizeof(uint32_t), hipMemcpyHostToDevice, C.st[0]));
+			HIP_OK(hipMemcpyAsync(C.d_key.p, h_key.data(), n_rec * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
+		}
+	} else
+		launch_bam_sort_write(C.st[0], d_u, (const uint64_t *)C.d_text_off.p, (int)n_blk, h.end, h.n_ref, (const uint32_t *)C.d_first.p, (uint64_t *)C.d_off.p,
+		                      (uint32_t *)C.d_size.p, (uint64_t *)C.d_key.p);
+	HIP_OK(hipStreamSynchronize(C.st[0]));
+	const double ms_walk = ms_since(t0);
+
+	// ---- sort ----
+	t0 = std::chrono::steady_clock::now();
+	uint64_t *const d_dst = (uint64_t *)C.d_key.p;   // the keys' buffer again, once they are sorted
+	launch_bam_sort_order(C.st[0], C.d_tmp.p, C.d_tmp.cap, (uint32_t)n_rec, (int)bsort::key_bits(h.n_ref), (const uint64_t *)C.d_key.p, (uint64_t *)C.d_key2.p,
+	                      (uint32_t *)C.d_idx.p, (uint32_t *)C.d_idx2.p, (const uint32_t *)C.d_size.p, (uint32_t *)C.d_ssize.p, d_dst);
+	HIP_OK(hipMemcpyAsync(C.h_ssize.p, C.d_ssize.p, (n_rec + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
+	HIP_OK(hipStreamSynchronize(C.st[0]));
+	const double ms_sort = ms_since(t0);
+
+	// ---- emit ----
+	t0 = std::chrono::steady_clock::now();
+	std::vector<uint64_t> rec_off(n_rec + 1);
+	rec_off[0] = 0;
+	for (size_t i = 0; i < n_rec; ++i) rec_off[i + 1] = rec_off[i] + ((const uint32_t *)C.h_ssize.p)[i];
+	if (rec_off[n_rec] != u - h.end) die("mi355x_bam_sort_dev: the sorted records have %llu bytes, the stream %llu", (unsigned long long)rec_off[n_rec], (unsigned long long)(u - h.end));
+	std::vector<size_t> cut;
+	bam_sort_cuts(hn, rec_off, cut);
+	const size_t n_out = cut.size() - 1, n_pieces = (n_out + BAM_DEV_BLOCKS - 1) / BAM_DEV_BLOCKS;
+	double gather_ms = 0;
+	uint64_t gather_bytes = 0, piece_gather[2] = {0, 0};
+	const bool gather_alone = getenv("MPIBWA_BAM_SORT_GATHER_ALONE") != nullptr;   // tools/bench_bam_sort.py: no other kernel beside a timed gather
+	auto start = [&](size_t k) {   // everything of a piece, queued on the piece's stream
+		const int s = (int)(k & 1);
+		const size_t b0 = k * BAM_DEV_BLOCKS, b1 = std::min(n_out, b0 + BAM_DEV_BLOCKS);
+		const int nb = (int)(b1 - b0);
+		const uint64_t p0 = cut[b0], p1 = cut[b1];   // (p1 - p0 <= BAM_DEV_BYTES: a block has at most 0xff00 bytes)
+		uint8_t *const d_piece = (uint8_t *)C.d_piece[s].p;
+		if (p0 < hn)   // (pageable memory: the copy is staged by the runtime and has left head when the call returns)
+			HIP_OK(hipMemcpyAsync(d_piece, head.data() + p0, (size_t)(std::min(p1, hn) - p0), hipMemcpyHostToDevice, C.st[s]));
+		piece_gather[s] = 0;
+		if (p1 > hn) {
+			const uint64_t lo = std::max(p0, hn) - hn, hi = p1 - hn;   // of the sorted records
+			const size_t r0 = (size_t)(std::upper_bound(rec_off.begin(), rec_off.end(), lo) - rec_off.begin()) - 1;
+			const size_t r1 = (size_t)(std::lower_bound(rec_off.begin(), rec_off.end(), hi) - rec_off.begin());
+			if (gather_alone) HIP_OK(hipStreamSynchronize(C.st[s ^ 1]));
+			HIP_OK(hipEventRecord(C.ev_g[s][0], C.st[s]));
+			launch_bam_sort_gather(C.st[s], d_u, (const uint64_t *)C.d_off.p, (const uint32_t *)C.d_idx2.p, d_dst, (uint32_t)n_rec, (uint32_t)r0, (uint32_t)r1, lo, hi,
+			                       d_piece + (std::max(p0, hn) - p0));
+			HIP_OK(hipEventRecord(C.ev_g[s][1], C.st[s]));
+			piece_gather[s] = hi - lo;
+		}
+		uint32_t *hcut = (uint32_t *)C.h_cut[s].p;
+		for (int j = 0; j <= nb; ++j) hcut[j] = (uint32_t)(cut[b0 + j] - p0);
+		HIP_OK(hipMemcpyAsync(C.d_cut[s].p, hcut, sizeof(uint32_t) * (nb + 1), hipMemcpyHostToDevice, C.st[s]));
+		HIP_OK(hipMemsetAsync(C.d_meta[s].p, 0, 2 * sizeof(unsigned long long), C.st[s]));
+		launch_bgzf_deflate(C.st[s], d_piece, (const uint32_t *)C.d_cut[s].p, nb, (uint8_t *)C.d_slots[s].p, (uint32_t *)C.d_sizes[s].p, (uint16_t *)C.d_tokens[s].p,
+		                    BAM_DEV_BLOCKS, (unsigned long long *)C.d_meta[s].p);
+		launch_bgzf_gather(C.st[s], (const uint8_t *)C.d_slots[s].p, (const uint32_t *)C.d_sizes[s].p, nb, (uint8_t *)C.d_out[s].p, (unsigned long long *)C.d_meta[s].p);
+		HIP_OK(hipMemcpyAsync(C.h_meta[s].p, C.d_meta[s].p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.st[s]));
+	};
+	size_t w = 0;
+	if (n_pieces) start(0);
+	for (size_t k = 0; k < n_pieces; ++k) {
+		const int s = (int)(k & 1);
+		if (k + 1 < n_pieces) start(k + 1);   // (the other stream: its kernels run beside this piece's way back)
+		HIP_OK(hipStreamSynchronize(C.st[s]));
+		if (piece_gather[s]) {
+			float ms = 0;
+			HIP_OK(hipEventElapsedTime(&ms, C.ev_g[s][0], C.ev_g[s][1]));
+			gather_ms += ms; gather_bytes += piece_gather[s];
+		}
+		const size_t zbytes = (size_t)((const unsigned long long *)C.h_meta[s].p)[0];
+		if (w + zbytes + 28 > cap) die("mi355x_bam_sort_dev: %zu bytes of blocks above the bound %zu", w + zbytes + 28, (size_t)bam_sort_bound_of(u));
+		HIP_OK(hipMemcpyAsync(C.h_out[s].p, C.d_out[s].p, zbytes, hipMemcpyDeviceToHost, C.st[s]));
+		HIP_OK(hipStreamSynchronize(C.st[s]));
+		memcpy(out + w, C.h_out[s].p, zbytes);
+		w += zbytes;
+	}
+	w += mi355x_bgzf_eof(out + w);
+	const double ms_emit = ms_since(t0);
+
+	g_bs_counts[1] += n_rec; g_bs_counts[2] += host_walk ? 1 : 0; g_bs_counts[3] += u; g_bs_counts[4] += n_blk; g_bs_counts[5] += n_out + 1; g_bs_counts[6] += w;
+	{
+		std::lock_guard<std::mutex> lk(g_bs_ms_mu);
+		const double v[8] = {ms_inflate, ms_walk, ms_sort, ms_emit, ms_since(t_all), gather_ms, (double)gather_bytes, 0};
+		memcpy(g_bs_ms, v, sizeof v);
+	}
+	return (int64_t)w;
+}
+
+} // namespace
+
+void release_bam_sort_contexts()
+{
+	if (!g_bs_mu.try_lock()) return;   // a sort is running: its buffers stay
+	if (g_bs.ready) g_bs.release();
+	g_bs_mu.unlock();
+}
+
+} // namespace mbw
+
+using namespace mbw;
+
+// mi355x_bam_sort on the device: the same record stream, cuts and return codes; the device deflate's one setting (include/mpibwa_amd.h)
+extern "C" int64_t mi355x_bam_sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
+{
+	g_bs_counts[0] += 1;
+	return sort_dev(bam, len, out, cap);
+}
+
+extern "C" void mi355x_bam_sort_dev_counts(uint64_t out[8])
+{
+	for (int k = 0; k < 8; ++k) out[k] = g_bs_counts[k].load();
+}
+
+// the last finished call's stages, for tools/bench_bam_sort.py: wall ms of inflate, walk, sort, emit and the whole call; the record gather
+// kernels' summed event ms and the bytes they moved; 0
+extern "C" void mi355x_bam_sort_dev_stage_ms(double out[8])
+{
+	std::lock_guard<std::mutex> lk(g_bs_ms_mu);
+	memcpy(out, g_bs_ms, sizeof g_bs_ms);
+}
+
+// the bytes of device memory, margin included, that the last call refused for memory needed (0: none was refused)
+extern "C" uint64_t mi355x_bam_sort_dev_refused_need(void)
+{
+	return g_bs_refused_need.load();
+}

@@ -621,6 +621,24 @@ void release_bam_contexts();      // the idle ones' buffers and streams (mi355x_
 void launch_bgzf_inflate(void *stream, const uint8_t *d_comp, uint32_t comp_len, const uint32_t *d_blk_off, const uint32_t *d_text_off, int n_blocks,
                          uint8_t *d_text, uint32_t text_cap, uint32_t *d_status);
 void release_bgzf_in_contexts();  // the idle ones' buffers and streams (mi355x_finalize)
+// ---- a BAM file to coordinate order on the device (bam_sort_kernel.hip, bam_sort_stage.hip; bam_sort_util.h) ----
+// d_u: the whole inflated stream (bsort::BAM_SORT_SLACK bytes behind its end), block b = d_u[d_text_off[b] .. d_text_off[b + 1]), records
+// from h_end on.  count: d_cnt[0 .. n_blk] = the records of every block's own chain (d_cnt[n_blk] = 0), *d_bad = 1 when a chain meets a
+// malformed record or does not end at its block's end (the caller zeroes it).  scan: d_first[0 .. n_blk] = their exclusive sums.
+// write: record i's offset in d_u, size and packed key.  All of it queued on the stream.
+void launch_bam_sort_count(void *stream, const uint8_t *d_u, const uint64_t *d_text_off, int n_blk, uint64_t h_end, int32_t n_ref, uint32_t *d_cnt, uint32_t *d_bad);
+void launch_bam_sort_scan(void *stream, void *d_tmp, size_t tmp_bytes, const uint32_t *d_cnt, uint32_t *d_first, int n_blk);
+void launch_bam_sort_write(void *stream, const uint8_t *d_u, const uint64_t *d_text_off, int n_blk, uint64_t h_end, int32_t n_ref, const uint32_t *d_first,
+                           uint64_t *d_off, uint32_t *d_size, uint64_t *d_key);
+size_t bam_sort_temp_bytes(uint32_t n_rec, int n_blk);   // hipCUB's room for the scans and the sort
+// the order: d_idx2[i] = the record that sorts to place i (stable, over the key's `bits` lowest bits), d_ssize[i] = its size (d_ssize[n_rec] = 0),
+// d_dst[0 .. n_rec] = the exclusive sums of those: where it stands in the sorted stream.  d_dst may be d_key: the keys are done with by then.
+void launch_bam_sort_order(void *stream, void *d_tmp, size_t tmp_bytes, uint32_t n_rec, int bits, const uint64_t *d_key, uint64_t *d_key2, uint32_t *d_idx,
+                           uint32_t *d_idx2, const uint32_t *d_size, uint32_t *d_ssize, uint64_t *d_dst);
+// sorted records r0 .. r1 - 1, as far as they lie in [lo, hi) of the sorted stream, back to back into d_piece[0 .. hi - lo)
+void launch_bam_sort_gather(void *stream, const uint8_t *d_u, const uint64_t *d_off, const uint32_t *d_idx, const uint64_t *d_dst, uint32_t n_rec, uint32_t r0,
+                            uint32_t r1, uint64_t lo, uint64_t hi, uint8_t *d_piece);
+void release_bam_sort_contexts(); // the sort buffers and streams, unless a sort is running (mi355x_finalize)
 // the calling thread on the device of the resident index, or, before any index, on device 0 after the checks of mi355x_init
 void use_device();
 

@@ -594,4 +594,5 @@ extern "C" void mi355x_finalize(void)
 	release_bgzf_contexts();
 	release_bgzf_in_contexts();
 	release_bam_contexts();
+	release_bam_sort_contexts();
 }

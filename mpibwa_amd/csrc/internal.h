@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstddef>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -29,6 +30,19 @@ namespace bam { struct ContigTable; }
 void bam_contig_blob(const bntseq_t *bns, std::vector<uint8_t> &blob);
 int64_t bam_encode_host(const char *sam, size_t len, const bam::ContigTable &tab, std::vector<uint8_t> &out, std::vector<uint64_t> *rec_off);
 void bam_cuts(const std::vector<uint64_t> &rec_off, std::vector<size_t> &cut);
+// sampost.cpp, for bam_sort.cpp: f(lo, hi) over [0, n) in grains on the rank's host threads (MPIBWA_SAMPOST_THREADS); the blocks
+// bytes[cut[b] .. cut[b + 1]) by zlib at `level` side by side into out (64 KiB per block are there), closed up; returns their size
+void host_parallel(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)> &f);
+size_t bgzf_blocks_at(const uint8_t *bytes, const std::vector<size_t> &cut, int level, uint8_t *out);
+// bam_sort.cpp, for both sort paths (it and bam_sort_stage.hip): the records of the inflated stream s[h_end .. u) by one hop from record
+// to record: their offsets, sizes (block_size's four bytes included) and packed keys (bam_sort_util.h); returns 0 or -(offset of the
+// first malformed record) - 1
+int64_t bam_sort_walk(const uint8_t *s, uint64_t h_end, uint64_t u, int32_t n_ref, std::vector<uint64_t> &off, std::vector<uint32_t> &size,
+                      std::vector<uint64_t> &key);
+// room for the sorted file of an inflated stream of u bytes (mi355x_bam_sort_bound); the cuts of the output stream: a new header of hn
+// bytes in blocks of its own, then bam_cuts of the sorted records (rec_off[0 .. n] from 0) behind it
+uint64_t bam_sort_bound_of(uint64_t u);
+void bam_sort_cuts(uint64_t hn, const std::vector<uint64_t> &rec_off, std::vector<size_t> &cut);
 
 // ---- plain records exchanged between host stages and HIP kernels ----
 

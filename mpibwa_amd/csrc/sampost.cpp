@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <string_view>
 #include <thread>
@@ -342,6 +343,9 @@ extern "C" int64_t mi355x_fixmate(bseq1_t *seqs, int n, const bntseq_t *bns)
 	return bad.load() >= 0 ? -bad.load() - 1 : lines.load();
 }
 
+// run_parallel for the host files beside this one (bam_sort.cpp): the same threads, the same MPIBWA_SAMPOST_THREADS
+void mbw::host_parallel(int64_t n, int64_t grain, const std::function<void(int64_t, int64_t)> &f) { run_parallel(n, grain, f); }
+
 // ---- BGZF ----
 // The cuts of both BGZF paths (this file's and the device's, bgzf_stage.hip): at most BGZF_INPUT bytes per block, cut back to the last
 // record end where there is one.
@@ -367,7 +371,7 @@ extern "C" size_t mi355x_bgzf_bound(size_t len) { return (len / (BGZF_INPUT / 2)
 // not depend on the number of threads.  level: zlib's (-1 = default, as src/bgzf.c:95).  Returns the compressed size, 0 when cap is
 // too small.
 // the blocks bytes[cut[b] .. cut[b + 1]) side by side into out (n_blocks * BGZF_MAX bytes are there), closed up; returns their size
-static size_t bgzf_blocks_at(const uint8_t *bytes, const std::vector<size_t> &cut, int level, uint8_t *out)
+size_t mbw::bgzf_blocks_at(const uint8_t *bytes, const std::vector<size_t> &cut, int level, uint8_t *out)
 {
 	const size_t n_blocks = cut.size() - 1;
 	std::vector<uint32_t> clen(n_blocks);

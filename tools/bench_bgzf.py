@@ -26,9 +26,9 @@ sys.path.insert(0, ROOT)
 from mpibwa_amd import api  # noqa: E402
 
 
-def chunk_text(mb):
+def chunk_text(mb, seed=9):
     import numpy as np
-    rng = np.random.default_rng(9)
+    rng = np.random.default_rng(seed)
     with gzip.open(os.path.join(ROOT, "tests", "golden", "mpibwa_examples", "HCC1187C_R1_10K.fastq.gz"), "rb") as g:
         lines = g.read().split(b"\n")
     reads = [(lines[k][1:].split()[0], lines[k + 1], lines[k + 3]) for k in range(0, len(lines) - 3, 4)]
