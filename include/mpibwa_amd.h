@@ -328,6 +328,16 @@ int mi355x_pair_maxreg(void);
 int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], int64_t n_processed, int n_pairs,
                       const void *regs, const int *n_regs, int max_len, uint8_t *status, void *desc, void *req);
 
+/* mi355x_pair_batch for a test that looks at everything the kernel writes.  pair_ok: n_pairs bytes, 0 = a pair the host did not pass
+ * (the kernel gives it code 2 and marks its requests and descriptors as the host's, nothing else).  status has room for
+ * mi355x_pair_stage_room(n_pairs) pairs — n_pairs rounded up to 64, and 64 more — desc and req for twice as many records; every byte of
+ * the three is `fill` before the launch and all of it comes back, so what lies behind pair n_pairs - 1 must still hold the pattern.
+ * Returns 0, or -1 as mi355x_pair_batch. */
+int mi355x_pair_stage_room(int n_pairs);
+int mi355x_pair_stage_batch(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], int64_t n_processed, int n_pairs,
+                            const void *regs, const int *n_regs, const uint8_t *pair_ok, int max_len, int fill, uint8_t *status,
+                            void *desc, void *req);
+
 /* The same decisions for the pairs pair_simple_kernel leaves because they need mate rescue, carry more than mi355x_pair_maxreg() regions
  * on an end, or have one end without a region: pair_wave_kernel, a pair per wavefront, up to mi355x_pair_wave_maxreg() regions per end.
  * The entry runs the pipeline's sequence: the host lists the rescue windows (src/bwamem_pair.c:131-150), the mate-rescue kernel aligns

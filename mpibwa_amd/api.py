@@ -22,7 +22,7 @@ EXPORTS = [
     "mi355x_sam_batch", "mi355x_sam_arena_bytes", "mi355x_se_batch", "mi355x_sam_se_batch", "mi355x_seed_batch", "mi355x_pair_wave_batch", "mi355x_pair_wave_maxreg",
     "mi355x_pair_wave_xa_batch", "mi355x_pair_wave_xa_cap", "mi355x_dedup_batch", "mi355x_dedup_maxreg", "mi355x_se_wave_batch",
     "mi355x_se_lines_cap", "mi355x_se_wave_lines_batch", "mi355x_sam_se_lines_batch", "mi355x_sam_lines_row", "mi355x_sam_lines_sa_stage",
-    "mi355x_pair_wave_lines_batch", "mi355x_sam_pe_lines_batch",
+    "mi355x_pair_wave_lines_batch", "mi355x_sam_pe_lines_batch", "mi355x_pair_stage_batch", "mi355x_pair_stage_room",
 ]
 
 
@@ -137,6 +137,9 @@ def load_library(build_if_missing=True):
     sig("mi355x_device_memory", C.c_int, [P(C.c_size_t), P(C.c_size_t)])
     sig("mi355x_buffer_growths", C.c_ulonglong, [])
     sig("mi355x_pair_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("mi355x_pair_stage_room", C.c_int, [C.c_int])
+    sig("mi355x_pair_stage_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p])
     sig("mi355x_pair_wave_maxreg", C.c_int, [])
     sig("mi355x_pair_wave_batch", C.c_int, [P(abi.mem_opt_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 8)
     sig("mi355x_pair_wave_xa_cap", C.c_int, [])
@@ -427,6 +430,27 @@ class Engine:
                                         max_len, status.ctypes.data, desc.ctypes.data, req.ctypes.data)
         if rc != 0:
             raise RuntimeError("mi355x_pair_batch: the kernel cannot use these insert-size statistics")
+        return status, desc, req
+
+    def pairs_stage(self, opt, pes, regs, n_regs, pair_ok=None, max_len=150, n_processed=0, fill=0xA5):
+        """pairs() through mi355x_pair_stage_batch: pair_ok (n_pairs,) bytes, default all 1; the three arrays come back whole, with room
+        for mi355x_pair_stage_room(n_pairs) pairs and every byte `fill` before the launch.
+        -> status (room,) uint8, desc (2 room,) DESC_DT, req (2 room,) AREQ_DT"""
+        regs = np.ascontiguousarray(regs, dtype=self.REG_DT)
+        assert regs.ndim == 2 and regs.shape[1] == self.lib.mi355x_pair_maxreg()
+        n_regs = np.ascontiguousarray(n_regs, dtype=np.int32)
+        n_pairs = len(n_regs) // 2
+        assert len(n_regs) == 2 * n_pairs and regs.shape[0] == 2 * n_pairs
+        pair_ok = np.ones(n_pairs, dtype=np.uint8) if pair_ok is None else np.ascontiguousarray(pair_ok, dtype=np.uint8)
+        assert len(pair_ok) == n_pairs
+        room = int(self.lib.mi355x_pair_stage_room(n_pairs))
+        status = np.zeros(room, dtype=np.uint8)
+        desc = np.zeros(2 * room, dtype=self.DESC_DT)
+        req = np.zeros(2 * room, dtype=self.AREQ_DT)
+        rc = self.lib.mi355x_pair_stage_batch(opt, C.cast(self.bns, C.c_void_p), C.cast(pes, C.c_void_p), n_processed, n_pairs, regs.ctypes.data,
+                                              n_regs.ctypes.data, pair_ok.ctypes.data, max_len, fill, status.ctypes.data, desc.ctypes.data, req.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mi355x_pair_stage_batch: the kernel cannot use these insert-size statistics")
         return status, desc, req
 
     PW_DECIDED_XA = 16

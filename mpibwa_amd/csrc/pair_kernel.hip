@@ -6,11 +6,11 @@
 //   mem_pair              src/bwamem_pair.c:182-243   (one hit per end: one candidate pair)
 //   mem_approx_mapq_se    src/bwamem.c:952-976
 //   mem_reg2aln           src/bwamem.c:1089-1105      (the band of the final global alignment: infer_bw, :792-800)
-//   mem_sort_dedup_patch  src/bwamem.c:437-489        (up to four regions per end, as long as no two of them get as far as
+//   mem_sort_dedup_patch  src/bwamem.c:437-489        (up to PR_MAXREG = 8 regions per end, as long as no two of them get as far as
 //                                                       mem_patch_reg's global alignment, :406-435)
 //   mem_mark_primary_se   src/bwamem.c:493-569        (reads without ALT hits)
-// The shape: each end has at most four regions (typically the hit and a few 19-25 bp chance matches), none on an ALT
-// contig; mem_matesw would return without aligning for every candidate hit; mem_pair finds a pair; no end has a second
+// The shape: each end has at most PR_MAXREG = 8 regions (typically the hit and a few 19-25 bp chance matches), none on an ALT
+// contig, and the two ends give at most PR_MAXPAIR = 16 candidate pairs; mem_matesw would return without aligning for every candidate hit; mem_pair finds a pair; no end has a second
 // good primary hit (the single-end logic's case) and no secondary hit is close enough to its primary for an XA entry
 // (src/bwamem_extra.c:91-110).  The unstable sorts (ks_introsort) and the hash tie-breaks are the reference's.  That is the bulk of a chunk (three pairs in four on the bench
 // workload).  For such a pair the kernel writes what the host's COLLECT pass would have produced — the two requests for

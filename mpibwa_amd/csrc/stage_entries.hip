@@ -155,6 +155,48 @@ extern "C" int mi355x_pair_batch(const mem_opt_t *opt, const bntseq_t *bns, cons
 	return 0;
 }
 
+// The same kernel for the designed stage test (tests/test_gpu_pair_stage.py): the caller also gives the pair_ok bytes (0: a pair the
+// host did not pass), and status, desc and req come back WHOLE — room for mi355x_pair_stage_room(n_pairs) pairs (n_pairs rounded up to
+// the workgroup, and one workgroup more), every byte `fill` before the launch — so that the caller sees what the kernel wrote and
+// what it left alone, behind the last pair too.
+extern "C" int mi355x_pair_stage_room(int n_pairs) { return n_pairs <= 0 ? 0 : (n_pairs + 63) / 64 * 64 + 64; }
+extern "C" int mi355x_pair_stage_batch(const mem_opt_t *opt, const bntseq_t *bns, const mem_pestat_t pes[4], int64_t n_processed, int n_pairs,
+                                       const void *regs, const int *n_regs, const uint8_t *pair_ok, int max_len, int fill, uint8_t *status,
+                                       void *desc, void *req)
+{
+	require_any_device();
+	if (n_pairs <= 0) return 0;
+	if (max_len <= 0) die("mi355x_pair_stage_batch: max_len must be positive");
+	PairParams pp;
+	size_t n_tab = 0;
+	if (!pair_params(opt, bns->l_pac, pes, n_processed, max_len, pp, &n_tab)) return -1;
+	std::vector<double> tab(n_tab + (size_t)pp.ltab_n);
+	pair_tables(opt, pes, pp, n_tab, tab.data());
+	std::vector<int64_t> ann_off;
+	std::vector<uint8_t> ann_alt;
+	contig_table(bns, ann_off, ann_alt);
+	const size_t n = (size_t)2 * n_pairs, room = (size_t)mi355x_pair_stage_room(n_pairs);
+	const DevReg *hr = (const DevReg *)regs;
+	for (size_t i = 0; i < n; ++i)   // nothing the kernel indexes with may point outside what is uploaded
+		for (int j = 0; j < n_regs[i] && j < PR_MAXREG; ++j)
+			if (hr[i * PR_MAXREG + j].rid < 0 || hr[i * PR_MAXREG + j].rid >= bns->n_seqs) die("mi355x_pair_stage_batch: bad contig in region %d of read %zu", j, i);
+	DevArr<DevReg> d_first(n * PR_MAXREG * sizeof(DevReg), regs);
+	DevArr<int> d_nf(n * 4, n_regs);
+	DevArr<uint8_t> d_ok(n_pairs, pair_ok), d_aa(ann_alt.size(), ann_alt.data()), d_st(room);
+	DevArr<int64_t> d_ao(ann_off.size() * 8, ann_off.data());
+	DevArr<double> d_tab(tab.size() * 8, tab.data());
+	DevArr<AlnReq> d_rq(2 * room * sizeof(AlnReq));
+	DevArr<SamDesc> d_ds(2 * room * sizeof(SamDesc));
+	d_st.fill(fill); d_rq.fill(fill); d_ds.fill(fill);
+	launch_pair_simple(0, pp, n_pairs, d_first, d_nf, d_ok, d_ao, d_aa, d_tab, d_tab + n_tab, d_st, d_rq, d_ds);
+	HIP_OK(hipDeviceSynchronize());
+	HIP_OK(hipGetLastError());
+	d_st.download(status, room);
+	d_ds.download(desc, 2 * room * sizeof(SamDesc));
+	d_rq.download(req, 2 * room * sizeof(AlnReq));
+	return 0;
+}
+
 // Stage entry of pair_wave_kernel (pair_wave_kernel.hip) for parity tests.  It runs the pipeline's own sequence — the host lists the
 // mate-rescue windows with their tags (sam_pe_msw_collect_tagged), launch_msw aligns them, pair_wave_kernel replays mem_sam_pe — on
 // n_pairs pairs given by their reads (nt4 codes, off[2 n_pairs + 1]) and both ends' regions as they stand after mem_sort_dedup_patch
