@@ -14,8 +14,10 @@
 //
 // The unstable sort of mem_chain_flt is ks_introsort (src/ksort.h:176-226) statement by statement (sortutil.h: its small form for the
 // at most 9 chains of a lane's read, the full sort with its frames in LDS in chain_heavy_kernel).
-// Floating-point compares (mask_level, drop_ratio, frac_rep) are IEEE single precision in the same expression shapes as
-// the reference (no contraction, no fast-math).
+// The arithmetic both kernels share with each other and with the host path — contig lookup, test_and_merge's verdict, the weight's
+// coverage sums, the filter's two predicates and its cut, the reference window — stands once, in chainmath.h; the kernels keep their
+// maps, loops and stores.  Floating-point compares (mask_level, drop_ratio, frac_rep) are IEEE single precision in the same
+// expression shapes as the reference (no contraction, no fast-math).
 //
 // Output per read, in the slots the read's seeds already own (seed_off[r] .. seed_off[r] + n_seeds[r]): the kept chains
 // (DevChain, in mem_chain_flt's order, with the reference window of mem_chain2aln), their seeds in the order
@@ -31,6 +33,7 @@
 #include "hip_util.h"
 #include "device.h"
 #include "sortutil.h"
+#include "chainmath.h"
 
 namespace mbw {
 
@@ -89,21 +92,6 @@ struct MapArray {
 	}
 };
 
-__device__ __forceinline__ int ck_pos2rid(const i64 *__restrict__ ann_off, int n_seqs, i64 l_pac, i64 pos_f)
-{
-	if (pos_f >= l_pac) return -1;
-	int left = 0, mid = 0, right = n_seqs;
-	while (left < right) {   // src/bntseq.c:349-363
-		mid = (left + right) >> 1;
-		if (pos_f >= ann_off[mid]) {
-			if (mid == n_seqs - 1 || pos_f < ann_off[mid + 1]) break;
-			left = mid + 1;
-		} else right = mid;
-	}
-	return mid;
-}
-__device__ __forceinline__ i64 ck_depos(i64 l_pac, i64 pos) { return pos >= l_pac ? (l_pac << 1) - 1 - pos : pos; }
-
 // mem_chain + mem_chain_flt + emission for ONE read (one lane).  Returns the number of kept chains, or -1: host path.
 template <int MAXCH>
 __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainParams &P, int rd, int ns, int lq, i64 so, const int *__restrict__ l_rep,
@@ -115,6 +103,8 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 	auto S_R = [&](int k) -> i64 { return (i64)sa[so + k]; };
 	auto S_Q = [&](int k) -> int { return qbl[2 * (so + k)]; };
 	auto S_L = [&](int k) -> int { return qbl[2 * (so + k) + 1]; };
+	auto ANN_OFF = [ann_off](int i) -> int64_t { return ann_off[i]; };
+	auto GAP = [gap](int q) -> int { return gap[q]; };
 	// the seeds of chain `id` in arrival order
 	auto members = [&](int id, auto fn) {
 		for (int k = 0; k < ns; ++k)
@@ -124,7 +114,7 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 	// ---------------- mem_chain: seeds into the ordered map ----------------
 	MapArray<MAXCH> map;
 	int n_ch = 0;
-	i64 c_lo = 0, c_hi = -1;
+	int64_t c_lo = 0, c_hi = -1;
 	int c_rid = -1;
 	for (int k = 0; k < ns; ++k) {
 		const i64 rb = S_R(k);
@@ -132,44 +122,27 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 		L.cid(k) = 255;
 		int rid;
 		if (rb >= c_lo && rb + len <= c_hi && len > 0) rid = c_rid;
-		else {   // bns_intv2rid, src/bntseq.c:365-376
-			if (rb < l_pac && rb + len > l_pac) rid = -2;
-			else {
-				const int rid_b = ck_pos2rid(ann_off, n_seqs, l_pac, ck_depos(l_pac, rb));
-				const int rid_e = len > 0 ? ck_pos2rid(ann_off, n_seqs, l_pac, ck_depos(l_pac, rb + len - 1)) : rid_b;
-				rid = rid_b == rid_e ? rid_b : -1;
-			}
+		else {
+			rid = intv2rid(ANN_OFF, n_seqs, l_pac, rb, rb + len);
 			if (rid >= 0) {
-				const i64 o = ann_off[rid], l = ann_off[rid + 1] - o;
-				if (rb < l_pac) { c_lo = o; c_hi = o + l; }
-				else { c_lo = (l_pac << 1) - o - l; c_hi = (l_pac << 1) - o; }
+				strand_span(l_pac, ann_off[rid], ann_off[rid + 1] - ann_off[rid], rb >= l_pac, &c_lo, &c_hi);
 				c_rid = rid;
 			}
 		}
 		if (rid < 0) continue;   // bridges two contigs or the strand boundary
 		const int id0 = map.lower(L, rb);   // closest chain at or before the seed (kb_intervalp)
-		bool merged = false;
-		if (id0 >= 0) {   // test_and_merge
-			const int id = id0;
-			const i64 first_r = st_pos(L, id), last_r = st_last_r(L, id);
-			const int first_q = (int)L.f(F_FIRST_Q, id), last_q = (int)L.f(F_LAST_Q, id), last_len = (int)L.f(F_LAST_LEN, id);
-			const int qend = last_q + last_len;
-			const i64 rend = last_r + last_len;
-			if ((int)L.f(F_RID, id) == rid) {
-				if (qb >= first_q && qb + len <= qend && rb >= first_r && rb + len <= rend) merged = true;   // contained: dropped
-				else if (!((last_r < l_pac || first_r < l_pac) && rb >= l_pac)) {                            // never chain across strands
-					const i64 x = qb - last_q, y = rb - last_r;
-					if (y >= 0 && x - y <= P.w && y - x <= P.w && x - last_len < P.max_chain_gap && y - last_len < P.max_chain_gap) {
-						L.f(F_LAST_R_LO, id) = (uint32_t)rb; L.f(F_LAST_R_HI, id) = (uint32_t)((unsigned long long)rb >> 32);
-						L.f(F_LAST_Q, id) = (uint32_t)qb; L.f(F_LAST_LEN, id) = (uint32_t)len;
-						L.f(F_N, id) += 1;
-						L.cid(k) = (uint8_t)id;
-						merged = true;
-					}
-				}
+		int verdict = MERGE_NEW;
+		if (id0 >= 0 && (int)L.f(F_RID, id0) == rid) {   // test_and_merge
+			verdict = merge_verdict(l_pac, P.w, P.max_chain_gap, st_pos(L, id0), (int)L.f(F_FIRST_Q, id0), st_last_r(L, id0), (int)L.f(F_LAST_Q, id0),
+			                        (int)L.f(F_LAST_LEN, id0), rb, qb, len);
+			if (verdict == MERGE_APPEND) {
+				L.f(F_LAST_R_LO, id0) = (uint32_t)rb; L.f(F_LAST_R_HI, id0) = (uint32_t)((unsigned long long)rb >> 32);
+				L.f(F_LAST_Q, id0) = (uint32_t)qb; L.f(F_LAST_LEN, id0) = (uint32_t)len;
+				L.f(F_N, id0) += 1;
+				L.cid(k) = (uint8_t)id0;
 			}
 		}
-		if (merged) continue;
+		if (verdict != MERGE_NEW) continue;
 		const int id = n_ch;
 		if (id >= MAXCH) return -1;
 		// (the record first: the map compares positions through it)
@@ -188,25 +161,10 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 	for (int t = 0; t < n_ch; ++t) {
 		const int id = L.ord(t);
 		// mem_chain_weight: seed coverage of the query, of the reference, the smaller one
-		i64 end = 0;
-		int w = 0, wq;
-		members(id, [&](int k) {
-			const int qb = S_Q(k), len = S_L(k);
-			if (qb >= end) w += len;
-			else if (qb + len > end) w += (int)(qb + len - end);
-			end = end > qb + len ? end : qb + len;
-		});
-		wq = w; w = 0; end = 0;
-		members(id, [&](int k) {
-			const i64 rb = S_R(k);
-			const int len = S_L(k);
-			if (rb >= end) w += len;
-			else if (rb + len > end) w += (int)(rb + len - end);
-			end = end > rb + len ? end : rb + len;
-		});
-		w = w < wq ? w : wq;
-		w = w < 1 << 30 ? w : (1 << 30) - 1;
-		const uint32_t w29 = (uint32_t)w & 0x1fffffffu;
+		CoverSum on_query, on_ref;
+		members(id, [&](int k) { on_query.add(S_Q(k), S_L(k)); });
+		members(id, [&](int k) { on_ref.add(S_R(k), S_L(k)); });
+		const uint32_t w29 = (uint32_t)chain_weight_of(on_query.w, on_ref.w) & 0x1fffffffu;
 		L.f(F_W, id) = w29; L.f(F_KEPT, id) = 0; L.f(F_FIRSTOV, id) = 0xffffffffu;
 		if ((int)w29 < P.min_chain_weight) continue;
 		L.ord(n++) = (uint8_t)id;
@@ -228,17 +186,10 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 		int kk;
 		for (kk = 0; kk < n_kept; ++kk) {
 			const int j = L.tmp(kk);
-			const int b_max = BEG(j) > BEG(i) ? BEG(j) : BEG(i);
-			const int e_min = END(j) < END(i) ? END(j) : END(i);
-			if (e_min > b_max && (!ALT(j) || ALT(i))) {
-				const int li_ = END(i) - BEG(i), lj_ = END(j) - BEG(j);
-				const int min_l = li_ < lj_ ? li_ : lj_;
-				if ((float)(e_min - b_max) >= (float)min_l * P.mask_level && min_l < P.max_chain_gap) {
-					large_ovlp = true;
-					if (L.f(F_FIRSTOV, L.ord(j)) == 0xffffffffu) L.f(F_FIRSTOV, L.ord(j)) = (uint32_t)i;
-					const int wi = (int)L.f(F_W, L.ord(i)), wj = (int)L.f(F_W, L.ord(j));
-					if ((float)wi < (float)wj * P.drop_ratio && wj - wi >= P.min_seed_len << 1) break;
-				}
+			if (flt_large_overlap(P.mask_level, P.max_chain_gap, BEG(j), END(j), ALT(j), BEG(i), END(i), ALT(i))) {
+				large_ovlp = true;
+				if (L.f(F_FIRSTOV, L.ord(j)) == 0xffffffffu) L.f(F_FIRSTOV, L.ord(j)) = (uint32_t)i;
+				if (flt_drops(P.drop_ratio, P.min_seed_len, (int)L.f(F_W, L.ord(j)), (int)L.f(F_W, L.ord(i)))) break;
 			}
 		}
 		if (kk == n_kept) {
@@ -250,16 +201,7 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 		const uint32_t fo = L.f(F_FIRSTOV, L.ord(L.tmp(kk)));
 		if (fo != 0xffffffffu) L.f(F_KEPT, L.ord(fo)) = 1;
 	}
-	{
-		int i = 0, cnt = 0;
-		for (; i < n; ++i) {   // at most max_chain_extend chains with kept = 1 or 2 are extended
-			const uint32_t kp = L.f(F_KEPT, L.ord(i));
-			if (kp == 0 || kp == 3) continue;
-			if (++cnt >= P.max_chain_extend) break;
-		}
-		for (; i < n; ++i)
-			if (L.f(F_KEPT, L.ord(i)) < 3) L.f(F_KEPT, L.ord(i)) = 0;
-	}
+	flt_cut_extend(n, [&](int i) -> uint32_t & { return L.f(F_KEPT, L.ord(i)); }, P.max_chain_extend);
 
 	// ---------------- emit the kept chains and their seeds ----------------
 	const float frac_rep = (float)l_rep[rd] / (float)lq;
@@ -288,26 +230,15 @@ __device__ __forceinline__ int chain_read(const StoreLds<MAXCH> &L, const ChainP
 			ds.rbeg = S_R(k); ds.qbeg = S_Q(k); ds.len = S_L(k);
 			seeds[cursor + a] = ds;
 			srt[cursor + a] = (unsigned int)a;
-			// widest reference span any seed of the chain could reach (src/bwamem.c:642-658)
-			const i64 b = ds.rbeg - (ds.qbeg + gap[ds.qbeg]);
-			const int tail = lq - ds.qbeg - ds.len;
-			const i64 e = ds.rbeg + ds.len + (tail + gap[tail]);
+			int64_t b, e;
+			seed_reach(ds.rbeg, ds.qbeg, ds.len, lq, GAP, &b, &e);
 			lo = b < lo ? b : lo;
 			hi = e > hi ? e : hi;
 		}
 		DevChain d;
-		i64 fb = ann_off[rid], fe = ann_off[rid + 1];
-		if (first_r >= l_pac) { const i64 tt = fb; fb = (l_pac << 1) - fe; fe = (l_pac << 1) - tt; }
-		d.far_beg = fb; d.far_end = fe;
+		strand_span(l_pac, ann_off[rid], ann_off[rid + 1] - ann_off[rid], first_r >= l_pac, &d.far_beg, &d.far_end);
 		d.seed_beg = (int)cursor; d.n_seeds = cs; d.rid = rid; d.frac_rep = frac_rep;
-		d.rmax0 = lo > 0 ? lo : 0;
-		d.rmax1 = hi < l_pac << 1 ? hi : l_pac << 1;
-		if (d.rmax0 < l_pac && l_pac < d.rmax1) {   // never cross the strand boundary
-			if (first_r < l_pac) d.rmax1 = l_pac;
-			else d.rmax0 = l_pac;
-		}
-		d.rmax0 = d.rmax0 > fb ? d.rmax0 : fb;       // bns_fetch_seq clamps to the contig
-		d.rmax1 = d.rmax1 < fe ? d.rmax1 : fe;
+		chain_window(l_pac, lo, hi, first_r, d.far_beg, d.far_end, &d.rmax0, &d.rmax1);
 		chains[so + n_out] = d;
 		++n_out;
 		cursor += cs;
@@ -453,7 +384,9 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 	i64 *g_clo = (i64 *)(sb + (((size_t)CAP * 18 + 15) & ~(size_t)15));   // per seed: start of its contig on its strand (-1: no contig), its contig
 	int *g_rid = (int *)(g_clo + CAP);
 	const i64 l_pac = P.l_pac;
-	const int n_list = (int)(*list_n < (unsigned int)list_cap ? *list_n : (unsigned int)list_cap);
+	auto ANN_OFF = [ann_off](int i) -> int64_t { return ann_off[i]; };
+	auto GAP = [gap](int q) -> int { return gap[q]; };
+	const int n_list =(int)(*list_n < (unsigned int)list_cap ? *list_n : (unsigned int)list_cap);
 	i64 pf_last = 0, pf_shift = 0;
 	auto pf_add = [&](int what, i64 v) { if (lane == 0) atomicAdd(prof + what, (unsigned long long)v); };
 	auto pf_tick = [&](int phase) {   // the time since the last border goes to `phase`
@@ -486,15 +419,9 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 			for (int k = lane; k < ns; k += 64) {
 				const i64 rb = S_R(k);
 				const int len = S_L(k);
-				int rid;
-				if (rb < l_pac && rb + len > l_pac) rid = -2;
-				else {
-					const int rid_b = ck_pos2rid(ann_off, n_seqs, l_pac, ck_depos(l_pac, rb));
-					const int rid_e = len > 0 ? ck_pos2rid(ann_off, n_seqs, l_pac, ck_depos(l_pac, rb + len - 1)) : rid_b;
-					rid = rid_b == rid_e ? rid_b : -1;
-				}
-				i64 lo = -1;
-				if (rid >= 0) lo = rb < l_pac ? ann_off[rid] : (l_pac << 1) - ann_off[rid + 1];
+				const int rid = intv2rid(ANN_OFF, n_seqs, l_pac, rb, rb + len);
+				int64_t lo = -1, hi;
+				if (rid >= 0) strand_span(l_pac, ann_off[rid], ann_off[rid + 1] - ann_off[rid], rb >= l_pac, &lo, &hi);
 				g_rid[k] = rid; g_clo[k] = lo;
 			}
 			hv_sync();
@@ -527,22 +454,18 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 					// (a chain lies in the contig of its first seed, hence of its position: the chain found is in this seed's contig — and on its
 					// strand — exactly when its position is not before the contig's start)
 					if (first_r >= c_lo) {   // test_and_merge, src/bwamem.c:190-211
-						const i64 last_r = first_r + (i64)S.last_off[id0];
-						const int first_q = S.first_q[id0], last_q = S.last_q[id0], last_len = S.last_len[id0];
-						const int qend = last_q + last_len;
-						const i64 rend = last_r + last_len;
-						if (qb >= first_q && qb + len <= qend && rb >= first_r && rb + len <= rend) { merged = true; if (lane == 0) S.cid[k] = HV_NONE; }
-						else if (!((last_r < l_pac || first_r < l_pac) && rb >= l_pac)) {
-							const i64 x = qb - last_q, y = rb - last_r;
-							if (y >= 0 && x - y <= P.w && y - x <= P.w && x - last_len < P.max_chain_gap && y - last_len < P.max_chain_gap) {
-								if (lane == 0) {
-									S.last_off[id0] = (uint32_t)(rb - first_r); S.last_q[id0] = (uint16_t)qb; S.last_len[id0] = (uint16_t)len;
-									S.nmem[id0] += 1;
-									S.cid[k] = (uint16_t)id0;
-									S.next[S.tail[id0]] = (uint16_t)k; S.next[k] = HV_NONE; S.tail[id0] = (uint16_t)k;
-								}
-								merged = true;
+						const int verdict = merge_verdict(l_pac, P.w, P.max_chain_gap, first_r, S.first_q[id0], first_r + (i64)S.last_off[id0], S.last_q[id0],
+						                                  S.last_len[id0], rb, qb, len);
+						// (branching on the verdict first and on the lane inside, as here, costs 6 VGPRs less than the other way round)
+						if (verdict == MERGE_CONTAINED) { merged = true; if (lane == 0) S.cid[k] = HV_NONE; }
+						else if (verdict == MERGE_APPEND) {
+							if (lane == 0) {
+								S.last_off[id0] = (uint32_t)(rb - first_r); S.last_q[id0] = (uint16_t)qb; S.last_len[id0] = (uint16_t)len;
+								S.nmem[id0] += 1;
+								S.cid[k] = (uint16_t)id0;
+								S.next[S.tail[id0]] = (uint16_t)k; S.next[k] = HV_NONE; S.tail[id0] = (uint16_t)k;
 							}
+							merged = true;
 						}
 					}
 				}
@@ -601,23 +524,10 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 			int w = 0, id = 0;
 			if (tt < n_ch) {
 				id = S.ord[tt];
-				i64 end = 0;
-				int wq;
-				for (int k = S.head[id]; k != HV_NONE; k = S.next[k]) {
-					const int qb = S_Q(k), len = S_L(k);
-					if (qb >= end) w += len;
-					else if (qb + len > end) w += (int)(qb + len - end);
-					end = end > qb + len ? end : qb + len;
-				}
-				wq = w; w = 0; end = 0;
-				for (int k = S.head[id]; k != HV_NONE; k = S.next[k]) {
-					const i64 rb = S_R(k);
-					const int len = S_L(k);
-					if (rb >= end) w += len;
-					else if (rb + len > end) w += (int)(rb + len - end);
-					end = end > rb + len ? end : rb + len;
-				}
-				w = w < wq ? w : wq;
+				CoverSum on_query, on_ref;
+				for (int k = S.head[id]; k != HV_NONE; k = S.next[k]) on_query.add(S_Q(k), S_L(k));
+				for (int k = S.head[id]; k != HV_NONE; k = S.next[k]) on_ref.add(S_R(k), S_L(k));
+				w = chain_weight_of(on_query.w, on_ref.w);
 			}
 			const bool pass = tt < n_ch && w >= P.min_chain_weight && w < 65536;
 			if (__ballot(tt < n_ch && w >= 65536)) ok = 0;   // (a weight beyond the sort word: reads of more than 65 kbp never come here)
@@ -648,22 +558,16 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 		hv_sync();
 		int nk = 1;
 		for (int i = 1; i < n; ++i) {
-			const int bi = cbeg[i], ei = cend[i], li = ei - bi, wi = (int)(skey[i] >> 16), alt_i = calt[i];
+			const int bi = cbeg[i], ei = cend[i], wi = (int)(skey[i] >> 16), alt_i = calt[i];
 			bool large = false, broke = false;
 			for (int k0 = 0; k0 < nk && !broke; k0 += 64) {
 				const int kk = k0 + lane;
 				bool sig = false, brk = false;
 				if (kk < nk) {
 					const int j = kidx[kk];
-					const int bj = cbeg[j], ej = cend[j];
-					const int b_max = bj > bi ? bj : bi, e_min = ej < ei ? ej : ei;
-					if (e_min > b_max && (!calt[j] || alt_i)) {
-						const int lj = ej - bj, min_l = li < lj ? li : lj;
-						if ((float)(e_min - b_max) >= (float)min_l * P.mask_level && min_l < P.max_chain_gap) {
-							sig = true;
-							const int wj = (int)(skey[j] >> 16);
-							brk = (float)wi < (float)wj * P.drop_ratio && wj - wi >= P.min_seed_len << 1;
-						}
+					if (flt_large_overlap(P.mask_level, P.max_chain_gap, cbeg[j], cend[j], calt[j], bi, ei, alt_i)) {
+						sig = true;
+						brk = flt_drops(P.drop_ratio, P.min_seed_len, (int)(skey[j] >> 16), wi);
 					}
 				}
 				unsigned long long sm = __ballot(sig);
@@ -690,15 +594,7 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 		}
 		hv_sync();
 		if (P.max_chain_extend < n) {   // at most max_chain_extend chains with kept = 1 or 2 are extended (src/bwamem.c:372-379)
-			if (lane == 0) {
-				int i = 0, cnt = 0;
-				for (; i < n; ++i) {
-					if (ckept[i] == 0 || ckept[i] == 3) continue;
-					if (++cnt >= P.max_chain_extend) break;
-				}
-				for (; i < n; ++i)
-					if (ckept[i] < 3) ckept[i] = 0;
-			}
+			if (lane == 0) flt_cut_extend(n, [ckept](int i) -> uint8_t & { return ckept[i]; }, P.max_chain_extend);
 			hv_sync();
 		}
 		pf_tick(HV_P_PAIR);
@@ -730,27 +626,17 @@ chain_heavy_kernel(ChainParams P, const int *__restrict__ list, const unsigned i
 				for (a = 0; a < cs; ++a) {
 					const DevSeed ds = seeds[my_cur + a];
 					srt[my_cur + a] = (unsigned int)a;
-					const i64 b = ds.rbeg - (ds.qbeg + gap[ds.qbeg]);
-					const int tail = lq - ds.qbeg - ds.len;
-					const i64 e = ds.rbeg + ds.len + (tail + gap[tail]);
+					int64_t b, e;
+					seed_reach(ds.rbeg, ds.qbeg, ds.len, lq, GAP, &b, &e);
 					lo = b < lo ? b : lo;
 					hi = e > hi ? e : hi;
 				}
 				const int rid = (int)S.rid[id];
 				const i64 first_r = S_R(S.head[id]);
 				DevChain d;
-				i64 fb = ann_off[rid], fe = ann_off[rid + 1];
-				if (first_r >= l_pac) { const i64 x = fb; fb = (l_pac << 1) - fe; fe = (l_pac << 1) - x; }
-				d.far_beg = fb; d.far_end = fe;
+				strand_span(l_pac, ann_off[rid], ann_off[rid + 1] - ann_off[rid], first_r >= l_pac, &d.far_beg, &d.far_end);
 				d.seed_beg = (int)my_cur; d.n_seeds = cs; d.rid = rid; d.frac_rep = frac_rep;
-				d.rmax0 = lo > 0 ? lo : 0;
-				d.rmax1 = hi < l_pac << 1 ? hi : l_pac << 1;
-				if (d.rmax0 < l_pac && l_pac < d.rmax1) {
-					if (first_r < l_pac) d.rmax1 = l_pac;
-					else d.rmax0 = l_pac;
-				}
-				d.rmax0 = d.rmax0 > fb ? d.rmax0 : fb;
-				d.rmax1 = d.rmax1 < fe ? d.rmax1 : fe;
+				chain_window(l_pac, lo, hi, first_r, d.far_beg, d.far_end, &d.rmax0, &d.rmax1);
 				chains[so + my_out] = d;
 			}
 			cursor += __shfl(pre, 63);

@@ -2,6 +2,7 @@
 #ifndef MBW_HOST_H
 #define MBW_HOST_H
 #include "internal.h"
+#include "chainmath.h"
 #include "pairmath.h"
 #include <cmath>
 #include <cstdlib>
@@ -187,7 +188,8 @@ int  bns_pos2rid(const bntseq_t *bns, int64_t pos_f);
 int  bns_intv2rid(const bntseq_t *bns, int64_t rb, int64_t re);
 inline int64_t bns_depos(const bntseq_t *bns, int64_t pos, int *is_rev)
 {
-	return (*is_rev = (pos >= bns->l_pac)) ? (bns->l_pac << 1) - 1 - pos : pos;
+	*is_rev = pos >= bns->l_pac;
+	return depos(bns->l_pac, pos);
 }
 std::vector<uint8_t> bns_get_seq(int64_t l_pac, const uint8_t *pac, int64_t beg, int64_t end, bool *ok);
 std::vector<uint8_t> bns_fetch_seq(const bntseq_t *bns, const uint8_t *pac, int64_t *beg, int64_t mid, int64_t *end, int *rid);

@@ -10,7 +10,9 @@
 // at the same reference position) and the tree shape decides which one a
 // predecessor query meets and in which order they are traversed, so the same
 // B-tree insertion / search rules are restated here rather than substituting
-// std::map.
+// std::map.  The arithmetic this path shares with the chaining kernels (contig
+// lookup, merge verdict, weight, filter predicates, reference window) is
+// chainmath.h's.
 #include "host.h"
 #include "device.h"
 #include "sortutil.h"
@@ -28,25 +30,12 @@ namespace mbw {
 // ---------------------------------------------------------------------------
 int bns_pos2rid(const bntseq_t *bns, int64_t pos_f)
 {
-	if (pos_f >= bns->l_pac) return -1;
-	int left = 0, mid = 0, right = bns->n_seqs;
-	while (left < right) {
-		mid = (left + right) >> 1;
-		if (pos_f >= bns->anns[mid].offset) {
-			if (mid == bns->n_seqs - 1 || pos_f < bns->anns[mid + 1].offset) break;
-			left = mid + 1;
-		} else right = mid;
-	}
-	return mid;
+	return pos2rid([bns](int i) -> int64_t { return bns->anns[i].offset; }, bns->n_seqs, bns->l_pac, pos_f);
 }
 
 int bns_intv2rid(const bntseq_t *bns, int64_t rb, int64_t re)
 {
-	int is_rev;
-	if (rb < bns->l_pac && re > bns->l_pac) return -2;
-	int rid_b = bns_pos2rid(bns, bns_depos(bns, rb, &is_rev));
-	int rid_e = rb < re ? bns_pos2rid(bns, bns_depos(bns, re - 1, &is_rev)) : rid_b;
-	return rid_b == rid_e ? rid_b : -1;
+	return intv2rid([bns](int i) -> int64_t { return bns->anns[i].offset; }, bns->n_seqs, bns->l_pac, rb, re);
 }
 
 static inline int pac_base(const uint8_t *pac, int64_t l) { return pac[l >> 2] >> ((~l & 3) << 1) & 3; }
@@ -78,12 +67,8 @@ std::vector<uint8_t> bns_fetch_seq(const bntseq_t *bns, const uint8_t *pac, int6
 	if (*end < *beg) std::swap(*beg, *end);
 	assert(*beg <= mid && mid < *end);
 	*rid = bns_pos2rid(bns, bns_depos(bns, mid, &is_rev));
-	int64_t far_beg = bns->anns[*rid].offset, far_end = far_beg + bns->anns[*rid].len;
-	if (is_rev) {
-		int64_t t = far_beg;
-		far_beg = (bns->l_pac << 1) - far_end;
-		far_end = (bns->l_pac << 1) - t;
-	}
+	int64_t far_beg, far_end;
+	strand_span(bns->l_pac, bns->anns[*rid].offset, bns->anns[*rid].len, is_rev != 0, &far_beg, &far_end);
 	*beg = std::max(*beg, far_beg);
 	*end = std::min(*end, far_end);
 	bool ok;
@@ -208,35 +193,18 @@ struct BTree {
 bool test_and_merge(const mem_opt_t *opt, int64_t l_pac, HChain &c, const HSeed &p, int seed_rid)
 {
 	const HSeed &last = c.seeds.back(), &first = c.seeds.front();
-	int64_t qend = last.qbeg + last.len, rend = last.rbeg + last.len;
 	if (seed_rid != c.rid) return false;
-	if (p.qbeg >= first.qbeg && p.qbeg + p.len <= qend && p.rbeg >= first.rbeg && p.rbeg + p.len <= rend) return true;
-	if ((last.rbeg < l_pac || first.rbeg < l_pac) && p.rbeg >= l_pac) return false;   // never chain across strands
-	int64_t x = p.qbeg - last.qbeg, y = p.rbeg - last.rbeg;
-	if (y >= 0 && x - y <= opt->w && y - x <= opt->w && x - last.len < opt->max_chain_gap && y - last.len < opt->max_chain_gap) {
-		c.seeds.push_back(p);
-		return true;
-	}
-	return false;
+	const int verdict = merge_verdict(l_pac, opt->w, opt->max_chain_gap, first.rbeg, first.qbeg, last.rbeg, last.qbeg, last.len, p.rbeg, p.qbeg, p.len);
+	if (verdict == MERGE_APPEND) c.seeds.push_back(p);
+	return verdict != MERGE_NEW;
 }
 
 int chain_weight(const HChain &c)
 {
-	int64_t end = 0;
-	int w = 0, tmp;
-	for (const HSeed &s : c.seeds) {
-		if (s.qbeg >= end) w += s.len;
-		else if (s.qbeg + s.len > end) w += s.qbeg + s.len - end;
-		end = end > s.qbeg + s.len ? end : s.qbeg + s.len;
-	}
-	tmp = w; w = 0; end = 0;
-	for (const HSeed &s : c.seeds) {
-		if (s.rbeg >= end) w += s.len;
-		else if (s.rbeg + s.len > end) w += s.rbeg + s.len - end;
-		end = end > s.rbeg + s.len ? end : s.rbeg + s.len;
-	}
-	w = w < tmp ? w : tmp;
-	return w < 1 << 30 ? w : (1 << 30) - 1;
+	CoverSum on_query, on_ref;
+	for (const HSeed &s : c.seeds) on_query.add(s.qbeg, s.len);
+	for (const HSeed &s : c.seeds) on_ref.add(s.rbeg, s.len);
+	return chain_weight_of(on_query.w, on_ref.w);
 }
 
 } // namespace
@@ -270,9 +238,7 @@ void chains_from_seeds(const mem_opt_t *opt, const bntseq_t *bns, int l_query, c
 		else {
 			rid = bns_intv2rid(bns, s.rbeg, s.rbeg + s.len);
 			if (rid >= 0) {
-				const int64_t o = bns->anns[rid].offset, l = bns->anns[rid].len;
-				if (s.rbeg < bns->l_pac) { c_lo = o; c_hi = o + l; }
-				else { c_lo = (bns->l_pac << 1) - o - l; c_hi = (bns->l_pac << 1) - o; }
+				strand_span(bns->l_pac, bns->anns[rid].offset, bns->anns[rid].len, s.rbeg >= bns->l_pac, &c_lo, &c_hi);
 				c_rid = rid;
 			}
 		}
@@ -338,22 +304,16 @@ void chain_filter(const mem_opt_t *opt, ChainScratch &S, std::vector<HChain *> &
 	a[0]->kept = 3;
 	keep(0);
 	const float mask_level = opt->mask_level, drop_ratio = opt->drop_ratio;
-	const int max_chain_gap = opt->max_chain_gap, two_seeds = opt->min_seed_len << 1;
+	const int max_chain_gap = opt->max_chain_gap, min_seed_len = opt->min_seed_len;
 	for (int i = 1; i < n; ++i) {
 		bool large_ovlp = false;
-		const int bi = CHN_BEG(a[i]), ei = CHN_END(a[i]), li = ei - bi, wi = (int)a[i]->w, alt_i = a[i]->is_alt ? 1 : 0;
+		const int bi = CHN_BEG(a[i]), ei = CHN_END(a[i]), wi = (int)a[i]->w, alt_i = a[i]->is_alt ? 1 : 0;
 		int kk;
 		for (kk = 0; kk < nk; ++kk) {
-			const int b_max = kbeg[kk] > bi ? kbeg[kk] : bi;
-			const int e_min = kend[kk] < ei ? kend[kk] : ei;
-			if (e_min > b_max && (!kalt[kk] || alt_i)) {
-				const int lj = kend[kk] - kbeg[kk];
-				const int min_l = li < lj ? li : lj;
-				if (e_min - b_max >= min_l * mask_level && min_l < max_chain_gap) {
-					large_ovlp = true;
-					if (kfirst[kk] < 0) kfirst[kk] = i;
-					if (wi < kw[kk] * drop_ratio && kw[kk] - wi >= two_seeds) break;
-				}
+			if (flt_large_overlap(mask_level, max_chain_gap, kbeg[kk], kend[kk], kalt[kk], bi, ei, alt_i)) {
+				large_ovlp = true;
+				if (kfirst[kk] < 0) kfirst[kk] = i;
+				if (flt_drops(drop_ratio, min_seed_len, kw[kk], wi)) break;
 			}
 		}
 		if (kk == nk) {
@@ -365,13 +325,7 @@ void chain_filter(const mem_opt_t *opt, ChainScratch &S, std::vector<HChain *> &
 		a[kept[kk]]->first = kfirst[kk];
 		if (kfirst[kk] >= 0) a[kfirst[kk]]->kept = 1;
 	}
-	int i = 0, cnt = 0;
-	for (; i < n; ++i) {   // at most max_chain_extend chains with kept = 1 or 2 are extended
-		if (a[i]->kept == 0 || a[i]->kept == 3) continue;
-		if (++cnt >= opt->max_chain_extend) break;
-	}
-	for (; i < n; ++i)
-		if (a[i]->kept < 3) a[i]->kept = 0;
+	flt_cut_extend(n, [&a](int i) -> int & { return a[i]->kept; }, opt->max_chain_extend);
 	k = 0;
 	for (int q = 0; q < n; ++q) {
 		if (a[q]->kept == 0) continue;
@@ -432,40 +386,24 @@ void pack_chain_for_device(const bntseq_t *bns, const HChain &ch, int l_query, c
 {
 	const int cs = (int)ch.seeds.size();
 	d.n_seeds = cs; d.rid = ch.rid; d.frac_rep = ch.frac_rep;
-	d.far_beg = d.far_end = 0;
-	if (cs) {
-		int is_rev;
-		bns_depos(bns, ch.seeds[0].rbeg, &is_rev);
-		int64_t fb = bns->anns[ch.rid].offset, fe = fb + bns->anns[ch.rid].len;
-		if (is_rev) { int64_t t = fb; fb = (bns->l_pac << 1) - fe; fe = (bns->l_pac << 1) - t; }
-		d.far_beg = fb; d.far_end = fe;
-	}
+	const int64_t l_pac = bns->l_pac, first_r = cs ? ch.seeds[0].rbeg : 0;
+	d.far_beg = d.far_end = 0;   // (a chain that mem_flt_chained_seeds emptied: an empty window)
+	if (cs) strand_span(l_pac, bns->anns[ch.rid].offset, bns->anns[ch.rid].len, first_r >= l_pac, &d.far_beg, &d.far_end);
 	key.resize(cs);
 	const HSeed *hsd = ch.seeds.data();
 	for (int k = 0; k < cs; ++k) key[k] = (uint64_t)hsd[k].score << 32 | (uint32_t)k;
 	if (cs == 2) { if (key[1] < key[0]) std::swap(key[0], key[1]); }
 	else if (cs > 2) std::sort(key.begin(), key.end());
-	int64_t lo = bns->l_pac << 1, hi = 0;
+	int64_t lo = l_pac << 1, hi = 0;
 	for (int k = 0; k < cs; ++k) {
 		const HSeed &t = hsd[(uint32_t)key[k]];
 		osd[k].rbeg = t.rbeg; osd[k].qbeg = t.qbeg; osd[k].len = t.len;
-		// widest reference span any seed of the chain could reach (src/bwamem.c:642-658)
-		const int64_t b = t.rbeg - (t.qbeg + gap_h[t.qbeg]);
-		const int tail = l_query - t.qbeg - t.len;
-		const int64_t e = t.rbeg + t.len + (tail + gap_h[tail]);
+		int64_t b, e;
+		seed_reach(t.rbeg, t.qbeg, t.len, l_query, [gap_h](int q) { return gap_h[q]; }, &b, &e);
 		lo = b < lo ? b : lo;
 		hi = e > hi ? e : hi;
 	}
-	d.rmax0 = lo > 0 ? lo : 0;
-	d.rmax1 = hi < bns->l_pac << 1 ? hi : bns->l_pac << 1;
-	if (cs) {
-		if (d.rmax0 < bns->l_pac && bns->l_pac < d.rmax1) {   // never cross the strand boundary
-			if (ch.seeds[0].rbeg < bns->l_pac) d.rmax1 = bns->l_pac;
-			else d.rmax0 = bns->l_pac;
-		}
-		d.rmax0 = d.rmax0 > d.far_beg ? d.rmax0 : d.far_beg;   // bns_fetch_seq clamps to the contig
-		d.rmax1 = d.rmax1 < d.far_end ? d.rmax1 : d.far_end;
-	}
+	chain_window(l_pac, lo, hi, first_r, d.far_beg, d.far_end, &d.rmax0, &d.rmax1);
 }
 
 int host_chain_read(const mem_opt_t *opt, const bntseq_t *bns, const uint8_t *pac, int l_query, const uint8_t *query, const uint64_t *sa, const int32_t *qbl,

@@ -189,12 +189,8 @@ static bool matesw_window(const mem_opt_t *opt, const bntseq_t *bns, const mem_p
 	int rev_mid;
 	const int64_t mid = (rb + re) >> 1;
 	int rid = bns_pos2rid(bns, bns_depos(bns, mid, &rev_mid));
-	int64_t far_beg = bns->anns[rid].offset, far_end = far_beg + bns->anns[rid].len;
-	if (rev_mid) {
-		int64_t t = far_beg;
-		far_beg = (l_pac << 1) - far_end;
-		far_end = (l_pac << 1) - t;
-	}
+	int64_t far_beg, far_end;
+	strand_span(l_pac, bns->anns[rid].offset, bns->anns[rid].len, rev_mid != 0, &far_beg, &far_end);
 	rb = std::max(rb, far_beg);
 	re = std::min(re, far_end);
 	*rb_ = rb; *re_ = re;

@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+import window_model
 from oracle import pyoracle as po
 
 
@@ -136,25 +137,13 @@ class Reference:
         return got
 
     def cal_max_gap(self, qlen):   # src/bwamem.c:621-628
-        o = self.opt.contents
-        l_del = int((qlen * o.a - o.o_del) / o.e_del + 1.)
-        l_ins = int((qlen * o.a - o.o_ins) / o.e_ins + 1.)
-        return min(max(l_del, l_ins, 1), o.w << 1)
+        return window_model.cal_max_gap(self.opt.contents, qlen)
 
     def window(self, lq, chain):
         """(rmax0, rmax1 before clamping, after clamping) of mem_chain2aln (src/bwamem.c:642-661)"""
         rid, _, sd = chain
-        lo = min(rb - (qb + self.cal_max_gap(qb)) for rb, qb, ln, _ in sd)
-        hi = max(rb + ln + (lq - qb - ln) + self.cal_max_gap(lq - qb - ln) for rb, qb, ln, _ in sd)
-        a, b = max(lo, 0), min(hi, 2 * self.l_pac)
-        if a < self.l_pac < b:
-            if sd[0][0] < self.l_pac:
-                b = self.l_pac
-            else:
-                a = self.l_pac
-        off, ln = self.contigs[rid]
-        fb, fe = (off, off + ln) if sd[0][0] < self.l_pac else (2 * self.l_pac - off - ln, 2 * self.l_pac - off)
-        return (lo, hi), (max(a, fb), min(b, fe))
+        before, _, after = window_model.chain_window(self.l_pac, self.contigs, self.cal_max_gap, lq, rid, sd)
+        return before, after
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

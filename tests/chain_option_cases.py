@@ -296,6 +296,38 @@ def alt_cases(geo, seed=CASE_SEED + 1):
     return cases
 
 
+# ---- reads whose reference window is cut: every other read here lies 500 bases clear of contig ends and of the strand boundary ----
+EDGE_FAMILIES = ("first_fwd", "first_rev", "last_fwd", "last_rev", "boundary_fwd", "boundary_rev")
+EDGE_DIST = (0, 37, 90)       # bases between the read and the edge
+EDGE_EXTRA = 12               # single-seed chains elsewhere that take a read to chain_heavy_kernel<256>
+
+
+def edge_cases(geo, seed=CASE_SEED + 2):
+    """Per family and distance of EDGE_DIST two reads with ONE chain of two seeds, (10, 50) and (100, 140) on one diagonal, the read that
+    far from the first or the last base of an inner contig (on either strand) or from l_pac (on either side of it): under the default
+    options the seeds reach 95 and 96 bases beyond the read (cal_max_gap of the 100 and 101 bases before and behind them), so the window
+    is cut at the contig's edge, in the boundary families also at the strand boundary.  The second read has EDGE_EXTRA chains of one
+    seed of 25-36 bases elsewhere as well: more than 9 chains, a read of chain_heavy_kernel<256>.
+    -> [(family, case)]"""
+    rng = np.random.default_rng(seed)
+    assert geo.n_seqs >= 3
+    grid = geo.slots(400)
+    l2 = 2 * geo.l_pac
+    cases = []
+    for fam in EDGE_FAMILIES:
+        for d in EDGE_DIST:
+            k = int(rng.integers(1, geo.n_seqs - 1))
+            lo, hi = geo.offs[k], geo.offs[k + 1]
+            at = {"first_fwd": lo + d, "last_fwd": hi - LQ - d, "first_rev": l2 - lo - LQ - d, "last_rev": l2 - hi + d,
+                  "boundary_fwd": geo.l_pac - LQ - d, "boundary_rev": geo.l_pac + d}[fam]
+            chain = [(10, 50, [at + 10]), (100, 140, [at + 100])]
+            cases.append((fam, (LQ, chain)))
+            lens = rng.choice(np.arange(25, 37), EDGE_EXTRA, replace=False)
+            far = [grid[i] for i in rng.choice(len(grid), EDGE_EXTRA, replace=False)]
+            cases.append((fam, (LQ, chain + [(1 + g, 1 + g + int(lens[g]), [far[g]]) for g in range(EDGE_EXTRA)])))
+    return cases
+
+
 # ---- the reference's answer ----
 def kept_intervals(case, min_seed_len):
     """mem_collect_intv drops the intervals shorter than min_seed_len (src/bwamem.c:127): they are no seeds, for nobody"""

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import chain_option_cases as oc
+import window_model
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")
@@ -74,6 +75,34 @@ def test_host_chaining_matches_the_reference_under_the_option(ref, host, genome,
     for k, (h, w) in enumerate(zip(got, ev.want)):
         hh = [(c[0], c[5], c[6]) for c in h]
         assert hh == w, (name, k, ev.klass[k], len(ev.seedsets[k]), len(hh), len(w), [(a, b) for a, b in zip(hh, w) if a != b][:2])
+    window_model.ChainWindows(host.bns, host.opt(**oc.OPTION_SETS[name])).check(ev.lens, ev.want, got, name)
+
+
+def test_windows_clamp_at_contig_edges_and_at_the_strand_boundary(ref, host, genome):
+    """The reads of oc.edge_cases: a chain within 100 bases of a contig's first and last base and of l_pac, on both strands, in a lane's
+    launch and in chain_heavy_kernel<256>.  Its window is cut at the contig's edge on either side and on either strand, and at the strand
+    boundary from either strand (the other reads lie 500 bases clear of both: none of their windows is cut); the host chaining hands
+    out the model's windows for them."""
+    cases, ev = oc.evaluated(ref, genome["prefix"], "default", oc.edge_cases)
+    win = window_model.ChainWindows(ref.bns, ref.opt())
+    cut = {}
+    for (fam, _), lq, w, klass in zip(cases, ev.lens, ev.want, ev.klass):
+        at_edge = [(rid, seeds) for rid, _, seeds in w if any(win.clamps(lq, rid, seeds))]
+        assert len(at_edge) == 1 and len(at_edge[0][1]) == 2 and klass in ("lane16x4", "heavy256"), (fam, klass, len(w))
+        rid, seeds = at_edge[0]
+        fb, fe, r0, r1 = win.of(lq, rid, seeds)
+        contig, strand = win.clamps(lq, rid, seeds)
+        rev = seeds[0][0] >= win.l_pac
+        assert rev == fam.endswith("rev") and contig and (r0 == fb if fam.startswith("first") != rev else r1 == fe), (fam, fb, fe, r0, r1)
+        if fam.startswith("boundary"):
+            assert strand and (r0 == win.l_pac if rev else r1 == win.l_pac), (fam, r0, r1)
+        cut[fam, klass] = cut.get((fam, klass), 0) + 1
+    assert cut == {(f, k): len(oc.EDGE_DIST) for f in oc.EDGE_FAMILIES for k in ("lane16x4", "heavy256")}, cut
+    _, base = oc.evaluated(ref, genome["prefix"], "default")
+    assert not any(any(win.clamps(lq, rid, seeds)) for lq, w in zip(base.lens, base.want) for rid, _, seeds in w)
+    got = host.chains(host.opt(), ev.lens, [0] * len(ev.lens), ev.seedsets, 1)
+    assert [[(c[0], c[5], c[6]) for c in h] for h in got] == ev.want
+    win.check(ev.lens, ev.want, got, "edges")
 
 
 def test_alt_reads_nest_both_ways(genome_alt):
@@ -93,3 +122,4 @@ def test_alt_reads_nest_both_ways(genome_alt):
         got = host.chains(host.opt(**oc.OPTION_SETS[name]), ev.lens, [0] * len(ev.lens), ev.seedsets, 1)
         for k, (h, w) in enumerate(zip(got, ev.want)):
             assert [(c[0], c[5], c[6]) for c in h] == w, (name, k, ev.klass[k])
+        window_model.ChainWindows(host.bns, host.opt(**oc.OPTION_SETS[name])).check(ev.lens, ev.want, got, "alt " + name)

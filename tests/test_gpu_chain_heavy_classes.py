@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+import window_model
 from oracle import pyoracle as po
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not po.chain_inject_available(), reason="oracle/_ref/libchaininj.so not present")]
@@ -100,6 +101,8 @@ def _check(engine, lens, seedsets, want, what):
         assert d is not None, (what, k, len(sd), "declined")
         dd = [(c[0], c[5], c[6]) for c in d]
         assert dd == w, (what, k, len(sd), len(dd), len(w), [(a, b) for a, b in zip(dd, w) if a != b][:2])
+    # ... and its contig bounds and reference window those of mem_chain2aln on the reference's chain
+    window_model.ChainWindows(engine.bns, engine.opt()).check(lens, want, dev, what)
     return dev
 
 

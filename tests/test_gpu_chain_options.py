@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import chain_option_cases as oc
+import window_model
 from mpibwa_amd import abi, simulate
 from oracle import pyoracle as po
 
@@ -39,6 +40,8 @@ def _check(engine, kw, ev, what, l_rep=None):
         dd = [(c[0], c[5], c[6]) for c in d]
         assert dd == w, (what, k, ev.klass[k], len(sd), len(dd), len(w), [(a, b) for a, b in zip(dd, w) if a != b][:2])
         n_chains += len(w)
+    # ... and its contig bounds and reference window those of mem_chain2aln on the reference's chain, under this option set's gap table
+    window_model.ChainWindows(engine.bns, engine.opt(**kw)).check(ev.lens, ev.want, dev, what)
     return n_chains
 
 
@@ -82,8 +85,17 @@ def test_device_steps_aside_where_mem_flt_chained_seeds_acts(engine, ref, genome
     host = engine.chains(engine.opt(min_chain_weight=5), ev.lens, [0] * n, ev.seedsets, 1)
     for k, (h, w) in enumerate(zip(host, ev.want)):
         assert [(c[0], c[5], c[6]) for c in h] == w, ("host path", k, ev.klass[k])
+    window_model.ChainWindows(engine.bns, engine.opt(min_chain_weight=5)).check(ev.lens, ev.want, host, "host path")
     _, ev7 = oc.evaluated(ref, genome["prefix"], "weight7", kw=dict(min_chain_weight=7))
     _check(engine, dict(min_chain_weight=7), ev7, "min_chain_weight=7")
+
+
+def test_windows_cut_at_contig_edges_and_at_the_strand_boundary(engine, ref, genome):
+    """(c2) the reads of oc.edge_cases (tests/test_chain_option_cases.py shows that their windows are cut where they are meant to be), in
+    chain_kernel<16, 4> and in chain_heavy_kernel<256>"""
+    _, ev = oc.evaluated(ref, genome["prefix"], "default", oc.edge_cases)
+    assert set(ev.klass) == {"lane16x4", "heavy256"}
+    _check(engine, {}, ev, "edges")
 
 
 @pytest.mark.parametrize("name", oc.ALT_SETS)

@@ -1,8 +1,12 @@
-"""The library's host chaining (general B-tree path, host_chain.cpp: used for reads with more than 9 chains or 64 seeds and
-under MPIBWA_HOST_CHAIN=1) against the reference's own mem_chain + mem_chain_flt (src/bwamem.c:251-385) on adversarial seed
-sets; no GPU involved (mi355x_chain_batch with which = 1 is host code of the product)."""
+"""The library's host chaining (host_chain.cpp: the reads the chaining kernels decline — more than 4 096 seeds, two chains at one
+position, long enough for mem_flt_chained_seeds to act — and every read under MPIBWA_HOST_CHAIN=1) against the reference's own
+mem_chain + mem_chain_flt (src/bwamem.c:251-385) on adversarial seed sets, and the contig bounds and reference window it hands to the
+extension against the model of mem_chain2aln's lines (tests/window_model.py); no GPU involved (mi355x_chain_batch with which = 1 is
+host code of the product)."""
 import numpy as np
 import pytest
+
+import window_model
 
 from oracle import pyoracle as po
 
@@ -22,6 +26,7 @@ def test_host_chaining_matches_the_reference_mem_chain(genome):
         host = eng.chains(eng.opt(**kw), lens, [0] * len(lens), seedsets, 1)
         for h, w, sd in zip(host, want, seedsets):
             assert [(c[0], c[5], c[6]) for c in h] == w, (kw, sd)
+        window_model.ChainWindows(eng.bns, eng.opt(**kw)).check(lens, want, host, kw)
         assert sum(len(w) > 9 for w in want) > 5 and sum(len(s) > 64 for s in seedsets) > 20
 
 
@@ -42,6 +47,7 @@ def test_host_chain_filter_on_reads_of_high_copy_repeats(genome):
         host = eng.chains(eng.opt(**kw), lens, [0] * len(lens), seedsets, 1)
         for h, w, sd in zip(host, want, seedsets):
             assert [(c[0], c[5], c[6]) for c in h] == w, kw
+        window_model.ChainWindows(eng.bns, eng.opt(**kw)).check(lens, want, host, kw)
         assert max(len(sd) for sd in seedsets) > 500 and max(len(w) for w in want) >= 30   # hundreds of chains in, the cap of max_chain_extend out
 
 
@@ -65,5 +71,6 @@ def test_host_chain_sort_on_reads_that_reach_the_comb_sort(genome):
         for h, w, sd in zip(host, want, seedsets):
             assert [(c[0], c[5], c[6]) for c in h] == w, (kw, len(sd), len(w))
             n_all += len(w) == len(sd)
+        window_model.ChainWindows(eng.bns, eng.opt(**kw)).check(lens, want, host, kw)
         print(kw, "reads", len(want), "with every chain kept", n_all)
         assert n_all == (len(cases) if not kw else 0), (kw, n_all)
