@@ -702,6 +702,36 @@ int64_t mi355x_bam_sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t
 void    mi355x_bam_sort_dev_counts(uint64_t out[8]);
 void    mi355x_bam_sort_dev_stage_ms(double out[8]);
 uint64_t mi355x_bam_sort_dev_refused_need(void);
+/* BAI index of a coordinate-sorted BAM file (SAM specification §5.2): the file a variant caller, a viewer or a duplicate
+ * marker opens the BAM file through.  csrc/bam_index_util.h states once what it contains: per record refID, pos, flag, l_read_name,
+ * n_cigar_op and the CIGAR words are read (the stored bin is not); beg = max(pos, 0), end = beg + the reference bases of M, D, N, = and X
+ * (1 for flag 0x4, no CIGAR or none of these), bin = reg2bin(beg, end); a maximal run of records of one bin is a chunk, chunks of a bin
+ * are joined only where the second begins in the BGZF block in which the first ends (htslib's folding of small bins into their parents
+ * is not done), pseudo-bin 37450 holds the contig's span and its mapped and unmapped counts, the linear index has a window per 16 384
+ * positions up to the contig's last covered one, refID -1 is counted in n_no_coor.
+ * mi355x_bam_index: on the rank's host threads, for any coordinate-sorted BAM file in memory, the library's own or a foreign writer's
+ * (records that span blocks, empty blocks, with or without the empty end block).  *bai is malloc'ed (the caller frees it), *bai_len its
+ * size.  Returns the number of records, or -(offset) - 1 with nothing allocated: bad BGZF blocks first, by INPUT FILE offset; then the
+ * first record in stream order that is malformed (mi355x_bam_sort's rules), sorts before its predecessor or ends beyond 2^29, by its
+ * offset in the INFLATED STREAM.  *reason (may be NULL): 0 fine, 1 a BGZF block, 2 the header or a record, 3 not in coordinate order,
+ * 4 beyond 2^29 (BAI's limit).
+ * mi355x_bam_index_dev: the same bytes and codes from the device — the sort's inflate kernel and record walk, then the index kernels
+ * (csrc/bam_index_kernel.hip).  A file whose blocks do not end on record boundaries, or in which the device finds a malformed,
+ * out-of-order or too long record, is indexed by the host path (it decides the code).  INT64_MIN: the file does not fit, under the
+ * sort's admission rule (the inflated stream, 20 + 52 bytes a record, 40 a run, 8 a window).  Shares the sort's buffers and mutex.
+ * mi355x_bam_sort_index_dev: mi355x_bam_sort_dev and the index of what it writes in one call — out gets exactly the bytes of
+ * mi355x_bam_sort_dev, the return value and codes are the sort's, *bai is the index of out, built from the order, the cuts and the
+ * compressed block sizes the sort holds on the device.  A record beyond 2^29 fails the call with reason 4 and -(its offset in the
+ * input's inflated stream) - 1, nothing written.  *bai is set only when the return value is positive.
+ * mi355x_bam_index_dev_counts: calls of both device entry points, records, calls whose walk the host did, runs before the join, chunks
+ * written, linear windows, BAI bytes, calls refused for memory — since load, all callers.
+ * mi355x_bam_index_dev_stage_ms: for tools/bench_bam_index.py — the last finished call's wall ms of inflate, walk, the index stages,
+ * the serialisation and the whole call, the index kernels' summed device ms, 0, 0. */
+int64_t mi355x_bam_index(const uint8_t *bam, size_t len, uint8_t **bai, size_t *bai_len, int *reason);
+int64_t mi355x_bam_index_dev(const uint8_t *bam, size_t len, uint8_t **bai, size_t *bai_len, int *reason);
+int64_t mi355x_bam_sort_index_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, uint8_t **bai, size_t *bai_len, int *reason);
+void    mi355x_bam_index_dev_counts(uint64_t out[8]);
+void    mi355x_bam_index_dev_stage_ms(double out[8]);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,11 @@ def load_library(build_if_missing=True):
     sig("mi355x_bam_sort_dev_counts", None, [P(C.c_uint64)])
     sig("mi355x_bam_sort_dev_stage_ms", None, [P(C.c_double)])
     sig("mi355x_bam_sort_dev_refused_need", C.c_uint64, [])
+    sig("mi355x_bam_index", C.c_int64, [C.c_char_p, C.c_size_t, P(C.c_void_p), P(C.c_size_t), P(C.c_int)])
+    sig("mi355x_bam_index_dev", C.c_int64, [C.c_char_p, C.c_size_t, P(C.c_void_p), P(C.c_size_t), P(C.c_int)])
+    sig("mi355x_bam_sort_index_dev", C.c_int64, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, P(C.c_void_p), P(C.c_size_t), P(C.c_int)])
+    sig("mi355x_bam_index_dev_counts", None, [P(C.c_uint64)])
+    sig("mi355x_bam_index_dev_stage_ms", None, [P(C.c_double)])
     sig("mi355x_route_by_chr", C.c_int64, [C.c_char_p, C.c_size_t, P(abi.bntseq_t), C.c_int, P(C.c_void_p), P(C.c_size_t)])
     sig("bwa_set_rg", C.c_void_p, [C.c_char_p])
     sig("bwa_insert_header", C.c_void_p, [C.c_char_p, C.c_void_p])

@@ -19,6 +19,15 @@
 // the other calls' contexts that may grow meanwhile; MPIBWA_BAM_SORT_MAX_BYTES caps the admitted bytes (the tests' way to a refusal).
 // The records' arrays can only be sized after the count pass, so there are two such checks; a refusal returns INT64_MIN and has written
 // nothing to out.
+//
+// The BAI index (bam_index_util.h, bam_index_kernel.hip) lives here too, because it is made of what a sort holds:
+//   mi355x_bam_sort_index_dev   the sort above, and between its sort and its emit stage the index stages over d_u, d_off, the order
+//             d_idx2, the places d_dst and the output's cuts (8 bytes a block go up); every piece's d_sizes come back beside its
+//             bytes, so that the host knows each output block's file offset when it writes the index.  The index stages' 52 bytes a
+//             record enter this call's second admission check only; a third one covers the runs and the windows once counted.
+//   mi355x_bam_index_dev        load_header, load_inflate and walk_count as the sort does them, the write pass of the walk, then the
+//             index stages with the file's own order and blocks.  What the device does not take — blocks that do not end on record
+//             boundaries, a malformed, out-of-order or too long record — goes to the host path (bam_index.cpp), which decides the code.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -30,6 +39,7 @@
 #include "hip_util.h"
 #include "device.h"
 #include "bam_sort_util.h"
+#include "bam_index_util.h"
 
 namespace mbw {
 namespace {
@@ -39,6 +49,11 @@ constexpr size_t BS_GROUP_BYTES = (size_t)BS_GROUP * 0x10000;    // their compre
 constexpr size_t BS_SLOT_BYTES = 0x10000, BS_SLACK = 16;
 constexpr size_t BS_MARGIN = 256u << 20;
 constexpr size_t BS_REC_BYTES = 40;                              // offset 8, size 4, key 8 (later the place in the sorted stream), key' 8, index 4, index' 4, sorted size 4
+
+// the index stages (bam_index_kernel.hip): per record the run key 8, v0 8, ref << 32 | end 8 and its maxima 8, beg 4, mapped 4 and its
+// sums 4, the head flag 1, the run's first record 4; per contig four words, n_intv and its sums; per run key 8, key' 8, number 4,
+// number' 4 and the chunk 16; per window 8
+constexpr size_t IX_REC_BYTES = 52, IX_REF_BYTES = 40, IX_RUN_BYTES = 40, IX_WIN_BYTES = 8;
 
 struct SortCtx {
 	bool ready = false;
@@ -50,9 +65,14 @@ struct SortCtx {
 	// grow with the file
 	DevBuf d_u, d_text_off, d_status, d_cnt, d_first, d_off, d_size, d_key, d_key2, d_idx, d_idx2, d_ssize, d_tmp;
 	PinBuf h_status, h_ssize;
+	// the index stages' (BamIndexBufs, device.h), allocated by the first call that indexes
+	DevBuf x_cut, x_rb, x_v0, x_mx, x_mxs, x_beg, x_map, x_maps, x_head, x_rs, x_nsel, x_stat, x_nintv, x_woff, x_rk, x_rk2, x_ri, x_ri2, x_rbeg, x_rend, x_io;
+	PinBuf h_sizes[2];
 	std::vector<DevBuf *> all()
 	{
-		std::vector<DevBuf *> v = {&d_flag, &d_u, &d_text_off, &d_status, &d_cnt, &d_first, &d_off, &d_size, &d_key, &d_key2, &d_idx, &d_idx2, &d_ssize, &d_tmp};
+		std::vector<DevBuf *> v = {&d_flag, &d_u, &d_text_off, &d_status, &d_cnt, &d_first, &d_off, &d_size, &d_key, &d_key2, &d_idx, &d_idx2, &d_ssize, &d_tmp,
+		                           &x_cut, &x_rb, &x_v0, &x_mx, &x_mxs, &x_beg, &x_map, &x_maps, &x_head, &x_rs, &x_nsel, &x_stat, &x_nintv, &x_woff, &x_rk, &x_rk2,
+		                           &x_ri, &x_ri2, &x_rbeg, &x_rend, &x_io};
 		for (int s = 0; s < 2; ++s)
 			for (DevBuf *b : {&d_comp[s], &d_goff[s], &d_piece[s], &d_cut[s], &d_slots[s], &d_sizes[s], &d_out[s], &d_meta[s], &d_tokens[s]}) v.push_back(b);
 		return v;
@@ -95,7 +115,7 @@ struct SortCtx {
 	void release()
 	{
 		for (DevBuf *b : all()) b->release();
-		for (PinBuf *b : {&h_flag, &h_status, &h_ssize}) b->release();
+		for (PinBuf *b : {&h_flag, &h_status, &h_ssize, &h_sizes[0], &h_sizes[1]}) b->release();
 		for (int s = 0; s < 2; ++s) {
 			for (PinBuf *b : {&h_comp[s], &h_goff[s], &h_cut[s], &h_out[s], &h_meta[s]}) b->release();
 			if (st[s]) (void)hipStreamDestroy(st[s]);
@@ -120,14 +140,18 @@ double ms_since(std::chrono::steady_clock::time_point t0)
 }
 
 // does a call that needs `need` bytes of device memory in g_bs's buffers fit?  (a refusal is counted and its need kept for the caller's message)
-bool admitted(size_t need)
+std::atomic<uint64_t> g_ix_counts[8];     // calls, records, calls whose walk the host did, runs before the join, chunks written, linear windows, BAI bytes, calls refused for memory
+std::mutex g_ix_ms_mu;
+double g_ix_ms[8];                        // the last call: inflate, walk, index, serialisation, all of it (wall ms); the index kernels (event ms); 0; 0
+
+bool admitted(size_t need, std::atomic<uint64_t> *counts = g_bs_counts)
 {
 	size_t free_b = 0, total_b = 0;
 	HIP_OK(hipMemGetInfo(&free_b, &total_b));
 	size_t have = free_b + g_bs.held();
 	if (const char *e = getenv("MPIBWA_BAM_SORT_MAX_BYTES")) have = std::min<size_t>(have, (size_t)strtoull(e, nullptr, 10));
 	if (need + BS_MARGIN <= have) return true;
-	g_bs_counts[7] += 1;
+	counts[7] += 1;
 	g_bs_refused_need = need + BS_MARGIN;
 	return false;
 }
@@ -144,37 +168,44 @@ int64_t header_code(const uint8_t *bam, size_t len, uint64_t u)
 	return hs < 0 ? hs : -(int64_t)u - 1;
 }
 
-int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
-{
-	const auto t_all = std::chrono::steady_clock::now();
+// what the sort and the stand-alone index share: the file's plan, its header, the resident inflated stream and the count pass
+struct Loaded {
 	std::vector<int64_t> blk, txt;
-	const int64_t bad = bgzf_in_plan(bam, len, blk, txt);
-	const size_t n_blk = blk.size() - 1;
-	const uint64_t u = (uint64_t)txt[n_blk];
-	if (n_blk >= (size_t)INT_MAX) die("mi355x_bam_sort_dev: %zu blocks", n_blk);
-
-	// the header, from as many leading blocks as it takes (1, 2, 4, ...)
+	int64_t bad = -1;
+	size_t n_blk = 0, need1 = 0;
+	uint64_t u = 0;
 	bsort::Header h;
-	std::vector<uint8_t> lead;
-	for (size_t k = 1;; k *= 2) {
-		const size_t nb = std::min(k, n_blk);
-		lead.resize((size_t)txt[nb] + 1);
-		const int64_t r = nb ? mi355x_bgzf_inflate(bam, (size_t)blk[nb], (char *)lead.data(), lead.size()) : 0;
-		if (r < 0) return r;   // (the first bad block of the file: every block before it is among these)
-		const int64_t hs = bsort::parse_header(lead.data(), (uint64_t)txt[nb], h);
-		if (hs == 0) break;
-		if (hs < 0 || nb == n_blk) return header_code(bam, len, u);
-	}
-	std::vector<uint8_t> head;
-	bsort::coordinate_header(lead.data(), h, head);
-	const uint64_t hn = head.size();
-	std::vector<uint8_t>().swap(lead);
+	std::vector<uint8_t> lead;   // the leading blocks' bytes, as far as the header reaches
+	double ms_inflate = 0;
+};
 
-	use_device();
-	std::lock_guard<std::mutex> hold(g_bs_mu);
-	SortCtx &C = g_bs;
-	const size_t need1 = SortCtx::fixed_bytes() + (size_t)u + bsort::BAM_SORT_SLACK + (n_blk + 1) * (sizeof(uint64_t) + 3 * sizeof(uint32_t));
-	if (!admitted(need1)) return INT64_MIN;
+// the plan and the header, from as many leading blocks as it takes (1, 2, 4, ...): on the host, before the lock.  false: *code is the call's
+bool load_header(const char *who, const uint8_t *bam, size_t len, Loaded &L, int64_t *code)
+{
+	L.bad = bgzf_in_plan(bam, len, L.blk, L.txt);
+	L.n_blk = L.blk.size() - 1;
+	L.u = (uint64_t)L.txt[L.n_blk];
+	if (L.n_blk >= (size_t)INT_MAX) die("%s: %zu blocks", who, L.n_blk);
+	for (size_t k = 1;; k *= 2) {
+		const size_t nb = std::min(k, L.n_blk);
+		L.lead.resize((size_t)L.txt[nb] + 1);
+		const int64_t r = nb ? mi355x_bgzf_inflate(bam, (size_t)L.blk[nb], (char *)L.lead.data(), L.lead.size()) : 0;
+		if (r < 0) { *code = r; return false; }   // (the first bad block of the file: every block before it is among these)
+		const int64_t hs = bsort::parse_header(L.lead.data(), (uint64_t)L.txt[nb], L.h);
+		if (hs == 0) break;
+		if (hs < 0 || nb == L.n_blk) { *code = header_code(bam, len, L.u); return false; }
+	}
+	return true;
+}
+
+// under the lock: the first admission check, the buffers, and every block inflated into d_u.  false: *code is the call's (INT64_MIN: refused)
+bool load_inflate(SortCtx &C, const uint8_t *bam, Loaded &L, std::atomic<uint64_t> *counts, int64_t *code)
+{
+	const std::vector<int64_t> &blk = L.blk, &txt = L.txt;
+	const size_t n_blk = L.n_blk;
+	const uint64_t u = L.u;
+	L.need1 = SortCtx::fixed_bytes() + (size_t)u + bsort::BAM_SORT_SLACK + (n_blk + 1) * (sizeof(uint64_t) + 3 * sizeof(uint32_t));
+	if (!admitted(L.need1, counts)) { *code = INT64_MIN; return false; }
 	if (!C.ready) C.init();
 	C.d_u.ensure((size_t)u + bsort::BAM_SORT_SLACK);
 	C.d_text_off.ensure((n_blk + 1) * sizeof(uint64_t));
@@ -184,7 +215,6 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 	C.h_status.ensure((n_blk + 1) * sizeof(uint32_t));
 	uint8_t *const d_u = (uint8_t *)C.d_u.p;
 
-	// ---- inflate ----
 	auto t0 = std::chrono::steady_clock::now();
 	HIP_OK(hipMemsetAsync(d_u + u, 0, bsort::BAM_SORT_SLACK, C.st[0]));
 	const size_t n_groups = (n_blk + BS_GROUP - 1) / BS_GROUP;
@@ -208,23 +238,141 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 	if (n_blk) HIP_OK(hipMemcpyAsync(C.h_status.p, C.d_status.p, n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
 	HIP_OK(hipStreamSynchronize(C.st[0]));
 	for (size_t b = 0; b < n_blk; ++b)
-		if (((const uint32_t *)C.h_status.p)[b]) return -blk[b] - 1;
-	if (bad >= 0) return -bad - 1;
-	const double ms_inflate = ms_since(t0);
+		if (((const uint32_t *)C.h_status.p)[b]) { *code = -blk[b] - 1; return false; }
+	if (L.bad >= 0) { *code = -L.bad - 1; return false; }
+	L.ms_inflate = ms_since(t0);
+	return true;
+}
 
-	// ---- walk ----
-	t0 = std::chrono::steady_clock::now();
-	HIP_OK(hipMemcpyAsync(C.d_text_off.p, txt.data(), (n_blk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
+// the count pass of the walk: the records, and whether the host has to walk (a foreign writer's blocks, or a malformed record)
+void walk_count(SortCtx &C, const Loaded &L, bool *host_walk, size_t *n_rec)
+{
+	const size_t n_blk = L.n_blk;
+	HIP_OK(hipMemcpyAsync(C.d_text_off.p, L.txt.data(), (n_blk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
 	HIP_OK(hipMemsetAsync(C.d_flag.p, 0, 16, C.st[0]));
 	C.d_tmp.ensure(bam_sort_temp_bytes(0, (int)n_blk));
-	launch_bam_sort_count(C.st[0], d_u, (const uint64_t *)C.d_text_off.p, (int)n_blk, h.end, h.n_ref, (uint32_t *)C.d_cnt.p, (uint32_t *)C.d_flag.p);
+	launch_bam_sort_count(C.st[0], (const uint8_t *)C.d_u.p, (const uint64_t *)C.d_text_off.p, (int)n_blk, L.h.end, L.h.n_ref, (uint32_t *)C.d_cnt.p, (uint32_t *)C.d_flag.p);
 	launch_bam_sort_scan(C.st[0], C.d_tmp.p, C.d_tmp.cap, (const uint32_t *)C.d_cnt.p, (uint32_t *)C.d_first.p, (int)n_blk);
 	uint32_t *hf = (uint32_t *)C.h_flag.p;
 	HIP_OK(hipMemcpyAsync(hf, C.d_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
 	HIP_OK(hipMemcpyAsync(hf + 1, (const uint32_t *)C.d_first.p + n_blk, sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
 	HIP_OK(hipStreamSynchronize(C.st[0]));
-	const bool host_walk = hf[0] != 0;
-	size_t n_rec = hf[1];
+	*host_walk = hf[0] != 0;
+	*n_rec = hf[1];
+}
+
+// what the index stages need of device memory before the runs and the windows are counted
+size_t index_need(size_t n_rec, int32_t n_ref, size_t n_cut)
+{
+	return IX_REC_BYTES * (n_rec + 1) + IX_REF_BYTES * ((size_t)n_ref + 1) + sizeof(uint64_t) * (n_cut + 1);
+}
+
+enum : int { IXB_OK = 0, IXB_FAILS = 1, IXB_REFUSED = 2, IXB_HOST = 3 };
+
+// The index stages over the n_rec records of a stream on the device (BamIndexBufs, device.h): `cut` are the indexed file's blocks in its
+// stream (d_cut: the same on the device, cut.size() words).  need: the call's device memory so far, index_need included.
+// IXB_OK: P is filled (block-number space); IXB_FAILS: *bad_off is the smallest offset in d_u of a record that ends beyond 2^29 or,
+// with keys, sorts before its predecessor; IXB_REFUSED: no memory for the runs and the windows; IXB_HOST: more windows than the device
+// path counts (32-bit), the host indexes.
+int index_build(SortCtx &C, const uint64_t *d_off, const uint32_t *d_order, const uint64_t *d_place, uint64_t place_base, const uint64_t *d_cut,
+                const std::vector<uint64_t> &cut, size_t n_rec, int32_t n_ref, const uint64_t *d_keys, size_t need, std::atomic<uint64_t> *counts, bidx::Parts &P,
+                uint64_t *bad_off, double *kernel_ms)
+{
+	if (std::min<uint64_t>(n_rec, (uint64_t)n_ref) >= ((uint64_t)1 << 17)) return IXB_HOST;   // (a contig has at most 2^15 windows)
+	hipStream_t st = C.st[0];
+	const size_t nr = n_rec + 1, nc = (size_t)n_ref + 1;
+	C.x_rb.ensure(nr * 8); C.x_v0.ensure(nr * 8); C.x_mx.ensure(nr * 8); C.x_mxs.ensure(nr * 8);
+	C.x_beg.ensure(nr * 4); C.x_map.ensure(nr * 4); C.x_maps.ensure(nr * 4); C.x_head.ensure(nr); C.x_rs.ensure(nr * 4); C.x_nsel.ensure(16);
+	C.x_stat.ensure(nc * 32); C.x_nintv.ensure(nc * 4); C.x_woff.ensure(nc * 4);
+	C.d_tmp.ensure(bam_index_temp_bytes((uint32_t)n_rec, n_ref, (uint32_t)n_rec));
+	BamIndexBufs B = {};
+	B.u = (const uint8_t *)C.d_u.p; B.off = d_off; B.order = d_order; B.place = d_place; B.place_base = place_base; B.cut = d_cut; B.n_cut = cut.size() - 1;
+	B.n_rec = (uint32_t)n_rec; B.n_ref = n_ref; B.keys = d_keys; B.end_v = bidx::end_voffset(cut.data(), cut.size() - 1);
+	B.rb = (uint64_t *)C.x_rb.p; B.v0 = (uint64_t *)C.x_v0.p; B.mx = (uint64_t *)C.x_mx.p; B.mxs = (uint64_t *)C.x_mxs.p;
+	B.beg = (uint32_t *)C.x_beg.p; B.map = (uint32_t *)C.x_map.p; B.maps = (uint32_t *)C.x_maps.p; B.head = (uint8_t *)C.x_head.p;
+	B.rs = (uint32_t *)C.x_rs.p; B.n_sel = (uint32_t *)C.x_nsel.p;
+	B.stat = (uint64_t *)C.x_stat.p; B.n_intv = (uint32_t *)C.x_nintv.p; B.woff = (uint32_t *)C.x_woff.p;
+	B.bad = (unsigned long long *)C.d_flag.p + 1; B.tmp = C.d_tmp.p; B.tmp_bytes = C.d_tmp.cap;
+	HIP_OK(hipMemsetAsync(B.bad, 0xff, sizeof(unsigned long long), st));
+	HIP_OK(hipEventRecord(C.ev_g[0][0], st));
+	launch_bam_index_records(st, B);
+	HIP_OK(hipEventRecord(C.ev_g[0][1], st));
+	uint32_t n_runs = 0, n_win = 0;
+	unsigned long long bad = 0;
+	HIP_OK(hipMemcpyAsync(&n_runs, B.n_sel, sizeof n_runs, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipMemcpyAsync(&n_win, B.woff + n_ref, sizeof n_win, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipMemcpyAsync(&bad, B.bad, sizeof bad, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	if (bad != ~0ull) { *bad_off = bad; return IXB_FAILS; }
+	if (!admitted(need + IX_RUN_BYTES * (size_t)n_runs + IX_WIN_BYTES * (size_t)n_win, counts)) return IXB_REFUSED;
+	C.x_rk.ensure((size_t)n_runs * 8 + 8); C.x_rk2.ensure((size_t)n_runs * 8 + 8); C.x_ri.ensure((size_t)n_runs * 4 + 4); C.x_ri2.ensure((size_t)n_runs * 4 + 4);
+	C.x_rbeg.ensure((size_t)n_runs * 8 + 8); C.x_rend.ensure((size_t)n_runs * 8 + 8); C.x_io.ensure((size_t)n_win * 8 + 8);
+	B.rk = (uint64_t *)C.x_rk.p; B.rk2 = (uint64_t *)C.x_rk2.p; B.ri = (uint32_t *)C.x_ri.p; B.ri2 = (uint32_t *)C.x_ri2.p;
+	B.rbeg = (uint64_t *)C.x_rbeg.p; B.rend = (uint64_t *)C.x_rend.p; B.io = (uint64_t *)C.x_io.p;
+	HIP_OK(hipEventRecord(C.ev_g[1][0], st));
+	launch_bam_index_runs(st, B, n_runs, n_win);
+	HIP_OK(hipEventRecord(C.ev_g[1][1], st));
+	P.n_ref = n_ref;
+	P.run_key.resize(n_runs); P.run_beg.resize(n_runs); P.run_end.resize(n_runs);
+	P.stat.resize(4 * nc); P.n_intv.resize(nc); P.ioffset.resize(n_win);
+	if (n_runs) {
+		HIP_OK(hipMemcpyAsync(P.run_key.data(), B.rk2, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
+		HIP_OK(hipMemcpyAsync(P.run_beg.data(), B.rbeg, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
+		HIP_OK(hipMemcpyAsync(P.run_end.data(), B.rend, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
+	}
+	HIP_OK(hipMemcpyAsync(P.stat.data(), B.stat, nc * 32, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipMemcpyAsync(P.n_intv.data(), B.n_intv, nc * 4, hipMemcpyDeviceToHost, st));
+	if (n_win) HIP_OK(hipMemcpyAsync(P.ioffset.data(), B.io, (size_t)n_win * 8, hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	P.n_no_coor = P.stat[4 * (size_t)n_ref];
+	P.stat.resize(4 * (size_t)n_ref); P.n_intv.resize((size_t)n_ref);
+	float a = 0, b = 0;
+	HIP_OK(hipEventElapsedTime(&a, C.ev_g[0][0], C.ev_g[0][1]));
+	HIP_OK(hipEventElapsedTime(&b, C.ev_g[1][0], C.ev_g[1][1]));
+	*kernel_ms = (double)a + (double)b;
+	return IXB_OK;
+}
+
+// what a call that also indexes gets back
+struct IndexWant {
+	std::vector<uint8_t> bai;
+	int reason = 0;
+};
+
+void index_counts(size_t n_rec, bool host_walk, const bidx::Parts &P, size_t n_runs, size_t bai_bytes)
+{
+	g_ix_counts[1] += n_rec; g_ix_counts[2] += host_walk ? 1 : 0; g_ix_counts[3] += n_runs; g_ix_counts[4] += P.n_chunks; g_ix_counts[5] += P.ioffset.size();
+	g_ix_counts[6] += bai_bytes;
+}
+
+int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, IndexWant *ix)
+{
+	const auto t_all = std::chrono::steady_clock::now();
+	std::atomic<uint64_t> *const refusals = g_bs_counts;
+	Loaded L;
+	int64_t code = 0;
+	if (!load_header("mi355x_bam_sort_dev", bam, len, L, &code)) return code;
+	const size_t n_blk = L.n_blk;
+	const uint64_t u = L.u;
+	const bsort::Header &h = L.h;
+	std::vector<uint8_t> head;
+	bsort::coordinate_header(L.lead.data(), h, head);
+	const uint64_t hn = head.size();
+	std::vector<uint8_t>().swap(L.lead);
+
+	use_device();
+	std::lock_guard<std::mutex> hold(g_bs_mu);
+	SortCtx &C = g_bs;
+	if (!load_inflate(C, bam, L, refusals, &code)) return code;
+	const size_t need1 = L.need1;
+	const double ms_inflate = L.ms_inflate;
+	uint8_t *const d_u = (uint8_t *)C.d_u.p;
+
+	// ---- walk ----
+	auto t0 = std::chrono::steady_clock::now();
+	bool host_walk = false;
+	size_t n_rec = 0;
+	walk_count(C, L, &host_walk, &n_rec);
 	std::vector<uint64_t> h_off, h_key;
 	std::vector<uint32_t> h_size;
 	if (host_walk) {   // a foreign writer's blocks, or a malformed record: the host's hop decides which
@@ -241,8 +389,14 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 		g_bs_refused_need = need1 + BS_REC_BYTES * (n_rec + 1) + BS_MARGIN;
 		return INT64_MIN;
 	}
-	const size_t tmp_bytes = bam_sort_temp_bytes((uint32_t)n_rec, (int)n_blk);
-	if (!admitted(need1 + BS_REC_BYTES * (n_rec + 1) + tmp_bytes)) return INT64_MIN;
+	size_t tmp_bytes = bam_sort_temp_bytes((uint32_t)n_rec, (int)n_blk);
+	size_t need2 = need1 + BS_REC_BYTES * (n_rec + 1);
+	if (ix) {   // the index stages' arrays, and the cuts of at most as many output blocks as the bound counts
+		tmp_bytes = std::max(tmp_bytes, bam_index_temp_bytes((uint32_t)n_rec, h.n_ref, (uint32_t)n_rec));
+		need2 += index_need(n_rec, h.n_ref, (size_t)(3 * ((u + bsort::BAM_SORT_HEADER_GROWTH) / 0xff00 + 1) + 3));
+	}
+	need2 += tmp_bytes;
+	if (!admitted(need2)) return INT64_MIN;
 	C.d_off.ensure((n_rec + 1) * sizeof(uint64_t));
 	C.d_size.ensure((n_rec + 1) * sizeof(uint32_t));
 	C.d_key.ensure((n_rec + 1) * sizeof(uint64_t));
@@ -282,6 +436,26 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 	std::vector<size_t> cut;
 	bam_sort_cuts(hn, rec_off, cut);
 	const size_t n_out = cut.size() - 1, n_pieces = (n_out + BAM_DEV_BLOCKS - 1) / BAM_DEV_BLOCKS;
+	// ---- index (mi355x_bam_sort_index_dev only): from the order and the cuts, before anything is written to out ----
+	bidx::Parts parts;
+	double ms_index = 0, ix_kernel_ms = 0;
+	bool ix_host = false;
+	std::vector<int64_t> out_off;   // the output blocks' file offsets
+	if (ix) {
+		const auto ti = std::chrono::steady_clock::now();
+		const std::vector<uint64_t> cut64(cut.begin(), cut.end());
+		C.x_cut.ensure(cut64.size() * sizeof(uint64_t));
+		C.h_sizes[0].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS); C.h_sizes[1].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS);
+		HIP_OK(hipMemcpyAsync(C.x_cut.p, cut64.data(), cut64.size() * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
+		uint64_t bad_off = 0;
+		const int r = index_build(C, (const uint64_t *)C.d_off.p, (const uint32_t *)C.d_idx2.p, d_dst, hn, (const uint64_t *)C.x_cut.p, cut64, n_rec, h.n_ref, nullptr,
+		                          need2, refusals, parts, &bad_off, &ix_kernel_ms);
+		if (r == IXB_FAILS) { ix->reason = bidx::BAI_TOO_LONG; return -(int64_t)bad_off - 1; }
+		if (r == IXB_REFUSED) return INT64_MIN;
+		ix_host = r == IXB_HOST;
+		out_off.reserve(n_out + 1);
+		ms_index = ms_since(ti);
+	}
 	double gather_ms = 0;
 	uint64_t gather_bytes = 0, piece_gather[2] = {0, 0};
 	const bool gather_alone = getenv("MPIBWA_BAM_SORT_GATHER_ALONE") != nullptr;   // tools/bench_bam_sort.py: no other kernel beside a timed gather
@@ -328,12 +502,35 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 		const size_t zbytes = (size_t)((const unsigned long long *)C.h_meta[s].p)[0];
 		if (w + zbytes + 28 > cap) die("mi355x_bam_sort_dev: %zu bytes of blocks above the bound %zu", w + zbytes + 28, (size_t)bam_sort_bound_of(u));
 		HIP_OK(hipMemcpyAsync(C.h_out[s].p, C.d_out[s].p, zbytes, hipMemcpyDeviceToHost, C.st[s]));
+		const size_t nb_k = std::min(n_out, (k + 1) * BAM_DEV_BLOCKS) - k * BAM_DEV_BLOCKS;
+		if (ix) HIP_OK(hipMemcpyAsync(C.h_sizes[s].p, C.d_sizes[s].p, nb_k * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[s]));
 		HIP_OK(hipStreamSynchronize(C.st[s]));
+		if (ix) {   // the piece's blocks, one by one
+			size_t at = w;
+			for (size_t j = 0; j < nb_k; ++j) { out_off.push_back((int64_t)at); at += ((const uint32_t *)C.h_sizes[s].p)[j]; }
+			if (at != w + zbytes) die("mi355x_bam_sort_index_dev: a piece's blocks have %zu bytes, the piece %zu", at - w, zbytes);
+		}
 		memcpy(out + w, C.h_out[s].p, zbytes);
 		w += zbytes;
 	}
+	if (ix) out_off.push_back((int64_t)w);
 	w += mi355x_bgzf_eof(out + w);
-	const double ms_emit = ms_since(t0);
+	const double ms_emit = ms_since(t0) - ms_index;
+	if (ix) {
+		const auto ts = std::chrono::steady_clock::now();
+		size_t n_runs = parts.run_key.size();
+		if (ix_host) {   // more windows than the device path counts: the host indexes what was written
+			const int64_t r = bam_index_host(out, w, ix->bai, &ix->reason);
+			if (r != (int64_t)n_rec) die("mi355x_bam_sort_index_dev: the host indexed %lld records of %zu", (long long)r, n_rec);
+			n_runs = 0;
+		} else
+			bidx::serialise(parts, out_off.data(), ix->bai);
+		g_ix_counts[2] += ix_host ? 1 : 0;
+		index_counts(n_rec, false, parts, n_runs, ix->bai.size());
+		std::lock_guard<std::mutex> lk(g_ix_ms_mu);
+		const double v[8] = {ms_inflate, ms_walk, ms_index, ms_since(ts), ms_since(t_all), ix_kernel_ms, 0, 0};
+		memcpy(g_ix_ms, v, sizeof v);
+	}
 
 	g_bs_counts[1] += n_rec; g_bs_counts[2] += host_walk ? 1 : 0; g_bs_counts[3] += u; g_bs_counts[4] += n_blk; g_bs_counts[5] += n_out + 1; g_bs_counts[6] += w;
 	{
@@ -342,6 +539,89 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 		memcpy(g_bs_ms, v, sizeof v);
 	}
 	return (int64_t)w;
+}
+
+// 1 for a negative code of the sort that a BGZF block caused, 2 for one that the header or a record caused (a failing file is inflated
+// once more on the host to tell)
+int sort_failure_reason(const uint8_t *bam, size_t len)
+{
+	std::vector<int64_t> blk, txt;
+	const int64_t bad = bgzf_in_plan(bam, len, blk, txt);
+	std::vector<uint8_t> text((size_t)txt.back() + 1);
+	const int64_t r = mi355x_bgzf_inflate(bam, len, (char *)text.data(), text.size());
+	return r < 0 || bad >= 0 ? bidx::BAI_BAD_BLOCK : bidx::BAI_BAD_RECORD;
+}
+
+// mi355x_bam_index_dev: the inflate and the walk of the sort, then the index stages with the file's own order and blocks.  Whatever
+// fails or does not suit the device goes to the host path, which decides the code.
+int64_t index_dev(const uint8_t *bam, size_t len, std::vector<uint8_t> &bai, int *reason)
+{
+	const auto t_all = std::chrono::steady_clock::now();
+	Loaded L;
+	int64_t code = 0;
+	auto by_host = [&]() {
+		g_ix_counts[2] += 1;
+		const int64_t n = bam_index_host(bam, len, bai, reason);
+		if (n >= 0) { g_ix_counts[1] += (uint64_t)n; g_ix_counts[6] += bai.size(); }
+		return n;
+	};
+	if (!load_header("mi355x_bam_index_dev", bam, len, L, &code)) return bam_index_host(bam, len, bai, reason);
+	std::vector<uint8_t>().swap(L.lead);
+	use_device();
+	std::unique_lock<std::mutex> hold(g_bs_mu);
+	SortCtx &C = g_bs;
+	if (!load_inflate(C, bam, L, g_ix_counts, &code)) {
+		hold.unlock();
+		return code == INT64_MIN ? code : bam_index_host(bam, len, bai, reason);
+	}
+	auto t0 = std::chrono::steady_clock::now();
+	bool host_walk = false;
+	size_t n_rec = 0;
+	walk_count(C, L, &host_walk, &n_rec);
+	if (host_walk) {   // a foreign writer's blocks, or a malformed record
+		hold.unlock();
+		return by_host();
+	}
+	if (n_rec >= (size_t)INT_MAX - 1) {
+		g_ix_counts[7] += 1;
+		return INT64_MIN;
+	}
+	const size_t n_blk = L.n_blk;
+	const size_t tmp_bytes = std::max(bam_sort_temp_bytes((uint32_t)n_rec, (int)n_blk), bam_index_temp_bytes((uint32_t)n_rec, L.h.n_ref, (uint32_t)n_rec));
+	const size_t need2 = L.need1 + (sizeof(uint64_t) + sizeof(uint32_t) + sizeof(uint64_t)) * (n_rec + 1) + index_need(n_rec, L.h.n_ref, 0) + tmp_bytes;
+	if (!admitted(need2, g_ix_counts)) return INT64_MIN;
+	C.d_off.ensure((n_rec + 1) * sizeof(uint64_t));
+	C.d_size.ensure((n_rec + 1) * sizeof(uint32_t));
+	C.d_key.ensure((n_rec + 1) * sizeof(uint64_t));
+	C.d_tmp.ensure(tmp_bytes);
+	launch_bam_sort_write(C.st[0], (const uint8_t *)C.d_u.p, (const uint64_t *)C.d_text_off.p, (int)n_blk, L.h.end, L.h.n_ref, (const uint32_t *)C.d_first.p,
+	                      (uint64_t *)C.d_off.p, (uint32_t *)C.d_size.p, (uint64_t *)C.d_key.p);
+	HIP_OK(hipStreamSynchronize(C.st[0]));
+	const double ms_walk = ms_since(t0);
+
+	t0 = std::chrono::steady_clock::now();
+	const std::vector<uint64_t> cut(L.txt.begin(), L.txt.end());
+	bidx::Parts parts;
+	uint64_t bad_off = 0;
+	double kernel_ms = 0;
+	const int r = index_build(C, (const uint64_t *)C.d_off.p, nullptr, (const uint64_t *)C.d_off.p, 0, (const uint64_t *)C.d_text_off.p, cut, n_rec, L.h.n_ref,
+	                          (const uint64_t *)C.d_key.p, need2, g_ix_counts, parts, &bad_off, &kernel_ms);
+	if (r == IXB_REFUSED) return INT64_MIN;
+	if (r != IXB_OK) {   // out of order, beyond 2^29, or more windows than the device counts
+		hold.unlock();
+		return by_host();
+	}
+	const double ms_index = ms_since(t0);
+	hold.unlock();
+	t0 = std::chrono::steady_clock::now();
+	const size_t n_runs = parts.run_key.size();
+	bidx::serialise(parts, L.blk.data(), bai);
+	index_counts(n_rec, false, parts, n_runs, bai.size());
+	*reason = bidx::BAI_OK;
+	std::lock_guard<std::mutex> lk(g_ix_ms_mu);
+	const double v[8] = {L.ms_inflate, ms_walk, ms_index, ms_since(t0), ms_since(t_all), kernel_ms, 0, 0};
+	memcpy(g_ix_ms, v, sizeof v);
+	return (int64_t)n_rec;
 }
 
 } // namespace
@@ -361,7 +641,43 @@ using namespace mbw;
 extern "C" int64_t mi355x_bam_sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap)
 {
 	g_bs_counts[0] += 1;
-	return sort_dev(bam, len, out, cap);
+	return sort_dev(bam, len, out, cap, nullptr);
+}
+
+// the sort and, from what it holds on the device, the BAI index of what it writes (include/mpibwa_amd.h)
+extern "C" int64_t mi355x_bam_sort_index_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, uint8_t **bai, size_t *bai_len, int *reason)
+{
+	g_bs_counts[0] += 1; g_ix_counts[0] += 1;
+	IndexWant ix;
+	const int64_t n = sort_dev(bam, len, out, cap, &ix);
+	if (reason) *reason = n >= 0 || n == INT64_MIN ? bidx::BAI_OK : ix.reason ? ix.reason : sort_failure_reason(bam, len);
+	if (n == INT64_MIN) g_ix_counts[7] += 1;
+	if (n > 0) bam_index_hand_over(ix.bai, bai, bai_len);
+	return n;
+}
+
+extern "C" int64_t mi355x_bam_index_dev(const uint8_t *bam, size_t len, uint8_t **bai, size_t *bai_len, int *reason)
+{
+	g_ix_counts[0] += 1;
+	std::vector<uint8_t> bytes;
+	int why = 0;
+	const int64_t n = index_dev(bam, len, bytes, &why);
+	if (reason) *reason = n == INT64_MIN ? 0 : why;
+	if (n >= 0) bam_index_hand_over(bytes, bai, bai_len);
+	return n;
+}
+
+extern "C" void mi355x_bam_index_dev_counts(uint64_t out[8])
+{
+	for (int k = 0; k < 8; ++k) out[k] = g_ix_counts[k].load();
+}
+
+// the last finished indexing call's stages, for tools/bench_bam_index.py: wall ms of inflate, walk, the index stages, the serialisation
+// and the whole call; the index kernels' summed event ms; 0; 0
+extern "C" void mi355x_bam_index_dev_stage_ms(double out[8])
+{
+	std::lock_guard<std::mutex> lk(g_ix_ms_mu);
+	memcpy(out, g_ix_ms, sizeof g_ix_ms);
 }
 
 extern "C" void mi355x_bam_sort_dev_counts(uint64_t out[8])

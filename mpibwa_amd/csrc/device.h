@@ -639,6 +639,27 @@ void launch_bam_sort_order(void *stream, void *d_tmp, size_t tmp_bytes, uint32_t
 void launch_bam_sort_gather(void *stream, const uint8_t *d_u, const uint64_t *d_off, const uint32_t *d_idx, const uint64_t *d_dst, uint32_t n_rec, uint32_t r0,
                             uint32_t r1, uint64_t lo, uint64_t hi, uint8_t *d_piece);
 void release_bam_sort_contexts(); // the sort buffers and streams, unless a sort is running (mi355x_finalize)
+// ---- the BAI index of a coordinate-sorted stream on the device (bam_index_kernel.hip, bam_sort_stage.hip; bam_index_util.h) ----
+// Record i of the file (i < n_rec) stands at u[off[order ? order[i] : i]] and at place_base + place[i] of the indexed file's stream,
+// whose blocks start at cut[0 .. n_cut] (cut[n_cut]: the stream's end).  keys (or none): the packed sort keys in file order, checked.
+// *bad: the smallest off of a record that fails the call (the caller sets it to ~0).  Virtual offsets are block << 16 | offset in block.
+struct BamIndexBufs {
+	const uint8_t *u; const uint64_t *off; const uint32_t *order; const uint64_t *place; uint64_t place_base; const uint64_t *cut; uint64_t n_cut;
+	uint32_t n_rec; int32_t n_ref; const uint64_t *keys; uint64_t end_v;   // end_v: v1 of the last record
+	// per record: the run key, v0, ref << 32 | end and its inclusive maxima, beg, mapped (n_rec + 1) and its exclusive sums (n_rec + 1),
+	// the head flags, the runs' first records and their number
+	uint64_t *rb, *v0, *mx, *mxs; uint32_t *beg, *map, *maps; uint8_t *head; uint32_t *rs, *n_sel;
+	// per contig (n_ref + 1): four words of statistics, n_intv and its exclusive sums
+	uint64_t *stat; uint32_t *n_intv, *woff;
+	// per run: key and number, both sorted; the chunks in sorted order.  per window: v0 of its first record or BAI_NO_RECORD
+	uint64_t *rk, *rk2; uint32_t *ri, *ri2; uint64_t *rbeg, *rend, *io;
+	unsigned long long *bad; void *tmp; size_t tmp_bytes;
+};
+size_t bam_index_temp_bytes(uint32_t n_rec, int32_t n_ref, uint32_t n_runs);   // hipCUB's room
+// the record pass, the scans, the runs' heads (rs, *n_sel), the contigs' statistics, n_intv and woff (woff[n_ref]: all windows)
+void launch_bam_index_records(void *stream, const BamIndexBufs &B);
+// once the host knows the runs and the windows: rk2, rbeg, rend (sorted by contig and bin, stably) and io
+void launch_bam_index_runs(void *stream, const BamIndexBufs &B, uint32_t n_runs, uint32_t n_win);
 // the calling thread on the device of the resident index, or, before any index, on device 0 after the checks of mi355x_init
 void use_device();
 

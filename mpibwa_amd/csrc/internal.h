@@ -43,6 +43,10 @@ int64_t bam_sort_walk(const uint8_t *s, uint64_t h_end, uint64_t u, int32_t n_re
 // bytes in blocks of its own, then bam_cuts of the sorted records (rec_off[0 .. n] from 0) behind it
 uint64_t bam_sort_bound_of(uint64_t u);
 void bam_sort_cuts(uint64_t hn, const std::vector<uint64_t> &rec_off, std::vector<size_t> &cut);
+// bam_index.cpp, for both index paths (it and bam_sort_stage.hip): the BAI index of a coordinate-sorted file on the host (the number of
+// records, or -(offset) - 1 and bam_index_util.h's reason), and the bytes handed over as a malloc'ed buffer
+int64_t bam_index_host(const uint8_t *bam, size_t len, std::vector<uint8_t> &bai, int *reason);
+void bam_index_hand_over(const std::vector<uint8_t> &bai, uint8_t **out, size_t *out_len);
 
 // ---- plain records exchanged between host stages and HIP kernels ----
 
