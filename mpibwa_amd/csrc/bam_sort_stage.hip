@@ -12,7 +12,9 @@
 //   emit      the sorted sizes come back (4 bytes a record), the host makes bam_cuts' cuts and groups them into pieces of at most
 //             BAM_DEV_BLOCKS blocks; per piece, alternating the streams: the record gather kernel, bgzf_deflate_kernel, bgzf_gather_kernel,
 //             and only compressed bytes come back.  The header's blocks are pieces like the others, their bytes come from the host.
-// The sorted stream is never materialised: device memory is the inflated stream, 40 bytes a record and the two piece contexts.
+// The sorted stream is never materialised: device memory is the inflated stream, 40 bytes a record and the two piece contexts.  The
+// groups go up through an InflateLane per stream and the pieces out through a DeflateLane per stream (bgzf_lane.h), as in
+// bgzf_in_stage.hip and bgzf_stage.hip; the context itself stays outside ctx_pool.h's pool: one sort at a time is another contract.
 //
 // One sort holds the buffers at a time (a mutex); they only grow, so a second call of the same size allocates nothing.  Before it
 // allocates, a call compares what it needs with what hipMemGetInfo reports free (plus what the buffers already hold), less BS_MARGIN for
@@ -36,17 +38,14 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
-#include "hip_util.h"
-#include "device.h"
+#include "bgzf_lane.h"
 #include "bam_sort_util.h"
 #include "bam_index_util.h"
 
 namespace mbw {
 namespace {
 
-constexpr int BS_GROUP = 512;                                    // blocks per inflate launch
-constexpr size_t BS_GROUP_BYTES = (size_t)BS_GROUP * 0x10000;    // their compressed bytes at their largest
-constexpr size_t BS_SLOT_BYTES = 0x10000, BS_SLACK = 16;
+constexpr int BS_GROUP = LANE_BLOCKS;                            // blocks per inflate launch
 constexpr size_t BS_MARGIN = 256u << 20;
 constexpr size_t BS_REC_BYTES = 40;                              // offset 8, size 4, key 8 (later the place in the sorted stream), key' 8, index 4, index' 4, sorted size 4
 
@@ -59,29 +58,34 @@ struct SortCtx {
 	bool ready = false;
 	hipStream_t st[2] = {nullptr, nullptr};
 	hipEvent_t ev[2] = {nullptr, nullptr}, ev_g[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-	// of one size whatever the file
-	DevBuf d_comp[2], d_goff[2], d_piece[2], d_cut[2], d_slots[2], d_sizes[2], d_out[2], d_meta[2], d_tokens[2], d_flag;
-	PinBuf h_comp[2], h_goff[2], h_cut[2], h_out[2], h_meta[2], h_flag;
+	// of one size whatever the file: per stream an inflate lane for the groups, and for the pieces their bytes and a deflate lane
+	InflateLane in[2];
+	DeflateLane lane[2];
+	DevBuf d_piece[2], d_flag;
+	PinBuf h_flag;
 	// grow with the file
 	DevBuf d_u, d_text_off, d_status, d_cnt, d_first, d_off, d_size, d_key, d_key2, d_idx, d_idx2, d_ssize, d_tmp;
 	PinBuf h_status, h_ssize;
-	// the index stages' (BamIndexBufs, device.h), allocated by the first call that indexes
+	// the index stages' (BamIndexBufs, device.h), allocated by the first call that indexes (as are the lanes' h_sizes)
 	DevBuf x_cut, x_rb, x_v0, x_mx, x_mxs, x_beg, x_map, x_maps, x_head, x_rs, x_nsel, x_stat, x_nintv, x_woff, x_rk, x_rk2, x_ri, x_ri2, x_rbeg, x_rend, x_io;
-	PinBuf h_sizes[2];
+	std::vector<DevBuf *> own()   // the device buffers outside the lanes
+	{
+		return {&d_piece[0], &d_piece[1], &d_flag, &d_u, &d_text_off, &d_status, &d_cnt, &d_first, &d_off, &d_size, &d_key, &d_key2, &d_idx, &d_idx2, &d_ssize, &d_tmp,
+		        &x_cut, &x_rb, &x_v0, &x_mx, &x_mxs, &x_beg, &x_map, &x_maps, &x_head, &x_rs, &x_nsel, &x_stat, &x_nintv, &x_woff, &x_rk, &x_rk2,
+		        &x_ri, &x_ri2, &x_rbeg, &x_rend, &x_io};
+	}
 	std::vector<DevBuf *> all()
 	{
-		std::vector<DevBuf *> v = {&d_flag, &d_u, &d_text_off, &d_status, &d_cnt, &d_first, &d_off, &d_size, &d_key, &d_key2, &d_idx, &d_idx2, &d_ssize, &d_tmp,
-		                           &x_cut, &x_rb, &x_v0, &x_mx, &x_mxs, &x_beg, &x_map, &x_maps, &x_head, &x_rs, &x_nsel, &x_stat, &x_nintv, &x_woff, &x_rk, &x_rk2,
-		                           &x_ri, &x_ri2, &x_rbeg, &x_rend, &x_io};
-		for (int s = 0; s < 2; ++s)
-			for (DevBuf *b : {&d_comp[s], &d_goff[s], &d_piece[s], &d_cut[s], &d_slots[s], &d_sizes[s], &d_out[s], &d_meta[s], &d_tokens[s]}) v.push_back(b);
+		std::vector<DevBuf *> v = own();
+		for (int s = 0; s < 2; ++s) {
+			for (DevBuf *b : in[s].dev()) v.push_back(b);
+			for (DevBuf *b : lane[s].dev()) v.push_back(b);
+		}
 		return v;
 	}
-	static size_t fixed_bytes()
-	{
-		return 2 * (BS_GROUP_BYTES + sizeof(uint32_t) * 2 * (BS_GROUP + 1) + (BAM_DEV_BYTES + BS_SLACK) + sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1) +
-		            2 * BAM_DEV_BLOCKS * BS_SLOT_BYTES + sizeof(uint32_t) * BAM_DEV_BLOCKS + 16 + sizeof(uint16_t) * (size_t)BAM_DEV_BYTES) + 16;
-	}
+	static constexpr size_t PIECE_BYTES = LANE_TEXT_BYTES + LANE_SLACK, FLAG_BYTES = 16;
+	// what init() allocates on the device: the first admission check counts it
+	static constexpr size_t fixed_bytes() { return 2 * (InflateLane::dev_bytes() + DeflateLane::dev_bytes() + PIECE_BYTES) + FLAG_BYTES; }
 	size_t held()
 	{
 		size_t n = 0;
@@ -90,34 +94,22 @@ struct SortCtx {
 	}
 	void init()
 	{
-		d_flag.ensure(16); h_flag.ensure(16);
+		d_flag.ensure(FLAG_BYTES); h_flag.ensure(FLAG_BYTES);
 		for (int s = 0; s < 2; ++s) {
 			HIP_OK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
 			HIP_OK(hipEventCreateWithFlags(&ev[s], hipEventDisableTiming));
 			for (int k = 0; k < 2; ++k) HIP_OK(hipEventCreate(&ev_g[s][k]));
-			d_comp[s].ensure(BS_GROUP_BYTES);
-			d_goff[s].ensure(sizeof(uint32_t) * 2 * (BS_GROUP + 1));
-			d_piece[s].ensure(BAM_DEV_BYTES + BS_SLACK);
-			d_cut[s].ensure(sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1));
-			d_slots[s].ensure(BAM_DEV_BLOCKS * BS_SLOT_BYTES);
-			d_sizes[s].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS);
-			d_out[s].ensure(BAM_DEV_BLOCKS * BS_SLOT_BYTES);
-			d_meta[s].ensure(2 * sizeof(unsigned long long));
-			d_tokens[s].ensure(sizeof(uint16_t) * (size_t)BAM_DEV_BYTES);
-			h_comp[s].ensure(BS_GROUP_BYTES);
-			h_goff[s].ensure(sizeof(uint32_t) * 2 * (BS_GROUP + 1));
-			h_cut[s].ensure(sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1));
-			h_out[s].ensure(BAM_DEV_BLOCKS * BS_SLOT_BYTES);
-			h_meta[s].ensure(2 * sizeof(unsigned long long));
+			in[s].init(); lane[s].init();
+			d_piece[s].ensure(PIECE_BYTES);
 		}
 		ready = true;
 	}
 	void release()
 	{
-		for (DevBuf *b : all()) b->release();
-		for (PinBuf *b : {&h_flag, &h_status, &h_ssize, &h_sizes[0], &h_sizes[1]}) b->release();
+		for (DevBuf *b : own()) b->release();
+		for (PinBuf *b : {&h_flag, &h_status, &h_ssize}) b->release();
 		for (int s = 0; s < 2; ++s) {
-			for (PinBuf *b : {&h_comp[s], &h_goff[s], &h_cut[s], &h_out[s], &h_meta[s]}) b->release();
+			in[s].release(); lane[s].release();
 			if (st[s]) (void)hipStreamDestroy(st[s]);
 			if (ev[s]) (void)hipEventDestroy(ev[s]);
 			for (int k = 0; k < 2; ++k) { if (ev_g[s][k]) (void)hipEventDestroy(ev_g[s][k]); ev_g[s][k] = nullptr; }
@@ -221,18 +213,8 @@ bool load_inflate(SortCtx &C, const uint8_t *bam, Loaded &L, std::atomic<uint64_
 	for (size_t g = 0; g < n_groups; ++g) {
 		const int s = (int)(g & 1);
 		const size_t b0 = g * BS_GROUP, b1 = std::min(n_blk, b0 + BS_GROUP);
-		const int nb = (int)(b1 - b0);
-		const size_t cbytes = (size_t)(blk[b1] - blk[b0]), tbytes = (size_t)(txt[b1] - txt[b0]);   // (each at most BS_GROUP_BYTES)
 		if (g >= 2) HIP_OK(hipEventSynchronize(C.ev[s]));   // the group before last on this stream has left the page-locked buffers
-		memcpy(C.h_comp[s].p, bam + blk[b0], cbytes);
-		uint32_t *ho = (uint32_t *)C.h_goff[s].p, *hb = ho, *ht = ho + (BS_GROUP + 1);
-		for (int k = 0; k <= nb; ++k) { hb[k] = (uint32_t)(blk[b0 + k] - blk[b0]); ht[k] = (uint32_t)(txt[b0 + k] - txt[b0]); }
-		uint32_t *dof = (uint32_t *)C.d_goff[s].p;
-		HIP_OK(hipMemcpyAsync(C.d_comp[s].p, C.h_comp[s].p, cbytes, hipMemcpyHostToDevice, C.st[s]));
-		HIP_OK(hipMemcpyAsync(dof, ho, sizeof(uint32_t) * 2 * (BS_GROUP + 1), hipMemcpyHostToDevice, C.st[s]));
-		HIP_OK(hipEventRecord(C.ev[s], C.st[s]));
-		launch_bgzf_inflate(C.st[s], (const uint8_t *)C.d_comp[s].p, (uint32_t)cbytes, dof, dof + (BS_GROUP + 1), nb, d_u + txt[b0], (uint32_t)tbytes,
-		                    (uint32_t *)C.d_status.p + b0);
+		C.in[s].queue(C.st[s], bam, blk.data(), txt.data(), b0, b1, d_u + txt[b0], (uint32_t *)C.d_status.p + b0, C.ev[s]);
 	}
 	HIP_OK(hipStreamSynchronize(C.st[1]));
 	if (n_blk) HIP_OK(hipMemcpyAsync(C.h_status.p, C.d_status.p, n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[0]));
@@ -445,7 +427,7 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, Index
 		const auto ti = std::chrono::steady_clock::now();
 		const std::vector<uint64_t> cut64(cut.begin(), cut.end());
 		C.x_cut.ensure(cut64.size() * sizeof(uint64_t));
-		C.h_sizes[0].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS); C.h_sizes[1].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS);
+		C.lane[0].want_sizes(); C.lane[1].want_sizes();
 		HIP_OK(hipMemcpyAsync(C.x_cut.p, cut64.data(), cut64.size() * sizeof(uint64_t), hipMemcpyHostToDevice, C.st[0]));
 		uint64_t bad_off = 0;
 		const int r = index_build(C, (const uint64_t *)C.d_off.p, (const uint32_t *)C.d_idx2.p, d_dst, hn, (const uint64_t *)C.x_cut.p, cut64, n_rec, h.n_ref, nullptr,
@@ -462,7 +444,6 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, Index
 	auto start = [&](size_t k) {   // everything of a piece, queued on the piece's stream
 		const int s = (int)(k & 1);
 		const size_t b0 = k * BAM_DEV_BLOCKS, b1 = std::min(n_out, b0 + BAM_DEV_BLOCKS);
-		const int nb = (int)(b1 - b0);
 		const uint64_t p0 = cut[b0], p1 = cut[b1];   // (p1 - p0 <= BAM_DEV_BYTES: a block has at most 0xff00 bytes)
 		uint8_t *const d_piece = (uint8_t *)C.d_piece[s].p;
 		if (p0 < hn)   // (pageable memory: the copy is staged by the runtime and has left head when the call returns)
@@ -479,14 +460,8 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, Index
 			HIP_OK(hipEventRecord(C.ev_g[s][1], C.st[s]));
 			piece_gather[s] = hi - lo;
 		}
-		uint32_t *hcut = (uint32_t *)C.h_cut[s].p;
-		for (int j = 0; j <= nb; ++j) hcut[j] = (uint32_t)(cut[b0 + j] - p0);
-		HIP_OK(hipMemcpyAsync(C.d_cut[s].p, hcut, sizeof(uint32_t) * (nb + 1), hipMemcpyHostToDevice, C.st[s]));
-		HIP_OK(hipMemsetAsync(C.d_meta[s].p, 0, 2 * sizeof(unsigned long long), C.st[s]));
-		launch_bgzf_deflate(C.st[s], d_piece, (const uint32_t *)C.d_cut[s].p, nb, (uint8_t *)C.d_slots[s].p, (uint32_t *)C.d_sizes[s].p, (uint16_t *)C.d_tokens[s].p,
-		                    BAM_DEV_BLOCKS, (unsigned long long *)C.d_meta[s].p);
-		launch_bgzf_gather(C.st[s], (const uint8_t *)C.d_slots[s].p, (const uint32_t *)C.d_sizes[s].p, nb, (uint8_t *)C.d_out[s].p, (unsigned long long *)C.d_meta[s].p);
-		HIP_OK(hipMemcpyAsync(C.h_meta[s].p, C.d_meta[s].p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.st[s]));
+		C.lane[s].cuts_up(C.st[s], cut.data() + b0, (int)(b1 - b0));
+		C.lane[s].queue(C.st[s], d_piece, (int)(b1 - b0));
 	};
 	size_t w = 0;
 	if (n_pieces) start(0);
@@ -499,19 +474,18 @@ int64_t sort_dev(const uint8_t *bam, size_t len, uint8_t *out, size_t cap, Index
 			HIP_OK(hipEventElapsedTime(&ms, C.ev_g[s][0], C.ev_g[s][1]));
 			gather_ms += ms; gather_bytes += piece_gather[s];
 		}
-		const size_t zbytes = (size_t)((const unsigned long long *)C.h_meta[s].p)[0];
+		DeflateLane &Z = C.lane[s];
+		const size_t zbytes = Z.packed();
 		if (w + zbytes + 28 > cap) die("mi355x_bam_sort_dev: %zu bytes of blocks above the bound %zu", w + zbytes + 28, (size_t)bam_sort_bound_of(u));
-		HIP_OK(hipMemcpyAsync(C.h_out[s].p, C.d_out[s].p, zbytes, hipMemcpyDeviceToHost, C.st[s]));
 		const size_t nb_k = std::min(n_out, (k + 1) * BAM_DEV_BLOCKS) - k * BAM_DEV_BLOCKS;
-		if (ix) HIP_OK(hipMemcpyAsync(C.h_sizes[s].p, C.d_sizes[s].p, nb_k * sizeof(uint32_t), hipMemcpyDeviceToHost, C.st[s]));
+		Z.fetch(C.st[s], ix ? nb_k : 0);
 		HIP_OK(hipStreamSynchronize(C.st[s]));
 		if (ix) {   // the piece's blocks, one by one
 			size_t at = w;
-			for (size_t j = 0; j < nb_k; ++j) { out_off.push_back((int64_t)at); at += ((const uint32_t *)C.h_sizes[s].p)[j]; }
+			for (size_t j = 0; j < nb_k; ++j) { out_off.push_back((int64_t)at); at += ((const uint32_t *)Z.h_sizes.p)[j]; }
 			if (at != w + zbytes) die("mi355x_bam_sort_index_dev: a piece's blocks have %zu bytes, the piece %zu", at - w, zbytes);
 		}
-		memcpy(out + w, C.h_out[s].p, zbytes);
-		w += zbytes;
+		w += Z.store(out + w);
 	}
 	if (ix) out_off.push_back((int64_t)w);
 	w += mi355x_bgzf_eof(out + w);

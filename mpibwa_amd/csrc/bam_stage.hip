@@ -2,36 +2,32 @@
 // (bam_kernel.hip) and on to BGZF blocks by the deflate kernel (bgzf_kernel.hip), with the records and the cuts of mi355x_bam_compress
 // (sampost.cpp).  DESIGN §8.4.
 //
-// The stage is bgzf_stage.hip's with the encoder in front: a call leases a context from a small pool and takes the text through it in
-// pieces of whole lines, at most BAM_DEV_TEXT bytes, two pieces in flight, each on a stream of its own.  Per piece: the text up, the
-// line starts, the size pass, the scan, the write pass, the cuts, bgzf_deflate_kernel, bgzf_gather_kernel — all queued at once; what
-// comes back is d_meta's two words and the piece's BamDevCtl, then only the compressed bytes.  A piece whose ctl says that it is not the
-// device's (a declined line, more lines / bytes / blocks than the buffers hold) is encoded by the host encoder, and its records and cuts
-// go up in the encoder's place: the deflate is the device's either way, so the bytes of a call do not depend on who encoded.  A malformed
-// line ends the call with the host encoder's code.  A context's buffers have one size whatever the text.
+// The stage is bgzf_stage.hip's with the encoder in front: a call leases a context from a small pool (ctx_pool.h) and takes the text
+// through it in pieces of whole lines, at most BAM_DEV_TEXT bytes, two pieces in flight, each on a stream and a deflate lane (bgzf_lane.h)
+// of its own.  Per piece: the text up, the line starts, the size pass, the scan, the write pass, the cuts, bgzf_deflate_kernel,
+// bgzf_gather_kernel — all queued at once; what comes back is d_meta's two words and the piece's BamDevCtl, then only the compressed
+// bytes.  A piece whose ctl says that it is not the device's (a declined line, more lines / bytes / blocks than the buffers hold) is
+// encoded by the host encoder, and its records and cuts go up in the encoder's place: the deflate is the device's either way, so the bytes
+// of a call do not depend on who encoded.  A malformed line ends the call with the host encoder's code.  A context's buffers have one size
+// whatever the text.
 #include <atomic>
-#include <condition_variable>
-#include <cstring>
-#include <mutex>
 #include <vector>
-#include "hip_util.h"
-#include "device.h"
+#include "bgzf_lane.h"
+#include "ctx_pool.h"
 #include "bam_util.h"
 
 namespace mbw {
 namespace {
 
 constexpr int BM_CTX = 8;
-constexpr size_t BM_SLOT_BYTES = 0x10000, BM_SLACK = 16;
 constexpr size_t BM_CONTIG_BYTES = 4u << 20;   // the contig table; a larger one sends the call's pieces to the host encoder
 
 struct BamCtx {
-	bool busy = false, ready = false;
 	hipStream_t st[2] = {nullptr, nullptr};
 	hipEvent_t ev[2] = {nullptr, nullptr};
-	DevBuf d_text[2], d_chunk[2], d_start[2], d_plan[2], d_group[2], d_off[2], d_next[2], d_bam[2], d_cut[2], d_ctl[2], d_contigs;
-	DevBuf d_slots[2], d_sizes[2], d_out[2], d_meta[2], d_tokens[2];
-	PinBuf h_text[2], h_cut[2], h_out[2], h_meta[2], h_ctl[2], h_ctl0;
+	DeflateLane lane[2];   // (the cuts kernel writes the lane's d_cut)
+	DevBuf d_text[2], d_chunk[2], d_start[2], d_plan[2], d_group[2], d_off[2], d_next[2], d_bam[2], d_ctl[2], d_contigs;
+	PinBuf h_text[2], h_ctl[2], h_ctl0;
 	void init()
 	{
 		d_contigs.ensure(BM_CONTIG_BYTES);
@@ -41,84 +37,46 @@ struct BamCtx {
 		for (int s = 0; s < 2; ++s) {
 			HIP_OK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
 			HIP_OK(hipEventCreateWithFlags(&ev[s], hipEventDisableTiming));
-			d_text[s].ensure(BAM_DEV_TEXT + BM_SLACK);
+			lane[s].init();
+			d_text[s].ensure(BAM_DEV_TEXT + LANE_SLACK);
 			d_chunk[s].ensure(sizeof(uint32_t) * (BAM_DEV_TEXT / BAM_DEV_CHUNK + 2));
 			d_start[s].ensure(sizeof(uint32_t) * (BAM_DEV_LINES + 1));
 			d_plan[s].ensure(bam_plan_bytes() * BAM_DEV_LINES);
 			d_group[s].ensure(sizeof(uint32_t) * (BAM_DEV_LINES / 64 + 1));
 			d_off[s].ensure(sizeof(uint32_t) * (BAM_DEV_LINES + 1));
 			d_next[s].ensure(sizeof(uint32_t) * BAM_DEV_LINES);
-			d_bam[s].ensure(BAM_DEV_BYTES + BM_SLACK);
-			d_cut[s].ensure(sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1));
+			d_bam[s].ensure(BAM_DEV_BYTES + LANE_SLACK);
 			d_ctl[s].ensure(sizeof(BamDevCtl));
-			d_slots[s].ensure(BAM_DEV_BLOCKS * BM_SLOT_BYTES);
-			d_sizes[s].ensure(sizeof(uint32_t) * BAM_DEV_BLOCKS);
-			d_out[s].ensure(BAM_DEV_BLOCKS * BM_SLOT_BYTES);
-			d_meta[s].ensure(2 * sizeof(unsigned long long));
-			d_tokens[s].ensure(sizeof(uint16_t) * (size_t)BAM_DEV_BYTES);
-			h_text[s].ensure(BAM_DEV_BYTES + BM_SLACK);   // a piece's text, or the records the host made of it
-			h_cut[s].ensure(sizeof(uint32_t) * (BAM_DEV_BLOCKS + 1));
-			h_out[s].ensure(BAM_DEV_BLOCKS * BM_SLOT_BYTES);
-			h_meta[s].ensure(2 * sizeof(unsigned long long));
+			h_text[s].ensure(BAM_DEV_BYTES + LANE_SLACK);   // a piece's text, or the records the host made of it
 			h_ctl[s].ensure(sizeof(BamDevCtl));
 		}
-		ready = true;
 	}
 	void release()
 	{
 		d_contigs.release(); h_ctl0.release();
 		for (int s = 0; s < 2; ++s) {
-			for (DevBuf *b : {&d_text[s], &d_chunk[s], &d_start[s], &d_plan[s], &d_group[s], &d_off[s], &d_next[s], &d_bam[s], &d_cut[s], &d_ctl[s],
-			                  &d_slots[s], &d_sizes[s], &d_out[s], &d_meta[s], &d_tokens[s]}) b->release();
-			for (PinBuf *b : {&h_text[s], &h_cut[s], &h_out[s], &h_meta[s], &h_ctl[s]}) b->release();
+			lane[s].release();
+			for (DevBuf *b : {&d_text[s], &d_chunk[s], &d_start[s], &d_plan[s], &d_group[s], &d_off[s], &d_next[s], &d_bam[s], &d_ctl[s]}) b->release();
+			h_text[s].release(); h_ctl[s].release();
 			if (st[s]) (void)hipStreamDestroy(st[s]);
 			if (ev[s]) (void)hipEventDestroy(ev[s]);
 			st[s] = nullptr; ev[s] = nullptr;
 		}
-		ready = false;
 	}
+	void drain() { for (hipStream_t s : st) (void)hipStreamSynchronize(s); }   // (a call that ends early leaves nothing queued on the context)
 	BamDevBufs bufs(int s, uint32_t text_len) const
 	{
 		BamDevBufs B;
 		B.text = (const uint8_t *)d_text[s].p; B.text_len = text_len; B.contigs = d_contigs.p;
 		B.chunk_cnt = (uint32_t *)d_chunk[s].p; B.line_start = (uint32_t *)d_start[s].p; B.plan = d_plan[s].p; B.group = (uint32_t *)d_group[s].p;
-		B.rec_off = (uint32_t *)d_off[s].p; B.next = (uint32_t *)d_next[s].p; B.bam = (uint8_t *)d_bam[s].p; B.cut = (uint32_t *)d_cut[s].p;
+		B.rec_off = (uint32_t *)d_off[s].p; B.next = (uint32_t *)d_next[s].p; B.bam = (uint8_t *)d_bam[s].p; B.cut = (uint32_t *)lane[s].d_cut.p;
 		B.ctl = (BamDevCtl *)d_ctl[s].p;
 		return B;
 	}
 };
 
-BamCtx g_bm[BM_CTX];
-std::mutex g_bm_mu;
-std::condition_variable g_bm_cv;
+CtxPool<BamCtx, BM_CTX> g_bm;
 std::atomic<uint64_t> g_bm_counts[6];   // records, records of pieces the host encoded, SAM bytes, BAM bytes, blocks, compressed bytes
-
-struct BamLease {
-	BamCtx *c = nullptr;
-	BamLease()
-	{
-		std::unique_lock<std::mutex> lk(g_bm_mu);
-		for (;;) {
-			for (int pass = 0; pass < 2 && !c; ++pass)   // one that has its buffers first
-				for (int i = 0; i < BM_CTX && !c; ++i)
-					if (!g_bm[i].busy && (pass == 1 || g_bm[i].ready)) c = &g_bm[i];
-			if (c) break;
-			g_bm_cv.wait(lk);
-		}
-		c->busy = true;
-		lk.unlock();
-		if (!c->ready) c->init();
-	}
-	~BamLease()
-	{
-		for (int s = 0; s < 2; ++s) (void)hipStreamSynchronize(c->st[s]);   // (a call that ends early leaves nothing queued on the context)
-		{
-			std::lock_guard<std::mutex> lk(g_bm_mu);
-			c->busy = false;
-		}
-		g_bm_cv.notify_one();
-	}
-};
 
 // the text in pieces of whole lines: piece[k] .. piece[k + 1]; a line longer than a piece stands alone (it is the host's)
 void bam_pieces(const char *sam, size_t body, std::vector<size_t> &piece)
@@ -149,23 +107,14 @@ int64_t bam_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, 
 	bam_pieces(sam, body, piece);
 	const size_t n_pieces = piece.size() - 1;
 	use_device();
-	BamLease lease;
-	BamCtx &C = *lease.c;
+	CtxPool<BamCtx, BM_CTX>::Lease lease(g_bm);
+	BamCtx &C = *lease;
 	const bool table_fits = blob.size() <= BM_CONTIG_BYTES;
 	if (table_fits) {
 		// (pageable memory: the copy is staged by the runtime and has left blob when the call returns)
 		HIP_OK(hipMemcpyAsync(C.d_contigs.p, blob.data(), blob.size(), hipMemcpyHostToDevice, C.st[0]));
 		HIP_OK(hipStreamSynchronize(C.st[0]));
 	}
-	auto queue_deflate = [&](int s, bool device_cuts) {
-		HIP_OK(hipMemsetAsync(C.d_meta[s].p, 0, 2 * sizeof(unsigned long long), C.st[s]));
-		const uint32_t *nb = device_cuts ? &((const BamDevCtl *)C.d_ctl[s].p)->n_blocks : nullptr;
-		launch_bgzf_deflate(C.st[s], (const uint8_t *)C.d_bam[s].p, (const uint32_t *)C.d_cut[s].p, BAM_DEV_BLOCKS, (uint8_t *)C.d_slots[s].p, (uint32_t *)C.d_sizes[s].p,
-		                    (uint16_t *)C.d_tokens[s].p, BAM_DEV_BLOCKS, (unsigned long long *)C.d_meta[s].p, nb);
-		launch_bgzf_gather(C.st[s], (const uint8_t *)C.d_slots[s].p, (const uint32_t *)C.d_sizes[s].p, BAM_DEV_BLOCKS, (uint8_t *)C.d_out[s].p,
-		                   (unsigned long long *)C.d_meta[s].p, nb);
-		HIP_OK(hipMemcpyAsync(C.h_meta[s].p, C.d_meta[s].p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.st[s]));
-	};
 	auto start = [&](size_t k) {   // everything of a piece, queued on the piece's stream
 		const int s = (int)(k & 1);
 		const size_t bytes = piece[k + 1] - piece[k];
@@ -183,7 +132,7 @@ int64_t bam_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, 
 		launch_bam_encode(C.st[s], B);
 		if (compress) {
 			launch_bam_cuts(C.st[s], B);
-			queue_deflate(s, true);
+			C.lane[s].queue(C.st[s], B.bam, LANE_BLOCKS, &B.ctl->n_blocks);   // (the cuts and their number stay on the device)
 		}
 		HIP_OK(hipMemcpyAsync(hc, C.d_ctl[s].p, sizeof(BamDevCtl), hipMemcpyDeviceToHost, C.st[s]));
 		HIP_OK(hipEventRecord(C.ev[s], C.st[s]));
@@ -196,6 +145,7 @@ int64_t bam_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, 
 	start(0);
 	for (size_t k = 0; k < n_pieces; ++k) {
 		const int s = (int)(k & 1);
+		DeflateLane &L = C.lane[s];
 		HIP_OK(hipEventSynchronize(C.ev[s]));
 		const BamDevCtl ctl = *(const BamDevCtl *)C.h_ctl[s].p;
 		const bool mine = ctl.err == 0xffffffffu && !ctl.decline;
@@ -215,44 +165,32 @@ int64_t bam_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, 
 				// through the deflate kernel in runs of at most BAM_DEV_BLOCKS blocks
 				for (size_t b0 = 0; b0 + 1 < cut.size(); b0 += BAM_DEV_BLOCKS) {
 					const size_t b1 = std::min(cut.size() - 1, b0 + BAM_DEV_BLOCKS), bytes = cut[b1] - cut[b0];
-					const int nb = (int)(b1 - b0);
 					memcpy(C.h_text[s].p, recs.data() + cut[b0], bytes);
-					uint32_t *hcut = (uint32_t *)C.h_cut[s].p;
-					for (int j = 0; j <= nb; ++j) hcut[j] = (uint32_t)(cut[b0 + j] - cut[b0]);
 					HIP_OK(hipMemcpyAsync(C.d_bam[s].p, C.h_text[s].p, bytes, hipMemcpyHostToDevice, C.st[s]));
-					HIP_OK(hipMemcpyAsync(C.d_cut[s].p, hcut, sizeof(uint32_t) * (nb + 1), hipMemcpyHostToDevice, C.st[s]));
-					HIP_OK(hipMemsetAsync(C.d_meta[s].p, 0, 2 * sizeof(unsigned long long), C.st[s]));
-					launch_bgzf_deflate(C.st[s], (const uint8_t *)C.d_bam[s].p, (const uint32_t *)C.d_cut[s].p, nb, (uint8_t *)C.d_slots[s].p,
-					                    (uint32_t *)C.d_sizes[s].p, (uint16_t *)C.d_tokens[s].p, BAM_DEV_BLOCKS, (unsigned long long *)C.d_meta[s].p);
-					launch_bgzf_gather(C.st[s], (const uint8_t *)C.d_slots[s].p, (const uint32_t *)C.d_sizes[s].p, nb, (uint8_t *)C.d_out[s].p,
-					                   (unsigned long long *)C.d_meta[s].p);
-					HIP_OK(hipMemcpyAsync(C.h_meta[s].p, C.d_meta[s].p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.st[s]));
+					L.cuts_up(C.st[s], cut.data() + b0, (int)(b1 - b0));
+					L.queue(C.st[s], (const uint8_t *)C.d_bam[s].p, (int)(b1 - b0));
 					HIP_OK(hipStreamSynchronize(C.st[s]));
-					const size_t zbytes = (size_t)((const unsigned long long *)C.h_meta[s].p)[0];
-					if (w + zbytes > cap) return 0;
-					HIP_OK(hipMemcpyAsync(C.h_out[s].p, C.d_out[s].p, zbytes, hipMemcpyDeviceToHost, C.st[s]));
+					if (w + L.packed() > cap) return 0;
+					L.fetch(C.st[s]);
 					HIP_OK(hipStreamSynchronize(C.st[s]));
-					memcpy(out + w, C.h_out[s].p, zbytes);
-					w += zbytes; n_blocks += (uint64_t)nb;
+					w += L.store(out + w); n_blocks += b1 - b0;
 				}
 			}
 			if (k + 1 < n_pieces) start(k + 1);
 			continue;
 		}
 		n_rec += ctl.n_lines; bam_bytes += ctl.bam_bytes;
-		if (!compress) {
+		if (!compress) {   // the records, through the lane's page-locked bytes
 			if (w + ctl.bam_bytes > cap) return 0;
-			HIP_OK(hipMemcpyAsync(C.h_out[s].p, C.d_bam[s].p, ctl.bam_bytes, hipMemcpyDeviceToHost, C.st[s]));
+			HIP_OK(hipMemcpyAsync(L.h_out.p, C.d_bam[s].p, ctl.bam_bytes, hipMemcpyDeviceToHost, C.st[s]));
 			HIP_OK(hipStreamSynchronize(C.st[s]));
-			memcpy(out + w, C.h_out[s].p, ctl.bam_bytes);
+			memcpy(out + w, L.h_out.p, ctl.bam_bytes);
 			w += ctl.bam_bytes;
 		} else {
-			const size_t zbytes = (size_t)((const unsigned long long *)C.h_meta[s].p)[0];
-			if (w + zbytes > cap) return 0;
-			HIP_OK(hipMemcpyAsync(C.h_out[s].p, C.d_out[s].p, zbytes, hipMemcpyDeviceToHost, C.st[s]));
+			if (w + L.packed() > cap) return 0;
+			L.fetch(C.st[s]);
 			HIP_OK(hipStreamSynchronize(C.st[s]));
-			memcpy(out + w, C.h_out[s].p, zbytes);
-			w += zbytes; n_blocks += ctl.n_blocks;
+			w += L.store(out + w); n_blocks += ctl.n_blocks;
 		}
 	}
 	if (body < len) return -(int64_t)body - 1;   // a last line without '\n', and no malformed line before it
@@ -264,20 +202,7 @@ int64_t bam_dev(const char *sam, size_t len, const bntseq_t *bns, uint8_t *out, 
 
 } // namespace
 
-void release_bam_contexts()
-{
-	std::unique_lock<std::mutex> lk(g_bm_mu);
-	for (int i = 0; i < BM_CTX; ++i) {
-		BamCtx &x = g_bm[i];
-		if (x.busy || !x.ready) continue;
-		x.busy = true;   // nobody leases it while its buffers go
-		lk.unlock();
-		x.release();
-		lk.lock();
-		x.busy = false;
-	}
-	g_bm_cv.notify_all();
-}
+void release_bam_contexts() { g_bm.release_idle(); }
 
 } // namespace mbw
 

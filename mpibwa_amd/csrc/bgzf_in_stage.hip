@@ -1,107 +1,55 @@
 // bgzf_in_stage.hip — mi355x_bgzf_inflate_dev: BGZF blocks to their text through the device decoder (bgzf_inflate_kernel.hip), with the
 // contract and the results of mi355x_bgzf_inflate (sampost.cpp), which block is reported for malformed input included.  DESIGN §8.3.
 //
-// The stage is bgzf_stage.hip's the other way round: a call leases a context from a small pool and takes the blocks through it in
-// pieces of at most BI_PIECE blocks, two pieces in flight, each on a stream of its own.  Per piece: the compressed bytes and the two
+// A call leases a context from a small pool (ctx_pool.h) and takes the blocks through it in pieces of at most BI_PIECE blocks, two pieces
+// in flight, each on a stream of its own with an inflate lane of its own (bgzf_lane.h).  Per piece: the compressed bytes and the two
 // offset tables up, bgzf_inflate_kernel (a block per wavefront), the text and the status words back.  Two things are simpler than on the
 // way out: the text offsets are known from the trailers before the launch, so every block writes to its final place (no gather kernel),
 // and only compressed bytes go up.  The caller's buffers are pageable, so both ends of every copy are the context's page-locked buffers.
 // A context's buffers have one size whatever the input: after its first call a context never allocates again.
 #include <atomic>
-#include <condition_variable>
-#include <cstring>
-#include <mutex>
 #include <vector>
-#include "hip_util.h"
-#include "device.h"
+#include "bgzf_lane.h"
+#include "ctx_pool.h"
 #include "inflate_util.h"
 
 namespace mbw {
 namespace {
 
 constexpr int BI_CTX = 8;                 // calls side by side; more callers wait their turn
-constexpr int BI_PIECE = 512;             // blocks per piece = workgroups per launch
-constexpr size_t BI_BYTES = (size_t)BI_PIECE * 0x10000;   // a piece's blocks, and a piece's text, at their largest
+constexpr int BI_PIECE = LANE_BLOCKS;     // blocks per piece
 
 struct BgzfInCtx {
-	bool busy = false, ready = false;
 	hipStream_t st[2] = {nullptr, nullptr};
-	DevBuf d_comp[2], d_text[2], d_off[2], d_status[2];
-	PinBuf h_comp[2], h_text[2], h_off[2], h_status[2];
+	InflateLane lane[2];
+	DevBuf d_text[2], d_status[2];
+	PinBuf h_text[2], h_status[2];
 	void init()
 	{
 		for (int s = 0; s < 2; ++s) {
 			HIP_OK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
-			d_comp[s].ensure(BI_BYTES);
-			d_text[s].ensure(BI_BYTES);
-			d_off[s].ensure(sizeof(uint32_t) * 2 * (BI_PIECE + 1));
-			d_status[s].ensure(sizeof(uint32_t) * BI_PIECE);
-			h_comp[s].ensure(BI_BYTES);
-			h_text[s].ensure(BI_BYTES);
-			h_off[s].ensure(sizeof(uint32_t) * 2 * (BI_PIECE + 1));
-			h_status[s].ensure(sizeof(uint32_t) * BI_PIECE);
+			lane[s].init();
+			d_text[s].ensure(LANE_BYTES); h_text[s].ensure(LANE_BYTES);   // a piece's text at its largest
+			d_status[s].ensure(sizeof(uint32_t) * BI_PIECE); h_status[s].ensure(sizeof(uint32_t) * BI_PIECE);
 		}
-		ready = true;
 	}
 	void release()
 	{
 		for (int s = 0; s < 2; ++s) {
-			for (DevBuf *b : {&d_comp[s], &d_text[s], &d_off[s], &d_status[s]}) b->release();
-			for (PinBuf *b : {&h_comp[s], &h_text[s], &h_off[s], &h_status[s]}) b->release();
+			lane[s].release(); d_text[s].release(); d_status[s].release(); h_text[s].release(); h_status[s].release();
 			if (st[s]) (void)hipStreamDestroy(st[s]);
 			st[s] = nullptr;
 		}
-		ready = false;
 	}
+	void drain() { for (hipStream_t s : st) (void)hipStreamSynchronize(s); }
 };
 
-BgzfInCtx g_bi[BI_CTX];
-std::mutex g_bi_mu;
-std::condition_variable g_bi_cv;
+CtxPool<BgzfInCtx, BI_CTX> g_bi;
 std::atomic<uint64_t> g_bi_counts[4];   // blocks, blocks that failed, compressed bytes, text bytes
-
-struct BgzfInLease {
-	BgzfInCtx *c = nullptr;
-	BgzfInLease()
-	{
-		std::unique_lock<std::mutex> lk(g_bi_mu);
-		for (;;) {
-			for (int pass = 0; pass < 2 && !c; ++pass)   // one that has its buffers first
-				for (int i = 0; i < BI_CTX && !c; ++i)
-					if (!g_bi[i].busy && (pass == 1 || g_bi[i].ready)) c = &g_bi[i];
-			if (c) break;
-			g_bi_cv.wait(lk);
-		}
-		c->busy = true;
-		lk.unlock();
-		if (!c->ready) c->init();
-	}
-	~BgzfInLease()
-	{
-		{
-			std::lock_guard<std::mutex> lk(g_bi_mu);
-			c->busy = false;
-		}
-		g_bi_cv.notify_one();
-	}
-};
 
 } // namespace
 
-void release_bgzf_in_contexts()
-{
-	std::unique_lock<std::mutex> lk(g_bi_mu);
-	for (int i = 0; i < BI_CTX; ++i) {
-		BgzfInCtx &x = g_bi[i];
-		if (x.busy || !x.ready) continue;
-		x.busy = true;   // nobody leases it while its buffers go
-		lk.unlock();
-		x.release();
-		lk.lock();
-		x.busy = false;
-	}
-	g_bi_cv.notify_all();
-}
+void release_bgzf_in_contexts() { g_bi.release_idle(); }
 
 } // namespace mbw
 
@@ -120,23 +68,14 @@ extern "C" int64_t mi355x_bgzf_inflate_dev(const uint8_t *in, size_t len, char *
 	uint64_t n_failed = 0;
 	if (n_blocks) {
 		use_device();
-		BgzfInLease lease;
-		BgzfInCtx &C = *lease.c;
+		CtxPool<BgzfInCtx, BI_CTX>::Lease lease(g_bi);
+		BgzfInCtx &C = *lease;
 		const size_t n_pieces = (n_blocks + BI_PIECE - 1) / BI_PIECE;
-		auto start = [&](size_t piece) {   // everything of a piece, queued on the piece's stream
+		auto start = [&](size_t piece) {   // everything of a piece, queued on the piece's stream (which has done with the piece before last)
 			const int s = (int)(piece & 1);
-			const size_t b0 = piece * BI_PIECE, b1 = std::min(n_blocks, b0 + BI_PIECE);
-			const int nb = (int)(b1 - b0);
-			const size_t cbytes = (size_t)(blk[b1] - blk[b0]), tbytes = (size_t)(txt[b1] - txt[b0]);   // (each at most BI_BYTES: a block and its text are at most 64 KiB)
-			memcpy(C.h_comp[s].p, in + blk[b0], cbytes);
-			uint32_t *ho = (uint32_t *)C.h_off[s].p, *hb = ho, *ht = ho + (BI_PIECE + 1);
-			for (int k = 0; k <= nb; ++k) { hb[k] = (uint32_t)(blk[b0 + k] - blk[b0]); ht[k] = (uint32_t)(txt[b0 + k] - txt[b0]); }
-			uint32_t *dof = (uint32_t *)C.d_off[s].p;
-			HIP_OK(hipMemcpyAsync(C.d_comp[s].p, C.h_comp[s].p, cbytes, hipMemcpyHostToDevice, C.st[s]));
-			HIP_OK(hipMemcpyAsync(dof, ho, sizeof(uint32_t) * 2 * (BI_PIECE + 1), hipMemcpyHostToDevice, C.st[s]));
-			launch_bgzf_inflate(C.st[s], (const uint8_t *)C.d_comp[s].p, (uint32_t)cbytes, dof, dof + (BI_PIECE + 1), nb, (uint8_t *)C.d_text[s].p, (uint32_t)tbytes,
-			                    (uint32_t *)C.d_status[s].p);
-			HIP_OK(hipMemcpyAsync(C.h_status[s].p, C.d_status[s].p, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, C.st[s]));
+			const size_t b0 = piece * BI_PIECE, b1 = std::min(n_blocks, b0 + BI_PIECE), tbytes = (size_t)(txt[b1] - txt[b0]);
+			C.lane[s].queue(C.st[s], in, blk.data(), txt.data(), b0, b1, (uint8_t *)C.d_text[s].p, (uint32_t *)C.d_status[s].p);
+			HIP_OK(hipMemcpyAsync(C.h_status[s].p, C.d_status[s].p, sizeof(uint32_t) * (b1 - b0), hipMemcpyDeviceToHost, C.st[s]));
 			if (tbytes) HIP_OK(hipMemcpyAsync(C.h_text[s].p, C.d_text[s].p, tbytes, hipMemcpyDeviceToHost, C.st[s]));
 		};
 		start(0);
